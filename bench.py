@@ -1,19 +1,25 @@
 #!/usr/bin/env python
 """Benchmark of the S2VT hot path on MI355X (BASELINE.json metric: training frames/s + greedy captions/s).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B_per_gpu] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 A "step" is one full optimisation step of train.py:116-127 (zero_grad, forward, MaskCriterion, backward,
 gradient all-reduce when N > 1, Adam) on synthetic [B, 80, 4096] fp32 features with seeded random-init
 weights; the default workload is BASELINE configs[1] (B=64 per GPU, H=E=1000, V=12000, fp32).  Scaling is
 weak: every rank keeps B per GPU.  Rank 0 prints ONE JSON line.  Inputs are resident in HBM before the timed
-region.  Beside the GPU number the line carries
+region.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given
+(dump_outputs below) and prints the headline line: nothing else runs.  With --full the line also carries
+everything measured beside the headline, each in extra steps after the timed region, among them
   * "roofline": the dominant kernel family of the step, timed live with HIP events on the launch stream
     (s2vt_prof_*), priced with the algorithmic flops/bytes of SURVEY.md §8(d);
   * "roofline_lstm_step": the fused LSTM timestep (north_star's target kernel) against the HBM roofline;
   * "cpu_baseline": the reference-shaped CPU model (oracle/, nn.LSTM/nn.Linear -> oneDNN, what the
-    reference's CPU run executes) timed on this host's cores on a bounded sample (rank 0, N=1 only).
+    reference's CPU run executes) timed on this host's cores on a bounded sample (rank 0, N=1 only);
+  * host enqueue cost, the per-rank step times and collective timing (N > 1), the B=128 shard, the fixed global
+    batch, greedy decode, beam search, config3 (B=256 bf16) and the reference's default sizes.
 """
 import argparse
 import json
@@ -103,6 +109,37 @@ def free_port():
         return sk.getsockname()[1]
 
 
+DUMP_SAMPLE = 1 << 19           # elements kept of a larger tensor by --dump-outputs
+DUMP_BUDGET = 64 << 20          # bytes written by --dump-outputs, at most
+
+
+def dump_outputs(out_dir, loss, model):
+    """--dump-outputs DIR: what the timed path handed its caller in its last step, as DIR/<name>.npy - `loss` (float64, the
+    value dp.train_step returned) and, for every parameter, `param.<name>` and `grad.<name>` (float32): the weights that step left
+    in the model and the gradients its backward wrote.  A tensor of more than DUMP_SAMPLE elements is written as a fixed sample
+    of them, the same in every run and build (distinct indices drawn by numpy's default_rng(0), ascending, into the flattened
+    tensor).  The inputs are seeded (synth), so two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64)}
+    for name, p in model.named_parameters():
+        idx = None
+        if p.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(p.numel(), DUMP_SAMPLE, replace=False, shuffle=False))
+            idx = torch.from_numpy(idx).to(p.device)
+        for kind, t in (("param", p), ("grad", p.grad)):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            arrays["%s.%s" % (kind, name)] = (flat if idx is None else flat[idx]).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BUDGET:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET))
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": len(arrays), "bytes": total}
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: this process has not touched the GPU; it starts the N ranks as
     CHILD processes through torch.distributed.run (one per GPU, rendezvous on 127.0.0.1) and relays rank 0's JSON line
@@ -158,15 +195,24 @@ def main():
                     help="0 fp32-input MFMA, 3 split-precision bf16x3 (default, fp32-equivalent), 1 bf16 operands "
                          "(BASELINE configs[2]: use with --batch 256)")
     ap.add_argument("--no-config3", action="store_true", help="skip the B=256 bf16 sub-record (BASELINE configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline (rooflines, host enqueue cost, collective "
+                         "timing, sub-workloads, decode, beam, CPU baselines); a plain run prints the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, parameters and gradients of the last timed step as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed steps and the live kernel timing of the headline workload (no B=128 shard, isolated "
-                         "pass, decode, beam, config3, CPU baseline): what tools/profile_round2.sh runs under rocprofv3, so "
-                         "that the kernel-stats averages are those of the headline workload alone")
+                    help="implies --full, narrowed to the timed steps and the live kernel timing of the headline workload (no B=128 "
+                         "shard, isolated pass, decode, beam, config3, CPU baseline): what tools/profile_round5.sh runs under "
+                         "rocprofv3, so that the kernel-stats averages are those of the headline workload alone")
     ap.add_argument("--graphs", type=int, default=None, choices=[0, 1],
                     help="s2vt_set_graph_mode: replay the forward / backward launch sequences as hipGraphs (default: the library's, off)")
     ap.add_argument("--selftest-launcher", action="store_true",
                     help="CPU-only rehearsal of the N-rank launch path (gloo); prints n_gpus")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.headline_only:
+        args.full = True
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher around us: start the N ranks ourselves (before anything touches the GPU) and exit with their code
@@ -252,6 +298,36 @@ def main():
     frames_per_s = world * B * L * args.steps / dt
     capi.check_async_error()      # a device-side error inside the timed steps (bad token, timed-out hand-off) voids the number
     final_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        log("outputs of the last timed step: %s" % dump_outputs(args.dump_outputs, loss, model))
+    x3 = (mode == 3) and (B % 64 == 0)
+    bf = (mode == 1) and (B % 64 == 0)
+    head = {
+        "metric": "training frames/sec (whole node)", "value": round(frames_per_s, 1), "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf else "f32",
+        "data": "synthetic",
+        "arithmetic": ("fp32 storage and accumulation; batched GEMM products as 3 bf16 planes x 6 plane products on the bf16 "
+                       "matrix cores (fp32-equivalent, ~2^-23 relative) - the batched GEMMs and every persistent recurrence kernel "
+                       "of s2vt_recurrence_plan (kind 3); launch-per-timestep recurrences (kind 0) on the exact fp32-input MFMA"
+                       if x3 else ("bf16 operands (weights, activations) on the bf16 matrix cores for batched and recurrent "
+                                   "GEMMs; fp32 accumulation, cell state, gate stash, gradients, master weights and Adam"
+                                   if bf else "fp32 storage, fp32-input MFMA, fp32 accumulation")),
+        "config": {"workload": ("BASELINE configs[2]: S2VT train step, B=%d per GPU x %d GPU, 80x4096 feats, hidden=embed=1000, "
+                                "vocab=12000, bf16 operands / fp32 accumulate, Adam" % (B, world)) if bf else
+                               ("BASELINE configs[1]: S2VT train step, B=%d per GPU x %d GPU, 80x4096 feats, "
+                                "hidden=embed=1000, vocab=12000, fp32, Adam" % (B, world)),
+                   "global_batch": B * world, "frames": L, "parallelism": "dp%d" % world},
+        "final_loss": round(final_loss, 6),
+    }
+    if not args.full:
+        log("timed region: %.3f ms/step, %.0f frames/s" % (ms_per_step, frames_per_s))
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if use_pg:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # per-rank step time (which rank is the straggler?) and the gradient all-reduce under the microscope: three extra steps with
     # events around every gradient group's collective on the communication stream (dp.FlatGradAllReducer.read_timing) - how long
     # each group took, when it started relative to the end of the backward, how much of it the step had to wait for
@@ -383,8 +459,6 @@ def main():
             return {k: (ms / nprof, n // nprof, busy / nprof) for k, (ms, n, busy) in r.items()}
 
         T = 2 * L - 1
-        x3 = (mode == 3) and (B % 64 == 0)
-        bf = (mode == 1) and (B % 64 == 0)
         esz = 2 if bf else 4
         gflop = gemm_flops_train(B, L, F, H, E, V) / 1e9
         pair_bytes = step_bytes_fwd(B, H, H, s=esz) + step_bytes_fwd(B, H, E + H, s=esz)
@@ -839,22 +913,7 @@ def main():
                                 "written and read, parameters read, gradients written, Adam's 28 B per parameter; algorithmic_bytes_8d_recurrence: "
                                 "SURVEY 8(d)'s streaming model of the 318 layer timesteps, which the persistent kernels do not move (W_hh stays in registers)"}
         out = {
-            "metric": "training frames/sec (whole node)", "value": round(frames_per_s, 1), "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "bf16" if bf else "f32",
-            "data": "synthetic",
-            "arithmetic": ("fp32 storage and accumulation; batched GEMM products as 3 bf16 planes x 6 plane products on the bf16 "
-                           "matrix cores (fp32-equivalent, ~2^-23 relative) - the batched GEMMs and every persistent recurrence kernel "
-                           "of s2vt_recurrence_plan (kind 3); launch-per-timestep recurrences (kind 0) on the exact fp32-input MFMA"
-                           if x3 else ("bf16 operands (weights, activations) on the bf16 matrix cores for batched and recurrent "
-                                       "GEMMs; fp32 accumulation, cell state, gate stash, gradients, master weights and Adam"
-                                       if bf else "fp32 storage, fp32-input MFMA, fp32 accumulation")),
-            "config": {"workload": ("BASELINE configs[2]: S2VT train step, B=%d per GPU x %d GPU, 80x4096 feats, hidden=embed=1000, "
-                                    "vocab=12000, bf16 operands / fp32 accumulate, Adam" % (B, world)) if bf else
-                                   ("BASELINE configs[1]: S2VT train step, B=%d per GPU x %d GPU, 80x4096 feats, "
-                                    "hidden=embed=1000, vocab=12000, fp32, Adam" % (B, world)),
-                       "global_batch": B * world, "frames": L, "parallelism": "dp%d" % world},
-            "final_loss": round(final_loss, 6), "host_enqueue_ms_per_step": round(host_ms, 3),
+            **head, "host_enqueue_ms_per_step": round(host_ms, 3),
             "host_enqueue_ms_by_phase": host_phases, "graph_mode": int(lib.s2vt_set_graph_mode(-1)),
             "pipeline_streams_overlap": int(lib.s2vt_pipeline_overlaps()),
             "roofline": roofline,

@@ -422,6 +422,24 @@ def gen_c5raw(seed, name="c5raw"):
     print(f"[{name}] wrote {name}.npz")
 
 
+def gen_tiny_seed17(name="tiny_seed17", seed=17, B=4):
+    """tests/test_oracle_golden.py::test_oracle_against_live_reference: the reference's train forward (logits) and greedy ids
+    on the tiny dims at seed 17, B = 4 - checked against the oracle here as the test checks them."""
+    S2VT, _ = _reference()
+    d = synth.CONFIGS["tiny"]
+    sd = synth.make_state_dict(d["V"], d["F"], d["H"], d["E"], seed=seed)
+    feats, caps, _ = synth.make_batch(B, d["L"], d["F"], d["V"], seed=seed)
+    m = _ref_model(S2VT, d, sd)
+    with torch.no_grad():
+        logits = m(feats, targets=caps[:, :-1], mode="train")
+        ids = m(feats, mode="test")
+    err = (logits - orc.forward_train(sd, feats, caps[:, :-1])).abs().max().item()
+    assert err < 2e-6 and torch.equal(ids, orc.greedy_decode(sd, feats)), err
+    np.savez_compressed(os.path.join(GOLD, name + ".npz"), seed=seed, dims=np.array([B] + [d[k] for k in "LFHEV"]),
+                        logits=logits.numpy(), greedy_ids=ids.numpy())
+    print(f"[{name}] oracle-vs-reference max|dlogits|={err:.3e}")
+
+
 def gen_pickle():
     """A full-module pickle WRITTEN BY THE REFERENCE class (train.py:167-168 style) at tiny
     dims, to test that the drop-in S2VTModel.S2VT loads reference checkpoints."""
@@ -477,6 +495,8 @@ if __name__ == "__main__":
     if "tiny" in which:
         gen("tiny", seed=7, n_steps=3, out_scale=1.0, do_beam=True, beam_width=3, full=True)
         gen_pickle()
+    if "tiny17" in which:
+        gen_tiny_seed17()
     if "c1" in which:
         gen("c1", seed=11, n_steps=3, out_scale=1.0, do_beam=True, beam_b=2, beam_width=5)
     # c2 / c5beam: (seed, out_scale) chosen by screen() so that the weakest decision of the reference's greedy decode

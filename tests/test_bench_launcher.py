@@ -38,11 +38,33 @@ def test_world_size_mismatch_aborts():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run prints the headline alone, times exactly --steps steps, and --dump-outputs writes the last timed step's loss,
+    parameters and gradients as float32 / float64 .npy files within the 64 MB budget."""
+    import numpy as np
+    d = tmp_path / "out"
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(d)])
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [l for l in r.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert {"metric", "value", "unit", "higher_is_better", "dtype"} <= set(out)
+    assert "roofline" not in out and "cpu_baseline" not in out          # the extras run with --full only
+    files = sorted(os.listdir(d))
+    assert "loss.npy" in files and "param.out_linear.weight.npy" in files and "grad.out_linear.weight.npy" in files
+    arrays = [np.load(d / f) for f in files]
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays)
+    assert sum(a.nbytes for a in arrays) <= 64 << 20
+    assert abs(float(np.load(d / "loss.npy")[0]) - out["final_loss"]) < 1e-5
+
+
+@pytest.mark.gpu
 def test_one_rank_rccl_line_carries_the_comm_record():
     """The N > 1 path of bench.py on the one GPU of the test box: a 1-rank RCCL group (S2VT_BENCH_PG=1) runs the overlapped
     all-reduce code, and the JSON line must say how long each gradient group's collective took and how much of it was exposed
     after the backward - the fields the first 8-GPU run will be read by."""
-    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--headline-only"],
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--headline-only"],
              {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29931",
               "S2VT_BENCH_PG": "1", "S2VT_PERSIST": "1", "S2VT_PIPE_BLOCK": "32"})       # (the options the asserted overlap rests on)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
