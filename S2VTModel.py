@@ -14,6 +14,7 @@ import s2vt_video_caption_amd  # noqa: F401  (registers the package alias)
 from s2vt_video_caption_amd import capi as _capi
 from s2vt_video_caption_amd import functional as _F
 from s2vt_video_caption_amd import beam as _beam
+from s2vt_video_caption_amd import gru_functional as _G
 
 
 class S2VT(nn.Module):
@@ -52,8 +53,9 @@ class S2VT(nn.Module):
         for rnn in (self.vid_rnn, self.word_rnn):
             if not isinstance(rnn, nn.LSTM) or rnn.num_layers != 1 or rnn.bidirectional or not rnn.bias:
                 raise NotImplementedError(
-                    "the HIP S2VT path implements the reference configuration (1-layer unidirectional LSTM); "
-                    "GRU / num_layers>1 / bidirectional are outside the hot path (SURVEY.md §8)")
+                    "the HIP S2VT whole-path drivers implement the reference configuration (1-layer unidirectional LSTM); "
+                    "a 1-layer GRU model runs through forward() on the GRU timestep kernels (gru_functional.py); "
+                    "num_layers>1 / bidirectional are outside the hot path (SURVEY.md §8)")
 
     def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30):
         """
@@ -65,6 +67,8 @@ class S2VT(nn.Module):
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        if _G.is_gru_model(self):
+            return self._forward_gru(feats, targets, mode)
         params = self._hip_params()
         feats = self.feat_drop(feats)                      # identity at the reference's p=0 (S2VTModel.py:52)
         if mode == 'beam_search':
@@ -83,6 +87,26 @@ class S2VT(nn.Module):
         elif mode == 'test':
             return _F.greedy_decode(feats, params, self.sos_ix, owner=self)
         return None                                        # the reference falls through for unknown modes
+
+    def _forward_gru(self, feats, targets, mode):
+        """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""
+        if mode == 'beam_search':
+            raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
+                                      "(S2VTModel.py:153, 'DO NOT SUPPORT GRU'); use mode='test'")
+        feats = self.feat_drop(feats)                      # S2VTModel.py:52
+        if mode == 'train':
+            if targets is None:
+                raise ValueError("mode='train' needs targets")
+            _F.require_hip(targets, "targets")
+            out_mask = None
+            if self.training and self.out_drop.p > 0:
+                # the LSTM path's draw (S2VTModel.py:79): nn.Dropout on a [B, L-1, H] ones tensor, batch-major as the GRU path uses it
+                out_mask = self.out_drop(torch.ones(feats.shape[0], self.length - 1, self.dim_hid, dtype=torch.float32,
+                                                    device=feats.device))
+            return _G.train_forward(self, feats, targets.reshape(targets.shape[0], -1), out_mask=out_mask)
+        elif mode == 'test':
+            return _G.greedy_decode(self, feats, self.sos_ix)
+        return None
 
     @staticmethod
     def _get_word2embed_from_glove(glove_path, ix2word):

@@ -315,6 +315,43 @@ int s2vt_lstm_seq_fwd(int32_t T, int32_t B, int32_t H, const float* gx, int32_t 
 int s2vt_lstm_seq_bwd(int32_t T, int32_t B, int32_t H, const float* w_hh, const float* dh_out, int32_t dh_first,
                       const float* c_all, float* stash_dg, float* w_hh_t, float* dc, void* stream);
 
+/* ---------------------------------------------------------------- GRU cell (rnn_type='gru')
+ * What nn.GRU computes for S2VT(rnn_type='gru') (S2VTModel.py:11-22; torch's gate order r, z, n):
+ *   r = sigmoid(gx_r + h W_hr^T + b_hr), z = sigmoid(gx_z + h W_hz^T + b_hz), n = tanh(gx_n + r * (h W_hn^T + b_hn)),
+ *   h' = n + z * (h - n), with gx = x W_ih^T + b_ih.  weight_hh [3H,H] and b_hh [3H] are passed as they are; b_hh is added
+ * inside the kernels (b_hn belongs inside the r product).  The fp32 fused timestep kernels of csrc/gru.hip (no whole-path
+ * driver: the model-level composition is gru_functional.py's).  Row strides are the natural widths. */
+/* One step (nn.GRU over one timestep: S2VTModel.py:67 / :77 per step): gx [B,3H] or, if NULL, b_ih alone (a zero input);
+ * h_prev NULL = zero state.  stash (optional, [B,4H]) receives r, z, n and ghn = h_prev W_hn^T + b_hn for the backward. */
+int s2vt_gru_step_fwd(int32_t B, int32_t H, const float* gx, const float* b_ih, const float* w_hh, const float* b_hh,
+                      const float* h_prev, float* h_out, float* stash, void* stream);
+/* One DECODE step of word_rnn (S2VTModel.py:100-103 with nn.GRU): gate input gx [B,3H] (vid_out half + b_ih) plus
+ * Emb[token(b)]·W_e^T computed in the kernel; token sources and w_e / ldw_e as s2vt_lstm_step_fwd_token.  A bad id never
+ * addresses memory outside the table (it is read as token 0).  tok_const outside [0, V) is refused at once (S2VT_ERR_INDEX); an
+ * id of `tok` outside [0, V) is reported as S2VT_ERR_INDEX by s2vt_check_async_error / a later call; a packed argmax word is in
+ * range by construction and posts nothing - a greedy loop of these steps makes no device-to-host copy and never waits. */
+int s2vt_gru_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
+                            const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
+                            const unsigned long long* tok_packed, int32_t tok_const, float* h_out, void* stream);
+/* BPTT of one step (autograd of the same, train.py:124): dh_t = dh_out + dh_{t+1} * z_{t+1} + dgh_next·W_hh (w_hh_t = W_hh^T
+ * [H,3H], stash_next = the stash of step t+1); dh [B,H] in: dh_{t+1}, out: dh_t.  dgh_next, stash_next and w_hh_t are all
+ * NULL at the last step (dh is then not read).  Writes dgx [B,3H] = d(gate input) and dgh [B,3H] = d(h W_hh^T + b_hh). */
+int s2vt_gru_step_bwd(int32_t B, int32_t H, const float* dgh_next, const float* w_hh_t, const float* stash_next, const float* dh_out,
+                      const float* stash, const float* h_prev, float* dh, float* dgx, float* dgh, void* stream);
+/* A whole layer from the zero state (vid_rnn / word_rnn at S2VTModel.py:67 / :77): gx [n_gx*B, 3H] time-major covers steps
+ * 0..n_gx-1, later steps see b_ih only (the zero-padded frames of S2VTModel.py:64-65).  h_all [T*B,H] out; stash [T*B,4H]
+ * optional (NULL: inference). */
+int s2vt_gru_seq_fwd(int32_t T, int32_t B, int32_t H, const float* gx, int32_t n_gx, const float* b_ih, const float* w_hh,
+                     const float* b_hh, float* h_all, float* stash, void* stream);
+/* BPTT over the layer: dh_out rows for steps >= dh_first ([(T-dh_first)*B, H]; NULL: none); h_all and stash of the forward
+ * (left untouched).  dgx, dgh [T*B,3H] out: dW_ih = dgx^T x, db_ih = colsum(dgx), dW_hh = dgh[B:]^T h_all[:-B],
+ * db_hh = colsum(dgh).  w_hh_t [H*3H] and dh [B*H] are scratch provided by the caller. */
+int s2vt_gru_seq_bwd(int32_t T, int32_t B, int32_t H, const float* w_hh, const float* dh_out, int32_t dh_first, const float* h_all,
+                     const float* stash, float* w_hh_t, float* dh, float* dgx, float* dgh, void* stream);
+/* tok[t*B + b] = targets[b*targets_ld + t] (int64 batch-major -> int32 time-major, t < Lm1): the word ids nn.Embedding gathers
+ * at S2VTModel.py:71.  An id outside [0, V) is clamped and reported as S2VT_ERR_INDEX by s2vt_check_async_error / the next call. */
+int s2vt_tokens_time_major(int32_t B, int32_t Lm1, int32_t V, const int64_t* targets, int64_t targets_ld, int32_t* tok, void* stream);
+
 /* Config-3 arithmetic of one LSTM layer forward (nn.LSTM at S2VTModel.py:67/:77 with bf16 operands, fp32 accumulate,
  * fp32 cell state): gx_stash [T*B,4H] gate input in (steps < n_gx; bias for the rest), activated gates out; h_all,
  * c_all [T*B,H] out.  persistent = 0: one launch per timestep; 1: one persistent launch per `block` timesteps

@@ -95,6 +95,13 @@ SIGNATURES = {
     "s2vt_lstm_step_bwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p]),
     "s2vt_lstm_seq_fwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 6),
     "s2vt_lstm_seq_bwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 5),
+    "s2vt_gru_step_fwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 8),
+    "s2vt_gru_step_fwd_token": (c_int32, [c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
+                                                                                           c_int32, c_void_p, c_void_p]),
+    "s2vt_gru_step_bwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 10),
+    "s2vt_gru_seq_fwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 6),
+    "s2vt_gru_seq_bwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 7),
+    "s2vt_tokens_time_major": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),
     "s2vt_lstm_seq_bf16_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_lstm_seq_fwd_bf16": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_int32, c_int32, c_void_p]),

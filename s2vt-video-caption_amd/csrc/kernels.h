@@ -119,6 +119,43 @@ struct StepBwdArgs {
 int lstm_step_bwd(hipStream_t stream, const StepBwdArgs& a);
 int lstm_step_bwd2(hipStream_t stream, const StepBwdArgs& a, const StepBwdArgs* b);
 
+// ---- gru.hip: the same launch-per-timestep scheme for nn.GRU (gate order r, z, n)
+struct GruFwdArgs {
+    int B, H;
+    const float* h_prev; int64_t ldh;        // h_{t-1} [B,H] (nullptr: zero state)
+    const float* w_hh; int64_t ldw;          // W_hh [3H,H]
+    const float* b_hh;                       // [3H]: b_hr, b_hz join the r / z pre-activations, b_hn the recurrent n term
+    // gate input x W_ih^T + b_ih per batch row [B,3H], or b_ih alone for a zero input (gx == nullptr)
+    const float* gx; int64_t ldgx;
+    const float* b_ih;
+    // optional token segment (greedy decode): Emb[tok(b)]·W_e^T [B,3H] added to the gate input, tokens as in StepFwdArgs
+    const float* x2; int64_t ldx2; int K2;
+    const float* w2; int64_t ldw2;
+    const int32_t* tok_idx;
+    const unsigned long long* tok_packed;
+    int tok_const;
+    int tok_limit; int* tok_err;
+    float* h_out; int64_t ldho;
+    float* stash; int64_t ldst;              // optional [B,4H]: r, z, n, ghn = h_{t-1} W_hn^T + b_hn (train only)
+};
+int gru_step_fwd(hipStream_t stream, const GruFwdArgs& a);
+
+struct GruBwdArgs {
+    int B, H;
+    // dh_t = dh_out_t + dh_{t+1} * z_{t+1} + dGh_{t+1}·W_hh (against W_hh^T [H,3H]); dgh_next == nullptr at the last step:
+    // then neither dGh_{t+1}, z_{t+1} nor dh_{t+1} is read
+    const float* dgh_next; int64_t lddgh;
+    const float* w_hh_t; int64_t ldwt;
+    const float* stash_next; int64_t ldstn;  // stash of step t+1 (its z)
+    const float* dh_out; int64_t lddho;      // gradient from above at this step (nullable)
+    const float* stash; int64_t ldst;        // r, z, n, ghn of this step
+    const float* h_prev; int64_t ldhp;       // h_{t-1} (nullptr: zero state)
+    float* dh; int64_t lddh;                 // in: dh_{t+1} (ignored at the last step), out: dh_t
+    float* dgx; int64_t lddgx;               // out [B,3H]: d(gate input) = dr_pre, dz_pre, dn_pre
+    float* dgh; int64_t lddgh_out;           // out [B,3H]: d(h W_hh^T + b_hh) = dr_pre, dz_pre, dn_pre * r
+};
+int gru_step_bwd(hipStream_t stream, const GruBwdArgs& a);
+
 // ---- lstm_bf16.hip: bf16-operand timestep kernels (config 3)
 struct StepFwdBf16Args {
     int B, H, Kp;                                   // Kp: k extent of the bf16 operands (H zero-padded to 64)

@@ -8,7 +8,7 @@ import ctypes
 import torch
 
 from . import capi
-from .functional import _ptr, _stream, _f32c
+from .functional import _ptr, _stream, _f32c, require_hip
 
 
 def gemm(a, b, bias=None, a_kmajor=True, b_kmajor=True, out=None, accumulate=False):
@@ -364,3 +364,102 @@ def lstm_seq_bwd_persist(T, B, w_hh, dh_out, dh_first, c_all, gates, block=0, se
                                                     _stream(dev)), "s2vt_lstm_seq_bwd_x3_persist")
         _check_persist_err(ws)
     return sets[0][3] if second is None else (sets[0][3], sets[1][3])
+
+
+# ---------------------------------------------------------------- GRU cell (include/s2vt_hip.h: s2vt_gru_*)
+def gru_step_fwd(gx, b_ih, w_hh, b_hh, h_prev, want_stash=False, B=None):
+    """One nn.GRU step: gx [B,3H] (x W_ih^T + b_ih) or None (then b_ih alone: a zero input); h_prev [B,H] or None (zero state;
+    with neither, `B` gives the batch).  Returns h [B,H] (and the stash [B,4H] = r, z, n, ghn)."""
+    lib = capi.load()
+    w_hh, b_hh = _f32c(w_hh, "w_hh"), _f32c(b_hh, "b_hh")
+    H = w_hh.shape[1]
+    B = gx.shape[0] if gx is not None else (h_prev.shape[0] if h_prev is not None else int(B))
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        h = torch.empty(B, H, dtype=torch.float32, device=dev)
+        stash = torch.empty(B, 4 * H, dtype=torch.float32, device=dev) if want_stash else None
+        capi.check(lib.s2vt_gru_step_fwd(B, H, _ptr(gx), _ptr(b_ih), _ptr(w_hh), _ptr(b_hh), _ptr(h_prev), _ptr(h), _ptr(stash),
+                                         _stream(dev)), "s2vt_gru_step_fwd")
+    return (h, stash) if want_stash else h
+
+
+def gru_step_fwd_token(gx, w_hh, b_hh, h_prev, emb, w_ih, tok=None, tok_packed=None, tok_const=0, out=None):
+    """One greedy decode step of a GRU word_rnn: gx [B,3H] (vid half of the gate input + b_ih), emb [V,E], w_ih [3H, E+H] (its
+    first E columns multiply the embedded word).  Token per row: `tok` int32 [B], else `tok_packed` (the packed argmax words of
+    s2vt_decode_step_argmax), else `tok_const`.  Ids outside [0, V) raise IndexError at the next capi.check_async_error()."""
+    lib = capi.load()
+    gx, w_hh, b_hh, emb, w_ih = (_f32c(gx, "gx"), _f32c(w_hh, "w_hh"), _f32c(b_hh, "b_hh"), _f32c(emb, "emb"), _f32c(w_ih, "w_ih"))
+    B, H = gx.shape[0], w_hh.shape[1]
+    V, E = emb.shape
+    dev = gx.device
+    with torch.cuda.device(dev):
+        h = out if out is not None else torch.empty(B, H, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_gru_step_fwd_token(B, H, E, V, _ptr(gx), _ptr(w_hh), _ptr(b_hh), _ptr(h_prev), _ptr(emb), _ptr(w_ih),
+                                               w_ih.stride(0), _ptr(tok), _ptr(tok_packed), int(tok_const), _ptr(h), _stream(dev)),
+                   "s2vt_gru_step_fwd_token")
+    return h
+
+
+def gru_step_bwd(dgh_next, w_hh_t, stash_next, dh_out, stash, h_prev, dh):
+    """BPTT of one GRU step; `dh` [B,H] holds dh_{t+1} on entry (ignored at the last step: dgh_next None) and dh_t on exit.
+    Returns (dgx, dgh) [B,3H]."""
+    lib = capi.load()
+    B, H4 = stash.shape
+    H = H4 // 4
+    dev = stash.device
+    with torch.cuda.device(dev):
+        dgx = torch.empty(B, 3 * H, dtype=torch.float32, device=dev)
+        dgh = torch.empty(B, 3 * H, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_gru_step_bwd(B, H, _ptr(dgh_next), _ptr(w_hh_t), _ptr(stash_next), _ptr(dh_out), _ptr(stash),
+                                         _ptr(h_prev), _ptr(dh), _ptr(dgx), _ptr(dgh), _stream(dev)), "s2vt_gru_step_bwd")
+    return dgx, dgh
+
+
+def gru_seq_fwd(T, B, gx, n_gx, b_ih, w_hh, b_hh, want_stash=False):
+    """A GRU layer from the zero state; gx [n_gx*B, 3H] time-major, b_ih alone for the later steps.  Returns (h_all [T*B,H],
+    stash [T*B,4H] or None)."""
+    lib = capi.load()
+    w_hh, b_hh = _f32c(w_hh, "w_hh"), _f32c(b_hh, "b_hh")
+    H = w_hh.shape[1]
+    dev = w_hh.device
+    if n_gx:
+        gx = _f32c(gx, "gx")
+    with torch.cuda.device(dev):
+        h_all = torch.empty(T * B, H, dtype=torch.float32, device=dev)
+        stash = torch.empty(T * B, 4 * H, dtype=torch.float32, device=dev) if want_stash else None
+        capi.check(lib.s2vt_gru_seq_fwd(T, B, H, _ptr(gx if n_gx else None), int(n_gx), _ptr(b_ih), _ptr(w_hh), _ptr(b_hh),
+                                        _ptr(h_all), _ptr(stash), _stream(dev)), "s2vt_gru_seq_fwd")
+    return h_all, stash
+
+
+def gru_seq_bwd(T, B, w_hh, dh_out, dh_first, h_all, stash):
+    """BPTT over a GRU layer (h_all, stash of gru_seq_fwd, left untouched).  Returns (dgx, dgh) [T*B,3H]."""
+    lib = capi.load()
+    w_hh = _f32c(w_hh, "w_hh")
+    H = w_hh.shape[1]
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        wt = torch.empty(H, 3 * H, dtype=torch.float32, device=dev)
+        dh = torch.empty(B, H, dtype=torch.float32, device=dev)
+        dgx = torch.empty(T * B, 3 * H, dtype=torch.float32, device=dev)
+        dgh = torch.empty(T * B, 3 * H, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_gru_seq_bwd(T, B, H, _ptr(w_hh), _ptr(dh_out), int(dh_first), _ptr(_f32c(h_all, "h_all")),
+                                        _ptr(_f32c(stash, "stash")), _ptr(wt), _ptr(dh), _ptr(dgx), _ptr(dgh), _stream(dev)),
+                   "s2vt_gru_seq_bwd")
+    return dgx, dgh
+
+
+def tokens_time_major(targets, Lm1, V):
+    """int32 [Lm1*B] time-major word ids of targets [B, >=Lm1] (int64); ids outside [0, V) are clamped and raise IndexError at
+    the next capi.check_async_error()."""
+    lib = capi.load()
+    require_hip(targets, "targets")
+    if targets.dtype != torch.int64 or targets.stride(1) != 1:
+        targets = targets.long().contiguous()
+    B = targets.shape[0]
+    dev = targets.device
+    with torch.cuda.device(dev):
+        tok = torch.empty(Lm1 * B, dtype=torch.int32, device=dev)
+        capi.check(lib.s2vt_tokens_time_major(B, Lm1, V, _ptr(targets), targets.stride(0), _ptr(tok), _stream(dev)),
+                   "s2vt_tokens_time_major")
+    return tok

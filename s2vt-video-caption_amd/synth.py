@@ -39,7 +39,11 @@ def make_state_dict(V, F, H, E, seed=0, out_scale=1.0):
     ``out_scale`` widens the logits (a larger top-2 margin makes greedy token
     ids robust to fp32 summation order, SURVEY.md §7 "Bit-exact token ids").
     """
-    shapes = param_shapes(V, F, H, E)
+    return _seeded_params(param_shapes(V, F, H, E), F, H, seed, out_scale)
+
+
+def _seeded_params(shapes, F, H, seed, out_scale):
+    """The recipe of make_state_dict over a {key: shape} layout (the LSTM's or the GRU's)."""
     sd = {}
     for idx, key in enumerate(sorted(shapes)):
         g = torch.Generator().manual_seed(1000003 * seed + idx)
@@ -91,3 +95,18 @@ CONFIGS = {
     # not a BASELINE config: B = 64 (split-precision / two-stream drivers) at dims small enough for long CPU reference runs
     "mid64": dict(B=64, L=24, F=512, H=256, E=256, V=1000),
 }
+
+
+def gru_param_shapes(V, F, H, E):
+    """state_dict layout of S2VT(rnn_type='gru'): nn.GRU keeps three gate blocks (r, z, n) where nn.LSTM keeps four."""
+    shapes = param_shapes(V, F, H, E)
+    for k in list(shapes):
+        if k.startswith(("vid_rnn.", "word_rnn.")):
+            shapes[k] = (3 * H,) + tuple(shapes[k][1:])
+    return shapes
+
+
+def make_gru_state_dict(V, F, H, E, seed=0, out_scale=1.0):
+    """make_state_dict's recipe for the GRU layout (same distributions, same per-key generators in sorted key order): every
+    recurrent tensor is the first 3H rows of the LSTM recipe's tensor of the same key and seed."""
+    return _seeded_params(gru_param_shapes(V, F, H, E), F, H, seed, out_scale)

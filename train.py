@@ -47,6 +47,9 @@ def parse(argv=None):
     ap.add_argument("--model", choices=("s2vt", "att_baseline"), default="s2vt",
                     help="s2vt: S2VTModel.S2VT (the hot path); att_baseline: attention_baseline.Att_Baseline, the network the "
                          "reference's committed train.py:86 instantiates")
+    ap.add_argument("--rnn-type", choices=("lstm", "gru"), default="lstm",
+                    help="S2VT's recurrent cell (the reference's Opt.rnn_type): gru runs the GRU timestep kernels with torch's Adam "
+                         "and, with several processes, the plain bucketed all-reduce")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
     return ap.parse_args(argv)
 
@@ -105,16 +108,17 @@ def run(opt):
     else:
         model = S2VT(len(word2ix), opt.feat_dim, length=opt.train_length, dim_hid=opt.dim_hidden, dim_embed=opt.dim_embed,
                      feat_dropout=opt.feat_dropout, rnn_dropout=opt.rnn_dropout, out_dropout=opt.out_dropout,
-                     sos_ix=word2ix['<sos>'], eos_ix=word2ix['<eos>'])
+                     rnn_type=opt.rnn_type, sos_ix=word2ix['<sos>'], eos_ix=word2ix['<eos>'])
+    flat = opt.model == "s2vt" and opt.rnn_type == "lstm"      # the LSTM whole path: flat gradient buffer, FlatAdam
     if opt.init_state:
         model.load_state_dict(torch.load(opt.init_state))
     model.to(dev)
     reducer = None
     if world > 1:       # S2VT: gradients written straight into the flat buffer, all-reduce overlapped with the backward;
-        reducer = dp.FlatGradAllReducer(model.parameters())            # Att_Baseline: plain bucketed all-reduce after it
-        if opt.model == "s2vt":
+        reducer = dp.FlatGradAllReducer(model.parameters())            # Att_Baseline, GRU: plain bucketed all-reduce after it
+        if flat:
             reducer.attach(model)
-    if opt.model == "s2vt":     # train.py:89-93's Adam, same arithmetic, as one launch over flat parameter / gradient / moment buffers
+    if flat:                    # train.py:89-93's Adam, same arithmetic, as one launch over flat parameter / gradient / moment buffers
         from s2vt_video_caption_amd.optim import FlatAdam
         optimizer = FlatAdam(model, lr=opt.lr, reducer=reducer)
     else:
