@@ -164,12 +164,21 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
     // nwait = how many of this wave's youngest vector-memory operations may still be outstanding when stage g must have landed
     // (the 6 requests of stage g + 1, plus the store instructions of an epilogue issued between them and now)
     // DEFERRED hi*hi group: the sixth product group of a stage (plane 0 x plane 0, whose operands are in registers) is issued at the
-    // START of the next stage, right behind that stage's 3 (MI + 2) fragment reads - the 2 MI MFMAs per wave (both waves of a SIMD:
-    // ~512 cycles) run while the reads cross the LDS pipe, where every wave of the workgroup used to sit idle for the ~400 cycles
-    // until its first fragments were back.  The order of the MFMAs on each accumulator is unchanged (bitwise the same sums).
+    // START of the next stage, in front of that stage's vmcnt wait and barrier: the 2 MI MFMAs per wave (both waves of a SIMD: ~512
+    // cycles) run while the wave waits for its stage to land and for the slowest wave at the barrier, time in which the matrix pipe
+    // used to be idle.  (It used to be issued behind the barrier, right after the fragment reads, to cover their latency; in front of
+    // the barrier the 14 GEMM shapes of a C2 step take 1.5-2 % less in sum: profiles/round6_gemm_x3_deferred_ab.txt.)
+    // The order of the MFMAs on each accumulator is unchanged (bitwise the same sums).
     bf16x8 a0p[MI], b0p[2];
     auto stage = [&](int g, auto more_tag, bool more_rt, __amdgpu_buffer_rsrc_t r2, int s2, int nwait, bool deferred) {
         const bool more = decltype(more_tag)::value || more_rt;       // (compile-time true inside a tile: no branch around the requests)
+        if (deferred) {     // the previous stage's hi*hi group, issued IN FRONT of the wait and the barrier (see above)
+#pragma unroll
+            for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0p[mi], b0p[ni], acc[mi][ni], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
         if (nwait == 6) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else if (nwait == 0) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
         else asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(6 + 8 * MI) : "memory");
@@ -222,13 +231,6 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
     X3_PROD(PA, PB)                                                        \
     if (req) { X3_REQ1(J, r2, s2, slot2) }                                 \
     __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_sched_barrier(0);       // (the deferred group stays BEHIND the fragment reads: it is what covers their latency)
-        if (deferred) {
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0p[mi], b0p[ni], acc[mi][ni], 0, 0, 0);
-        }
         if (req) { X3_REQ1(5, r2, s2, slot2) }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (TT) {
