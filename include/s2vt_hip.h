@@ -352,6 +352,46 @@ int s2vt_gru_seq_bwd(int32_t T, int32_t B, int32_t H, const float* w_hh, const f
  * at S2VTModel.py:71.  An id outside [0, V) is clamped and reported as S2VT_ERR_INDEX by s2vt_check_async_error / the next call. */
 int s2vt_tokens_time_major(int32_t B, int32_t Lm1, int32_t V, const int64_t* targets, int64_t targets_ld, int32_t* tok, void* stream);
 
+/* ---------------------------------------------------------------- stacked LSTM chain (num_layers > 1)
+ * S2VT with num_layers = N (S2VTModel.py:11-22: nn.LSTM(num_layers=N) for vid_rnn and word_rnn) is one chain of 2N LSTM layers
+ * over T = 2L-1 steps: vid_l0 .. vid_l(N-1), word_l0 (input [Emb | vid top]), word_l1 .. word_l(N-1).  Layer j > 0 of a chain
+ * reads the output of layer j-1 at the same step (its masked copy hm when layer j-1 has a dropout mask).  The entry points run
+ * the chain as a layer wavefront (csrc/lstm_stack.hip): launch d advances every layer-step (j, t = d - j), so the chain takes
+ * T + n - 1 launches (more where a diagonal holds more layer-steps than one launch).  fp32 throughout; row strides are the
+ * natural widths (H, 4H) unless given; all step-indexed buffers are time-major (row t*B + b). */
+typedef struct s2vt_lstm_layer {
+    const float* w_hh;               /* [4H,H] weight_hh_l{k} */
+    const float* w_in;               /* [4H, ldw_in] with the H input columns first: weight_ih_l{k} of the layer (k > 0), or the
+                                        last H columns of word_rnn.weight_ih_l0 (the vid half).  NULL: no dense input */
+    int64_t ldw_in;
+    const float* x_in;               /* layer 0 only: its dense input [T*B,H] (e.g. vid top for the word chain); NULL: none */
+    const float* gx;                 /* gate input rows x W_ih^T + b_ih + b_hh for steps [gx_t0, gx_t0 + n_gx): [n_gx*B, 4H] */
+    int32_t gx_t0, n_gx;
+    const float* bias;               /* [4H] b_ih + b_hh: the gate input of every other step */
+    const float* h0; const float* c0;  /* [B,H] initial state (NULL: zero) */
+    const float* mask;               /* [T*B,H] dropout mask (0 or 1/(1-p)) of this output as the next layer's input, or NULL */
+    /* token segment (greedy decode, T = 1): Emb[tok] . W_e^T with tok = the packed argmax word (tok_packed, from
+     * s2vt_decode_step_argmax) or tok_const; emb [V,E], w_e [4H, ldw_e] with the E embedding columns first */
+    const float* emb; const float* w_e; int64_t ldw_e; int32_t E, V;
+    const unsigned long long* tok_packed; int32_t tok_const;
+    float* h; float* c;              /* [T*B,H] out */
+    float* stash;                    /* [T*B,4H] activated gates i,f,g,o (train; NULL: not kept) */
+    float* hm;                       /* [T*B,H] m . h (required with mask) */
+    /* backward only */
+    const float* dh_ext; int32_t dh_t0;  /* gradient from outside for steps >= dh_t0: [(T-dh_t0)*B, H]; NULL: none */
+    float* dg;                       /* [T*B,4H] out: gradient of the gate pre-activations (may alias stash) */
+} s2vt_lstm_layer;
+/* Forward of the chain (S2VTModel.py:67 and :77 for N layers each; greedy decode :86-:106 with T = 1, h0/c0 and the token
+ * segment on word_l0).  Arguments are checked before any launch. */
+int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_lstm_layer* layers, void* stream);
+/* BPTT of the same chain (autograd at train.py:124): reads w_hh, w_in, mask, c0, c, stash, dh_ext of each layer, writes dg; the
+ * initial states are constants (no gradient).  dh of layer j at step t = dh_ext + dG^j_{t+1} W_hh^j + m^j_t . (dG^{j+1}_t W_in^{j+1}).
+ * The caller forms the weight gradients: dW_hh = dg[B:]^T h[:-B] (+ dg[:B]^T h0), dW_in = dg^T x, biases = column sums of dg.
+ * workspace: s2vt_lstm_chain_bwd_workspace_bytes (transposed weights and the dc rows). */
+size_t s2vt_lstm_chain_bwd_workspace_bytes(int32_t B, int32_t H, int32_t n);
+int s2vt_lstm_chain_bwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_lstm_layer* layers, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
 /* Config-3 arithmetic of one LSTM layer forward (nn.LSTM at S2VTModel.py:67/:77 with bf16 operands, fp32 accumulate,
  * fp32 cell state): gx_stash [T*B,4H] gate input in (steps < n_gx; bias for the rest), activated gates out; h_all,
  * c_all [T*B,H] out.  persistent = 0: one launch per timestep; 1: one persistent launch per `block` timesteps

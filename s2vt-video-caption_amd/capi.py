@@ -33,6 +33,15 @@ class Grads(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in PARAM_FIELDS]
 
 
+class LstmLayer(ctypes.Structure):
+    """s2vt_lstm_layer of include/s2vt_hip.h: one layer of a stacked LSTM chain"""
+    _fields_ = [("w_hh", c_void_p), ("w_in", c_void_p), ("ldw_in", c_int64), ("x_in", c_void_p), ("gx", c_void_p),
+                ("gx_t0", c_int32), ("n_gx", c_int32), ("bias", c_void_p), ("h0", c_void_p), ("c0", c_void_p),
+                ("mask", c_void_p), ("emb", c_void_p), ("w_e", c_void_p), ("ldw_e", c_int64), ("E", c_int32), ("V", c_int32),
+                ("tok_packed", c_void_p), ("tok_const", c_int32), ("h", c_void_p), ("c", c_void_p), ("stash", c_void_p),
+                ("hm", c_void_p), ("dh_ext", c_void_p), ("dh_t0", c_int32), ("dg", c_void_p)]
+
+
 # name -> (restype, argtypes): every symbol include/s2vt_hip.h declares
 ABI_VERSION = 9          # S2VT_ABI_VERSION of include/s2vt_hip.h this binding was written against
 
@@ -99,6 +108,9 @@ SIGNATURES = {
     "s2vt_gru_step_fwd_token": (c_int32, [c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
                                                                                            c_int32, c_void_p, c_void_p]),
     "s2vt_gru_step_bwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 10),
+    "s2vt_lstm_chain_fwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(LstmLayer), c_void_p]),
+    "s2vt_lstm_chain_bwd_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_lstm_chain_bwd": (c_int32, [c_int32, c_int32, c_int32, c_int32, POINTER(LstmLayer), c_void_p, c_size_t, c_void_p]),
     "s2vt_gru_seq_fwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 6),
     "s2vt_gru_seq_bwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 7),
     "s2vt_tokens_time_major": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p, c_void_p]),

@@ -156,6 +156,41 @@ struct GruBwdArgs {
 };
 int gru_step_bwd(hipStream_t stream, const GruBwdArgs& a);
 
+// ---- lstm_stack.hip: layer-wavefront kernels of a stacked LSTM chain (one launch = up to CHAIN_MAX independent layer-steps
+// of one B, H).  Row strides are the natural widths (H, 4H) except the weight blocks W_in and W_e.
+constexpr int CHAIN_MAX = 4;
+struct ChainFwdStep {
+    const float* gx;                         // [B,4H] gate input row block (x W_ih^T + b_ih + b_hh), or NULL: bias alone
+    const float* bias;                       // [4H]
+    const float* h_prev;                     // [B,H] (NULL: zero state)
+    const float* w_hh;                       // [4H,H]
+    const float* c_prev;                     // [B,H] (NULL: zero state)
+    const float* x;                          // [B,H] dense input (the layer below's output at this step), or NULL
+    const float* w_in; int64_t ldw_in;       // [4H, K=H] input-weight block of x
+    // token segment (greedy decode): Emb[tok(b)] · W_e^T, tok from the packed argmax word or tok_const; ids outside
+    // [0, tok_limit) read row 0
+    const float* emb; int E;
+    const float* w_e; int64_t ldw_e;
+    const unsigned long long* tok_packed; int tok_const; int tok_limit;
+    const float* mask;                       // [B,H] dropout mask of this output as the next layer's input (NULL: none)
+    float* h_out; float* c_out;              // [B,H]
+    float* stash;                            // [B,4H] activated gates i,f,g,o (NULL: not kept)
+    float* hm_out;                           // [B,H] mask ⊙ h (with mask)
+};
+struct ChainFwdLaunch { int B, H, n, tiles; ChainFwdStep s[CHAIN_MAX]; };
+struct ChainBwdStep {
+    const float* dg_next; const float* w_hh_t;   // dG of this layer at t+1 [B,4H] (NULL at the last step), W_hh^T [H,4H]
+    const float* dg_up; const float* w_in_t;     // dG of the layer above at t [B,4H] (NULL at the top), its W_in^T [H,4H]
+    const float* mask;                           // [B,H] this layer's output mask (scales the dg_up term), or NULL
+    const float* dh_ext;                         // [B,H] gradient from outside (nullable)
+    const float* stash; const float* c; const float* c_prev;   // activated gates [B,4H], c_t, c_{t-1} (NULL: zero)
+    float* dc;                                   // [B,H] in dL/dc_t, out dL/dc_{t-1}
+    float* dg;                                   // [B,4H] out (may alias stash)
+};
+struct ChainBwdLaunch { int B, H, n, tiles; ChainBwdStep s[CHAIN_MAX]; };
+int lstm_chain_fwd_launch(hipStream_t stream, const ChainFwdLaunch& a);
+int lstm_chain_bwd_launch(hipStream_t stream, const ChainBwdLaunch& a);
+
 // ---- lstm_bf16.hip: bf16-operand timestep kernels (config 3)
 struct StepFwdBf16Args {
     int B, H, Kp;                                   // Kp: k extent of the bf16 operands (H zero-padded to 64)

@@ -463,3 +463,49 @@ def tokens_time_major(targets, Lm1, V):
         capi.check(lib.s2vt_tokens_time_major(B, Lm1, V, _ptr(targets), targets.stride(0), _ptr(tok), _stream(dev)),
                    "s2vt_tokens_time_major")
     return tok
+
+
+_LAYER_TENSORS = ("w_hh", "w_in", "x_in", "gx", "bias", "h0", "c0", "mask", "emb", "w_e", "h", "c", "stash", "hm", "dh_ext", "dg")
+
+
+def _chain_struct(layers):
+    """capi.LstmLayer array of a chain: each layer a dict of s2vt_lstm_layer fields (tensors for the pointers, contiguous except
+    w_in / w_e, whose row stride is taken from the tensor; tok_packed an int64 tensor)"""
+    arr = (capi.LstmLayer * len(layers))()
+    for s, lay in zip(arr, layers):
+        for k in _LAYER_TENSORS:
+            t = lay.get(k)
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.stride(-1) != 1 or (k not in ("w_in", "w_e") and not t.is_contiguous()):
+                raise capi.S2VTHipError("chain layer field %s: float32 rows with unit column stride expected" % k)
+            setattr(s, k, t.data_ptr())
+        if lay.get("w_in") is not None:
+            s.ldw_in = lay["w_in"].stride(0)
+        if lay.get("w_e") is not None:
+            s.ldw_e = lay["w_e"].stride(0)
+        if lay.get("tok_packed") is not None:
+            s.tok_packed = lay["tok_packed"].data_ptr()
+        for k in ("gx_t0", "n_gx", "E", "V", "tok_const", "dh_t0"):
+            setattr(s, k, int(lay.get(k, 0)))
+    return arr
+
+
+def lstm_chain_fwd(T, B, H, layers):
+    """s2vt_lstm_chain_fwd over `layers` (dicts, see _chain_struct); the output tensors h, c (stash, hm) are the caller's."""
+    lib = capi.load()
+    dev = layers[0]["w_hh"].device
+    arr = _chain_struct(layers)
+    with torch.cuda.device(dev):
+        capi.check(lib.s2vt_lstm_chain_fwd(T, B, H, len(layers), arr, _stream(dev)), "s2vt_lstm_chain_fwd")
+
+
+def lstm_chain_bwd(T, B, H, layers):
+    """s2vt_lstm_chain_bwd: writes each layer's dg (which may be its stash) from the forward's c / stash and dh_ext."""
+    lib = capi.load()
+    dev = layers[0]["w_hh"].device
+    arr = _chain_struct(layers)
+    with torch.cuda.device(dev):
+        nbytes = lib.s2vt_lstm_chain_bwd_workspace_bytes(B, H, len(layers))
+        ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
+        capi.check(lib.s2vt_lstm_chain_bwd(T, B, H, len(layers), arr, _ptr(ws), nbytes, _stream(dev)), "s2vt_lstm_chain_bwd")

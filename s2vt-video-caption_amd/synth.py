@@ -12,7 +12,18 @@ import math
 import torch
 
 # state_dict layout of the reference model (S2VTModel.py:19-28), see SURVEY.md §5.
-def param_shapes(V, F, H, E):
+def param_shapes(V, F, H, E, num_layers=1):
+    """num_layers > 1 adds nn.LSTM's weight_ih_l{k} [4H,H], weight_hh_l{k} [4H,H], bias_ih_l{k}, bias_hh_l{k} [4H] for k >= 1 to
+    both recurrences (S2VTModel.py:17-20); the one-layer layout is unchanged."""
+    shapes = _shapes_l0(V, F, H, E)
+    for rnn in ("vid_rnn", "word_rnn"):
+        for k in range(1, num_layers):
+            shapes.update({"%s.weight_ih_l%d" % (rnn, k): (4 * H, H), "%s.weight_hh_l%d" % (rnn, k): (4 * H, H),
+                           "%s.bias_ih_l%d" % (rnn, k): (4 * H,), "%s.bias_hh_l%d" % (rnn, k): (4 * H,)})
+    return shapes
+
+
+def _shapes_l0(V, F, H, E):
     return {
         "vid_rnn.weight_ih_l0": (4 * H, H),
         "vid_rnn.weight_hh_l0": (4 * H, H),
@@ -30,7 +41,7 @@ def param_shapes(V, F, H, E):
     }
 
 
-def make_state_dict(V, F, H, E, seed=0, out_scale=1.0):
+def make_state_dict(V, F, H, E, seed=0, out_scale=1.0, num_layers=1):
     """Seeded parameters with torch-default-like magnitudes.
 
     LSTM / Linear tensors: U(-k, k), k = 1/sqrt(fan) (fan = H for the LSTMs,
@@ -38,8 +49,9 @@ def make_state_dict(V, F, H, E, seed=0, out_scale=1.0):
     (seed + index in sorted key order) so adding a key never shifts the others.
     ``out_scale`` widens the logits (a larger top-2 margin makes greedy token
     ids robust to fp32 summation order, SURVEY.md §7 "Bit-exact token ids").
+    ``num_layers`` > 1: the _l1... keys of a stacked model join the sorted key order with the same recipe (fan = H).
     """
-    return _seeded_params(param_shapes(V, F, H, E), F, H, seed, out_scale)
+    return _seeded_params(param_shapes(V, F, H, E, num_layers), F, H, seed, out_scale)
 
 
 def _seeded_params(shapes, F, H, seed, out_scale):

@@ -30,7 +30,12 @@ def parse(argv=None):
     ap.add_argument("--feat-dim", type=int, default=4096)
     ap.add_argument("--feat-dropout", type=float, default=0.0)
     ap.add_argument("--out-dropout", type=float, default=0.0)
-    ap.add_argument("--rnn-dropout", type=float, default=0.0, help="accepted as upstream; no effect with one LSTM layer")
+    ap.add_argument("--rnn-dropout", type=float, default=0.0,
+                    help="nn.LSTM's dropout between the layers of vid_rnn / word_rnn (the reference's Opt.rnn_dropout); no effect "
+                         "with one layer")
+    ap.add_argument("--num-layers", type=int, default=1,
+                    help="layers of vid_rnn and word_rnn (the reference's Opt.num_layers): > 1 runs the stacked-LSTM chain "
+                         "kernels with torch's Adam and, across processes, the plain bucketed all-reduce")
     ap.add_argument("--batch-size", type=int, default=16, help="per process")
     ap.add_argument("--workers", type=int, default=0,
                     help="DataLoader worker processes (0 = the reference's behaviour: items are loaded by the feed thread; "
@@ -108,8 +113,9 @@ def run(opt):
     else:
         model = S2VT(len(word2ix), opt.feat_dim, length=opt.train_length, dim_hid=opt.dim_hidden, dim_embed=opt.dim_embed,
                      feat_dropout=opt.feat_dropout, rnn_dropout=opt.rnn_dropout, out_dropout=opt.out_dropout,
-                     rnn_type=opt.rnn_type, sos_ix=word2ix['<sos>'], eos_ix=word2ix['<eos>'])
-    flat = opt.model == "s2vt" and opt.rnn_type == "lstm"      # the LSTM whole path: flat gradient buffer, FlatAdam
+                     num_layers=opt.num_layers, rnn_type=opt.rnn_type, sos_ix=word2ix['<sos>'], eos_ix=word2ix['<eos>'])
+    # the one-layer LSTM whole path: flat gradient buffer, FlatAdam
+    flat = opt.model == "s2vt" and opt.rnn_type == "lstm" and opt.num_layers == 1
     if opt.init_state:
         model.load_state_dict(torch.load(opt.init_state))
     model.to(dev)
