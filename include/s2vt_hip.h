@@ -148,9 +148,14 @@ int s2vt_beam_queue_result(int32_t B, int32_t beam_width, int32_t max_depth, voi
 /* Data-parallel overlap (no reference counterpart: the reference is single-device).  After s2vt_train_backward has
  * RETURNED (all of its work is enqueued), make `stream` wait until a group of that call's parameter gradients is
  * final, so that their all-reduce can run under the rest of the backward:
- *   group 0 = out_linear (weight, bias): final ~1 ms into the backward;
- *   group 1 = word_rnn (4 tensors) + embedding: final before the vid_rnn / feat_linear weight-gradient GEMMs.
- * The remaining gradients (vid_rnn, feat_linear) are final when the backward's own stream is. */
+ *   group 0 = out_linear.weight, out_linear.bias: final ~1 ms into the backward (behind the last persistent BPTT launch
+ *             where the schedule has one);
+ *   group 1 = word_rnn.weight_ih, weight_hh, bias_ih, bias_hh + embedding.weight: final before the vid_rnn / feat_linear
+ *             weight-gradient GEMMs.
+ * The promise: every write to a group's tensors that the backward enqueues, on the caller's stream and on the side lane
+ * alike, is ordered before the group's event - the values `stream` sees once the wait completes are the final gradients bit
+ * for bit, under every schedule and option (tests/test_gpu_grad_release.py).  The remaining gradients (vid_rnn, feat_linear)
+ * are final when the backward's own stream is. */
 int s2vt_backward_wait_grads(int32_t group, void* stream);
 /* Order check of that overlap for the last s2vt_train_backward of the plane drivers: how many persistent BPTT launches it
  * enqueued, and how many of them were already enqueued when gradient group 0's event was recorded for the last time.  The two
@@ -553,6 +558,12 @@ int s2vt_graph_stats(int64_t* captures, int64_t* replays);
  * workgroups that each hold `lds_bytes` (<= 160 KB) of LDS and spin for `microseconds` (<= 5 s) - a stand-in for a foreign
  * kernel (an RCCL all-reduce on a communication stream, another tenant of the GPU) sitting on the compute units. */
 int s2vt_test_occupy_cus(int32_t workgroups, int32_t lds_bytes, int64_t microseconds, void* stream);
+/* Test support: while microseconds > 0, every launch the train backward driver issues through the Lane helpers
+ * (psplit, pdual, pgemm, pgemm_tt, colsum_finish) on the selected lanes (bit 0: the caller's stream, bit 1: the side
+ * lane) is preceded on the same stream by one occupy_kernel workgroup (no LDS) that spins for `microseconds`.  It makes a
+ * late producer deterministically late (tests/test_gpu_grad_release.py: a gradient group released before its last write is
+ * then caught on every run).  lanes 0..3, microseconds 0..5e6, else an error; 0 (the default) turns it off and costs nothing. */
+int s2vt_test_lane_delay(int32_t lanes, int64_t microseconds);
 
 /* ---------------------------------------------------------------- live kernel timing (bench.py)
  * When enabled, launch sites bracket kernels of one kind with hipEvents on the launch stream.

@@ -149,6 +149,7 @@ SIGNATURES = {
                                                                                                   c_void_p]),
     "s2vt_pipeline_overlaps": (c_int32, []),
     "s2vt_test_occupy_cus": (c_int32, [c_int32, c_int32, c_int64, c_void_p]),
+    "s2vt_test_lane_delay": (c_int32, [c_int32, c_int64]),
     "s2vt_set_graph_mode": (c_int32, [c_int32]),
     "s2vt_graph_stats": (c_int32, [POINTER(c_int64), POINTER(c_int64)]),
     "s2vt_prof_enable": (c_int32, [c_int32]),

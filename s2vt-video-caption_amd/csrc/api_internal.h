@@ -153,6 +153,17 @@ int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, cons
           RowMap cm, const float* bias, bool acc);
 int pgemm_tt(const Lane& ln, int M, int N, int K, const PB& A, int a_row0, const PB& B, int b_row0, float* C, int64_t ldc, RowMap cm,
              const float* bias, bool acc);
+int lcolsum_finish(const Lane& ln, const float* partial, int nchunks, int cols, float* out, bool accumulate);   // colsum_finish on ln.s
+// Test support (s2vt_test_lane_delay): inside a LaneDelayScope - the train backward drivers, `caller` = their own stream - every
+// launch of the Lane helpers above (and lgemm) on a selected lane (bit 0: the caller's stream, bit 1: the side lane) is preceded
+// on its stream by one occupy_kernel workgroup (no LDS) that spins for g_lane_delay_us.  Off (the default): no launch at all.
+extern int g_lane_delay_lanes;
+extern long long g_lane_delay_us;
+struct LaneDelayScope {
+    explicit LaneDelayScope(hipStream_t caller);
+    ~LaneDelayScope();
+};
+int lane_delay(hipStream_t s);
 
 int seq_fwd_bf16(hipStream_t st, int t0, int t1, int B, int H, float* gx_stash, int n_gx, const float* bias, const PB& wb, const PB& hb,
                  float* h_all, float* c_all);

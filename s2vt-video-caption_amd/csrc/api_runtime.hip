@@ -290,6 +290,7 @@ int handoff(hipStream_t from, hipStream_t to, size_t ev_index) {
 
 int lgemm(const Lane& ln, bool ak, bool bk, int M, int N, int K, const float* A, int64_t lda, RowMap am,
                  const float* B, int64_t ldb, RowMap bm, float* C, int64_t ldc, RowMap cm, const float* bias, bool acc) {
+    if (int rc = lane_delay(ln.s)) return rc;
     ProfScope ps(ln.s, K_GEMM, 1);
     return gemm_f32(ln.s, ak, bk, M, N, K, A, lda, am, B, ldb, bm, C, ldc, cm, bias, acc, ln.gws, ln.gws_floats);
 }
@@ -328,6 +329,14 @@ int s2vt_graph_stats(int64_t* captures, int64_t* replays) {
 
 int s2vt_test_occupy_cus(int32_t workgroups, int32_t lds_bytes, int64_t microseconds, void* stream) {
     return occupy_cus((hipStream_t)stream, workgroups, lds_bytes, microseconds);
+}
+
+int s2vt_test_lane_delay(int32_t lanes, int64_t microseconds) {
+    S2VT_REQUIRE(lanes >= 0 && lanes <= 3 && microseconds >= 0 && microseconds <= 5000000,
+                 "s2vt_test_lane_delay: lanes must be 0..3 and microseconds 0..5000000 (got %d, %lld)", (int)lanes, (long long)microseconds);
+    g_lane_delay_lanes = lanes;
+    g_lane_delay_us = microseconds;
+    return 0;
 }
 
 int s2vt_set_pipeline_block(int32_t steps) {

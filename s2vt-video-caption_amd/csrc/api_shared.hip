@@ -76,8 +76,21 @@ std::vector<int> pipe_bounds(int T, int L, int blk) {
 
 int XP = 3;        // planes per operand of the running plane driver (3 or 1); set by the entry points
 
+int g_lane_delay_lanes = 0;
+long long g_lane_delay_us = 0;
+static thread_local hipStream_t t_delay_caller = nullptr;
+static thread_local bool t_delay_active = false;
+LaneDelayScope::LaneDelayScope(hipStream_t caller) { t_delay_caller = caller; t_delay_active = true; }
+LaneDelayScope::~LaneDelayScope() { t_delay_active = false; t_delay_caller = nullptr; }
+int lane_delay(hipStream_t s) {
+    if (g_lane_delay_us <= 0 || !t_delay_active) return 0;
+    if (!(g_lane_delay_lanes & (s == t_delay_caller ? 1 : 2))) return 0;
+    return occupy_cus(s, 1, 0, g_lane_delay_us);
+}
+
 // rows [r0, r0+rows) of the operand <- planes of in[rows][cols]
 int psplit(const Lane& ln, const PB& dst, int r0, const float* in, int64_t ld, RowMap imap, int rows, int cols) {
+    if (int rc = lane_delay(ln.s)) return rc;
     return split_planes(ln.s, XP, false, in, ld, imap, rows, cols, dst.p + (int64_t)r0 * dst.ld, dst.ld, dst.kpad, rows);
 }
 // one pass over in[rows][cols]: row planes into r (operand rows r0..), transposed planes into t (k range k0..),
@@ -85,6 +98,7 @@ int psplit(const Lane& ln, const PB& dst, int r0, const float* in, int64_t ld, R
 int pdual(const Lane& ln, const float* in, int64_t ld, RowMap imap, int rows, int cols, const PB* r, int r0,
                  const PB* t, int k0, float* colpart) {
     if (!r && !t && !colpart) return 0;          // (bf16 mode with transposed-read GEMMs: the recurrence kernels wrote the rows already)
+    if (int rc = lane_delay(ln.s)) return rc;
     return split_planes_dual(ln.s, XP, in, ld, imap, rows, cols, r ? r->p + (int64_t)r0 * r->ld : nullptr, r ? r->ld : 0,
                              r ? r->kpad : 0, t ? t->p + koff(k0) : nullptr, t ? t->ld : 0, t ? pad64(rows) : 0,
                              colpart);
@@ -92,6 +106,7 @@ int pdual(const Lane& ln, const float* in, int64_t ld, RowMap imap, int rows, in
 // C[M,N] (+)= A[rows a0.., k ka..ka+K) · B[rows b0.., k kb..kb+K)^T
 int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, const PB& B, int b0, int kb, float* C,
                  int64_t ldc, RowMap cm, const float* bias, bool acc) {
+    if (int rc = lane_delay(ln.s)) return rc;
     ProfScope ps(ln.s, cu_plan_cap_current() ? K_GEMM_CORUN : K_GEMM, 1);
     return gemm_bf16_nt(ln.s, XP, M, N, pad64(K), A.p + (int64_t)a0 * A.ld + koff(ka), A.ld,
                         B.p + (int64_t)b0 * B.ld + koff(kb), B.ld, C, ldc, cm, bias, acc, ln.gws, ln.gws_floats);
@@ -103,12 +118,17 @@ int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, cons
 // C[M,N] = A_img[a_row0 .., :M]^T . B_img[b_row0 .., :N] over K image rows (row offsets: multiples of 64)
 int pgemm_tt(const Lane& ln, int M, int N, int K, const PB& A, int a_row0, const PB& B, int b_row0, float* C, int64_t ldc,
                     RowMap cm, const float* bias, bool acc) {
+    if (int rc = lane_delay(ln.s)) return rc;
     ProfScope ps(ln.s, cu_plan_cap_current() ? K_GEMM_CORUN : K_GEMM, 1);
     if (XP == 1)
         return gemm_b1_tt(ln.s, M, N, K, A.p + (int64_t)a_row0 * A.ld, A.ld, B.p + (int64_t)b_row0 * B.ld, B.ld, C, ldc, cm, bias, acc,
                           ln.gws, ln.gws_floats);
     return gemm_x3_tt(ln.s, M, N, K, A.p + (int64_t)a_row0 * A.ld, A.ld, B.p + (int64_t)b_row0 * B.ld, B.ld, C, ldc, cm, bias, acc,
                       ln.gws, ln.gws_floats);
+}
+int lcolsum_finish(const Lane& ln, const float* partial, int nchunks, int cols, float* out, bool accumulate) {
+    if (int rc = lane_delay(ln.s)) return rc;
+    return colsum_finish(ln.s, partial, nchunks, cols, out, accumulate);
 }
 
 // bf16-operand layer forward over steps [t0, t1): hb = bf16 row images of h (time-major, ld = hb.ld), the k-major

@@ -196,6 +196,15 @@ static int masked_logits_planes(const Lane& ln, const TrainWS& w, const PlaneWS&
     return psplit(ln, **a_img, *a_row0, w.dh2dec, H, ID, R, H);
 }
 
+// The part of a graph key that follows the run-time options: the value of EVERY entry of the option table (a schedule option added
+// later is in the key without anyone having to remember it), the thread's CU plan cap and the test hook s2vt_test_lane_delay
+static void key_options(std::vector<uint64_t>& key) {
+    for (int i = 0; i < O_COUNT; ++i) key.push_back((uint64_t)(uint32_t)option(i));
+    key.push_back((uint64_t)(uint32_t)cu_plan_cap_current());
+    key.push_back((uint64_t)g_lane_delay_lanes);
+    key.push_back((uint64_t)g_lane_delay_us);
+}
+
 static int train_forward_x3(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
                             int64_t targets_ld, float* logits, const TrainWS& w, const PlaneWS& q, hipStream_t st,
                             const float* out_mask) {
@@ -413,7 +422,7 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
         if (!corun_k && (rc = pgemm_tt(lb, V, H, R, q.dlog, 0, q.h2decB, 0, g->out_w, H, ID, nullptr, false))) return rc;
         if (!corun_k && ce_pow2 && (rc = scale_by_device_scalar(sx, g->out_w, (int64_t)V * H, w.ce_alpha))) return rc;
     }
-    if ((rc = colsum_finish(sx, w.colsum_c, cdiv(R, 64), V, g->out_b, false))) return rc;
+    if ((rc = lcolsum_finish(lb, w.colsum_c, cdiv(R, 64), V, g->out_b, false))) return rc;
     // (a persistent BPTT re-records "group 0 is final" behind its last launch - no collective may start beside one - so it is not
     // recorded here for those schedules: option cu_reserve counts from the release that holds)
     if (!corun_k && !pbf_bwd && !px3_bwd && (rc = grads_ready(0, sx))) return rc;
@@ -485,7 +494,7 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
                 return r;
             };
             std::vector<size_t> dh1_done((size_t)nb);
-            size_t word_grads_done = 0;
+            size_t word_grads_done = 0, wo_done = 0;
             {
                 CuPlanCap cap(corun_cus);
                 for (int k = nb - 1; k >= 0; --k) {
@@ -508,6 +517,9 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
                 }
                 while (wo_r < R)
                     if ((rc = wo_part())) return rc;
+                // (the parts left over when dW_o has more of them than word_rnn has stages: nothing on the caller's stream waits for
+                // the dh1 events behind them, so group 0's release below waits for this one)
+                if ((rc = event_at(sx, &wo_done))) return rc;
                 // word_rnn's weight gradients (dG2 is complete): beside vid_rnn's stages
                 if ((rc = pgemm_tt(lb, 4 * H, H, (T - 1) * B, q.dg2, B, q.h2r, 0, g->word_w_hh, H, ID, nullptr, false))) return rc;
                 if ((rc = pgemm_tt(lb, 4 * H, H, T * B, q.dg2, 0, q.h1, 0, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
@@ -541,6 +553,7 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
                 }
             }
             bias_chunk = emit ? 32 : 64;
+            if ((rc = wait_for(st, wo_done))) return rc;           // every part of dW_o, including those enqueued after the last stage
             if ((rc = grads_ready(0, st))) return rc;              // (out_linear's gradients: released behind the last persistent launch)
             if ((rc = handoff(st, sx, ev++))) return rc;           // lane B's vid_rnn gradients need dG1
             word_gemms_done = true;
@@ -673,7 +686,7 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
     if ((rc = pgemm_tt(la, 4 * H, H, T * B, q.dg2, 0, q.h1, 0, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
     if ((rc = pgemm_tt(la, 4 * H, E, R, q.dg2, L * B, q.emb, 0, g->word_w_ih, E + H, ID, nullptr, false))) return rc;
     }
-    if ((rc = colsum_finish(st, w.colsum_a, T * B / bias_chunk, 4 * H, g->word_b_ih, false))) return rc;
+    if ((rc = lcolsum_finish(la, w.colsum_a, T * B / bias_chunk, 4 * H, g->word_b_ih, false))) return rc;
     S2VT_HIP(hipMemcpyAsync(g->word_b_hh, g->word_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
     if (demb_done) {
         hipEvent_t e;
@@ -692,14 +705,14 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
     // (one-layer BPTT schedule: the timesteps >= hh1_t0 of this sum ran beside vid_rnn's later stages - the rest is accumulated)
     if ((rc = pgemm_tt(lt, 4 * H, H, ((hh1_t0 > 0 ? hh1_t0 : T) - 1) * B, q.dg1, B, q.h1, 0, g->vid_w_hh, H, ID, nullptr, hh1_t0 > 0))) return rc;
     if ((rc = pgemm_tt(lt, 4 * H, H, L * B, q.dg1, 0, q.x1, 0, g->vid_w_ih, H, ID, nullptr, false))) return rc;
-    if ((rc = colsum_finish(lt.s, w.colsum_b, T * B / bias_chunk, 4 * H, g->vid_b_ih, false))) return rc;
+    if ((rc = lcolsum_finish(lt, w.colsum_b, T * B / bias_chunk, 4 * H, g->vid_b_ih, false))) return rc;
     S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, lt.s));
     // dx1 comes out in BATCH-major row order (the order of feats' rows, whose row planes the forward wrote): dW_f = dx1^T feats
     // reads both transposed - no time-major transposed copy of the features, no transposed dx1 (q.x1 is free: dW_ih1 is done)
     if ((rc = pgemm(lt, L * B, H, 4 * H, q.dg1, 0, 0, q.wih1T, 0, 0, w.dx1, H, perm(B, L), nullptr, false))) return rc;
     if ((rc = pdual(lt, w.dx1, H, ID, L * B, H, &q.x1, 0, nullptr, 0, w.colsum_b))) return rc;
     if ((rc = pgemm_tt(lt, H, F, L * B, q.x1, 0, q.feats, 0, g->feat_w, F, ID, nullptr, false))) return rc;
-    if ((rc = colsum_finish(lt.s, w.colsum_b, L * B / 64, H, g->feat_b, false))) return rc;
+    if ((rc = lcolsum_finish(lt, w.colsum_b, L * B / 64, H, g->feat_b, false))) return rc;
     if (dfeats) {   // rarely requested (nothing reads it in the reference): fp32-MFMA GEMM
         if ((rc = lgemm(lt, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, ID, nullptr, false)))
             return rc;
@@ -813,9 +826,10 @@ static int train_forward_core(const s2vt_dims* d, const s2vt_params* p, const fl
                      workspace_bytes, w.bytes + q.bytes);
         std::vector<uint64_t> key;
         if (graph_on()) {
-            key.reserve(32);
+            key.reserve(64);
             key.push_back(0xF0);
-            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V, gemm_mode(), persist_bits(), pipe_block(), option(O_CU_RESERVE)}) key.push_back((uint64_t)v);
+            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V}) key.push_back((uint64_t)v);
+            key_options(key);
             const float* const* pp = reinterpret_cast<const float* const*>(p);
             for (size_t i = 0; i < sizeof(s2vt_params) / sizeof(void*); ++i) key_ptr(key, pp[i]);
             key_ptr(key, feats); key_ptr(key, targets); key.push_back((uint64_t)targets_ld); key_ptr(key, logits);
@@ -934,9 +948,10 @@ static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const f
                      workspace_bytes, w.bytes + q.bytes);
         std::vector<uint64_t> key;
         if (graph_on()) {
-            key.reserve(48);
+            key.reserve(80);
             key.push_back(0xB0 + (dlog_ready ? 1 : 0));
-            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V, gemm_mode(), persist_bits(), pipe_block(), option(O_CU_RESERVE)}) key.push_back((uint64_t)v);
+            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V}) key.push_back((uint64_t)v);
+            key_options(key);
             const float* const* pp = reinterpret_cast<const float* const*>(p);
             for (size_t i = 0; i < sizeof(s2vt_params) / sizeof(void*); ++i) key_ptr(key, pp[i]);
             float* const* gp = reinterpret_cast<float* const*>(g);
@@ -945,8 +960,10 @@ static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const f
             key_ptr(key, st);
         }
         bool graphed = false;
-        int rc0 = run_graphed(st, key, [&](hipStream_t s_) { return train_backward_x3(d, p, feats, dlogits, g, dfeats, w, q, s_, out_mask, dlog_ready); },
-                              &graphed);
+        int rc0 = run_graphed(st, key, [&](hipStream_t s_) {
+                LaneDelayScope delay(s_);
+                return train_backward_x3(d, p, feats, dlogits, g, dfeats, w, q, s_, out_mask, dlog_ready);
+            }, &graphed);
         if (!rc0 && graphed) {       // (see grads_ready) every gradient group is final behind the graph
             if ((rc0 = grads_ready(0, st))) return rc0;
             if ((rc0 = grads_ready(1, st))) return rc0;
@@ -962,6 +979,7 @@ static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const f
     if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
     const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // word_rnn lane (caller's stream)
     const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // vid_rnn lane
+    LaneDelayScope delay(st);
     size_t ev = 0;
     if ((rc = handoff(st, sx, ev++))) return rc;
     // lane A: gradient into the decode-step hidden states, then word_rnn BPTT       (autograd of S2VTModel.py:80, :77)

@@ -44,6 +44,22 @@ def test_workspace_queries_and_argument_errors(lib):
         capi.check(rc, "s2vt_train_forward")
 
 
+def test_lane_delay_hook_argument_errors(lib):
+    """s2vt_test_lane_delay (test support of tests/test_gpu_grad_release.py): lanes outside 0..3 and delays outside 0..5e6 us are
+    refused with a message and leave the hook as it was; in-range values are accepted, and 0 turns it off.  Host logic only."""
+    from s2vt_video_caption_amd import capi
+    for lanes, us in ((-1, 100), (4, 100), (1, -1), (2, 5000001), (3, 1 << 40)):
+        rc = lib.s2vt_test_lane_delay(lanes, us)
+        assert rc == -1 and b"s2vt_test_lane_delay" in lib.s2vt_last_error(), (lanes, us)
+        with pytest.raises(capi.S2VTHipError):
+            capi.check(rc, "s2vt_test_lane_delay")
+    try:
+        for lanes, us in ((0, 0), (1, 1), (2, 300), (3, 5000000), (0, 5000000)):
+            assert lib.s2vt_test_lane_delay(lanes, us) == 0, (lanes, us)
+    finally:
+        assert lib.s2vt_test_lane_delay(0, 0) == 0
+
+
 def test_option_table_set_query_clamp_and_the_padding_rule(lib):
     """s2vt_set_option / s2vt_option_name on the host alone (no device call behind them): a negative value queries, values are
     clamped to the option's range, an unknown name is refused; s2vt_padded_batch follows pad_min_batch and the arithmetic mode."""
