@@ -16,6 +16,7 @@ from s2vt_video_caption_amd import functional as _F
 from s2vt_video_caption_amd import beam as _beam
 from s2vt_video_caption_amd import gru_functional as _G
 from s2vt_video_caption_amd import stack_functional as _S
+from s2vt_video_caption_amd import sampling as _sampling
 
 
 class S2VT(nn.Module):
@@ -60,20 +61,26 @@ class S2VT(nn.Module):
                     "models are not implemented (the reference's forward fails on a bidirectional model: word_rnn expects "
                     "dim_embed + dim_hid inputs and gets dim_embed + 2*dim_hid)")
 
-    def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30):
+    def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30, temperature=1.0, seed=None):
         """
         :param feats: [B, L, feat_dim]
         :param targets: [B, L-1] word ids (train mode)
         :param mode: 'train' -> logits [B, L-1, V]; 'test' -> greedy ids [B, L-1] (int64);
-                     'beam_search' -> list of id sequences (each starting with <sos>)
+                     'beam_search' -> list of id sequences (each starting with <sos>);
+                     'sample' -> ids [B, L-1] (int64) drawn step by step from softmax(logit / temperature), never stopping at
+                     <eos> (not in the reference; for sequence-level training, utils.RewardCriterion)
+        :param temperature: mode='sample' only: finite and > 0
+        :param seed: mode='sample' only: None draws a 63-bit seed from torch's default generator (torch.manual_seed makes the
+                     run reproducible); an int is used as is.  Same seed, same weights, same clips -> same ids.
         """
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        sample = _sampling.check_sample_args(temperature, seed) if mode == 'sample' else None
         if _G.is_gru_model(self):
-            return self._forward_gru(feats, targets, mode)
+            return self._forward_gru(feats, targets, mode, sample)
         if _S.is_stacked_lstm_model(self):
-            return self._forward_stacked(feats, targets, mode)
+            return self._forward_stacked(feats, targets, mode, sample)
         params = self._hip_params()
         feats = self.feat_drop(feats)                      # identity at the reference's p=0 (S2VTModel.py:52)
         if mode == 'beam_search':
@@ -91,9 +98,11 @@ class S2VT(nn.Module):
             return _F.train_forward(feats, targets, params, grad_sink=_F.grad_sink_for(self), out_mask=out_mask)
         elif mode == 'test':
             return _F.greedy_decode(feats, params, self.sos_ix, owner=self)
+        elif mode == 'sample':
+            return _F.greedy_decode(feats, params, self.sos_ix, owner=self, sample=sample)
         return None                                        # the reference falls through for unknown modes
 
-    def _forward_gru(self, feats, targets, mode):
+    def _forward_gru(self, feats, targets, mode, sample=None):
         """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
@@ -111,9 +120,11 @@ class S2VT(nn.Module):
             return _G.train_forward(self, feats, targets.reshape(targets.shape[0], -1), out_mask=out_mask)
         elif mode == 'test':
             return _G.greedy_decode(self, feats, self.sos_ix)
+        elif mode == 'sample':
+            return _G.greedy_decode(self, feats, self.sos_ix, sample=sample)
         return None
 
-    def _forward_stacked(self, feats, targets, mode):
+    def _forward_stacked(self, feats, targets, mode, sample=None):
         """nn.LSTM with num_layers > 1: the layer-wavefront chain kernels under autograd glue (stack_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a stacked model (num_layers > 1): the reference's BeamSearchNode views the "
@@ -133,6 +144,8 @@ class S2VT(nn.Module):
             return _S.train_forward(self, feats, targets.reshape(targets.shape[0], -1), out_mask=out_mask, rnn_masks=rnn_masks)
         elif mode == 'test':
             return _S.greedy_decode(self, feats, self.sos_ix)
+        elif mode == 'sample':
+            return _S.greedy_decode(self, feats, self.sos_ix, sample=sample)
         return None
 
     @staticmethod

@@ -35,9 +35,10 @@ class Att_Baseline(nn.Module):
         self.att_prev_hid = nn.Linear(dim_hid, dim_hid, bias=True)
         self.att_apply = nn.Linear(dim_hid, 1, bias=False)
 
-    def forward(self, feats, targets=None, mode='train'):
+    def forward(self, feats, targets=None, mode='train', temperature=1.0, seed=None):
         """feats [B, length, dim_feat] (HIP, fp32).  mode 'train': targets [B, length-1] int64 -> logits [B, length-1, vocab]
-        (autograd-connected to every parameter); mode 'test': greedy ids [B, length] int64."""
+        (autograd-connected to every parameter); mode 'test': greedy ids [B, length] int64; mode 'sample': ids [B, length] drawn
+        from softmax(logit / temperature) step by step (seed None: drawn from torch's default generator)."""
         _require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.dim_feat:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.dim_feat, tuple(feats.shape)))
@@ -47,4 +48,7 @@ class Att_Baseline(nn.Module):
             return _A.train_forward(self, feats.float(), targets)
         if mode == 'test':
             return _A.greedy_decode(self, feats.float())
-        raise ValueError("mode must be 'train' or 'test', got %r" % (mode,))
+        if mode == 'sample':
+            from s2vt_video_caption_amd import sampling
+            return _A.greedy_decode(self, feats.float(), sample=sampling.check_sample_args(temperature, seed))
+        raise ValueError("mode must be 'train', 'test' or 'sample', got %r" % (mode,))

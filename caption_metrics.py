@@ -41,7 +41,7 @@ def tokenize(captions):
     return {k: [ptb_tokenize(c["caption"]) for c in v] for k, v in captions.items()}
 
 
-def _ngrams(words, n):
+def ngrams(words, n):
     """Counter over all 1..n-grams of a token list."""
     c = Counter()
     for k in range(1, n + 1):
@@ -69,12 +69,12 @@ def bleu(gts, res, n=4):
     per_id = [[] for _ in range(n)]
     for i in ids:
         hyp = res[i][0].split()
-        hyp_counts = _ngrams(hyp, n)
+        hyp_counts = ngrams(hyp, n)
         ref_max, ref_lens = Counter(), []
         for r in gts[i]:
             rw = r.split()
             ref_lens.append(len(rw))
-            for g, c in _ngrams(rw, n).items():
+            for g, c in ngrams(rw, n).items():
                 if c > ref_max[g]:
                     ref_max[g] = c
         match = [0] * n
@@ -133,42 +133,55 @@ def rouge_l(gts, res, beta=1.2):
     return float(np.mean(scores)), scores
 
 
+def cider_document_frequencies(refs):
+    """(df, log(#ids)) of CIDEr over {id: [n-gram Counter per reference]}: in how many ids' reference sets an n-gram occurs"""
+    df = Counter()
+    for i in refs:
+        df.update(set(g for c in refs[i] for g in c))
+    return df, np.log(float(len(refs)))
+
+
+def cider_vector(counts, df, log_n, n=4):
+    """TF-IDF vectors (one dict per n-gram order), their norms and the scorer's length (the number of bigrams) of one caption"""
+    v = [dict() for _ in range(n)]
+    length = 0
+    for g, tf in counts.items():
+        k = len(g) - 1
+        v[k][g] = float(tf) * (log_n - np.log(max(1.0, df.get(g, 0.0))))
+        if k == 1:
+            length += tf
+    norm = [np.sqrt(sum(w * w for w in d.values())) for d in v]
+    return v, norm, length
+
+
+def cider_of_vectors(hyp, ref_vecs, n=4, sigma=6.0):
+    """CIDEr of one candidate (cider_vector) against its references' vectors: clipped cosine per order, Gaussian length penalty,
+    mean over orders and references, x10"""
+    hv, hn, hl = hyp
+    total = np.zeros(n)
+    for rv, rn, rl in ref_vecs:
+        pen = np.e ** (-(float(hl - rl) ** 2) / (2 * sigma ** 2))
+        for k in range(n):
+            dot = sum(min(w, rv[k].get(g, 0.0)) * rv[k].get(g, 0.0) for g, w in hv[k].items())
+            if hn[k] != 0 and rn[k] != 0:
+                dot /= hn[k] * rn[k]
+            total[k] += dot * pen
+    return np.mean(total) / len(ref_vecs) * 10.0
+
+
 def cider(gts, res, n=4, sigma=6.0):
     """CIDEr: TF-IDF weighted n-gram cosine similarity (document frequency over the reference sets of the corpus,
     idf = log(#ids) - log(max(1, df))), clipped on the candidate side, Gaussian length penalty, averaged over orders and
     references, x10.  The length that enters the penalty is the scorer's (the number of bigrams).  Returns
-    (mean, per-id array)."""
+    (mean, per-id array).  (The pieces are functions of their own: self_critical.CiderRewarder scores single captions with the
+    document frequencies of a fixed corpus.)"""
     ids = _check(gts, res)
-    refs = {i: [_ngrams(r.split(), n) for r in gts[i]] for i in ids}
-    df = Counter()
-    for i in ids:
-        df.update(set(g for c in refs[i] for g in c))
-    log_n = np.log(float(len(ids)))
-
-    def vec(counts):
-        v = [dict() for _ in range(n)]
-        length = 0
-        for g, tf in counts.items():
-            k = len(g) - 1
-            v[k][g] = float(tf) * (log_n - np.log(max(1.0, df.get(g, 0.0))))
-            if k == 1:
-                length += tf
-        norm = [np.sqrt(sum(w * w for w in d.values())) for d in v]
-        return v, norm, length
-
+    refs = {i: [ngrams(r.split(), n) for r in gts[i]] for i in ids}
+    df, log_n = cider_document_frequencies(refs)
     scores = []
     for i in ids:
-        hv, hn, hl = vec(_ngrams(res[i][0].split(), n))
-        total = np.zeros(n)
-        for rc in refs[i]:
-            rv, rn, rl = vec(rc)
-            pen = np.e ** (-(float(hl - rl) ** 2) / (2 * sigma ** 2))
-            for k in range(n):
-                dot = sum(min(w, rv[k].get(g, 0.0)) * rv[k].get(g, 0.0) for g, w in hv[k].items())
-                if hn[k] != 0 and rn[k] != 0:
-                    dot /= hn[k] * rn[k]
-                total[k] += dot * pen
-        scores.append(np.mean(total) / len(refs[i]) * 10.0)
+        hyp = cider_vector(ngrams(res[i][0].split(), n), df, log_n, n)
+        scores.append(cider_of_vectors(hyp, [cider_vector(rc, df, log_n, n) for rc in refs[i]], n, sigma))
     scores = np.array(scores)
     return float(np.mean(scores)), scores
 

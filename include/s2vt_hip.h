@@ -224,6 +224,20 @@ int s2vt_mask_criterion_forward(int32_t B, int32_t Lm1, int32_t V, const float* 
 int s2vt_mask_criterion_backward(int32_t B, int32_t Lm1, const float* mask, int64_t mask_ld, const float* out3, const float* gout,
                                  float* g_ce, void* stream);
 
+/* Reward-weighted CE (utils.RewardCriterion; sequence-level training on sampled captions):
+ *     loss = sum_i w_i * (lse_i - logit_i[target_i]) / norm,     norm = max(number of i with w_i != 0, 1)
+ * over the B*(L-1) rows, w = weight[:, 1:] (fp32 [B, L], row stride weight_ld, read like the mask above; any sign).  The
+ * normaliser is the number of tokens that carry a weight - with a 0/1 mask the masked mean, with self-critical advantages the mean
+ * over the sampled tokens up to <eos> - and an all-zero weight gives 0, not NaN.  out2 = {loss, norm} (two device floats); lse and
+ * rowloss as for s2vt_mean_ce_forward; target ids outside [0, V) are reported as S2VT_ERR_INDEX the same way.  Fixed summation
+ * order.  No gradient flows to the weight. */
+int s2vt_weighted_ce_forward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target, int64_t target_ld,
+                             const float* weight, int64_t weight_ld, float* lse, float* rowloss, float* out2, void* stream);
+/* dlogits_i = w_i * (softmax(logits_i) - onehot(target_i)) * gout[0] / out2[1]  (rows with w_i == 0: zeros). */
+int s2vt_weighted_ce_backward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target, int64_t target_ld,
+                              const float* weight, int64_t weight_ld, const float* lse, const float* out2, const float* gout,
+                              float* dlogits, void* stream);
+
 /* The same gradient handed to s2vt_train_backward WITHOUT an fp32 dlogits tensor (utils.py:22 under loss.backward(), train.py:124):
  * evaluates (softmax(logits) - onehot(target)) * gout[0] / (B*(L-1)) inside the plane-split pass of the TRAIN workspace the
  * logits came from - the operand planes and bias-gradient partial sums the backward's first kernel would otherwise produce from
@@ -469,6 +483,33 @@ int s2vt_decode_step_argmax(int32_t B, int32_t H, int32_t V, const float* h, con
 size_t s2vt_decode_step_argmax_x3_workspace_bytes(int32_t B, int32_t H, int32_t V);
 int s2vt_decode_step_argmax_x3(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
                                unsigned long long* packed, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------- sampled decoding (S2VT.forward(mode='sample'))
+ * A draw from softmax(logit / temperature) per decode step instead of the arg-max, by Gumbel-max: the arg-max kernels above with
+ * score = logit * (1 / temperature) + g ahead of their packed max (lowest index wins ties; the packed word's high half is the
+ * ordered SCORE).  g is counter-based noise, defined once (csrc/philox.h; s2vt-video-caption_amd/sampling.py restates it in numpy):
+ *     x = word (v % 4) of Philox4x32-10(counter = (v / 4, batch row, decode step, 0x47554D42), key = (seed low, seed high 32 bits))
+ *     u = ((x >> 9) + 0.5) * 2^-23        g = -log(-log(u))
+ * for vocabulary index v.  The noise of an element depends on (seed, decode step, batch row, v) and on nothing else: not on the
+ * batch padding, the tile shape, the schedule (option "decode_fused"), the gemm mode or which kernel ran - row b of a batch of 10
+ * and row b of the same clips padded to 64 rows get the same noise.  (The LOGITS of the kernels differ by rounding, so two paths
+ * may draw differently where two scores are closer than that.)  temperature must be > 0 and finite with a finite reciprocal (the kernels multiply by
+ * 1 / temperature: fp32 subnormals are refused); every argument is checked on the host before any device call.
+ * s2vt_decode_step_sample[_x3]: one step; `step` = the decode step, row0 = the batch row of h's row 0.  packed as for the arg-max. */
+int s2vt_decode_step_sample(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out, float temperature,
+                            uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, void* stream);
+size_t s2vt_decode_step_sample_x3_workspace_bytes(int32_t B, int32_t H, int32_t V);
+int s2vt_decode_step_sample_x3(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out, float temperature,
+                               uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/* The whole decode: s2vt_greedy_decode[_cached] with a draw at every step (ids int64 [B, L-1], never stops at <eos>).  Same
+ * workspace (s2vt_decode_workspace_bytes), same weight-image cache: a cache filled by a greedy call serves a sampling call and the
+ * reverse. */
+int s2vt_sample_decode(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature, uint64_t seed,
+                       int64_t* ids, void* workspace, size_t workspace_bytes, void* stream);
+int s2vt_sample_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature,
+                              uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                              int32_t cache_valid, void* stream);
 
 /* ---------------------------------------------------------------- run-time options
  * ONE table holds every switch of the library (csrc/options.hip).  The first read of an option takes S2VT_<NAME> (upper case)

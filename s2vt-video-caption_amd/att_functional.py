@@ -155,8 +155,9 @@ def train_forward(model, feats, targets):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats):
-    """mode='test' (attention_baseline.py:85-104): ids [B, L] - L steps, the first input is <sos>."""
+def greedy_decode(model, feats, sample=None):
+    """mode='test' (attention_baseline.py:85-104): ids [B, L] - L steps, the first input is <sos>.  sample = (temperature, seed):
+    mode='sample', a draw from softmax(logit / temperature) per step (ops.decode_step_sample) instead of the arg-max."""
     B, L, _ = feats.shape
     H, E = model.dim_hid, model.dim_embed
     ctxv = context_of(model, encode(model, feats))
@@ -168,10 +169,11 @@ def greedy_decode(model, feats):
     tok = torch.full((B,), int(model.sos_ix), dtype=torch.long, device=feats.device)
     h = c = None
     preds = []
-    for _ in range(L):
+    for i in range(L):
         gx = ops.gemm(model.embedding(tok).contiguous(), w_e) + gctx
         h, c = ops.lstm_step_fwd(gx, None, w_hh, h, c)
-        tok = ops.decode_step_argmax(h, wo, bo)
+        tok = ops.decode_step_argmax(h, wo, bo) if sample is None else \
+            ops.decode_step_sample(h, wo, bo, temperature=sample[0], seed=sample[1], step=i)
         preds.append(tok)
     capi.check_async_error(wait=False)
     return torch.stack(preds, dim=1)

@@ -6,7 +6,7 @@ compute path fails loudly.
 """
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # S2VT_LIB: another build of the library (A/B timing of two builds on one GPU box: tools/bench_gemm_shapes.py); never set in production
@@ -135,6 +135,19 @@ SIGNATURES = {
     "s2vt_decode_step_argmax": (c_int32, [c_int32, c_int32, c_int32] + [c_void_p] * 5),
     "s2vt_decode_step_argmax_x3_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_decode_step_argmax_x3": (c_int32, [c_int32, c_int32, c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "s2vt_decode_step_sample": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_uint64, c_int32, c_int32,
+                                          c_void_p, c_void_p]),
+    "s2vt_decode_step_sample_x3_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_decode_step_sample_x3": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_float, c_uint64, c_int32,
+                                             c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "s2vt_sample_decode": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_float, c_uint64, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    "s2vt_sample_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_float, c_uint64, c_void_p, c_void_p,
+                                            c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_weighted_ce_forward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                           c_void_p, c_void_p, c_void_p]),
+    "s2vt_weighted_ce_backward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "s2vt_mean_ce_backward_fused": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
     "s2vt_set_option": (c_int32, [c_char_p, c_int32]),

@@ -142,7 +142,7 @@ struct EncodeOut { float *vid_h, *vid_c, *word_h, *word_c; float* gx_dec; int de
                                      // optional: word_rnn's vid_out gate input (+ biases) of the first `depth` decode steps [depth][B][4H]
 static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc = nullptr);
+                              void* stream, const EncodeOut* enc = nullptr, const GumbelArgs* smp = nullptr);
 // schedule of the 79 token-dependent decode steps on the plane path: 1 = fused (the next step's recurrent GEMM inside the
 // argmax launch + a cell-update launch), 0 = a step kernel and an argmax kernel per step, batch halves as two chains
 static int decode_schedule() { return option(O_DECODE_FUSED); }
@@ -171,13 +171,13 @@ int s2vt_decode_encode_cached(const s2vt_dims* d, const s2vt_params* p, const fl
 }
 static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc);
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp);
 static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc) {
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp) {
     S2VT_REQUIRE(dims_ok(d) && p && feats && (ids || enc) && workspace, "s2vt_greedy_decode: null/invalid argument");
     if (!batch_padded(*d, enc != nullptr))
-        return greedy_decode_core(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream, enc);
+        return greedy_decode_core(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream, enc, smp);
     const s2vt_dims dp = padded_dims(*d);
     const size_t core = decode_core_bytes(dp);
     const DecodePad s = carve_decode_pad(*d, dp, reinterpret_cast<char*>(workspace) + core);
@@ -188,12 +188,12 @@ static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const fl
     S2VT_HIP(hipMemcpyAsync(s.feats, feats, B * L * F * sizeof(float), hipMemcpyDeviceToDevice, st));
     if ((rc = fill_zero(st, s.feats + B * L * F, (Bp - B) * L * F * sizeof(float)))) return rc;
     if (!enc) {
-        if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, s.ids, workspace, core, cache, cache_bytes, cache_valid, stream, nullptr))) return rc;
+        if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, s.ids, workspace, core, cache, cache_bytes, cache_valid, stream, nullptr, smp))) return rc;
         S2VT_HIP(hipMemcpyAsync(ids, s.ids, B * (L - 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         return 0;
     }
     const EncodeOut pe{s.states, s.states + Bp * H, s.states + 2 * Bp * H, s.states + 3 * Bp * H, enc->depth > 0 ? s.gx_dec : nullptr, enc->depth};
-    if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, nullptr, workspace, core, cache, cache_bytes, cache_valid, stream, &pe))) return rc;
+    if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, nullptr, workspace, core, cache, cache_bytes, cache_valid, stream, &pe, nullptr))) return rc;
     float* outs[4] = {enc->vid_h, enc->vid_c, enc->word_h, enc->word_c};
     for (int k = 0; k < 4; ++k)
         S2VT_HIP(hipMemcpyAsync(outs[k], s.states + (size_t)k * Bp * H, B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -204,7 +204,7 @@ static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const fl
 }
 static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc) {
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp) {
     S2VT_REQUIRE(dims_ok(d) && p && feats && (ids || enc) && workspace, "s2vt_greedy_decode: null/invalid argument");
     S2VT_REQUIRE(sos_ix >= 0 && sos_ix < d->V, "s2vt_greedy_decode: sos_ix %d outside vocabulary %d", sos_ix, d->V);
     const DecodeWS w = carve_decode(*d, workspace);
@@ -307,6 +307,14 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
         if (t >= L && ax3) { a.h_planes = w.ph2.p + (int64_t)b0 * w.ph2.ld; a.ldhp = w.ph2.ld; }
         return a;
     };
+    // mode='sample' (smp != null): the launch of decode step t - L over the batch rows from b0 draws instead of taking the arg-max
+    GumbelArgs gcur;
+    auto gumbel_at = [&](int t, int b0) -> const GumbelArgs* {
+        if (!smp) return nullptr;
+        gcur = *smp;
+        gcur.step = (uint32_t)(t - L); gcur.row0 = (uint32_t)b0;
+        return &gcur;
+    };
     auto word_step = [&](hipStream_t s, int t, const float* hprev, const float* cprev, int b0 = 0, int nb = -1) -> int {
         int r;
         if (nb < 0) nb = B;
@@ -326,7 +334,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
             ax.bias = p->out_b;
             ax.packed = w.packed + (int64_t)(t - L) * B + b0;
             ax.dbg = 0; ax.stamps = nullptr;
-            if ((r = logits_argmax_x3(s, ax))) return r;
+            if ((r = logits_argmax_x3(s, ax, gumbel_at(t, b0)))) return r;
         } else if (t >= L) {  // the same on the fp32-input MFMA (lstm.hip), for batches the plane path does not take
             ProfScope ps(s, K_ARGMAX, 1);
             LogitsArgmaxArgs la2;
@@ -335,7 +343,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
             la2.w_out = p->out_w; la2.ldw = H; la2.b_out = p->out_b;
             la2.packed = w.packed + (int64_t)(t - L) * B + b0;
             la2.stamps = nullptr;
-            if ((r = logits_argmax(s, la2))) return r;
+            if ((r = logits_argmax(s, la2, gumbel_at(t, b0)))) return r;
         }
         return 0;
     };
@@ -435,7 +443,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
                 ax.packed = w.packed + (int64_t)(with_logits ? t - L : 0) * B;
                 if (with_z) { ax.W2 = kc.whh.p; ax.ldw2 = kc.whh.ld; ax.M2 = 4 * H; ax.z = w.zbuf; ax.ldz = 4 * (int64_t)H; }
                 ax.v_off = with_logits ? 0 : cdiv(V, 64);
-                return logits_argmax_x3(st, ax);
+                return logits_argmax_x3(st, ax, with_logits ? gumbel_at(t, 0) : nullptr);
             };
             // h_{L-1} of the encode phase as blocked planes, then z(L) alone
             if ((rc = handoff(sx, st, ev++))) return rc;
@@ -503,8 +511,44 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
     return post_async_error(st, w.err);
 }
 
+// ------------------------------------------------------------------ sampled decode (mode='sample')
+// The greedy drivers with the sampling variants of their arg-max launches: same workspace, same weight-image cache.
+// finite and > 0 with a finite reciprocal - what the kernels multiply by: NaN fails the compares, inf gives 0, a subnormal gives inf
+static bool temperature_ok(float t) { const float r = 1.0f / t; return t > 0.f && r > 0.f && r <= 3.4028234e38f; }
+static GumbelArgs gumbel_args(float temperature, uint64_t seed, uint32_t step, uint32_t row0, uint32_t rows) {
+    return GumbelArgs{1.0f / temperature, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), step, row0, rows};
+}
+int s2vt_sample_decode(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature, uint64_t seed,
+                       int64_t* ids, void* workspace, size_t workspace_bytes, void* stream) {
+    S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace, "s2vt_sample_decode: null/invalid argument");
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_sample_decode: temperature and 1 / temperature must be finite and > 0 (got %g)", (double)temperature);
+    const GumbelArgs g = gumbel_args(temperature, seed, 0, 0, (uint32_t)d->B);
+    return greedy_decode_impl(d, p, feats, sos_ix, ids, workspace, workspace_bytes, nullptr, 0, false, stream, nullptr, &g);
+}
+int s2vt_sample_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature,
+                              uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                              int32_t cache_valid, void* stream) {
+    S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace && cache, "s2vt_sample_decode_cached: null/invalid argument");
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_sample_decode_cached: temperature and 1 / temperature must be finite and > 0 (got %g)", (double)temperature);
+    const GumbelArgs g = gumbel_args(temperature, seed, 0, 0, (uint32_t)d->B);
+    return greedy_decode_impl(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid != 0, stream, nullptr, &g);
+}
+
+static int decode_step_argmax_impl(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
+                                   unsigned long long* packed, void* stream, const GumbelArgs* smp);
+int s2vt_decode_step_sample(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out, float temperature,
+                            uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, void* stream) {
+    S2VT_REQUIRE(B > 0 && H > 0 && V > 0 && h && w_out && packed && step >= 0 && row0 >= 0, "s2vt_decode_step_sample: bad arguments");
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_decode_step_sample: temperature and 1 / temperature must be finite and > 0 (got %g)", (double)temperature);
+    const GumbelArgs g = gumbel_args(temperature, seed, (uint32_t)step, (uint32_t)row0, (uint32_t)row0 + (uint32_t)B);
+    return decode_step_argmax_impl(B, H, V, h, w_out, b_out, packed, stream, &g);
+}
 int s2vt_decode_step_argmax(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
                             unsigned long long* packed, void* stream) {
+    return decode_step_argmax_impl(B, H, V, h, w_out, b_out, packed, stream, nullptr);
+}
+static int decode_step_argmax_impl(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
+                                   unsigned long long* packed, void* stream, const GumbelArgs* smp) {
     LogitsArgmaxArgs la;
     la.B = B; la.H = H; la.V = V; la.h = h; la.ldh = H; la.w_out = w_out; la.ldw = H; la.b_out = b_out;
     la.packed = packed;
@@ -513,7 +557,7 @@ int s2vt_decode_step_argmax(int32_t B, int32_t H, int32_t V, const float* h, con
     la.stamps = g_xstamps;
 #endif
     ProfScope ps((hipStream_t)stream, K_ARGMAX, 1);
-    return logits_argmax((hipStream_t)stream, la);
+    return logits_argmax((hipStream_t)stream, la, smp);
 }
 
 // The same decode step on the bf16 matrix cores (argmax_x3.hip): both operands are split into blocked 3-plane images in the
@@ -525,10 +569,31 @@ static size_t argmax_x3_ws_bytes(int B, int H, int V) {
 size_t s2vt_decode_step_argmax_x3_workspace_bytes(int32_t B, int32_t H, int32_t V) {
     return (B > 0 && H > 0 && V > 0) ? argmax_x3_ws_bytes(B, H, V) : 0;
 }
+static int decode_step_argmax_x3_impl(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
+                                      unsigned long long* packed, void* workspace, size_t workspace_bytes, void* stream,
+                                      const GumbelArgs* smp);
 int s2vt_decode_step_argmax_x3(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
                                unsigned long long* packed, void* workspace, size_t workspace_bytes, void* stream) {
     S2VT_REQUIRE(B > 0 && H > 0 && V > 0 && h && w_out && packed && workspace, "s2vt_decode_step_argmax_x3: bad arguments");
     S2VT_REQUIRE(workspace_bytes >= argmax_x3_ws_bytes(B, H, V), "s2vt_decode_step_argmax_x3: workspace too small");
+    return decode_step_argmax_x3_impl(B, H, V, h, w_out, b_out, packed, workspace, workspace_bytes, stream, nullptr);
+}
+size_t s2vt_decode_step_sample_x3_workspace_bytes(int32_t B, int32_t H, int32_t V) {
+    return s2vt_decode_step_argmax_x3_workspace_bytes(B, H, V);
+}
+int s2vt_decode_step_sample_x3(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out, float temperature,
+                               uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+    S2VT_REQUIRE(B > 0 && H > 0 && V > 0 && h && w_out && packed && workspace && step >= 0 && row0 >= 0,
+                 "s2vt_decode_step_sample_x3: bad arguments");
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_decode_step_sample_x3: temperature and 1 / temperature must be finite and > 0 (got %g)", (double)temperature);
+    S2VT_REQUIRE(workspace_bytes >= argmax_x3_ws_bytes(B, H, V), "s2vt_decode_step_sample_x3: workspace too small");
+    const GumbelArgs g = gumbel_args(temperature, seed, (uint32_t)step, (uint32_t)row0, (uint32_t)row0 + (uint32_t)B);
+    return decode_step_argmax_x3_impl(B, H, V, h, w_out, b_out, packed, workspace, workspace_bytes, stream, &g);
+}
+static int decode_step_argmax_x3_impl(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,
+                                      unsigned long long* packed, void* workspace, size_t workspace_bytes, void* stream,
+                                      const GumbelArgs* smp) {
     hipStream_t st = (hipStream_t)stream;
     const int kp = pad64(H);
     Carver c{reinterpret_cast<char*>(workspace), 0, 0};
@@ -550,7 +615,7 @@ int s2vt_decode_step_argmax_x3(int32_t B, int32_t H, int32_t V, const float* h, 
     ax.stamps = g_xstamps;
 #endif
     ProfScope ps(st, K_ARGMAX, 1);
-    return logits_argmax_x3(st, ax);
+    return logits_argmax_x3(st, ax, smp);
 }
 
 

@@ -63,6 +63,35 @@ int s2vt_mask_criterion_backward(int32_t B, int32_t Lm1, const float* mask, int6
     return mask_criterion_bwd((hipStream_t)stream, mask, mask_ld, (int64_t)B * Lm1, Lm1, out3, gout, g_ce);
 }
 
+// RewardCriterion.forward (utils.py of this repository; the reference has no such loss): the per-row CE kernel, then one workgroup
+// that weights the rows with weight[:, 1:] and divides by the number of non-zero weights.  out2 = {loss, norm}.
+int s2vt_weighted_ce_forward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target, int64_t target_ld,
+                             const float* weight, int64_t weight_ld, float* lse, float* rowloss, float* out2, void* stream) {
+    S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0 && target_ld >= Lm1 + 1 && weight_ld >= Lm1 + 1, "s2vt_weighted_ce_forward: bad dims");
+    S2VT_REQUIRE(logits && target && weight && lse && rowloss && out2, "s2vt_weighted_ce_forward: null argument");
+    hipStream_t st = (hipStream_t)stream;
+    int* flags = nullptr;
+    int rc;
+    if ((rc = device_flags(&flags))) return rc;
+    const int rc0 = poll_async_error(false);
+    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    {
+        ProfScope ps(st, K_CE, 1);
+        if ((rc = weighted_ce_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, weight, weight_ld, lse, rowloss, out2, flags)))
+            return rc;
+    }
+    return rc0 ? rc0 : post_async_error(st, flags, 2);
+}
+int s2vt_weighted_ce_backward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target, int64_t target_ld,
+                              const float* weight, int64_t weight_ld, const float* lse, const float* out2, const float* gout,
+                              float* dlogits, void* stream) {
+    S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0 && target_ld >= Lm1 + 1 && weight_ld >= Lm1 + 1, "s2vt_weighted_ce_backward: bad dims");
+    S2VT_REQUIRE(logits && target && weight && lse && out2 && gout && dlogits, "s2vt_weighted_ce_backward: null argument");
+    ProfScope ps((hipStream_t)stream, K_CE, 1);
+    return weighted_ce_bwd((hipStream_t)stream, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, weight, weight_ld, lse, out2, gout,
+                           dlogits);
+}
+
 // ------------------------------------------------------------------ per-op entry points
 int s2vt_gemm_f32(int32_t a_kmajor, int32_t b_kmajor, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda,
                   const float* B, int64_t ldb, float* C, int64_t ldc, const float* bias, int32_t accumulate,

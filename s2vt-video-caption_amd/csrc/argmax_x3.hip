@@ -47,8 +47,10 @@ __device__ __forceinline__ uint32_t ax_ordered_bits(float x) {
 #define AX_DBG(P) 0
 #endif
 
-template <int NB>
-__global__ __launch_bounds__(256) void logits_argmax_x3_kernel(ArgmaxX3Args p) {
+// SAMPLE: score = logit * inv_temperature + Gumbel noise in the epilogue (philox.h) - a draw from softmax(logit / temperature)
+// instead of the arg-max.  A compile-time variant: the greedy instantiations keep their code and registers.
+template <int NB, bool SAMPLE = false>
+__global__ __launch_bounds__(256) void logits_argmax_x3_kernel(ArgmaxX3Args p, GumbelArgs ga) {
     constexpr int NSEG = 1 + NB;                       // row-block segments of a stage: W_o block, then the h blocks
     constexpr int STAGE = NSEG * AX_SEG;
     constexpr int NPIECE = NSEG * 12;                  // 1-KB pieces per stage
@@ -255,11 +257,25 @@ __global__ __launch_bounds__(256) void logits_argmax_x3_kernel(ArgmaxX3Args p) {
     for (int ni = 0; ni < NB; ++ni) {
         const int col = ((NB == 2) ? wn * 64 + ni * 32 : wn * 32) + li;
         unsigned long long best = 0ull;
+        // (a lane's rows m_base + 8 q + (0..3) are four consecutive vocabulary indices from a multiple of 4: one Philox block
+        // per q and batch column; columns of the batch padding - the tile's and the driver's - generate no noise: their plain
+        // arg-max keeps the token of a pad row inside the vocabulary, and nobody reads it)
+        float gn[4][4];
+        if constexpr (SAMPLE) {
+            const int b = bt * 64 * NB + col;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) gn[q][e] = 0.f;
+                if (b < p.B && ga.row0 + (uint32_t)b < ga.rows && m_base + 8 * q < p.V) gumbel4(ga, (uint32_t)(m_base + 8 * q) >> 2, ga.row0 + (uint32_t)b, gn[q]);
+            }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int m = m_base + (r & 3) + 8 * (r >> 2);
             if (m < p.V) {
-                const float v = acc[ni][r] + bv[r >> 2][r & 3];
+                float v = acc[ni][r] + bv[r >> 2][r & 3];
+                if constexpr (SAMPLE) v = v * ga.inv_temperature + gn[r >> 2][r & 3];
                 const unsigned long long key =
                     ((unsigned long long)ax_ordered_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)m);
                 best = key > best ? key : best;
@@ -279,7 +295,7 @@ __global__ __launch_bounds__(256) void logits_argmax_x3_kernel(ArgmaxX3Args p) {
     XSTAMP(p.stamps, xrec, 6);
 }
 
-int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a) {
+int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a, const GumbelArgs* sample) {
     S2VT_REQUIRE(a.B > 0 && a.V > 0 && a.K > 0 && a.K % 64 == 0 && a.W && a.Hp && a.packed, "logits_argmax_x3: bad arguments");
     S2VT_REQUIRE(a.ldw >= 3 * (int64_t)a.K && a.ldh >= 3 * (int64_t)a.K && a.ldw % 8 == 0 && a.ldh % 8 == 0 &&
                      (reinterpret_cast<uintptr_t>(a.W) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.Hp) & 15) == 0,
@@ -290,10 +306,13 @@ int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a) {
     S2VT_REQUIRE(a.v_off == 0 || (a.v_off == cdiv(a.V, 64) && a.M2 > 0), "logits_argmax_x3: v_off is 0 or every vocabulary block");
     const int vblocks = cdiv(a.V, 64) - a.v_off + cdiv(a.M2, 64);
     ArgmaxX3Args b = a;
+    const GumbelArgs ga = sample ? *sample : GumbelArgs{1.f, 0u, 0u, 0u, 0u, 0u};
     if (a.B > 64) {
-        hipLaunchKernelGGL(logits_argmax_x3_kernel<2>, dim3(vblocks, cdiv(a.B, 128)), dim3(256), 0, stream, b);
+        if (sample) hipLaunchKernelGGL((logits_argmax_x3_kernel<2, true>), dim3(vblocks, cdiv(a.B, 128)), dim3(256), 0, stream, b, ga);
+        else hipLaunchKernelGGL((logits_argmax_x3_kernel<2>), dim3(vblocks, cdiv(a.B, 128)), dim3(256), 0, stream, b, ga);
     } else {
-        hipLaunchKernelGGL(logits_argmax_x3_kernel<1>, dim3(vblocks, 1), dim3(256), 0, stream, b);
+        if (sample) hipLaunchKernelGGL((logits_argmax_x3_kernel<1, true>), dim3(vblocks, 1), dim3(256), 0, stream, b, ga);
+        else hipLaunchKernelGGL((logits_argmax_x3_kernel<1>), dim3(vblocks, 1), dim3(256), 0, stream, b, ga);
     }
     S2VT_LAUNCH_CHECK("logits_argmax_x3_kernel");
     return 0;

@@ -210,6 +210,77 @@ int mean_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, const i
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- reward-weighted CE (utils.RewardCriterion)
+// loss = sum_r w_r * (lse_r - logit_r[target_r]) / norm,  w_r = weight[b][j + 1] of row r = b * Lm1 + j (read at [:, 1:] like the
+// mask above), norm = max(number of rows with w_r != 0, 1): the mean over the tokens that carry a weight - a self-critical
+// advantage of either sign, or a 0/1 padding mask - and 0 (not NaN) when none does.  out2 = {loss, norm}.  The per-row kernel is
+// the mean CE's; ONE workgroup sums in a fixed order (thread strips, wave butterfly, four waves in order): deterministic.
+__global__ __launch_bounds__(256) void weighted_ce_fwd_kernel(const float* rowloss, int64_t rows, const float* weight, int64_t ldw,
+                                                              int Lm1, float* out) {
+    __shared__ float sred[4];
+    const int tid = threadIdx.x;
+    float num = 0.f, cnt = 0.f;
+    for (int64_t r = tid; r < rows; r += 256) {
+        const float w = weight[(r / Lm1) * ldw + (r % Lm1) + 1];
+        if (w != 0.f) { num += w * rowloss[r]; cnt += 1.f; }       // (a zero weight drops the row even where its loss is inf)
+    }
+    num = block_sum_256(num, sred);
+    cnt = block_sum_256(cnt, sred);                                // (integers below 2^24: exact)
+    if (tid == 0) {
+        const float norm = fmaxf(cnt, 1.f);
+        out[0] = num / norm; out[1] = norm;
+    }
+}
+// dlogits[r][v] = w_r * (exp(logit - lse_r) - [v == target_r]) * gout / norm; rows without a weight are written as zeros
+__global__ __launch_bounds__(256) void weighted_ce_bwd_kernel(const float* logits, int V, const int64_t* target, int Lm1, int64_t ldt,
+                                                              const float* weight, int64_t ldw, const float* lse, const float* fwd_out,
+                                                              const float* gout, float* dlogits) {
+    const int64_t r = blockIdx.x;
+    const float* row = logits + r * V;
+    float* drow = dlogits + r * V;
+    const float w = weight[(r / Lm1) * ldw + (r % Lm1) + 1];
+    const int tid = threadIdx.x;
+    if (w == 0.f) {
+        for (int c = tid; c < V; c += 256) drow[c] = 0.f;
+        return;
+    }
+    const float l = lse[r];
+    const float scale = w * (gout[0] / fwd_out[1]);
+    int64_t t = row_target(target, r, Lm1, ldt);
+    t = t < 0 ? 0 : (t >= V ? V - 1 : t);
+    const bool vec = (V % 4 == 0) && ((reinterpret_cast<uintptr_t>(row) & 15) == 0) &&
+                     ((reinterpret_cast<uintptr_t>(drow) & 15) == 0);
+    if (vec) {
+        for (int c = tid * 4; c < V; c += 1024) {
+            const f32x4 v = *reinterpret_cast<const f32x4*>(row + c);
+            f32x4 d;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = (expf(v[j] - l) - ((c + j) == t ? 1.f : 0.f)) * scale;
+            *reinterpret_cast<f32x4*>(drow + c) = d;
+        }
+    } else {
+        for (int c = tid; c < V; c += 256) drow[c] = (expf(row[c] - l) - (c == t ? 1.f : 0.f)) * scale;
+    }
+}
+
+int weighted_ce_fwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
+                    const float* weight, int64_t ldw, float* lse, float* rowloss, float* out2, int* err_flag) {
+    S2VT_REQUIRE(rows > 0 && V > 0 && logits && target && weight && lse && rowloss && out2, "weighted_ce_fwd: bad arguments");
+    hipLaunchKernelGGL(ce_row_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, V, target, Lm1, ldt, lse, rowloss, err_flag);
+    S2VT_LAUNCH_CHECK("ce_row_kernel");
+    hipLaunchKernelGGL(weighted_ce_fwd_kernel, dim3(1), dim3(256), 0, s, rowloss, rows, weight, ldw, Lm1, out2);
+    S2VT_LAUNCH_CHECK("weighted_ce_fwd_kernel");
+    return 0;
+}
+int weighted_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
+                    const float* weight, int64_t ldw, const float* lse, const float* fwd_out, const float* gout, float* dlogits) {
+    S2VT_REQUIRE(rows > 0 && V > 0 && logits && target && weight && lse && fwd_out && gout && dlogits, "weighted_ce_bwd: bad arguments");
+    hipLaunchKernelGGL(weighted_ce_bwd_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, V, target, Lm1, ldt, weight, ldw, lse,
+                       fwd_out, gout, dlogits);
+    S2VT_LAUNCH_CHECK("weighted_ce_bwd_kernel");
+    return 0;
+}
+
 
 // ---------------------------------------------------------------------------------- beam-search fan-out
 // Per logits row: log_softmax (S2VTModel.py:214) and the 20 most probable tokens with their log-probs, returned in

@@ -1,6 +1,7 @@
 // Internal launch interface between the HIP kernels and the C-ABI drivers (api.hip).
 #pragma once
 #include "common.h"
+#include "philox.h"
 
 namespace s2vt {
 
@@ -312,7 +313,8 @@ struct LogitsArgmaxArgs {
     unsigned long long* packed;              // [B] zero-initialised; atomicMax of (ordered logit << 32 | ~index)
     unsigned long long* stamps;              // timing experiments only (experiment.h); null in the product
 };
-int logits_argmax(hipStream_t stream, const LogitsArgmaxArgs& a);
+// sample != null: a draw from softmax(logit / temperature) by Gumbel-max instead of the arg-max (philox.h)
+int logits_argmax(hipStream_t stream, const LogitsArgmaxArgs& a, const GumbelArgs* sample = nullptr);
 
 // ---- argmax_x3.hip: the same decode step on the bf16 matrix cores (operands as blocked 3-plane images, split.hip)
 struct ArgmaxX3Args {
@@ -331,7 +333,7 @@ struct ArgmaxX3Args {
     int dbg;                                        // timing experiments only (S2VT_AX_DBG): 0 in the product
     unsigned long long* stamps;                     // timing experiments only (experiment.h); null in the product
 };
-int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a);
+int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a, const GumbelArgs* sample = nullptr);
 
 // ---- misc.hip
 int add_vectors(hipStream_t s, const float* a, const float* b, float* out, int n);
@@ -364,5 +366,10 @@ int mask_criterion_fwd(hipStream_t s, const float* logits, int64_t rows, int V, 
                        const float* mask, int64_t ldm, float* lse, float* rowloss, float* out3, int* err_flag);
 int mask_criterion_bwd(hipStream_t s, const float* mask, int64_t ldm, int64_t rows, int Lm1, const float* fwd_out, const float* gout,
                        float* g_ce);
+// reward-weighted CE (utils.RewardCriterion): out2 = {sum_r w_r * ce_r / norm, norm = max(#rows with w_r != 0, 1)}
+int weighted_ce_fwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
+                    const float* weight, int64_t ldw, float* lse, float* rowloss, float* out2, int* err_flag);
+int weighted_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
+                    const float* weight, int64_t ldw, const float* lse, const float* fwd_out, const float* gout, float* dlogits);
 
 }  // namespace s2vt

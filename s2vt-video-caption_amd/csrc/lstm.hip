@@ -397,8 +397,11 @@ __device__ __forceinline__ uint32_t ordered_bits(float x) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-template <int MT, int NT, bool VEC, int NWAVE>
-__global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgmaxArgs p) {
+// SAMPLE: score = logit * inv_temperature + Gumbel noise ahead of the packed max - the arg-max is then a draw from
+// softmax(logit / temperature) (Gumbel-max; philox.h).  A thread's CPT = 4 columns are four consecutive vocabulary indices from a
+// multiple of 4: one Philox block serves them.  A compile-time variant: the greedy instantiations keep their code and registers.
+template <int MT, int NT, bool VEC, int NWAVE, bool SAMPLE = false>
+__global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgmaxArgs p, GumbelArgs ga) {
     constexpr int TM = 16 * MT, TN = 16 * NT;
     constexpr int NTHR = NWAVE * 64;
     constexpr int NA = (MT * NT == 1) ? 2 : 1;
@@ -459,11 +462,17 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgm
     // 8 threads per batch row, TN/8 columns each; first-max (lowest index) wins ties.
     const int b = b0 + bl;
     unsigned long long best = 0ull;
+    float gn[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (SAMPLE) {
+        static_assert(CPT == 4 && TN % 4 == 0, "one Philox block per thread");
+        if (active && b < p.B && ga.row0 + (uint32_t)b < ga.rows && n0 + sub * CPT < p.V) gumbel4(ga, (uint32_t)(n0 + sub * CPT) >> 2, ga.row0 + (uint32_t)b, gn);
+    }
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
         const int nl = sub * CPT + j, n = n0 + nl;
         if (active && b < p.B && n < p.V) {
-            const float v = read_sum<MT, NT, NWAVE>(red, bl, nl) + bv[j];
+            float v = read_sum<MT, NT, NWAVE>(red, bl, nl) + bv[j];
+            if constexpr (SAMPLE) v = v * ga.inv_temperature + gn[j];
             const unsigned long long key =
                 ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)n);
             best = key > best ? key : best;
@@ -478,15 +487,19 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgm
     XSTAMP(p.stamps, xrec, 4);
 }
 
-int logits_argmax(hipStream_t stream, const LogitsArgmaxArgs& a) {
+int logits_argmax(hipStream_t stream, const LogitsArgmaxArgs& a, const GumbelArgs* sample) {
     S2VT_REQUIRE(a.B > 0 && a.H > 0 && a.V > 0 && a.h && a.w_out && a.packed, "logits_argmax: bad arguments");
     const bool vec = vec_ok(a.h, a.ldh) && vec_ok(a.w_out, a.ldw) && a.H % 4 == 0;
     dim3 grid(xcd_grid(cdiv(a.V, 32), cdiv(a.B, 32)));
     // 4 waves per tile (K split four ways, 36.9 KB LDS, four workgroups per CU): with eight (two workgroups per CU) every
     // workgroup of a CU sat in its reduction / argmax phase at about the same time and the CU's ingest idled meanwhile
     // (in-kernel stamps of all 1500 workgroups, tools/bench_argmax_stamps.py; 2 % on a greedy decode)
-    if (vec) hipLaunchKernelGGL((logits_argmax_kernel<2, 2, true, 4>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((logits_argmax_kernel<2, 2, false, 4>), grid, dim3(256), 0, stream, a);
+    const GumbelArgs ga = sample ? *sample : GumbelArgs{1.f, 0u, 0u, 0u, 0u, 0u};
+    if (sample) {
+        if (vec) hipLaunchKernelGGL((logits_argmax_kernel<2, 2, true, 4, true>), grid, dim3(256), 0, stream, a, ga);
+        else hipLaunchKernelGGL((logits_argmax_kernel<2, 2, false, 4, true>), grid, dim3(256), 0, stream, a, ga);
+    } else if (vec) hipLaunchKernelGGL((logits_argmax_kernel<2, 2, true, 4>), grid, dim3(256), 0, stream, a, ga);
+    else hipLaunchKernelGGL((logits_argmax_kernel<2, 2, false, 4>), grid, dim3(256), 0, stream, a, ga);
     S2VT_LAUNCH_CHECK("logits_argmax_kernel");
     return 0;
 }

@@ -1,0 +1,63 @@
+// Counter-based Gumbel noise of the sampled decode (mode='sample'): Philox4x32-10 (Salmon et al., "Parallel random numbers:
+// as easy as 1, 2, 3", SC'11) in plain 32-bit integer arithmetic, and the map from one 32-bit word to one standard Gumbel
+// draw.  Stated once here for the device; sampling.py restates it in numpy (what the tests compare against).
+//
+// One draw per (call seed, decode step, batch row, vocabulary index v):
+//     key     = (seed & 0xFFFFFFFF, seed >> 32)
+//     counter = (v / 4, batch row, decode step, GUMBEL_STREAM_TAG)
+//     x       = word v % 4 of philox4x32_10(counter, key)
+//     u       = ((x >> 9) + 0.5) * 2^-23            exact in fp32, strictly inside (0, 1)
+//     g       = -log(-log(u))                        in [-2.82, 16.64]
+// Nothing of a kernel's tiling, of the batch padding or of the launch enters: an element has the same noise wherever it is
+// computed.
+#pragma once
+#include <stdint.h>
+
+#include <hip/hip_runtime.h>
+
+namespace s2vt {
+
+constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // round multipliers
+constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // Weyl key increments
+constexpr uint32_t GUMBEL_STREAM_TAG = 0x47554D42u;                       // "GUMB": counter word 3 of the sampler's stream
+
+struct GumbelArgs {                  // what a sampling launch adds to its greedy sibling's arguments
+    float inv_temperature;           // score = logit * inv_temperature + g
+    uint32_t seed_lo, seed_hi;
+    uint32_t step;                   // decode step of the launch
+    uint32_t row0;                   // batch row of the launch's row 0 (a launch over one half of the batch)
+    uint32_t rows;                   // rows of the caller's batch: rows past it (batch padding of the plane path) generate no noise
+};
+
+struct Philox4 { uint32_t w[4]; };
+
+__host__ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)PHILOX_M0 * c0, p1 = (uint64_t)PHILOX_M1 * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0;
+        c0 = n0; c2 = n2;
+        k0 += PHILOX_W0; k1 += PHILOX_W1;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// One standard Gumbel draw from one 32-bit word.  t = -log(u) is taken from 1 - u (exact: both are multiples of 2^-24) with
+// log1p where u is next to 1 - there log(u) itself would lose every digit of the small result, and g = -log(t) depends on its
+// RELATIVE error.  logf / log1pf are the accurate library functions (about 1 ulp), not the fast-math intrinsics: |g| reaches
+// 16.6 where one fp32 ulp is 1.9e-6, and the tests hold the device to 2 ulp of the float64 value there.
+__device__ __forceinline__ float gumbel_from_bits(uint32_t x) {
+    const float u = ((float)(x >> 9) + 0.5f) * 0x1p-23f;
+    const float t = (u > 0.5f) ? -log1pf(-(1.0f - u)) : -logf(u);
+    return -logf(t);
+}
+
+// the four draws of vocabulary indices 4 * v4 .. 4 * v4 + 3 of batch row `row`
+__device__ __forceinline__ void gumbel4(const GumbelArgs& a, uint32_t v4, uint32_t row, float g[4]) {
+    const Philox4 r = philox4x32_10(v4, row, a.step, GUMBEL_STREAM_TAG, a.seed_lo, a.seed_hi);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) g[e] = gumbel_from_bits(r.w[e]);
+}
+
+}  // namespace s2vt

@@ -208,10 +208,13 @@ def decode_cache_entry(owner, raw_params, d, dev, lib):
 
 
 @torch.no_grad()
-def greedy_decode(feats, params, sos_ix, owner=None):
+def greedy_decode(feats, params, sos_ix, owner=None, sample=None):
     """ids int64 [B, L-1] of S2VT.forward(mode='test').  `owner`: the module the parameters belong to (enables the
-    weight-image cache above)."""
+    weight-image cache above).  `sample` = (temperature, seed): mode='sample' - the same driver, workspace and cache with a draw
+    from softmax(logit / temperature) at every step (s2vt_sample_decode[_cached])."""
     lib = capi.load()
+    if sample is not None:
+        temperature, seed = sample
     feats = _f32c(feats, "feats")
     raw = params
     params = tuple(_f32c(p.detach(), "parameter") for p in params)
@@ -224,13 +227,21 @@ def greedy_decode(feats, params, sos_ix, owner=None):
         ps = _params_struct(capi.Params, params)
         cache, valid = decode_cache_entry(owner, raw, d, dev, lib)
         if cache is not None:
-            capi.check(lib.s2vt_greedy_decode_cached(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), int(sos_ix), _ptr(ids),
-                                                     _ptr(ws), nbytes, _ptr(cache), cache.numel(), 1 if valid else 0,
-                                                     _stream(dev)), "s2vt_greedy_decode_cached")
+            if sample is not None:
+                capi.check(lib.s2vt_sample_decode_cached(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), int(sos_ix), temperature, seed,
+                                                         _ptr(ids), _ptr(ws), nbytes, _ptr(cache), cache.numel(), 1 if valid else 0,
+                                                         _stream(dev)), "s2vt_sample_decode_cached")
+            else:
+                capi.check(lib.s2vt_greedy_decode_cached(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), int(sos_ix), _ptr(ids),
+                                                         _ptr(ws), nbytes, _ptr(cache), cache.numel(), 1 if valid else 0,
+                                                         _stream(dev)), "s2vt_greedy_decode_cached")
             entry = _DECODE_CACHES.get(owner)
             if entry is not None and entry[1] is cache and lib.s2vt_decode_uses_cache(ctypes.byref(d)):
                 entry[2] = True                     # (stream-ordered: later calls on this stream see the filled images; a batch of
                                                     #  at most 16 clips decodes on the launch-per-timestep path and fills nothing)
+        elif sample is not None:
+            capi.check(lib.s2vt_sample_decode(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), int(sos_ix), temperature, seed, _ptr(ids),
+                                              _ptr(ws), nbytes, _stream(dev)), "s2vt_sample_decode")
         else:
             capi.check(lib.s2vt_greedy_decode(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), int(sos_ix), _ptr(ids),
                                               _ptr(ws), nbytes, _stream(dev)), "s2vt_greedy_decode")
@@ -374,6 +385,52 @@ class _MaskCriterion(torch.autograd.Function):
             capi.check(lib.s2vt_mask_criterion_backward(B, Lm1, _ptr(mask), mask.stride(0), _ptr(out3), _ptr(gout), _ptr(g_ce),
                                                         _stream(dev)), "s2vt_mask_criterion_backward")
         return _ce_backward(lib, ctx.train_node, logits, target, lse, g_ce), None, None
+
+
+class _WeightedCE(torch.autograd.Function):
+    """RewardCriterion.forward: s2vt_weighted_ce_forward / _backward, dlogits materialised"""
+
+    @staticmethod
+    def forward(ctx, logits, target, weight):
+        lib = capi.load()
+        logits, target = _ce_inputs(logits, target)
+        require_hip(weight, "weight")
+        if weight.dtype != torch.float32:
+            weight = weight.float()
+        if weight.dim() != 2 or weight.stride(1) != 1:
+            weight = weight.reshape(weight.shape[0], -1).contiguous()
+        B, Lm1, V = logits.shape
+        if weight.shape[0] != B or weight.shape[1] != Lm1 + 1:
+            raise ValueError("weight must be [B, L] = [%d, %d], got %s" % (B, Lm1 + 1, tuple(weight.shape)))
+        dev = logits.device
+        with torch.cuda.device(dev):
+            scratch = torch.empty(2 * B * Lm1 + 2, dtype=torch.float32, device=dev)
+            lse, rowloss, out2 = scratch[:B * Lm1], scratch[B * Lm1:2 * B * Lm1], scratch[2 * B * Lm1:]
+            capi.check(lib.s2vt_weighted_ce_forward(B, Lm1, V, _ptr(logits), _ptr(target), target.stride(0), _ptr(weight),
+                                                    weight.stride(0), _ptr(lse), _ptr(rowloss), _ptr(out2), _stream(dev)),
+                       "s2vt_weighted_ce_forward")
+        ctx.save_for_backward(logits, target, lse, weight, out2)
+        return out2[0].reshape(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        lib = capi.load()
+        logits, target, lse, weight, out2 = ctx.saved_tensors
+        B, Lm1, V = logits.shape
+        dev = logits.device
+        gout = _f32c(gout.reshape(1), "grad_output")
+        with torch.cuda.device(dev):
+            dlogits = torch.empty_like(logits)
+            capi.check(lib.s2vt_weighted_ce_backward(B, Lm1, V, _ptr(logits), _ptr(target), target.stride(0), _ptr(weight),
+                                                     weight.stride(0), _ptr(lse), _ptr(out2), _ptr(gout), _ptr(dlogits), _stream(dev)),
+                       "s2vt_weighted_ce_backward")
+        return dlogits, None, None
+
+
+def weighted_cross_entropy(logits, target, weight):
+    """sum_i w_i * CE_i / max(#{w_i != 0}, 1) over logits [B, L-1, V] against target[:, 1:], w = weight[:, 1:] (fp32 [B, L], any
+    sign).  No gradient flows to the weight."""
+    return _WeightedCE.apply(logits, target, weight)
 
 
 def mean_cross_entropy(logits, target):

@@ -96,12 +96,12 @@ def train_forward(model, feats, targets, out_mask=None):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix):
-    """mode='test' (S2VTModel.py:82-110): ids int64 [B, L-1].  vid_rnn without a stash, word_rnn's encode over the first L steps,
+def greedy_decode(model, feats, sos_ix, sample=None):
+    """mode='test' (S2VTModel.py:82-110): ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the same loop with
+    s2vt_decode_step_sample in place of the arg-max.  vid_rnn without a stash, word_rnn's encode over the first L steps,
     then L-1 decode steps of s2vt_gru_step_fwd_token (the previous step's packed argmax word is read on the device) and
     s2vt_decode_step_argmax.  No host synchronisation inside the loop: <sos> is checked on the host by the first step, and the
     packed words are in range by construction, so no step posts a device error flag."""
-    lib = capi.load()
     B, L, _ = feats.shape
     H, E, V = model.dim_hid, model.dim_embed, model.vocab_size
     T = 2 * L - 1
@@ -122,7 +122,6 @@ def greedy_decode(model, feats, sos_ix):
         for i in range(L - 1):
             h = ops.gru_step_fwd_token(gx_dec[i * B:(i + 1) * B], w_hh, b_hh, h, emb, w_ih, tok_packed=packed[i - 1] if i else None,
                                        tok_const=int(sos_ix), out=hs[i % 2])
-            capi.check(lib.s2vt_decode_step_argmax(B, H, V, _ptr(h), _ptr(wo), _ptr(bo), _ptr(packed[i]), _stream(dev)),
-                       "s2vt_decode_step_argmax")
+            ops.decode_step_token_into(h, wo, bo, packed[i], sample=sample, step=i)
     capi.check_async_error(wait=False)
     return (0xFFFFFFFF - (packed & 0xFFFFFFFF)).t().contiguous()

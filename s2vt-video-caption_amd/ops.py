@@ -218,6 +218,56 @@ def decode_step_argmax(h, w_out, b_out, planes=False):
         return 0xFFFFFFFF - (packed & 0xFFFFFFFF)
 
 
+def decode_step_sample(h, w_out, b_out, temperature=1.0, seed=0, step=0, row0=0, planes=False, return_packed=False):
+    """token ids int64 [B]: one draw per row from softmax((h·w_out^T + b_out) / temperature) by Gumbel-max - the arg-max kernels of
+    decode_step_argmax with the noise of sampling.gumbel_noise(seed, step, row0 + b, V) added to logit / temperature.
+    return_packed: (ids, packed) with the raw packed words (high half = the ordered bits of the winning score)."""
+    lib = capi.load()
+    h, w_out = _f32c(h, "h"), _f32c(w_out, "w_out")
+    B, H = h.shape
+    V = w_out.shape[0]
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    dev = h.device
+    with torch.cuda.device(dev):
+        packed = torch.zeros(B, dtype=torch.int64, device=dev)
+        if planes:
+            nbytes = lib.s2vt_decode_step_sample_x3_workspace_bytes(B, H, V)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            capi.check(lib.s2vt_decode_step_sample_x3(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), temperature, int(seed), int(step),
+                                                      int(row0), _ptr(packed), _ptr(ws), nbytes, _stream(dev)),
+                       "s2vt_decode_step_sample_x3")
+        else:
+            capi.check(lib.s2vt_decode_step_sample(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), temperature, int(seed), int(step),
+                                                   int(row0), _ptr(packed), _stream(dev)), "s2vt_decode_step_sample")
+        ids = 0xFFFFFFFF - (packed & 0xFFFFFFFF)
+    return (ids, packed) if return_packed else ids
+
+
+def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0):
+    """out_linear + arg-max of one decode step into the caller's packed word row `packed_i` (int64 [B], zeroed) - what the greedy
+    loops of the GRU and stacked models run per step; sample = (temperature, seed): the draw of mode='sample' for decode step
+    `step` instead (s2vt_decode_step_sample).  No allocation, no synchronisation."""
+    lib = capi.load()
+    B, H = h.shape
+    V = w_out.shape[0]
+    dev = h.device
+    if sample is None:
+        capi.check(lib.s2vt_decode_step_argmax(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), _ptr(packed_i), _stream(dev)),
+                   "s2vt_decode_step_argmax")
+    else:
+        capi.check(lib.s2vt_decode_step_sample(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), sample[0], sample[1], int(step), 0,
+                                               _ptr(packed_i), _stream(dev)), "s2vt_decode_step_sample")
+
+
+def packed_score(packed):
+    """fp32 scores from the high halves of packed arg-max words (the inverse of the kernels' order-preserving bit map)"""
+    hi = (packed >> 32) & 0xFFFFFFFF
+    u = torch.where(hi >= 0x80000000, hi - 0x80000000, 0xFFFFFFFF - hi)            # the float's own bits, as a non-negative int64
+    return torch.where(u >= 0x80000000, u - 0x100000000, u).to(torch.int32).view(torch.float32)
+
+
 def beam_step(params, dims, row_b, row_state, tok, vid_h, vid_c, word_h, word_c):
     """One s2vt_beam_step call (include/s2vt_hip.h).  params: 13 tensors in capi.PARAM_KEYS order; dims = (B,L,F,H,E,V);
     row_b / row_state / tok: int32 [R].  Returns (vid_h', vid_c', word_h' [R,H], word_c' [R,H], top_ix [R,20] int32,

@@ -1,0 +1,81 @@
+"""The sampled decode's noise, restated in numpy (host side; float64).
+
+`mode='sample'` draws a token from softmax(logit / temperature) as the arg-max of `logit / temperature + g` with g i.i.d.
+standard Gumbel noise (Gumbel-max).  The device generates g inside the arg-max kernels' epilogues (csrc/philox.h); this module is
+the same definition written a second time - what the tests compare the device against, and the documentation of the mapping:
+
+    one draw per (seed, decode step, batch row, vocabulary index v)
+    key     = (seed & 0xFFFFFFFF, seed >> 32)
+    counter = (v // 4, batch row, decode step, STREAM_TAG)
+    x       = word v % 4 of philox4x32_10(counter, key)
+    u       = ((x >> 9) + 0.5) * 2**-23           (exact in fp32, strictly inside (0, 1))
+    g       = -log(-log(u))                       (in [-2.82, 16.64])
+
+Nothing of a kernel's tiling, of the batch padding or of the launch enters.
+"""
+import numpy as np
+
+M0, M1 = 0xD2511F53, 0xCD9E8D57          # Philox4x32 round multipliers
+W0, W1 = 0x9E3779B9, 0xBB67AE85          # Weyl key increments
+STREAM_TAG = 0x47554D42                  # "GUMB": counter word 3 of the sampler's stream (GUMBEL_STREAM_TAG of csrc/philox.h)
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 (Salmon et al., SC'11).  counter: uint32 [..., 4], key: uint32 [..., 2] (broadcast against each other);
+    returns uint32 [..., 4]."""
+    counter = np.asarray(counter, dtype=np.uint32)
+    key = np.asarray(key, dtype=np.uint32)
+    shape = np.broadcast_shapes(counter.shape[:-1], key.shape[:-1])
+    c = [np.broadcast_to(counter[..., i], shape).astype(np.uint64) for i in range(4)]
+    k = [np.broadcast_to(key[..., i], shape).astype(np.uint64) for i in range(2)]
+    for _ in range(10):
+        p0 = np.uint64(M0) * c[0]            # 32 x 32 -> 64 bits: no overflow in uint64
+        p1 = np.uint64(M1) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ k[0], p1 & _MASK32, (p0 >> np.uint64(32)) ^ c[3] ^ k[1], p0 & _MASK32]
+        k = [(k[0] + np.uint64(W0)) & _MASK32, (k[1] + np.uint64(W1)) & _MASK32]
+    return np.stack(c, axis=-1).astype(np.uint32)
+
+
+def uniform_from_bits(x):
+    """u = ((x >> 9) + 0.5) * 2^-23 in float64 (the value is exact in fp32 as well)"""
+    return ((np.asarray(x, dtype=np.uint32) >> np.uint32(9)).astype(np.float64) + 0.5) * 2.0 ** -23
+
+
+def gumbel_from_bits(x):
+    u = uniform_from_bits(x)
+    return -np.log(-np.log1p(-(1.0 - u)))    # 1 - u is exact; log1p keeps -log(u) accurate next to u = 1
+
+
+def gumbel_noise(seed, step, rows, V):
+    """float64 [len(rows), V]: the noise of decode step `step` for the batch rows `rows` (an int n means rows 0..n-1)."""
+    rows = np.arange(rows, dtype=np.uint32) if np.isscalar(rows) else np.asarray(rows, dtype=np.uint32)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    nblk = (int(V) + 3) // 4
+    counter = np.empty((rows.shape[0], nblk, 4), dtype=np.uint32)
+    counter[..., 0] = np.arange(nblk, dtype=np.uint32)[None, :]
+    counter[..., 1] = rows[:, None]
+    counter[..., 2] = np.uint32(step)
+    counter[..., 3] = np.uint32(STREAM_TAG)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32)
+    bits = philox4x32_10(counter, key).reshape(rows.shape[0], nblk * 4)[:, :int(V)]
+    return gumbel_from_bits(bits)
+
+
+def draw_seed(generator=None):
+    """A 63-bit seed from torch's default (CPU) generator: `torch.manual_seed` makes a run of seed=None calls reproducible."""
+    import torch
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64, generator=generator).item())
+
+
+def check_sample_args(temperature, seed):
+    """(temperature as float, seed as int in [0, 2^64)) or ValueError - before anything reaches the library"""
+    t = float(temperature)
+    if not (t > 0.0 and t < float("inf")):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    seed = draw_seed() if seed is None else int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2^64), got %r" % (seed,))
+    return t, seed

@@ -171,12 +171,12 @@ def _layer_masks(N, rnn_masks, rows, H):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix):
-    """mode='test' (S2VTModel.py:82-110) of a stacked model: ids int64 [B, L-1].  The vid chain over T steps, the word chain's
+def greedy_decode(model, feats, sos_ix, sample=None):
+    """mode='test' (S2VTModel.py:82-110) of a stacked model: ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the
+    same loop with s2vt_decode_step_sample in place of the arg-max.  The vid chain over T steps, the word chain's
     encode over the first L steps, then L-1 decode steps of one word-chain call each (T = 1, the previous step's state, the packed
     argmax word read on the device) followed by s2vt_decode_step_argmax.  No host synchronisation inside the loop.  In training
     mode with rnn_dropout > 0, masks are drawn as nn.LSTM would apply them."""
-    lib = capi.load()
     B, L, Fd = feats.shape
     H, E, V = model.dim_hid, model.dim_embed, model.vocab_size
     N = model.vid_rnn.num_layers
@@ -227,8 +227,7 @@ def greedy_decode(model, feats, sos_ix):
                     lay["hm"] = bufs[i % 2][k]["hm"]
             ops.lstm_chain_fwd(1, B, H, step)
             state = [(lay["h"], lay["c"]) for lay in step]
-            capi.check(lib.s2vt_decode_step_argmax(B, H, V, _ptr(state[-1][0]), _ptr(wo), _ptr(bo), _ptr(packed[i]), _stream(dev)),
-                       "s2vt_decode_step_argmax")
+            ops.decode_step_token_into(state[-1][0], wo, bo, packed[i], sample=sample, step=i)
     capi.check_async_error(wait=False)
     return (0xFFFFFFFF - (packed & 0xFFFFFFFF)).t().contiguous()
 

@@ -55,6 +55,12 @@ def parse(argv=None):
     ap.add_argument("--rnn-type", choices=("lstm", "gru"), default="lstm",
                     help="S2VT's recurrent cell (the reference's Opt.rnn_type): gru runs the GRU timestep kernels with torch's Adam "
                          "and, with several processes, the plain bucketed all-reduce")
+    ap.add_argument("--self-critical", action="store_true",
+                    help="sequence-level training on CIDEr instead of cross-entropy: per batch a sampled (mode='sample') and a greedy "
+                         "(mode='test') caption are scored against the clip's references (document frequencies of the training split), "
+                         "and the sampled tokens' log-likelihood is weighted with reward(sampled) - reward(greedy) "
+                         "(utils.RewardCriterion).  Start from a cross-entropy-trained --init-state.  Single process.")
+    ap.add_argument("--sc-temperature", type=float, default=1.0, help="temperature of the sampled caption (--self-critical)")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
     return ap.parse_args(argv)
 
@@ -134,6 +140,40 @@ def run(opt):
                                    path=os.path.join(opt.save_path, start_time + 'stop.pth'))        # :98-100
     criterion = MaskCriterion()
     hist = {"train_loss": [], "valid_loss": [], "lr": [], "stopped_at": None, "checkpoints": []}
+    rewarder = None
+    if opt.self_critical:
+        if world > 1 or opt.model != "s2vt":
+            raise NotImplementedError("--self-critical runs S2VT in a single process")
+        from utils import RewardCriterion
+        from s2vt_video_caption_amd.self_critical import CiderRewarder, advantage_weights
+        sos, eos = word2ix['<sos>'], word2ix['<eos>']
+        rewarder = CiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos)
+        reward_criterion = RewardCriterion()
+        # wall-clock split of the self-critical steps (ms, summed over the run; each phase ends with a device synchronisation)
+        hist["sc_split_ms"] = {"sample": 0.0, "greedy": 0.0, "scoring": 0.0, "train": 0.0, "steps": 0}
+        hist["reward_sample"], hist["reward_greedy"] = [], []
+
+    def self_critical_step(feats, ids):
+        sp = hist["sc_split_ms"]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            sampled = model(feats, mode='sample', temperature=opt.sc_temperature).cpu()
+        t1 = time.perf_counter()
+        with torch.no_grad():
+            greedy = model(feats, mode='test').cpu()
+        t2 = time.perf_counter()
+        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
+        weight = advantage_weights(sampled, r_s - r_g, eos).to(dev)
+        caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
+        t3 = time.perf_counter()
+        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
+        t4 = time.perf_counter()
+        for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
+            sp[k] += 1e3 * v
+        sp["steps"] += 1
+        hist["reward_sample"].append(float(r_s.mean()))
+        hist["reward_greedy"].append(float(r_g.mean()))
+        return loss
 
     def save(name):
         if rank == 0:
@@ -148,7 +188,10 @@ def run(opt):
         for feats, targets, ids, masks in dataloader.feed_batches(train_loader, dev):
             # train.py:116-127; check_errors: a device-side error of this step (IndexError for a caption id outside the vocabulary)
             # is raised BEFORE optimizer.step(), as in the reference, whose nn.Embedding raises in the forward
-            loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True)
+            if rewarder is not None:
+                loss = self_critical_step(feats, ids)
+            else:
+                loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True)
             running += float(loss)
             count += 1
         train_loss = running / max(count, 1)

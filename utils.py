@@ -25,6 +25,19 @@ class MaskCriterion(nn.Module):
         return _F.mask_criterion(logits, target, mask)
 
 
+class RewardCriterion(nn.Module):
+    """Reward-weighted caption loss for sequence-level (self-critical) training - not in the reference.
+    loss = sum_i w_i * CE_i / max(#{i: w_i != 0}, 1) over the N*(seq_len-1) positions, CE_i the cross-entropy of logits[i] against
+    target[:, 1:], w = weight[:, 1:] (fp32 [N, seq_len], any sign): the advantage reward(sampled) - reward(greedy) on the sampled
+    tokens up to and including <eos>, zero after it; a 0/1 weight makes it a masked mean that works.  An all-zero weight gives
+    0.  HIP kernels (s2vt_weighted_ce_forward / _backward); the gradient of the logits is MATERIALISED ([N, seq_len-1, V] fp32):
+    the fused hand-over of MaskCriterion's backward into the model's plane-split pass is not extended to this loss.  No gradient
+    flows to the weight."""
+
+    def forward(self, logits, target, weight):
+        return _F.weighted_cross_entropy(logits, target, weight)
+
+
 class EarlyStopping:
     """Patience counter on the validation loss; every improvement writes the FULL module with `torch.save(model, path)`
     (the reference's checkpoint format).  Same public surface as upstream: `patience, verbose, delta, path, trace_func`,
