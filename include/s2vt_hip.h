@@ -238,6 +238,48 @@ int s2vt_weighted_ce_backward(int32_t B, int32_t Lm1, int32_t V, const float* lo
                               const float* weight, int64_t weight_ld, const float* lse, const float* out2, const float* gout,
                               float* dlogits, void* stream);
 
+/* ---------------------------------------------------------------- self-critical rewards on the device (train.py --sc-reward device)
+ * The reference side of CIDEr (caption_metrics.cider_vector / cider_of_vectors over token ids) as flat device arrays, built once
+ * per run by self_critical.DeviceCiderRewarder.  An n-gram KEY is exact: up to four tokens of 16 bits each in a uint64, the first
+ * token in bits 63..48, an absent position 0 (a real token is never 0: the pad id is stripped), so the number of non-zero fields
+ * is the order.  Every fp64 factor that needs log / exp is precomputed by the host with caption_metrics' own expressions; the
+ * device only adds, multiplies, divides, takes sqrt and min.
+ *   idf_keys / idf_vals [n_idf]  every n-gram of the training references, keys ascending, value log_n - log(max(1, df)); a key
+ *                                that is absent has idf = log_n
+ *   clip_ref_off [n_clips + 1]   CSR: the references of clip c are clip_ref_off[c] .. clip_ref_off[c+1] - 1 (at least one each)
+ *   ent_off [4*n_refs + 1]       CSR: the (key, tf*idf) entries of reference r, order k = 1..4, are ent_off[4r + k-1] ..
+ *                                ent_off[4r + k] - 1 of ent_keys / ent_w, keys strictly ascending inside one (r, k)
+ *   ref_norm [4*n_refs]          cider_vector's norm of reference r, order k at [4r + k-1];  ref_len [n_refs] its length (bigrams)
+ *   pen [n_pen]                  pen[d] = e ** (-(d*d) / (2 sigma**2)), d = |candidate length - reference length|; n_pen covers
+ *                                every reference length and S2VT_CIDER_MAX_T */
+#define S2VT_CIDER_MAX_T 512       /* longest id row s2vt_cider_rewards takes (its n-gram list lives in LDS) */
+typedef struct s2vt_cider_table {
+    const uint64_t* idf_keys; const double* idf_vals;
+    const int32_t* clip_ref_off; const int32_t* ent_off;
+    const uint64_t* ent_keys; const double* ent_w;
+    const double* ref_norm; const int32_t* ref_len;
+    const double* pen;
+    double log_n;
+    int64_t n_idf;
+    int32_t n_clips, n_refs, n_pen;
+} s2vt_cider_table;
+/* out[b] (fp64) = CiderRewarder.score(clip clip_rows[b], ids[b]) for the B rows of ids (int64 [B, T], row stride ld): the row is
+ * stripped like self_critical.strip_caption (a leading sos dropped, pads dropped, cut at the first eos), its 1..4-grams are sorted
+ * and counted in LDS, weighted with their idf, and compared with every reference of the clip (clipped product min(w_h, w_r) * w_r
+ * per order, divided by the norms where both are non-zero, length penalty, mean over orders and references, x10).  One workgroup
+ * per row, every sum in a fixed order, no floating-point atomics: a row's value does not depend on the rest of the batch.
+ * `table` is a HOST struct of device pointers; clip_rows int32 [B] on the device.  T > S2VT_CIDER_MAX_T is refused (S2VT_ERR_ARG).
+ * A token outside [0, 65535] among those the scorer reads (before the first eos) or a clip row outside [0, n_clips) is never
+ * used as an index: the row scores without it (0 for a bad clip row) and the call is reported as S2VT_ERR_INDEX by
+ * s2vt_check_async_error / a later call. */
+int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, const int64_t* ids, int32_t B, int32_t T, int64_t ld,
+                       int32_t sos, int32_t eos, double* out, void* stream);
+/* What the self-critical step feeds the train step (self_critical.advantage_weights and the <sos> column, on the device):
+ * caps int64 [B, T+1] = sos || sampled (int64 [B, T], contiguous); weight fp32 [B, T+1] = fp32(r_sample[b] - r_greedy[b]) - the
+ * fp64 difference rounded once - on positions 1 .. the first eos of the row inclusive (all T without one), zero elsewhere. */
+int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t T, int32_t sos,
+                    int32_t eos, int64_t* caps, float* weight, void* stream);
+
 /* The same gradient handed to s2vt_train_backward WITHOUT an fp32 dlogits tensor (utils.py:22 under loss.backward(), train.py:124):
  * evaluates (softmax(logits) - onehot(target)) * gout[0] / (B*(L-1)) inside the plane-split pass of the TRAIN workspace the
  * logits came from - the operand planes and bias-gradient partial sums the backward's first kernel would otherwise produce from

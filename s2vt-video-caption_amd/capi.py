@@ -42,6 +42,15 @@ class LstmLayer(ctypes.Structure):
                 ("hm", c_void_p), ("dh_ext", c_void_p), ("dh_t0", c_int32), ("dg", c_void_p)]
 
 
+class CiderTable(ctypes.Structure):
+    """s2vt_cider_table of include/s2vt_hip.h: the reference side of CIDEr as flat device arrays"""
+    _fields_ = [(n, c_void_p) for n in ("idf_keys", "idf_vals", "clip_ref_off", "ent_off", "ent_keys", "ent_w", "ref_norm", "ref_len",
+                                        "pen")] + [("log_n", c_double), ("n_idf", c_int64), ("n_clips", c_int32), ("n_refs", c_int32),
+                                                   ("n_pen", c_int32)]
+
+
+CIDER_MAX_T = 512        # S2VT_CIDER_MAX_T of include/s2vt_hip.h
+
 # name -> (restype, argtypes): every symbol include/s2vt_hip.h declares
 ABI_VERSION = 9          # S2VT_ABI_VERSION of include/s2vt_hip.h this binding was written against
 
@@ -148,6 +157,9 @@ SIGNATURES = {
                                            c_void_p, c_void_p, c_void_p]),
     "s2vt_weighted_ce_backward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "s2vt_cider_rewards": (c_int32, [POINTER(CiderTable), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                                     c_void_p]),
+    "s2vt_sc_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "s2vt_mean_ce_backward_fused": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
     "s2vt_set_option": (c_int32, [c_char_p, c_int32]),

@@ -1,0 +1,255 @@
+// Self-critical rewards on the device (train.py --sc-reward device): CIDEr of a batch of id rows against a reference table that
+// self_critical.DeviceCiderRewarder builds once (s2vt_cider_table of include/s2vt_hip.h), and the <sos>-prefixed captions and
+// advantage weights the train step takes.  fp64 throughout; every factor that needs log / exp comes precomputed from the host, so
+// the kernels only add, multiply, divide, take sqrt and min - in a fixed order, without floating-point atomics.
+#include "api_internal.h"
+
+// a * b + c stays two roundings, as in the host's arithmetic
+#pragma clang fp contract(off)
+
+namespace s2vt {
+
+constexpr int kCiderThreads = 256;
+constexpr int kCiderMaxT = S2VT_CIDER_MAX_T;
+constexpr int kCiderMaxN = 4 * kCiderMaxT;          // 1..4-grams of kCiderMaxT words: fewer than 4 per word; a power of two
+static_assert((kCiderMaxN & (kCiderMaxN - 1)) == 0, "the bitonic sort needs a power of two");
+static_assert(kCiderThreads == 4 * 64, "one wavefront per n-gram order");
+
+// order of a key = its number of non-zero 16-bit fields (tokens are never 0), counted from the top
+__device__ __forceinline__ int cider_key_order(uint64_t k) {
+    return (k & 0xFFFFull) ? 4 : (k & 0xFFFF0000ull) ? 3 : (k & 0xFFFF00000000ull) ? 2 : 1;
+}
+// index of `key` in the ascending keys[lo, hi), or -1
+__device__ __forceinline__ int64_t cider_find(const uint64_t* keys, int64_t lo, int64_t hi, uint64_t key) {
+    const int64_t end = hi;
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (keys[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo < end && keys[lo] == key ? lo : -1;
+}
+// butterfly sum over the 64 lanes: the same association order in every lane and on every call
+__device__ __forceinline__ double cider_wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// One workgroup = one candidate row.
+__global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider_table tb, const int32_t* clip_rows, const int64_t* ids,
+                                                                      int T, int64_t ld, int sos, int eos, double* out, int* err) {
+    __shared__ int32_t words[kCiderMaxT];
+    __shared__ uint64_t keys[kCiderMaxN];
+    __shared__ double wts[kCiderMaxN];            // tf * idf at the first entry of a run of equal keys, 0 elsewhere
+    __shared__ int s_m;
+    __shared__ double s_hn[4];
+    __shared__ double s_tot[kCiderThreads / 64][4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int crow = clip_rows[b];
+    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) {
+            atomicExch(err, 2);
+            out[b] = 0.0;
+        }
+        return;
+    }
+    // ---- the words of the row (strip_caption): one wavefront walks it in chunks of 64 and compacts with ballots
+    if (wave == 0) {
+        const int64_t* row = ids + (int64_t)b * ld;
+        int m = 0;
+        bool bad = false;
+        for (int base = 0; base < T; base += 64) {
+            const int i = base + lane;
+            const int64_t t = i < T ? row[i] : 0;
+            const unsigned long long eosm = __ballot(i < T && t == (int64_t)eos);
+            const bool before = eosm == 0 || lane < __ffsll((long long)eosm) - 1;
+            const bool oor = before && (t < 0 || t > 65535);
+            bad |= oor;
+            const bool keep = i < T && before && !oor && t != 0 && !(i == 0 && t == (int64_t)sos);
+            const unsigned long long km = __ballot(keep);
+            if (keep) words[m + __popcll(km & ((1ull << lane) - 1ull))] = (int32_t)t;
+            m += __popcll(km);
+            if (eosm) break;
+        }
+        if (__ballot(bad) && lane == 0) atomicExch(err, 2);
+        if (lane == 0) s_m = m;
+    }
+    __syncthreads();
+    const int m = s_m;
+    const int n1 = m, n2 = m > 1 ? m - 1 : 0, n3 = m > 2 ? m - 2 : 0, n4 = m > 3 ? m - 3 : 0;
+    const int total = n1 + n2 + n3 + n4;
+    int N = 1;
+    while (N < total) N <<= 1;                    // <= kCiderMaxN since m <= T <= kCiderMaxT
+    // ---- every 1..4-gram as a key; the tail of the power of two is filled with the largest value and stays behind the sort
+    for (int i = tid; i < N; i += kCiderThreads) {
+        uint64_t key = ~0ull;
+        if (i < total) {
+            int k, p;
+            if (i < n1) { k = 1; p = i; }
+            else if (i < n1 + n2) { k = 2; p = i - n1; }
+            else if (i < n1 + n2 + n3) { k = 3; p = i - n1 - n2; }
+            else { k = 4; p = i - n1 - n2 - n3; }
+            key = 0;
+            for (int j = 0; j < k; ++j) key |= (uint64_t)(uint32_t)words[p + j] << (48 - 16 * j);
+        }
+        keys[i] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < N; i += kCiderThreads) {
+                const int x = i ^ j;
+                if (x > i) {
+                    const uint64_t a = keys[i], c = keys[x];
+                    if ((a > c) == ((i & k) == 0)) {
+                        keys[i] = c;
+                        keys[x] = a;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // ---- unique n-grams: the first entry of a run carries tf (the run's length) * idf
+    for (int i = tid; i < N; i += kCiderThreads) {
+        double w = 0.0;
+        if (i < total) {
+            const uint64_t key = keys[i];
+            if (i == 0 || keys[i - 1] != key) {
+                int tf = 1;
+                while (i + tf < total && keys[i + tf] == key) ++tf;
+                const int64_t at = cider_find(tb.idf_keys, 0, tb.n_idf, key);
+                w = (double)tf * (at >= 0 ? tb.idf_vals[at] : tb.log_n);
+            }
+        }
+        wts[i] = w;
+    }
+    __syncthreads();
+    // ---- the candidate's norm per order: wavefront k takes order k + 1
+    {
+        double s = 0.0;
+        for (int i = lane; i < total; i += 64) {
+            const double w = wts[i];
+            if (w != 0.0 && cider_key_order(keys[i]) == wave + 1) s += w * w;
+        }
+        s = cider_wave_sum(s);
+        if (lane == 0) s_hn[wave] = sqrt(s);
+    }
+    __syncthreads();
+    // ---- against the references of the clip: wavefront w takes references w, w + 4, ..; its lanes share the n-grams
+    const int r0 = tb.clip_ref_off[crow], r1 = tb.clip_ref_off[crow + 1];
+    double tot0 = 0.0, tot1 = 0.0, tot2 = 0.0, tot3 = 0.0;
+    for (int r = r0 + wave; r < r1; r += kCiderThreads / 64) {
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int i = lane; i < total; i += 64) {
+            const double w = wts[i];
+            if (w == 0.0) continue;               // not the head of a run, or idf 0: contributes exactly 0
+            const uint64_t key = keys[i];
+            const int k = cider_key_order(key) - 1;
+            const int64_t at = cider_find(tb.ent_keys, tb.ent_off[4 * (int64_t)r + k], tb.ent_off[4 * (int64_t)r + k + 1], key);
+            if (at < 0) continue;
+            const double wr = tb.ent_w[at];
+            const double c = (w < wr ? w : wr) * wr;
+            if (k == 0) a0 += c;
+            else if (k == 1) a1 += c;
+            else if (k == 2) a2 += c;
+            else a3 += c;
+        }
+        a0 = cider_wave_sum(a0);
+        a1 = cider_wave_sum(a1);
+        a2 = cider_wave_sum(a2);
+        a3 = cider_wave_sum(a3);
+        int d = n2 - tb.ref_len[r];
+        d = d < 0 ? -d : d;
+        const double pen = tb.pen[d < tb.n_pen ? d : tb.n_pen - 1];
+        const double* rn = tb.ref_norm + 4 * (int64_t)r;
+        if (s_hn[0] != 0.0 && rn[0] != 0.0) a0 /= s_hn[0] * rn[0];
+        if (s_hn[1] != 0.0 && rn[1] != 0.0) a1 /= s_hn[1] * rn[1];
+        if (s_hn[2] != 0.0 && rn[2] != 0.0) a2 /= s_hn[2] * rn[2];
+        if (s_hn[3] != 0.0 && rn[3] != 0.0) a3 /= s_hn[3] * rn[3];
+        tot0 += a0 * pen;
+        tot1 += a1 * pen;
+        tot2 += a2 * pen;
+        tot3 += a3 * pen;
+    }
+    if (lane == 0) {
+        s_tot[wave][0] = tot0;
+        s_tot[wave][1] = tot1;
+        s_tot[wave][2] = tot2;
+        s_tot[wave][3] = tot3;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double t[4];
+        for (int k = 0; k < 4; ++k) t[k] = ((s_tot[0][k] + s_tot[1][k]) + s_tot[2][k]) + s_tot[3][k];
+        const double mean = (((t[0] + t[1]) + t[2]) + t[3]) / 4.0;
+        out[b] = mean / (double)(r1 - r0) * 10.0;
+    }
+}
+
+// One workgroup = one row of sampled ids.
+__global__ __launch_bounds__(kCiderThreads) void sc_weights_kernel(const int64_t* sampled, const double* r_sample, const double* r_greedy,
+                                                                   int T, int sos, int eos, int64_t* caps, float* weight) {
+    __shared__ int s_first;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t* row = sampled + (int64_t)b * T;
+    if (tid == 0) s_first = T;
+    __syncthreads();
+    for (int i = tid; i < T; i += kCiderThreads)
+        if (row[i] == (int64_t)eos) atomicMin(&s_first, i);
+    __syncthreads();
+    const int first = s_first;                    // index of the first <eos>, T without one
+    const float adv = (float)(r_sample[b] - r_greedy[b]);
+    int64_t* crow = caps + (int64_t)b * (T + 1);
+    float* wrow = weight + (int64_t)b * (T + 1);
+    if (tid == 0) {
+        crow[0] = sos;
+        wrow[0] = 0.0f;
+    }
+    for (int i = tid; i < T; i += kCiderThreads) {
+        crow[1 + i] = row[i];
+        wrow[1 + i] = (i <= first ? 1.0f : 0.0f) * adv;
+    }
+}
+
+}  // namespace s2vt
+
+using namespace s2vt;
+
+extern "C" {
+
+int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, const int64_t* ids, int32_t B, int32_t T, int64_t ld,
+                       int32_t sos, int32_t eos, double* out, void* stream) {
+    S2VT_REQUIRE(table && clip_rows && ids && out, "s2vt_cider_rewards: null argument");
+    S2VT_REQUIRE(B > 0 && T > 0 && ld >= T, "s2vt_cider_rewards: bad dims (B %d, T %d, ld %lld)", (int)B, (int)T, (long long)ld);
+    S2VT_REQUIRE(T <= S2VT_CIDER_MAX_T, "s2vt_cider_rewards: T = %d ids per row, the n-gram list in LDS holds rows of up to %d", (int)T,
+                 S2VT_CIDER_MAX_T);
+    const s2vt_cider_table& tb = *table;
+    S2VT_REQUIRE(tb.clip_ref_off && tb.ent_off && tb.ref_norm && tb.ref_len && tb.pen && tb.n_clips > 0 && tb.n_refs > 0 && tb.n_pen > 0 &&
+                     tb.n_idf >= 0 && (tb.n_idf == 0 || (tb.idf_keys && tb.idf_vals)),
+                 "s2vt_cider_rewards: incomplete table");
+    hipStream_t st = (hipStream_t)stream;
+    int* flags = nullptr;
+    int rc;
+    if ((rc = device_flags(&flags))) return rc;
+    const int rc0 = poll_async_error(false);
+    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    hipLaunchKernelGGL(cider_rewards_kernel, dim3((unsigned)B), dim3(kCiderThreads), 0, st, tb, clip_rows, ids, (int)T, ld, (int)sos,
+                       (int)eos, out, flags);
+    S2VT_LAUNCH_CHECK("cider_rewards_kernel");
+    // two calls per self-critical step: the ring of records, so that a call never waits for the copy of the one before it
+    return rc0 ? rc0 : post_async_error(st, flags, 3);
+}
+
+int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t T, int32_t sos,
+                    int32_t eos, int64_t* caps, float* weight, void* stream) {
+    S2VT_REQUIRE(sampled && r_sample && r_greedy && caps && weight, "s2vt_sc_weights: null argument");
+    S2VT_REQUIRE(B > 0 && T > 0, "s2vt_sc_weights: bad dims (B %d, T %d)", (int)B, (int)T);
+    hipLaunchKernelGGL(sc_weights_kernel, dim3((unsigned)B), dim3(kCiderThreads), 0, (hipStream_t)stream, sampled, r_sample, r_greedy,
+                       (int)T, (int)sos, (int)eos, caps, weight);
+    S2VT_LAUNCH_CHECK("sc_weights_kernel");
+    return 0;
+}
+
+}  // extern "C"

@@ -559,3 +559,47 @@ def lstm_chain_bwd(T, B, H, layers):
         nbytes = lib.s2vt_lstm_chain_bwd_workspace_bytes(B, H, len(layers))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         capi.check(lib.s2vt_lstm_chain_bwd(T, B, H, len(layers), arr, _ptr(ws), nbytes, _stream(dev)), "s2vt_lstm_chain_bwd")
+
+
+def cider_rewards(table, clip_rows, ids, sos_ix, eos_ix):
+    """fp64 [B]: CIDEr of the id rows `ids` (int64 [B, T], unit column stride) against the references of the clips `clip_rows`
+    (int32 [B], rows of the table) - s2vt_cider_rewards.  `table` is a capi.CiderTable of device pointers that the caller keeps
+    alive (self_critical.DeviceCiderRewarder).  A token outside [0, 65535] raises IndexError at the next capi.check_async_error()."""
+    lib = capi.load()
+    require_hip(ids, "ids")
+    require_hip(clip_rows, "clip_rows")
+    if ids.dim() != 2 or clip_rows.dtype != torch.int32 or clip_rows.numel() != ids.shape[0]:
+        raise capi.S2VTHipError("cider_rewards: ids [B, T] and clip_rows int32 [B] expected")
+    if ids.dtype != torch.int64 or ids.stride(1) != 1:
+        ids = ids.long().contiguous()
+    B, T = ids.shape
+    if T > capi.CIDER_MAX_T:
+        raise ValueError("cider_rewards: rows of %d ids; the kernel's n-gram list in LDS holds rows of up to %d" % (T, capi.CIDER_MAX_T))
+    dev = ids.device
+    with torch.cuda.device(dev):
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+        capi.check(lib.s2vt_cider_rewards(ctypes.byref(table), _ptr(clip_rows.contiguous()), _ptr(ids), B, T, ids.stride(0), int(sos_ix),
+                                          int(eos_ix), _ptr(out), _stream(dev)), "s2vt_cider_rewards")
+    return out
+
+
+def sc_weights(sampled, r_sample, r_greedy, sos_ix, eos_ix):
+    """(caps int64 [B, T+1] = <sos> || sampled, weight fp32 [B, T+1] = self_critical.advantage_weights(sampled, r_sample - r_greedy,
+    eos_ix)) from sampled ids int64 [B, T] and the two fp64 reward vectors [B], all on the device - s2vt_sc_weights."""
+    lib = capi.load()
+    require_hip(sampled, "sampled")
+    if sampled.dim() != 2 or sampled.dtype != torch.int64:
+        raise capi.S2VTHipError("sc_weights: sampled must be int64 [B, T]")
+    sampled = sampled.contiguous()
+    B, T = sampled.shape
+    for name, r in (("r_sample", r_sample), ("r_greedy", r_greedy)):
+        require_hip(r, name)
+        if r.dtype != torch.float64 or tuple(r.shape) != (B,) or not r.is_contiguous():
+            raise capi.S2VTHipError("sc_weights: %s must be a contiguous float64 [B]" % name)
+    dev = sampled.device
+    with torch.cuda.device(dev):
+        caps = torch.empty(B, T + 1, dtype=torch.int64, device=dev)
+        weight = torch.empty(B, T + 1, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_sc_weights(_ptr(sampled), _ptr(r_sample), _ptr(r_greedy), B, T, int(sos_ix), int(eos_ix), _ptr(caps),
+                                       _ptr(weight), _stream(dev)), "s2vt_sc_weights")
+    return caps, weight

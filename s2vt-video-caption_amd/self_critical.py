@@ -52,3 +52,140 @@ def advantage_weights(sampled, advantage, eos_ix):
     pos = torch.arange(1, Lm1 + 1)[None, :]
     w[:, 1:] = (pos <= first[:, None]).float() * torch.as_tensor(advantage, dtype=torch.float32)[:, None]
     return w
+
+
+# ------------------------------------------------------------------ the same score on the device (train.py --sc-reward device)
+KEY_TOKENS, KEY_BITS = 4, 16         # an n-gram key: up to four tokens of 16 bits in a uint64, first token on top, absent positions 0
+
+
+def pack_key(gram):
+    """exact uint64 key of an n-gram (tuple of 1..4 token ids in [1, 65535]); the number of non-zero fields is its order"""
+    if not 1 <= len(gram) <= KEY_TOKENS:
+        raise ValueError("n-grams of 1..%d tokens have a key, got %d" % (KEY_TOKENS, len(gram)))
+    key = 0
+    for j, t in enumerate(gram):
+        t = int(t)
+        if not 0 < t < (1 << KEY_BITS):
+            raise ValueError("token id %d does not fit the %d-bit fields of an n-gram key (ids 1..%d)" % (t, KEY_BITS, (1 << KEY_BITS) - 1))
+        key |= t << (KEY_BITS * (KEY_TOKENS - 1 - j))
+    return key
+
+
+def unpack_key(key):
+    """the n-gram (tuple of token ids) of a key"""
+    key = int(key)
+    toks = [(key >> (KEY_BITS * (KEY_TOKENS - 1 - j))) & ((1 << KEY_BITS) - 1) for j in range(KEY_TOKENS)]
+    while toks and toks[-1] == 0:
+        toks.pop()
+    return tuple(toks)
+
+
+class DeviceCiderRewarder(object):
+    """CiderRewarder's score as a HIP kernel (s2vt_cider_rewards) over a reference table that is built here once and lives on
+    the card.  Every factor that needs log / exp (idf, the references' tf-idf weights and norms, the length penalties) is
+    computed on the host with caption_metrics' own expressions and stored as float64; the table is plain arrays:
+
+      idf_keys, idf_vals [n_idf]   every n-gram of the training references, keys ascending; an absent key has idf log_n
+      clip_ref_off [n_clips + 1]   CSR: the references of clip c (row number of video_ids[c])
+      ent_off [4 * n_refs + 1]     CSR: the (ent_keys, ent_w = tf * idf) entries of reference r and order k at 4r + k-1, keys ascending
+      ref_norm [4 * n_refs], ref_len [n_refs], pen [n_pen]
+
+    `host` keeps the numpy copies (table_walk scores from them without a GPU); `device` uploads them at construction,
+    otherwise the first rewards() call uploads to the device of its ids."""
+
+    def __init__(self, captions, video_ids, sos_ix, eos_ix, n=4, sigma=6.0, device=None, vocab_size=None):
+        if n != KEY_TOKENS:
+            raise ValueError("the n-gram keys and the kernel are laid out for n = %d, got %d" % (KEY_TOKENS, n))
+        if vocab_size is not None and vocab_size > (1 << KEY_BITS):
+            raise ValueError("vocab_size %d: n-gram keys hold token ids below %d" % (vocab_size, 1 << KEY_BITS))
+        from . import capi
+        self.n, self.sigma, self.sos_ix, self.eos_ix = n, sigma, sos_ix, eos_ix
+        base = CiderRewarder(captions, video_ids, sos_ix, eos_ix, n, sigma)
+        df, log_n = base.df, base.log_n
+        self.video_ids = list(video_ids)
+        self.row_of = {v: i for i, v in enumerate(self.video_ids)}
+        idf = sorted((pack_key(g), log_n - np.log(max(1.0, df.get(g, 0.0)))) for g in df)
+        clip_ref_off, ent_off, ent_keys, ent_w, ref_norm, ref_len = [0], [0], [], [], [], []
+        for v in self.video_ids:
+            if not base.refs[v]:
+                raise ValueError("clip %r has no reference caption" % (v,))
+            for counts in base.refs[v]:
+                vec, norm, length = cider_vector(counts, df, log_n, n)
+                for k in range(n):
+                    ent = sorted((pack_key(g), w) for g, w in vec[k].items())
+                    ent_keys += [e[0] for e in ent]
+                    ent_w += [e[1] for e in ent]
+                    ent_off.append(len(ent_keys))
+                ref_norm += [float(x) for x in norm]
+                ref_len.append(int(length))
+            clip_ref_off.append(len(ref_len))
+        n_pen = max(max(ref_len), capi.CIDER_MAX_T) + 1          # every |candidate length - reference length| that can occur
+        pen = [np.e ** (-(float(d) ** 2) / (2 * sigma ** 2)) for d in range(n_pen)]
+        self.host = {
+            "idf_keys": np.array([e[0] for e in idf], dtype=np.uint64), "idf_vals": np.array([e[1] for e in idf], dtype=np.float64),
+            "clip_ref_off": np.array(clip_ref_off, dtype=np.int32), "ent_off": np.array(ent_off, dtype=np.int32),
+            "ent_keys": np.array(ent_keys, dtype=np.uint64), "ent_w": np.array(ent_w, dtype=np.float64),
+            "ref_norm": np.array(ref_norm, dtype=np.float64), "ref_len": np.array(ref_len, dtype=np.int32),
+            "pen": np.array(pen, dtype=np.float64)}
+        self.log_n = float(log_n)
+        self._dev = None            # (device, tensors, capi.CiderTable)
+        if device is not None:
+            self._upload(torch.device(device))
+
+    def _upload(self, device):
+        from . import capi
+        if device.type != "cuda":
+            raise capi.S2VTHipError("DeviceCiderRewarder scores on a HIP device, got %s (CiderRewarder is the host scorer)" % (device,))
+        # torch has no arithmetic on uint64: the keys travel as the same bits in int64
+        tens = {k: torch.from_numpy(a.view(np.int64) if a.dtype == np.uint64 else a).to(device) for k, a in self.host.items()}
+        tb = capi.CiderTable()
+        for k, t in tens.items():
+            setattr(tb, k, t.data_ptr())
+        tb.log_n, tb.n_idf = self.log_n, len(self.host["idf_keys"])
+        tb.n_clips, tb.n_refs, tb.n_pen = len(self.video_ids), len(self.host["ref_len"]), len(self.host["pen"])
+        self._dev = (tens["pen"].device, tens, tb)         # the tensors keep the pointers of tb alive
+
+    def rewards(self, video_ids, ids):
+        """fp64 HIP tensor [B]: the score of each row of `ids` (HIP int64 [B, T], contiguous or row-strided) against the references
+        of its clip.  Host work: B dictionary look-ups (KeyError for an unknown clip) and one small copy of the row numbers."""
+        from . import ops
+        from .functional import require_hip
+        require_hip(ids, "ids")
+        rows = [self.row_of[v] for v in video_ids]
+        if self._dev is None or self._dev[0] != ids.device:
+            self._upload(ids.device)
+        clip_rows = torch.tensor(rows, dtype=torch.int32).to(ids.device, non_blocking=True)
+        return ops.cider_rewards(self._dev[2], clip_rows, ids, self.sos_ix, self.eos_ix)
+
+    def table_walk(self, video_id, tokens):
+        """the kernel's walk over the flat arrays in numpy (float64), on the host copy: what s2vt_cider_rewards computes for one row"""
+        h = self.host
+        words = strip_caption(tokens, self.sos_ix, self.eos_ix)
+        keys = np.array([pack_key(words[i:i + k]) for k in range(1, self.n + 1) for i in range(len(words) - k + 1)], dtype=np.uint64)
+        uniq, tf = np.unique(keys, return_counts=True)
+        order = np.array([len(unpack_key(u)) for u in uniq], dtype=np.int64)
+        at = np.searchsorted(h["idf_keys"], uniq)
+        w = np.empty(len(uniq), dtype=np.float64)
+        for i in range(len(uniq)):
+            hit = at[i] < len(h["idf_keys"]) and h["idf_keys"][at[i]] == uniq[i]
+            w[i] = float(tf[i]) * (h["idf_vals"][at[i]] if hit else self.log_n)
+        hn = [np.sqrt(sum(x * x for x in w[order == k + 1])) for k in range(self.n)]
+        hl = max(len(words) - 1, 0)
+        c = self.row_of[video_id]
+        r0, r1 = int(h["clip_ref_off"][c]), int(h["clip_ref_off"][c + 1])
+        total = np.zeros(self.n)
+        for r in range(r0, r1):
+            pen = h["pen"][abs(hl - int(h["ref_len"][r]))]
+            for k in range(self.n):
+                lo, hi = int(h["ent_off"][4 * r + k]), int(h["ent_off"][4 * r + k + 1])
+                rk, rw = h["ent_keys"][lo:hi], h["ent_w"][lo:hi]
+                dot = 0.0
+                for i in np.nonzero(order == k + 1)[0]:
+                    j = int(np.searchsorted(rk, uniq[i]))
+                    if j < len(rk) and rk[j] == uniq[i]:
+                        dot += min(w[i], rw[j]) * rw[j]
+                rn = h["ref_norm"][4 * r + k]
+                if hn[k] != 0 and rn != 0:
+                    dot /= hn[k] * rn
+                total[k] += dot * pen
+        return float(np.mean(total) / (r1 - r0) * 10.0)

@@ -61,8 +61,72 @@ def parse(argv=None):
                          "and the sampled tokens' log-likelihood is weighted with reward(sampled) - reward(greedy) "
                          "(utils.RewardCriterion).  Start from a cross-entropy-trained --init-state.  Single process.")
     ap.add_argument("--sc-temperature", type=float, default=1.0, help="temperature of the sampled caption (--self-critical)")
+    ap.add_argument("--sc-reward", choices=("host", "device"), default="host",
+                    help="where --self-critical scores the captions.  host: self_critical.CiderRewarder on the CPU, between two copies "
+                         "of the ids.  device: self_critical.DeviceCiderRewarder - the reference table is built once and lives on the "
+                         "card, the rewards, the <sos>-prefixed captions and the advantage weights come from HIP kernels "
+                         "(s2vt_cider_rewards, s2vt_sc_weights) and the ids never leave the device")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
     return ap.parse_args(argv)
+
+
+def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
+                            reducer=None):
+    """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
+    train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
+    (every phase ends with a device synchronisation), hist["reward_sample"] / ["reward_greedy"] the batch means.  sc_reward
+    "host": rewarder is a CiderRewarder and the ids make a round trip through the host; "device": a DeviceCiderRewarder, and
+    nothing but the two batch means leaves the card."""
+    from s2vt_video_caption_amd import dp, ops
+    from s2vt_video_caption_amd.self_critical import advantage_weights
+
+    def host_step(feats, ids):
+        sp = hist["sc_split_ms"]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            sampled = model(feats, mode='sample', temperature=temperature).cpu()
+        t1 = time.perf_counter()
+        with torch.no_grad():
+            greedy = model(feats, mode='test').cpu()
+        t2 = time.perf_counter()
+        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
+        weight = advantage_weights(sampled, r_s - r_g, eos).to(dev)
+        caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
+        t3 = time.perf_counter()
+        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
+        t4 = time.perf_counter()
+        for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
+            sp[k] += 1e3 * v
+        sp["steps"] += 1
+        hist["reward_sample"].append(float(r_s.mean()))
+        hist["reward_greedy"].append(float(r_g.mean()))
+        return loss
+
+    def device_step(feats, ids):
+        sp = hist["sc_split_ms"]
+        t0 = time.perf_counter()
+        with torch.no_grad():
+            sampled = model(feats, mode='sample', temperature=temperature)
+        torch.cuda.synchronize(dev)
+        t1 = time.perf_counter()
+        with torch.no_grad():
+            greedy = model(feats, mode='test')
+        torch.cuda.synchronize(dev)
+        t2 = time.perf_counter()
+        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
+        caps, weight = ops.sc_weights(sampled, r_s, r_g, sos, eos)
+        means = torch.stack([r_s.mean(), r_g.mean()]).tolist()          # the phase's synchronisation
+        t3 = time.perf_counter()
+        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
+        t4 = time.perf_counter()
+        for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
+            sp[k] += 1e3 * v
+        sp["steps"] += 1
+        hist["reward_sample"].append(means[0])
+        hist["reward_greedy"].append(means[1])
+        return loss
+
+    return device_step if sc_reward == "device" else host_step
 
 
 def run(opt):
@@ -145,35 +209,21 @@ def run(opt):
         if world > 1 or opt.model != "s2vt":
             raise NotImplementedError("--self-critical runs S2VT in a single process")
         from utils import RewardCriterion
-        from s2vt_video_caption_amd.self_critical import CiderRewarder, advantage_weights
+        from s2vt_video_caption_amd.self_critical import CiderRewarder, DeviceCiderRewarder
         sos, eos = word2ix['<sos>'], word2ix['<eos>']
-        rewarder = CiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos)
+        if opt.sc_reward == "device":
+            rewarder = DeviceCiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, device=dev,
+                                           vocab_size=len(word2ix))
+        else:
+            rewarder = CiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos)
         reward_criterion = RewardCriterion()
         # wall-clock split of the self-critical steps (ms, summed over the run; each phase ends with a device synchronisation)
         hist["sc_split_ms"] = {"sample": 0.0, "greedy": 0.0, "scoring": 0.0, "train": 0.0, "steps": 0}
         hist["reward_sample"], hist["reward_greedy"] = [], []
 
-    def self_critical_step(feats, ids):
-        sp = hist["sc_split_ms"]
-        t0 = time.perf_counter()
-        with torch.no_grad():
-            sampled = model(feats, mode='sample', temperature=opt.sc_temperature).cpu()
-        t1 = time.perf_counter()
-        with torch.no_grad():
-            greedy = model(feats, mode='test').cpu()
-        t2 = time.perf_counter()
-        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
-        weight = advantage_weights(sampled, r_s - r_g, eos).to(dev)
-        caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
-        t3 = time.perf_counter()
-        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
-        t4 = time.perf_counter()
-        for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
-            sp[k] += 1e3 * v
-        sp["steps"] += 1
-        hist["reward_sample"].append(float(r_s.mean()))
-        hist["reward_greedy"].append(float(r_g.mean()))
-        return loss
+    if rewarder is not None:
+        self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
+                                                     opt.sc_reward, reducer)
 
     def save(name):
         if rank == 0:
