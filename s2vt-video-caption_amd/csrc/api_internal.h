@@ -86,6 +86,7 @@ static inline bool batch_pads(int B, bool decode = false) {
     return option(O_GEMM_MODE) != 0 && B % 64 != 0 && B >= (from > 0 ? from : 1);
 }
 static inline bool dims_ok(const s2vt_dims* d) { return d && d->B > 0 && d->L > 1 && d->F > 0 && d->H > 0 && d->E > 0 && d->V > 0; }
+static inline int pad64(int x) { return (x + 63) / 64 * 64; }
 
 // ---- options as the drivers read them (csrc/options.hip)
 static inline int pipe_block() { return option(O_PIPE_BLOCK); }      // timesteps per pipeline block; 0 = both layers on the caller's stream
@@ -112,6 +113,27 @@ static inline bool persist_x3_bwd_on(int B, int H) {
     const int m = option(O_PERSIST_X3_BWD);
     if (m == 0 || !persist_on()) return false;
     return m == 1 || lstm_seq_bwd_x3_persist_supported(B, H) == 1;
+}
+// Which recurrence the whole-path train drivers run for (B, H) under the current modes and options - the ONE statement of it: the
+// drivers (api_train.hip) switch on it and s2vt_recurrence_plan reports it (the enum's values are that entry point's).  The plane
+// drivers run at B % 64 == 0 in gemm modes 1 and 3; everything else is the fp32-MFMA driver's launches per timestep.  A driver ANDs
+// on what only it knows (its workspace provides the images / rings, the bf16 images' k paddings match) and falls back to
+// REC_PER_STEP otherwise.  carve_train's predicates are deliberately broader and free of device queries (a workspace-size function
+// works without a GPU): wherever this plan selects a persistent kernel, the workspace has been carved for it.
+enum RecKind { REC_PER_STEP = 0, REC_BF16_PERSIST = 1, REC_X3_PERSIST = 3 };
+struct RecurrencePlan { RecKind fwd, bwd; };
+static inline RecurrencePlan train_recurrence_plan(int B, int H) {
+    RecurrencePlan pl = {REC_PER_STEP, REC_PER_STEP};
+    const int gm = gemm_mode();
+    if (pipe_block() <= 0 || gm == 0 || B % 64 != 0) return pl;
+    if (gm == 1) {
+        if (persist_on() && lstm_seq_fwd_bf16_persist_supported(B, H, pad64(H))) pl.fwd = REC_BF16_PERSIST;
+        if (persist_on() && lstm_seq_bwd_bf16_persist_supported(B, H, pad64(4 * H))) pl.bwd = REC_BF16_PERSIST;
+    } else if (H <= 1024) {
+        if (persist_x3_fwd_on() && lstm_seq_fwd_x3_persist_supported(B, H)) pl.fwd = REC_X3_PERSIST;
+        if (persist_x3_bwd_on(B, H) && lstm_seq_bwd_x3_persist_supported(B, H)) pl.bwd = REC_X3_PERSIST;
+    }
+    return pl;
 }
 // the recurrence options that decide how a train workspace is carved and which images a forward leaves in it
 static inline int persist_bits() { return persist_mode() | (persist_x3_fwd_on() ? 2 : 0) | (option(O_PERSIST_X3_BWD) << 2); }
@@ -140,7 +162,6 @@ int balanced_block(int L, int blk);
 std::vector<int> pipe_bounds(int T, int L, int blk);
 
 extern int XP;            // planes per operand of the running plane driver (3 or 1); set by the entry points
-static inline int pad64(int x) { return (x + 63) / 64 * 64; }
 struct PB { unsigned short* p; int64_t ld; int kpad; };       // packed planes of a k-major operand [rows][k]
 // element offset of k index k0 (a multiple of 64) inside an operand: row layout (1 plane) k0; blocked 3-plane layout
 // (gemm_x3.hip) k0/16 records of 3072 elements

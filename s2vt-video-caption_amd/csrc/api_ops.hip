@@ -424,16 +424,9 @@ extern "C" int s2vt_experiment_set_stamps(unsigned long long* buf, int block) { 
 // 0 = one launch per timestep, 1 = persistent bf16, 2 = persistent exact-fp32 MFMA, 3 = persistent split precision.
 int s2vt_recurrence_plan(int32_t B, int32_t H, int32_t* fwd, int32_t* bwd) {
     S2VT_REQUIRE(B > 0 && H > 0 && fwd && bwd, "s2vt_recurrence_plan: bad arguments");
-    *fwd = *bwd = 0;
-    const int gm = gemm_mode();
-    if (pipe_block() <= 0 || gm == 0 || B % 64 != 0) return 0;     // (the plane drivers run at B % 64 == 0 in gemm modes 1 and 3)
-    if (gm == 1) {
-        if (persist_on() && lstm_seq_fwd_bf16_persist_supported(B, H, pad64(H))) *fwd = 1;
-        if (persist_on() && lstm_seq_bwd_bf16_persist_supported(B, H, pad64(4 * H))) *bwd = 1;
-        return 0;
-    }
-    if (H <= 1024 && persist_x3_fwd_on() && lstm_seq_fwd_x3_persist_supported(B, H)) *fwd = 3;
-    if (H <= 1024 && persist_x3_bwd_on(B, H) && lstm_seq_bwd_x3_persist_supported(B, H)) *bwd = 3;
+    const RecurrencePlan pl = train_recurrence_plan(B, H);
+    *fwd = pl.fwd;
+    *bwd = pl.bwd;
     return 0;
 }
 

@@ -43,7 +43,7 @@ static TrainWS carve_train(const s2vt_dims& d, void* base) {
     w.psync_b = c.take<unsigned int>(lstm_persist_sync_bytes() / sizeof(unsigned int));
     w.xkp = (H <= 1024) ? (int64_t)((H + 63) / 64 * 64) : 0;
     // images of the split-precision persistent forward: only where that kernel can be selected (the shape / mode part of
-    // train_forward_x3's predicate - no device query here: s2vt_train_workspace_bytes has no side effect and works without a
+    // train_recurrence_plan's predicate - no device query here: s2vt_train_workspace_bytes has no side effect and works without a
     // GPU); the bf16 configuration (gemm mode 1) and the fp32-MFMA mode never read them (0.5 GB at B = 256)
     w.xfwd = w.xkp > 0 && gemm_mode() == 3 && B % 64 == 0 && pipe_block() > 0 && persist_x3_fwd_on();
     w.xw1 = c.take<unsigned short>(w.xfwd ? 3 * 4 * H * w.xkp : 0);
@@ -181,21 +181,6 @@ static int check_forward_record(const void* ws, const s2vt_dims& d, bool planes,
     return 0;
 }
 
-// out_mask: optional out_drop mask (S2VTModel.py:79), time-major [(L-1)*B, H], entries 0 or 1/(1-p); nullptr = no dropout.
-// The masked decode-step hidden states replace the row planes of the logits GEMM (the recurrence is done with them by then).
-// (the weight-gradient GEMMs read the UNMASKED rows of q.h2r transposed in the backward, so the masked rows go to the scratch
-// image q.h2decB - which the backward fills itself before it reads it - and *a_img / *a_row0 name the logits GEMM's operand)
-static int masked_logits_planes(const Lane& ln, const TrainWS& w, const PlaneWS& q, const float* out_mask, int B, int L, int H,
-                                const PB** a_img, int* a_row0) {
-    *a_img = &q.h2r; *a_row0 = L * B;
-    if (!out_mask) return 0;
-    const int R = (L - 1) * B;
-    int rc;
-    if ((rc = mul_vectors(ln.s, w.h2 + (int64_t)L * B * H, out_mask, w.dh2dec, (int64_t)R * H))) return rc;   // dh2dec: free in the forward
-    *a_img = &q.h2decB; *a_row0 = 0;
-    return psplit(ln, **a_img, *a_row0, w.dh2dec, H, ID, R, H);
-}
-
 // The part of a graph key that follows the run-time options: the value of EVERY entry of the option table (a schedule option added
 // later is in the key without anyone having to remember it), the thread's CU plan cap and the test hook s2vt_test_lane_delay
 static void key_options(std::vector<uint64_t>& key) {
@@ -205,31 +190,251 @@ static void key_options(std::vector<uint64_t>& key) {
     key.push_back((uint64_t)g_lane_delay_us);
 }
 
+// One k16 record of the blocked 3-plane layout (gemm_x3.hip) - 16 k columns of a 64-row block: [3 planes][2 halves of 8 columns][64 rows]
+// 16-byte slots of 8 bf16 elements
+static constexpr size_t K16_HALF_ELEMS = 64 * 8;                        // 512 elements = 1024 bytes
+static constexpr size_t K16_REC_ELEMS = 3 * 2 * K16_HALF_ELEMS;         // 3072 elements = 6144 bytes
+
+// What a BPTT schedule reports to the shared tail of train_backward_x3
+struct BpttDone {
+    int bias_chunk = 64;      // rows per partial column sum of dG (32: written by the persistent split-precision BPTT itself)
+    int hh1_t0 = 0;           // dW_hh1's timesteps >= hh1_t0 are done already (0: none)
+    long word_grads_ev = -1;  // event behind word_rnn's weight-gradient GEMMs, if the schedule ran them itself (on lane B) ...
+    long demb_ev = -1;        // ... and behind the embedded-word gradient GEMM
+};
+
+// What every schedule of the plane drivers works with - dims, the parameter / gradient / workspace views, the two lanes (la: the caller's
+// stream st, lb: the side stream sx; the same stream when pipe_block is 0), the running event index, the pipeline's block bounds -
+// and the call shapes the schedules share.  Lives on the stack of one train_forward_x3 / train_backward_x3 call.
+struct TrainDriver {
+    const s2vt_params* p; const s2vt_grads* g; const TrainWS& w; const PlaneWS& q;
+    const float* out_mask; float* logits;       // (logits: forward only)
+    const int B, L, F, H, E, V, T, R, blk;
+    const int64_t BH, B4H;
+    const bool bf;                    // bf16 mode: the bf16 timestep kernels write the h / dG planes themselves
+    const bool emit;                  // the persistent x3 BPTT hands dG over as the GEMMs' row-plane image itself (see x3_bptt_begin)
+    hipStream_t st, sx;
+    Lane la, lb;
+    size_t ev = 0;
+    std::vector<int> bd;
+    TrainDriver(const s2vt_dims* d, const s2vt_params* p_, const s2vt_grads* g_, const TrainWS& w_, const PlaneWS& q_, hipStream_t st_,
+                const float* out_mask_, float* logits_)
+        : p(p_), g(g_), w(w_), q(q_), out_mask(out_mask_), logits(logits_), B(d->B), L(d->L), F(d->F), H(d->H), E(d->E), V(d->V),
+          T(2 * d->L - 1), R((d->L - 1) * d->B), blk(pipe_block()), BH((int64_t)d->B * d->H), B4H(4 * (int64_t)d->B * d->H), bf(XP == 1),
+          emit(d->H % 8 == 0), st(st_), sx(st_) {}
+    int open_lanes() {
+        int rc;
+        if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
+        la = Lane{st, w.gws_a, w.gws_floats, w.colsum_a};
+        lb = Lane{sx, w.gws_b, w.gws_floats, w.colsum_b};
+        return 0;
+    }
+    void set_bounds(bool persistent) { bd = pipe_bounds(T, L, persistent ? balanced_block(L, blk) : blk); }
+
+    int hand(hipStream_t from, hipStream_t to) { return handoff(from, to, ev++); }      // `to` waits for everything enqueued on `from`
+    int record(hipStream_t s, long* idx) {      // an event behind everything enqueued on s so far; *idx names it for wait()
+        hipEvent_t e;
+        *idx = (long)ev++;
+        if (const int r = get_event((size_t)*idx, &e)) return r;
+        S2VT_HIP(hipEventRecord(e, s));
+        return 0;
+    }
+    int wait(hipStream_t s, long idx) {
+        hipEvent_t e;
+        if (const int r = get_event((size_t)idx, &e)) return r;
+        S2VT_HIP(hipStreamWaitEvent(s, e, 0));
+        return 0;
+    }
+    // zero `elems` elements from element `first` on of every 64-row block of a blocked 3-plane image, on the caller's stream
+    int zero_k16(const PB& img, size_t first, size_t elems) {
+        S2VT_HIP(hipMemset2DAsync(img.p + first, (size_t)64 * img.ld * 2, 0, elems * 2, (size_t)(T * B / 64), st));
+        return 0;
+    }
+    // ---- forward
+    // vid_out half of word_rnn's gate input for the steps [t0, t1): rows < L get the biases here, rows >= L accumulate onto the
+    // embedded-word half                                                                                   S2VTModel.py:75-77
+    int vid_half_gemm(const Lane& ln, int t0, int t1) {
+        const bool cap = t0 >= L;
+        return pgemm(ln, (t1 - t0) * B, 4 * H, H, q.h1, t0 * B, 0, q.wv, 0, 0, w.s2 + t0 * B4H, 4 * H, ID, cap ? nullptr : w.bsum2, cap);
+    }
+    // logits of the decode steps >= first_step.  out_mask: optional out_drop mask (S2VTModel.py:79), time-major [(L-1)*B, H], entries 0
+    // or 1/(1-p); nullptr = no dropout.  The masked decode-step hidden states replace the row planes of the logits GEMM (the recurrence
+    // is done with them by then).  (the weight-gradient GEMMs read the UNMASKED rows of q.h2r transposed in the backward, so the masked
+    // rows go to the scratch image q.h2decB - which the backward fills itself before it reads it)
+    // (decode step t' of row (t', b) lands in logits row b (L-1) + t': a range of steps from t'0 on = the same row map, t'0 rows further)
+    int logits_gemm(const Lane& ln, int first_step) {
+        const PB* a = &q.h2r;
+        int a0 = L * B, rc;
+        if (out_mask) {
+            if ((rc = mul_vectors(ln.s, w.h2 + (int64_t)L * B * H, out_mask, w.dh2dec, (int64_t)R * H))) return rc;   // dh2dec: free in the forward
+            a = &q.h2decB; a0 = 0;
+            if ((rc = psplit(ln, *a, a0, w.dh2dec, H, ID, R, H))) return rc;
+        }
+        return pgemm(ln, R - first_step * B, V, H, *a, a0 + first_step * B, 0, q.wo, 0, 0, logits + (int64_t)first_step * V, V, perm(B, L - 1),
+                     p->out_b, false);
+    }
+    int fwd_x3_persistent(int f_cus, int tenths, int gxe_c);
+    int fwd_bf16_persistent();
+    int fwd_two_lanes();
+
+    // ---- backward (layer 2 = word_rnn: dG2 / colsum_a, layer 1 = vid_rnn: dG1 / colsum_b)
+    // dG of the steps [t0, t1) of a layer: row planes (dh1, d-embedding and - read transposed - weight-gradient GEMMs; want_planes = false:
+    // the BPTT kernel wrote them) and the bias-gradient partial sums over 64 rows, all from one read
+    int split_dg_block(const Lane& ln, int layer, int t0, int t1, bool want_planes) {
+        return pdual(ln, (layer == 2 ? w.s2 : w.s1) + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, want_planes ? (layer == 2 ? &q.dg2 : &q.dg1) : nullptr,
+                     t0 * B, nullptr, t0 * B, (layer == 2 ? w.colsum_a : w.colsum_b) + (int64_t)(t0 * B / 64) * 4 * H);
+    }
+    // gradient into vid_out for the steps [t0, t1): dh1 = dG2 . W_v
+    int dh1_gemm(const Lane& ln, int t0, int t1) {
+        return pgemm(ln, (t1 - t0) * B, H, 4 * H, q.dg2, t0 * B, 0, q.wvT, 0, 0, w.dh1 + t0 * BH, H, ID, nullptr, false);
+    }
+    // word_rnn's weight gradients, dW = dG2^T . (h2 | h1 | emb): row planes of both, read transposed
+    int word_weight_grads(const Lane& ln) {
+        int rc;
+        if ((rc = pgemm_tt(ln, 4 * H, H, (T - 1) * B, q.dg2, B, q.h2r, 0, g->word_w_hh, H, ID, nullptr, false))) return rc;
+        if ((rc = pgemm_tt(ln, 4 * H, H, T * B, q.dg2, 0, q.h1, 0, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
+        return pgemm_tt(ln, 4 * H, E, R, q.dg2, L * B, q.emb, 0, g->word_w_ih, E + H, ID, nullptr, false);
+    }
+    // the gradient into the embedded words (the embedding gradient's input)
+    int demb_gemm(const Lane& ln) { return pgemm(ln, R, E, 4 * H, q.dg2, L * B, 0, q.weT, 0, 0, w.de, E, ID, nullptr, false); }
+    SeqBwdX3Args bwd_x3_args(int layer, int t0, int t1) {
+        const bool word = layer == 2;
+        SeqBwdX3Args a = word ? persist_bwd_x3_args(T, t0, t1, B, H, w.xkp, w.xhp, w.xwt2, w.dh2dec, L, w.c2, w.s2, w.dc2, w.xpart2, w.xpslot,
+                                                    w.xnslots, w.psync_a, w.err + 1)
+                              : persist_bwd_x3_args(T, t0, t1, B, H, w.xkp, w.xhp, w.xwt1, w.dh1, 0, w.c1, w.s1, w.dc1, w.xpart1, w.xpslot,
+                                                    w.xnslots, w.psync_b, w.err + 1);
+        if (emit) {
+            a.dgp = word ? q.dg2.p : q.dg1.p; a.lddgp = word ? q.dg2.ld : q.dg1.ld;
+            a.colpart = word ? w.colsum_a : w.colsum_b; a.skip_dg = 1;
+        }
+        return a;
+    }
+    int x3_bptt_begin();
+    int bptt_x3_one_layer(int corun_cus, int corun_k, BpttDone* done);
+    int bptt_x3_two_layer(int corun_cus, int corun_k, BpttDone* done);
+    int bptt_bf16_persistent();
+    int bptt_two_lanes();
+};
+
+// fp32-equivalent persistent schedule (lstm_persist_x3.hip: split precision on the bf16 matrix cores), ONE stream:
+// stage k = vid_rnn block k next to word_rnn block k-1
+// (co-run: the last gxe_c rows of the embedded-word GEMM and the first lg_c decode steps of the logits GEMM run beside the one-layer
+// first / last stage, on the f_cus compute units those leave idle - as dW_o does in the backward)
+int TrainDriver::fwd_x3_persistent(int f_cus, int tenths, int gxe_c) {
+    int rc;
+    if ((rc = hand(sx, st))) return rc;
+    const int nb = (int)bd.size() - 1;
+    // the kernel writes h_t into the GEMMs' row images itself (the hand-off payload's own 16-byte pieces); the k16 records past
+    // the last column slice are zeroed here (H = 1000: units 1008..1023)
+    for (const PB* img : {&q.h1, &q.h2r}) {
+        const size_t kc0 = (size_t)cdiv(H, 16), kc1 = (size_t)(img->kpad / 16);
+        if (kc1 > kc0 && (rc = zero_k16(*img, kc0 * K16_REC_ELEMS, (kc1 - kc0) * K16_REC_ELEMS))) return rc;
+    }
+    // decode steps whose logits run beside the last (word_rnn-only) stage: their h2 rows are final before it starts
+    int lg_c = (nb >= 2 && !out_mask) ? (L - 1) * ((2 * tenths + 1) / 3) / 10 : 0;
+    if (lg_c > bd[nb - 1] - L) lg_c = bd[nb - 1] - L > 0 ? bd[nb - 1] - L : 0;
+    for (int k = 0; k <= nb; ++k) {
+        const bool hv = k < nb, hw = k >= 1;
+        const bool co_first = k == 0 && nb >= 2 && gxe_c > 0, co_last = k == nb && lg_c > 0;
+        if ((co_first || co_last) && (rc = hand(st, sx))) return rc;       // (the part starts with the stage, not before it)
+        {
+        ProfScope ps(st, K_STEP_FWD, (hv ? bd[k + 1] - bd[k] : 0) + (hw ? bd[k] - bd[k - 1] : 0));
+        SeqFwdX3Args av, aw;
+        if (hv) av = persist_fwd_x3_args(bd[k], bd[k + 1], B, H, T, w.xkp, w.s1, L, w.bsum1, w.xw1, w.xh1, w.h1, w.c1, w.psync_a, w.err + 1);
+        if (hw) aw = persist_fwd_x3_args(bd[k - 1], bd[k], B, H, T, w.xkp, w.s2, T, w.bsum2, w.xw2, w.xh2, w.h2, w.c2, w.psync_b, w.err + 1);
+        av.hblk = q.h1.p; av.ldhblk = q.h1.ld;
+        aw.hblk = q.h2r.p; aw.ldhblk = q.h2r.ld;
+        if (hv && hw) rc = lstm_seq_fwd_x3_persist2(st, av, &aw);
+        else rc = lstm_seq_fwd_x3_persist2(st, hv ? av : aw, nullptr);
+        }
+        if (rc) return rc;
+        if (co_first || co_last) {
+            {
+                CuPlanCap cap(f_cus);
+                if (co_first)
+                    rc = pgemm(lb, gxe_c, 4 * H, E, q.emb, R - gxe_c, 0, q.we, 0, 0, w.s2 + (int64_t)L * B4H + (int64_t)(R - gxe_c) * 4 * H, 4 * H,
+                               ID, w.bsum2, false);
+                else
+                    rc = pgemm(lb, lg_c * B, V, H, q.h2r, L * B, 0, q.wo, 0, 0, logits, V, perm(B, L - 1), p->out_b, false);
+            }
+            if (rc || (rc = hand(sx, st))) return rc;
+        }
+        if (hv && (rc = vid_half_gemm(la, bd[k], bd[k + 1]))) return rc;
+    }
+    return logits_gemm(la, lg_c);
+}
+
+// Persistent schedule, ONE stream: the launch of pipeline stage k runs vid_rnn block k next to word_rnn block k-1
+// (lstm_persist.hip: two workgroups per CU, each layer's W_hh slices resident in registers); between two
+// launches the plane split + input GEMM of the vid block just finished run alone on the chip.
+int TrainDriver::fwd_bf16_persistent() {
+    int rc;
+    if ((rc = hand(sx, st))) return rc;              // weight planes / embedded-word half from lane B
+    const int nb = (int)bd.size() - 1;
+    for (int k = 0; k <= nb; ++k) {
+        const bool hv = k < nb, hw = k >= 1;
+        SeqFwdBf16Args av, aw;
+        if (hv) av = persist_fwd_args(bd[k], bd[k + 1], B, H, w.s1, L, w.bsum1, q.whh1, q.h1, w.h1, w.c1, w.psync_a, w.err + 1);
+        if (hw) aw = persist_fwd_args(bd[k - 1], bd[k], B, H, w.s2, T, w.bsum2, q.whh2, q.h2r, w.h2, w.c2, w.psync_b, w.err + 1);
+        {
+            ProfScope ps(st, K_STEP_FWD, (hv ? bd[k + 1] - bd[k] : 0) + (hw ? bd[k] - bd[k - 1] : 0));
+            if (hv && hw) rc = lstm_seq_fwd_bf16_persist2(st, av, &aw);
+            else rc = lstm_seq_fwd_bf16_persist2(st, hv ? av : aw, nullptr);
+            if (rc) return rc;
+        }
+        if (hv && (rc = vid_half_gemm(la, bd[k], bd[k + 1]))) return rc;
+    }
+    return logits_gemm(la, 0);
+}
+
+// Launches per timestep, two lanes: vid_rnn block k on the caller's stream next to word_rnn block k-1 on the side lane
+int TrainDriver::fwd_two_lanes() {
+    int rc;
+    for (size_t k = 0; k + 1 < bd.size(); ++k) {
+        const int t0 = bd[k], t1 = bd[k + 1];
+        rc = bf ? seq_fwd_bf16(st, t0, t1, B, H, w.s1, L, w.bsum1, q.whh1, q.h1, w.h1, w.c1)
+                : seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true);
+        if (rc) return rc;
+        if ((rc = hand(st, sx))) return rc;
+        if ((rc = pdual(lb, w.h1 + t0 * BH, H, ID, (t1 - t0) * B, H, bf ? nullptr : &q.h1, t0 * B, nullptr, t0 * B, nullptr))) return rc;
+        if ((rc = vid_half_gemm(lb, t0, t1))) return rc;
+        rc = bf ? seq_fwd_bf16(sx, t0, t1, B, H, w.s2, T, w.bsum2, q.whh2, q.h2r, w.h2, w.c2)
+                : seq_fwd(sx, t0, t1, B, H, w.s2, T, w.bsum2, p->word_w_hh, w.h2, w.c2, true);
+        if (rc) return rc;
+        // h2 planes: transposed (k = time-major row) for dW_hh2; row planes of the decode steps for the logits GEMM
+        if ((rc = pdual(lb, w.h2 + t0 * BH, H, ID, (t1 - t0) * B, H, bf ? nullptr : &q.h2r, t0 * B, nullptr, t0 * B, nullptr))) return rc;
+    }
+    if ((rc = logits_gemm(lb, 0))) return rc;
+    return hand(sx, st);
+}
+
 static int train_forward_x3(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
                             int64_t targets_ld, float* logits, const TrainWS& w, const PlaneWS& q, hipStream_t st,
                             const float* out_mask) {
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1, R = (L - 1) * B;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
+    TrainDriver x(d, p, nullptr, w, q, st, out_mask, logits);
+    const int B = x.B, L = x.L, F = x.F, H = x.H, E = x.E, V = x.V, T = x.T, R = x.R;
+    const int64_t B4H = x.B4H;
     int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};
-    size_t ev = 0;
+    if ((rc = x.open_lanes())) return rc;
+    const hipStream_t sx = x.sx;
+    const Lane &la = x.la, &lb = x.lb;
+    const bool bf = x.bf;
     if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
     if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
-    const bool bf = (XP == 1);        // bf16 mode: bf16 timestep kernels write the h planes themselves
     if (bf) {   // zero the k padding of the bf16 h row images (valid columns are written by the step kernels)
         if ((rc = zero_pad_cols_u16(st, q.h1.p, (int64_t)T * B, q.h1.ld, H, q.h1.kpad))) return rc;
         if ((rc = zero_pad_cols_u16(st, q.h2r.p, (int64_t)T * B, q.h2r.ld, H, q.h2r.kpad))) return rc;
         if ((rc = pdual(la, p->vid_w_hh, H, ID, 4 * H, H, &q.whh1, 0, &q.whh1T, 0, nullptr))) return rc;
     }
-    if ((rc = handoff(st, sx, ev++))) return rc;
+    if ((rc = x.hand(st, sx))) return rc;
     if (bf && (rc = pdual(lb, p->word_w_hh, H, ID, 4 * H, H, &q.whh2, 0, &q.whh2T, 0, nullptr))) return rc;
-    const bool px3_fwd = !bf && XP == 3 && blk > 0 && w.xfwd && persist_x3_fwd_on() && lstm_seq_fwd_x3_persist_supported(B, H);
+    // the plan, and what only this driver knows: the workspace provides the images / the bf16 images' k paddings match
+    RecKind kind = train_recurrence_plan(B, H).fwd;
+    if (kind == REC_X3_PERSIST && !w.xfwd) kind = REC_PER_STEP;
+    if (kind == REC_BF16_PERSIST && !persist_fwd_ok(B, H, q.whh1, q.h1)) kind = REC_PER_STEP;
+    const bool px3_fwd = kind == REC_X3_PERSIST;
     if (px3_fwd) {   // W_hh of both layers as row-major planes for the persistent split-precision recurrence
         if ((rc = split3_rows(sx, p->vid_w_hh, H, 4 * H, H, (int)w.xkp, w.xw1, 4 * (int64_t)H * w.xkp))) return rc;
         if ((rc = split3_rows(sx, p->word_w_hh, H, 4 * H, H, (int)w.xkp, w.xw2, 4 * (int64_t)H * w.xkp))) return rc;
@@ -240,11 +445,10 @@ static int train_forward_x3(const s2vt_dims* d, const s2vt_params* p, const floa
     if ((rc = pdual(lb, p->word_w_ih + E, E + H, ID, 4 * H, H, &q.wv, 0, &q.wvT, 0, nullptr))) return rc;
     if ((rc = pdual(lb, p->out_w, H, ID, V, H, &q.wo, 0, &q.woT, 0, nullptr))) return rc;
     if ((rc = pdual(lb, p->emb_w, E, gather(w.tok), R, E, &q.emb, 0, nullptr, 0, nullptr))) return rc;
-    // (co-run: the last gxe_c rows of this GEMM and the first lg_c decode steps of the logits GEMM run beside the one-layer first /
-    // last stage of the persistent schedule below, on the compute units those leave idle - as dW_o does in the backward)
+    // (co-run of the persistent x3 schedule, see fwd_x3_persistent: the last gxe_c rows of this GEMM run beside its first stage)
     const int f_wgs = px3_fwd ? lstm_seq_fwd_x3_persist_single_workgroups(B, H) : 0;
     const int f_cus = f_wgs > 0 ? (planned_compute_units() - f_wgs - 2) / 8 * 8 : 0;
-    const bool stages3 = px3_fwd && pipe_bounds(T, L, balanced_block(L, blk)).size() >= 3;      // at least two blocks: one-layer first / last stages
+    const bool stages3 = px3_fwd && pipe_bounds(T, L, balanced_block(L, x.blk)).size() >= 3;      // at least two blocks: one-layer first / last stages
     const int tenths = (stages3 && sx != st && f_cus >= 64 && R >= 2560 && B % 64 == 0) ? option(O_CORUN) : 0;
     const int gxe_c = (R / 64 * (2 * tenths < 8 ? 2 * tenths : 8) / 10) * 64;
     if ((rc = pgemm(lb, R - gxe_c, 4 * H, E, q.emb, 0, 0, q.we, 0, 0, w.s2 + (int64_t)L * B4H, 4 * H, ID, w.bsum2, false))) return rc;
@@ -255,143 +459,227 @@ static int train_forward_x3(const s2vt_dims* d, const s2vt_params* p, const floa
     if ((rc = pgemm(la, B * L, H, F, q.feats, 0, 0, q.wf, 0, 0, w.x1, H, perm(L, B), p->feat_b, false))) return rc;
     if ((rc = pdual(la, w.x1, H, ID, L * B, H, &q.x1, 0, nullptr, 0, nullptr))) return rc;
     if ((rc = pgemm(la, L * B, 4 * H, H, q.x1, 0, 0, q.wih1, 0, 0, w.s1, 4 * H, ID, w.bsum1, false))) return rc;
-    const bool pbf_fwd = bf && blk > 0 && persist_fwd_ok(B, H, q.whh1, q.h1);
-    const std::vector<int> bd = pipe_bounds(T, L, (pbf_fwd || px3_fwd) ? balanced_block(L, blk) : blk);
-    if (px3_fwd) {
-        // fp32-equivalent persistent schedule (lstm_persist_x3.hip: split precision on the bf16 matrix cores), ONE stream:
-        // stage k = vid_rnn block k next to word_rnn block k-1
-        if ((rc = handoff(sx, st, ev++))) return rc;
-        const int nb = (int)bd.size() - 1;
-        // the kernel writes h_t into the GEMMs' row images itself (the hand-off payload's own 16-byte pieces); the k16 records past
-        // the last column slice are zeroed here (H = 1000: units 1008..1023)
-        for (const PB* img : {&q.h1, &q.h2r}) {
-            const size_t kc0 = (size_t)cdiv(H, 16), kc1 = (size_t)(img->kpad / 16);
-            if (kc1 > kc0) S2VT_HIP(hipMemset2DAsync(img->p + kc0 * 3072, (size_t)64 * img->ld * 2, 0, (kc1 - kc0) * 6144, (size_t)(T * B / 64), st));
-        }
-        // decode steps whose logits run beside the last (word_rnn-only) stage: their h2 rows are final before it starts
-        int lg_c = (nb >= 2 && !out_mask) ? (L - 1) * ((2 * tenths + 1) / 3) / 10 : 0;
-        if (lg_c > bd[nb - 1] - L) lg_c = bd[nb - 1] - L > 0 ? bd[nb - 1] - L : 0;
-        for (int k = 0; k <= nb; ++k) {
-            const bool hv = k < nb, hw = k >= 1;
-            const bool co_first = k == 0 && nb >= 2 && gxe_c > 0, co_last = k == nb && lg_c > 0;
-            if ((co_first || co_last) && (rc = handoff(st, sx, ev++))) return rc;       // (the part starts with the stage, not before it)
-            {
-            ProfScope ps(st, K_STEP_FWD, (hv ? bd[k + 1] - bd[k] : 0) + (hw ? bd[k] - bd[k - 1] : 0));
-            SeqFwdX3Args av, aw;
-            if (hv) av = persist_fwd_x3_args(bd[k], bd[k + 1], B, H, T, w.xkp, w.s1, L, w.bsum1, w.xw1, w.xh1, w.h1, w.c1, w.psync_a, w.err + 1);
-            if (hw) aw = persist_fwd_x3_args(bd[k - 1], bd[k], B, H, T, w.xkp, w.s2, T, w.bsum2, w.xw2, w.xh2, w.h2, w.c2, w.psync_b, w.err + 1);
-            av.hblk = q.h1.p; av.ldhblk = q.h1.ld;
-            aw.hblk = q.h2r.p; aw.ldhblk = q.h2r.ld;
-            if (hv && hw) rc = lstm_seq_fwd_x3_persist2(st, av, &aw);
-            else rc = lstm_seq_fwd_x3_persist2(st, hv ? av : aw, nullptr);
-            }
-            if (rc) return rc;
-            if (co_first || co_last) {
-                {
-                    CuPlanCap cap(f_cus);
-                    if (co_first)
-                        rc = pgemm(lb, gxe_c, 4 * H, E, q.emb, R - gxe_c, 0, q.we, 0, 0, w.s2 + (int64_t)L * B4H + (int64_t)(R - gxe_c) * 4 * H, 4 * H,
-                                   ID, w.bsum2, false);
-                    else
-                        rc = pgemm(lb, lg_c * B, V, H, q.h2r, L * B, 0, q.wo, 0, 0, logits, V, perm(B, L - 1), p->out_b, false);
-                }
-                if (rc || (rc = handoff(sx, st, ev++))) return rc;
-            }
-            if (hv) {
-                const int t0 = bd[k], t1 = bd[k + 1];
-                const bool cap = t0 >= L;
-                if ((rc = pgemm(la, (t1 - t0) * B, 4 * H, H, q.h1, t0 * B, 0, q.wv, 0, 0, w.s2 + t0 * B4H, 4 * H, ID,
-                                cap ? nullptr : w.bsum2, cap)))
-                    return rc;
-            }
-        }
-        const PB* lg; int lg0;
-        if ((rc = masked_logits_planes(la, w, q, out_mask, B, L, H, &lg, &lg0))) return rc;
-        // (decode step t' of row (t', b) lands in logits row b (L-1) + t': a range of steps from t'0 on = the same row map, t'0 rows further)
-        return pgemm(la, R - lg_c * B, V, H, *lg, lg0 + lg_c * B, 0, q.wo, 0, 0, logits + (int64_t)lg_c * V, V, perm(B, L - 1), p->out_b, false);
+    x.set_bounds(kind != REC_PER_STEP);
+    switch (kind) {
+    case REC_X3_PERSIST: return x.fwd_x3_persistent(f_cus, tenths, gxe_c);
+    case REC_BF16_PERSIST: return x.fwd_bf16_persistent();
+    default: return x.fwd_two_lanes();
     }
-    if (pbf_fwd) {
-        // Persistent schedule, ONE stream: the launch of pipeline stage k runs vid_rnn block k next to word_rnn block k-1
-        // (lstm_persist.hip: two workgroups per CU, each layer's W_hh slices resident in registers); between two
-        // launches the plane split + input GEMM of the vid block just finished run alone on the chip.
-        if ((rc = handoff(sx, st, ev++))) return rc;              // weight planes / embedded-word half from lane B
-        const int nb = (int)bd.size() - 1;
-        for (int k = 0; k <= nb; ++k) {
-            const bool hv = k < nb, hw = k >= 1;
-            SeqFwdBf16Args av, aw;
-            if (hv) av = persist_fwd_args(bd[k], bd[k + 1], B, H, w.s1, L, w.bsum1, q.whh1, q.h1, w.h1, w.c1, w.psync_a, w.err + 1);
-            if (hw) aw = persist_fwd_args(bd[k - 1], bd[k], B, H, w.s2, T, w.bsum2, q.whh2, q.h2r, w.h2, w.c2, w.psync_b, w.err + 1);
-            {
-                ProfScope ps(st, K_STEP_FWD, (hv ? bd[k + 1] - bd[k] : 0) + (hw ? bd[k] - bd[k - 1] : 0));
-                if (hv && hw) rc = lstm_seq_fwd_bf16_persist2(st, av, &aw);
-                else rc = lstm_seq_fwd_bf16_persist2(st, hv ? av : aw, nullptr);
-                if (rc) return rc;
-            }
-            if (hv) {   // vid_out half of the word_rnn gate input for block k
-                const int t0 = bd[k], t1 = bd[k + 1];
-                const bool cap = t0 >= L;
-                if ((rc = pgemm(la, (t1 - t0) * B, 4 * H, H, q.h1, t0 * B, 0, q.wv, 0, 0, w.s2 + t0 * B4H, 4 * H, ID,
-                                cap ? nullptr : w.bsum2, cap)))
-                    return rc;
-            }
+}
+
+// W_hh^T of both layers as planes (each on the lane that transposed it), then the caller's stream takes over: both x3 BPTT schedules
+// run their persistent launches on ONE stream
+int TrainDriver::x3_bptt_begin() {
+    int rc;
+    if ((rc = split3_wt(st, w.wt2, H, (int)w.xkp, (int)w.xhp, w.xwt2, w.xkp * 4 * w.xhp))) return rc;
+    if ((rc = split3_wt(sx, w.wt1, H, (int)w.xkp, (int)w.xhp, w.xwt1, w.xkp * 4 * w.xhp))) return rc;
+    if ((rc = hand(sx, st))) return rc;               // W_hh1^T and the out_linear gradients of lane B
+    // The kernel hands dG over as the GEMMs' row-plane image itself (+ its 32-row column sums for the bias gradients): its dG tile
+    // is in LDS as planes anyway - no split pass reads dG back, the fp32 dG is never stored.  (H % 8: a 16-byte slot of the image
+    // holds 8 consecutive units of one gate.)  The k padding [4H, pad64(4H)) of both images is zeroed here once per backward.
+    if (emit && q.dg2.kpad > 4 * H) {
+        const size_t kc0 = (size_t)(4 * H / 16), kc1 = (size_t)(q.dg2.kpad / 16);       // k16 records [kc0, kc1) of every 64-row block
+        const size_t first = (4 * H % 16) ? kc0 + 1 : kc0;                              // (4H % 16 == 8: the straddling record's upper half
+        for (const PB* img : {&q.dg2, &q.dg1}) {                                        //  is zeroed piece by piece below)
+            if (kc1 > first && (rc = zero_k16(*img, first * K16_REC_ELEMS, (kc1 - first) * K16_REC_ELEMS))) return rc;
+            if (4 * H % 16)
+                for (int pl = 0; pl < 3; ++pl)
+                    if ((rc = zero_k16(*img, kc0 * K16_REC_ELEMS + (pl * 2 + 1) * K16_HALF_ELEMS, K16_HALF_ELEMS))) return rc;
         }
-        const PB* lg; int lg0;
-        if ((rc = masked_logits_planes(la, w, q, out_mask, B, L, H, &lg, &lg0))) return rc;
-        return pgemm(la, R, V, H, *lg, lg0, 0, q.wo, 0, 0, logits, V, perm(B, L - 1), p->out_b, false);
     }
-    for (size_t k = 0; k + 1 < bd.size(); ++k) {
+    return 0;
+}
+
+// ONE layer per launch - word_rnn's blocks, then vid_rnn's (the word_rnn BPTT does not depend on vid_rnn's) - on half of the
+// compute units, and the backward's GEMMs on the other half (lane B, planned for the idle units): beside word_rnn's stages
+// dW_o (cut over k = rows, accumulated in a fixed order) and every finished block's dh1 GEMM; beside vid_rnn's stages
+// word_rnn's weight gradients.  A two-layer stage does two blocks in ~440 us with nothing beside it; two one-layer stages take
+// ~2 x 345 us and give half of the device to GEMMs for that long (profiles/round5_corun.txt).
+int TrainDriver::bptt_x3_one_layer(int corun_cus, int corun_k, BpttDone* done) {
+    int rc;
+    const int nb = (int)bd.size() - 1;
+    if ((rc = hand(st, sx))) return rc;                     // the parts start with the first stage, not beside the dh2 GEMM
+    int wo_r = 0;                                           // next row of dW_o's k range
+    auto wo_part = [&]() -> int {
+        if (wo_r >= R) return 0;
+        int kk = corun_k < R - wo_r ? corun_k : R - wo_r;
+        if (R - wo_r - kk < 512) kk = R - wo_r;
+        const int r = pgemm_tt(lb, V, H, kk, q.dlog, wo_r, q.h2decB, wo_r, g->out_w, H, ID, nullptr, wo_r > 0);
+        wo_r += kk;
+        return r;
+    };
+    std::vector<long> dh1_done((size_t)nb);
+    long wo_done = 0;
+    {
+        CuPlanCap cap(corun_cus);
+        for (int k = nb - 1; k >= 0; --k) {
+            const int t0 = bd[k], t1 = bd[k + 1];
+            {
+                ProfScope ps(st, K_STEP_BWD, t1 - t0);
+                if ((rc = lstm_seq_bwd_x3_persist2(st, bwd_x3_args(2, t0, t1), nullptr))) return rc;
+                ++g_bwd_persist_launches;
+            }
+            if ((rc = wo_part())) return rc;
+            if ((rc = hand(st, sx))) return rc;             // dG2 rows of block k
+            if (!emit && (rc = split_dg_block(lb, 2, t0, t1, true))) return rc;
+            if ((rc = dh1_gemm(lb, t0, t1))) return rc;
+            if ((rc = record(sx, &dh1_done[(size_t)k]))) return rc;
+        }
+        while (wo_r < R)
+            if ((rc = wo_part())) return rc;
+        // (the parts left over when dW_o has more of them than word_rnn has stages: nothing on the caller's stream waits for
+        // the dh1 events behind them, so group 0's release below waits for this one)
+        if ((rc = record(sx, &wo_done))) return rc;
+        // word_rnn's weight gradients (dG2 is complete): beside vid_rnn's stages
+        if ((rc = word_weight_grads(lb))) return rc;
+        if ((rc = record(sx, &done->word_grads_ev))) return rc;     // lane A's tail ends with "word_rnn + embedding gradients final": after these
+        // ... and the gradient into the embedded words
+        if ((rc = demb_gemm(lb))) return rc;
+        if ((rc = record(sx, &done->demb_ev))) return rc;
+    }
+    // dW_hh1 = dG1[t]^T h1[t-1] over t >= hh1_t0 (the blocks vid_rnn's BPTT finishes first) beside its later stages
+    const int kc = nb / 2;
+    const int hh1_t0 = nb >= 4 ? bd[kc] : 0;
+    for (int k = nb - 1; k >= 0; --k) {
         const int t0 = bd[k], t1 = bd[k + 1];
-        if (bf) {
-            if ((rc = seq_fwd_bf16(st, t0, t1, B, H, w.s1, L, w.bsum1, q.whh1, q.h1, w.h1, w.c1))) return rc;
-        } else {
-            if ((rc = seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true))) return rc;
+        if ((rc = wait(st, dh1_done[(size_t)k]))) return rc;
+        ProfScope ps(st, K_STEP_BWD, t1 - t0);
+        if ((rc = lstm_seq_bwd_x3_persist2(st, bwd_x3_args(1, t0, t1), nullptr))) return rc;
+        ++g_bwd_persist_launches;
+        if (!emit && (rc = split_dg_block(la, 1, t0, t1, true))) return rc;
+        if (hh1_t0 > 0 && k == kc) {
+            if ((rc = hand(st, sx))) return rc;             // dG1 rows of the blocks [kc, nb)
+            CuPlanCap cap(corun_cus);
+            if ((rc = pgemm_tt(lb, 4 * H, H, (T - hh1_t0) * B, q.dg1, hh1_t0 * B, q.h1, (hh1_t0 - 1) * B, g->vid_w_hh, H, ID, nullptr, false))) return rc;
         }
-        if ((rc = handoff(st, sx, ev++))) return rc;
-        const bool cap = t0 >= L;
-        if ((rc = pdual(lb, w.h1 + t0 * BH, H, ID, (t1 - t0) * B, H, bf ? nullptr : &q.h1, t0 * B, nullptr, t0 * B, nullptr)))
-            return rc;
-        if ((rc = pgemm(lb, (t1 - t0) * B, 4 * H, H, q.h1, t0 * B, 0, q.wv, 0, 0, w.s2 + t0 * B4H, 4 * H, ID,
-                        cap ? nullptr : w.bsum2, cap)))
-            return rc;
-        if (bf) {
-            if ((rc = seq_fwd_bf16(sx, t0, t1, B, H, w.s2, T, w.bsum2, q.whh2, q.h2r, w.h2, w.c2))) return rc;
-        } else {
-            if ((rc = seq_fwd(sx, t0, t1, B, H, w.s2, T, w.bsum2, p->word_w_hh, w.h2, w.c2, true))) return rc;
-        }
-        // h2 planes: transposed (k = time-major row) for dW_hh2; row planes of the decode steps for the logits GEMM
-        if ((rc = pdual(lb, w.h2 + t0 * BH, H, ID, (t1 - t0) * B, H, bf ? nullptr : &q.h2r, t0 * B, nullptr,
-                        t0 * B, nullptr)))
-            return rc;
     }
-    const PB* lg; int lg0;
-    if ((rc = masked_logits_planes(lb, w, q, out_mask, B, L, H, &lg, &lg0))) return rc;
-    if ((rc = pgemm(lb, R, V, H, *lg, lg0, 0, q.wo, 0, 0, logits, V, perm(B, L - 1), p->out_b, false))) return rc;
-    return handoff(sx, st, ev++);
+    done->bias_chunk = emit ? 32 : 64;
+    done->hh1_t0 = hh1_t0;
+    if ((rc = wait(st, wo_done))) return rc;                // every part of dW_o, including those enqueued after the last stage
+    if ((rc = grads_ready(0, st))) return rc;               // (out_linear's gradients: released behind the last persistent launch)
+    return hand(st, sx);                                    // lane B's vid_rnn gradients need dG1
+}
+
+// fp32-equivalent persistent schedule (split precision: lstm_persist_x3.hip), ONE stream: stage k = word_rnn BPTT of
+// block k next to vid_rnn BPTT of block k+1.  corun_k > 0: dW_o's GEMM is cut over k = rows into three parts, two of which run beside
+// the one-layer first / last stage on the compute units those leave idle, the rest on lane B behind the last stage
+int TrainDriver::bptt_x3_two_layer(int corun_cus, int corun_k, BpttDone* done) {
+    int rc;
+    const int nb = (int)bd.size() - 1;
+    for (int k = nb - 1; k >= -1; --k) {
+        const bool hw = k >= 0, hv = k + 1 <= nb - 1;
+        const bool solo = corun_k && nb >= 2 && (k == nb - 1 || k == -1);      // a one-layer stage: half of the compute units idle
+        if (solo && (rc = hand(st, sx))) return rc;                              // (the part starts with the stage, not before it)
+        {
+            ProfScope ps(st, K_STEP_BWD, (hw ? bd[k + 1] - bd[k] : 0) + (hv ? bd[k + 2] - bd[k + 1] : 0));
+            SeqBwdX3Args aw, av;
+            if (hw) aw = bwd_x3_args(2, bd[k], bd[k + 1]);
+            if (hv) av = bwd_x3_args(1, bd[k + 1], bd[k + 2]);
+            if (hw && hv) rc = lstm_seq_bwd_x3_persist2(st, aw, &av);
+            else rc = lstm_seq_bwd_x3_persist2(st, hw ? aw : av, nullptr);
+            ++g_bwd_persist_launches;
+            if (rc) return rc;
+        }
+        if (solo) {      // dW_o rows [r0, r0 + corun_k) on lane B, planned for the units the stage leaves idle; the caller's stream
+            const int r0 = (k == nb - 1) ? 0 : corun_k;              // goes on when both are done
+            {
+                CuPlanCap cap(corun_cus);
+                if ((rc = pgemm_tt(lb, V, H, corun_k, q.dlog, r0, q.h2decB, r0, g->out_w, H, ID, nullptr, r0 > 0))) return rc;
+            }
+            if ((rc = hand(sx, st))) return rc;
+        }
+        if (hw) {
+            if (!emit && (rc = split_dg_block(la, 2, bd[k], bd[k + 1], true))) return rc;
+            if ((rc = dh1_gemm(la, bd[k], bd[k + 1]))) return rc;
+        }
+        if (hv && !emit && (rc = split_dg_block(la, 1, bd[k + 1], bd[k + 2], true))) return rc;
+    }
+    done->bias_chunk = emit ? 32 : 64;
+    if (!corun_k && (rc = grads_ready(0, st))) return rc;      // (behind the last persistent launch: see bptt_bf16_persistent)
+    if ((rc = hand(st, sx))) return rc;
+    if (corun_k) {      // the rest of dW_o's rows: first thing of lane B's tail, then the out_linear gradients are final
+        const bool two = nb >= 2;
+        const int r0 = two ? 2 * corun_k : 0;
+        if ((rc = pgemm_tt(lb, V, H, R - r0, q.dlog, r0, q.h2decB, r0, g->out_w, H, ID, nullptr, two))) return rc;
+        if ((rc = grads_ready(0, sx))) return rc;
+    }
+    return 0;
+}
+
+// Persistent schedule, ONE stream (mirror of the forward): the launch of stage k runs the word_rnn BPTT of block k
+// next to the vid_rnn BPTT of block k+1 (lstm_persist.hip); between two launches the dG planes / partial column sums
+// of the blocks just finished and the dh1 GEMM of the word block run alone on the chip.
+int TrainDriver::bptt_bf16_persistent() {
+    int rc;
+    if ((rc = hand(sx, st))) return rc;                        // out_linear gradients of lane B first: no GEMM beside
+    const int nb = (int)bd.size() - 1;                         // a persistent launch
+    for (int k = nb - 1; k >= -1; --k) {
+        const bool hw = k >= 0, hv = k + 1 <= nb - 1;
+        SeqBwdBf16Args aw, av;
+        if (hw) aw = seq_bwd_bf16_args(T, bd[k], bd[k + 1], B, H, q.whh2T, q.dg2, w.dh2dec, L, w.c2, w.s2, w.dc2, w.psync_a, w.err + 1);
+        if (hv) av = seq_bwd_bf16_args(T, bd[k + 1], bd[k + 2], B, H, q.whh1T, q.dg1, w.dh1, 0, w.c1, w.s1, w.dc1, w.psync_b, w.err + 1);
+        {
+            ProfScope ps(st, K_STEP_BWD, (hw ? bd[k + 1] - bd[k] : 0) + (hv ? bd[k + 2] - bd[k + 1] : 0));
+            if (hw && hv) rc = lstm_seq_bwd_bf16_persist2(st, aw, &av);
+            else rc = lstm_seq_bwd_bf16_persist2(st, hw ? aw : av, nullptr);
+            ++g_bwd_persist_launches;
+            if (rc) return rc;
+        }
+        if (hw) {
+            if ((rc = split_dg_block(la, 2, bd[k], bd[k + 1], false))) return rc;
+            if ((rc = dh1_gemm(la, bd[k], bd[k + 1]))) return rc;
+        }
+        if (hv && (rc = split_dg_block(la, 1, bd[k + 1], bd[k + 2], false))) return rc;
+    }
+    // Data-parallel overlap: a persistent launch needs every one of its workgroups resident, so no foreign kernel (the
+    // RCCL all-reduce of gradient group 0 on the caller's communication stream) may start beside one and hold LDS /
+    // wave slots on a compute unit.  "Group 0 is final" is therefore re-recorded HERE, behind the last persistent
+    // launch: s2vt_backward_wait_grads(0) then releases the out_linear all-reduce when the recurrence has left the
+    // chip, and it overlaps the weight-gradient GEMMs below instead of the BPTT.
+    if ((rc = grads_ready(0, st))) return rc;
+    return hand(st, sx);                                       // lane B's parameter-gradient GEMMs need dG1
+}
+
+// Launches per timestep, two lanes: word_rnn's BPTT of block k on the caller's stream next to vid_rnn's of block k+1 on the side lane
+int TrainDriver::bptt_two_lanes() {
+    int rc;
+    for (size_t k = bd.size() - 1; k >= 1; --k) {
+        const int t0 = bd[k - 1], t1 = bd[k];
+        rc = bf ? seq_bwd_bf16(st, T, t0, t1, B, H, q.whh2T, w.dh2dec, L, w.c2, w.s2, q.dg2, w.dc2)
+                : seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2);
+        if (rc) return rc;
+        if ((rc = split_dg_block(la, 2, t0, t1, !bf))) return rc;
+        if ((rc = dh1_gemm(la, t0, t1))) return rc;
+        if ((rc = hand(st, sx))) return rc;
+        rc = bf ? seq_bwd_bf16(sx, T, t0, t1, B, H, q.whh1T, w.dh1, 0, w.c1, w.s1, q.dg1, w.dc1)
+                : seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1);
+        if (rc) return rc;
+        if ((rc = split_dg_block(lb, 1, t0, t1, !bf))) return rc;
+    }
+    return 0;
 }
 
 static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                              const s2vt_grads* g, float* dfeats, const TrainWS& w, const PlaneWS& q, hipStream_t st,
                              const float* out_mask, bool dlog_ready) {
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1, R = (L - 1) * B;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
+    TrainDriver x(d, p, g, w, q, st, out_mask, nullptr);
+    const int B = x.B, L = x.L, F = x.F, H = x.H, E = x.E, V = x.V, T = x.T, R = x.R;
+    const int64_t BH = x.BH;
     int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // word_rnn lane
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // vid_rnn lane
-    size_t ev = 0;
-    const bool bf = (XP == 1);
+    if ((rc = x.open_lanes())) return rc;
+    const hipStream_t sx = x.sx;
+    const Lane &la = x.la, &lb = x.lb;        // la: word_rnn lane, lb: vid_rnn lane
+    const bool bf = x.bf;
     if (bf) {   // zero the k padding of the bf16 dG row images
         if ((rc = zero_pad_cols_u16(st, q.dg2.p, (int64_t)T * B, q.dg2.ld, 4 * H, q.dg2.kpad))) return rc;
         if ((rc = zero_pad_cols_u16(st, q.dg1.p, (int64_t)T * B, q.dg1.ld, 4 * H, q.dg1.kpad))) return rc;
     }
-    if ((rc = handoff(st, sx, ev++))) return rc;
+    if ((rc = x.hand(st, sx))) return rc;
     // lane A: dlogits planes in both orientations + its column sums (one read), gradient into the decode-step
     // hidden states (k = V), then word_rnn BPTT.  (W^T planes were written by the forward.)
     // (dlog_ready: s2vt_mean_ce_backward_fused wrote these planes and partial sums straight from the logits)
     if (!dlog_ready && (rc = pdual(la, dlogits, V, ID, R, V, &q.dlog, 0, nullptr, 0, w.colsum_c))) return rc;
-    if ((rc = handoff(st, sx, ev++))) return rc;
+    if ((rc = x.hand(st, sx))) return rc;
     if ((rc = pgemm(la, R, H, V, q.dlog, 0, 0, q.woT, 0, 0, w.dh2dec, H, perm(L - 1, B), nullptr, false))) return rc;
     // bf16 mode with the fused criterion backward: the dlogits planes carry the power of two of gout / rows only (split.hip); the
     // mantissa multiplies the two fp32 products of those planes - here and dW_o below (the bias gradient already has it)
@@ -399,9 +687,11 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
     if (ce_pow2 && (rc = scale_by_device_scalar(st, w.dh2dec, (int64_t)R * H, w.ce_alpha))) return rc;
     if (out_mask && (rc = mul_vectors(st, w.dh2dec, out_mask, w.dh2dec, (int64_t)R * H))) return rc;      // autograd of out_drop
     if (!bf && (rc = transpose_f32(st, p->word_w_hh, 4 * H, H, w.wt2))) return rc;       // (the bf16 BPTT reads the W_hh^T planes instead)
-    const bool pbf_bwd = bf && blk > 0 && persist_on() && lstm_seq_bwd_bf16_persist_supported(B, H, q.dg2.kpad) && q.dg2.kpad == q.whh2T.kpad;
-    const bool px3_bwd = !bf && XP == 3 && blk > 0 && w.xnslots > 0 && persist_x3_bwd_on(B, H) && lstm_seq_bwd_x3_persist_supported(B, H) &&
-                         w.xnslots > (blk < T ? blk : T);
+    // the plan, and what only this driver knows: the bf16 images' k paddings match / the workspace provides the rings
+    RecKind kind = train_recurrence_plan(B, H).bwd;
+    if (kind == REC_BF16_PERSIST && q.dg2.kpad != q.whh2T.kpad) kind = REC_PER_STEP;
+    if (kind == REC_X3_PERSIST && !(w.xnslots > (x.blk < T ? x.blk : T))) kind = REC_PER_STEP;
+    const bool px3_bwd = kind == REC_X3_PERSIST;
     // rows of dW_o's k range that run beside EACH of the two one-layer BPTT stages (0: no co-run): 3/10 of the rows each - a stage
     // (option corun, tenths) - a stage lasts about as long as that part takes on the idle half of the device (profiles/round5_corun.txt)
     const int x3_ns = px3_bwd ? lstm_seq_bwd_x3_persist_supported(B, H) : 0;                 // chains per workgroup
@@ -417,306 +707,158 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
         }
         // rows in dlogits' (batch-major) order, read transposed by the GEMM
         if ((rc = psplit(lb, q.h2decB, 0, h2dec, H, perm(L - 1, B), R, H))) return rc;
-        // (co-run: dW_o is not needed before the optimizer - its GEMM is cut over k = rows into three parts, two of which run beside the
-        // one-layer stages of the persistent BPTT below, on the compute units those leave idle)
+        // (co-run: dW_o is not needed before the optimizer - its GEMM is cut over k = rows into parts that run beside the
+        // one-layer stages of the persistent x3 BPTT, on the compute units those leave idle)
         if (!corun_k && (rc = pgemm_tt(lb, V, H, R, q.dlog, 0, q.h2decB, 0, g->out_w, H, ID, nullptr, false))) return rc;
         if (!corun_k && ce_pow2 && (rc = scale_by_device_scalar(sx, g->out_w, (int64_t)V * H, w.ce_alpha))) return rc;
     }
     if ((rc = lcolsum_finish(lb, w.colsum_c, cdiv(R, 64), V, g->out_b, false))) return rc;
     // (a persistent BPTT re-records "group 0 is final" behind its last launch - no collective may start beside one - so it is not
     // recorded here for those schedules: option cu_reserve counts from the release that holds)
-    if (!corun_k && !pbf_bwd && !px3_bwd && (rc = grads_ready(0, sx))) return rc;
+    if (kind == REC_PER_STEP && (rc = grads_ready(0, sx))) return rc;
     if (!bf && (rc = transpose_f32(sx, p->vid_w_hh, 4 * H, H, w.wt1))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, (pbf_bwd || px3_bwd) ? balanced_block(L, blk) : blk);
-    int bias_chunk = 64;      // rows per partial column sum of dG (32: written by the persistent split-precision BPTT itself)
-    bool word_gemms_done = false, demb_done = false;                // (the one-layer BPTT schedule ran word_rnn's weight-gradient GEMMs and the
-    size_t word_grads_ev = 0, demb_ev = 0;                          //  embedded-word gradient GEMM already, on lane B: their events;
-    int hh1_t0 = 0;                                                 //  dW_hh1's timesteps >= hh1_t0 are done as well)
-    const bool solo_sched = corun_k > 0 && bd.size() >= 3 && option(O_BPTT_SOLO) != 0;
-    if (px3_bwd) {   // W_hh^T of both layers as planes (each on the lane that transposed it)
-        if ((rc = split3_wt(st, w.wt2, H, (int)w.xkp, (int)w.xhp, w.xwt2, w.xkp * 4 * w.xhp))) return rc;
-        if ((rc = split3_wt(sx, w.wt1, H, (int)w.xkp, (int)w.xhp, w.xwt1, w.xkp * 4 * w.xhp))) return rc;
+    x.set_bounds(kind != REC_PER_STEP);
+    BpttDone done;
+    switch (kind) {
+    case REC_X3_PERSIST:
+        if ((rc = x.x3_bptt_begin())) return rc;
+        if (corun_k > 0 && x.bd.size() >= 3 && option(O_BPTT_SOLO) != 0) rc = x.bptt_x3_one_layer(corun_cus, corun_k, &done);
+        else rc = x.bptt_x3_two_layer(corun_cus, corun_k, &done);
+        break;
+    case REC_BF16_PERSIST: rc = x.bptt_bf16_persistent(); break;
+    default: rc = x.bptt_two_lanes(); break;
     }
-    if (px3_bwd) {
-        // fp32-equivalent persistent schedule (split precision: lstm_persist_x3.hip), ONE stream: stage k = word_rnn BPTT of
-        // block k next to vid_rnn BPTT of block k+1
-        if ((rc = handoff(sx, st, ev++))) return rc;               // W_hh1^T and the out_linear gradients of lane B
-        const int nb = (int)bd.size() - 1;
-        // The kernel hands dG over as the GEMMs' row-plane image itself (+ its 32-row column sums for the bias gradients): its dG tile
-        // is in LDS as planes anyway - no split pass reads dG back, the fp32 dG is never stored.  (H % 8: a 16-byte slot of the image
-        // holds 8 consecutive units of one gate.)  The k padding [4H, pad64(4H)) of both images is zeroed here once per backward.
-        const bool emit = H % 8 == 0;
-        if (emit && q.dg2.kpad > 4 * H) {
-            const size_t kc0 = (size_t)(4 * H / 16), kc1 = (size_t)(q.dg2.kpad / 16);       // k16 records [kc0, kc1) of every 64-row block
-            const size_t first = (4 * H % 16) ? kc0 + 1 : kc0;                              // (4H % 16 == 8: the straddling record's upper half
-            for (const PB* img : {&q.dg2, &q.dg1}) {                                        //  is zeroed piece by piece below)
-                if (kc1 > first)
-                    S2VT_HIP(hipMemset2DAsync(img->p + first * 3072, (size_t)64 * img->ld * 2, 0, (kc1 - first) * 6144, (size_t)(T * B / 64), st));
-                if (4 * H % 16)
-                    for (int pl = 0; pl < 3; ++pl)
-                        S2VT_HIP(hipMemset2DAsync(img->p + kc0 * 3072 + (pl * 2 + 1) * 512, (size_t)64 * img->ld * 2, 0, 1024, (size_t)(T * B / 64), st));
-            }
-        }
-        if (solo_sched) {
-            // ONE layer per launch - word_rnn's blocks, then vid_rnn's (the word_rnn BPTT does not depend on vid_rnn's) - on half of the
-            // compute units, and the backward's GEMMs on the other half (lane B, planned for the idle units): beside word_rnn's stages
-            // dW_o (cut over k = rows, accumulated in a fixed order) and every finished block's dh1 GEMM; beside vid_rnn's stages
-            // word_rnn's weight gradients.  A two-layer stage does two blocks in ~440 us with nothing beside it; two one-layer stages take
-            // ~2 x 345 us and give half of the device to GEMMs for that long (profiles/round5_corun.txt).
-            auto event_at = [&](hipStream_t s_, size_t* idx) -> int {
-                hipEvent_t e;
-                *idx = ev++;
-                const int r = get_event(*idx, &e);
-                if (r) return r;
-                S2VT_HIP(hipEventRecord(e, s_));
-                return 0;
-            };
-            auto wait_for = [&](hipStream_t s_, size_t idx) -> int {
-                hipEvent_t e;
-                const int r = get_event(idx, &e);
-                if (r) return r;
-                S2VT_HIP(hipStreamWaitEvent(s_, e, 0));
-                return 0;
-            };
-            auto emit_args = [&](SeqBwdX3Args& a, bool word) {
-                if (!emit) return;
-                a.dgp = word ? q.dg2.p : q.dg1.p; a.lddgp = word ? q.dg2.ld : q.dg1.ld;
-                a.colpart = word ? w.colsum_a : w.colsum_b; a.skip_dg = 1;
-            };
-            if ((rc = handoff(st, sx, ev++))) return rc;            // the parts start with the first stage, not beside the dh2 GEMM
-            int wo_r = 0;                                           // next row of dW_o's k range
-            auto wo_part = [&]() -> int {
-                if (wo_r >= R) return 0;
-                int kk = corun_k < R - wo_r ? corun_k : R - wo_r;
-                if (R - wo_r - kk < 512) kk = R - wo_r;
-                const int r = pgemm_tt(lb, V, H, kk, q.dlog, wo_r, q.h2decB, wo_r, g->out_w, H, ID, nullptr, wo_r > 0);
-                wo_r += kk;
-                return r;
-            };
-            std::vector<size_t> dh1_done((size_t)nb);
-            size_t word_grads_done = 0, wo_done = 0;
-            {
-                CuPlanCap cap(corun_cus);
-                for (int k = nb - 1; k >= 0; --k) {
-                    const int t0 = bd[k], t1 = bd[k + 1];
-                    {
-                        ProfScope ps(st, K_STEP_BWD, t1 - t0);
-                        SeqBwdX3Args aw = persist_bwd_x3_args(T, t0, t1, B, H, w.xkp, w.xhp, w.xwt2, w.dh2dec, L, w.c2, w.s2, w.dc2, w.xpart2, w.xpslot,
-                                                              w.xnslots, w.psync_a, w.err + 1);
-                        emit_args(aw, true);
-                        if ((rc = lstm_seq_bwd_x3_persist2(st, aw, nullptr))) return rc;
-                        ++g_bwd_persist_launches;
-                    }
-                    if ((rc = wo_part())) return rc;
-                    if ((rc = handoff(st, sx, ev++))) return rc;    // dG2 rows of block k
-                    if (!emit && (rc = pdual(lb, w.s2 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, &q.dg2, t0 * B, nullptr, t0 * B,
-                                             w.colsum_a + (int64_t)(t0 * B / 64) * 4 * H)))
-                        return rc;
-                    if ((rc = pgemm(lb, (t1 - t0) * B, H, 4 * H, q.dg2, t0 * B, 0, q.wvT, 0, 0, w.dh1 + t0 * BH, H, ID, nullptr, false))) return rc;
-                    if ((rc = event_at(sx, &dh1_done[(size_t)k]))) return rc;
-                }
-                while (wo_r < R)
-                    if ((rc = wo_part())) return rc;
-                // (the parts left over when dW_o has more of them than word_rnn has stages: nothing on the caller's stream waits for
-                // the dh1 events behind them, so group 0's release below waits for this one)
-                if ((rc = event_at(sx, &wo_done))) return rc;
-                // word_rnn's weight gradients (dG2 is complete): beside vid_rnn's stages
-                if ((rc = pgemm_tt(lb, 4 * H, H, (T - 1) * B, q.dg2, B, q.h2r, 0, g->word_w_hh, H, ID, nullptr, false))) return rc;
-                if ((rc = pgemm_tt(lb, 4 * H, H, T * B, q.dg2, 0, q.h1, 0, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
-                if ((rc = pgemm_tt(lb, 4 * H, E, R, q.dg2, L * B, q.emb, 0, g->word_w_ih, E + H, ID, nullptr, false))) return rc;
-                if ((rc = event_at(sx, &word_grads_done))) return rc;
-                // ... and the gradient into the embedded words (the embedding gradient's input)
-                if ((rc = pgemm(lb, R, E, 4 * H, q.dg2, L * B, 0, q.weT, 0, 0, w.de, E, ID, nullptr, false))) return rc;
-                if ((rc = event_at(sx, &demb_ev))) return rc;
-                demb_done = true;
-            }
-            // dW_hh1 = dG1[t]^T h1[t-1] over t >= hh1_t0 (the blocks vid_rnn's BPTT finishes first) beside its later stages
-            const int kc = nb / 2;
-            if (nb >= 4) hh1_t0 = bd[kc];
-            for (int k = nb - 1; k >= 0; --k) {
-                const int t0 = bd[k], t1 = bd[k + 1];
-                if ((rc = wait_for(st, dh1_done[(size_t)k]))) return rc;
-                ProfScope ps(st, K_STEP_BWD, t1 - t0);
-                SeqBwdX3Args av = persist_bwd_x3_args(T, t0, t1, B, H, w.xkp, w.xhp, w.xwt1, w.dh1, 0, w.c1, w.s1, w.dc1, w.xpart1, w.xpslot,
-                                                      w.xnslots, w.psync_b, w.err + 1);
-                emit_args(av, false);
-                if ((rc = lstm_seq_bwd_x3_persist2(st, av, nullptr))) return rc;
-                ++g_bwd_persist_launches;
-                if (!emit && (rc = pdual(la, w.s1 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, &q.dg1, t0 * B, nullptr, t0 * B,
-                                         w.colsum_b + (int64_t)(t0 * B / 64) * 4 * H)))
-                    return rc;
-                if (hh1_t0 > 0 && k == kc) {
-                    if ((rc = handoff(st, sx, ev++))) return rc;   // dG1 rows of the blocks [kc, nb)
-                    CuPlanCap cap(corun_cus);
-                    if ((rc = pgemm_tt(lb, 4 * H, H, (T - hh1_t0) * B, q.dg1, hh1_t0 * B, q.h1, (hh1_t0 - 1) * B, g->vid_w_hh, H, ID, nullptr, false)))
-                        return rc;
-                }
-            }
-            bias_chunk = emit ? 32 : 64;
-            if ((rc = wait_for(st, wo_done))) return rc;           // every part of dW_o, including those enqueued after the last stage
-            if ((rc = grads_ready(0, st))) return rc;              // (out_linear's gradients: released behind the last persistent launch)
-            if ((rc = handoff(st, sx, ev++))) return rc;           // lane B's vid_rnn gradients need dG1
-            word_gemms_done = true;
-            word_grads_ev = word_grads_done;                       // lane A's tail ends with "word_rnn + embedding gradients final": after these
-        } else
-        for (int k = nb - 1; k >= -1; --k) {
-            const bool hw = k >= 0, hv = k + 1 <= nb - 1;
-            const bool solo = corun_k && nb >= 2 && (k == nb - 1 || k == -1);      // a one-layer stage: half of the compute units idle
-            if (solo && (rc = handoff(st, sx, ev++))) return rc;                     // (the part starts with the stage, not before it)
-            {
-                ProfScope ps(st, K_STEP_BWD, (hw ? bd[k + 1] - bd[k] : 0) + (hv ? bd[k + 2] - bd[k + 1] : 0));
-                SeqBwdX3Args aw, av;
-                if (hw) aw = persist_bwd_x3_args(T, bd[k], bd[k + 1], B, H, w.xkp, w.xhp, w.xwt2, w.dh2dec, L, w.c2, w.s2, w.dc2,
-                                                 w.xpart2, w.xpslot, w.xnslots, w.psync_a, w.err + 1);
-                if (hv) av = persist_bwd_x3_args(T, bd[k + 1], bd[k + 2], B, H, w.xkp, w.xhp, w.xwt1, w.dh1, 0, w.c1, w.s1, w.dc1,
-                                                 w.xpart1, w.xpslot, w.xnslots, w.psync_b, w.err + 1);
-                if (emit) {
-                    aw.dgp = q.dg2.p; aw.lddgp = q.dg2.ld; aw.colpart = w.colsum_a; aw.skip_dg = 1;
-                    av.dgp = q.dg1.p; av.lddgp = q.dg1.ld; av.colpart = w.colsum_b; av.skip_dg = 1;
-                }
-                if (hw && hv) rc = lstm_seq_bwd_x3_persist2(st, aw, &av);
-                else rc = lstm_seq_bwd_x3_persist2(st, hw ? aw : av, nullptr);
-                ++g_bwd_persist_launches;
-                if (rc) return rc;
-            }
-            if (solo) {      // dW_o rows [r0, r0 + corun_k) on lane B, planned for the units the stage leaves idle; the caller's stream
-                const int r0 = (k == nb - 1) ? 0 : corun_k;              // goes on when both are done
-                {
-                    CuPlanCap cap(corun_cus);
-                    if ((rc = pgemm_tt(lb, V, H, corun_k, q.dlog, r0, q.h2decB, r0, g->out_w, H, ID, nullptr, r0 > 0))) return rc;
-                }
-                if ((rc = handoff(sx, st, ev++))) return rc;
-            }
-            if (hw) {
-                const int t0 = bd[k], t1 = bd[k + 1];
-                if (!emit && (rc = pdual(la, w.s2 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, &q.dg2, t0 * B, nullptr, t0 * B,
-                                         w.colsum_a + (int64_t)(t0 * B / 64) * 4 * H)))
-                    return rc;
-                if ((rc = pgemm(la, (t1 - t0) * B, H, 4 * H, q.dg2, t0 * B, 0, q.wvT, 0, 0, w.dh1 + t0 * BH, H, ID, nullptr, false)))
-                    return rc;
-            }
-            if (hv && !emit) {
-                const int t0 = bd[k + 1], t1 = bd[k + 2];
-                if ((rc = pdual(la, w.s1 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, &q.dg1, t0 * B,
-                                nullptr, t0 * B, w.colsum_b + (int64_t)(t0 * B / 64) * 4 * H)))
-                    return rc;
-            }
-        }
-        if (!solo_sched) {
-        bias_chunk = emit ? 32 : 64;
-        if (!corun_k && (rc = grads_ready(0, st))) return rc;      // (see the bf16 branch below)
-        if ((rc = handoff(st, sx, ev++))) return rc;
-        }
-        if (corun_k && !solo_sched) {      // the rest of dW_o's rows: first thing of lane B's tail, then the out_linear gradients are final
-            const bool two = nb >= 2;
-            const int r0 = two ? 2 * corun_k : 0;
-            if ((rc = pgemm_tt(lb, V, H, R - r0, q.dlog, r0, q.h2decB, r0, g->out_w, H, ID, nullptr, two))) return rc;
-            if ((rc = grads_ready(0, sx))) return rc;
-        }
-    } else if (pbf_bwd) {
-        // Persistent schedule, ONE stream (mirror of the forward): the launch of stage k runs the word_rnn BPTT of block k
-        // next to the vid_rnn BPTT of block k+1 (lstm_persist.hip); between two launches the dG planes / partial column sums
-        // of the blocks just finished and the dh1 GEMM of the word block run alone on the chip.
-        if ((rc = handoff(sx, st, ev++))) return rc;               // out_linear gradients of lane B first: no GEMM beside
-        const int nb = (int)bd.size() - 1;                         // a persistent launch
-        for (int k = nb - 1; k >= -1; --k) {
-            const bool hw = k >= 0, hv = k + 1 <= nb - 1;
-            SeqBwdBf16Args aw, av;
-            if (hw) aw = seq_bwd_bf16_args(T, bd[k], bd[k + 1], B, H, q.whh2T, q.dg2, w.dh2dec, L, w.c2, w.s2, w.dc2, w.psync_a, w.err + 1);
-            if (hv) av = seq_bwd_bf16_args(T, bd[k + 1], bd[k + 2], B, H, q.whh1T, q.dg1, w.dh1, 0, w.c1, w.s1, w.dc1, w.psync_b, w.err + 1);
-            {
-                ProfScope ps(st, K_STEP_BWD, (hw ? bd[k + 1] - bd[k] : 0) + (hv ? bd[k + 2] - bd[k + 1] : 0));
-                if (hw && hv) rc = lstm_seq_bwd_bf16_persist2(st, aw, &av);
-                else rc = lstm_seq_bwd_bf16_persist2(st, hw ? aw : av, nullptr);
-                ++g_bwd_persist_launches;
-                if (rc) return rc;
-            }
-            if (hw) {
-                const int t0 = bd[k], t1 = bd[k + 1];
-                if ((rc = pdual(la, w.s2 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, nullptr, t0 * B, nullptr, t0 * B,
-                                w.colsum_a + (int64_t)(t0 * B / 64) * 4 * H)))
-                    return rc;
-                if ((rc = pgemm(la, (t1 - t0) * B, H, 4 * H, q.dg2, t0 * B, 0, q.wvT, 0, 0, w.dh1 + t0 * BH, H, ID, nullptr, false)))
-                    return rc;
-            }
-            if (hv) {
-                const int t0 = bd[k + 1], t1 = bd[k + 2];
-                if ((rc = pdual(la, w.s1 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, nullptr, t0 * B, nullptr, t0 * B,
-                                w.colsum_b + (int64_t)(t0 * B / 64) * 4 * H)))
-                    return rc;
-            }
-        }
-        // Data-parallel overlap: a persistent launch needs every one of its workgroups resident, so no foreign kernel (the
-        // RCCL all-reduce of gradient group 0 on the caller's communication stream) may start beside one and hold LDS /
-        // wave slots on a compute unit.  "Group 0 is final" is therefore re-recorded HERE, behind the last persistent
-        // launch: s2vt_backward_wait_grads(0) then releases the out_linear all-reduce when the recurrence has left the
-        // chip, and it overlaps the weight-gradient GEMMs below instead of the BPTT.
-        if ((rc = grads_ready(0, st))) return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;               // lane B's parameter-gradient GEMMs need dG1
-    } else {
-    for (size_t k = bd.size() - 1; k >= 1; --k) {
-        const int t0 = bd[k - 1], t1 = bd[k];
-        if (bf) {
-            if ((rc = seq_bwd_bf16(st, T, t0, t1, B, H, q.whh2T, w.dh2dec, L, w.c2, w.s2, q.dg2, w.dc2))) return rc;
-        } else {
-            if ((rc = seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2))) return rc;
-        }
-        // dG2 of this block: row planes (dh1, d-embedding GEMMs), transposed planes (weight gradients) and the
-        // bias-gradient partial sums, all from one read
-        if ((rc = pdual(la, w.s2 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, bf ? nullptr : &q.dg2, t0 * B, nullptr, t0 * B,
-                        w.colsum_a + (int64_t)(t0 * B / 64) * 4 * H)))
-            return rc;
-        if ((rc = pgemm(la, (t1 - t0) * B, H, 4 * H, q.dg2, t0 * B, 0, q.wvT, 0, 0, w.dh1 + t0 * BH, H, ID, nullptr, false)))
-            return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;
-        if (bf) {
-            if ((rc = seq_bwd_bf16(sx, T, t0, t1, B, H, q.whh1T, w.dh1, 0, w.c1, w.s1, q.dg1, w.dc1))) return rc;
-        } else {
-            if ((rc = seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1))) return rc;
-        }
-        if ((rc = pdual(lb, w.s1 + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, bf ? nullptr : &q.dg1, t0 * B,
-                        nullptr, t0 * B, w.colsum_b + (int64_t)(t0 * B / 64) * 4 * H)))
-            return rc;
-    }
-    }
+    if (rc) return rc;
     // lane A: word_rnn parameter gradients + embedding gradient
-    // dW = dG^T . (h | emb): row planes of both, read transposed
-    if (!word_gemms_done) {
-    if ((rc = pgemm_tt(la, 4 * H, H, (T - 1) * B, q.dg2, B, q.h2r, 0, g->word_w_hh, H, ID, nullptr, false))) return rc;
-    if ((rc = pgemm_tt(la, 4 * H, H, T * B, q.dg2, 0, q.h1, 0, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
-    if ((rc = pgemm_tt(la, 4 * H, E, R, q.dg2, L * B, q.emb, 0, g->word_w_ih, E + H, ID, nullptr, false))) return rc;
-    }
-    if ((rc = lcolsum_finish(la, w.colsum_a, T * B / bias_chunk, 4 * H, g->word_b_ih, false))) return rc;
+    if (done.word_grads_ev < 0 && (rc = x.word_weight_grads(la))) return rc;
+    if ((rc = lcolsum_finish(la, w.colsum_a, T * B / done.bias_chunk, 4 * H, g->word_b_ih, false))) return rc;
     S2VT_HIP(hipMemcpyAsync(g->word_b_hh, g->word_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
-    if (demb_done) {
-        hipEvent_t e;
-        if ((rc = get_event(demb_ev, &e))) return rc;
-        S2VT_HIP(hipStreamWaitEvent(st, e, 0));
-    } else if ((rc = pgemm(la, R, E, 4 * H, q.dg2, L * B, 0, q.weT, 0, 0, w.de, E, ID, nullptr, false))) return rc;
+    if ((rc = done.demb_ev >= 0 ? x.wait(st, done.demb_ev) : x.demb_gemm(la))) return rc;
     if ((rc = embedding_grad(st, w.de, R, E, w.tok, V, g->emb_w, w.embws))) return rc;
-    if (word_gemms_done) {
-        hipEvent_t e;
-        if ((rc = get_event(word_grads_ev, &e))) return rc;
-        S2VT_HIP(hipStreamWaitEvent(st, e, 0));
-    }
+    if (done.word_grads_ev >= 0 && (rc = x.wait(st, done.word_grads_ev))) return rc;
     if ((rc = grads_ready(1, st))) return rc;
     // lane B: vid_rnn and feat_linear parameter gradients
-    const Lane lt = lb;
     // (one-layer BPTT schedule: the timesteps >= hh1_t0 of this sum ran beside vid_rnn's later stages - the rest is accumulated)
-    if ((rc = pgemm_tt(lt, 4 * H, H, ((hh1_t0 > 0 ? hh1_t0 : T) - 1) * B, q.dg1, B, q.h1, 0, g->vid_w_hh, H, ID, nullptr, hh1_t0 > 0))) return rc;
-    if ((rc = pgemm_tt(lt, 4 * H, H, L * B, q.dg1, 0, q.x1, 0, g->vid_w_ih, H, ID, nullptr, false))) return rc;
-    if ((rc = lcolsum_finish(lt, w.colsum_b, T * B / bias_chunk, 4 * H, g->vid_b_ih, false))) return rc;
-    S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, lt.s));
+    const int hh1_rows = ((done.hh1_t0 > 0 ? done.hh1_t0 : T) - 1) * B;
+    if ((rc = pgemm_tt(lb, 4 * H, H, hh1_rows, q.dg1, B, q.h1, 0, g->vid_w_hh, H, ID, nullptr, done.hh1_t0 > 0))) return rc;
+    if ((rc = pgemm_tt(lb, 4 * H, H, L * B, q.dg1, 0, q.x1, 0, g->vid_w_ih, H, ID, nullptr, false))) return rc;
+    if ((rc = lcolsum_finish(lb, w.colsum_b, T * B / done.bias_chunk, 4 * H, g->vid_b_ih, false))) return rc;
+    S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sx));
     // dx1 comes out in BATCH-major row order (the order of feats' rows, whose row planes the forward wrote): dW_f = dx1^T feats
     // reads both transposed - no time-major transposed copy of the features, no transposed dx1 (q.x1 is free: dW_ih1 is done)
-    if ((rc = pgemm(lt, L * B, H, 4 * H, q.dg1, 0, 0, q.wih1T, 0, 0, w.dx1, H, perm(B, L), nullptr, false))) return rc;
-    if ((rc = pdual(lt, w.dx1, H, ID, L * B, H, &q.x1, 0, nullptr, 0, w.colsum_b))) return rc;
-    if ((rc = pgemm_tt(lt, H, F, L * B, q.x1, 0, q.feats, 0, g->feat_w, F, ID, nullptr, false))) return rc;
-    if ((rc = lcolsum_finish(lt, w.colsum_b, L * B / 64, H, g->feat_b, false))) return rc;
-    if (dfeats) {   // rarely requested (nothing reads it in the reference): fp32-MFMA GEMM
-        if ((rc = lgemm(lt, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, ID, nullptr, false)))
-            return rc;
+    if ((rc = pgemm(lb, L * B, H, 4 * H, q.dg1, 0, 0, q.wih1T, 0, 0, w.dx1, H, perm(B, L), nullptr, false))) return rc;
+    if ((rc = pdual(lb, w.dx1, H, ID, L * B, H, &q.x1, 0, nullptr, 0, w.colsum_b))) return rc;
+    if ((rc = pgemm_tt(lb, H, F, L * B, q.x1, 0, q.feats, 0, g->feat_w, F, ID, nullptr, false))) return rc;
+    if ((rc = lcolsum_finish(lb, w.colsum_b, L * B / 64, H, g->feat_b, false))) return rc;
+    // dfeats: rarely requested (nothing reads it in the reference): fp32-MFMA GEMM
+    if (dfeats && (rc = lgemm(lb, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, ID, nullptr, false))) return rc;
+    return x.hand(sx, st);
+}
+
+// The launch-per-timestep fp32-MFMA driver (gemm mode 0, and batches the plane drivers do not take): fp32 operands read in place
+static int train_forward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
+                             int64_t targets_ld, float* logits, const TrainWS& w, hipStream_t st, const float* out_mask) {
+    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1;
+    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
+    const int blk = pipe_block();
+    hipStream_t sx = st;
+    int rc;
+    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
+    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // vid_rnn lane (caller's stream)
+    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // word_rnn lane
+    size_t ev = 0;
+    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
+    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
+    if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
+    if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
+    if ((rc = handoff(st, sx, ev++))) return rc;
+    // lane B, independent of vid_rnn: embedded-word half of the word_rnn gate input (+ both biases) for the
+    // L-1 caption steps                                                             S2VTModel.py:71-75
+    if ((rc = lgemm(lb, true, true, (L - 1) * B, 4 * H, E, p->emb_w, E, gather(w.tok), p->word_w_ih, E + H, ID,
+                    w.s2 + (int64_t)L * B4H, 4 * H, ID, w.bsum2, false))) return rc;
+    // lane A: x1 (time-major) = feats·W_f^T + b_f ; gx1 = x1·W_ih1^T + biases       S2VTModel.py:54, 64-67
+    if ((rc = lgemm(la, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, w.x1, H, perm(L, B), p->feat_b, false))) return rc;
+    if ((rc = lgemm(la, true, true, L * B, 4 * H, H, w.x1, H, ID, p->vid_w_ih, H, ID, w.s1, 4 * H, ID, w.bsum1, false))) return rc;
+    const std::vector<int> bd = pipe_bounds(T, L, blk);
+    for (size_t k = 0; k + 1 < bd.size(); ++k) {
+        const int t0 = bd[k], t1 = bd[k + 1];
+        if ((rc = seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true))) return rc;
+        if ((rc = handoff(st, sx, ev++))) return rc;
+        // vid_out half of the word_rnn gate input for this block: rows < L get the biases here, rows >= L
+        // accumulate onto the embedded-word half                                    S2VTModel.py:75-77
+        const bool cap = t0 >= L;
+        if ((rc = lgemm(lb, true, true, (t1 - t0) * B, 4 * H, H, w.h1 + t0 * BH, H, ID, p->word_w_ih + E, E + H, ID,
+                        w.s2 + t0 * B4H, 4 * H, ID, cap ? nullptr : w.bsum2, cap))) return rc;
+        if ((rc = seq_fwd(sx, t0, t1, B, H, w.s2, T, w.bsum2, p->word_w_hh, w.h2, w.c2, true))) return rc;
     }
+    // logits[b, j, :] = (out_drop mask (.)) h2[L + j]·W_o^T + b_o                    S2VTModel.py:78-80
+    const float* hdec = w.h2 + L * BH;
+    if (out_mask) {
+        if ((rc = mul_vectors(sx, hdec, out_mask, w.dh2dec, (int64_t)(L - 1) * B * H))) return rc;     // dh2dec: free in the forward
+        hdec = w.dh2dec;
+    }
+    if ((rc = lgemm(lb, true, true, (L - 1) * B, V, H, hdec, H, ID, p->out_w, H, ID, logits, V, perm(B, L - 1), p->out_b, false))) return rc;
+    return handoff(sx, st, ev++);
+}
+
+static int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
+                              const s2vt_grads* g, float* dfeats, const TrainWS& w, hipStream_t st, const float* out_mask) {
+    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1, R = (L - 1) * B;
+    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
+    const int blk = pipe_block();
+    hipStream_t sx = st;
+    int rc;
+    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
+    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // word_rnn lane (caller's stream)
+    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // vid_rnn lane
+    LaneDelayScope delay(st);
+    size_t ev = 0;
+    if ((rc = handoff(st, sx, ev++))) return rc;
+    // lane A: gradient into the decode-step hidden states, then word_rnn BPTT       (autograd of S2VTModel.py:80, :77)
+    if ((rc = lgemm(la, true, false, R, H, V, dlogits, V, ID, p->out_w, H, ID, w.dh2dec, H, perm(L - 1, B), nullptr, false))) return rc;
+    if (out_mask && (rc = mul_vectors(st, w.dh2dec, out_mask, w.dh2dec, (int64_t)R * H))) return rc;      // autograd of out_drop
+    if ((rc = transpose_f32(st, p->word_w_hh, 4 * H, H, w.wt2))) return rc;
+    // lane B meanwhile: out_linear weight/bias gradients (need only dlogits and the (masked) h2) and W_hh1^T
+    const float* hdec = w.h2 + L * BH;
+    if (out_mask) {
+        if ((rc = mul_vectors(sx, hdec, out_mask, w.dx1, (int64_t)R * H))) return rc;      // dx1: free until the vid_rnn input gradient
+        hdec = w.dx1;
+    }
+    if ((rc = lgemm(lb, false, false, V, H, R, dlogits, V, ID, hdec, H, perm(L - 1, B), g->out_w, H, ID, nullptr, false))) return rc;
+    if ((rc = colsum_f32(sx, dlogits, R, V, V, lb.colsum, g->out_b, false))) return rc;
+    if ((rc = grads_ready(0, sx))) return rc;
+    if ((rc = transpose_f32(sx, p->vid_w_hh, 4 * H, H, w.wt1))) return rc;
+    const std::vector<int> bd = pipe_bounds(T, L, blk);
+    for (size_t k = bd.size() - 1; k >= 1; --k) {
+        const int t0 = bd[k - 1], t1 = bd[k];
+        if ((rc = seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2))) return rc;
+        // gradient into vid_out for this block: dh1 = dG2·W_v                        (autograd of :75)
+        if ((rc = lgemm(la, true, false, (t1 - t0) * B, H, 4 * H, w.s2 + t0 * B4H, 4 * H, ID, p->word_w_ih + E, E + H, ID,
+                        w.dh1 + t0 * BH, H, ID, nullptr, false))) return rc;
+        if ((rc = handoff(st, sx, ev++))) return rc;
+        if ((rc = seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1))) return rc;   // (autograd of :67)
+    }
+    // lane A: word_rnn parameter gradients + embedding gradient (run while lane B finishes the vid_rnn BPTT)
+    if ((rc = lgemm(la, false, false, 4 * H, H, (T - 1) * B, w.s2 + B4H, 4 * H, ID, w.h2, H, ID, g->word_w_hh, H, ID, nullptr, false))) return rc;
+    if ((rc = lgemm(la, false, false, 4 * H, H, T * B, w.s2, 4 * H, ID, w.h1, H, ID, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
+    // dW_ih2[:, :E] = dG2[L..]^T · Emb[tok]: the embedded rows are gathered once (time-major) into w.de, which
+    // is free until the d(embedded words) GEMM below overwrites it
+    if ((rc = gather_rows_f32(st, p->emb_w, E, w.tok, R, E, w.de))) return rc;
+    if ((rc = lgemm(la, false, false, 4 * H, E, R, w.s2 + (int64_t)L * B4H, 4 * H, ID, w.de, E, ID, g->word_w_ih, E + H, ID, nullptr, false))) return rc;
+    if ((rc = colsum_f32(st, w.s2, (int64_t)T * B, 4 * H, 4 * H, la.colsum, g->word_b_ih, false))) return rc;
+    S2VT_HIP(hipMemcpyAsync(g->word_b_hh, g->word_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
+    if ((rc = lgemm(la, true, false, R, E, 4 * H, w.s2 + (int64_t)L * B4H, 4 * H, ID, p->word_w_ih, E + H, ID, w.de, E, ID, nullptr, false))) return rc;
+    if ((rc = embedding_grad(st, w.de, R, E, w.tok, V, g->emb_w, w.embws))) return rc;
+    if ((rc = grads_ready(1, st))) return rc;
+    // lane B: vid_rnn and feat_linear parameter gradients                           (autograd of :67, :54)
+    if ((rc = lgemm(lb, false, false, 4 * H, H, (T - 1) * B, w.s1 + B4H, 4 * H, ID, w.h1, H, ID, g->vid_w_hh, H, ID, nullptr, false))) return rc;
+    if ((rc = lgemm(lb, false, false, 4 * H, H, L * B, w.s1, 4 * H, ID, w.x1, H, ID, g->vid_w_ih, H, ID, nullptr, false))) return rc;
+    if ((rc = colsum_f32(sx, w.s1, (int64_t)T * B, 4 * H, 4 * H, lb.colsum, g->vid_b_ih, false))) return rc;
+    S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sx));
+    if ((rc = lgemm(lb, true, false, L * B, H, 4 * H, w.s1, 4 * H, ID, p->vid_w_ih, H, ID, w.dx1, H, ID, nullptr, false))) return rc;
+    if ((rc = lgemm(lb, false, false, H, F, L * B, w.dx1, H, ID, feats, F, perm(B, L), g->feat_w, F, ID, nullptr, false))) return rc;
+    if ((rc = colsum_f32(sx, w.dx1, (int64_t)L * B, H, H, lb.colsum, g->feat_b, false))) return rc;
+    if (dfeats && (rc = lgemm(lb, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, perm(B, L), nullptr, false))) return rc;
     return handoff(sx, st, ev++);
 }
 
@@ -749,7 +891,16 @@ static PadWS carve_pad(const s2vt_dims& d, const s2vt_dims& dp, void* base) {
     w.bytes = align_up(c.off, 256);
     return w;
 }
-static size_t train_core_bytes(const s2vt_dims& d);
+static size_t train_core_bytes(const s2vt_dims& d) {
+    size_t n = carve_train(d, nullptr).bytes;
+    if (planes_ok(d)) {
+        const int keep = XP;                       // a size query must not change the state of a running path
+        XP = (gemm_mode() == 1) ? 1 : 3;
+        n += carve_planes(d, nullptr).bytes;
+        XP = keep;
+    }
+    return n;
+}
 
 int32_t s2vt_padded_batch(int32_t B) {
     if (B <= 0) return 0;
@@ -765,21 +916,46 @@ size_t s2vt_train_workspace_bytes(const s2vt_dims* d) {
     }
     return train_core_bytes(*d);
 }
-static size_t train_core_bytes(const s2vt_dims& dd) {
-    const s2vt_dims* d = &dd;
-    size_t n = carve_train(*d, nullptr).bytes;
-    if (planes_ok(*d)) {
-        const int keep = XP;                       // a size query must not change the state of a running path
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        n += carve_planes(*d, nullptr).bytes;
-        XP = keep;
-    }
-    return n;
+
+// hipGraph key of a plane driver's launch sequence: tag, dims, every option (key_options), the parameter and gradient pointers, then
+// the call's own words (pointers and strides) in the order given.  Empty while graph mode is off.
+static inline uint64_t kw(const void* p) { return (uint64_t)(uintptr_t)p; }
+static std::vector<uint64_t> graph_key(uint64_t tag, const s2vt_dims* d, const s2vt_params* p, const s2vt_grads* g, std::initializer_list<uint64_t> words) {
+    std::vector<uint64_t> key;
+    if (!graph_on()) return key;
+    key.reserve(80);
+    key.push_back(tag);
+    for (int v : {d->B, d->L, d->F, d->H, d->E, d->V}) key.push_back((uint64_t)v);
+    key_options(key);
+    const float* const* pp = reinterpret_cast<const float* const*>(p);
+    for (size_t i = 0; i < sizeof(s2vt_params) / sizeof(void*); ++i) key_ptr(key, pp[i]);
+    float* const* gp = reinterpret_cast<float* const*>(g);
+    for (size_t i = 0; g && i < sizeof(s2vt_grads) / sizeof(void*); ++i) key_ptr(key, gp[i]);
+    key.insert(key.end(), words);
+    return key;
 }
 
 static int train_forward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
                               int64_t targets_ld, float* logits, void* workspace, size_t workspace_bytes, void* stream,
-                              const float* out_mask);
+                              const float* out_mask) {
+    const TrainWS w = carve_train(*d, workspace);
+    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_train_forward: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    int rc0 = poll_async_error(false);       // a device-side error of the previous forward, if its flags have arrived
+    if (rc0) return rc0;
+    record_forward(workspace, *d, planes_ok(*d));
+    if (planes_ok(*d)) {
+        XP = (gemm_mode() == 1) ? 1 : 3;
+        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
+        S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_forward: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
+        const std::vector<uint64_t> key = graph_key(0xF0, d, p, nullptr, {kw(feats), kw(targets), (uint64_t)targets_ld, kw(logits), kw(workspace),
+                                                                           kw(out_mask), kw(st)});
+        rc0 = run_graphed(st, key, [&](hipStream_t s_) { return train_forward_x3(d, p, feats, targets, targets_ld, logits, w, q, s_, out_mask); });
+    } else {
+        rc0 = train_forward_f32(d, p, feats, targets, targets_ld, logits, w, st, out_mask);
+    }
+    return rc0 ? rc0 : post_async_error(st, w.err);
+}
 static int train_forward_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
                               int64_t targets_ld, float* logits, void* workspace, size_t workspace_bytes, void* stream,
                               const float* out_mask) {
@@ -803,89 +979,9 @@ static int train_forward_impl(const s2vt_dims* d, const s2vt_params* p, const fl
         S2VT_HIP(hipMemcpy2DAsync(s.mask, Bp * H * sizeof(float), out_mask, B * H * sizeof(float), B * H * sizeof(float), L - 1,
                                   hipMemcpyDeviceToDevice, st));
     }
-    if ((rc = train_forward_core(&dp, p, s.feats, s.targets, (int64_t)(L - 1), s.logits, workspace, core, stream, out_mask ? s.mask : nullptr)))
-        return rc;
+    if ((rc = train_forward_core(&dp, p, s.feats, s.targets, (int64_t)(L - 1), s.logits, workspace, core, stream, out_mask ? s.mask : nullptr))) return rc;
     S2VT_HIP(hipMemcpyAsync(logits, s.logits, B * (L - 1) * V * sizeof(float), hipMemcpyDeviceToDevice, st));      // batch-major: the first B rows
     return 0;
-}
-static int train_forward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
-                              int64_t targets_ld, float* logits, void* workspace, size_t workspace_bytes, void* stream,
-                              const float* out_mask) {
-    const TrainWS w = carve_train(*d, workspace);
-    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_train_forward: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    {   // a device-side error of the previous forward, if its flags have arrived
-        int rc0 = poll_async_error(false);
-        if (rc0) return rc0;
-    }
-    record_forward(workspace, *d, planes_ok(*d));
-    if (planes_ok(*d)) {
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
-        S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_forward: workspace %zu < %zu bytes",
-                     workspace_bytes, w.bytes + q.bytes);
-        std::vector<uint64_t> key;
-        if (graph_on()) {
-            key.reserve(64);
-            key.push_back(0xF0);
-            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V}) key.push_back((uint64_t)v);
-            key_options(key);
-            const float* const* pp = reinterpret_cast<const float* const*>(p);
-            for (size_t i = 0; i < sizeof(s2vt_params) / sizeof(void*); ++i) key_ptr(key, pp[i]);
-            key_ptr(key, feats); key_ptr(key, targets); key.push_back((uint64_t)targets_ld); key_ptr(key, logits);
-            key_ptr(key, workspace); key_ptr(key, out_mask); key_ptr(key, st);
-        }
-        int rc0 = run_graphed(st, key, [&](hipStream_t s_) { return train_forward_x3(d, p, feats, targets, targets_ld, logits, w, q, s_, out_mask); });
-        return rc0 ? rc0 : post_async_error(st, w.err);
-    }
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
-    int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // vid_rnn lane (caller's stream)
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // word_rnn lane
-    size_t ev = 0;
-    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
-    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
-    if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
-    if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
-    if ((rc = handoff(st, sx, ev++))) return rc;
-    // lane B, independent of vid_rnn: embedded-word half of the word_rnn gate input (+ both biases) for the
-    // L-1 caption steps                                                             S2VTModel.py:71-75
-    if ((rc = lgemm(lb, true, true, (L - 1) * B, 4 * H, E, p->emb_w, E, gather(w.tok), p->word_w_ih, E + H, ID,
-                    w.s2 + (int64_t)L * B4H, 4 * H, ID, w.bsum2, false)))
-        return rc;
-    // lane A: x1 (time-major) = feats·W_f^T + b_f ; gx1 = x1·W_ih1^T + biases       S2VTModel.py:54, 64-67
-    if ((rc = lgemm(la, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, w.x1, H, perm(L, B), p->feat_b, false)))
-        return rc;
-    if ((rc = lgemm(la, true, true, L * B, 4 * H, H, w.x1, H, ID, p->vid_w_ih, H, ID, w.s1, 4 * H, ID, w.bsum1, false)))
-        return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, blk);
-    for (size_t k = 0; k + 1 < bd.size(); ++k) {
-        const int t0 = bd[k], t1 = bd[k + 1];
-        if ((rc = seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true))) return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;
-        // vid_out half of the word_rnn gate input for this block: rows < L get the biases here, rows >= L
-        // accumulate onto the embedded-word half                                    S2VTModel.py:75-77
-        const bool cap = t0 >= L;
-        if ((rc = lgemm(lb, true, true, (t1 - t0) * B, 4 * H, H, w.h1 + t0 * BH, H, ID, p->word_w_ih + E, E + H, ID,
-                        w.s2 + t0 * B4H, 4 * H, ID, cap ? nullptr : w.bsum2, cap)))
-            return rc;
-        if ((rc = seq_fwd(sx, t0, t1, B, H, w.s2, T, w.bsum2, p->word_w_hh, w.h2, w.c2, true))) return rc;
-    }
-    // logits[b, j, :] = (out_drop mask (.)) h2[L + j]·W_o^T + b_o                    S2VTModel.py:78-80
-    const float* hdec = w.h2 + L * BH;
-    if (out_mask) {
-        if ((rc = mul_vectors(sx, hdec, out_mask, w.dh2dec, (int64_t)(L - 1) * B * H))) return rc;     // dh2dec: free in the forward
-        hdec = w.dh2dec;
-    }
-    if ((rc = lgemm(lb, true, true, (L - 1) * B, V, H, hdec, H, ID, p->out_w, H, ID, logits, V, perm(B, L - 1),
-                    p->out_b, false)))
-        return rc;
-    if ((rc = handoff(sx, st, ev++))) return rc;
-    return post_async_error(st, w.err);
 }
 
 int s2vt_train_forward(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
@@ -900,7 +996,39 @@ int s2vt_train_forward_dropout(const s2vt_dims* d, const s2vt_params* p, const f
 
 static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                                const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream,
-                               const float* out_mask);
+                               const float* out_mask) {
+    g_bwd_persist_launches = 0;          // (s2vt_backward_order describes THIS backward, whichever driver it takes)
+    g_bwd_group0_after = 0;
+    struct ReserveWindow {               // option cu_reserve: off until gradient group 0 is released, off again when the backward is enqueued
+        ReserveWindow() { cu_reserve_window(false); }
+        ~ReserveWindow() { cu_reserve_window(false); }
+    } reserve_window;
+    const TrainWS w = carve_train(*d, workspace);
+    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_train_backward: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    hipStream_t st = (hipStream_t)stream;
+    bool dlog_ready = false;
+    int rc0 = poll_async_error(false);          // flags of the forward, if they have arrived already
+    if (rc0 || (rc0 = check_forward_record(workspace, *d, planes_ok(*d), &dlog_ready))) return rc0;
+    S2VT_REQUIRE(dlogits || dlog_ready, "s2vt_train_backward: dlogits is null and s2vt_mean_ce_backward_fused has not run on this workspace");
+    if (planes_ok(*d)) {
+        XP = (gemm_mode() == 1) ? 1 : 3;
+        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
+        S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_backward: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
+        const std::vector<uint64_t> key = graph_key(0xB0 + (dlog_ready ? 1 : 0), d, p, g, {kw(feats), kw(dlogits), kw(dfeats), kw(workspace),
+                                                                                            kw(out_mask), kw(st)});
+        bool graphed = false;
+        rc0 = run_graphed(st, key, [&](hipStream_t s_) {
+                LaneDelayScope delay(s_);
+                return train_backward_x3(d, p, feats, dlogits, g, dfeats, w, q, s_, out_mask, dlog_ready);
+            }, &graphed);
+        if (!rc0 && graphed) {       // (see grads_ready) every gradient group is final behind the graph
+            if ((rc0 = grads_ready(0, st))) return rc0;
+            if ((rc0 = grads_ready(1, st))) return rc0;
+        }
+        return rc0 ? rc0 : post_async_error(st, w.err, 1);
+    }
+    return train_backward_f32(d, p, feats, dlogits, g, dfeats, w, st, out_mask);
+}
 static int train_backward_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                                const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream,
                                const float* out_mask) {
@@ -917,136 +1045,9 @@ static int train_backward_impl(const s2vt_dims* d, const s2vt_params* p, const f
     int rc;
     S2VT_HIP(hipMemcpyAsync(s.logits, dlogits, B * (L - 1) * V * sizeof(float), hipMemcpyDeviceToDevice, st));
     if ((rc = fill_zero(st, s.logits + B * (L - 1) * V, (Bp - B) * (L - 1) * V * sizeof(float)))) return rc;
-    if ((rc = train_backward_core(&dp, p, s.feats, s.logits, g, dfeats ? s.dfeats : nullptr, workspace, core, stream, out_mask ? s.mask : nullptr)))
-        return rc;
+    if ((rc = train_backward_core(&dp, p, s.feats, s.logits, g, dfeats ? s.dfeats : nullptr, workspace, core, stream, out_mask ? s.mask : nullptr))) return rc;
     if (dfeats) S2VT_HIP(hipMemcpyAsync(dfeats, s.dfeats, B * L * F * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
-}
-static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
-                               const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream,
-                               const float* out_mask) {
-    g_bwd_persist_launches = 0;          // (s2vt_backward_order describes THIS backward, whichever driver it takes)
-    g_bwd_group0_after = 0;
-    struct ReserveWindow {               // option cu_reserve: off until gradient group 0 is released, off again when the backward is enqueued
-        ReserveWindow() { cu_reserve_window(false); }
-        ~ReserveWindow() { cu_reserve_window(false); }
-    } reserve_window;
-    const TrainWS w = carve_train(*d, workspace);
-    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_train_backward: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
-    hipStream_t st = (hipStream_t)stream;
-    bool dlog_ready = false;
-    {
-        int rc0 = poll_async_error(false);          // flags of the forward, if they have arrived already
-        if (rc0) return rc0;
-        if ((rc0 = check_forward_record(workspace, *d, planes_ok(*d), &dlog_ready))) return rc0;
-    }
-    S2VT_REQUIRE(dlogits || dlog_ready, "s2vt_train_backward: dlogits is null and s2vt_mean_ce_backward_fused has not run on this workspace");
-    if (planes_ok(*d)) {
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
-        S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_backward: workspace %zu < %zu bytes",
-                     workspace_bytes, w.bytes + q.bytes);
-        std::vector<uint64_t> key;
-        if (graph_on()) {
-            key.reserve(80);
-            key.push_back(0xB0 + (dlog_ready ? 1 : 0));
-            for (int v : {d->B, d->L, d->F, d->H, d->E, d->V}) key.push_back((uint64_t)v);
-            key_options(key);
-            const float* const* pp = reinterpret_cast<const float* const*>(p);
-            for (size_t i = 0; i < sizeof(s2vt_params) / sizeof(void*); ++i) key_ptr(key, pp[i]);
-            float* const* gp = reinterpret_cast<float* const*>(g);
-            for (size_t i = 0; i < sizeof(s2vt_grads) / sizeof(void*); ++i) key_ptr(key, gp[i]);
-            key_ptr(key, feats); key_ptr(key, dlogits); key_ptr(key, dfeats); key_ptr(key, workspace); key_ptr(key, out_mask);
-            key_ptr(key, st);
-        }
-        bool graphed = false;
-        int rc0 = run_graphed(st, key, [&](hipStream_t s_) {
-                LaneDelayScope delay(s_);
-                return train_backward_x3(d, p, feats, dlogits, g, dfeats, w, q, s_, out_mask, dlog_ready);
-            }, &graphed);
-        if (!rc0 && graphed) {       // (see grads_ready) every gradient group is final behind the graph
-            if ((rc0 = grads_ready(0, st))) return rc0;
-            if ((rc0 = grads_ready(1, st))) return rc0;
-        }
-        return rc0 ? rc0 : post_async_error(st, w.err, 1);
-    }
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int R = (L - 1) * B;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
-    int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // word_rnn lane (caller's stream)
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // vid_rnn lane
-    LaneDelayScope delay(st);
-    size_t ev = 0;
-    if ((rc = handoff(st, sx, ev++))) return rc;
-    // lane A: gradient into the decode-step hidden states, then word_rnn BPTT       (autograd of S2VTModel.py:80, :77)
-    if ((rc = lgemm(la, true, false, R, H, V, dlogits, V, ID, p->out_w, H, ID, w.dh2dec, H, perm(L - 1, B), nullptr, false)))
-        return rc;
-    if (out_mask && (rc = mul_vectors(st, w.dh2dec, out_mask, w.dh2dec, (int64_t)R * H))) return rc;      // autograd of out_drop
-    if ((rc = transpose_f32(st, p->word_w_hh, 4 * H, H, w.wt2))) return rc;
-    // lane B meanwhile: out_linear weight/bias gradients (need only dlogits and the (masked) h2) and W_hh1^T
-    const float* hdec = w.h2 + L * BH;
-    if (out_mask) {
-        if ((rc = mul_vectors(sx, hdec, out_mask, w.dx1, (int64_t)R * H))) return rc;      // dx1: free until the vid_rnn input gradient
-        hdec = w.dx1;
-    }
-    if ((rc = lgemm(lb, false, false, V, H, R, dlogits, V, ID, hdec, H, perm(L - 1, B), g->out_w, H, ID, nullptr, false)))
-        return rc;
-    if ((rc = colsum_f32(sx, dlogits, R, V, V, lb.colsum, g->out_b, false))) return rc;
-    if ((rc = grads_ready(0, sx))) return rc;
-    if ((rc = transpose_f32(sx, p->vid_w_hh, 4 * H, H, w.wt1))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, blk);
-    for (size_t k = bd.size() - 1; k >= 1; --k) {
-        const int t0 = bd[k - 1], t1 = bd[k];
-        if ((rc = seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2))) return rc;
-        // gradient into vid_out for this block: dh1 = dG2·W_v                        (autograd of :75)
-        if ((rc = lgemm(la, true, false, (t1 - t0) * B, H, 4 * H, w.s2 + t0 * B4H, 4 * H, ID, p->word_w_ih + E, E + H, ID,
-                        w.dh1 + t0 * BH, H, ID, nullptr, false)))
-            return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;
-        if ((rc = seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1))) return rc;   // (autograd of :67)
-    }
-    // lane A: word_rnn parameter gradients + embedding gradient (run while lane B finishes the vid_rnn BPTT)
-    if ((rc = lgemm(la, false, false, 4 * H, H, (T - 1) * B, w.s2 + B4H, 4 * H, ID, w.h2, H, ID, g->word_w_hh, H, ID,
-                    nullptr, false)))
-        return rc;
-    if ((rc = lgemm(la, false, false, 4 * H, H, T * B, w.s2, 4 * H, ID, w.h1, H, ID, g->word_w_ih + E, E + H, ID, nullptr,
-                    false)))
-        return rc;
-    // dW_ih2[:, :E] = dG2[L..]^T · Emb[tok]: the embedded rows are gathered once (time-major) into w.de, which
-    // is free until the d(embedded words) GEMM below overwrites it
-    if ((rc = gather_rows_f32(st, p->emb_w, E, w.tok, R, E, w.de))) return rc;
-    if ((rc = lgemm(la, false, false, 4 * H, E, R, w.s2 + (int64_t)L * B4H, 4 * H, ID, w.de, E, ID, g->word_w_ih, E + H,
-                    ID, nullptr, false)))
-        return rc;
-    if ((rc = colsum_f32(st, w.s2, (int64_t)T * B, 4 * H, 4 * H, la.colsum, g->word_b_ih, false))) return rc;
-    S2VT_HIP(hipMemcpyAsync(g->word_b_hh, g->word_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
-    if ((rc = lgemm(la, true, false, R, E, 4 * H, w.s2 + (int64_t)L * B4H, 4 * H, ID, p->word_w_ih, E + H, ID, w.de, E, ID,
-                    nullptr, false)))
-        return rc;
-    if ((rc = embedding_grad(st, w.de, R, E, w.tok, V, g->emb_w, w.embws))) return rc;
-    if ((rc = grads_ready(1, st))) return rc;
-    // lane B: vid_rnn and feat_linear parameter gradients                           (autograd of :67, :54)
-    if ((rc = lgemm(lb, false, false, 4 * H, H, (T - 1) * B, w.s1 + B4H, 4 * H, ID, w.h1, H, ID, g->vid_w_hh, H, ID,
-                    nullptr, false)))
-        return rc;
-    if ((rc = lgemm(lb, false, false, 4 * H, H, L * B, w.s1, 4 * H, ID, w.x1, H, ID, g->vid_w_ih, H, ID, nullptr, false)))
-        return rc;
-    if ((rc = colsum_f32(sx, w.s1, (int64_t)T * B, 4 * H, 4 * H, lb.colsum, g->vid_b_ih, false))) return rc;
-    S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sx));
-    if ((rc = lgemm(lb, true, false, L * B, H, 4 * H, w.s1, 4 * H, ID, p->vid_w_ih, H, ID, w.dx1, H, ID, nullptr, false)))
-        return rc;
-    if ((rc = lgemm(lb, false, false, H, F, L * B, w.dx1, H, ID, feats, F, perm(B, L), g->feat_w, F, ID, nullptr, false)))
-        return rc;
-    if ((rc = colsum_f32(sx, w.dx1, (int64_t)L * B, H, H, lb.colsum, g->feat_b, false))) return rc;
-    if (dfeats) {
-        if ((rc = lgemm(lb, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, perm(B, L), nullptr, false)))
-            return rc;
-    }
-    return handoff(sx, st, ev++);
 }
 
 int s2vt_train_backward(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
@@ -1100,13 +1101,11 @@ int s2vt_mean_ce_backward_fused(const s2vt_dims* d, const float* logits, const i
     int rc;
     {
         ProfScope ps(st, K_CE, 1);
-        if ((rc = split_planes_dual(st, XP, logits, V, ID, R, V, q.dlog.p, q.dlog.ld, q.dlog.kpad, nullptr, 0, 0, w.colsum_c, &ce)))
-            return rc;
+        if ((rc = split_planes_dual(st, XP, logits, V, ID, R, V, q.dlog.p, q.dlog.ld, q.dlog.kpad, nullptr, 0, 0, w.colsum_c, &ce))) return rc;
     }
     std::lock_guard<std::mutex> lock(g_fwd_mutex);
     g_fwd_records[workspace].dlog_ready = true;
     return 0;
 }
-
 
 }
