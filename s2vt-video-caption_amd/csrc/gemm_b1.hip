@@ -21,29 +21,20 @@
 // workgroups of one XCD work on neighbouring tiles that share operand panels in its L2) and the stage pipeline runs ON across
 // tiles - the last stage of a tile requests the first stage of the next one, so that transfer lands under the epilogue's
 // stores and no tile but the first pays a prologue.
+// The frame it shares with gemm_x3.hip - argument struct, tile walk, epilogue, launch planner - is gemm_persist.h; this file keeps
+// the stage image, the loader, the fragment reads and the MFMA schedule.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_persist.h"
 #include "kernels.h"
 
 namespace s2vt {
 
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 typedef short bf16x4 __attribute__((ext_vector_type(4)));
-
-struct GemmB1Args {
-    int M, N, K;                              // K: multiple of 64 (zero-padded rows)
-    const unsigned short* A; int64_t lda;     // bf16 rows
-    const unsigned short* B; int64_t ldb;
-    float* C; int64_t ldc; RowMap cmap;
-    const float* bias;
-    int accumulate;
-    int ksplit;                               // k extent of a split-K slice (blockIdx.y), multiple of 64
-    float* slabs;
-    int ntm, ntn;                             // tile grid of this launch's tile height
-};
 
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t b1_rsrc(const void* base, unsigned bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)bytes, 0x00020000);
@@ -56,7 +47,7 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t b1_rsrc(const void* base, unsi
 // G ^ 2 (k & 3) (source-side swizzle again), and a fragment is two ds_read_b64_tr_b16 per lane (4 k rows x 16 columns each): the
 // 32 lanes of a half-wave then read 4 rows x 64 B that fall on 256 different bytes of the bank row.
 template <int MI, bool TT>
-__global__ __launch_bounds__(512) void gemm_b1_kernel(GemmB1Args p) {
+__global__ __launch_bounds__(512) void gemm_b1_kernel(PersistGemmArgs p) {
     static_assert(!TT || MI == 4, "the transposed-read variant is built for 256-column tiles of both images");
     constexpr int TM = 64 * MI, ROWS = TM + 256, STAGE = ROWS * 128, IMG_A = TM * 128, NREQ = MI + 4;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * STAGE];
@@ -66,24 +57,12 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(GemmB1Args p) {
     const int wm = wave >> 2, wn = wave & 3;
     const int li = lane & 31, lh = lane >> 5;
 
-    // ---- this workgroup's share of the tiles: the XCD of blockIdx % 8 owns a contiguous chunk of the (grouped) tile order,
-    // its gridDim / 8 workgroups walk that chunk side by side
-    const int items = p.ntm * p.ntn;
-    const int cpx = (items + 7) >> 3, gx = (int)gridDim.x >> 3;
-    const int xcd = blockIdx.x & 7;
-    const int q_end = ((xcd + 1) * cpx < items) ? (xcd + 1) * cpx : items;
-    int q = xcd * cpx + (int)(blockIdx.x >> 3);
+    const PersistWalk walk(p, blockIdx, gridDim);      // this workgroup's share of the tiles and its k slice
+    const int q_end = walk.q_end, gx = walk.gx, kbeg = walk.kbeg, kend = walk.kend;
+    int q = walk.q;
     if (q >= q_end) return;
-    const int kbeg = blockIdx.y * p.ksplit;
-    const int kend = (kbeg + p.ksplit < p.K) ? kbeg + p.ksplit : p.K;
     const int nk = (kend - kbeg) >> 6;                 // k64 stages per tile
-    auto tile_of = [&](int t, int& m0, int& n0) {
-        constexpr int GM = 4;
-        const int gsz = GM * p.ntn, grp = t / gsz, first_m = grp * GM;
-        const int gm = (p.ntm - first_m < GM) ? (p.ntm - first_m) : GM;
-        m0 = (first_m + (t % gsz) % gm) * TM;
-        n0 = ((t % gsz) / gm) * 256;
-    };
+    auto tile_of = [&](int t, int& m0, int& n0) { walk.tile_of<TM>(t, m0, n0); };
 
     // ---- loader role: request j of wave w covers stage rows 8w + 64j .. + 7 (j < MI: A rows of the tile, else B rows
     // 8w + 64(j - MI) ..): lane -> (row lane / 8, position lane % 8) <- piece (lane % 8) ^ ((row >> 1) & 7), and
@@ -249,12 +228,7 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(GemmB1Args p) {
     int m1 = 0, n1 = 0;
     if (qn < q_end) tile_of(qn, m1, n1);
     __amdgpu_buffer_rsrc_t ra1 = rsrc_a(m1), rb1 = rsrc_b(n1);
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    zero_acc<MI>(acc);
     for (int g = 0;; ++g) {             // the stages of all of this workgroup's tiles, one after the other
         const bool has_next = qn < q_end;
         for (; s + 1 < nk; ++s, ++g) {
@@ -264,95 +238,16 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(GemmB1Args p) {
         stage(g, std::false_type{}, has_next, ra1, rb1, 0, wait_all);      // the tile's last stage requests the next tile's first
         wait_all = true;
 
-        // ---- epilogue (the next tile's first stage is in flight under these stores).  The 32x32 accumulator layout gives a
-        // lane ONE column and 16 rows; stored as it stands that is 32 MI dword store instructions per wave, and a tile's
-        // epilogue is bound by their issue (16 us of a 44-us tile at K = 1024: with a quarter of them, timing only, the K = 1000
-        // shapes ran 20-25 % faster).  So every 4x4 block (registers 4j..4j+3 x the lanes of a quad) is transposed inside the
-        // quad (DPP quad_perm, two butterfly rounds) and a lane stores FOUR consecutive columns of one row as 16 bytes: a wave
-        // instruction then writes 8 rows x 128 B, a quarter of the instructions for the same bytes.
-        const bool full_m = m0 + TM <= p.M;
-        {
-            // (the lane's coordinates are made opaque here: address arithmetic of the epilogue that does not depend on the tile
-            // would otherwise be hoisted out of the tile loop and held in registers across the stage pipeline)
-            int e_li = li, e_lh = lh;
-            asm volatile("" : "+v"(e_li), "+v"(e_lh));
-            const int t = e_li & 3;
-            const bool odd = t & 1, hi = t & 2;
-            const int ncol = n0 + wn * 64 + (e_li & ~3);                   // first of this lane's four columns (ni = 0)
-            const bool vec = p.slabs ? ((p.N & 3) == 0 && (reinterpret_cast<uintptr_t>(p.slabs) & 15) == 0)
-                                     : ((p.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0);      // 16-byte rows
-            f32x4 bv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-            if (p.bias && !p.slabs) {
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int n = ncol + ni * 32 + k;
-                        bv[ni][k] = n < p.N ? p.bias[n] : 0.f;
-                    }
-            }
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + wm * 32 * MI + mi * 32 + 8 * j + 4 * e_lh + t;      // this lane's row after the transpose
-                    f32x4 v[2];
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        float a0 = acc[mi][ni][4 * j], a1 = acc[mi][ni][4 * j + 1], a2 = acc[mi][ni][4 * j + 2], a3 = acc[mi][ni][4 * j + 3];
-                        // round 1: lanes t <-> t ^ 1 exchange (a0, a1) and (a2, a3) crosswise; round 2: t <-> t ^ 2, (a0, a2) and (a1, a3)
-                        float s, r;
-                        s = odd ? a0 : a1; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, false));
-                        a0 = odd ? r : a0; a1 = odd ? a1 : r;
-                        s = odd ? a2 : a3; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, false));
-                        a2 = odd ? r : a2; a3 = odd ? a3 : r;
-                        s = hi ? a0 : a2; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, false));
-                        a0 = hi ? r : a0; a2 = hi ? a2 : r;
-                        s = hi ? a1 : a3; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, false));
-                        a1 = hi ? r : a1; a3 = hi ? a3 : r;
-                        v[ni] = f32x4{a0, a1, a2, a3};
-                    }
-                    if (m >= p.M) continue;
-                    float* row = p.slabs ? p.slabs + ((int64_t)blockIdx.y * p.M + m) * p.N : p.C + (int64_t)map_row(p.cmap, m) * p.ldc;
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        const int n = ncol + ni * 32;
-                        f32x4 o = v[ni];
-                        if (!p.slabs) { o[0] += bv[ni][0]; o[1] += bv[ni][1]; o[2] += bv[ni][2]; o[3] += bv[ni][3]; }
-                        if (vec && n + 4 <= p.N) {
-                            f32x4* q4 = reinterpret_cast<f32x4*>(row + n);
-                            if (p.accumulate && !p.slabs) { const f32x4 c = *q4; o[0] += c[0]; o[1] += c[1]; o[2] += c[2]; o[3] += c[3]; }
-                            *q4 = o;
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; ++k)
-                                if (n + k < p.N) {
-                                    float x = o[k];
-                                    if (p.accumulate && !p.slabs) x += row[n + k];
-                                    row[n + k] = x;
-                                }
-                        }
-                    }
-                }
-            }
-        }
+        // ---- epilogue: the next tile's first stage is in flight under its stores
+        store_tile<MI>(acc, m0, n0, wm, wn, li, lh, p.M, p.N, p.C, p.ldc, p.cmap, p.bias, p.accumulate, p.slabs);
         if (!has_next) break;
-        // at least 8 MI vector-memory instructions followed the requests of the next tile's first stage when all rows are valid and
-        // both column groups of the wave lie inside N: "at most 8 MI operations outstanding" then says those requests have landed
-        // (the counter retires in issue order) without sitting out the stores
-        wait_all = !(full_m && n0 + wn * 64 + 64 <= p.N);
+        wait_all = !store_tile_counted<MI>(p, m0, n0, wn);      // (counted: the next stage need not sit out these stores)
         q = qn; m0 = m1; n0 = n1; ra = ra1; rb = rb1;
         qn = q + gx;
         if (qn < q_end) tile_of(qn, m1, n1);
         ra1 = rsrc_a(m1); rb1 = rsrc_b(n1);
         s = 0;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        zero_acc<MI>(acc);
     }
 #undef B1_REQ
 #undef B1_RD
@@ -362,9 +257,6 @@ __global__ __launch_bounds__(512) void gemm_b1_kernel(GemmB1Args p) {
 #undef B1_PROD
 #undef B1_FENCE
 }
-
-int splitk_reduce(hipStream_t stream, const float* slabs, int nsplit, int M, int N, float* C, int64_t ldc, RowMap cmap,
-                  const float* bias, bool accumulate);
 
 // Per-tile cost model (us) of the launcher: a k64 stage of a (64 MI) x 256 tile and the tile's epilogue, measured with
 // tools/bench_gemm_shapes.py under S2VT_B1_MI (the stage is co-limited by the matrix pipes and by the ~65 GB/s a compute unit
@@ -380,20 +272,6 @@ void gemm_b1_tune(int tile_rows, int nsplit) {
 
 static int gemm_b1_impl(hipStream_t stream, bool tt, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
                        int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
-                       size_t splitk_ws_floats);
-int gemm_b1(hipStream_t stream, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
-            int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
-            size_t splitk_ws_floats) {
-    return gemm_b1_impl(stream, false, M, N, K, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats);
-}
-// C[M,N] (+)= X_A^T X_B from the bf16 ROW images X_A [K][lda >= pad(M)], X_B [K][ldb >= pad(N)]; K % 64 == 0
-int gemm_b1_tt(hipStream_t stream, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
-               int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
-               size_t splitk_ws_floats) {
-    return gemm_b1_impl(stream, true, M, N, K, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats);
-}
-static int gemm_b1_impl(hipStream_t stream, bool tt, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
-                       int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
                        size_t splitk_ws_floats) {
     if (M <= 0 || N <= 0) return 0;
     if (tt)
@@ -405,74 +283,37 @@ static int gemm_b1_impl(hipStream_t stream, bool tt, int M, int N, int K, const 
                      (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0,
                  "gemm_b1: K must be the zero-padded multiple of 64 of the bf16 rows, rows 16-B aligned");
     S2VT_REQUIRE(lda < (1 << 21) && ldb < (1 << 21), "gemm_b1: row stride beyond the 32-bit offsets of a 320-row tile");
-    GemmB1Args p;
-    p.M = M; p.N = N; p.K = K;
-    p.A = A; p.lda = lda;
-    p.B = B; p.ldb = ldb;
-    p.C = C; p.ldc = ldc; p.cmap = cmap; p.bias = bias; p.accumulate = accumulate ? 1 : 0;
-    // option "cu_reserve" = n: plan the persistent grids for n compute units fewer.  A launch is sized to ONE workgroup per compute
-    // unit with a static share of the tiles each; a long-lived foreign kernel on some of the units (a communication kernel of a
-    // data-parallel run) makes the workgroups that find no unit wait for a whole share (multi-GPU).
-    const int ncu = planned_compute_units();
-    // s2vt_gemm_tune(1, tile_rows, nsplit): overrides of the time model (kernel tests run every tile height,
-    // tools/bench_gemm_shapes.py calibrates the model with them)
-    const int force_mi = g_b1_force_mi, force_n = g_b1_force_n;
-    // tile height, split-K factor and grid by the time model: every workgroup walks ceil(its XCD's chunk / workgroups of the
-    // XCD) tiles of nk stages + an epilogue; split-K adds the fixed-order slab combine ((n + 1) passes over M x N floats at
-    // ~3.5 TB/s + a launch)
-    const int ntn = cdiv(N, 256);
-    int best_mi = 4, best_ns = 1, best_g = 8;
-    double best = 1e30;
-    // (transposed reads: a k slice of a row image behind one descriptor and int offsets stays below 2 GB - larger images are cut
-    // into k slices, as in gemm_x3.hip)
-    const int64_t ldmax = lda > ldb ? lda : ldb, kTTSpan = 0x7FFFF000ll;
+    // (force_*: s2vt_gemm_tune(1, tile_rows, nsplit) - kernel tests run every tile height, tools/bench_gemm_shapes.py calibrates the
+    // model with them; a k slice of a transposed row image stays below the 2 GB of the signed 32-bit offsets)
     static const int order[4] = {4, 5, 3, 2};
-    for (int oi = 0; oi < 4; ++oi) {
-        const int mi = order[oi];
-        if (tt ? mi != 4 : (force_mi && force_mi != mi)) continue;
-        const int tiles = cdiv(M, 64 * mi) * ntn;
-        for (int n = 1; n <= 16; ++n) {
-            if (n > 1 && (!splitk_ws || K < 512 || K / n < 256 || (size_t)n * M * N > splitk_ws_floats)) break;
-            if (force_n && n != force_n) continue;
-            const int ks = cdiv(cdiv(K, n), 64) * 64, nn = cdiv(K, ks);
-            if (nn != n) continue;
-            if (tt && (int64_t)ks * ldmax * 2 >= kTTSpan) continue;     // (a k slice of a row image must fit the signed 32-bit offsets)
-            int g = ncu / nn / 8 * 8;
-            if (g < 8) g = 8;
-            if (g > cdiv(tiles, 8) * 8) g = cdiv(tiles, 8) * 8;
-            const int per_wg = cdiv(cdiv(tiles, 8), g / 8);
-            const double rounds = (double)cdiv(g * nn, ncu);           // (more workgroups than compute units: they queue)
-            const double t = rounds * per_wg * ((ks / 64) * kB1Stage[mi] + kB1Epi[mi]) + 3.0 +
-                             (nn > 1 ? (nn + 1.0) * M * (double)N * 4.0 / 3.5e6 + 8.0 : 0.0);
-            if (t < best * 0.98) { best = t; best_mi = mi; best_ns = nn; best_g = g; }
-        }
-    }
-    if (best > 1e29) {      // (an override that no candidate met: one slice of 256-row tiles)
-        S2VT_REQUIRE(!tt || (int64_t)K * ldmax * 2 < kTTSpan,
-                     "gemm_b1_tt: a row image of %lld bytes needs k slices below 2 GB and split-K scratch for them (%zu floats given)",
-                     (long long)((int64_t)K * ldmax * 2), splitk_ws_floats);
-        best_mi = 4; best_ns = 1;
-        best_g = cdiv(cdiv(M, 256) * ntn, 8) * 8;
-        if (best_g > ncu) best_g = ncu;
-    }
-    p.ntm = cdiv(M, 64 * best_mi); p.ntn = ntn;
-    p.ksplit = (best_ns > 1) ? cdiv(cdiv(K, best_ns), 64) * 64 : K;
-    const int nsplit = (best_ns > 1) ? cdiv(K, p.ksplit) : 1;
-    p.slabs = (nsplit > 1) ? splitk_ws : nullptr;
-    const dim3 grid(best_g, nsplit);
-    if (tt) {
-        hipLaunchKernelGGL((gemm_b1_kernel<4, true>), grid, dim3(512), 0, stream, p);
-    } else {
-        switch (best_mi) {
-            case 2: hipLaunchKernelGGL((gemm_b1_kernel<2, false>), grid, dim3(512), 0, stream, p); break;
-            case 3: hipLaunchKernelGGL((gemm_b1_kernel<3, false>), grid, dim3(512), 0, stream, p); break;
-            case 5: hipLaunchKernelGGL((gemm_b1_kernel<5, false>), grid, dim3(512), 0, stream, p); break;
-            default: hipLaunchKernelGGL((gemm_b1_kernel<4, false>), grid, dim3(512), 0, stream, p); break;
-        }
-    }
-    S2VT_LAUNCH_CHECK("gemm_b1_kernel");
-    if (nsplit > 1) return splitk_reduce(stream, splitk_ws, nsplit, M, N, C, ldc, cmap, bias, accumulate);
-    return 0;
+    const PersistPlanIn in = {tt, M, N, K, lda > ldb ? lda : ldb, splitk_ws ? splitk_ws_floats : 0, g_b1_force_mi, g_b1_force_n,
+                              order, 4, true, 64, kB1Stage, kB1Epi, 0x7FFFF000ll};
+    return launch_persistent_gemm(
+        stream, in, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats, "gemm_b1_kernel",
+        "gemm_b1_tt: a row image of %lld bytes needs k slices below 2 GB and split-K scratch for them (%zu floats given)",
+        [&](int mi, dim3 grid, const PersistGemmArgs& p) {
+            if (tt) {
+                hipLaunchKernelGGL((gemm_b1_kernel<4, true>), grid, dim3(512), 0, stream, p);
+            } else {
+                switch (mi) {
+                    case 2: hipLaunchKernelGGL((gemm_b1_kernel<2, false>), grid, dim3(512), 0, stream, p); break;
+                    case 3: hipLaunchKernelGGL((gemm_b1_kernel<3, false>), grid, dim3(512), 0, stream, p); break;
+                    case 5: hipLaunchKernelGGL((gemm_b1_kernel<5, false>), grid, dim3(512), 0, stream, p); break;
+                    default: hipLaunchKernelGGL((gemm_b1_kernel<4, false>), grid, dim3(512), 0, stream, p); break;
+                }
+            }
+        });
+}
+int gemm_b1(hipStream_t stream, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
+            int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
+            size_t splitk_ws_floats) {
+    return gemm_b1_impl(stream, false, M, N, K, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats);
+}
+// C[M,N] (+)= X_A^T X_B from the bf16 ROW images X_A [K][lda >= pad(M)], X_B [K][ldb >= pad(N)]; K % 64 == 0
+int gemm_b1_tt(hipStream_t stream, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
+               int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
+               size_t splitk_ws_floats) {
+    return gemm_b1_impl(stream, true, M, N, K, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats);
 }
 
 }  // namespace s2vt

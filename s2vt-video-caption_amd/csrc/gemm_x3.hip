@@ -17,11 +17,14 @@
 // PERSISTENT: a launch is at most one workgroup per compute unit; each walks its share of the tiles (XCD-aware order) and
 // the ring runs ON across tiles - the last two stages of a tile request the first two of the next one, so no tile but the
 // first pays a prologue and the transfers land under the epilogue's stores.
+// The frame it shares with gemm_b1.hip - argument struct, tile walk, epilogue, launch planner - is gemm_persist.h; this file keeps
+// the stage image, the loader, the fragment reads and the MFMA schedule.
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "common.h"
+#include "gemm_persist.h"
 #include "kernels.h"
 
 namespace s2vt {
@@ -31,32 +34,6 @@ typedef short bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int X_REC = 6144;                // bytes of one (64-row block, k16 chunk) record: 6 pieces x 1 KB
 constexpr int X_NS = 3;                    // ring depth
-
-struct GemmX3Args {
-    int M, N, K;                              // K = padded k extent of this call (multiple of 64)
-    const unsigned short* A; int64_t lda;     // blocked planes; row-block stride = 64 * lda elements
-    const unsigned short* B; int64_t ldb;
-    float* C; int64_t ldc; RowMap cmap;
-    const float* bias;
-    int accumulate;
-    int ksplit;
-    float* slabs;
-    int ntm, ntn;                             // tile grid of this launch's tile height
-};
-
-// 4x4 transpose inside every quad of lanes: lane t of a quad holds (a0..a3) = column t of a 4x4 block whose rows are the four
-// registers; afterwards it holds row t (two butterfly rounds of DPP quad_perm exchanges)
-__device__ __forceinline__ void quad_transpose4(float& a0, float& a1, float& a2, float& a3, bool odd, bool hi) {
-    float s, r;
-    s = odd ? a0 : a1; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, false));
-    a0 = odd ? r : a0; a1 = odd ? a1 : r;
-    s = odd ? a2 : a3; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0xB1, 0xF, 0xF, false));
-    a2 = odd ? r : a2; a3 = odd ? a3 : r;
-    s = hi ? a0 : a2; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, false));
-    a0 = hi ? r : a0; a2 = hi ? a2 : r;
-    s = hi ? a1 : a3; r = __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, s), 0x4E, 0xF, 0xF, false));
-    a1 = hi ? r : a1; a3 = hi ? a3 : r;
-}
 
 // MI = 32-row MFMA tiles per wave in M: workgroup tile (64 MI) x 256, wave tile (32 MI) x 64.  The A operand fills MI 64-row
 // records of a stage, the B operand always four.
@@ -69,7 +46,7 @@ __device__ __forceinline__ void quad_transpose4(float& a0, float& a1, float& a2,
 // ds_read_b64_tr_b16 per lane (4 k rows x 16 columns each, transposed by the LDS hardware): a half-wave reads 4 rows x 64 B =
 // 256 contiguous bytes, conflict-free.  Same bytes staged, twice the (half-size) fragment reads, same MFMAs, same epilogue.
 template <int MI, bool TT>
-__global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
+__global__ __launch_bounds__(512) void gemm_x3_kernel(PersistGemmArgs p) {
     // (TT: the tile's 2 MI + 8 column pairs x 3 planes are 6 requests for each of MI + 4 loader waves, as in the NN form)
     constexpr int NRA = MI, TMR = 64 * MI, X_STAGE = (NRA + 4) * X_REC;
     __shared__ __attribute__((aligned(1024))) unsigned char smem[X_NS * X_STAGE];
@@ -79,24 +56,12 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
     const int wm = wave >> 2, wn = wave & 3;
     const int li = lane & 31, lh = lane >> 5;
 
-    // ---- this workgroup's share of the tiles (as gemm_b1_kernel): the XCD of blockIdx % 8 owns a contiguous chunk of the
-    // grouped tile order, its gridDim / 8 workgroups walk that chunk side by side
-    const int items = p.ntm * p.ntn;
-    const int cpx = (items + 7) >> 3, gx = (int)gridDim.x >> 3;
-    const int xcd = blockIdx.x & 7;
-    const int q_end = ((xcd + 1) * cpx < items) ? (xcd + 1) * cpx : items;
-    int q = xcd * cpx + (int)(blockIdx.x >> 3);
+    const PersistWalk walk(p, blockIdx, gridDim);      // this workgroup's share of the tiles and its k slice
+    const int q_end = walk.q_end, gx = walk.gx, kbeg = walk.kbeg, kend = walk.kend;
+    int q = walk.q;
     if (q >= q_end) return;
-    const int kbeg = blockIdx.y * p.ksplit;
-    const int kend = (kbeg + p.ksplit < p.K) ? kbeg + p.ksplit : p.K;
     const int nk = (kend - kbeg) >> 4;                 // k16 stages per tile (a multiple of 4)
-    auto tile_of = [&](int t, int& m0, int& n0) {
-        constexpr int GM = 4;
-        const int gsz = GM * p.ntn, grp = t / gsz, first_m = grp * GM;
-        const int gm = (p.ntm - first_m < GM) ? (p.ntm - first_m) : GM;
-        m0 = (first_m + (t % gsz) % gm) * TMR;
-        n0 = ((t % gsz) / gm) * 256;
-    };
+    auto tile_of = [&](int t, int& m0, int& n0) { walk.tile_of<TMR>(t, m0, n0); };
 
     // ---- loader role: waves 0..NRA-1 stream the A row-blocks of the tile, the next four waves the B row-blocks (wave index
     // = record index inside a stage; with MI < 4 the last waves load nothing); a row-block past the operand's last one is
@@ -272,12 +237,7 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
     if (qn < q_end) tile_of(qn, m1, n1);
     __amdgpu_buffer_rsrc_t r1 = rsrc_of(m1, n1);
     int nwait = 6;
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+    zero_acc<MI>(acc);
     for (int g = 0;; ++g) {             // the stages of all of this workgroup's tiles, one after the other
         const bool has_next = qn < q_end;
         for (; s + 2 < nk; ++s, ++g) {
@@ -292,91 +252,19 @@ __global__ __launch_bounds__(512) void gemm_x3_kernel(GemmX3Args p) {
 #pragma unroll
             for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0p[mi], b0p[ni], acc[mi][ni], 0, 0, 0);
 
-        // ---- epilogue (the next tile's first stages are in flight under these stores).  The 32x32 accumulator layout gives a
-        // lane ONE column and 16 rows; stored as it stands that is 32 MI dword store instructions per wave, and a tile's
-        // epilogue is bound by their issue.  Every 4x4 block (registers 4j..4j+3 x the lanes of a quad) is transposed inside
-        // the quad and a lane stores FOUR consecutive columns of one row as 16 bytes: a wave instruction then writes 8 rows x
-        // 128 B, a quarter of the instructions for the same bytes.
-        bool counted;
-        {
-            // (the lane's coordinates are made opaque here: address arithmetic of the epilogue that does not depend on the tile
-            // would otherwise be hoisted out of the tile loop and held in registers across the stage pipeline)
-            int e_li = li, e_lh = lh;
-            asm volatile("" : "+v"(e_li), "+v"(e_lh));
-            const int t = e_li & 3;
-            const bool odd = t & 1, hi = t & 2;
-            const int ncol = n0 + wn * 64 + (e_li & ~3);                   // first of this lane's four columns (ni = 0)
-            const bool vec = p.slabs ? ((p.N & 3) == 0 && (reinterpret_cast<uintptr_t>(p.slabs) & 15) == 0)
-                                     : ((p.ldc & 3) == 0 && (reinterpret_cast<uintptr_t>(p.C) & 15) == 0);      // 16-byte rows
-            // at least 8 MI vector-memory instructions follow the requests of the next tile's first stages: all rows valid and
-            // both column groups of the wave inside N (the next stage's counted wait relies on that lower bound)
-            counted = m0 + TMR <= p.M && n0 + wn * 64 + 64 <= p.N;
-            f32x4 bv[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
-            if (p.bias && !p.slabs) {
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int n = ncol + ni * 32 + k;
-                        bv[ni][k] = n < p.N ? p.bias[n] : 0.f;
-                    }
-            }
-#pragma unroll
-            for (int mi = 0; mi < MI; ++mi) {
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int m = m0 + wm * 32 * MI + mi * 32 + 8 * j + 4 * e_lh + t;      // this lane's row after the transpose
-                    f32x4 v[2];
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        float a0 = acc[mi][ni][4 * j], a1 = acc[mi][ni][4 * j + 1], a2 = acc[mi][ni][4 * j + 2], a3 = acc[mi][ni][4 * j + 3];
-                        quad_transpose4(a0, a1, a2, a3, odd, hi);
-                        v[ni] = f32x4{a0, a1, a2, a3};
-                    }
-                    if (m >= p.M) continue;
-                    float* row = p.slabs ? p.slabs + ((int64_t)blockIdx.y * p.M + m) * p.N : p.C + (int64_t)map_row(p.cmap, m) * p.ldc;
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni) {
-                        const int n = ncol + ni * 32;
-                        f32x4 o = v[ni];
-                        if (!p.slabs) { o[0] += bv[ni][0]; o[1] += bv[ni][1]; o[2] += bv[ni][2]; o[3] += bv[ni][3]; }
-                        if (vec && n + 4 <= p.N) {
-                            f32x4* q4 = reinterpret_cast<f32x4*>(row + n);
-                            if (p.accumulate && !p.slabs) { const f32x4 c = *q4; o[0] += c[0]; o[1] += c[1]; o[2] += c[2]; o[3] += c[3]; }
-                            *q4 = o;
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; ++k)
-                                if (n + k < p.N) {
-                                    float x = o[k];
-                                    if (p.accumulate && !p.slabs) x += row[n + k];
-                                    row[n + k] = x;
-                                }
-                        }
-                    }
-                }
-            }
-        }
+        // ---- epilogue: the next tile's first stages are in flight under its stores
+        store_tile<MI>(acc, m0, n0, wm, wn, li, lh, p.M, p.N, p.C, p.ldc, p.cmap, p.bias, p.accumulate, p.slabs);
         if (!has_next) break;
-        nwait = counted ? 6 + 8 * MI : 6;       // (6: everything but the youngest six operations - also correct, only later)
+        nwait = store_tile_counted<MI>(p, m0, n0, wn) ? 6 + 8 * MI : 6;       // (6: everything but the youngest six operations - also correct, only later)
         q = qn; m0 = m1; n0 = n1; r0 = r1;
         qn = q + gx;
         if (qn < q_end) tile_of(qn, m1, n1);
         r1 = rsrc_of(m1, n1);
         s = 0;
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[mi][ni][r] = 0.f;
+        zero_acc<MI>(acc);
     }
 #undef X3_REQ1
 }
-
-int splitk_reduce(hipStream_t stream, const float* slabs, int nsplit, int M, int N, float* C, int64_t ldc, RowMap cmap,
-                  const float* bias, bool accumulate);
 
 // Per-tile cost model (us) of the launcher: a k16 stage of a (64 MI) x 256 tile and the tile's epilogue (tools/bench_gemm_shapes.py
 // under S2VT_X3_MI); the stage is bound by the six plane products (12 MI MFMAs per wave)
@@ -390,7 +278,41 @@ void gemm_x3_tune(int tile_rows, int nsplit) {
 
 static int gemm_x3_impl(hipStream_t stream, bool tt, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
                        int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
-                       size_t splitk_ws_floats);
+                       size_t splitk_ws_floats) {
+    if (M <= 0 || N <= 0) return 0;
+    if (tt) {
+        S2VT_REQUIRE(K > 0 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= 3 * (int64_t)((M + 63) / 64 * 64) &&
+                         ldb >= 3 * (int64_t)((N + 63) / 64 * 64) && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
+                         (reinterpret_cast<uintptr_t>(B) & 15) == 0,
+                     "gemm_x3_tt: K (image rows) must be a multiple of 64, the row images hold pad64(M) / pad64(N) columns");
+    } else
+    S2VT_REQUIRE(K > 0 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= 3 * (int64_t)K && ldb >= 3 * (int64_t)K &&
+                     (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0,
+                 "gemm_x3: K must be the zero-padded multiple of 64 of the blocked plane layout, operands 16-B aligned");
+    // (force_*: s2vt_gemm_tune(3, tile_rows, nsplit) - kernel tests run every tile height, tools/bench_gemm_shapes.py; a k slice of a
+    // transposed row image stays below the 4 GB of the unsigned 32-bit offsets)
+    static const int order[3] = {4, 3, 2};
+    const PersistPlanIn in = {tt, M, N, K, lda > ldb ? lda : ldb, splitk_ws ? splitk_ws_floats : 0, g_x3_force_mi, g_x3_force_n,
+                              order, 3, false, 16, kX3Stage, kX3Epi, 0xFFFFF000ll};
+    return launch_persistent_gemm(
+        stream, in, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats, "gemm_x3_kernel",
+        "gemm_x3_tt: a row image of %lld bytes needs k slices below 4 GB and split-K scratch for them (%zu floats given)",
+        [&](int mi, dim3 grid, const PersistGemmArgs& p) {
+            if (tt) {
+                switch (mi) {
+                    case 2: hipLaunchKernelGGL((gemm_x3_kernel<2, true>), grid, dim3(512), 0, stream, p); break;
+                    case 3: hipLaunchKernelGGL((gemm_x3_kernel<3, true>), grid, dim3(512), 0, stream, p); break;
+                    default: hipLaunchKernelGGL((gemm_x3_kernel<4, true>), grid, dim3(512), 0, stream, p); break;
+                }
+            } else {
+                switch (mi) {
+                    case 2: hipLaunchKernelGGL((gemm_x3_kernel<2, false>), grid, dim3(512), 0, stream, p); break;
+                    case 3: hipLaunchKernelGGL((gemm_x3_kernel<3, false>), grid, dim3(512), 0, stream, p); break;
+                    default: hipLaunchKernelGGL((gemm_x3_kernel<4, false>), grid, dim3(512), 0, stream, p); break;
+                }
+            }
+        });
+}
 // A, B: blocked 3-plane operands (see the header of this file); K = their common padded k extent for this call.
 int gemm_x3(hipStream_t stream, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
             int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
@@ -403,91 +325,6 @@ int gemm_x3_tt(hipStream_t stream, int M, int N, int K, const unsigned short* A,
                int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
                size_t splitk_ws_floats) {
     return gemm_x3_impl(stream, true, M, N, K, A, lda, B, ldb, C, ldc, cmap, bias, accumulate, splitk_ws, splitk_ws_floats);
-}
-static int gemm_x3_impl(hipStream_t stream, bool tt, int M, int N, int K, const unsigned short* A, int64_t lda, const unsigned short* B,
-                       int64_t ldb, float* C, int64_t ldc, RowMap cmap, const float* bias, bool accumulate, float* splitk_ws,
-                       size_t splitk_ws_floats) {
-    if (M <= 0 || N <= 0) return 0;
-    if (tt) {
-        S2VT_REQUIRE(K > 0 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= 3 * (int64_t)((M + 63) / 64 * 64) &&
-                         ldb >= 3 * (int64_t)((N + 63) / 64 * 64) && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
-                         (reinterpret_cast<uintptr_t>(B) & 15) == 0,
-                     "gemm_x3_tt: K (image rows) must be a multiple of 64, the row images hold pad64(M) / pad64(N) columns");
-    } else
-    S2VT_REQUIRE(K > 0 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && lda >= 3 * (int64_t)K && ldb >= 3 * (int64_t)K &&
-                     (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0,
-                 "gemm_x3: K must be the zero-padded multiple of 64 of the blocked plane layout, operands 16-B aligned");
-    GemmX3Args p;
-    p.M = M; p.N = N; p.K = K;
-    p.A = A; p.lda = lda;
-    p.B = B; p.ldb = ldb;
-    p.C = C; p.ldc = ldc; p.cmap = cmap; p.bias = bias; p.accumulate = accumulate ? 1 : 0;
-    // option "cu_reserve" = n: plan the persistent grids for n compute units fewer.  A launch is sized to ONE workgroup per compute
-    // unit with a static share of the tiles each; a long-lived foreign kernel on some of the units (a communication kernel of a
-    // data-parallel run) makes the workgroups that find no unit wait for a whole share (multi-GPU).
-    const int ncu = planned_compute_units();
-    // s2vt_gemm_tune(3, tile_rows, nsplit): overrides of the time model (kernel tests run every tile height, tools/bench_gemm_shapes.py)
-    const int force_mi = g_x3_force_mi, force_n = g_x3_force_n;
-    // One workgroup per CU.  Tile height, split-K factor and grid by the time model: every workgroup walks ceil(its XCD's chunk /
-    // workgroups of the XCD) tiles of nk stages + an epilogue; split-K adds the fixed-order slab combine ((n + 1) passes over
-    // M x N floats at ~3.5 TB/s + a launch)
-    const int ntn = cdiv(N, 256);
-    int best_mi = 4, best_ns = 1, best_g = 8;
-    double best = 1e30;
-    // Transposed reads address a k slice of a row image through ONE buffer descriptor and 32-bit offsets: a slice (ks image rows of
-    // ld elements) must stay below 4 GB.  An image beyond that (dlogits from B = 768 on at V = 12000) is cut into k slices here -
-    // the split-K path with its fixed-order combine - instead of being refused.
-    const int64_t ldmax = lda > ldb ? lda : ldb, kTTSpan = 0xFFFFF000ll;
-    static const int order[3] = {4, 3, 2};
-    for (int oi = 0; oi < 3; ++oi) {
-        const int mi = order[oi];
-        if (force_mi && force_mi != mi) continue;
-        const int tiles = cdiv(M, 64 * mi) * ntn;
-        for (int n = 1; n <= 16; ++n) {
-            if (n > 1 && (!splitk_ws || K < 512 || K / n < 256 || (size_t)n * M * N > splitk_ws_floats)) break;
-            if (force_n && n != force_n) continue;
-            const int ks = cdiv(cdiv(K, n), 64) * 64, nn = cdiv(K, ks);
-            if (nn != n) continue;
-            if (tt && (int64_t)ks * ldmax * 2 >= kTTSpan) continue;     // (a k slice of a row image must fit the 32-bit offsets)
-            int g = ncu / nn / 8 * 8;
-            if (g < 8) g = 8;
-            if (g > cdiv(tiles, 8) * 8) g = cdiv(tiles, 8) * 8;
-            const int per_wg = cdiv(cdiv(tiles, 8), g / 8);
-            const double rounds = (double)cdiv(g * nn, ncu);
-            const double t = rounds * per_wg * ((ks / 16) * kX3Stage[mi] + kX3Epi[mi]) + 3.0 +
-                             (nn > 1 ? (nn + 1.0) * M * (double)N * 4.0 / 3.5e6 + 8.0 : 0.0);
-            if (t < best * 0.98) { best = t; best_mi = mi; best_ns = nn; best_g = g; }
-        }
-    }
-    if (best > 1e29) {      // (an override that no candidate met: one slice of 256-row tiles)
-        S2VT_REQUIRE(!tt || (int64_t)K * ldmax * 2 < kTTSpan,
-                     "gemm_x3_tt: a row image of %lld bytes needs k slices below 4 GB and split-K scratch for them (%zu floats given)",
-                     (long long)((int64_t)K * ldmax * 2), splitk_ws_floats);
-        best_mi = 4; best_ns = 1;
-        best_g = cdiv(cdiv(M, 256) * ntn, 8) * 8;
-        if (best_g > ncu) best_g = ncu;
-    }
-    p.ntm = cdiv(M, 64 * best_mi); p.ntn = ntn;
-    p.ksplit = (best_ns > 1) ? cdiv(cdiv(K, best_ns), 64) * 64 : K;
-    const int nsplit = (best_ns > 1) ? cdiv(K, p.ksplit) : 1;
-    p.slabs = (nsplit > 1) ? splitk_ws : nullptr;
-    const dim3 grid(best_g, nsplit);
-    if (tt) {
-        switch (best_mi) {
-            case 2: hipLaunchKernelGGL((gemm_x3_kernel<2, true>), grid, dim3(512), 0, stream, p); break;
-            case 3: hipLaunchKernelGGL((gemm_x3_kernel<3, true>), grid, dim3(512), 0, stream, p); break;
-            default: hipLaunchKernelGGL((gemm_x3_kernel<4, true>), grid, dim3(512), 0, stream, p); break;
-        }
-    } else {
-        switch (best_mi) {
-            case 2: hipLaunchKernelGGL((gemm_x3_kernel<2, false>), grid, dim3(512), 0, stream, p); break;
-            case 3: hipLaunchKernelGGL((gemm_x3_kernel<3, false>), grid, dim3(512), 0, stream, p); break;
-            default: hipLaunchKernelGGL((gemm_x3_kernel<4, false>), grid, dim3(512), 0, stream, p); break;
-        }
-    }
-    S2VT_LAUNCH_CHECK("gemm_x3_kernel");
-    if (nsplit > 1) return splitk_reduce(stream, splitk_ws, nsplit, M, N, C, ldc, cmap, bias, accumulate);
-    return 0;
 }
 
 }  // namespace s2vt
