@@ -1,4 +1,4 @@
-// Internal launch interface between the HIP kernels and the C-ABI drivers (api.hip).
+// Internal launch interface between the HIP kernels and the C-ABI drivers (api_*.hip).
 #pragma once
 #include "common.h"
 #include "philox.h"

@@ -34,71 +34,25 @@
 // carry sc1 as well.  Every spin is bounded (1 s of wall clock): on a time-out the workgroup sets *err and exits.
 // All workgroups of a launch must be co-resident (2 per CU): the launchers ask the runtime how many workgroups of the
 // kernel the device holds at once (compute units x occupancy, coresident_capacity()) and a shape that does not fit is
-// reported as unsupported, so the drivers fall back to one launch per timestep (api.hip).
-#include <mutex>
-
+// reported as unsupported, so the drivers fall back to one launch per timestep (api_train.hip).
 #include "common.h"
 #include "experiment.h"
 #include "kernels.h"
+#include "lstm_persist_frame.h"
 
 namespace s2vt {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned int gu32;
-
-constexpr int P_SR = 32;                          // batch rows per sub-step (= per chain)
 constexpr int P_UN = 16;                          // hidden units per workgroup (64 gate columns)
 constexpr int P_NT = 256;                         // 4 waves
 constexpr int P_KCH = 16;                         // k chunks of 64 (Kp <= 1024)
-constexpr int P_SLAB = P_KCH * P_SR * 128;        // h_{t-1} image: 64 KB
+constexpr int P_SLAB = P_KCH * PF_SR * 128;       // h_{t-1} image: 64 KB
 constexpr int P_RLD = 72;                         // row stride of the partial-sum image (floats): 8 mod 64, so the epilogue's
                                                   // f32x2 reads (4 rows x {0-7, 32-39} per half-wave) and the partial writes are conflict-free
 constexpr int P_HSM = P_SLAB;                     // bf16 h_t tile [32][16]
-constexpr int P_MAXNS = 4;
-constexpr int P_CST = P_HSM + P_SR * P_UN * 2;    // fp32 c_t of the workgroup's cells, per chain [32][16]
-constexpr int P_LDS = P_CST + P_MAXNS * P_SR * P_UN * 4;
+constexpr int P_CST = P_HSM + PF_SR * P_UN * 2;   // fp32 c_t of the workgroup's cells, per chain [32][16]
+constexpr int P_LDS = P_CST + PF_MAXNS * PF_SR * P_UN * 4;
 constexpr int P_MAX_WG = 512;                     // design point: 2 workgroups on each of 256 CUs (config 3 needs 2 x 252);
                                                   // the launchers cap this by what the device reports (persist_capacity)
-constexpr unsigned long long P_SPIN_TICKS = 100000000ull;      // 1 s of the 100-MHz wall clock
-
-__device__ __forceinline__ unsigned short f2bf_rn(float x) {
-    unsigned int u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
-
-// sigmoid / tanh on the hardware exp and reciprocal (1 ulp each): absolute error ~2e-7, far below the bf16 rounding of
-// the operands this kernel works on
-__device__ __forceinline__ float fast_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float fast_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
-
-#ifdef S2VT_EXPERIMENT_PLAIN_LOADS      // timing experiment only (tools/bench_bptt_stamps.py): what would hand-off loads without sc1 cost?
-#define P_LOAD_AUX 0
-#else
-#define P_LOAD_AUX 16 /* sc1 */
-#endif
-__device__ __forceinline__ void glds16_sc1(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, P_LOAD_AUX);
-}
-
-// one lane waits for *cnt >= target (relaxed agent-scope = sc1 loads); false on time-out
-__device__ __forceinline__ bool spin_until(const unsigned int* cnt, unsigned int target) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        const unsigned int v = __hip_atomic_load((gu32*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v >= target) return true;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > P_SPIN_TICKS) return false;
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
-
-#define P_DSR(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
-// workgroup barrier WITHOUT the vmcnt(0) drain __syncthreads() implies: global loads/stores stay in flight across it
-#define P_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 // FULL: Kp == 1024 (16 k chunks: the config-3 shape), counted vmcnt pipeline; otherwise every request is awaited first
 template <bool FULL>
@@ -144,22 +98,15 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
         fa[s] = lbase + (unsigned)(cbeg * 4096 + li * 128 + (((2 * s + lh) ^ ((li >> 1) & 7)) * 16));
 
     // ---- epilogue role: 2 adjacent units of one row per thread, the same (row, units) in every step
-    const int erow = tid >> 3, eul = (tid & 7) * 2;
-    const int eunit = u0 + eul;
-    const bool e_ok0 = eunit < H, e_ok1 = eunit + 1 < H;
-    const bool e_vec = e_ok1 && ((H & 1) == 0);        // 8-byte accesses: both units valid and rows 8-byte aligned
-    const int ecol = (eul >> 3) * 32 + (eul & 7);      // + g*8: column of gate g inside the workgroup's 64
+    const CellLane<P_UN> e(tid, u0, H);
+    const int ecol = (e.ul >> 3) * 32 + (e.ul & 7);    // + g*8: column of gate g inside the workgroup's 64
     // c_t of this thread's cells lives in LDS between steps (only this thread touches its entries)
     float* cst = reinterpret_cast<float*>(smem + P_CST);
     for (int s = 0; s < p.NS; ++s) {
-        const int b = row0 + s * P_SR + erow;
+        const int b = row0 + s * PF_SR + e.row;
         f32x2 c0 = {0.f, 0.f};
-        if (p.t0 > 0 && b < B) {
-            const float* q = p.c_all + ((int64_t)(p.t0 - 1) * B + b) * H + eunit;
-            if (e_ok0) c0[0] = q[0];
-            if (e_ok1) c0[1] = q[1];
-        }
-        *reinterpret_cast<f32x2*>(cst + (s * P_SR + erow) * P_UN + eul) = c0;
+        if (p.t0 > 0 && b < B) c0 = e.carry(p.c_all + ((int64_t)(p.t0 - 1) * B + b) * H + e.unit);
+        *reinterpret_cast<f32x2*>(cst + (s * PF_SR + e.row) * P_UN + e.ul) = c0;
     }
 
     float* red = reinterpret_cast<float*>(smem);
@@ -169,38 +116,23 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
     for (int t = p.t0; t < p.t1; ++t) {
 #pragma unroll 1
         for (int s = 0; s < p.NS; ++s) {
-            const int rbase = row0 + s * P_SR;            // first batch row of this sub-step
-            unsigned int* cnt = p.sync + (rbase / P_SR) * 32;          // one counter per 32-row chain, whatever NS the launch uses
+            const int rbase = row0 + s * PF_SR;            // first batch row of this sub-step
+            unsigned int* cnt = chain_counter(p.sync, rbase);
             const int xrec = (bid == p.stamp_block) ? (t - p.t0) * p.NS + s : -1;
             XSTAMP(p.stamps, xrec, 0);
 
-            if (t > p.t0) {          // h_{t-1} of this chain published by every column slice of the row group?
-                if (tid == 0) {
-                    const bool ok = spin_until(cnt, (unsigned int)(nC * t));     // every workgroup of the chain has finished steps 0..t-1
-                    s_flag = ok ? 1 : 0;
-                    if (!ok) atomicExch(p.err, 1);
-                }
-                P_BARRIER();
-                if (s_flag == 0) return;
-            }
+            // h_{t-1} of this chain published by every column slice of the row group (each has finished steps 0..t-1)?
+            if (t > p.t0 && !chain_arrived(cnt, (unsigned int)(nC * t), p.err, s_flag)) return;
             XSTAMP(p.stamps, xrec, 1);
 
             // epilogue operands requested now, consumed after the contraction
-            const int eb = rbase + erow;
+            const int eb = rbase + e.row;
             const bool rok = eb < B;
             f32x2 gxv[4];
             {
                 const float* gsrc = (t < p.n_gx) ? p.gx_stash + ((int64_t)t * B + eb) * H4 : p.bias;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float* q = gsrc + (int64_t)g * H + eunit;
-                    if (e_vec) {
-                        gxv[g] = *reinterpret_cast<const f32x2*>(rok ? q : g_zero4);
-                    } else {
-                        gxv[g][0] = *((rok && e_ok0) ? q : g_zero4);
-                        gxv[g][1] = *((rok && e_ok1) ? q + 1 : g_zero4);
-                    }
-                }
+                for (int g = 0; g < 4; ++g) gxv[g] = e.load(gsrc + (int64_t)g * H + e.unit, rok);
             }
 
             f32x16 acc;
@@ -226,8 +158,8 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
                     asm volatile("s_barrier" ::: "memory");                                                        \
                     if (FULL || cbeg + (I) < cend) {                                                               \
                         bf16x8 a0, a1, a2, a3;                                                                     \
-                        P_DSR(a0, fa[0], (I) * 4096); P_DSR(a1, fa[1], (I) * 4096);                                \
-                        P_DSR(a2, fa[2], (I) * 4096); P_DSR(a3, fa[3], (I) * 4096);                                \
+                        PF_DSR(a0, fa[0], (I) * 4096); PF_DSR(a1, fa[1], (I) * 4096);                                \
+                        PF_DSR(a2, fa[2], (I) * 4096); PF_DSR(a3, fa[3], (I) * 4096);                                \
                         asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(a0));                                           \
                         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, wreg[(I) * 4 + 0], acc, 0, 0, 0);        \
                         asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a1));                                           \
@@ -246,14 +178,14 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
             }
 
             XSTAMP(p.stamps, xrec, 4);
-            P_BARRIER();                       // every wave is done with the h image: the partial sums may take its place
+            PF_BARRIER();                       // every wave is done with the h image: the partial sums may take its place
             {
-                float* rp = red + (kw * P_SR) * P_RLD;
+                float* rp = red + (kw * PF_SR) * P_RLD;
 #pragma unroll
                 for (int r = 0; r < 16; ++r)
                     rp[((r & 3) + 8 * (r >> 2) + 4 * lh) * P_RLD + cw * 32 + li] = acc[r];
             }
-            P_BARRIER();
+            PF_BARRIER();
             XSTAMP(p.stamps, xrec, 5);
 
             f32x2 gate[4], cv, hv;
@@ -261,26 +193,25 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
                 f32x2 pre[4];
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    pre[g] = *reinterpret_cast<const f32x2*>(red + erow * P_RLD + ecol + g * 8) +
-                             *reinterpret_cast<const f32x2*>(red + (P_SR + erow) * P_RLD + ecol + g * 8) + gxv[g];
-                f32x2* cp = reinterpret_cast<f32x2*>(cst + (s * P_SR + erow) * P_UN + eul);
+                    pre[g] = *reinterpret_cast<const f32x2*>(red + e.row * P_RLD + ecol + g * 8) +
+                             *reinterpret_cast<const f32x2*>(red + (PF_SR + e.row) * P_RLD + ecol + g * 8) + gxv[g];
+                f32x2* cp = reinterpret_cast<f32x2*>(cst + (s * PF_SR + e.row) * P_UN + e.ul);
                 const f32x2 cprev = *cp;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    gate[0][j] = fast_sigmoid(pre[0][j]);
-                    gate[1][j] = fast_sigmoid(pre[1][j]);
-                    gate[2][j] = fast_tanh(pre[2][j]);
-                    gate[3][j] = fast_sigmoid(pre[3][j]);
-                    const bool ok = rok && (j ? e_ok1 : e_ok0);
-                    cv[j] = ok ? gate[1][j] * cprev[j] + gate[0][j] * gate[2][j] : 0.f;
-                    hv[j] = gate[3][j] * fast_tanh(cv[j]);
+                    float gj[4], cj, hj;
+                    cell_forward<ActFast>(pre[0][j], pre[1][j], pre[2][j], pre[3][j], cprev[j], rok && e.ok(j), gj, cj, hj);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) gate[g][j] = gj[g];
+                    cv[j] = cj;
+                    hv[j] = hj;
                 }
                 *cp = cv;
-                *reinterpret_cast<unsigned int*>(hsm + erow * P_UN + eul) =
+                *reinterpret_cast<unsigned int*>(hsm + e.row * P_UN + e.ul) =
                     (unsigned int)f2bf_rn(hv[0]) | ((unsigned int)f2bf_rn(hv[1]) << 16);
             }
             XSTAMP(p.stamps, xrec, 6);
-            P_BARRIER();
+            PF_BARRIER();
             if (wave == 0) {   // bf16 h_t tile: 32 rows x 32 B = ONE 16-byte write-through store instruction, issued first:
                                // it is what the other workgroups wait for
                 const int rl = lane >> 1, part = lane & 1;
@@ -290,24 +221,13 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
             }
             if (rok) {
                 const int64_t rowi = (int64_t)t * B + eb;
-                float* cdst = p.c_all + rowi * H + eunit;
-                float* hdst = p.h_all ? p.h_all + rowi * H + eunit : nullptr;
-                float* st = p.gx_stash + rowi * H4 + eunit;
-                if (e_vec) {
-                    *reinterpret_cast<f32x2*>(cdst) = cv;
-                    if (hdst) *reinterpret_cast<f32x2*>(hdst) = hv;
+                float* cdst = p.c_all + rowi * H + e.unit;
+                float* hdst = p.h_all ? p.h_all + rowi * H + e.unit : nullptr;
+                float* st = p.gx_stash + rowi * H4 + e.unit;
+                e.store(cdst, cv);
+                if (hdst) e.store(hdst, hv);
 #pragma unroll
-                    for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x2*>(st + (int64_t)g * H) = gate[g];
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        if (j ? e_ok1 : e_ok0) {
-                            cdst[j] = cv[j];
-                            if (hdst) hdst[j] = hv[j];
-#pragma unroll
-                            for (int g = 0; g < 4; ++g) st[(int64_t)g * H + j] = gate[g][j];
-                        }
-                }
+                for (int g = 0; g < 4; ++g) e.store(st + (int64_t)g * H, gate[g]);
             }
             XSTAMP(p.stamps, xrec, 7);
             if (wave == 0) {   // the ONE wave that stored the hand-off payload drains and signals for the workgroup
@@ -316,31 +236,9 @@ __device__ __forceinline__ void seq_fwd_body(const SeqFwdBf16Args& p, const int 
                 if (lane == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             XSTAMP(p.stamps, xrec, 9);
-            P_BARRIER();       // hsm / cst / partial sums are free again
+            PF_BARRIER();       // hsm / cst / partial sums are free again
         }
     }
-}
-
-// Which role a block plays: (layer, workgroup index inside the layer = rg * nC + cs).  xg == 0: blocks [0, na) are layer A in
-// order, the rest layer B.  xg = G > 0 (XCD-aware, the launchers choose it when 8 % G == 0 and G * nC % 8 == 0): the hardware
-// deals workgroups to the 8 XCDs round-robin (block b -> XCD b % 8, speed only - nothing depends on it for correctness); a GROUP
-// is the nC column slices of one (layer, row group), i.e. the workgroups that read the SAME rows in every sub-step, and group g
-// is dealt to the XCDs {g, g + G, ..}: its rows then enter 8/G L2s instead of all eight, and a line is shared by nC * G / 8
-// readers of one L2 instead of nC / 8.
-__device__ __forceinline__ int persist_role(int bid, int na, int nC, int xg, bool& layer_b) {
-    if (xg <= 0) { layer_b = bid >= na; return layer_b ? bid - na : bid; }
-    const int x = bid & 7, q = bid >> 3, per = 8 / xg;
-    const int g = x % xg, cs = q * per + x / xg;
-    const int rgs = na / nC;                         // row groups of layer A (= of layer B: the launcher checked)
-    layer_b = g >= rgs;
-    return (layer_b ? g - rgs : g) * nC + cs;
-}
-// the launcher's side of it: G groups, or 0 for the plain order
-static int xcd_groups(int na, int nb, int nC) {
-    if (nC <= 0 || na % nC || nb % nC) return 0;
-    if (nb && nb != na) return 0;
-    const int G = (na + nb) / nC;
-    return (G > 0 && 8 % G == 0 && ((na + nb) % 8) == 0) ? G : 0;
 }
 
 // grid = [na workgroups of layer pa | workgroups of layer pb] (nb may be 0), or dealt by persist_role
@@ -350,39 +248,16 @@ __global__ __launch_bounds__(P_NT, 2) void lstm_seq_fwd_bf16_persist_kernel(SeqF
     __shared__ int s_flag;                 // poll result of the polling lane
     bool lb;
     const int vb = persist_role((int)blockIdx.x, na, (pa.H + P_UN - 1) / P_UN, xg, lb);
+    if (vb < 0) return;               // (an idle block of a padded grid: the bf16 launches never produce one)
     if (!lb) seq_fwd_body<FULL>(pa, vb, smem, s_flag);
     else seq_fwd_body<FULL>(pb, vb, smem, s_flag);
 }
 
-int lstm_seq_fwd_bf16_persist_supported(int B, int H, int Kp);
-size_t lstm_persist_sync_bytes();
-
-int coresident_capacity(const void* kernel, int block) {
-    struct Entry { int dev; const void* k; int cap; };
-    static Entry cache[32];
-    static int n = 0;
-    static std::mutex mu;               // the forward (caller's thread) and the backward (autograd's thread) both size launches
-    std::lock_guard<std::mutex> lock(mu);
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    for (int i = 0; i < n; ++i)
-        if (cache[i].dev == dev && cache[i].k == kernel) return cache[i].cap;
-    int cus = 0, occ = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, block, 0) != hipSuccess) occ = 0;
-    (void)hipGetLastError();
-    const int cap = (cus > 0 && occ > 0) ? cus * occ : 0;
-    if (n < 32) cache[n++] = Entry{dev, kernel, cap};
-    return cap;
-}
 // what one launch of the bf16 kernels may hold: the smaller of the three kernels' capacities, at most the design point
 static int persist_capacity() {
-    int cap = P_MAX_WG;
-    const int c1 = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_fwd_bf16_persist_kernel<true>), P_NT);
-    const int c2 = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_fwd_bf16_persist_kernel<false>), P_NT);
-    if (c1 < cap) cap = c1;
-    if (c2 < cap) cap = c2;
-    return cap;
+    const int c1 = persist_capacity_of(&lstm_seq_fwd_bf16_persist_kernel<true>, P_NT, P_MAX_WG);
+    const int c2 = persist_capacity_of(&lstm_seq_fwd_bf16_persist_kernel<false>, P_NT, P_MAX_WG);
+    return c1 < c2 ? c1 : c2;
 }
 
 // =============================================================================================== backward (BPTT)
@@ -416,8 +291,8 @@ struct BwdCfg {
     static constexpr int NTU = UN / 16;                      // 16-unit MFMA column tiles
     static constexpr int RLD = UN + 2;                       // row stride of a partial tile (floats)
     static constexpr int DGSM = NW * Q_RING;                 // bf16 dG_t tile [32][4 * UN]
-    static constexpr int DCST = DGSM + P_SR * 4 * UN * 2;    // fp32 dc of the workgroup's cells, per chain [32][UN]
-    static constexpr int LDS = DCST + P_MAXNS * P_SR * UN * 4;
+    static constexpr int DCST = DGSM + PF_SR * 4 * UN * 2;    // fp32 dc of the workgroup's cells, per chain [32][UN]
+    static constexpr int LDS = DCST + PF_MAXNS * PF_SR * UN * 4;
     static_assert(CPW * 2 * NTU == 32, "the W_hh^T slice of a wave is 32 bf16x8 registers");
     static_assert(LDS <= 160 * 1024, "LDS budget");
 };
@@ -474,16 +349,15 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
         }
 
     // ---- epilogue role: 2 adjacent units of one row per thread (32 rows x UN / 2 pairs = NT threads)
-    const int erow = tid / (UN / 2), eul = (tid % (UN / 2)) * 2;
-    const int eunit = u0 + eul;
-    const bool e_ok = eunit + 1 < H;                   // H % 8 == 0: a pair is valid or not as a whole
+    const CellLane<UN> e(tid, u0, H);
+    const bool e_ok = e.ok1;                           // H % 8 == 0: a pair is valid or not as a whole
     float* dcst = reinterpret_cast<float*>(smem + C::DCST);
     const bool last_block = (p.t1 == p.T);
     for (int s = 0; s < p.NS; ++s) {
-        const int b = row0 + s * P_SR + erow;
+        const int b = row0 + s * PF_SR + e.row;
         f32x2 d0 = {0.f, 0.f};
-        if (!last_block && e_ok && b < B) d0 = *reinterpret_cast<const f32x2*>(p.dc + (int64_t)b * H + eunit);
-        *reinterpret_cast<f32x2*>(dcst + (s * P_SR + erow) * UN + eul) = d0;
+        if (!last_block && e_ok && b < B) d0 = e.load_pair(p.dc + (int64_t)b * H + e.unit, true);
+        *reinterpret_cast<f32x2*>(dcst + (s * PF_SR + e.row) * UN + e.ul) = d0;
     }
     unsigned short* dgsm = reinterpret_cast<unsigned short*>(smem + C::DGSM);
     const int64_t H4 = 4 * (int64_t)H;
@@ -491,36 +365,30 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
     for (int t = p.t1 - 1; t >= p.t0; --t) {
 #pragma unroll 1
         for (int s = 0; s < p.NS; ++s) {
-            const int rbase = row0 + s * P_SR;
-            unsigned int* cnt = p.sync + (rbase / P_SR) * 32;          // one counter per 32-row chain, whatever NS the launch uses
+            const int rbase = row0 + s * PF_SR;
+            unsigned int* cnt = chain_counter(p.sync, rbase);
             const int done = p.t1 - 1 - t;             // steps of this launch already finished by every workgroup?
             const int done_all = p.T - 1 - t;          // ... and of the whole sequence: the counters run on from launch to launch
             const int xrec = (bid == p.stamp_block) ? done * p.NS + s : -1;
             XSTAMP(p.stamps, xrec, 0);
-            if (done > 0) {
-                if (tid == 0) {
-                    const bool ok = spin_until(cnt, (unsigned int)(nC * done_all));
-                    s_flag = ok ? 1 : 0;
-                    if (!ok) atomicExch(p.err, 1);
-                }
-                P_BARRIER();
-                if (s_flag == 0) return;
-            }
+            if (done > 0 && !chain_arrived(cnt, (unsigned int)(nC * done_all), p.err, s_flag)) return;
 
             XSTAMP(p.stamps, xrec, 1);
             // epilogue operands requested now (older than every ring request: they never hold a counted wait up)
-            const int eb = rbase + erow;
+            const int eb = rbase + e.row;
             const bool ok = e_ok && eb < B;
             const int64_t rowi = (int64_t)t * B + eb;
             f32x2 stv[4], cv, cpv, dhov;
             {
-                const float* st = p.stash_dg + rowi * H4 + eunit;
+                const float* st = p.stash_dg + rowi * H4 + e.unit;
+                // (longhand, not CellLane::load_pair(): through the helper both instantiations take two more SGPRs,
+                // profiles/recur_frame_refactor.txt)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) stv[g] = *reinterpret_cast<const f32x2*>(ok ? st + (int64_t)g * H : g_zero4);
-                cv = *reinterpret_cast<const f32x2*>(ok ? p.c_all + rowi * H + eunit : g_zero4);
-                cpv = *reinterpret_cast<const f32x2*>((ok && t > 0) ? p.c_all + (rowi - B) * H + eunit : g_zero4);
+                cv = *reinterpret_cast<const f32x2*>(ok ? p.c_all + rowi * H + e.unit : g_zero4);
+                cpv = *reinterpret_cast<const f32x2*>((ok && t > 0) ? p.c_all + (rowi - B) * H + e.unit : g_zero4);
                 dhov = *reinterpret_cast<const f32x2*>((ok && p.dh_out && t >= p.dh_first)
-                                                           ? p.dh_out + ((int64_t)(t - p.dh_first) * B + eb) * H + eunit : g_zero4);
+                                                           ? p.dh_out + ((int64_t)(t - p.dh_first) * B + eb) * H + e.unit : g_zero4);
             }
 
             f32x4 acc[2][C::NTU];
@@ -548,8 +416,8 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
                 if ((J) < C::CPW) {                                                                           \
                     asm volatile("s_waitcnt vmcnt(" #VM ")" ::: "memory");                                    \
                     bf16x8 a00, a01, a10, a11;                                                                \
-                    P_DSR(a00, fa[0][0], ((J) % Q_NSLOT) * 4096); P_DSR(a10, fa[1][0], ((J) % Q_NSLOT) * 4096); \
-                    P_DSR(a01, fa[0][1], ((J) % Q_NSLOT) * 4096); P_DSR(a11, fa[1][1], ((J) % Q_NSLOT) * 4096); \
+                    PF_DSR(a00, fa[0][0], ((J) % Q_NSLOT) * 4096); PF_DSR(a10, fa[1][0], ((J) % Q_NSLOT) * 4096); \
+                    PF_DSR(a01, fa[0][1], ((J) % Q_NSLOT) * 4096); PF_DSR(a11, fa[1][1], ((J) % Q_NSLOT) * 4096); \
                     asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(a00), "+v"(a10));                              \
                     Q_MFMA(J, 0, a00, a10)                                                                    \
                     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a01), "+v"(a11));                              \
@@ -585,7 +453,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
 #pragma unroll
                         for (int r = 0; r < 4; ++r) rp[(rt * 16 + 4 * lq + r) * C::RLD + ut * 16 + lm] = acc[rt][ut][r];
             }
-            P_BARRIER();
+            PF_BARRIER();
             XSTAMP(p.stamps, xrec, 4);
 
             f32x2 dg[4], dcn;
@@ -593,34 +461,30 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
                 f32x2 dh = dhov;
 #pragma unroll
                 for (int w = 0; w < NW; ++w)
-                    dh += *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(smem + w * Q_RING) + erow * C::RLD + eul);
-                f32x2* dp = reinterpret_cast<f32x2*>(dcst + (s * P_SR + erow) * UN + eul);
+                    dh += *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(smem + w * Q_RING) + e.row * C::RLD + e.ul);
+                f32x2* dp = reinterpret_cast<f32x2*>(dcst + (s * PF_SR + e.row) * UN + e.ul);
                 const f32x2 dcv = *dp;
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const float ig = stv[0][j], fg = stv[1][j], gg = stv[2][j], og = stv[3][j];
-                    const float tc = fast_tanh(cv[j]);
-                    const float dc = dh[j] * og * (1.0f - tc * tc) + dcv[j];
-                    const float d_o = dh[j] * tc;
-                    dg[0][j] = dc * gg * ig * (1.0f - ig);
-                    dg[1][j] = dc * cpv[j] * fg * (1.0f - fg);
-                    dg[2][j] = dc * ig * (1.0f - gg * gg);
-                    dg[3][j] = d_o * og * (1.0f - og);
-                    dcn[j] = ok ? dc * fg : 0.f;
+                    float dj[4], dcj;
+                    cell_backward<ActFast>(dh[j], stv[0][j], stv[1][j], stv[2][j], stv[3][j], cv[j], cpv[j], dcv[j], dj, dcj);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) dg[g][j] = dj[g];
+                    dcn[j] = ok ? dcj : 0.f;
                 }
                 *dp = dcn;
 #pragma unroll
                 for (int g = 0; g < 4; ++g)
-                    *reinterpret_cast<unsigned int*>(dgsm + erow * (4 * UN) + g * UN + eul) =
+                    *reinterpret_cast<unsigned int*>(dgsm + e.row * (4 * UN) + g * UN + e.ul) =
                         ok ? ((unsigned int)f2bf_rn(dg[g][0]) | ((unsigned int)f2bf_rn(dg[g][1]) << 16)) : 0u;
             }
             XSTAMP(p.stamps, xrec, 5);
-            P_BARRIER();
+            PF_BARRIER();
             XSTAMP(p.stamps, xrec, 6);
             if (wave == 0) {   // bf16 dG_t tile: 4 gates x (32 rows x UN*2 B): 16-byte write-through stores of ONE wave
                 constexpr int PPR = UN / 8;                                  // 16-byte parts per (row, gate)
 #pragma unroll
-                for (int pass = 0; pass < (P_SR * PPR) / 64; ++pass) {
+                for (int pass = 0; pass < (PF_SR * PPR) / 64; ++pass) {
                     const int idx = pass * 64 + lane, rl = idx / PPR, part = idx % PPR;
                     if (rbase + rl < B && u0 + part * 8 < H) {
                         unsigned short* drow = p.dgb + ((int64_t)t * B + rbase + rl) * p.lddgb + u0 + part * 8;
@@ -638,10 +502,10 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
                 }
             }
             if (ok) {
-                float* st = p.stash_dg + rowi * H4 + eunit;
+                float* st = p.stash_dg + rowi * H4 + e.unit;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x2*>(st + (int64_t)g * H) = dg[g];
-                if (t == p.t0) *reinterpret_cast<f32x2*>(p.dc + (int64_t)eb * H + eunit) = dcn;      // carried to the next launch
+                for (int g = 0; g < 4; ++g) e.store_pair(st + (int64_t)g * H, dg[g]);
+                if (t == p.t0) e.store_pair(p.dc + (int64_t)eb * H + e.unit, dcn);      // carried to the next launch
             }
             XSTAMP(p.stamps, xrec, 7);
             if (wave == 0) {
@@ -650,7 +514,7 @@ __device__ __forceinline__ void seq_bwd_body(const SeqBwdBf16Args& p, const int 
                 if (lane == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
             XSTAMP(p.stamps, xrec, 9);
-            P_BARRIER();       // rings (partial tiles), dG tile and dc state are free again
+            PF_BARRIER();       // rings (partial tiles), dG tile and dc state are free again
         }
     }
 }
@@ -661,6 +525,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4) ? 2 : 1) void lstm_seq_bwd_bf16_
     __shared__ int s_flag;
     bool lb;
     const int vb = persist_role((int)blockIdx.x, na, (pa.H + UN - 1) / UN, xg, lb);
+    if (vb < 0) return;
     if (!lb) seq_bwd_body<NW, UN>(pa, vb, smem, s_flag);
     else seq_bwd_body<NW, UN>(pb, vb, smem, s_flag);
 }
@@ -671,11 +536,7 @@ __global__ __launch_bounds__(NW * 64, (NW == 4) ? 2 : 1) void lstm_seq_bwd_bf16_
 // half the chains per workgroup, half the sub-steps per timestep.  The hand-off counters are per 32-row chain, so launches of
 // one layer with different NS continue each other.
 static int chains_for(int B, int H, int cap, int un, bool single = false) {
-    const int nC = cdiv(H, un), lim = single ? cap : cap / 2;
-    int R = B / P_SR;                       // row groups (one 32-row chain each) ...
-    int ns = 1;
-    while (R * nC > lim && ns < P_MAXNS && R % 2 == 0) { R /= 2; ns *= 2; }       // ... merged until a layer fits half
-    return (R * nC <= lim && R <= 64) ? ns : 0;                                   // the device (two layers co-run)
+    return plan_chains(B, cdiv(H, un), single ? cap : cap / 2, true);
 }
 
 // Which shape of the BPTT kernel a layer of (B, H) runs with: 32 units per workgroup (one workgroup per compute unit)
@@ -684,17 +545,15 @@ static int chains_for(int B, int H, int cap, int un, bool single = false) {
 struct BwdPlan { int un, ns, cap; };
 static BwdPlan bwd_plan(int B, int H, int Kp4, bool single = false) {
     BwdPlan none = {0, 0, 0};
-    if (!(B > 0 && B % P_SR == 0 && H % 8 == 0 && Kp4 % 64 == 0 && Kp4 >= 4 * H && Kp4 <= 64 * Q_KCH)) return none;
+    if (!(B > 0 && B % PF_SR == 0 && H % 8 == 0 && Kp4 % 64 == 0 && Kp4 >= 4 * H && Kp4 <= 64 * Q_KCH)) return none;
     const int pref = option(O_BPTT_UNITS);
     if (pref != 16) {
-        int cap = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_bwd_bf16_persist_kernel<8, 32>), 512);
-        if (cap > P_MAX_WG / 2) cap = P_MAX_WG / 2;
+        const int cap = persist_capacity_of(&lstm_seq_bwd_bf16_persist_kernel<8, 32>, 512, P_MAX_WG / 2);
         const int ns = chains_for(B, H, cap, 32, single);
         if (ns > 0 && chains_for(B, H, cap, 32) > 0) return BwdPlan{32, ns, cap};        // (the kernel shape is the pair's choice)
     }
     if (pref != 32) {
-        int cap = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_bwd_bf16_persist_kernel<4, 16>), 256);
-        if (cap > P_MAX_WG) cap = P_MAX_WG;
+        const int cap = persist_capacity_of(&lstm_seq_bwd_bf16_persist_kernel<4, 16>, 256, P_MAX_WG);
         const int ns = chains_for(B, H, cap, 16, single);
         if (ns > 0 && chains_for(B, H, cap, 16) > 0) return BwdPlan{16, ns, cap};
     }
@@ -715,43 +574,37 @@ static int prep_bwd(SeqBwdBf16Args& a, BwdPlan* plan, bool single = false) {
                      (reinterpret_cast<uintptr_t>(a.dc) & 7) == 0 && (!a.dh_out || (reinterpret_cast<uintptr_t>(a.dh_out) & 7) == 0),
                  "lstm_seq_bwd_bf16_persist: operands must be aligned bf16 rows zero-padded to Kp / 8-byte aligned fp32 rows");
     a.NS = plan->ns;
-    a.RB = plan->ns * P_SR;
+    a.RB = plan->ns * PF_SR;
     return 0;
 }
 
 int lstm_seq_bwd_bf16_persist2(hipStream_t stream, SeqBwdBf16Args a, const SeqBwdBf16Args* b) {
-    int rc;
-    BwdPlan pa, pb;
-    if ((rc = prep_bwd(a, &pa, b == nullptr))) return rc;
-    SeqBwdBf16Args bb = b ? *b : a;
-    pb = pa;
-    if (b) {
-        if ((rc = prep_bwd(bb, &pb))) return rc;
-        S2VT_REQUIRE(bb.sync != a.sync, "lstm_seq_bwd_bf16_persist: paired layers need their own counters");
-        S2VT_REQUIRE(pb.un == pa.un, "lstm_seq_bwd_bf16_persist: paired layers must run the same kernel shape");
-    }
-    const int na = (a.B / a.RB) * cdiv(a.H, pa.un), nb = b ? (bb.B / bb.RB) * cdiv(bb.H, pb.un) : 0;
-    S2VT_REQUIRE(na + nb <= pa.cap, "lstm_seq_bwd_bf16_persist: %d workgroups would not be co-resident (device capacity %d)",
-                 na + nb, pa.cap);
-    // the hand-off counters count finished timesteps of the whole sequence: zeroed with its first block only (a memset
-    // is a 5-us kernel of its own on this stream: 28 of them per train step when every launch zeroed its counters)
-    if (a.t1 == a.T) S2VT_HIP(hipMemsetAsync(a.sync, 0, lstm_persist_sync_bytes(), stream));
-    if (b && bb.t1 == bb.T) S2VT_HIP(hipMemsetAsync(bb.sync, 0, lstm_persist_sync_bytes(), stream));
-    const int xg = (!b || (bb.B == a.B && bb.H == a.H)) ? xcd_groups(na, nb, cdiv(a.H, pa.un)) : 0;
-    if (pa.un == 32)
-        hipLaunchKernelGGL((lstm_seq_bwd_bf16_persist_kernel<8, 32>), dim3(na + nb), dim3(512), 0, stream, a, bb, na, xg);
-    else
-        hipLaunchKernelGGL((lstm_seq_bwd_bf16_persist_kernel<4, 16>), dim3(na + nb), dim3(256), 0, stream, a, bb, na, xg);
-    S2VT_LAUNCH_CHECK("lstm_seq_bwd_bf16_persist_kernel");
-    return 0;
+    return launch_persistent_layers<true>(
+        stream, a, b, XCD_EXACT, "lstm_seq_bwd_bf16_persist", "lstm_seq_bwd_bf16_persist: paired layers need their own counters",
+        "lstm_seq_bwd_bf16_persist_kernel",
+        [](SeqBwdBf16Args& x, bool single, PersistLayer* l) {
+            BwdPlan plan;
+            const int rc = prep_bwd(x, &plan, single);
+            *l = PersistLayer{plan.un, plan.cap};
+            return rc;
+        },
+        [](const SeqBwdBf16Args&, const SeqBwdBf16Args&, const PersistLayer& la, const PersistLayer& lb) -> const char* {
+            return lb.un == la.un ? nullptr : "lstm_seq_bwd_bf16_persist: paired layers must run the same kernel shape";
+        },
+        [&](dim3 grid, const SeqBwdBf16Args& pa, const SeqBwdBf16Args& pb, int na, int xg, const PersistLayer& l) {
+            if (l.un == 32)
+                hipLaunchKernelGGL((lstm_seq_bwd_bf16_persist_kernel<8, 32>), grid, dim3(512), 0, stream, pa, pb, na, xg);
+            else
+                hipLaunchKernelGGL((lstm_seq_bwd_bf16_persist_kernel<4, 16>), grid, dim3(256), 0, stream, pa, pb, na, xg);
+        });
 }
 
 int lstm_seq_fwd_bf16_persist_supported(int B, int H, int Kp) {
-    if (!(B > 0 && B % P_SR == 0 && Kp % 64 == 0 && Kp >= H && Kp <= 64 * P_KCH)) return 0;
+    if (!(B > 0 && B % PF_SR == 0 && Kp % 64 == 0 && Kp >= H && Kp <= 64 * P_KCH)) return 0;
     return chains_for(B, H, persist_capacity(), P_UN);
 }
 
-size_t lstm_persist_sync_bytes() { return (size_t)64 * P_MAXNS * 32 * sizeof(unsigned int); }   // <= 64 row groups
+size_t lstm_persist_sync_bytes() { return (size_t)64 * PF_MAXNS * 32 * sizeof(unsigned int); }   // <= 64 row groups
 
 static int prep(SeqFwdBf16Args& a, const char* who, bool single = false) {
     // (`single` is not used here: a one-layer forward launch with half the chains per workgroup - 504 workgroups of ONE layer,
@@ -766,35 +619,31 @@ static int prep(SeqFwdBf16Args& a, const char* who, bool single = false) {
                      (reinterpret_cast<uintptr_t>(a.hb) & 15) == 0 && (reinterpret_cast<uintptr_t>(a.wb) & 15) == 0,
                  "%s: operands must be 16-B aligned bf16 rows zero-padded to Kp", who);
     a.NS = ns;
-    a.RB = ns * P_SR;
+    a.RB = ns * PF_SR;
     return 0;
 }
 
 // one layer (b == nullptr) or two layers side by side in one launch
 int lstm_seq_fwd_bf16_persist2(hipStream_t stream, SeqFwdBf16Args a, const SeqFwdBf16Args* b) {
-    int rc;
-    if ((rc = prep(a, "lstm_seq_fwd_bf16_persist", b == nullptr))) return rc;
-    SeqFwdBf16Args bb = b ? *b : a;
-    if (b) {
-        if ((rc = prep(bb, "lstm_seq_fwd_bf16_persist"))) return rc;
-        S2VT_REQUIRE(bb.Kp == a.Kp && bb.sync != a.sync, "lstm_seq_fwd_bf16_persist: paired layers need the same Kp and their own counters");
-    }
-    const int na = (a.B / a.RB) * cdiv(a.H, P_UN), nb = b ? (bb.B / bb.RB) * cdiv(bb.H, P_UN) : 0;
-    S2VT_REQUIRE(na + nb <= persist_capacity(), "lstm_seq_fwd_bf16_persist: %d workgroups would not be co-resident (device capacity %d)",
-                 na + nb, persist_capacity());
-    // (counters: see the BPTT launcher) zeroed with the sequence's first block
-    if (a.t0 == 0) S2VT_HIP(hipMemsetAsync(a.sync, 0, lstm_persist_sync_bytes(), stream));
-    if (b && bb.t0 == 0) S2VT_HIP(hipMemsetAsync(bb.sync, 0, lstm_persist_sync_bytes(), stream));
-    // (no XCD-aware dealing for the forward: with TWO workgroups per compute unit the neighbours on a CU must be out of phase to
-    // hide each other's hand-off latencies, and dealing a group to one XCD makes them members of the same chain - measured
+    static const char pair_msg[] = "lstm_seq_fwd_bf16_persist: paired layers need the same Kp and their own counters";
+    // (XCD_NONE - no XCD-aware dealing for the forward: with TWO workgroups per compute unit the neighbours on a CU must be out of
+    // phase to hide each other's hand-off latencies, and dealing a group to one XCD makes them members of the same chain - measured
     // 1.99 vs 1.84 ms per config-3 forward; the one-per-CU BPTT launch gains from it: 2.90 vs 3.12 ms)
-    const int xg = 0;
-    if (a.Kp == 64 * P_KCH)
-        hipLaunchKernelGGL((lstm_seq_fwd_bf16_persist_kernel<true>), dim3(na + nb), dim3(P_NT), 0, stream, a, bb, na, xg);
-    else
-        hipLaunchKernelGGL((lstm_seq_fwd_bf16_persist_kernel<false>), dim3(na + nb), dim3(P_NT), 0, stream, a, bb, na, xg);
-    S2VT_LAUNCH_CHECK("lstm_seq_fwd_bf16_persist_kernel");
-    return 0;
+    return launch_persistent_layers<false>(
+        stream, a, b, XCD_NONE, "lstm_seq_fwd_bf16_persist", pair_msg, "lstm_seq_fwd_bf16_persist_kernel",
+        [](SeqFwdBf16Args& x, bool single, PersistLayer* l) {
+            *l = PersistLayer{P_UN, persist_capacity()};
+            return prep(x, "lstm_seq_fwd_bf16_persist", single);
+        },
+        [](const SeqFwdBf16Args& pa, const SeqFwdBf16Args& pb, const PersistLayer&, const PersistLayer&) -> const char* {
+            return pb.Kp == pa.Kp ? nullptr : pair_msg;
+        },
+        [&](dim3 grid, const SeqFwdBf16Args& pa, const SeqFwdBf16Args& pb, int na, int xg, const PersistLayer&) {
+            if (pa.Kp == 64 * P_KCH)
+                hipLaunchKernelGGL((lstm_seq_fwd_bf16_persist_kernel<true>), grid, dim3(P_NT), 0, stream, pa, pb, na, xg);
+            else
+                hipLaunchKernelGGL((lstm_seq_fwd_bf16_persist_kernel<false>), grid, dim3(P_NT), 0, stream, pa, pb, na, xg);
+        });
 }
 int lstm_seq_fwd_bf16_persist(hipStream_t stream, SeqFwdBf16Args a) { return lstm_seq_fwd_bf16_persist2(stream, a, nullptr); }
 

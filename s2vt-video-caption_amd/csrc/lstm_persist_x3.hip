@@ -1,5 +1,5 @@
 // Persistent SPLIT-PRECISION LSTM forward recurrence for gfx950 (BASELINE config 2: B = 64, fp32-equivalent arithmetic):
-// the third member of the family lstm_persist.hip (bf16) / lstm_persist_f32.hip (exact-fp32 MFMA).  One launch runs a block of
+// the split-precision member of the family of lstm_persist.hip (bf16; the shared frame is lstm_persist_frame.h).  One launch runs a block of
 // timesteps of one layer - or of both layers side by side (S2VTModel.py:67 / :77 -> nn.LSTM over the steps) - with every
 // workgroup's slice of W_hh resident in registers and the same cross-workgroup hand-off protocol.
 //
@@ -24,44 +24,20 @@
 #include "common.h"
 #include "experiment.h"
 #include "kernels.h"
+#include "lstm_persist_frame.h"
 
 namespace s2vt {
 
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) unsigned int gu32;
-
-constexpr int X_SR = 32;                          // batch rows per sub-step (= per chain)
 constexpr int X_UN = 16;                          // hidden units per workgroup (64 gate columns)
 constexpr int X_NT = 256;                         // 4 waves = 4 k quarters
-constexpr int X_PLANE = X_SR * 128;               // one plane of a k64 chunk: 32 rows x 128 B
+constexpr int X_PLANE = PF_SR * 128;               // one plane of a k64 chunk: 32 rows x 128 B
 constexpr int X_CHUNK = 3 * X_PLANE;              // 12 KB
 constexpr int X_RING = 3 * X_CHUNK;               // per-wave ring: 3 slots
 constexpr int X_RLD = 72;                         // row stride of a partial-sum tile (floats): conflict-free f32x2 epilogue reads
 constexpr int X_HSM = 4 * X_RING;                 // bf16 h_t planes [3][32][16]
-constexpr int X_MAXNS = 4;
-constexpr int X_CST = X_HSM + 3 * X_SR * X_UN * 2;        // fp32 c_t of the workgroup's cells, per chain [32][16]
-constexpr int X_LDS = X_CST + X_MAXNS * X_SR * X_UN * 4;  // 158720 B
+constexpr int X_CST = X_HSM + 3 * PF_SR * X_UN * 2;        // fp32 c_t of the workgroup's cells, per chain [32][16]
+constexpr int X_LDS = X_CST + PF_MAXNS * PF_SR * X_UN * 4;  // 158720 B
 constexpr int X_MAX_WG = 256;                     // design point: one workgroup per CU; capped by coresident_capacity() at launch
-constexpr unsigned long long X_SPIN_TICKS = 100000000ull;      // 1 s of the 100-MHz wall clock
-
-__device__ __forceinline__ void glds16x_sc1(const void* g, void* l) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                     (__attribute__((address_space(3))) void*)l, 16, 0, 16 /* sc1 */);
-}
-__device__ __forceinline__ bool spin_until_x(const unsigned int* cnt, unsigned int target) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    for (;;) {
-        const unsigned int v = __hip_atomic_load((gu32*)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (v >= target) return true;
-        if (__builtin_amdgcn_s_memrealtime() - t0 > X_SPIN_TICKS) return false;
-        __builtin_amdgcn_s_sleep(2);
-    }
-}
-#define X_DSR(DST, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(DST) : "v"(ADDR), "n"(OFF))
-#define X_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int bid, unsigned char* smem, int& s_flag) {
     const unsigned lbase = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -113,21 +89,14 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
     for (int s = 0; s < 4; ++s) fa[s] = lbase + (unsigned)(kq * X_RING + li * 128 + (((2 * s + lh) ^ ((li >> 1) & 7)) * 16));
 
     // ---- epilogue role: 2 adjacent units of one row per thread, the same (row, units) in every step
-    const int erow = tid >> 3, eul = (tid & 7) * 2;
-    const int eunit = u0 + eul;
-    const bool e_ok0 = eunit < H, e_ok1 = eunit + 1 < H;
-    const bool e_vec = e_ok1 && ((H & 1) == 0);
-    const int ecol = (eul >> 3) * 32 + (eul & 7);      // + g*8: column of gate g inside the workgroup's 64
+    const CellLane<X_UN> e(tid, u0, H);
+    const int ecol = (e.ul >> 3) * 32 + (e.ul & 7);      // + g*8: column of gate g inside the workgroup's 64
     float* cst = reinterpret_cast<float*>(smem + X_CST);
     for (int s = 0; s < p.NS; ++s) {
-        const int b = row0 + s * X_SR + erow;
+        const int b = row0 + s * PF_SR + e.row;
         f32x2 c0 = {0.f, 0.f};
-        if (p.t0 > 0 && b < B) {
-            const float* q = p.c_all + ((int64_t)(p.t0 - 1) * B + b) * H + eunit;
-            if (e_ok0) c0[0] = q[0];
-            if (e_ok1) c0[1] = q[1];
-        }
-        *reinterpret_cast<f32x2*>(cst + (s * X_SR + erow) * X_UN + eul) = c0;
+        if (p.t0 > 0 && b < B) c0 = e.carry(p.c_all + ((int64_t)(p.t0 - 1) * B + b) * H + e.unit);
+        *reinterpret_cast<f32x2*>(cst + (s * PF_SR + e.row) * X_UN + e.ul) = c0;
     }
     unsigned short* hsm = reinterpret_cast<unsigned short*>(smem + X_HSM);
     const int64_t H4 = 4 * (int64_t)H;
@@ -137,37 +106,22 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
     for (int t = p.t0; t < p.t1; ++t) {
 #pragma unroll 1
         for (int s = 0; s < p.NS; ++s) {
-            const int rbase = row0 + s * X_SR;
-            unsigned int* cnt = p.sync + (rbase / X_SR) * 32;          // one counter per 32-row chain, whatever NS the launch uses
+            const int rbase = row0 + s * PF_SR;
+            unsigned int* cnt = chain_counter(p.sync, rbase);
             const int xrec = (bid == p.stamp_block) ? (t - p.t0) * p.NS + s : -1;
             XSTAMP(p.stamps, xrec, 0);
-            if (t > p.t0) {          // h_{t-1} of this chain published by every column slice of the row group?
-                if (tid == 0) {
-                    const bool ok = spin_until_x(cnt, (unsigned int)(nC * t));
-                    s_flag = ok ? 1 : 0;
-                    if (!ok) atomicExch(p.err, 1);
-                }
-                X_BARRIER();
-                if (s_flag == 0) return;
-            }
+            // h_{t-1} of this chain published by every column slice of the row group?
+            if (t > p.t0 && !chain_arrived(cnt, (unsigned int)(nC * t), p.err, s_flag)) return;
             XSTAMP(p.stamps, xrec, 1);
 
             // epilogue operands requested now, consumed after the contraction
-            const int eb = rbase + erow;
+            const int eb = rbase + e.row;
             const bool rok = eb < B;
             f32x2 gxv[4];
             {
                 const float* gsrc = (t < p.n_gx) ? p.gx_stash + ((int64_t)t * B + eb) * H4 : p.bias;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float* q = gsrc + (int64_t)g * H + eunit;
-                    if (e_vec) {
-                        gxv[g] = *reinterpret_cast<const f32x2*>(rok ? q : g_zero4);
-                    } else {
-                        gxv[g][0] = *((rok && e_ok0) ? q : g_zero4);
-                        gxv[g][1] = *((rok && e_ok1) ? q + 1 : g_zero4);
-                    }
-                }
+                for (int g = 0; g < 4; ++g) gxv[g] = e.load(gsrc + (int64_t)g * H + e.unit, rok);
             }
 
             f32x16 acc0, acc1;
@@ -180,13 +134,13 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
                 // that every wave issues the same number of requests (counted waits)
                 // request N (plane N / 4, row octet N % 4) of chunk C
 #define X_REQ(C, N)                                                                                             \
-                glds16x_sc1((4 * kq + (C)) * 64 < Kp ? abase + (4 * kq + (C)) * 128 + ((N) / 4) * hplane_b + voff[(N) % 4] : zsrc, \
+                glds16_sc1((4 * kq + (C)) * 64 < Kp ? abase + (4 * kq + (C)) * 128 + ((N) / 4) * hplane_b + voff[(N) % 4] : zsrc, \
                             ring + ((C) % 3) * X_CHUNK + ((N) / 4) * X_PLANE + ((N) % 4) * 1024);
 #define X_ISSUE(C)                                                                                              \
                 X_REQ(C, 0) X_REQ(C, 1) X_REQ(C, 2) X_REQ(C, 3) X_REQ(C, 4) X_REQ(C, 5)                         \
                 X_REQ(C, 6) X_REQ(C, 7) X_REQ(C, 8) X_REQ(C, 9) X_REQ(C, 10) X_REQ(C, 11)
                 // A fragment of plane PL for k16 step I (chunk I / 4 in slot (I / 4) % 3)
-#define X_RD1(PL, I) X_DSR(af[PL], fa[(I) & 3], (((I) >> 2) % 3) * X_CHUNK + (PL) * X_PLANE);
+#define X_RD1(PL, I) PF_DSR(af[PL], fa[(I) & 3], (((I) >> 2) % 3) * X_CHUNK + (PL) * X_PLANE);
 #define X_WAIT1(PL, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(af[PL]));
 #define X_MF(A, W, ACC) ACC = __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, W, ACC, 0, 0, 0);
                 // k16 step I: the six plane products for both column halves, small terms first.  ONE fragment set: a plane's
@@ -240,11 +194,7 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
 #undef X_MM2
 #undef X_WAIT1
 #undef X_RD1
-#undef X_STEP
-#undef X_MM
 #undef X_MF
-#undef X_WAIT
-#undef X_RD
 #undef X_ISSUE
 #undef X_REQ
             }
@@ -258,7 +208,7 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
                     rp[row * X_RLD + 32 + li] = acc1[r];
                 }
             }
-            X_BARRIER();
+            PF_BARRIER();
             XSTAMP(p.stamps, xrec, 5);
 
             f32x2 gate[4], cv, hv;
@@ -269,31 +219,31 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
                     f32x2 v = gxv[g];
 #pragma unroll
                     for (int w = 0; w < 4; ++w)
-                        v += *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(smem + w * X_RING) + erow * X_RLD + ecol + g * 8);
+                        v += *reinterpret_cast<const f32x2*>(reinterpret_cast<const float*>(smem + w * X_RING) + e.row * X_RLD + ecol + g * 8);
                     pre[g] = v;
                 }
-                f32x2* cp = reinterpret_cast<f32x2*>(cst + (s * X_SR + erow) * X_UN + eul);
+                f32x2* cp = reinterpret_cast<f32x2*>(cst + (s * PF_SR + e.row) * X_UN + e.ul);
                 const f32x2 cprev = *cp;
                 unsigned short pb[2][3];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    gate[0][j] = sigmoidf_(pre[0][j]);
-                    gate[1][j] = sigmoidf_(pre[1][j]);
-                    gate[2][j] = tanhf_(pre[2][j]);
-                    gate[3][j] = sigmoidf_(pre[3][j]);
-                    const bool ok = rok && (j ? e_ok1 : e_ok0);
-                    cv[j] = ok ? gate[1][j] * cprev[j] + gate[0][j] * gate[2][j] : 0.f;
-                    hv[j] = ok ? gate[3][j] * tanhf_(cv[j]) : 0.f;
+                    const bool ok = rok && e.ok(j);
+                    float gj[4], cj, hj;
+                    cell_forward<ActExact>(pre[0][j], pre[1][j], pre[2][j], pre[3][j], cprev[j], ok, gj, cj, hj);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) gate[g][j] = gj[g];
+                    cv[j] = cj;
+                    hv[j] = ok ? hj : 0.f;          // (pad lanes of the plane image and of h_all read as zeros)
                     split3_bits(hv[j], pb[j]);
                 }
                 *cp = cv;
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
-                    *reinterpret_cast<unsigned int*>(hsm + pl * (X_SR * X_UN) + erow * X_UN + eul) =
+                    *reinterpret_cast<unsigned int*>(hsm + pl * (PF_SR * X_UN) + e.row * X_UN + e.ul) =
                         (unsigned int)pb[0][pl] | ((unsigned int)pb[1][pl] << 16);
             }
             XSTAMP(p.stamps, xrec, 6);
-            X_BARRIER();
+            PF_BARRIER();
             if (kq == 0) {   // the h_t planes: three tiles of 32 rows x 32 B = three 16-byte write-through store instructions,
                              // issued first: they are what the other workgroups wait for
                 const int rl = lane >> 1, part = lane & 1;
@@ -301,7 +251,7 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
                 if (rbase + rl < B) {
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl) {
-                        const u32x4 v = *reinterpret_cast<const u32x4*>(hsm + pl * (X_SR * X_UN) + rl * X_UN + part * 8);
+                        const u32x4 v = *reinterpret_cast<const u32x4*>(hsm + pl * (PF_SR * X_UN) + rl * X_UN + part * 8);
                         asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(dst + pl * p.hplane), "v"(v) : "memory");
                     }
                     if (cs == nC - 1) {     // the last column slice keeps the pad columns [16 nC, Kp) of the image at zero
@@ -324,7 +274,7 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
                     unsigned short* dst = p.hblk + (r >> 6) * (64 * p.ldhblk) + (int64_t)(u0 >> 4) * 3072 + part * 512 + (r & 63) * 8;
 #pragma unroll
                     for (int pl = 0; pl < 3; ++pl)
-                        *reinterpret_cast<u32x4*>(dst + pl * 1024) = *reinterpret_cast<const u32x4*>(hsm + pl * (X_SR * X_UN) + rl * X_UN + part * 8);
+                        *reinterpret_cast<u32x4*>(dst + pl * 1024) = *reinterpret_cast<const u32x4*>(hsm + pl * (PF_SR * X_UN) + rl * X_UN + part * 8);
                 }
             }
             XSTAMP(p.stamps, xrec, 7);
@@ -337,90 +287,48 @@ __device__ __forceinline__ void seq_fwd_x3_body(const SeqFwdX3Args& p, const int
             XSTAMP(p.stamps, xrec, 9);
             if (rok) {
                 const int64_t rowi = (int64_t)t * B + eb;
-                float* cdst = p.c_all + rowi * H + eunit;
-                float* hdst = p.h_all + rowi * H + eunit;
-                float* st = p.gx_stash + rowi * H4 + eunit;
+                float* cdst = p.c_all + rowi * H + e.unit;
+                float* hdst = p.h_all + rowi * H + e.unit;
+                float* st = p.gx_stash + rowi * H4 + e.unit;
                 const bool stash = p.no_stash == 0;
-                if (e_vec) {
-                    *reinterpret_cast<f32x2*>(cdst) = cv;
-                    *reinterpret_cast<f32x2*>(hdst) = hv;
-                    if (stash) {
+                e.store(cdst, cv);
+                e.store(hdst, hv);
+                if (stash) {
 #pragma unroll
-                        for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x2*>(st + (int64_t)g * H) = gate[g];
-                    }
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        if (j ? e_ok1 : e_ok0) {
-                            cdst[j] = cv[j];
-                            hdst[j] = hv[j];
-                            if (stash) {
-#pragma unroll
-                                for (int g = 0; g < 4; ++g) st[(int64_t)g * H + j] = gate[g][j];
-                            }
-                        }
+                    for (int g = 0; g < 4; ++g) e.store(st + (int64_t)g * H, gate[g]);
                 }
             }
-            X_BARRIER();       // hsm / cst / partial sums are free again
+            PF_BARRIER();       // hsm / cst / partial sums are free again
         }
     }
 }
 
-// xg == 0: grid = [na workgroups of layer pa | workgroups of layer pb] (nb may be 0).
-// xg = G > 0 (XCD-aware; both layers of one shape): the hardware deals workgroup b to XCD b % 8 (speed only - nothing depends on
-// it for correctness); a GROUP is the nC column slices of one (layer, row group) - the workgroups that exchange one chain's h_t
-// tiles - and group g is dealt to the XCDs {g, g + G, ..}: a consumer's sc1 loads then find the tile in the L2 its producers
-// wrote through, and a row's lines enter 8 / G L2s instead of all eight.  The grid is 8 * ceil(nC / (8 / G)) blocks; the few
-// whose slice index falls past nC exit at once (nobody waits for them: the counters count the nC real slices).
+// grid = [na workgroups of layer pa | workgroups of layer pb] (nb may be 0), or dealt by persist_role (XCD-aware, padded grid)
 __global__ __launch_bounds__(X_NT, 1) void lstm_seq_fwd_x3_persist_kernel(SeqFwdX3Args pa, SeqFwdX3Args pb, int na, int xg) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[X_LDS];
     __shared__ int s_flag;
-    const int bid = (int)blockIdx.x;
     bool lb;
-    int vb;
-    if (xg > 0) {
-        const int nC = (pa.H + X_UN - 1) / X_UN;
-        const int x = bid & 7, q = bid >> 3, per = 8 / xg;
-        const int g = x % xg, cs = q * per + x / xg;
-        if (cs >= nC) return;
-        const int rgs = na / nC;                     // row groups of layer A
-        lb = g >= rgs;
-        vb = (lb ? g - rgs : g) * nC + cs;
-    } else {
-        lb = bid >= na;
-        vb = lb ? bid - na : bid;
-    }
+    const int vb = persist_role((int)blockIdx.x, na, (pa.H + X_UN - 1) / X_UN, xg, lb);
+    if (vb < 0) return;
     // ONE copy of the body: the layer's arguments are selected field by field (scalar selects on kernel arguments)
     seq_fwd_x3_body(lb ? pb : pa, vb, smem, s_flag);
 }
 
-size_t lstm_persist_sync_bytes();
-
-static int fwd_x3_capacity() {
-    const int cap = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_fwd_x3_persist_kernel), X_NT);
-    return cap < X_MAX_WG ? cap : X_MAX_WG;
-}
+static int fwd_x3_capacity() { return persist_capacity_of(&lstm_seq_fwd_x3_persist_kernel, X_NT, X_MAX_WG); }
 // number of 32-row chains per workgroup (0: unsupported, or two layers of the shape do not fit the device's resident capacity)
 int lstm_seq_fwd_x3_persist_supported(int B, int H) {
-    if (!(B > 0 && B % X_SR == 0 && H >= 8 && H <= 1024)) return 0;
-    const int cap = fwd_x3_capacity();
-    const int nC = cdiv(H, X_UN);
-    int R = B / X_SR, ns = 1;
-    while (R * nC > cap / 2 && ns < X_MAXNS && R % 2 == 0) { R /= 2; ns *= 2; }
-    return (R * nC <= cap / 2 && R <= 64) ? ns : 0;
+    if (!(B > 0 && B % PF_SR == 0 && H >= 8 && H <= 1024)) return 0;
+    return plan_chains(B, cdiv(H, X_UN), fwd_x3_capacity() / 2, true);
 }
 
 // chains per workgroup of a launch with ONE layer: it may use the whole device (a pair shares it half / half)
 static int fwd_x3_single_ns(int B, int H) {
     if (!lstm_seq_fwd_x3_persist_supported(B, H)) return 0;
-    const int cap = fwd_x3_capacity(), nC = cdiv(H, X_UN);
-    int R = B / X_SR, ns = 1;
-    while (R * nC > cap && ns < X_MAXNS && R % 2 == 0) { R /= 2; ns *= 2; }
-    return (R * nC <= cap) ? ns : 0;
+    return plan_chains(B, cdiv(H, X_UN), fwd_x3_capacity(), false);
 }
 int lstm_seq_fwd_x3_persist_single_workgroups(int B, int H) {
     const int ns = fwd_x3_single_ns(B, H);
-    return ns > 0 ? (B / (ns * X_SR)) * cdiv(H, X_UN) : 0;
+    return ns > 0 ? (B / (ns * PF_SR)) * cdiv(H, X_UN) : 0;
 }
 static int prep_x(SeqFwdX3Args& a, bool single = false) {
     const int ns = single ? fwd_x3_single_ns(a.B, a.H) : lstm_seq_fwd_x3_persist_supported(a.B, a.H);
@@ -434,35 +342,23 @@ static int prep_x(SeqFwdX3Args& a, bool single = false) {
                      (reinterpret_cast<uintptr_t>(a.hp) & 15) == 0,
                  "lstm_seq_fwd_x3_persist: plane images must be 16-byte aligned with rows of Kp = H rounded up to 64");
     a.NS = ns;
-    a.RB = ns * X_SR;
+    a.RB = ns * PF_SR;
     return 0;
 }
 
+// XCD-aware dealing (see persist_role) when the groups divide the 8 XCDs and the padded grid still fits the device
 int lstm_seq_fwd_x3_persist2(hipStream_t stream, SeqFwdX3Args a, const SeqFwdX3Args* b) {
-    int rc;
-    if ((rc = prep_x(a, b == nullptr))) return rc;
-    SeqFwdX3Args bb = b ? *b : a;
-    if (b) {
-        if ((rc = prep_x(bb))) return rc;
-        S2VT_REQUIRE(bb.sync != a.sync, "lstm_seq_fwd_x3_persist: paired layers need their own counters");
-    }
-    const int na = (a.B / a.RB) * cdiv(a.H, X_UN), nb = b ? (bb.B / bb.RB) * cdiv(bb.H, X_UN) : 0;
-    S2VT_REQUIRE(na + nb <= fwd_x3_capacity(), "lstm_seq_fwd_x3_persist: %d workgroups would not be co-resident (device capacity %d)",
-                 na + nb, fwd_x3_capacity());
-    // the hand-off counters count finished timesteps of the whole sequence: zeroed with its first block only
-    if (a.t0 == 0) S2VT_HIP(hipMemsetAsync(a.sync, 0, lstm_persist_sync_bytes(), stream));
-    if (b && bb.t0 == 0) S2VT_HIP(hipMemsetAsync(bb.sync, 0, lstm_persist_sync_bytes(), stream));
-    // XCD-aware dealing (see the kernel) when the groups divide the 8 XCDs and the padded grid still fits the device
-    const int nC = cdiv(a.H, X_UN);
-    const int G = (na + nb) / nC;
-    int xg = 0, grid = na + nb;
-    if ((!b || (bb.B == a.B && bb.H == a.H)) && G > 0 && G <= 8 && 8 % G == 0) {
-        const int padded = 8 * cdiv(nC, 8 / G);
-        if (padded <= fwd_x3_capacity()) { xg = G; grid = padded; }
-    }
-    hipLaunchKernelGGL(lstm_seq_fwd_x3_persist_kernel, dim3(grid), dim3(X_NT), 0, stream, a, bb, na, xg);
-    S2VT_LAUNCH_CHECK("lstm_seq_fwd_x3_persist_kernel");
-    return 0;
+    return launch_persistent_layers<false>(
+        stream, a, b, XCD_PADDED, "lstm_seq_fwd_x3_persist", "lstm_seq_fwd_x3_persist: paired layers need their own counters",
+        "lstm_seq_fwd_x3_persist_kernel",
+        [](SeqFwdX3Args& x, bool single, PersistLayer* l) {
+            *l = PersistLayer{X_UN, fwd_x3_capacity()};
+            return prep_x(x, single);
+        },
+        [](const SeqFwdX3Args&, const SeqFwdX3Args&, const PersistLayer&, const PersistLayer&) -> const char* { return nullptr; },
+        [&](dim3 grid, const SeqFwdX3Args& pa, const SeqFwdX3Args& pb, int na, int xg, const PersistLayer&) {
+            hipLaunchKernelGGL(lstm_seq_fwd_x3_persist_kernel, grid, dim3(X_NT), 0, stream, pa, pb, na, xg);
+        });
 }
 
 // fp32 [R][C] (row stride ld) -> three bf16 planes [3][R][Cp] (x = p0 + p1 + p2), columns [C, Cp) zero: W_hh for the kernel above
@@ -508,7 +404,7 @@ int split3_rows(hipStream_t stream, const float* src, int64_t ld, int R, int C, 
 constexpr int Y_GBUF = 64 * 2048;                 // gather buffer: up to 64 producer blocks of [32][16] fp32
 constexpr int Y_TILE = Y_GBUF;                    // own dG_t tile as planes [3][32 rows][64 k] bf16 (swizzled like a forward chunk)
 constexpr int Y_DCST = Y_TILE + 3 * X_PLANE;      // dL/dc carry of the workgroup's cells, per chain [32][16]
-constexpr int Y_CSUM = Y_DCST + X_MAXNS * X_SR * X_UN * 4;    // per-wave column sums of the dG tile [4 waves][64 gate columns]
+constexpr int Y_CSUM = Y_DCST + PF_MAXNS * PF_SR * X_UN * 4;    // per-wave column sums of the dG tile [4 waves][64 gate columns]
 constexpr int Y_LDS = Y_CSUM + 4 * 64 * 4;                    // 152576 B
 
 __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int bid, unsigned char* smem, int& s_flag) {
@@ -554,95 +450,71 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
         }
 
     // ---- cell role: 2 adjacent units of one row per thread
-    const int erow = tid >> 3, eul = (tid & 7) * 2;
-    const int eunit = u0 + eul;
-    const bool e_ok0 = eunit < H, e_ok1 = eunit + 1 < H;
-    const bool e_vec = e_ok1 && ((H & 1) == 0);
+    const CellLane<X_UN> e(tid, u0, H);
     float* dcst = reinterpret_cast<float*>(smem + Y_DCST);
     const bool last_block = (p.t1 == p.T);
     for (int s = 0; s < p.NS; ++s) {
-        const int b = row0 + s * X_SR + erow;
+        const int b = row0 + s * PF_SR + e.row;
         f32x2 d0 = {0.f, 0.f};
-        if (!last_block && b < B) {
-            const float* q = p.dc + (int64_t)b * H + eunit;
-            if (e_ok0) d0[0] = q[0];
-            if (e_ok1) d0[1] = q[1];
-        }
-        *reinterpret_cast<f32x2*>(dcst + (s * X_SR + erow) * X_UN + eul) = d0;
+        if (!last_block && b < B) d0 = e.carry(p.dc + (int64_t)b * H + e.unit);
+        *reinterpret_cast<f32x2*>(dcst + (s * PF_SR + e.row) * X_UN + e.ul) = d0;
     }
     const int64_t H4 = 4 * (int64_t)H;
     const float* gbuf = reinterpret_cast<const float*>(smem);
     unsigned char* tile = smem + Y_TILE;
-    // tile write position of this thread's two cells for gate g: row erow, piece 2g + (eul >> 3), element eul & 7
+    // tile write position of this thread's two cells for gate g: row e.row, piece 2g + (e.ul >> 3), element e.ul & 7
     unsigned tw[4];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) tw[g] = (unsigned)(erow * 128 + (((2 * g + (eul >> 3)) ^ ((erow >> 1) & 7)) * 16) + (eul & 7) * 2);
+    for (int g = 0; g < 4; ++g) tw[g] = (unsigned)(e.row * 128 + (((2 * g + (e.ul >> 3)) ^ ((e.row >> 1) & 7)) * 16) + (e.ul & 7) * 2);
 
     for (int t = p.t1 - 1; t >= p.t0; --t) {
 #pragma unroll 1
         for (int s = 0; s < p.NS; ++s) {
-            const int rbase = row0 + s * X_SR;
-            const int chain = rbase / X_SR;
-            unsigned int* cnt = p.sync + (rg * X_MAXNS + s) * 32;
+            const int rbase = row0 + s * PF_SR;
+            const int chain = rbase / PF_SR;
+            unsigned int* cnt = chain_counter(p.sync, rbase);
             const int xrec = (bid == p.stamp_block) ? (p.t1 - 1 - t) * p.NS + s : -1;
             XSTAMP(p.stamps, xrec, 0);
 
             // cell operands requested first, consumed after the gather
-            const int eb = rbase + erow;
+            const int eb = rbase + e.row;
             const bool rok = eb < B;
             const int64_t rowi = (int64_t)t * B + eb;
             f32x2 stv[4], cv, cpv, dhov;
             {
-                const float* st = p.stash_dg + rowi * H4 + eunit;
-                const float* cq = p.c_all + rowi * H + eunit;
+                const float* st = p.stash_dg + rowi * H4 + e.unit;
+                const float* cq = p.c_all + rowi * H + e.unit;
                 const bool hasdh = p.dh_out && t >= p.dh_first;
-                const float* dq = hasdh ? p.dh_out + ((int64_t)(t - p.dh_first) * B + eb) * H + eunit : g_zero4;
+                const float* dq = hasdh ? p.dh_out + ((int64_t)(t - p.dh_first) * B + eb) * H + e.unit : g_zero4;
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float* q = st + (int64_t)g * H;
-                    if (e_vec) stv[g] = *reinterpret_cast<const f32x2*>(rok ? q : g_zero4);
-                    else { stv[g][0] = *((rok && e_ok0) ? q : g_zero4); stv[g][1] = *((rok && e_ok1) ? q + 1 : g_zero4); }
-                }
-                if (e_vec) {
-                    cv = *reinterpret_cast<const f32x2*>(rok ? cq : g_zero4);
-                    cpv = *reinterpret_cast<const f32x2*>((rok && t > 0) ? cq - (int64_t)B * H : g_zero4);
-                    dhov = *reinterpret_cast<const f32x2*>((rok && hasdh) ? dq : g_zero4);
-                } else {
-                    cv[0] = *((rok && e_ok0) ? cq : g_zero4); cv[1] = *((rok && e_ok1) ? cq + 1 : g_zero4);
-                    cpv[0] = *((rok && e_ok0 && t > 0) ? cq - (int64_t)B * H : g_zero4);
-                    cpv[1] = *((rok && e_ok1 && t > 0) ? cq - (int64_t)B * H + 1 : g_zero4);
-                    dhov[0] = *((rok && e_ok0 && hasdh) ? dq : g_zero4); dhov[1] = *((rok && e_ok1 && hasdh) ? dq + 1 : g_zero4);
-                }
+                for (int g = 0; g < 4; ++g) stv[g] = e.load(st + (int64_t)g * H, rok);
+                cv = e.load(cq, rok);
+                cpv = e.load(cq - (int64_t)B * H, rok && t > 0);
+                dhov = e.load(dq, rok && hasdh);
             }
 
             f32x2 dh = {0.f, 0.f};
             if (t < p.T - 1) {
                 // the nC partial blocks of dG_{t+1} . W_hh addressed to this column slice: published by every slice of the chain?
-                if (tid == 0) {
-                    const bool ok = spin_until_x(cnt, (unsigned int)(nC * (p.T - 1 - t)));
-                    s_flag = ok ? 1 : 0;
-                    if (!ok) atomicExch(p.err, 1);
-                }
-                X_BARRIER();
-                if (s_flag == 0) return;
+                if (!chain_arrived(cnt, (unsigned int)(nC * (p.T - 1 - t)), p.err, s_flag)) return;
                 XSTAMP(p.stamps, xrec, 1);
                 const unsigned char* src = reinterpret_cast<const unsigned char*>(
-                    p.part + (int64_t)(t % p.nslots) * p.part_slot + ((int64_t)(chain * nC + cs) * nC) * (X_SR * X_UN)) + lane * 16;
-                for (int r = kw; r < 2 * nC; r += 4) glds16x_sc1(src + r * 1024, smem + r * 1024);
+                    p.part + (int64_t)(t % p.nslots) * p.part_slot + ((int64_t)(chain * nC + cs) * nC) * (PF_SR * X_UN)) + lane * 16;
+                for (int r = kw; r < 2 * nC; r += 4) glds16_sc1(src + r * 1024, smem + r * 1024);
                 XSTAMP(p.stamps, xrec, 2);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                X_BARRIER();
+                PF_BARRIER();
                 XSTAMP(p.stamps, xrec, 3);
-                const float* gp = gbuf + erow * X_UN + eul;
+                const float* gp = gbuf + e.row * X_UN + e.ul;
                 int c = 0;                  // summed in producer order; eight LDS reads in flight at a time
                 for (; c + 8 <= nC; c += 8) {
                     f32x2 v[8];
 #pragma unroll
-                    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const f32x2*>(gp + (c + i) * (X_SR * X_UN));
+                    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const f32x2*>(gp + (c + i) * (PF_SR * X_UN));
 #pragma unroll
                     for (int i = 0; i < 8; ++i) dh += v[i];
                 }
-                for (; c < nC; ++c) dh += *reinterpret_cast<const f32x2*>(gp + c * (X_SR * X_UN));
+                for (; c < nC; ++c) dh += *reinterpret_cast<const f32x2*>(gp + c * (PF_SR * X_UN));
             } else {
                 XSTAMP(p.stamps, xrec, 1);
                 XSTAMP(p.stamps, xrec, 2);
@@ -652,23 +524,18 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
 
             f32x2 dg[4];
             {
-                f32x2* dp = reinterpret_cast<f32x2*>(dcst + (s * X_SR + erow) * X_UN + eul);
+                f32x2* dp = reinterpret_cast<f32x2*>(dcst + (s * PF_SR + e.row) * X_UN + e.ul);
                 const f32x2 dcin = *dp;
                 f32x2 dcn;
                 unsigned short pb[4][2][3];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const bool ok = rok && (j ? e_ok1 : e_ok0);
-                    const float d = dh[j] + dhov[j];
-                    const float ig = stv[0][j], fg = stv[1][j], gg = stv[2][j], og = stv[3][j];
-                    const float tc = tanhf_(cv[j]);
-                    const float dc = d * og * (1.0f - tc * tc) + dcin[j];
-                    const float d_o = d * tc;
-                    dg[0][j] = ok ? dc * gg * ig * (1.0f - ig) : 0.f;
-                    dg[1][j] = ok ? dc * cpv[j] * fg * (1.0f - fg) : 0.f;
-                    dg[2][j] = ok ? dc * ig * (1.0f - gg * gg) : 0.f;
-                    dg[3][j] = ok ? d_o * og * (1.0f - og) : 0.f;
-                    dcn[j] = ok ? dc * fg : 0.f;
+                    const bool ok = rok && e.ok(j);
+                    float dj[4], dcj;
+                    cell_backward<ActExact>(dh[j] + dhov[j], stv[0][j], stv[1][j], stv[2][j], stv[3][j], cv[j], cpv[j], dcin[j], dj, dcj);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) dg[g][j] = ok ? dj[g] : 0.f;
+                    dcn[j] = ok ? dcj : 0.f;
 #pragma unroll
                     for (int g = 0; g < 4; ++g) split3_bits(dg[g][j], pb[g][j]);
                 }
@@ -679,25 +546,13 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
                     for (int pl = 0; pl < 3; ++pl)
                         *reinterpret_cast<unsigned int*>(tile + pl * X_PLANE + tw[g]) = (unsigned int)pb[g][0][pl] | ((unsigned int)pb[g][1][pl] << 16);
                 if (rok) {
-                    float* st = p.stash_dg + rowi * H4 + eunit;
+                    float* st = p.stash_dg + rowi * H4 + e.unit;
                     const bool keep = p.skip_dg == 0;
-                    if (e_vec) {
-                        if (keep) {
+                    if (keep) {
 #pragma unroll
-                            for (int g = 0; g < 4; ++g) *reinterpret_cast<f32x2*>(st + (int64_t)g * H) = dg[g];
-                        }
-                        if (t == p.t0) *reinterpret_cast<f32x2*>(p.dc + (int64_t)eb * H + eunit) = dcn;
-                    } else {
-#pragma unroll
-                        for (int j = 0; j < 2; ++j)
-                            if (j ? e_ok1 : e_ok0) {
-                                if (keep) {
-#pragma unroll
-                                    for (int g = 0; g < 4; ++g) st[(int64_t)g * H + j] = dg[g][j];
-                                }
-                                if (t == p.t0) p.dc[(int64_t)eb * H + eunit + j] = dcn[j];
-                            }
+                        for (int g = 0; g < 4; ++g) e.store(st + (int64_t)g * H, dg[g]);
                     }
+                    if (t == p.t0) e.store(p.dc + (int64_t)eb * H + e.unit, dcn);       // carried to the next launch
                 }
                 if (p.colpart) {    // column sums of the tile over its 32 rows: 8 rows per wave by shuffles, the 4 waves through LDS
                     float* cs_w = reinterpret_cast<float*>(smem + Y_CSUM) + kw * 64;
@@ -706,19 +561,19 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
                         f32x2 v = dg[g];
 #pragma unroll
                         for (int off = 8; off < 64; off <<= 1) { v[0] += __shfl_xor(v[0], off); v[1] += __shfl_xor(v[1], off); }
-                        if (lane < 8) *reinterpret_cast<f32x2*>(cs_w + g * 16 + eul) = v;
+                        if (lane < 8) *reinterpret_cast<f32x2*>(cs_w + g * 16 + e.ul) = v;
                     }
                 }
             }
             XSTAMP(p.stamps, xrec, 5);
-            X_BARRIER();           // the dG_t tile is complete (and everyone is done with the gather buffer)
+            PF_BARRIER();           // the dG_t tile is complete (and everyone is done with the gather buffer)
             // dG_t as the batched GEMMs' row image + its 32-row column sums: issued BEHIND the hand-off (t > 0: after the signal)
             auto emit_planes = [&]() {
                 if (p.colpart && kw == 0) {
                     const int g = lane >> 4, u = lane & 15;
                     const float* cs0 = reinterpret_cast<const float*>(smem + Y_CSUM) + lane;
                     const float sum = ((cs0[0] + cs0[64]) + cs0[128]) + cs0[192];
-                    if (u0 + u < H) p.colpart[((int64_t)t * (B / X_SR) + chain) * H4 + (int64_t)g * H + u0 + u] = sum;
+                    if (u0 + u < H) p.colpart[((int64_t)t * (B / PF_SR) + chain) * H4 + (int64_t)g * H + u0 + u] = sum;
                 }
                 if (p.dgp) {
                     const int row = tid >> 3, p8 = tid & 7;                 // piece p8 = gate 2 bits, unit octet 1 bit
@@ -735,9 +590,9 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
             };
 
             if (t > 0) {           // partial products of dG_t for step t - 1 (nobody consumes those of step 0)
-                float* pslot = p.part + (int64_t)((t - 1) % p.nslots) * p.part_slot + ((int64_t)chain * nC * nC + cs) * (X_SR * X_UN)
+                float* pslot = p.part + (int64_t)((t - 1) % p.nslots) * p.part_slot + ((int64_t)chain * nC * nC + cs) * (PF_SR * X_UN)
                                + l16 * X_UN + 4 * kg;
-                const int64_t cstride = (int64_t)nC * (X_SR * X_UN);           // floats between the blocks of two consumers
+                const int64_t cstride = (int64_t)nC * (PF_SR * X_UN);           // floats between the blocks of two consumers
                 // the whole dG_t tile as B operands, once: gfr[plane][bt][ks] (12 fragments; every output column tile uses all)
                 bf16x8 gfr[3][2][2];
 #pragma unroll
@@ -745,7 +600,7 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
 #pragma unroll
                     for (int bt = 0; bt < 2; ++bt)
 #pragma unroll
-                        for (int ks = 0; ks < 2; ++ks) X_DSR(gfr[pl][bt][ks], fa[bt][ks], pl * X_PLANE);
+                        for (int ks = 0; ks < 2; ++ks) PF_DSR(gfr[pl][bt][ks], fa[bt][ks], pl * X_PLANE);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
                 for (int pl = 0; pl < 3; ++pl)
@@ -789,57 +644,38 @@ __device__ __forceinline__ void seq_bwd_x3_body(const SeqBwdX3Args& p, const int
                 // hand-off: EVERY wave stored a part of the payload: each drains its own stores, then the barrier, then one add
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 XSTAMP(p.stamps, xrec, 7);
-                X_BARRIER();
+                PF_BARRIER();
                 if (tid == 0) __hip_atomic_fetch_add((gu32*)cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 XSTAMP(p.stamps, xrec, 8);
                 emit_planes();
-                if (p.dgp || p.colpart) X_BARRIER();       // (the tile and the column sums are rewritten by the next sub-step's cells)
+                if (p.dgp || p.colpart) PF_BARRIER();       // (the tile and the column sums are rewritten by the next sub-step's cells)
             } else {
                 emit_planes();
-                X_BARRIER();
+                PF_BARRIER();
             }
         }
     }
 }
 
-// block roles as in the forward kernel (xg: XCD-aware dealing)
+// block roles as in the forward kernel
 __global__ __launch_bounds__(X_NT, 1) void lstm_seq_bwd_x3_persist_kernel(SeqBwdX3Args pa, SeqBwdX3Args pb, int na, int xg) {
     __shared__ __attribute__((aligned(1024))) unsigned char smem[Y_LDS];
     __shared__ int s_flag;
-    const int bid = (int)blockIdx.x;
     bool lb;
-    int vb;
-    if (xg > 0) {
-        const int nC = (pa.H + X_UN - 1) / X_UN;
-        const int x = bid & 7, q = bid >> 3, per = 8 / xg;
-        const int g = x % xg, cs = q * per + x / xg;
-        if (cs >= nC) return;
-        const int rgs = na / nC;
-        lb = g >= rgs;
-        vb = (lb ? g - rgs : g) * nC + cs;
-    } else {
-        lb = bid >= na;
-        vb = lb ? bid - na : bid;
-    }
+    const int vb = persist_role((int)blockIdx.x, na, (pa.H + X_UN - 1) / X_UN, xg, lb);
+    if (vb < 0) return;
     seq_bwd_x3_body(lb ? pb : pa, vb, smem, s_flag);
 }
 
-static int bwd_x3_capacity() {
-    const int cap = coresident_capacity(reinterpret_cast<const void*>(&lstm_seq_bwd_x3_persist_kernel), X_NT);
-    return cap < X_MAX_WG ? cap : X_MAX_WG;
-}
+static int bwd_x3_capacity() { return persist_capacity_of(&lstm_seq_bwd_x3_persist_kernel, X_NT, X_MAX_WG); }
 int lstm_seq_bwd_x3_persist_supported(int B, int H) {
-    if (!(B > 0 && B % X_SR == 0 && H >= 8 && H <= 1024)) return 0;
-    const int cap = bwd_x3_capacity();
-    const int nC = cdiv(H, X_UN);
-    int R = B / X_SR, ns = 1;
-    while (R * nC > cap / 2 && ns < X_MAXNS && R % 2 == 0) { R /= 2; ns *= 2; }
-    return (R * nC <= cap / 2 && R <= 64) ? ns : 0;
+    if (!(B > 0 && B % PF_SR == 0 && H >= 8 && H <= 1024)) return 0;
+    return plan_chains(B, cdiv(H, X_UN), bwd_x3_capacity() / 2, true);
 }
 // floats of one ring slot of the partial-sum buffer: [chains][nC consumers][nC producers][32][16]
 size_t lstm_seq_bwd_x3_part_slot_floats(int B, int H) {
     const size_t nC = (size_t)cdiv(H, X_UN);
-    return (size_t)(B / X_SR) * nC * nC * X_SR * X_UN;
+    return (size_t)(B / PF_SR) * nC * nC * PF_SR * X_UN;
 }
 
 static int prep_y(SeqBwdX3Args& a) {
@@ -857,34 +693,24 @@ static int prep_y(SeqBwdX3Args& a) {
                  "lstm_seq_bwd_x3_persist: the dG row image needs H %% 8 == 0, B %% 64 == 0 and rows of 3 * pad64(4H) elements");
     S2VT_REQUIRE(!a.skip_dg || a.dgp, "lstm_seq_bwd_x3_persist: skip_dg without a plane image");
     a.NS = ns;
-    a.RB = ns * X_SR;
+    a.RB = ns * PF_SR;
     return 0;
 }
 
 int lstm_seq_bwd_x3_persist2(hipStream_t stream, SeqBwdX3Args a, const SeqBwdX3Args* b) {
-    int rc;
-    if ((rc = prep_y(a))) return rc;
-    SeqBwdX3Args bb = b ? *b : a;
-    if (b) {
-        if ((rc = prep_y(bb))) return rc;
-        S2VT_REQUIRE(bb.sync != a.sync && bb.part != a.part, "lstm_seq_bwd_x3_persist: paired layers need their own counters and partial sums");
-    }
-    const int nC = cdiv(a.H, X_UN);
-    const int na = (a.B / a.RB) * nC, nb = b ? (bb.B / bb.RB) * cdiv(bb.H, X_UN) : 0;
-    S2VT_REQUIRE(na + nb <= bwd_x3_capacity(), "lstm_seq_bwd_x3_persist: %d workgroups would not be co-resident (device capacity %d)",
-                 na + nb, bwd_x3_capacity());
-    // the hand-off counters count finished timesteps of the whole sequence: zeroed with its first block (t1 == T) only
-    if (a.t1 == a.T) S2VT_HIP(hipMemsetAsync(a.sync, 0, lstm_persist_sync_bytes(), stream));
-    if (b && bb.t1 == bb.T) S2VT_HIP(hipMemsetAsync(bb.sync, 0, lstm_persist_sync_bytes(), stream));
-    const int G = (na + nb) / nC;
-    int xg = 0, grid = na + nb;
-    if ((!b || (bb.B == a.B && bb.H == a.H)) && G > 0 && G <= 8 && 8 % G == 0) {
-        const int padded = 8 * cdiv(nC, 8 / G);
-        if (padded <= bwd_x3_capacity()) { xg = G; grid = padded; }
-    }
-    hipLaunchKernelGGL(lstm_seq_bwd_x3_persist_kernel, dim3(grid), dim3(X_NT), 0, stream, a, bb, na, xg);
-    S2VT_LAUNCH_CHECK("lstm_seq_bwd_x3_persist_kernel");
-    return 0;
+    static const char pair_msg[] = "lstm_seq_bwd_x3_persist: paired layers need their own counters and partial sums";
+    return launch_persistent_layers<true>(
+        stream, a, b, XCD_PADDED, "lstm_seq_bwd_x3_persist", pair_msg, "lstm_seq_bwd_x3_persist_kernel",
+        [](SeqBwdX3Args& x, bool, PersistLayer* l) {
+            *l = PersistLayer{X_UN, bwd_x3_capacity()};
+            return prep_y(x);
+        },
+        [](const SeqBwdX3Args& pa, const SeqBwdX3Args& pb, const PersistLayer&, const PersistLayer&) -> const char* {
+            return pb.part != pa.part ? nullptr : pair_msg;
+        },
+        [&](dim3 grid, const SeqBwdX3Args& pa, const SeqBwdX3Args& pb, int na, int xg, const PersistLayer&) {
+            hipLaunchKernelGGL(lstm_seq_bwd_x3_persist_kernel, grid, dim3(X_NT), 0, stream, pa, pb, na, xg);
+        });
 }
 
 // W_hh^T fp32 [H][4H] (row j: the 4H gate columns k = g H + u) -> three bf16 planes [3][Kp][4 Hp] with the gate blocks re-based

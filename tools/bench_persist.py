@@ -1,4 +1,9 @@
-"""Time the bf16 layer forward: one launch per timestep vs the persistent kernel (tools, GPU box)."""
+"""Time the layer recurrences: one launch per timestep vs the persistent kernels (tools, GPU box).  Every line carries the first
+argument as a tag and the sha1 of every output tensor of every timed run; the inputs are seeded, so two library builds on one box
+(S2VT_LIB, interleaved processes) can be compared for speed AND for bit-equal results.
+usage: [S2VT_LIB=<library>] python tools/bench_persist.py [TAG]"""
+import hashlib
+import os
 import sys
 import time
 
@@ -8,9 +13,26 @@ sys.path.insert(0, ".")
 import s2vt_video_caption_amd  # noqa
 from s2vt_video_caption_amd import build, capi, ops
 
-build.build()
+TAG = sys.argv[1] if len(sys.argv) > 1 else "-"
+if not os.environ.get("S2VT_LIB"):
+    build.build()
 capi.load()
 DEV = "cuda:0"
+
+
+def sha(out):
+    """sha1 (16 hex digits) of every tensor of a run's result, in order"""
+    if torch.is_tensor(out):
+        return [hashlib.sha1(out.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()[:16]]
+    if isinstance(out, (tuple, list)):
+        return [h for o in out for h in sha(o)]
+    return []
+
+
+def show(line, shas):
+    print("%s %s | sha1 %s" % (TAG, line, " ".join("/".join(r) for r in shas)), flush=True)
+
+
 T, H = 159, 1000
 for B in (256, 128, 64):
     g = torch.Generator().manual_seed(1)
@@ -19,29 +41,33 @@ for B in (256, 128, 64):
     w = (torch.randn(4 * H, H, generator=g) * H ** -0.5).to(DEV)
     for persistent, block in ((False, 0), (True, 0), (True, 32)):
         lib = capi.load()
+        shas = []
         for rep in range(3):
             lib.s2vt_prof_reset()
             lib.s2vt_prof_enable(1)
-            ops.lstm_seq_fwd_bf16(gx, 80, bias, w, T, B, H, persistent=persistent, block=block)
+            out = ops.lstm_seq_fwd_bf16(gx, 80, bias, w, T, B, H, persistent=persistent, block=block)
             torch.cuda.synchronize()
             lib.s2vt_prof_enable(0)
             ms, n = capi.prof_read(1)
             dt = ms * 1e-3
+            shas.append(sha(out))
         # bytes of the SURVEY 8(d) accounting for a vid-shaped layer (I = H, bf16 operands, train)
         s = 2
         by = s * 4 * H * 2 * H + 4 * 8 * H + s * B * 2 * H + 4 * B * H + s * B * H + 4 * B * H + s * B * 4 * H
         if persistent and block == 32:      # both layers in one launch: time per PAIR of layer steps
+            shas2 = []
             for rep in range(3):
                 lib.s2vt_prof_reset()
                 lib.s2vt_prof_enable(1)
-                ops.lstm_seq_fwd_bf16_pair(gx, gx, 80, bias, bias, w, w, T, B, H, block=block)
+                out = ops.lstm_seq_fwd_bf16_pair(gx, gx, 80, bias, bias, w, w, T, B, H, block=block)
                 torch.cuda.synchronize()
                 lib.s2vt_prof_enable(0)
                 ms2, n2 = capi.prof_read(1)
-            print("B=%d two layers in one launch, block=%d: %.3f ms, %.2f us per step PAIR, %.2f TB/s (8d bytes of a vid+word pair)" %
-                  (B, block, ms2, ms2 / T * 1e3, (by + s * 4 * H * H + s * B * H) / (ms2 * 1e-3 / T) / 1e12), flush=True)
-        print("B=%d persistent=%s block=%d: %.3f ms per layer pass (HIP events), %.2f us/step, %.2f TB/s (8d bytes)" %
-              (B, persistent, block, dt * 1e3, dt / T * 1e6, by / (dt / T) / 1e12), flush=True)
+                shas2.append(sha(out))
+            show("B=%d two layers in one launch, block=%d: %.3f ms, %.2f us per step PAIR, %.2f TB/s (8d bytes of a vid+word pair)" %
+                 (B, block, ms2, ms2 / T * 1e3, (by + s * 4 * H * H + s * B * H) / (ms2 * 1e-3 / T) / 1e12), shas2)
+        show("B=%d persistent=%s block=%d: %.3f ms per layer pass (HIP events), %.2f us/step, %.2f TB/s (8d bytes)" %
+             (B, persistent, block, dt * 1e3, dt / T * 1e6, by / (dt / T) / 1e12), shas)
 
 # ---- BPTT: one launch per timestep vs persistent (single layer, and two layers in one launch)
 print("---- BPTT", flush=True)
@@ -56,14 +82,16 @@ for B in (256, 64):
                      ("persistent block=32", lambda: ops.lstm_seq_bwd_bf16(w, dh, 0, c_all, gates, T, B, H, persistent=True, block=32)),
                      ("persistent two layers one launch block=32",
                       lambda: ops.lstm_seq_bwd_bf16_pair(w, w, dh, dh, 0, c_all, c_all, gates, gates, T, B, H, block=32))):
+        shas = []
         for rep in range(3):
             lib.s2vt_prof_reset()
             lib.s2vt_prof_enable(1)
-            fn()
+            out = fn()
             torch.cuda.synchronize()
             lib.s2vt_prof_enable(0)
             ms, n = capi.prof_read(2)
-        print("B=%d BPTT %s: %.3f ms, %.2f us per layer step (%d layer steps)" % (B, name, ms, ms * 1e3 / max(n, 1), n), flush=True)
+            shas.append(sha(out))
+        show("B=%d BPTT %s: %.3f ms, %.2f us per layer step (%d layer steps)" % (B, name, ms, ms * 1e3 / max(n, 1), n), shas)
 
 # ---- fp32 (config 2 arithmetic): launch per timestep vs persistent
 print("---- fp32", flush=True)
@@ -84,11 +112,13 @@ for B in (64, 128):
             ("bwd persistent two layers one launch", 2, lambda: ops.lstm_seq_bwd_persist(T, B, w, dh, 0, c_all, gates, block=32,
                                                                                        second=(w, dh, c_all, gates))))
     for name, kind, fn in runs:
+        shas = []
         for rep in range(3):
             lib.s2vt_prof_reset()
             lib.s2vt_prof_enable(1)
-            fn()
+            out = fn()
             torch.cuda.synchronize()
             lib.s2vt_prof_enable(0)
             ms, n = capi.prof_read(kind)
-        print("B=%d fp32 %s: %.3f ms, %.2f us per layer step (%d layer steps)" % (B, name, ms, ms * 1e3 / max(n, 1), n), flush=True)
+            shas.append(sha(out))
+        show("B=%d fp32 %s: %.3f ms, %.2f us per layer step (%d layer steps)" % (B, name, ms, ms * 1e3 / max(n, 1), n), shas)
