@@ -61,7 +61,8 @@ class S2VT(nn.Module):
                     "models are not implemented (the reference's forward fails on a bidirectional model: word_rnn expects "
                     "dim_embed + dim_hid inputs and gets dim_embed + 2*dim_hid)")
 
-    def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30, temperature=1.0, seed=None):
+    def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30, ss_prob=0.0, ss_temperature=None,
+                temperature=1.0, seed=None):
         """
         :param feats: [B, L, feat_dim]
         :param targets: [B, L-1] word ids (train mode)
@@ -70,24 +71,36 @@ class S2VT(nn.Module):
                      'sample' -> ids [B, L-1] (int64) drawn step by step from softmax(logit / temperature), never stopping at
                      <eos> (not in the reference; for sequence-level training, utils.RewardCriterion)
         :param temperature: mode='sample' only: finite and > 0
-        :param seed: mode='sample' only: None draws a 63-bit seed from torch's default generator (torch.manual_seed makes the
-                     run reproducible); an int is used as is.  Same seed, same weights, same clips -> same ids.
+        :param seed: mode='sample' and scheduled sampling: None draws a 63-bit seed from torch's default generator
+                     (torch.manual_seed makes the run reproducible); an int is used as is.  Same seed, same weights, same clips ->
+                     same ids.
+        :param ss_prob: mode='train' only - scheduled sampling (Bengio et al., 2015; not in the reference): each decode-step input
+                     is, with this probability, the word the model itself chose at the previous step instead of targets' (the
+                     first, <sos>, is always targets').  The words are fixed by one decode pass without gradient, dropout or host
+                     round trip (functional.scheduled_inputs), then the usual train forward runs on them.  0 (default): plain
+                     teacher forcing, nothing else is run.  Must be in [0, 1].
+        :param ss_temperature: the model's choice in that pass: None = the arg-max, a number = a draw from
+                     softmax(logit / ss_temperature)
         """
+        ss_prob = _F.check_ss_prob(ss_prob) if mode == 'train' else 0.0      # (ignored elsewhere, as temperature is outside 'sample')
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
         sample = _sampling.check_sample_args(temperature, seed) if mode == 'sample' else None
         if _G.is_gru_model(self):
-            return self._forward_gru(feats, targets, mode, sample)
+            return self._forward_gru(feats, targets, mode, sample, (ss_prob, ss_temperature, seed))
         if _S.is_stacked_lstm_model(self):
-            return self._forward_stacked(feats, targets, mode, sample)
+            return self._forward_stacked(feats, targets, mode, sample, (ss_prob, ss_temperature, seed))
         params = self._hip_params()
+        clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # identity at the reference's p=0 (S2VTModel.py:52)
         if mode == 'beam_search':
             return _beam.beam_search(self, feats, params, beam_width=beam_width, max_depth=max_beam_depth)
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")
+            if ss_prob > 0:
+                targets = _F.scheduled_inputs(clean, targets, params, ss_prob, temperature=ss_temperature, seed=seed, owner=self)
             out_mask = None
             if self.training and self.out_drop.p > 0:
                 # S2VTModel.py:79 applies nn.Dropout to the [B, L-1, H] decode-step hidden states: the same call on a ones
@@ -102,16 +115,19 @@ class S2VT(nn.Module):
             return _F.greedy_decode(feats, params, self.sos_ix, owner=self, sample=sample)
         return None                                        # the reference falls through for unknown modes
 
-    def _forward_gru(self, feats, targets, mode, sample=None):
+    def _forward_gru(self, feats, targets, mode, sample=None, ss=(0.0, None, None)):
         """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
                                       "(S2VTModel.py:153, 'DO NOT SUPPORT GRU'); use mode='test'")
+        clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")
             _F.require_hip(targets, "targets")
+            if ss[0] > 0:
+                targets = _G.scheduled_inputs(self, clean, targets.reshape(targets.shape[0], -1), ss[0], temperature=ss[1], seed=ss[2])
             out_mask = None
             if self.training and self.out_drop.p > 0:
                 # the LSTM path's draw (S2VTModel.py:79): nn.Dropout on a [B, L-1, H] ones tensor, batch-major as the GRU path uses it
@@ -124,17 +140,20 @@ class S2VT(nn.Module):
             return _G.greedy_decode(self, feats, self.sos_ix, sample=sample)
         return None
 
-    def _forward_stacked(self, feats, targets, mode, sample=None):
+    def _forward_stacked(self, feats, targets, mode, sample=None, ss=(0.0, None, None)):
         """nn.LSTM with num_layers > 1: the layer-wavefront chain kernels under autograd glue (stack_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a stacked model (num_layers > 1): the reference's BeamSearchNode views the "
                                       "per-sample [num_layers, H] state as [1, 1, -1] (S2VTModel.py:253-254) and raises for "
                                       "num_layers > 1; use mode='test'")
+        clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")
             _F.require_hip(targets, "targets")
+            if ss[0] > 0:
+                targets = _S.scheduled_inputs(self, clean, targets.reshape(targets.shape[0], -1), ss[0], temperature=ss[1], seed=ss[2])
             B, T = feats.shape[0], 2 * self.length - 1
             # draw order: the inter-layer masks of vid_rnn, then of word_rnn (nn.LSTM's dropout, S2VTModel.py:17-20), then out_drop
             rnn_masks = _S.draw_rnn_masks(self, T, B, feats.device)

@@ -394,6 +394,13 @@ int s2vt_gru_step_fwd(int32_t B, int32_t H, const float* gx, const float* b_ih, 
 int s2vt_gru_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
                             const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
                             const unsigned long long* tok_packed, int32_t tok_const, float* h_out, void* stream);
+/* The same step inside a scheduled-sampling pass (s2vt_scheduled_decode below states the rule): token(b) = the packed word of
+ * tok_packed where coin(row0 + b, step) < ss_prob, targets[b * targets_ld + step] otherwise (always at step 0, where tok_packed
+ * may be NULL).  A ground-truth id outside [0, V) is read as token 0 and reported like a bad id of `tok`. */
+int s2vt_gru_step_fwd_token_ss(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
+                               const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e,
+                               const unsigned long long* tok_packed, const int64_t* targets, int64_t targets_ld, float ss_prob,
+                               uint64_t seed, int32_t step, int32_t row0, float* h_out, void* stream);
 /* BPTT of one step (autograd of the same, train.py:124): dh_t = dh_out + dh_{t+1} * z_{t+1} + dgh_next·W_hh (w_hh_t = W_hh^T
  * [H,3H], stash_next = the stash of step t+1); dh [B,H] in: dh_{t+1}, out: dh_t.  dgh_next, stash_next and w_hh_t are all
  * NULL at the last step (dh is then not read).  Writes dgx [B,3H] = d(gate input) and dgh [B,3H] = d(h W_hh^T + b_hh). */
@@ -441,6 +448,10 @@ typedef struct s2vt_lstm_layer {
     /* backward only */
     const float* dh_ext; int32_t dh_t0;  /* gradient from outside for steps >= dh_t0: [(T-dh_t0)*B, H]; NULL: none */
     float* dg;                       /* [T*B,4H] out: gradient of the gate pre-activations (may alias stash) */
+    /* scheduled sampling of the token segment (forward only; NULL: none): the coin of (ss_row0 + b, ss_step) picks tok_packed's
+     * word or ss_targets[b * ss_ld + ss_step], as s2vt_scheduled_decode defines it; a ground-truth id outside [0, V) is read as
+     * token 0 and reported as S2VT_ERR_INDEX by s2vt_check_async_error / a later call */
+    const int64_t* ss_targets; int64_t ss_ld; uint64_t ss_seed; float ss_prob; int32_t ss_step, ss_row0;
 } s2vt_lstm_layer;
 /* Forward of the chain (S2VTModel.py:67 and :77 for N layers each; greedy decode :86-:106 with T = 1, h0/c0 and the token
  * segment on word_l0).  Arguments are checked before any launch. */
@@ -552,6 +563,43 @@ int s2vt_sample_decode(const s2vt_dims* d, const s2vt_params* p, const float* fe
 int s2vt_sample_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature,
                               uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                               int32_t cache_valid, void* stream);
+
+/* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
+ * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
+ * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with
+ * a coin per (batch row, step) in front of every token step and hand out the words that were fed; the unchanged teacher-forced
+ * train step then runs on those words.  Nothing differentiates through the choice or the coin.
+ *   targets [B, T] int64, T = L - 1: the input words of mode='train' (caps[:, :-1], <sos> first), row stride targets_ld.
+ *   used[b, 0]  = targets[b, 0]
+ *   draws[b, j] = the model's choice at decode step j, the word layer having been fed used[b, 0..j]: the arg-max of the logits
+ *                 (draw_mode 0) or the Gumbel-max draw of the sampled decode (draw_mode 1: the noise of (seed, decode step j,
+ *                 batch row b, v) exactly as above - same stream tag, same mapping)
+ *   used[b, j]  = draws[b, j-1] if coin(b, j) < p, else targets[b, j]                                  (j = 1 .. T-1)
+ *   coin(b, j)  = ((x >> 9) + 0.5) * 2^-23, x = word 0 of Philox4x32-10(counter = (0, b, j, 0x53534D58), key = (seed low, seed
+ *                 high 32 bits)): exact in fp32, strictly inside (0, 1); compared in fp32 with p, so p = 0 never and p = 1
+ *                 always takes the model's word.  b is the row of the caller's batch: batch padding, the two-chain schedule
+ *                 and tile shapes never enter (the noise contract of the sampled decode).
+ * Inference arithmetic (no dropout, weights as they stand).  A ground-truth id outside [0, V) that is fed is read as token 0 and
+ * reported as S2VT_ERR_INDEX by s2vt_check_async_error / the next call (used still records the id as given).
+ * s2vt_scheduled_decode[_cached]: s2vt_sample_decode[_cached] with the coin - same workspace (s2vt_decode_workspace_bytes), same
+ * weight-image cache, same schedules and padding.  used [B, L-1] and draws [B, L-1] (nullable) int64, contiguous.  0 <= ss_prob
+ * <= 1 (NaN refused), draw_mode 0 or 1, the temperature rule of the sampled decode when draw_mode = 1 (ignored otherwise): all
+ * checked on the host before anything is enqueued. */
+int s2vt_scheduled_decode(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t targets_ld,
+                          float ss_prob, int32_t draw_mode, float temperature, uint64_t seed, int64_t* used, int64_t* draws,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int s2vt_scheduled_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t targets_ld,
+                                 float ss_prob, int32_t draw_mode, float temperature, uint64_t seed, int64_t* used, int64_t* draws,
+                                 void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
+                                 void* stream);
+/* One step of the rule on token ids: out[b] = draw_tokens[b] if step > 0 and coin(row0 + b, step) < ss_prob, else
+ * targets[b * targets_ld + step] (b < B; all int64). */
+int s2vt_ss_mix(const int64_t* draw_tokens, const int64_t* targets, int64_t targets_ld, int32_t B, float ss_prob, uint64_t seed,
+                int32_t step, int32_t row0, int64_t* out, void* stream);
+/* used / draws (nullable) [B, steps] from the packed arg-max words packed[steps][B] of a loop of scheduled steps
+ * (s2vt_gru_step_fwd_token_ss, s2vt_lstm_chain_fwd with ss_targets), by the same rule. */
+int s2vt_ss_unpack(const unsigned long long* packed, int32_t steps, int32_t B, const int64_t* targets, int64_t targets_ld, float ss_prob,
+                   uint64_t seed, int64_t* used, int64_t* draws, void* stream);
 
 /* ---------------------------------------------------------------- run-time options
  * ONE table holds every switch of the library (csrc/options.hip).  The first read of an option takes S2VT_<NAME> (upper case)

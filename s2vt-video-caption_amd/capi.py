@@ -39,7 +39,9 @@ class LstmLayer(ctypes.Structure):
                 ("gx_t0", c_int32), ("n_gx", c_int32), ("bias", c_void_p), ("h0", c_void_p), ("c0", c_void_p),
                 ("mask", c_void_p), ("emb", c_void_p), ("w_e", c_void_p), ("ldw_e", c_int64), ("E", c_int32), ("V", c_int32),
                 ("tok_packed", c_void_p), ("tok_const", c_int32), ("h", c_void_p), ("c", c_void_p), ("stash", c_void_p),
-                ("hm", c_void_p), ("dh_ext", c_void_p), ("dh_t0", c_int32), ("dg", c_void_p)]
+                ("hm", c_void_p), ("dh_ext", c_void_p), ("dh_t0", c_int32), ("dg", c_void_p),
+                ("ss_targets", c_void_p), ("ss_ld", c_int64), ("ss_seed", c_uint64), ("ss_prob", c_float), ("ss_step", c_int32),
+                ("ss_row0", c_int32)]
 
 
 class CiderTable(ctypes.Structure):
@@ -153,6 +155,15 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "s2vt_sample_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_float, c_uint64, c_void_p, c_void_p,
                                             c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_scheduled_decode": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float, c_uint64,
+                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "s2vt_scheduled_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float,
+                                               c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_ss_mix": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p, c_void_p]),
+    "s2vt_ss_unpack": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int64, c_float, c_uint64, c_void_p, c_void_p, c_void_p]),
+    "s2vt_gru_step_fwd_token_ss": (c_int32, [c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p, c_int64,
+                                                                                              c_float, c_uint64, c_int32, c_int32, c_void_p,
+                                                                                              c_void_p]),
     "s2vt_weighted_ce_forward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                            c_void_p, c_void_p, c_void_p]),
     "s2vt_weighted_ce_backward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,

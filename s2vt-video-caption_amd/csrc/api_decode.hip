@@ -138,11 +138,15 @@ int32_t s2vt_decode_uses_cache(const s2vt_dims* d) {
     return (d->B % 64 == 0 || batch_padded(*d)) ? 1 : 0;
 }
 
+// scheduled sampling (s2vt_scheduled_decode): the ground-truth words, the coin's probability and seed, and where the words
+// that were fed (used) and every step's own choice (draws, optional) go - both [rows][L-1] for the rows of the caller's batch
+struct SchedArgs { const int64_t* targets; int64_t ldt; float p; uint32_t seed_lo, seed_hi; uint32_t rows; int64_t* used; int64_t* draws; };
 struct EncodeOut { float *vid_h, *vid_c, *word_h, *word_c; float* gx_dec; int depth; };      // states [B, H] after the L encode steps;
                                      // optional: word_rnn's vid_out gate input (+ biases) of the first `depth` decode steps [depth][B][4H]
 static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc = nullptr, const GumbelArgs* smp = nullptr);
+                              void* stream, const EncodeOut* enc = nullptr, const GumbelArgs* smp = nullptr,
+                              const SchedArgs* ss = nullptr);
 // schedule of the 79 token-dependent decode steps on the plane path: 1 = fused (the next step's recurrent GEMM inside the
 // argmax launch + a cell-update launch), 0 = a step kernel and an argmax kernel per step, batch halves as two chains
 static int decode_schedule() { return option(O_DECODE_FUSED); }
@@ -171,13 +175,13 @@ int s2vt_decode_encode_cached(const s2vt_dims* d, const s2vt_params* p, const fl
 }
 static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc, const GumbelArgs* smp);
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp, const SchedArgs* ss);
 static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc, const GumbelArgs* smp) {
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp, const SchedArgs* ss) {
     S2VT_REQUIRE(dims_ok(d) && p && feats && (ids || enc) && workspace, "s2vt_greedy_decode: null/invalid argument");
     if (!batch_padded(*d, enc != nullptr))
-        return greedy_decode_core(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream, enc, smp);
+        return greedy_decode_core(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream, enc, smp, ss);
     const s2vt_dims dp = padded_dims(*d);
     const size_t core = decode_core_bytes(dp);
     const DecodePad s = carve_decode_pad(*d, dp, reinterpret_cast<char*>(workspace) + core);
@@ -188,12 +192,13 @@ static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const fl
     S2VT_HIP(hipMemcpyAsync(s.feats, feats, B * L * F * sizeof(float), hipMemcpyDeviceToDevice, st));
     if ((rc = fill_zero(st, s.feats + B * L * F, (Bp - B) * L * F * sizeof(float)))) return rc;
     if (!enc) {
-        if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, s.ids, workspace, core, cache, cache_bytes, cache_valid, stream, nullptr, smp))) return rc;
+        if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, s.ids, workspace, core, cache, cache_bytes, cache_valid, stream, nullptr, smp, ss))) return rc;
+        if (ss) return 0;         // (used / draws were written for the caller's rows by the core itself)
         S2VT_HIP(hipMemcpyAsync(ids, s.ids, B * (L - 1) * sizeof(int64_t), hipMemcpyDeviceToDevice, st));
         return 0;
     }
     const EncodeOut pe{s.states, s.states + Bp * H, s.states + 2 * Bp * H, s.states + 3 * Bp * H, enc->depth > 0 ? s.gx_dec : nullptr, enc->depth};
-    if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, nullptr, workspace, core, cache, cache_bytes, cache_valid, stream, &pe, nullptr))) return rc;
+    if ((rc = greedy_decode_core(&dp, p, s.feats, sos_ix, nullptr, workspace, core, cache, cache_bytes, cache_valid, stream, &pe, nullptr, nullptr))) return rc;
     float* outs[4] = {enc->vid_h, enc->vid_c, enc->word_h, enc->word_c};
     for (int k = 0; k < 4; ++k)
         S2VT_HIP(hipMemcpyAsync(outs[k], s.states + (size_t)k * Bp * H, B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -204,7 +209,7 @@ static int greedy_decode_impl(const s2vt_dims* d, const s2vt_params* p, const fl
 }
 static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, int64_t* ids,
                               void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, bool cache_valid,
-                              void* stream, const EncodeOut* enc, const GumbelArgs* smp) {
+                              void* stream, const EncodeOut* enc, const GumbelArgs* smp, const SchedArgs* ss) {
     S2VT_REQUIRE(dims_ok(d) && p && feats && (ids || enc) && workspace, "s2vt_greedy_decode: null/invalid argument");
     S2VT_REQUIRE(sos_ix >= 0 && sos_ix < d->V, "s2vt_greedy_decode: sos_ix %d outside vocabulary %d", sos_ix, d->V);
     const DecodeWS w = carve_decode(*d, workspace);
@@ -299,6 +304,11 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
             // the packed word is the previous step's argmax: a producer that left it unwritten would decode as token
             // 0xFFFFFFFF - clamped and flagged (w.err[0], S2VT_ERR_INDEX) instead of read from beyond the table
             a.tok_limit = V; a.tok_err = w.err;
+            if (ss) {           // scheduled sampling: the coin of (batch row, decode step) picks the packed word or the ground truth
+                a.ss.forced = ss->targets + (int64_t)b0 * ss->ldt; a.ss.ld = ss->ldt;
+                a.ss.p = ss->p; a.ss.seed_lo = ss->seed_lo; a.ss.seed_hi = ss->seed_hi;
+                a.ss.step = (uint32_t)(t - L); a.ss.row0 = (uint32_t)b0; a.ss.rows = ss->rows;
+            }
         }
         a.gx = w.gx2 + t * B4H + o4; a.ldgx = 4 * (int64_t)H;
         a.c_prev = cprev ? cprev + o1 : nullptr; a.ldc = H;
@@ -314,6 +324,14 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
         gcur = *smp;
         gcur.step = (uint32_t)(t - L); gcur.row0 = (uint32_t)b0;
         return &gcur;
+    };
+    // the packed words of the L - 1 steps as ids - or, scheduled, as the words that were fed and the draws (caller's rows only)
+    auto finish_ids = [&]() -> int {
+        if (!ss) return unpack_tokens(st, w.packed, L - 1, B, ids);
+        SsArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.forced = ss->targets; sa.ld = ss->ldt; sa.p = ss->p; sa.seed_lo = ss->seed_lo; sa.seed_hi = ss->seed_hi; sa.rows = ss->rows;
+        return unpack_scheduled(st, w.packed, L - 1, B, std::min(B, (int)ss->rows), sa, ss->used, ss->draws);
     };
     auto word_step = [&](hipStream_t s, int t, const float* hprev, const float* cprev, int b0 = 0, int nb = -1) -> int {
         int r;
@@ -458,7 +476,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
                 }
                 if ((rc = pair(t, true, t + 1 < T))) return rc;
             }
-            if ((rc = unpack_tokens(st, w.packed, L - 1, B, ids))) return rc;
+            if ((rc = finish_ids())) return rc;
             return post_async_error(st, w.err);
         }
         const int nh = (ax3 && B % 128 == 0 && sx != st) ? 2 : 1;
@@ -469,7 +487,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
                                     t == L ? w.c2_all + (int64_t)(L - 1) * BH : w.c2, hf * (B / nh), B / nh)))
                     return rc;
         if (nh == 2 && (rc = handoff(sx, st, ev++))) return rc;
-        if ((rc = unpack_tokens(st, w.packed, L - 1, B, ids))) return rc;
+        if ((rc = finish_ids())) return rc;
         return post_async_error(st, w.err);                   // (a timed-out hand-off surfaces like the train path's)
     }
     const std::vector<int> bd = pipe_bounds(T, L, blk);
@@ -507,7 +525,7 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
             if ((rc = word_step(sx, t, t ? w.h2 + ((t - 1) & 1) * BH : nullptr, t ? w.c2 : nullptr))) return rc;
     }
     if ((rc = handoff(sx, st, ev++))) return rc;
-    if ((rc = unpack_tokens(st, w.packed, L - 1, B, ids))) return rc;
+    if ((rc = finish_ids())) return rc;
     return post_async_error(st, w.err);
 }
 
@@ -532,6 +550,55 @@ int s2vt_sample_decode_cached(const s2vt_dims* d, const s2vt_params* p, const fl
     S2VT_REQUIRE(temperature_ok(temperature), "s2vt_sample_decode_cached: temperature and 1 / temperature must be finite and > 0 (got %g)", (double)temperature);
     const GumbelArgs g = gumbel_args(temperature, seed, 0, 0, (uint32_t)d->B);
     return greedy_decode_impl(d, p, feats, sos_ix, ids, workspace, workspace_bytes, cache, cache_bytes, cache_valid != 0, stream, nullptr, &g);
+}
+
+// ------------------------------------------------------------------ scheduled sampling (mode='train', ss_prob > 0)
+// The decode drivers once more, each token step fed by the coin: the ground-truth word, or the model's own previous choice.
+static int scheduled_decode_impl(const char* who, const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
+                                 int64_t targets_ld, float ss_prob, int32_t draw_mode, float temperature, uint64_t seed, int64_t* used,
+                                 int64_t* draws, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                                 bool cache_valid, void* stream) {
+    S2VT_REQUIRE(dims_ok(d) && p && feats && targets && used && workspace, "%s: null/invalid argument", who);
+    S2VT_REQUIRE(targets_ld >= d->L - 1, "%s: targets row stride %lld < L - 1 = %d", who, (long long)targets_ld, d->L - 1);
+    S2VT_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "%s: ss_prob must be in [0, 1] (got %g)", who, (double)ss_prob);     // (NaN fails both)
+    S2VT_REQUIRE(draw_mode == 0 || draw_mode == 1, "%s: draw_mode must be 0 (arg-max) or 1 (sample), got %d", who, (int)draw_mode);
+    S2VT_REQUIRE(draw_mode == 0 || temperature_ok(temperature), "%s: temperature and 1 / temperature must be finite and > 0 (got %g)", who,
+                 (double)temperature);
+    const GumbelArgs g = gumbel_args(draw_mode ? temperature : 1.0f, seed, 0, 0, (uint32_t)d->B);
+    const SchedArgs ss{targets, targets_ld, ss_prob, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), (uint32_t)d->B, used, draws};
+    return greedy_decode_impl(d, p, feats, 0, used, workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream, nullptr,
+                              draw_mode ? &g : nullptr, &ss);
+}
+int s2vt_scheduled_decode(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t targets_ld,
+                          float ss_prob, int32_t draw_mode, float temperature, uint64_t seed, int64_t* used, int64_t* draws,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+    return scheduled_decode_impl("s2vt_scheduled_decode", d, p, feats, targets, targets_ld, ss_prob, draw_mode, temperature, seed, used,
+                                 draws, workspace, workspace_bytes, nullptr, 0, false, stream);
+}
+int s2vt_scheduled_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t targets_ld,
+                                 float ss_prob, int32_t draw_mode, float temperature, uint64_t seed, int64_t* used, int64_t* draws,
+                                 void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
+                                 void* stream) {
+    S2VT_REQUIRE(cache, "s2vt_scheduled_decode_cached: null cache");
+    return scheduled_decode_impl("s2vt_scheduled_decode_cached", d, p, feats, targets, targets_ld, ss_prob, draw_mode, temperature, seed,
+                                 used, draws, workspace, workspace_bytes, cache, cache_bytes, cache_valid != 0, stream);
+}
+static bool ss_prob_ok(float p) { return p >= 0.f && p <= 1.f; }
+static SsArgs ss_args(const int64_t* targets, int64_t ld, float p, uint64_t seed, int32_t step, int32_t row0, int32_t B) {
+    return SsArgs{targets, ld, p, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), (uint32_t)step, (uint32_t)row0,
+                  (uint32_t)row0 + (uint32_t)B};
+}
+int s2vt_ss_mix(const int64_t* draw_tokens, const int64_t* targets, int64_t targets_ld, int32_t B, float ss_prob, uint64_t seed,
+                int32_t step, int32_t row0, int64_t* out, void* stream) {
+    S2VT_REQUIRE(draw_tokens && targets && out && B > 0 && step >= 0 && row0 >= 0 && targets_ld > step, "s2vt_ss_mix: null/invalid argument");
+    S2VT_REQUIRE(ss_prob_ok(ss_prob), "s2vt_ss_mix: ss_prob must be in [0, 1] (got %g)", (double)ss_prob);
+    return ss_mix((hipStream_t)stream, draw_tokens, B, ss_args(targets, targets_ld, ss_prob, seed, step, row0, B), out);
+}
+int s2vt_ss_unpack(const unsigned long long* packed, int32_t steps, int32_t B, const int64_t* targets, int64_t targets_ld, float ss_prob,
+                   uint64_t seed, int64_t* used, int64_t* draws, void* stream) {
+    S2VT_REQUIRE(packed && targets && used && steps > 0 && B > 0 && targets_ld >= steps, "s2vt_ss_unpack: null/invalid argument");
+    S2VT_REQUIRE(ss_prob_ok(ss_prob), "s2vt_ss_unpack: ss_prob must be in [0, 1] (got %g)", (double)ss_prob);
+    return unpack_scheduled((hipStream_t)stream, packed, steps, B, B, ss_args(targets, targets_ld, ss_prob, seed, 0, 0, B), used, draws);
 }
 
 static int decode_step_argmax_impl(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,

@@ -25,9 +25,33 @@ int s2vt_gru_step_fwd(int32_t B, int32_t H, const float* gx, const float* b_ih, 
     return gru_step_fwd((hipStream_t)stream, a);
 }
 
+}  // (C linkage ends)
+static int gru_step_fwd_token_impl(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
+                                   const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
+                                   const unsigned long long* tok_packed, int32_t tok_const, const SsArgs* ss, float* h_out, void* stream);
+extern "C" {
 int s2vt_gru_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
                             const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
                             const unsigned long long* tok_packed, int32_t tok_const, float* h_out, void* stream) {
+    return gru_step_fwd_token_impl(B, H, E, V, gx, w_hh, b_hh, h_prev, emb, w_e, ldw_e, tok, tok_packed, tok_const, nullptr, h_out, stream);
+}
+// the same step of a scheduled-sampling pass: the coin of (row0 + b, step) picks tok_packed's word or targets[b][step]; a bad
+// ground-truth id is posted like a bad `tok`
+int s2vt_gru_step_fwd_token_ss(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
+                               const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e,
+                               const unsigned long long* tok_packed, const int64_t* targets, int64_t targets_ld, float ss_prob,
+                               uint64_t seed, int32_t step, int32_t row0, float* h_out, void* stream) {
+    S2VT_REQUIRE(targets && step >= 0 && row0 >= 0 && targets_ld > step && (tok_packed || step == 0),
+                 "s2vt_gru_step_fwd_token_ss: null/invalid argument");
+    S2VT_REQUIRE(ss_prob >= 0.f && ss_prob <= 1.f, "s2vt_gru_step_fwd_token_ss: ss_prob must be in [0, 1] (got %g)", (double)ss_prob);
+    const SsArgs ss{targets, targets_ld, ss_prob, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), (uint32_t)step,
+                    (uint32_t)row0, (uint32_t)row0 + (uint32_t)B};
+    return gru_step_fwd_token_impl(B, H, E, V, gx, w_hh, b_hh, h_prev, emb, w_e, ldw_e, nullptr, tok_packed, 0, &ss, h_out, stream);
+}
+}  // extern "C"
+static int gru_step_fwd_token_impl(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* b_hh,
+                                   const float* h_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
+                                   const unsigned long long* tok_packed, int32_t tok_const, const SsArgs* ss, float* h_out, void* stream) {
     S2VT_REQUIRE(gru_rows_ok(1, B, H) && E > 0 && V > 0 && gx && w_hh && b_hh && emb && w_e && h_out && ldw_e >= E,
                  "s2vt_gru_step_fwd_token: null/invalid argument");
     hipStream_t st = (hipStream_t)stream;
@@ -36,13 +60,14 @@ int s2vt_gru_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const fl
     // to report (the kernel still reads an impossible id as token 0).  Only a caller's int32 array (tok) needs the device flag,
     // posted on the ring record of the asynchronous-error table, so that one call per step never waits for an earlier step.
     // The greedy loop (first step tok_const, then tok_packed) therefore makes no device-to-host copy and never synchronises.
-    if (!tok && !tok_packed && (tok_const < 0 || tok_const >= V)) {
+    if (!tok && !tok_packed && !ss && (tok_const < 0 || tok_const >= V)) {
         set_error("s2vt_gru_step_fwd_token: token id %d outside [0, %d)", (int)tok_const, (int)V);
         return S2VT_ERR_INDEX;
     }
     int* flags = nullptr;
     int rc, rc0 = 0;
-    if (tok) {
+    const bool posts = tok || ss;      // (ids of the caller: a caller's int32 array, or the ground-truth words of a scheduled pass)
+    if (posts) {
         if ((rc = device_flags(&flags))) return rc;
         rc0 = poll_async_error(false);
         if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
@@ -55,14 +80,16 @@ int s2vt_gru_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const fl
     a.x2 = emb; a.ldx2 = E; a.K2 = E; a.w2 = w_e; a.ldw2 = ldw_e;
     a.tok_idx = tok; a.tok_packed = tok_packed; a.tok_const = tok_const;
     a.tok_limit = V; a.tok_err = flags;
+    if (ss) a.ss = *ss;
     a.h_out = h_out; a.ldho = H;
     {
         ProfScope ps(st, K_STEP_FWD, 1);
         if ((rc = gru_step_fwd(st, a))) return rc;
     }
-    if (!tok) return 0;
+    if (!posts) return 0;
     return rc0 ? rc0 : post_async_error(st, flags, 3);
 }
+extern "C" {
 
 int s2vt_gru_step_bwd(int32_t B, int32_t H, const float* dgh_next, const float* w_hh_t, const float* stash_next, const float* dh_out,
                       const float* stash, const float* h_prev, float* dh, float* dgx, float* dgh, void* stream) {

@@ -20,7 +20,11 @@ static int check_chain(const char* who, int32_t T, int32_t B, int32_t H, int32_t
         S2VT_REQUIRE(!l.mask || l.hm, "%s: layer %d: a mask needs the hm output", who, j);
         S2VT_REQUIRE(!l.emb || (T == 1 && l.w_e && l.E > 0 && l.V > 0 && l.ldw_e >= l.E),
                      "%s: layer %d: the token segment needs T = 1, w_e, E, V and ldw_e >= E", who, j);
-        S2VT_REQUIRE(!l.emb || l.tok_packed || (l.tok_const >= 0 && l.tok_const < l.V),
+        S2VT_REQUIRE(!l.ss_targets || (l.emb && l.ss_prob >= 0.f && l.ss_prob <= 1.f && l.ss_step >= 0 && l.ss_row0 >= 0 &&
+                                       l.ss_ld > l.ss_step && (l.tok_packed || l.ss_step == 0)),
+                     "%s: layer %d: scheduled sampling needs the token segment, ss_prob in [0, 1], a step inside the targets' rows and "
+                     "tok_packed after step 0", who, j);
+        S2VT_REQUIRE(!l.emb || l.tok_packed || l.ss_targets || (l.tok_const >= 0 && l.tok_const < l.V),
                      "%s: layer %d: token id %d outside [0, %d)", who, j, (int)l.tok_const, (int)l.V);
         if (bwd) {
             S2VT_REQUIRE(l.stash && l.dg, "%s: layer %d needs stash and dg", who, j);
@@ -38,6 +42,17 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
     if ((rc = check_chain("s2vt_lstm_chain_fwd", T, B, H, n, layers, false))) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
+    // a scheduled-sampling token segment reads the caller's ground-truth ids: a bad one is posted on the ring of the
+    // asynchronous-error table (as s2vt_gru_step_fwd_token does for a caller's int32 ids), so a loop of steps never waits
+    int* flags = nullptr;
+    int rc0 = 0;
+    bool posts = false;
+    for (int j = 0; j < n; ++j) posts = posts || (layers[j].emb && layers[j].ss_targets);
+    if (posts) {
+        if ((rc = device_flags(&flags))) return rc;
+        rc0 = poll_async_error(false);
+        if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    }
     for (int d = 0; d < T + n - 1; ++d) {
         ChainFwdLaunch a;
         memset(&a, 0, sizeof(a));
@@ -61,6 +76,11 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
             if (l.emb) {
                 s.emb = l.emb; s.E = l.E; s.w_e = l.w_e; s.ldw_e = l.ldw_e;
                 s.tok_packed = l.tok_packed; s.tok_const = l.tok_const; s.tok_limit = l.V;
+                if (l.ss_targets) {
+                    s.ss = SsArgs{l.ss_targets, l.ss_ld, l.ss_prob, (uint32_t)(l.ss_seed & 0xFFFFFFFFull), (uint32_t)(l.ss_seed >> 32),
+                                  (uint32_t)l.ss_step, (uint32_t)l.ss_row0, (uint32_t)l.ss_row0 + (uint32_t)B};
+                    s.tok_err = flags;
+                }
             }
             s.mask = l.mask ? l.mask + t * BH : nullptr;
             s.h_out = l.h + t * BH; s.c_out = l.c + t * BH;
@@ -73,7 +93,8 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
         }
         if (a.n && (rc = lstm_chain_fwd_launch(st, a))) return rc;
     }
-    return 0;
+    if (!posts) return 0;
+    return rc0 ? rc0 : post_async_error(st, flags, 3);
 }
 
 size_t s2vt_lstm_chain_bwd_workspace_bytes(int32_t B, int32_t H, int32_t n) {

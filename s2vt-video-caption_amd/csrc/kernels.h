@@ -89,6 +89,9 @@ struct StepFwdArgs {
     // producer bug (e.g. a packed argmax word that no workgroup wrote) then surfaces as an error code, not as a GPU fault.
     // tok_limit == 0: no token segment in use
     int tok_limit; int* tok_err;
+    // optional (scheduled sampling, philox.h): with ss.forced the token of row b is the packed word only where the row's coin
+    // falls below ss.p, the forced ground-truth id otherwise; tok_idx is then not read.  Same guard for a forced id.
+    SsArgs ss;
     // optional: CONTRACTION ONLY - z_out[b][g*H + u] = sum_k h_prev[b][k] W_hh[g*H + u][k] (the reduced partial sums, nothing
     // added) and no cell update: the recurrent half of a decode step that does not depend on the previous step's token, so it
     // runs beside that step's out_linear + argmax; lstm_cell_pointwise() finishes the step (same additions in the same order)
@@ -136,6 +139,7 @@ struct GruFwdArgs {
     const unsigned long long* tok_packed;
     int tok_const;
     int tok_limit; int* tok_err;
+    SsArgs ss;                               // optional scheduled-sampling block, as in StepFwdArgs
     float* h_out; int64_t ldho;
     float* stash; int64_t ldst;              // optional [B,4H]: r, z, n, ghn = h_{t-1} W_hn^T + b_hn (train only)
 };
@@ -173,6 +177,7 @@ struct ChainFwdStep {
     const float* emb; int E;
     const float* w_e; int64_t ldw_e;
     const unsigned long long* tok_packed; int tok_const; int tok_limit;
+    SsArgs ss; int* tok_err;                 // optional scheduled-sampling block, as in StepFwdArgs (a bad forced id raises *tok_err)
     const float* mask;                       // [B,H] dropout mask of this output as the next layer's input (NULL: none)
     float* h_out; float* c_out;              // [B,H]
     float* stash;                            // [B,4H] activated gates i,f,g,o (NULL: not kept)
@@ -352,6 +357,12 @@ int gather_rows_f32(hipStream_t s, const float* src, int64_t ld, const int32_t* 
 size_t embedding_grad_ws_ints(int64_t rows, int V);
 int embedding_grad(hipStream_t s, const float* d_rows, int64_t rows, int E, const int32_t* tok, int V, float* d_emb, int* ws);
 int unpack_tokens(hipStream_t s, const unsigned long long* packed, int steps, int B, int64_t* out_ids);
+// scheduled sampling: packed[step][ldp rows] -> used [B][steps] (the words each step was fed: ss.forced, or the previous step's
+// draw where the coin fell below ss.p) and, optionally, draws [B][steps] (every step's own choice); ss.step is not read
+int unpack_scheduled(hipStream_t s, const unsigned long long* packed, int steps, int ldp, int B, const SsArgs& ss, int64_t* used,
+                     int64_t* draws);
+// one step of the rule on token ids: out[b] = coin(row0 + b, step) < p ? draw_tokens[b] : forced[b * ld + step]
+int ss_mix(hipStream_t s, const int64_t* draw_tokens, int B, const SsArgs& ss, int64_t* out);
 int fill_zero(hipStream_t s, void* p, size_t bytes);
 int occupy_cus(hipStream_t s, int workgroups, int lds_bytes, long long microseconds);   // test support (co-residency tests)
 int zero_pad_cols_u16(hipStream_t s, unsigned short* p, int64_t rows, int64_t ld, int col0, int col1);

@@ -52,8 +52,15 @@ __device__ __forceinline__ float wave_reduce_scatter(float (&v)[M], int lane) {
 
 __device__ __forceinline__ int64_t gemv_token(const StepFwdArgs& p, int b) {
     int64_t tok = p.tok_const;
-    if (p.tok_idx) tok = p.tok_idx[b];
-    else if (p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
+    bool forced = false;
+    if (p.ss.forced) {       // (wave-uniform: a kernel argument)
+        const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
+        if (forced) tok = t;
+    }
+    if (!forced) {
+        if (p.tok_idx) tok = p.tok_idx[b];
+        else if (p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
+    }
     if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
         if (p.tok_err) *p.tok_err = 1;
         tok = 0;

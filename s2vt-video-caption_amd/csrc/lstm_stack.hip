@@ -95,8 +95,16 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdStep& p, int B, int
         for (int i = 0; i < MT * LPT; ++i) {
             const int b = b0 + lrow + RPL * i;
             int64_t tok = p.tok_const;
-            if (b < B && p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
-            if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) tok = 0;
+            bool forced = false;
+            if (b < B && p.ss.forced) {       // scheduled sampling (wave-uniform on the argument): the coin picks the word
+                const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
+                if (forced) tok = t;
+            }
+            if (!forced && b < B && p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
+            if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
+                if (p.tok_err) *p.tok_err = 1;
+                tok = 0;
+            }
             arow[i] = (b < B) ? p.emb + tok * p.E : nullptr;
         }
 #pragma unroll

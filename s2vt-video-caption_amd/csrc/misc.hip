@@ -391,7 +391,44 @@ int unpack_tokens(hipStream_t s, const unsigned long long* packed, int steps, in
     return 0;
 }
 
-// p[r][col0:col1) = 0 for every row (zero padding of bf16 row images whose valid columns are written elsewhere)
+// scheduled sampling: packed[step][ldp] -> used[b][step] (forced word, or the previous step's draw where the coin fell below p)
+// and draws[b][step] (optional)
+__global__ void unpack_scheduled_kernel(const unsigned long long* packed, int steps, int ldp, int B, SsArgs ss, int64_t* used,
+                                        int64_t* draws) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= steps * B) return;
+    const int st = i / B, b = i % B;
+    if (draws) draws[(int64_t)b * steps + st] = packed_token(packed[(int64_t)st * ldp + b]);
+    ss.step = (uint32_t)st;
+    bool has;
+    const int64_t tok = ss_token(ss, st ? packed + (int64_t)(st - 1) * ldp : nullptr, b, &has);
+    if (has) used[(int64_t)b * steps + st] = tok;
+}
+int unpack_scheduled(hipStream_t s, const unsigned long long* packed, int steps, int ldp, int B, const SsArgs& ss, int64_t* used,
+                     int64_t* draws) {
+    const int n = steps * B;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(unpack_scheduled_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, packed, steps, ldp, B, ss, used, draws);
+    S2VT_LAUNCH_CHECK("unpack_scheduled_kernel");
+    return 0;
+}
+
+// one step of the scheduled-sampling rule on token ids: out[b] = coin(row0 + b, step) < p ? draw_tokens[b] : forced[b * ld + step]
+// (step 0 has no previous draw: the forced word)
+__global__ void ss_mix_kernel(const int64_t* draw_tokens, int B, SsArgs ss, int64_t* out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const bool own = ss.step > 0 && ss_coin(ss.seed_lo, ss.seed_hi, ss.row0 + (uint32_t)b, ss.step) < ss.p;
+    out[b] = own ? draw_tokens[b] : ss.forced[(int64_t)b * ss.ld + ss.step];
+}
+int ss_mix(hipStream_t s, const int64_t* draw_tokens, int B, const SsArgs& ss, int64_t* out) {
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(ss_mix_kernel, dim3(cdiv(B, 256)), dim3(256), 0, s, draw_tokens, B, ss, out);
+    S2VT_LAUNCH_CHECK("ss_mix_kernel");
+    return 0;
+}
+
+// p[r][col0:col1) = 0 for every row(zero padding of bf16 row images whose valid columns are written elsewhere)
 __global__ void zero_pad_cols_kernel(unsigned short* p, int64_t rows, int64_t ld, int col0, int ncols) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * ncols) return;

@@ -20,6 +20,7 @@ namespace s2vt {
 constexpr uint32_t PHILOX_M0 = 0xD2511F53u, PHILOX_M1 = 0xCD9E8D57u;      // round multipliers
 constexpr uint32_t PHILOX_W0 = 0x9E3779B9u, PHILOX_W1 = 0xBB67AE85u;      // Weyl key increments
 constexpr uint32_t GUMBEL_STREAM_TAG = 0x47554D42u;                       // "GUMB": counter word 3 of the sampler's stream
+constexpr uint32_t SS_STREAM_TAG = 0x53534D58u;                           // "SSMX": counter word 3 of the scheduled-sampling coins
 
 struct GumbelArgs {                  // what a sampling launch adds to its greedy sibling's arguments
     float inv_temperature;           // score = logit * inv_temperature + g
@@ -58,6 +59,41 @@ __device__ __forceinline__ void gumbel4(const GumbelArgs& a, uint32_t v4, uint32
     const Philox4 r = philox4x32_10(v4, row, a.step, GUMBEL_STREAM_TAG, a.seed_lo, a.seed_hi);
 #pragma unroll
     for (int e = 0; e < 4; ++e) g[e] = gumbel_from_bits(r.w[e]);
+}
+
+// ---- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0)): the coin that decides, per batch row and decode step,
+// whether the step is fed the model's own previous draw or the ground-truth word.
+//     coin(b, j) = ((x >> 9) + 0.5) * 2^-23,  x = word 0 of philox4x32_10(counter = (0, b, j, SS_STREAM_TAG), key = seed halves)
+// exact in fp32 and strictly inside (0, 1): compared in fp32 with p, p = 0 never and p = 1 always takes the model's word.
+// b is the row of the CALLER's batch (row0 + the launch's row); padding, tiles and schedules do not enter.
+struct SsArgs {                      // what a scheduled-sampling launch adds to a token step's arguments (forced == null: absent)
+    const int64_t* forced;           // ground-truth words, row 0 = the launch's row 0: row b, step j at forced[b * ld + j]
+    int64_t ld;
+    float p;                         // probability of taking the model's word
+    uint32_t seed_lo, seed_hi;
+    uint32_t step;                   // decode step j of the launch (step 0 has no previous draw: always the forced word)
+    uint32_t row0;                   // batch row of the launch's row 0
+    uint32_t rows;                   // rows of the caller's batch: rows past it (batch padding) have no forced word
+};
+
+__host__ __device__ __forceinline__ float ss_coin(uint32_t seed_lo, uint32_t seed_hi, uint32_t row, uint32_t step) {
+    const Philox4 r = philox4x32_10(0u, row, step, SS_STREAM_TAG, seed_lo, seed_hi);
+    return ((float)(r.w[0] >> 9) + 0.5f) * 0x1p-23f;
+}
+
+// token index of a packed arg-max word (ordered score << 32 | 0xFFFFFFFF - index)
+__host__ __device__ __forceinline__ int64_t packed_token(unsigned long long w) {
+    return (int64_t)(0xFFFFFFFFu - (uint32_t)(w & 0xFFFFFFFFull));
+}
+
+// The token a scheduled step feeds row b of its launch: `packed` = the previous step's packed words of the launch's rows (null
+// at step 0).  *has = false for a padding row (the caller keeps its own rule there).
+__device__ __forceinline__ int64_t ss_token(const SsArgs& s, const unsigned long long* packed, int b, bool* has) {
+    const uint32_t row = s.row0 + (uint32_t)b;
+    *has = row < s.rows;
+    if (!*has) return 0;
+    if (packed && s.step > 0 && ss_coin(s.seed_lo, s.seed_hi, row, s.step) < s.p) return packed_token(packed[b]);
+    return s.forced[(int64_t)b * s.ld + s.step];
 }
 
 }  // namespace s2vt

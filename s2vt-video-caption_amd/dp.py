@@ -212,19 +212,20 @@ def global_mean(total, count, device="cpu"):
     return float(t[0] / torch.clamp(t[1], min=1.0))
 
 
-def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False):
+def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False, forward_kwargs=None):
     """One optimisation step of train.py:116-127 on this rank's shard; returns the (local) loss tensor.
     With `reducer`, gradients are averaged over ranks before the optimiser step.
     `check_errors`: synchronise and raise device-side errors of this step (a caption id outside the vocabulary -> IndexError, as
     nn.Embedding raises in the reference's forward; a timed-out hand-off) BEFORE optimizer.step(), so that a bad batch never
     reaches the weights - what the reference's ordering gives for free.  Costs one synchronisation per step; a loop that reads
-    loss.item() every step (train.py:127) pays that anyway."""
+    loss.item() every step (train.py:127) pays that anyway.
+    `forward_kwargs`: further keywords of the model's forward (scheduled sampling: ss_prob, ss_temperature)."""
     if reducer is not None:
         reducer.zero_grad()
     else:
         optimizer.zero_grad()
     model.train()
-    probs = model(feats, targets=caps[:, :-1], mode='train')
+    probs = model(feats, targets=caps[:, :-1], mode='train', **(forward_kwargs or {}))
     loss = criterion(probs, caps, mask)
     loss.backward()
     if reducer is not None:

@@ -248,6 +248,65 @@ def greedy_decode(feats, params, sos_ix, owner=None, sample=None):
     return ids
 
 
+def check_ss_prob(ss_prob):
+    """ss_prob as a float in [0, 1] or ValueError - before anything reaches the library"""
+    p = float(ss_prob)
+    if not 0.0 <= p <= 1.0:            # (NaN fails both compares)
+        raise ValueError("ss_prob must be in [0, 1], got %r" % (ss_prob,))
+    return p
+
+
+def check_scheduled_args(targets, B, T, ss_prob, temperature, seed):
+    """(targets int64 with unit column stride, ss_prob, temperature or None, seed) of a scheduled pass, or ValueError"""
+    from . import sampling
+    p = check_ss_prob(ss_prob)
+    require_hip(targets, "targets")
+    if targets.dtype != torch.int64:
+        targets = targets.long()
+    if targets.dim() != 2 or targets.stride(1) != 1:
+        targets = targets.reshape(targets.shape[0], -1).contiguous()
+    if targets.shape[0] != B or targets.shape[1] != T:
+        raise ValueError("targets must be [B, L-1] = [%d, %d], got %s" % (B, T, tuple(targets.shape)))
+    t, seed = sampling.check_sample_args(1.0 if temperature is None else temperature, seed)
+    return targets, p, (None if temperature is None else t), seed
+
+
+@torch.no_grad()
+def scheduled_inputs(feats, targets, params, ss_prob, temperature=None, seed=None, owner=None, return_draws=False):
+    """The input words of a scheduled-sampling train step (include/s2vt_hip.h, s2vt_scheduled_decode): used int64 [B, L-1] with
+    used[:, 0] = targets[:, 0] and used[b, j] = the model's own choice at step j-1 where coin(b, j) < ss_prob, targets[b, j]
+    otherwise.  The model's choice is the arg-max (temperature None) or a draw from softmax(logit / temperature).  One decode call
+    in inference arithmetic, no gradient; same workspace and weight-image cache (`owner`) as greedy_decode.  seed None: drawn from
+    torch's generator (sampling.draw_seed).  return_draws: (used, draws), draws [B, L-1] = every step's choice."""
+    lib = capi.load()
+    feats = _f32c(feats, "feats")
+    raw = params
+    params = tuple(_f32c(p.detach(), "parameter") for p in params)
+    d = _dims(feats, params)
+    targets, ss_prob, temperature, seed = check_scheduled_args(targets, d.B, d.L - 1, ss_prob, temperature, seed)
+    mode, temp = (0, 1.0) if temperature is None else (1, temperature)
+    dev = feats.device
+    with torch.cuda.device(dev):
+        nbytes = lib.s2vt_decode_workspace_bytes(ctypes.byref(d))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        used = torch.empty(d.B, d.L - 1, dtype=torch.int64, device=dev)
+        draws = torch.empty(d.B, d.L - 1, dtype=torch.int64, device=dev) if return_draws else None
+        ps = _params_struct(capi.Params, params)
+        cache, valid = decode_cache_entry(owner, raw, d, dev, lib)
+        if cache is not None:
+            capi.check(lib.s2vt_scheduled_decode_cached(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(targets), targets.stride(0),
+                                                        ss_prob, mode, temp, seed, _ptr(used), _ptr(draws), _ptr(ws), nbytes, _ptr(cache),
+                                                        cache.numel(), 1 if valid else 0, _stream(dev)), "s2vt_scheduled_decode_cached")
+            entry = _DECODE_CACHES.get(owner)
+            if entry is not None and entry[1] is cache and lib.s2vt_decode_uses_cache(ctypes.byref(d)):
+                entry[2] = True
+        else:
+            capi.check(lib.s2vt_scheduled_decode(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(targets), targets.stride(0), ss_prob,
+                                                 mode, temp, seed, _ptr(used), _ptr(draws), _ptr(ws), nbytes, _stream(dev)),
+                       "s2vt_scheduled_decode")
+    return (used, draws) if return_draws else used
+
+
 @torch.no_grad()
 def decode_encode(feats, params, owner, depth=0):
     """The encode phase of a decode on the plane path (s2vt_decode_encode_cached): (vid_h, vid_c, word_h, word_c, gx_dec), the

@@ -96,9 +96,10 @@ def train_forward(model, feats, targets, out_mask=None):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix, sample=None):
+def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
     """mode='test' (S2VTModel.py:82-110): ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the same loop with
-    s2vt_decode_step_sample in place of the arg-max.  vid_rnn without a stash, word_rnn's encode over the first L steps,
+    s2vt_decode_step_sample in place of the arg-max.  ss = (targets, ss_prob, seed): the scheduled-sampling pass - every token
+    step is s2vt_gru_step_fwd_token_ss, and (used, draws) are returned instead of the ids.  vid_rnn without a stash, word_rnn's encode over the first L steps,
     then L-1 decode steps of s2vt_gru_step_fwd_token (the previous step's packed argmax word is read on the device) and
     s2vt_decode_step_argmax.  No host synchronisation inside the loop: <sos> is checked on the host by the first step, and the
     packed words are in range by construction, so no step posts a device error flag."""
@@ -121,7 +122,20 @@ def greedy_decode(model, feats, sos_ix, sample=None):
         hs = torch.empty(2, B, H, dtype=torch.float32, device=dev)
         for i in range(L - 1):
             h = ops.gru_step_fwd_token(gx_dec[i * B:(i + 1) * B], w_hh, b_hh, h, emb, w_ih, tok_packed=packed[i - 1] if i else None,
-                                       tok_const=int(sos_ix), out=hs[i % 2])
+                                       tok_const=int(sos_ix), out=hs[i % 2], ss=None if ss is None else ss + (i,))
             ops.decode_step_token_into(h, wo, bo, packed[i], sample=sample, step=i)
     capi.check_async_error(wait=False)
+    if ss is not None:
+        return ops.ss_unpack(packed, *ss)
     return (0xFFFFFFFF - (packed & 0xFFFFFFFF)).t().contiguous()
+
+
+def scheduled_inputs(model, feats, targets, ss_prob, temperature=None, seed=None, return_draws=False):
+    """functional.scheduled_inputs for a GRU model: the greedy / sampled decode loop above with the coin in front of every
+    token step (inference arithmetic, no gradient)."""
+    from .functional import check_scheduled_args
+    B, L, _ = feats.shape
+    targets, ss_prob, temperature, seed = check_scheduled_args(targets, B, L - 1, ss_prob, temperature, seed)
+    used, draws = greedy_decode(model, feats, 0, sample=None if temperature is None else (temperature, seed),
+                                ss=(targets, ss_prob, seed))
+    return (used, draws) if return_draws else used

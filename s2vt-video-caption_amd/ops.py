@@ -433,10 +433,12 @@ def gru_step_fwd(gx, b_ih, w_hh, b_hh, h_prev, want_stash=False, B=None):
     return (h, stash) if want_stash else h
 
 
-def gru_step_fwd_token(gx, w_hh, b_hh, h_prev, emb, w_ih, tok=None, tok_packed=None, tok_const=0, out=None):
+def gru_step_fwd_token(gx, w_hh, b_hh, h_prev, emb, w_ih, tok=None, tok_packed=None, tok_const=0, out=None, ss=None):
     """One greedy decode step of a GRU word_rnn: gx [B,3H] (vid half of the gate input + b_ih), emb [V,E], w_ih [3H, E+H] (its
     first E columns multiply the embedded word).  Token per row: `tok` int32 [B], else `tok_packed` (the packed argmax words of
-    s2vt_decode_step_argmax), else `tok_const`.  Ids outside [0, V) raise IndexError at the next capi.check_async_error()."""
+    s2vt_decode_step_argmax), else `tok_const`.  Ids outside [0, V) raise IndexError at the next capi.check_async_error().
+    `ss` = (targets int64 [B, T], ss_prob, seed, step): a scheduled-sampling step (s2vt_gru_step_fwd_token_ss) - the coin of
+    (row, step) picks tok_packed's word or targets[:, step]."""
     lib = capi.load()
     gx, w_hh, b_hh, emb, w_ih = (_f32c(gx, "gx"), _f32c(w_hh, "w_hh"), _f32c(b_hh, "b_hh"), _f32c(emb, "emb"), _f32c(w_ih, "w_ih"))
     B, H = gx.shape[0], w_hh.shape[1]
@@ -444,6 +446,12 @@ def gru_step_fwd_token(gx, w_hh, b_hh, h_prev, emb, w_ih, tok=None, tok_packed=N
     dev = gx.device
     with torch.cuda.device(dev):
         h = out if out is not None else torch.empty(B, H, dtype=torch.float32, device=dev)
+        if ss is not None:
+            targets, ss_prob, seed, step = ss
+            capi.check(lib.s2vt_gru_step_fwd_token_ss(B, H, E, V, _ptr(gx), _ptr(w_hh), _ptr(b_hh), _ptr(h_prev), _ptr(emb), _ptr(w_ih),
+                                                      w_ih.stride(0), _ptr(tok_packed), _ptr(targets), targets.stride(0), float(ss_prob),
+                                                      int(seed), int(step), 0, _ptr(h), _stream(dev)), "s2vt_gru_step_fwd_token_ss")
+            return h
         capi.check(lib.s2vt_gru_step_fwd_token(B, H, E, V, _ptr(gx), _ptr(w_hh), _ptr(b_hh), _ptr(h_prev), _ptr(emb), _ptr(w_ih),
                                                w_ih.stride(0), _ptr(tok), _ptr(tok_packed), int(tok_const), _ptr(h), _stream(dev)),
                    "s2vt_gru_step_fwd_token")
@@ -538,6 +546,10 @@ def _chain_struct(layers):
             s.tok_packed = lay["tok_packed"].data_ptr()
         for k in ("gx_t0", "n_gx", "E", "V", "tok_const", "dh_t0"):
             setattr(s, k, int(lay.get(k, 0)))
+        if lay.get("ss") is not None:        # (targets int64 [B, T], ss_prob, seed, step): a scheduled-sampling token segment
+            targets, ss_prob, seed, step = lay["ss"]
+            s.ss_targets, s.ss_ld, s.ss_prob, s.ss_seed, s.ss_step, s.ss_row0 = (targets.data_ptr(), targets.stride(0), float(ss_prob),
+                                                                                 int(seed), int(step), 0)
     return arr
 
 
@@ -559,6 +571,49 @@ def lstm_chain_bwd(T, B, H, layers):
         nbytes = lib.s2vt_lstm_chain_bwd_workspace_bytes(B, H, len(layers))
         ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev)
         capi.check(lib.s2vt_lstm_chain_bwd(T, B, H, len(layers), arr, _ptr(ws), nbytes, _stream(dev)), "s2vt_lstm_chain_bwd")
+
+
+def _ss_targets(targets):
+    require_hip(targets, "targets")
+    if targets.dim() != 2:
+        raise ValueError("targets must be [B, T], got %s" % (tuple(targets.shape),))
+    if targets.dtype != torch.int64 or targets.stride(1) != 1:
+        targets = targets.long().contiguous()
+    return targets
+
+
+def ss_mix(draw_tokens, targets, ss_prob, seed, step, row0=0):
+    """int64 [B]: one step of the scheduled-sampling rule (s2vt_ss_mix) - draw_tokens[b] where step > 0 and
+    coin(row0 + b, step) < ss_prob, targets[b, step] otherwise.  draw_tokens int64 [B], targets int64 [B, T]."""
+    lib = capi.load()
+    targets = _ss_targets(targets)
+    require_hip(draw_tokens, "draw_tokens")
+    if draw_tokens.dtype != torch.int64 or tuple(draw_tokens.shape) != (targets.shape[0],):
+        raise capi.S2VTHipError("ss_mix: draw_tokens must be int64 [B]")
+    draw_tokens = draw_tokens.contiguous()
+    B = targets.shape[0]
+    if not 0 <= int(step) < targets.shape[1]:
+        raise ValueError("ss_mix: step %d outside the %d columns of targets" % (step, targets.shape[1]))
+    dev = targets.device
+    with torch.cuda.device(dev):
+        out = torch.empty(B, dtype=torch.int64, device=dev)
+        capi.check(lib.s2vt_ss_mix(_ptr(draw_tokens), _ptr(targets), targets.stride(0), B, float(ss_prob), int(seed), int(step), int(row0),
+                                   _ptr(out), _stream(dev)), "s2vt_ss_mix")
+    return out
+
+
+def ss_unpack(packed, targets, ss_prob, seed, want_draws=True):
+    """(used, draws or None) int64 [B, T] from the packed arg-max words [T, B] (int64) of a loop of scheduled steps - s2vt_ss_unpack."""
+    lib = capi.load()
+    targets = _ss_targets(targets)
+    T, B = packed.shape
+    dev = targets.device
+    with torch.cuda.device(dev):
+        used = torch.empty(B, T, dtype=torch.int64, device=dev)
+        draws = torch.empty(B, T, dtype=torch.int64, device=dev) if want_draws else None
+        capi.check(lib.s2vt_ss_unpack(_ptr(packed), T, B, _ptr(targets), targets.stride(0), float(ss_prob), int(seed), _ptr(used),
+                                      _ptr(draws), _stream(dev)), "s2vt_ss_unpack")
+    return used, draws
 
 
 def cider_rewards(table, clip_rows, ids, sos_ix, eos_ix):

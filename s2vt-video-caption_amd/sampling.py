@@ -18,6 +18,7 @@ import numpy as np
 M0, M1 = 0xD2511F53, 0xCD9E8D57          # Philox4x32 round multipliers
 W0, W1 = 0x9E3779B9, 0xBB67AE85          # Weyl key increments
 STREAM_TAG = 0x47554D42                  # "GUMB": counter word 3 of the sampler's stream (GUMBEL_STREAM_TAG of csrc/philox.h)
+SS_STREAM_TAG = 0x53534D58               # "SSMX": counter word 3 of the scheduled-sampling coins (SS_STREAM_TAG of csrc/philox.h)
 _MASK32 = np.uint64(0xFFFFFFFF)
 
 
@@ -62,6 +63,34 @@ def gumbel_noise(seed, step, rows, V):
     key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32)
     bits = philox4x32_10(counter, key).reshape(rows.shape[0], nblk * 4)[:, :int(V)]
     return gumbel_from_bits(bits)
+
+
+def ss_coin(seed, step, rows):
+    """float32 [len(rows)]: the scheduled-sampling coins of decode step `step` for the batch rows `rows` (an int n means rows
+    0..n-1): u = ((x >> 9) + 0.5) * 2^-23 with x = word 0 of philox4x32_10((0, row, step, SS_STREAM_TAG), seed halves) - exact
+    in fp32, strictly inside (0, 1).  The step is fed the model's own previous word where coin < np.float32(p)."""
+    rows = np.arange(rows, dtype=np.uint32) if np.isscalar(rows) else np.asarray(rows, dtype=np.uint32)
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("seed must be in [0, 2^64)")
+    counter = np.zeros((rows.shape[0], 4), dtype=np.uint32)
+    counter[:, 1] = rows
+    counter[:, 2] = np.uint32(step)
+    counter[:, 3] = np.uint32(SS_STREAM_TAG)
+    key = np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32)
+    return uniform_from_bits(philox4x32_10(counter, key)[:, 0]).astype(np.float32)
+
+
+def ss_used(targets, draws, p, seed, row0=0):
+    """int64 [B, T]: the words a scheduled pass feeds - targets[:, 0], then draws[:, j-1] where ss_coin < float32(p), targets[:, j]
+    otherwise (numpy arrays; the definition the device is compared against)."""
+    targets, draws = np.asarray(targets, dtype=np.int64), np.asarray(draws, dtype=np.int64)
+    used = targets.copy()
+    rows = np.arange(targets.shape[0], dtype=np.uint32) + np.uint32(row0)
+    for j in range(1, targets.shape[1]):
+        own = ss_coin(seed, j, rows) < np.float32(p)
+        used[own, j] = draws[own, j - 1]
+    return used
 
 
 def draw_seed(generator=None):

@@ -171,9 +171,10 @@ def _layer_masks(N, rnn_masks, rows, H):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix, sample=None):
+def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
     """mode='test' (S2VTModel.py:82-110) of a stacked model: ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the
-    same loop with s2vt_decode_step_sample in place of the arg-max.  The vid chain over T steps, the word chain's
+    same loop with s2vt_decode_step_sample in place of the arg-max.  ss = (targets, ss_prob, seed): the scheduled-sampling pass -
+    the token layer of every step takes the coin's word, no dropout masks are drawn, and (used, draws) are returned.  The vid chain over T steps, the word chain's
     encode over the first L steps, then L-1 decode steps of one word-chain call each (T = 1, the previous step's state, the packed
     argmax word read on the device) followed by s2vt_decode_step_argmax.  No host synchronisation inside the loop.  In training
     mode with rnn_dropout > 0, masks are drawn as nn.LSTM would apply them."""
@@ -182,7 +183,7 @@ def greedy_decode(model, feats, sos_ix, sample=None):
     N = model.vid_rnn.num_layers
     T = 2 * L - 1
     dev = feats.device
-    p = float(model.vid_rnn.dropout) if model.training else 0.0
+    p = float(model.vid_rnn.dropout) if (model.training and ss is None) else 0.0
 
     def mask(rows):
         return F.dropout(torch.ones(rows, H, dtype=torch.float32, device=dev), p=p, training=True) if p > 0 else None
@@ -220,7 +221,8 @@ def greedy_decode(model, feats, sos_ix, sample=None):
         packed = torch.zeros(L - 1, B, dtype=torch.int64, device=dev)
         for i in range(L - 1):
             step = stack(model.word_rnn, B, dict(x_in=vtop[(L + i) * B:(L + i + 1) * B], w_in=w_v, emb=emb, w_e=w0, E=E, V=V,
-                                                 tok_packed=packed[i - 1] if i else None, tok_const=int(sos_ix)))
+                                                 tok_packed=packed[i - 1] if i else None, tok_const=int(sos_ix),
+                                                 ss=None if ss is None else ss + (i,)))
             for k, lay in enumerate(step):
                 lay.update(h0=state[k][0], c0=state[k][1], h=bufs[i % 2][k]["h"], c=bufs[i % 2][k]["c"])
                 if lay["mask"] is not None:
@@ -229,7 +231,20 @@ def greedy_decode(model, feats, sos_ix, sample=None):
             state = [(lay["h"], lay["c"]) for lay in step]
             ops.decode_step_token_into(state[-1][0], wo, bo, packed[i], sample=sample, step=i)
     capi.check_async_error(wait=False)
+    if ss is not None:
+        return ops.ss_unpack(packed, *ss)
     return (0xFFFFFFFF - (packed & 0xFFFFFFFF)).t().contiguous()
+
+
+def scheduled_inputs(model, feats, targets, ss_prob, temperature=None, seed=None, return_draws=False):
+    """functional.scheduled_inputs for a stacked model: the decode loop above with the coin in front of every token step
+    (inference arithmetic: no dropout masks, no gradient)."""
+    from .functional import check_scheduled_args
+    B, L, _ = feats.shape
+    targets, ss_prob, temperature, seed = check_scheduled_args(targets, B, L - 1, ss_prob, temperature, seed)
+    used, draws = greedy_decode(model, feats, 0, sample=None if temperature is None else (temperature, seed),
+                                ss=(targets, ss_prob, seed))
+    return (used, draws) if return_draws else used
 
 
 def _with_outputs(layers, rows, H, dev, hm=False):

@@ -67,7 +67,38 @@ def parse(argv=None):
                          "card, the rewards, the <sos>-prefixed captions and the advantage weights come from HIP kernels "
                          "(s2vt_cider_rewards, s2vt_sc_weights) and the ids never leave the device")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
-    return ap.parse_args(argv)
+    ap.add_argument("--scheduled-sampling-start", type=int, default=-1, metavar="E",
+                    help="scheduled sampling (Bengio et al., 2015) from epoch E on: each decode-step input of a training step is, with "
+                         "the epoch's probability, the word the model itself chose at the previous step instead of the caption's "
+                         "(S2VT.forward(ss_prob=...)); -1 (default): off.  The usual stage between cross-entropy and --self-critical "
+                         "training.  Validation stays teacher-forced")
+    ap.add_argument("--scheduled-sampling-increase-every", type=int, default=5, metavar="N",
+                    help="the probability grows every N epochs after the start")
+    ap.add_argument("--scheduled-sampling-increase-prob", type=float, default=0.05, metavar="d", help="by this much")
+    ap.add_argument("--scheduled-sampling-max-prob", type=float, default=0.25, metavar="m", help="up to this value")
+    ap.add_argument("--ss-temperature", type=float, default=None,
+                    help="the model's own word is a draw from softmax(logit / temperature); absent: the arg-max")
+    opt = ap.parse_args(argv)
+    if opt.scheduled_sampling_start >= 0:
+        if opt.self_critical:
+            ap.error("--scheduled-sampling-start cannot be combined with --self-critical (it is the stage before it)")
+        if opt.model == "att_baseline":
+            ap.error("--scheduled-sampling-start needs --model s2vt (Att_Baseline has no scheduled sampling)")
+        if opt.scheduled_sampling_increase_every < 1:
+            ap.error("--scheduled-sampling-increase-every must be at least 1")
+        if not (0.0 <= opt.scheduled_sampling_max_prob <= 1.0 and opt.scheduled_sampling_increase_prob >= 0.0):
+            ap.error("--scheduled-sampling-max-prob must be in [0, 1] and --scheduled-sampling-increase-prob >= 0")
+        if opt.ss_temperature is not None and not 0.0 < opt.ss_temperature < float("inf"):
+            ap.error("--ss-temperature must be finite and > 0")
+    return opt
+
+
+def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
+    """Scheduled-sampling probability of an epoch: 0 before `start` (or with start < 0: off), then inc * ((epoch - start) // every),
+    capped at max_prob."""
+    if start < 0 or epoch < start:
+        return 0.0
+    return min(inc * ((epoch - start) // every), max_prob)
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
@@ -203,7 +234,7 @@ def run(opt):
     early_stopping = EarlyStopping(patience=opt.early_stopping_patience, verbose=rank == 0,
                                    path=os.path.join(opt.save_path, start_time + 'stop.pth'))        # :98-100
     criterion = MaskCriterion()
-    hist = {"train_loss": [], "valid_loss": [], "lr": [], "stopped_at": None, "checkpoints": []}
+    hist = {"train_loss": [], "valid_loss": [], "lr": [], "stopped_at": None, "checkpoints": [], "ss_prob": []}
     rewarder = None
     if opt.self_critical:
         if world > 1 or opt.model != "s2vt":
@@ -234,6 +265,11 @@ def run(opt):
         if sampler is not None:
             sampler.set_epoch(epoch)
         hist["lr"].append(optimizer.param_groups[0]['lr'])
+        ss_prob = ss_prob_for_epoch(epoch, opt.scheduled_sampling_start, opt.scheduled_sampling_increase_every,
+                                    opt.scheduled_sampling_increase_prob, opt.scheduled_sampling_max_prob)
+        hist["ss_prob"].append(ss_prob)
+        # (ss_prob == 0 passes no keyword at all: the plain teacher-forced step; every process draws its own seeds)
+        ss_kwargs = dict(ss_prob=ss_prob, ss_temperature=opt.ss_temperature) if ss_prob > 0 else None
         running, count = 0.0, 0
         for feats, targets, ids, masks in dataloader.feed_batches(train_loader, dev):
             # train.py:116-127; check_errors: a device-side error of this step (IndexError for a caption id outside the vocabulary)
@@ -241,7 +277,8 @@ def run(opt):
             if rewarder is not None:
                 loss = self_critical_step(feats, ids)
             else:
-                loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True)
+                loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True,
+                                     forward_kwargs=ss_kwargs)
             running += float(loss)
             count += 1
         train_loss = running / max(count, 1)
@@ -260,8 +297,9 @@ def run(opt):
         hist["train_loss"].append(train_loss)
         hist["valid_loss"].append(valid_loss)
         if rank == 0:
-            print("epoch {} train loss:{} valid loss: {} lr: {}".format(epoch, train_loss, valid_loss,
-                                                                        optimizer.param_groups[0]['lr']))
+            print("epoch {} train loss:{} valid loss: {} lr: {}{}".format(
+                epoch, train_loss, valid_loss, optimizer.param_groups[0]['lr'],
+                " ss_prob: {}".format(ss_prob) if opt.scheduled_sampling_start >= 0 else ""))
         lr_scheduler.step(valid_loss)                                                          # train.py:155
         n_before = early_stopping.val_loss_min
         if rank == 0:
