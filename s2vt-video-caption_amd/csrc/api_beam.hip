@@ -118,8 +118,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
             StepFwdArgs a = {};
             a.B = R; a.H = H;
             a.h_prev = w.ph; a.ldh = H; a.w_hh = p->word_w_hh; a.ldw = H;
-            a.gx_tab = kc.gtab; a.ldtab = 4 * (int64_t)H; a.tok_idx = tok;
-            a.tok_limit = V; a.tok_err = w.err;
+            a.gx_tab = kc.gtab; a.ldtab = 4 * (int64_t)H;
+            a.tok.tok_idx = tok; a.tok.tok_limit = V; a.tok.tok_err = w.err;
             a.gx = gx_vid ? gx_vid : w.gx; a.ldgx = 4 * H; a.gx_idx = row_b;
             a.c_prev = w.pc; a.ldc = H;
             a.h_out = word_h_out; a.ldho = H; a.c_out = word_c_out; a.ldco = H;
@@ -139,8 +139,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         StepFwdArgs a = {};
         a.B = R; a.H = H;
         a.h_prev = w.ph; a.ldh = H; a.w_hh = p->word_w_hh; a.ldw = H;
-        a.x2 = p->emb_w; a.ldx2 = E; a.K2 = E; a.w2 = p->word_w_ih; a.ldw2 = E + H; a.tok_idx = tok;
-        a.tok_limit = V; a.tok_err = w.err;            // nn.Embedding raises IndexError for such an id (S2VTModel.py:211)
+        a.x2 = p->emb_w; a.ldx2 = E; a.K2 = E; a.w2 = p->word_w_ih; a.ldw2 = E + H;
+        a.tok.tok_idx = tok; a.tok.tok_limit = V; a.tok.tok_err = w.err;            // nn.Embedding raises IndexError for such an id (S2VTModel.py:211)
         a.gx = w.gx; a.ldgx = 4 * H;
         a.c_prev = w.pc; a.ldc = H;
         a.h_out = word_h_out; a.ldho = H; a.c_out = word_c_out; a.ldco = H;

@@ -299,15 +299,14 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
                 a.x2 = p->emb_w; a.ldx2 = E; a.K2 = E;
                 a.w2 = p->word_w_ih; a.ldw2 = E + H;
             }
-            a.tok_packed = (t > L) ? w.packed + (int64_t)(t - L - 1) * B + b0 : nullptr;
-            a.tok_const = sos_ix;
+            a.tok.tok_packed = (t > L) ? w.packed + (int64_t)(t - L - 1) * B + b0 : nullptr;
+            a.tok.tok_const = sos_ix;
             // the packed word is the previous step's argmax: a producer that left it unwritten would decode as token
             // 0xFFFFFFFF - clamped and flagged (w.err[0], S2VT_ERR_INDEX) instead of read from beyond the table
-            a.tok_limit = V; a.tok_err = w.err;
+            a.tok.tok_limit = V; a.tok.tok_err = w.err;
             if (ss) {           // scheduled sampling: the coin of (batch row, decode step) picks the packed word or the ground truth
-                a.ss.forced = ss->targets + (int64_t)b0 * ss->ldt; a.ss.ld = ss->ldt;
-                a.ss.p = ss->p; a.ss.seed_lo = ss->seed_lo; a.ss.seed_hi = ss->seed_hi;
-                a.ss.step = (uint32_t)(t - L); a.ss.row0 = (uint32_t)b0; a.ss.rows = ss->rows;
+                a.tok.ss = SsArgs{ss->targets + (int64_t)b0 * ss->ldt, ss->ldt, ss->p, ss->seed_lo, ss->seed_hi, (uint32_t)(t - L),
+                                  (uint32_t)b0, ss->rows};
             }
         }
         a.gx = w.gx2 + t * B4H + o4; a.ldgx = 4 * (int64_t)H;

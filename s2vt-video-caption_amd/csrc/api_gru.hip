@@ -78,9 +78,7 @@ static int gru_step_fwd_token_impl(int32_t B, int32_t H, int32_t E, int32_t V, c
     a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H; a.b_hh = b_hh;
     a.gx = gx; a.ldgx = 3 * (int64_t)H;
     a.x2 = emb; a.ldx2 = E; a.K2 = E; a.w2 = w_e; a.ldw2 = ldw_e;
-    a.tok_idx = tok; a.tok_packed = tok_packed; a.tok_const = tok_const;
-    a.tok_limit = V; a.tok_err = flags;
-    if (ss) a.ss = *ss;
+    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags, ss ? *ss : SsArgs{}};
     a.h_out = h_out; a.ldho = H;
     {
         ProfScope ps(st, K_STEP_FWD, 1);

@@ -185,8 +185,7 @@ int s2vt_lstm_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const f
     a.B = B; a.H = H;
     a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H;
     a.x2 = emb; a.ldx2 = E; a.K2 = E; a.w2 = w_e; a.ldw2 = ldw_e;
-    a.tok_idx = tok; a.tok_packed = tok_packed; a.tok_const = tok_const;
-    a.tok_limit = V; a.tok_err = flags;
+    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags, {}};
     a.gx = gx; a.ldgx = 4 * (int64_t)H;
     a.c_prev = c_prev; a.ldc = H;
     a.h_out = h_out; a.ldho = H; a.c_out = c_out; a.ldco = H;

@@ -22,7 +22,6 @@ int seq_fwd(hipStream_t st, int t0, int t1, int B, int H, float* gx_stash, int n
         a.h_out = h_all + t * BH; a.ldho = H;
         a.c_out = c_all + t * BH; a.ldco = H;
         a.stash = write_stash ? gx_stash + t * B4H : nullptr; a.ldst = 4 * (int64_t)H;
-        a.tok_const = 0;
         int rc = lstm_step_fwd(st, a);
         if (rc) return rc;
     }

@@ -75,11 +75,11 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
             s.w_in = s.x ? l.w_in : nullptr; s.ldw_in = l.ldw_in;
             if (l.emb) {
                 s.emb = l.emb; s.E = l.E; s.w_e = l.w_e; s.ldw_e = l.ldw_e;
-                s.tok_packed = l.tok_packed; s.tok_const = l.tok_const; s.tok_limit = l.V;
+                s.tok.tok_packed = l.tok_packed; s.tok.tok_const = l.tok_const; s.tok.tok_limit = l.V;
                 if (l.ss_targets) {
-                    s.ss = SsArgs{l.ss_targets, l.ss_ld, l.ss_prob, (uint32_t)(l.ss_seed & 0xFFFFFFFFull), (uint32_t)(l.ss_seed >> 32),
-                                  (uint32_t)l.ss_step, (uint32_t)l.ss_row0, (uint32_t)l.ss_row0 + (uint32_t)B};
-                    s.tok_err = flags;
+                    s.tok.ss = SsArgs{l.ss_targets, l.ss_ld, l.ss_prob, (uint32_t)(l.ss_seed & 0xFFFFFFFFull), (uint32_t)(l.ss_seed >> 32),
+                                      (uint32_t)l.ss_step, (uint32_t)l.ss_row0, (uint32_t)l.ss_row0 + (uint32_t)B};
+                    s.tok.tok_err = flags;
                 }
             }
             s.mask = l.mask ? l.mask + t * BH : nullptr;

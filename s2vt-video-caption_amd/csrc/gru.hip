@@ -16,7 +16,7 @@
 #include <stdlib.h>
 #include "common.h"
 #include "kernels.h"
-#include "mfma_tile.h"
+#include "step_frame.h"
 
 namespace s2vt {
 
@@ -24,50 +24,24 @@ constexpr int GRU_NW = 8;            // waves per workgroup = K-split factor
 constexpr int GRU_TM = 16;           // batch rows per workgroup
 constexpr int GRU_UN = 16;           // hidden units per forward workgroup (3 gate tiles of 16 columns)
 
-// token of batch row b for the embedding segment; ids outside [0, tok_limit) -> token 0 + error flag (as lstm.hip)
-__device__ __forceinline__ int64_t gru_token(const GruFwdArgs& p, int b) {
-    int64_t tok = p.tok_const;
-    bool forced = false;
-    if (p.ss.forced) {       // (wave-uniform: a kernel argument)
-        const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
-        if (forced) tok = t;
-    }
-    if (!forced) {
-        if (p.tok_idx) tok = p.tok_idx[b];
-        else if (p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
-    }
-    if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
-        if (p.tok_err) *p.tok_err = 1;
-        tok = 0;
-    }
-    return tok;
-}
-
 // ------------------------------------------------------------------------------ forward step
 // (two workgroups per CU: 73.7 KB of LDS each, <= 128 VGPRs)
 template <bool VEC, bool TOK>
 __global__ __launch_bounds__(GRU_NW * 64, GRU_NW / 2) void gru_step_fwd_kernel(GruFwdArgs p) {
     constexpr int TM = GRU_TM, UN = GRU_UN, NT = 3, TN = 16 * NT;
-    constexpr int NWAVE = GRU_NW, NTHR = NWAVE * 64;
+    constexpr int NWAVE = GRU_NW;
     // partial tiles: 3 gate tiles (+ the n tile of the token segment); a half-wave of the epilogue reads 2 rows x 16 columns,
     // a row stride of 16 (mod 64) banks puts them on disjoint banks
     constexpr int NP = TOK ? 4 : 3, RLD = 16 * NP + 16;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    static_assert(NWAVE * TM * RLD <= NWAVE * (TM + TN) * SLD, "partial tiles fit the staging area");
-    static_assert(TM * UN <= NTHR, "one epilogue element per thread");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((p.H + UN - 1) / UN, (p.B + TM - 1) / TM, tx, ty)) return;
-    const int b0 = ty * TM, u0 = tx * UN;
-    const int lrow = lane / LPR;
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(1, NT, NWAVE)];
+    static_assert(NWAVE * TM * RLD <= step_lds_floats(1, NT, NWAVE), "partial tiles fit the staging area");
+    StepTile t;
+    if (!step_tile<1, NT, NWAVE, UN>(t, smem, p.H, p.B)) return;
+    const int ebl = t.ebl, eu = t.ecl, eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
 
     // epilogue operands (one output element per thread): requested ahead of the K loop, so that their latency hides behind the
     // contraction - except in the token variant, whose two segments leave no registers for them (loaded after the loop there)
-    const int ebl = tid / UN, eu = tid % UN;
-    const int eb = b0 + ebl, eunit = u0 + eu;
-    const bool evalid = (tid < TM * UN) && (eb < p.B) && (eunit < p.H);
     float gxv[3], bhv[3], hpv;
     auto load_epilogue = [&]() {
         const float* gsrc = p.gx ? p.gx + (int64_t)eb * p.ldgx : p.b_ih;
@@ -87,56 +61,27 @@ __global__ __launch_bounds__(GRU_NW * 64, GRU_NW / 2) void gru_step_fwd_kernel(G
     constexpr int NPF = VEC ? PF : 1;
     constexpr int NPFX = 1;
     f32x4 acc[1][NT][1];
-#pragma unroll
-    for (int ni = 0; ni < NT; ++ni) acc[0][ni][0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
     f32x4 xn = f32x4{0.f, 0.f, 0.f, 0.f};
     if (TOK) {
-        const float* arow[LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.x2 + gru_token(p, b) * p.ldx2 : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < p.H) ? p.w2 + ((int64_t)g * p.H + u) * p.ldw2 : nullptr;
-        }
-        wave_gemm_nt<1, NT, 1, VEC, NWAVE, NPFX>(acc, p.x2, p.w2, arow, brow, p.K2, sA, sB, wave, lane);
+        segment_gate_major<VEC, NWAVE, UN, NPFX>(acc, t, p.x2, [&](int b) { return p.x2 + token_of(p.tok, b) * p.ldx2; }, p.B, p.w2, p.ldw2, p.H, p.K2);
         xn = acc[0][2][0];
         acc[0][2][0] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    if (p.h_prev) {
-        const float* arow[LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.h_prev + (int64_t)b * p.ldh : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < p.H) ? p.w_hh + ((int64_t)g * p.H + u) * p.ldw : nullptr;
-        }
-        wave_gemm_nt<1, NT, 1, VEC, NWAVE, NPF>(acc, p.h_prev, p.w_hh, arow, brow, p.H, sA, sB, wave, lane);
-    }
+    if (p.h_prev) segment_gate_major<VEC, NWAVE, UN, NPF>(acc, t, p.h_prev, DenseRows{p.h_prev, p.ldh}, p.B, p.w_hh, p.ldw, p.H, p.H);
 
     if (TOK) load_epilogue();
-    __syncthreads();
-    float* red = smem;
     if (TOK) {
         f32x4 accw[1][4][1];
         accw[0][0][0] = acc[0][0][0];
         accw[0][1][0] = acc[0][1][0];
         accw[0][2][0] = acc[0][2][0];
         accw[0][3][0] = xn;
-        write_partials<1, 4, 1, RLD>(accw, red, wave, lane);
+        reduce_partials<RLD>(accw, t);
     } else {
-        write_partials<1, NT, 1, RLD>(acc, red, wave, lane);
+        reduce_partials<RLD>(acc, t);
     }
-    __syncthreads();
+    const float* red = t.red;
 
     if (evalid) {
         const float sr = read_sum<1, NP, NWAVE, RLD>(red, ebl, eu);
@@ -163,7 +108,7 @@ int gru_step_fwd(hipStream_t stream, const GruFwdArgs& a) {
     S2VT_REQUIRE(a.B > 0 && a.H > 0 && a.w_hh && a.b_hh && a.h_out && (a.gx || a.b_ih), "gru_step_fwd: bad arguments");
     S2VT_REQUIRE(a.ldh >= a.H && a.ldw >= a.H && a.ldho >= a.H && (!a.gx || a.ldgx >= 3 * (int64_t)a.H) &&
                  (!a.stash || a.ldst >= 4 * (int64_t)a.H), "gru_step_fwd: row stride below the row length");
-    S2VT_REQUIRE(!a.x2 || (a.w2 && a.K2 > 0 && a.ldx2 >= a.K2 && a.ldw2 >= a.K2 && a.tok_limit > 0),
+    S2VT_REQUIRE(!a.x2 || (a.w2 && a.K2 > 0 && a.ldx2 >= a.K2 && a.ldw2 >= a.K2 && a.tok.tok_limit > 0),
                  "gru_step_fwd: a token segment needs W_e, K2 and tok_limit (rows of the table)");
     const bool vec = (!a.h_prev || (vec_ok(a.h_prev, a.ldh) && vec_ok(a.w_hh, a.ldw) && a.H % 4 == 0)) &&
                      (!a.x2 || (vec_ok(a.x2, a.ldx2) && vec_ok(a.w2, a.ldw2) && a.K2 % 4 == 0));
@@ -183,20 +128,12 @@ int gru_step_fwd(hipStream_t stream, const GruFwdArgs& a) {
 template <bool VEC>
 __global__ __launch_bounds__(GRU_NW * 64) void gru_step_bwd_kernel(GruBwdArgs p) {
     constexpr int TM = GRU_TM, TN = 16;
-    constexpr int NWAVE = GRU_NW, NTHR = NWAVE * 64;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    static_assert(TM * TN <= NTHR, "one epilogue element per thread");
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((p.H + TN - 1) / TN, (p.B + TM - 1) / TM, tx, ty)) return;
-    const int b0 = ty * TM, n0 = tx * TN;
-    const int lrow = lane / LPR;
-
-    const int ebl = tid / TN, eul = tid % TN;
-    const int eb = b0 + ebl, eunit = n0 + eul;
-    const bool evalid = (tid < TM * TN) && (eb < p.B) && (eunit < p.H);
+    constexpr int NWAVE = GRU_NW;
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(1, 1, NWAVE)];
+    StepTile t;
+    if (!step_tile<1, 1, NWAVE, TN>(t, smem, p.H, p.B)) return;
+    const int eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
     const bool next = p.dgh_next != nullptr;
     float stv[4], hpv, dhov, dhnv, znv;
     {
@@ -209,26 +146,12 @@ __global__ __launch_bounds__(GRU_NW * 64) void gru_step_bwd_kernel(GruBwdArgs p)
     }
 
     f32x4 acc[1][1][2];
-    acc[0][0][0] = acc[0][0][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (next) {
-        const float* arow[LPT];
-        const float* brow[LPT];
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.dgh_next + (int64_t)b * p.lddgh : nullptr;
-            const int n = n0 + lrow + RPL * i;
-            brow[i] = (n < p.H) ? p.w_hh_t + (int64_t)n * p.ldwt : nullptr;
-        }
-        wave_gemm_nt<1, 1, 2, VEC, NWAVE>(acc, p.dgh_next, p.w_hh_t, arow, brow, 3 * p.H, sA, sB, wave, lane);
-    }
-    __syncthreads();
-    float* red = smem;
-    write_partials<1, 1, 2>(acc, red, wave, lane);
-    __syncthreads();
+    zero_acc(acc);
+    if (next) segment_plain<VEC, NWAVE>(acc, t, p.dgh_next, DenseRows{p.dgh_next, p.lddgh}, p.B, p.w_hh_t, p.ldwt, p.H, 3 * p.H);
+    reduce_partials(acc, t);
 
     if (evalid) {
-        const float dh = read_sum<1, 1, NWAVE>(red, ebl, eul) + dhov + dhnv * znv;
+        const float dh = read_sum<1, 1, NWAVE>(t.red, t.ebl, t.ecl) + dhov + dhnv * znv;
         const float r = stv[0], z = stv[1], n = stv[2], ghn = stv[3];
         const float dn = dh * (1.0f - z);
         const float dz = dh * (hpv - n);

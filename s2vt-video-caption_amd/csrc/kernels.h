@@ -63,9 +63,7 @@ struct StepFwdArgs {
     // segment 2 (optional): x2[row(b), 0:K2] · W2[4H, 0:K2]^T, row(b) = token id (embedding gather)
     const float* x2; int64_t ldx2; int K2;
     const float* w2; int64_t ldw2;
-    const int32_t* tok_idx;                  // int32 token per batch row, or
-    const unsigned long long* tok_packed;    // packed argmax word of the previous decode step, or
-    int tok_const;                           // one token for every row (<sos>); used when both null
+    TokenSrc tok;                            // the token of row b (philox.h)
     // pre-computed gate input (x-part + both biases) per batch row, or bias only
     const float* gx; int64_t ldgx;
     const int32_t* gx_idx;                   // optional: batch row b reads gx row gx_idx[b] (beam search: every beam slot of a sample
@@ -81,17 +79,9 @@ struct StepFwdArgs {
     // split launch in between.  Columns H..kpad of the image must have been zeroed by the caller.
     unsigned short* h_planes; int64_t ldhp;
     // optional: a per-TOKEN gate-input table added to gx in the epilogue, row = the token the x2 segment would gather
-    // (tok_idx / tok_packed / tok_const): gtab[tok][4H] = Emb[tok]·W_e^T computed once per decode call replaces the
+    // (`tok`): gtab[tok][4H] = Emb[tok]·W_e^T computed once per decode call replaces the
     // E-wide second K segment of every decode step (x2 must then be null)
     const float* gx_tab; int64_t ldtab;
-    // guard of the token path (tok_idx / tok_packed / tok_const): an id outside [0, tok_limit) is read as token 0 and raises
-    // *tok_err (the S2VT_ERR_INDEX flag word of the caller's workspace) instead of addressing memory outside the table - a
-    // producer bug (e.g. a packed argmax word that no workgroup wrote) then surfaces as an error code, not as a GPU fault.
-    // tok_limit == 0: no token segment in use
-    int tok_limit; int* tok_err;
-    // optional (scheduled sampling, philox.h): with ss.forced the token of row b is the packed word only where the row's coin
-    // falls below ss.p, the forced ground-truth id otherwise; tok_idx is then not read.  Same guard for a forced id.
-    SsArgs ss;
     // optional: CONTRACTION ONLY - z_out[b][g*H + u] = sum_k h_prev[b][k] W_hh[g*H + u][k] (the reduced partial sums, nothing
     // added) and no cell update: the recurrent half of a decode step that does not depend on the previous step's token, so it
     // runs beside that step's out_linear + argmax; lstm_cell_pointwise() finishes the step (same additions in the same order)
@@ -132,14 +122,10 @@ struct GruFwdArgs {
     // gate input x W_ih^T + b_ih per batch row [B,3H], or b_ih alone for a zero input (gx == nullptr)
     const float* gx; int64_t ldgx;
     const float* b_ih;
-    // optional token segment (greedy decode): Emb[tok(b)]·W_e^T [B,3H] added to the gate input, tokens as in StepFwdArgs
+    // optional token segment (greedy decode): Emb[tok(b)]·W_e^T [B,3H] added to the gate input
     const float* x2; int64_t ldx2; int K2;
     const float* w2; int64_t ldw2;
-    const int32_t* tok_idx;
-    const unsigned long long* tok_packed;
-    int tok_const;
-    int tok_limit; int* tok_err;
-    SsArgs ss;                               // optional scheduled-sampling block, as in StepFwdArgs
+    TokenSrc tok;
     float* h_out; int64_t ldho;
     float* stash; int64_t ldst;              // optional [B,4H]: r, z, n, ghn = h_{t-1} W_hn^T + b_hn (train only)
 };
@@ -172,12 +158,10 @@ struct ChainFwdStep {
     const float* c_prev;                     // [B,H] (NULL: zero state)
     const float* x;                          // [B,H] dense input (the layer below's output at this step), or NULL
     const float* w_in; int64_t ldw_in;       // [4H, K=H] input-weight block of x
-    // token segment (greedy decode): Emb[tok(b)] · W_e^T, tok from the packed argmax word or tok_const; ids outside
-    // [0, tok_limit) read row 0
+    // token segment (greedy decode): Emb[tok(b)] · W_e^T; tok.tok_idx stays null (the chain has no such source)
     const float* emb; int E;
     const float* w_e; int64_t ldw_e;
-    const unsigned long long* tok_packed; int tok_const; int tok_limit;
-    SsArgs ss; int* tok_err;                 // optional scheduled-sampling block, as in StepFwdArgs (a bad forced id raises *tok_err)
+    TokenSrc tok;
     const float* mask;                       // [B,H] dropout mask of this output as the next layer's input (NULL: none)
     float* h_out; float* c_out;              // [B,H]
     float* stash;                            // [B,4H] activated gates i,f,g,o (NULL: not kept)

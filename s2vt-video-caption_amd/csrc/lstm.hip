@@ -21,7 +21,7 @@
 #include "common.h"
 #include "experiment.h"
 #include "kernels.h"
-#include "mfma_tile.h"
+#include "step_frame.h"
 
 namespace s2vt {
 
@@ -50,87 +50,39 @@ __global__ __launch_bounds__(NW_FWD * 64, NW_FWD / 2) void lstm_step_fwd_kernel(
     else lstm_step_fwd_body<MT, NT, VEC>(pb, blockIdx.x - na);
 }
 
-// token of batch row b for the embedding segment / the per-token table; ids outside [0, tok_limit) -> token 0 + error flag
-__device__ __forceinline__ int64_t step_token(const StepFwdArgs& p, int b) {
-    int64_t tok = p.tok_const;
-    bool forced = false;
-    if (p.ss.forced) {       // (wave-uniform: a kernel argument)
-        const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
-        if (forced) tok = t;
-    }
-    if (!forced) {
-        if (p.tok_idx) tok = p.tok_idx[b];
-        else if (p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
-    }
-    if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
-        if (p.tok_err) *p.tok_err = 1;
-        tok = 0;
-    }
-    return tok;
-}
-
 // gates -> (c_t, h_t) and every optional output of a step, for one cell (shared by the fused epilogue and the stand-alone
 // cell kernel: one expression, one rounding sequence)
 __device__ __forceinline__ void step_cell_outputs(const StepFwdArgs& p, int b, int unit, const float (&pre)[4], float cpv) {
-    const float ig = sigmoidf_(pre[0]);
-    const float fg = sigmoidf_(pre[1]);
-    const float gg = tanhf_(pre[2]);
-    const float og = sigmoidf_(pre[3]);
-    const float c = fg * cpv + ig * gg;
-    const float h = og * tanhf_(c);
-    p.h_out[(int64_t)b * p.ldho + unit] = h;
-    if (p.h_out2) p.h_out2[(int64_t)b * p.ldho2 + unit] = h;
-    p.c_out[(int64_t)b * p.ldco + unit] = c;
+    const LstmCell k = lstm_cell(pre, cpv);
+    p.h_out[(int64_t)b * p.ldho + unit] = k.h;
+    if (p.h_out2) p.h_out2[(int64_t)b * p.ldho2 + unit] = k.h;
+    p.c_out[(int64_t)b * p.ldco + unit] = k.c;
     if (p.stash) {
         float* st = p.stash + (int64_t)b * p.ldst + unit;
-        st[0] = ig;
-        st[(int64_t)p.H] = fg;
-        st[(int64_t)2 * p.H] = gg;
-        st[(int64_t)3 * p.H] = og;
+        st[0] = k.i;
+        st[(int64_t)p.H] = k.f;
+        st[(int64_t)2 * p.H] = k.g;
+        st[(int64_t)3 * p.H] = k.o;
     }
-    if (p.h_planes) {
-        // blocked plane layout (split.hip): element (row b, k = unit, plane pl) at
-        //   (b/64)*(64*ld) + (k/16)*3072 + (pl*2 + (k%16)/8)*512 + (b%64)*8 + k%8.
-        // The 8 threads of a row hold the 8 consecutive units u0..u0+7 (u0 % 8 == 0): their 2-byte stores fill one 16-byte
-        // slot, the rows of the tile consecutive slots of the same piece
-        unsigned short pl3[3];
-        split3_bits(h, pl3);
-        unsigned short* q = p.h_planes + (int64_t)(b >> 6) * (64 * p.ldhp) + (int64_t)(unit >> 4) * 3072 +
-                            ((unit >> 3) & 1) * 512 + (b & 63) * 8 + (unit & 7);
-        q[0] = pl3[0];
-        q[1024] = pl3[1];
-        q[2048] = pl3[2];
-    }
+    // the 8 threads of a row hold the 8 consecutive units u0..u0+7 (u0 % 8 == 0): one 16-byte slot of the plane image
+    if (p.h_planes) store_h_planes(p.h_planes, p.ldhp, b, unit, k.h);
 }
 
 template <int MT, int NT, bool VEC>
 __device__ __forceinline__ void lstm_step_fwd_body(const StepFwdArgs& p, int bid) {
     constexpr int TM = 16 * MT, TN = 16 * NT, UN = TN / 4;
-    constexpr int NWAVE = NW_FWD, NTHR = NWAVE * 64;
+    constexpr int NWAVE = NW_FWD;
     constexpr int NA = (MT * NT == 1) ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((p.H + UN - 1) / UN, (p.B + TM - 1) / TM, tx, ty, bid)) return;
-    const int b0 = ty * TM, u0 = tx * UN;
-    const int lrow = lane / LPR;
-
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(MT, NT, NWAVE)];
+    StepTile t;
+    if (!step_tile<MT, NT, NWAVE, UN>(t, smem, p.H, p.B, bid)) return;
+    const int ebl = t.ebl, eu = t.ecl, eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
     f32x4 acc[MT][NT][NA];
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-            for (int a = 0; a < NA; ++a) acc[mi][ni][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // Epilogue operands (gate inputs, c_{t-1}) are requested NOW, ahead of the K loop, so their HBM/MALL latency
     // is hidden behind the contraction instead of being exposed after it (one output element per thread).
-    static_assert(TM * UN <= NTHR, "one epilogue element per thread");
-    const int ebl = tid / UN, eu = tid % UN;
-    const int eb = b0 + ebl, eunit = u0 + eu;
-    const bool evalid = (tid < TM * UN) && (eb < p.B) && (eunit < p.H);
     float gxv[4] = {0.f, 0.f, 0.f, 0.f}, cpv = 0.f;
     if (!p.z_out) {
         const float* gsrc = p.gx ? p.gx + (int64_t)((p.gx_idx && evalid) ? p.gx_idx[eb] : eb) * p.ldgx : p.bias;
@@ -144,55 +96,22 @@ __device__ __forceinline__ void lstm_step_fwd_body(const StepFwdArgs& p, int bid
     }
     float gtv[4] = {0.f, 0.f, 0.f, 0.f};
     if (p.gx_tab && !p.z_out) {       // embedded-word half of the gate input from the per-token table (two dependent loads, behind the K loop)
-        const int64_t tok = evalid ? step_token(p, eb) : 0;
+        const int64_t tok = evalid ? token_of(p.tok, eb) : 0;
         const float* trow = p.gx_tab + tok * p.ldtab;
 #pragma unroll
         for (int g = 0; g < 4; ++g) gtv[g] = *(evalid ? trow + (int64_t)g * p.H + eunit : g_zero4);
     }
 
-    if (p.h_prev) {
-        const float* arow[MT * LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.h_prev + (int64_t)b * p.ldh : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < p.H) ? p.w_hh + ((int64_t)g * p.H + u) * p.ldw : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.h_prev, p.w_hh, arow, brow, p.H, sA, sB, wave, lane);
-    }
-    if (p.x2 && !p.z_out) {
-        const float* arow[MT * LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            if (b < p.B) {
-                arow[i] = p.x2 + step_token(p, b) * p.ldx2;
-            } else {
-                arow[i] = nullptr;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < p.H) ? p.w2 + ((int64_t)g * p.H + u) * p.ldw2 : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.x2, p.w2, arow, brow, p.K2, sA, sB, wave, lane);
-    }
+    if (p.h_prev) segment_gate_major<VEC, NWAVE, UN>(acc, t, p.h_prev, DenseRows{p.h_prev, p.ldh}, p.B, p.w_hh, p.ldw, p.H, p.H);
+    if (p.x2 && !p.z_out)
+        segment_gate_major<VEC, NWAVE, UN>(acc, t, p.x2, [&](int b) { return p.x2 + token_of(p.tok, b) * p.ldx2; }, p.B, p.w2, p.ldw2, p.H, p.K2);
 
     // a half-wave of the epilogue reads 4 rows x UN = 8 consecutive columns per gate: row stride 8 (mod 32) puts the 32
     // lanes on 32 banks (stride 33 put them on 11: 4-way conflicts on each of the 32 reads of a thread)
     constexpr int RLD = TN + 8;
-    static_assert(UN == 8 && NWAVE * TM * RLD <= NWAVE * (TM + TN) * SLD, "partial tiles fit the staging area");
-    __syncthreads();
-    float* red = smem;
-    write_partials<MT, NT, NA, RLD>(acc, red, wave, lane);
-    __syncthreads();
+    static_assert(UN == 8 && NWAVE * TM * RLD <= step_lds_floats(MT, NT, NWAVE), "partial tiles fit the staging area");
+    reduce_partials<RLD>(acc, t);
+    const float* red = t.red;
 
     if (evalid && p.z_out) {           // contraction only: the cell update is lstm_cell_pointwise's
 #pragma unroll
@@ -219,7 +138,7 @@ __global__ __launch_bounds__(256) void lstm_cell_pointwise_kernel(StepFwdArgs p)
     typedef float vec __attribute__((ext_vector_type(NU)));
     const float* gsrc = p.gx ? p.gx + (int64_t)(p.gx_idx ? p.gx_idx[b] : b) * p.ldgx : p.bias;
     const float* zsrc = p.z_out + (int64_t)b * p.ldz + unit;
-    const float* trow = p.gx_tab ? p.gx_tab + step_token(p, b) * p.ldtab + unit : nullptr;
+    const float* trow = p.gx_tab ? p.gx_tab + token_of(p.tok, b) * p.ldtab + unit : nullptr;
     vec zv[4], gxv[4], gtv[4], cpv;
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
@@ -248,7 +167,7 @@ int lstm_step_fwd2(hipStream_t stream, const StepFwdArgs& a, const StepFwdArgs* 
     S2VT_REQUIRE(a.B > 0 && a.H > 0 && ((a.h_out && a.c_out) || a.z_out), "lstm_step_fwd: bad arguments");
     S2VT_REQUIRE(a.gx || a.bias || a.z_out, "lstm_step_fwd: need gx or bias");
     S2VT_REQUIRE(!a.z_out || (a.h_prev && !b && a.ldz >= 4 * (int64_t)a.H), "lstm_step_fwd: a contraction-only step needs h_prev and runs alone");
-    S2VT_REQUIRE(!(a.x2 || a.gx_tab) || a.tok_limit > 0, "lstm_step_fwd: a token segment needs tok_limit (rows of the table)");
+    S2VT_REQUIRE(!(a.x2 || a.gx_tab) || a.tok.tok_limit > 0, "lstm_step_fwd: a token segment needs tok_limit (rows of the table)");
     S2VT_REQUIRE(!b || (b->B == a.B && b->H == a.H && b->h_out && b->c_out && (b->gx || b->bias)),
                  "lstm_step_fwd: paired steps must have the same batch and hidden size");
     // B <= 4: gate GEMVs (lstm_gemv.hip) - measured faster than the 16-row tile up to there (a B = 1 greedy decode 3.07 vs 3.67 ms,
@@ -276,7 +195,7 @@ int lstm_cell_pointwise(hipStream_t stream, const StepFwdArgs& a) {
     S2VT_REQUIRE(a.B > 0 && a.H > 0 && a.h_out && a.c_out && a.z_out && a.ldz >= 4 * (int64_t)a.H, "lstm_cell_pointwise: bad arguments");
     S2VT_REQUIRE(a.gx || a.bias, "lstm_cell_pointwise: need gx or bias");
     S2VT_REQUIRE(!a.x2, "lstm_cell_pointwise: the token segment must be the per-token table (gx_tab), not a second K segment");
-    S2VT_REQUIRE(!a.gx_tab || a.tok_limit > 0, "lstm_cell_pointwise: a token segment needs tok_limit (rows of the table)");
+    S2VT_REQUIRE(!a.gx_tab || a.tok.tok_limit > 0, "lstm_cell_pointwise: a token segment needs tok_limit (rows of the table)");
     const bool v4 = a.H % 4 == 0 && vec_ok(a.z_out, a.ldz) && (!a.gx || vec_ok(a.gx, a.ldgx)) && (!a.bias || vec_ok(a.bias, 4)) &&
                     (!a.gx_tab || vec_ok(a.gx_tab, a.ldtab)) && (!a.c_prev || vec_ok(a.c_prev, a.ldc));
     if (v4) hipLaunchKernelGGL(lstm_cell_pointwise_kernel<4>, dim3((unsigned)cdiv(a.B * (a.H / 4), 256)), dim3(256), 0, stream, a);
@@ -297,31 +216,18 @@ __global__ __launch_bounds__(NW_BWD * 64) void lstm_step_bwd_kernel(StepBwdArgs 
 
 template <int MT, int NT, bool VEC>
 __device__ __forceinline__ void lstm_step_bwd_body(const StepBwdArgs& p, int bid) {
-    constexpr int TM = 16 * MT, TN = 16 * NT;
-    constexpr int NWAVE = NW_BWD, NTHR = NWAVE * 64;
+    constexpr int TN = 16 * NT;
+    constexpr int NWAVE = NW_BWD;
     constexpr int NA = (MT * NT == 1) ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((p.H + TN - 1) / TN, (p.B + TM - 1) / TM, tx, ty, bid)) return;
-    const int b0 = ty * TM, n0 = tx * TN;
-    const int lrow = lane / LPR;
-
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(MT, NT, NWAVE)];
+    StepTile t;
+    if (!step_tile<MT, NT, NWAVE, TN>(t, smem, p.H, p.B, bid)) return;
+    const int eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
     f32x4 acc[MT][NT][NA];
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-            for (int a = 0; a < NA; ++a) acc[mi][ni][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // epilogue operands requested ahead of the K loop (see the forward kernel)
-    static_assert(TM * TN <= NTHR, "one epilogue element per thread");
-    const int ebl = tid / TN, eul = tid % TN;
-    const int eb = b0 + ebl, eunit = n0 + eul;
-    const bool evalid = (tid < TM * TN) && (eb < p.B) && (eunit < p.H);
     float stv[4], cv, cpv, dcv, dhov;
     {
 #pragma unroll
@@ -336,39 +242,16 @@ __device__ __forceinline__ void lstm_step_bwd_body(const StepBwdArgs& p, int bid
         cv = *q1; cpv = *q2; dcv = *q3; dhov = *q4;
     }
 
-    if (p.dg_next) {
-        const float* arow[MT * LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.dg_next + (int64_t)b * p.lddg : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int n = n0 + lrow + RPL * i;
-            brow[i] = (n < p.H) ? p.w_hh_t + (int64_t)n * p.ldwt : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.dg_next, p.w_hh_t, arow, brow, 4 * p.H, sA, sB, wave, lane);
-    }
-    __syncthreads();
-    float* red = smem;
-    write_partials<MT, NT, NA>(acc, red, wave, lane);
-    __syncthreads();
+    if (p.dg_next) segment_plain<VEC, NWAVE>(acc, t, p.dg_next, DenseRows{p.dg_next, p.lddg}, p.B, p.w_hh_t, p.ldwt, p.H, 4 * p.H);
+    reduce_partials(acc, t);
 
     if (evalid) {
-        const int b = eb, unit = eunit;
-        const float dh = read_sum<MT, NT, NWAVE>(red, ebl, eul) + dhov;
-        const float ig = stv[0], fg = stv[1], gg = stv[2], og = stv[3];
-        const float tc = tanhf_(cv);
-        const float dc = dh * og * (1.0f - tc * tc) + dcv;
-        const float d_o = dh * tc;
-        float* dg = p.dg + (int64_t)b * p.lddg_out + unit;
-        dg[0] = dc * gg * ig * (1.0f - ig);
-        dg[(int64_t)p.H] = dc * cpv * fg * (1.0f - fg);
-        dg[(int64_t)2 * p.H] = dc * ig * (1.0f - gg * gg);
-        dg[(int64_t)3 * p.H] = d_o * og * (1.0f - og);
-        p.dc[(int64_t)b * p.lddc + unit] = dc * fg;
+        const float dh = read_sum<MT, NT, NWAVE>(t.red, t.ebl, t.ecl) + dhov;
+        const LstmCellGrad d = lstm_cell_grad(dh, stv, cv, cpv, dcv);
+        float* dg = p.dg + (int64_t)eb * p.lddg_out + eunit;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dg[(int64_t)g * p.H] = d.dg[g];
+        p.dc[(int64_t)eb * p.lddc + eunit] = d.dc_prev;
     }
 }
 
@@ -412,16 +295,12 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgm
     constexpr int TM = 16 * MT, TN = 16 * NT;
     constexpr int NTHR = NWAVE * 64;
     constexpr int NA = (MT * NT == 1) ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((p.V + TN - 1) / TN, (p.B + TM - 1) / TM, tx, ty)) return;
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(MT, NT, NWAVE)];
+    StepTile t;
+    if (!step_tile<MT, NT, NWAVE, TN, false>(t, smem, p.V, p.B)) return;
+    const int tid = t.tid, b0 = t.b0, n0 = t.n0;
     const int xrec = p.stamps ? (int)blockIdx.x : -1;
     XSTAMP(p.stamps, xrec, 0);
-    const int b0 = ty * TM, n0 = tx * TN;
-    const int lrow = lane / LPR;
 
     // epilogue role: 8 threads per batch row, TN/8 columns each; the bias of those columns is requested NOW, ahead of the
     // contraction (in-kernel stamps: fetched in the epilogue it cost every tile ~1.5 us of exposed latency)
@@ -437,32 +316,13 @@ __global__ __launch_bounds__(NWAVE * 64, 4) void logits_argmax_kernel(LogitsArgm
     }
 
     f32x4 acc[MT][NT][NA];
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-            for (int a = 0; a < NA; ++a) acc[mi][ni][a] = f32x4{0.f, 0.f, 0.f, 0.f};
-    {
-        const float* arow[MT * LPT];
-        const float* brow[NT * LPT];
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < p.B) ? p.h + (int64_t)b * p.ldh : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int n = n0 + lrow + RPL * i;
-            brow[i] = (n < p.V) ? p.w_out + (int64_t)n * p.ldw : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.h, p.w_out, arow, brow, p.H, sA, sB, wave, lane);
-    }
+    zero_acc(acc);
+    segment_plain<VEC, NWAVE>(acc, t, p.h, DenseRows{p.h, p.ldh}, p.B, p.w_out, p.ldw, p.V, p.H);
     XSTAMP(p.stamps, xrec, 1);
     __syncthreads();
-    XSTAMP(p.stamps, xrec, 2);
-    float* red = smem;
-    write_partials<MT, NT, NA>(acc, red, wave, lane);
+    XSTAMP(p.stamps, xrec, 2);       // (a stamp inside the reduction: it stays longhand here)
+    float* red = t.red;
+    write_partials<MT, NT, NA>(acc, red, t.wave, t.lane);
     __syncthreads();
     XSTAMP(p.stamps, xrec, 3);
 

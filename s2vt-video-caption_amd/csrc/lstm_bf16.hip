@@ -8,6 +8,7 @@
 // timestep's A operand and, unchanged, the k-major bf16 plane of the batched GEMMs that consume it.
 #include "common.h"
 #include "kernels.h"
+#include "step_frame.h"
 
 namespace s2vt {
 
@@ -181,12 +182,8 @@ __global__ __launch_bounds__(BNT) void lstm_step_fwd_bf16_kernel(StepFwdBf16Args
         float pre[4];
 #pragma unroll
         for (int g = 0; g < 4; ++g) pre[g] = read_sum32<MT, NT>(red, bl, g * UN + u) + gxv[e][g];
-        const float ig = sigmoidf_(pre[0]);
-        const float fg = sigmoidf_(pre[1]);
-        const float gg = tanhf_(pre[2]);
-        const float og = sigmoidf_(pre[3]);
-        const float c = fg * cpv[e] + ig * gg;
-        const float h = og * tanhf_(c);
+        const LstmCell k = lstm_cell(pre, cpv[e]);
+        const float ig = k.i, fg = k.f, gg = k.g, og = k.o, c = k.c, h = k.h;
         if (p.h_out) p.h_out[(int64_t)b * p.ldho + unit] = h;
         p.hb_out[(int64_t)b * p.ldhbo + unit] = f2bf(h);
         p.c_out[(int64_t)b * p.ldco + unit] = c;
@@ -277,12 +274,8 @@ __global__ __launch_bounds__(BNT) void lstm_step_bwd_bf16_kernel(StepBwdBf16Args
         const int b = b0 + bl, unit = n0 + ul;
         if (idx >= TM * TN || b >= p.B || unit >= p.H) continue;
         const float dh = read_sum32<MT, NT>(red, bl, ul) + dhov[e];
-        const float ig = stv[e][0], fg = stv[e][1], gg = stv[e][2], og = stv[e][3];
-        const float tc = tanhf_(cv[e]);
-        const float dc = dh * og * (1.0f - tc * tc) + dcv[e];
-        const float d_o = dh * tc;
-        const float d4[4] = {dc * gg * ig * (1.0f - ig), dc * cpv[e] * fg * (1.0f - fg), dc * ig * (1.0f - gg * gg),
-                             d_o * og * (1.0f - og)};
+        const LstmCellGrad d = lstm_cell_grad(dh, stv[e], cv[e], cpv[e], dcv[e]);
+        const float (&d4)[4] = d.dg;
         float* dg = p.dg + (int64_t)b * p.lddg + unit;
         unsigned short* dgb = p.dgb + (int64_t)b * p.lddgbo + unit;
 #pragma unroll
@@ -290,7 +283,7 @@ __global__ __launch_bounds__(BNT) void lstm_step_bwd_bf16_kernel(StepBwdBf16Args
             dg[(int64_t)g * p.H] = d4[g];
             dgb[(int64_t)g * p.H] = f2bf(d4[g]);
         }
-        p.dc[(int64_t)b * p.lddc + unit] = dc * fg;
+        p.dc[(int64_t)b * p.lddc + unit] = d.dc_prev;
     }
 }
 

@@ -14,6 +14,7 @@
 // additions; the fp32-MFMA tile kernel stays the path of B > 8, of paired steps and of contraction-only steps.
 #include "common.h"
 #include "kernels.h"
+#include "step_frame.h"
 
 namespace s2vt {
 
@@ -48,24 +49,6 @@ __device__ __forceinline__ float wave_reduce_scatter(float (&v)[M], int lane) {
     wave_reduce_scatter_step<M, 4>(v, lane);
     wave_reduce_scatter_step<M, 5>(v, lane);
     return v[0];
-}
-
-__device__ __forceinline__ int64_t gemv_token(const StepFwdArgs& p, int b) {
-    int64_t tok = p.tok_const;
-    bool forced = false;
-    if (p.ss.forced) {       // (wave-uniform: a kernel argument)
-        const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
-        if (forced) tok = t;
-    }
-    if (!forced) {
-        if (p.tok_idx) tok = p.tok_idx[b];
-        else if (p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
-    }
-    if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
-        if (p.tok_err) *p.tok_err = 1;
-        tok = 0;
-    }
-    return tok;
 }
 
 constexpr int GV_UNITS = 4;            // hidden units (= waves) per workgroup
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(64 * GV_UNITS) void lstm_step_fwd_gemv_kernel(StepF
     if (p.x2) {
         for (int i = tid; i < NB * (xld >> 2); i += 64 * GV_UNITS) {
             const int b = i / (xld >> 2), k = (i % (xld >> 2)) * 4;
-            const float* row = b < p.B ? p.x2 + gemv_token(p, b) * p.ldx2 + k : g_zero4;
+            const float* row = b < p.B ? p.x2 + token_of(p.tok, b) * p.ldx2 + k : g_zero4;
             *reinterpret_cast<f32x4*>(xs + b * xld + k) = *reinterpret_cast<const f32x4*>(row);
         }
     }
@@ -137,7 +120,7 @@ __global__ __launch_bounds__(64 * GV_UNITS) void lstm_step_fwd_gemv_kernel(StepF
         for (int g = 0; g < 4; ++g) gxv[g] = *((evalid && gsrc) ? gsrc + (int64_t)g * H + un : g_zero4);
         cpv = *((evalid && p.c_prev) ? p.c_prev + (int64_t)eb * p.ldc + un : g_zero4);
         if (p.gx_tab) {
-            const int64_t tok = evalid ? gemv_token(p, eb) : 0;
+            const int64_t tok = evalid ? token_of(p.tok, eb) : 0;
             const float* trow = p.gx_tab + tok * p.ldtab;
 #pragma unroll
             for (int g = 0; g < 4; ++g) gtv[g] = *(evalid ? trow + (int64_t)g * H + un : g_zero4);
@@ -170,24 +153,15 @@ __global__ __launch_bounds__(64 * GV_UNITS) void lstm_step_fwd_gemv_kernel(StepF
     if (!evalid) return;
 #pragma unroll
     for (int g = 0; g < 4; ++g) pre[g] = pre[g] + gxv[g] + gtv[g];
-    // cell (lstm.hip::step_cell_outputs: one expression, one rounding sequence)
-    const float ig = sigmoidf_(pre[0]), fg = sigmoidf_(pre[1]), gg = tanhf_(pre[2]), og = sigmoidf_(pre[3]);
-    const float c = fg * cpv + ig * gg;
-    const float h = og * tanhf_(c);
-    p.h_out[(int64_t)eb * p.ldho + unit] = h;
-    if (p.h_out2) p.h_out2[(int64_t)eb * p.ldho2 + unit] = h;
-    p.c_out[(int64_t)eb * p.ldco + unit] = c;
+    const LstmCell k = lstm_cell(pre, cpv);
+    p.h_out[(int64_t)eb * p.ldho + unit] = k.h;
+    if (p.h_out2) p.h_out2[(int64_t)eb * p.ldho2 + unit] = k.h;
+    p.c_out[(int64_t)eb * p.ldco + unit] = k.c;
     if (p.stash) {
         float* st = p.stash + (int64_t)eb * p.ldst + unit;
-        st[0] = ig; st[(int64_t)H] = fg; st[(int64_t)2 * H] = gg; st[(int64_t)3 * H] = og;
+        st[0] = k.i; st[(int64_t)H] = k.f; st[(int64_t)2 * H] = k.g; st[(int64_t)3 * H] = k.o;
     }
-    if (p.h_planes) {       // blocked plane layout (split.hip), as lstm.hip writes it
-        unsigned short pl3[3];
-        split3_bits(h, pl3);
-        unsigned short* q = p.h_planes + (int64_t)(eb >> 6) * (64 * p.ldhp) + (int64_t)(unit >> 4) * 3072 + ((unit >> 3) & 1) * 512 +
-                            (eb & 63) * 8 + (unit & 7);
-        q[0] = pl3[0]; q[1024] = pl3[1]; q[2048] = pl3[2];
-    }
+    if (p.h_planes) store_h_planes(p.h_planes, p.ldhp, eb, unit, k.h);
 }
 
 // the shapes this kernel takes (everything else: the MFMA tile kernel of lstm.hip)
@@ -199,7 +173,7 @@ bool lstm_step_fwd_gemv_ok(const StepFwdArgs& a) {
 
 int lstm_step_fwd_gemv(hipStream_t stream, const StepFwdArgs& a) {
     S2VT_REQUIRE(lstm_step_fwd_gemv_ok(a) && a.h_out && a.c_out && (a.gx || a.bias), "lstm_step_fwd_gemv: unsupported shape / arguments");
-    S2VT_REQUIRE(!(a.x2 || a.gx_tab) || a.tok_limit > 0, "lstm_step_fwd_gemv: a token segment needs tok_limit (rows of the table)");
+    S2VT_REQUIRE(!(a.x2 || a.gx_tab) || a.tok.tok_limit > 0, "lstm_step_fwd_gemv: a token segment needs tok_limit (rows of the table)");
     const int nb = a.B <= 1 ? 1 : a.B <= 2 ? 2 : a.B <= 4 ? 4 : 8;
     const size_t lds = (size_t)nb * (((a.H + 3) & ~3) + (a.x2 ? ((a.K2 + 3) & ~3) : 0)) * sizeof(float);
     const dim3 grid((unsigned)cdiv(a.H, GV_UNITS)), block(64 * GV_UNITS);

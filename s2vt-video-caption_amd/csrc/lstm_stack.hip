@@ -15,44 +15,28 @@
 //             them (exact by linearity; one accumulator set).
 #include "common.h"
 #include "kernels.h"
-#include "mfma_tile.h"
+#include "step_frame.h"
 
 namespace s2vt {
 
 constexpr int NW_CHAIN = 8;      // waves per workgroup (K split), as the one-layer kernels
-
-__device__ __forceinline__ float chain_sigmoid(float x) { return 1.0f / (1.0f + __expf(-x)); }
-__device__ __forceinline__ float chain_tanh(float x) { return 1.0f - 2.0f / (1.0f + __expf(2.0f * x)); }
 
 // ------------------------------------------------------------------------------ forward diagonal
 template <int MT, bool VEC>
 __device__ __forceinline__ void chain_fwd_body(const ChainFwdStep& p, int B, int H, int bid) {
     constexpr int NT = 2;
     constexpr int TM = 16 * MT, TN = 16 * NT, UN = TN / 4;
-    constexpr int NWAVE = NW_CHAIN, NTHR = NWAVE * 64;
+    constexpr int NWAVE = NW_CHAIN;
     constexpr int NA = (MT * NT == 1) ? 2 : 1;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((H + UN - 1) / UN, (B + TM - 1) / TM, tx, ty, bid)) return;
-    const int b0 = ty * TM, u0 = tx * UN;
-    const int lrow = lane / LPR;
-
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(MT, NT, NWAVE)];
+    StepTile t;
+    if (!step_tile<MT, NT, NWAVE, UN>(t, smem, H, B, bid)) return;
+    const int ebl = t.ebl, eu = t.ecl, eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
     f32x4 acc[MT][NT][NA];
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-#pragma unroll
-            for (int a = 0; a < NA; ++a) acc[mi][ni][a] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
     // epilogue operands requested ahead of the K loop (one output cell per thread)
-    static_assert(TM * UN <= NTHR, "one epilogue element per thread");
-    const int ebl = tid / UN, eu = tid % UN;
-    const int eb = b0 + ebl, eunit = u0 + eu;
-    const bool evalid = (tid < TM * UN) && (eb < B) && (eunit < H);
     float gxv[4], cpv, mv;
     {
         const float* gsrc = p.gx ? p.gx + (int64_t)eb * 4 * H : p.bias;
@@ -62,86 +46,32 @@ __device__ __forceinline__ void chain_fwd_body(const ChainFwdStep& p, int B, int
         mv = *((evalid && p.mask) ? p.mask + (int64_t)eb * H + eunit : g_zero4);
     }
 
-    const float* arow[MT * LPT];
-    const float* brow[NT * LPT];
-    if (p.h_prev) {     // recurrent segment h_{t-1} · W_hh^T
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < B) ? p.h_prev + (int64_t)b * H : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < H) ? p.w_hh + ((int64_t)g * H + u) * H : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.h_prev, p.w_hh, arow, brow, H, sA, sB, wave, lane);
-    }
-    if (p.x) {          // dense input segment x_t · W_in^T (the layer below's output at the same step)
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            arow[i] = (b < B) ? p.x + (int64_t)b * H : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < H) ? p.w_in + ((int64_t)g * H + u) * p.ldw_in : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.x, p.w_in, arow, brow, H, sA, sB, wave, lane);
-    }
-    if (p.emb) {        // token segment Emb[tok] · W_e^T (greedy decode); an id outside [0, tok_limit) reads row 0
-#pragma unroll
-        for (int i = 0; i < MT * LPT; ++i) {
-            const int b = b0 + lrow + RPL * i;
-            int64_t tok = p.tok_const;
-            bool forced = false;
-            if (b < B && p.ss.forced) {       // scheduled sampling (wave-uniform on the argument): the coin picks the word
-                const int64_t t = ss_token(p.ss, p.tok_packed, b, &forced);
-                if (forced) tok = t;
-            }
-            if (!forced && b < B && p.tok_packed) tok = (int64_t)(0xFFFFFFFFu - (uint32_t)(p.tok_packed[b] & 0xFFFFFFFFull));
-            if ((uint64_t)tok >= (uint64_t)(int64_t)p.tok_limit) {
-                if (p.tok_err) *p.tok_err = 1;
-                tok = 0;
-            }
-            arow[i] = (b < B) ? p.emb + tok * p.E : nullptr;
-        }
-#pragma unroll
-        for (int i = 0; i < NT * LPT; ++i) {
-            const int r = lrow + RPL * i, g = r / UN, u = u0 + r % UN;
-            brow[i] = (u < H) ? p.w_e + ((int64_t)g * H + u) * p.ldw_e : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.emb, p.w_e, arow, brow, p.E, sA, sB, wave, lane);
-    }
+    // recurrent segment h_{t-1} · W_hh^T, dense input segment x_t · W_in^T (the layer below's output at the same step),
+    // token segment Emb[tok] · W_e^T (greedy decode)
+    if (p.h_prev) segment_gate_major<VEC, NWAVE, UN>(acc, t, p.h_prev, DenseRows{p.h_prev, H}, B, p.w_hh, H, H, H);
+    if (p.x) segment_gate_major<VEC, NWAVE, UN>(acc, t, p.x, DenseRows{p.x, H}, B, p.w_in, p.ldw_in, H, H);
+    if (p.emb)
+        segment_gate_major<VEC, NWAVE, UN>(acc, t, p.emb, [&](int b) { return p.emb + token_of(p.tok, b) * p.E; }, B, p.w_e, p.ldw_e, H, p.E);
 
     constexpr int RLD = TN + 8;      // conflict-free epilogue reads (see lstm.hip)
-    static_assert(UN == 8 && NWAVE * TM * RLD <= NWAVE * (TM + TN) * SLD, "partial tiles fit the staging area");
-    __syncthreads();
-    float* red = smem;
-    write_partials<MT, NT, NA, RLD>(acc, red, wave, lane);
-    __syncthreads();
+    static_assert(UN == 8 && NWAVE * TM * RLD <= step_lds_floats(MT, NT, NWAVE), "partial tiles fit the staging area");
+    reduce_partials<RLD>(acc, t);
 
     if (evalid) {
         float pre[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) pre[g] = read_sum<MT, NT, NWAVE, RLD>(red, ebl, g * UN + eu) + gxv[g];
-        const float ig = chain_sigmoid(pre[0]);
-        const float fg = chain_sigmoid(pre[1]);
-        const float gg = chain_tanh(pre[2]);
-        const float og = chain_sigmoid(pre[3]);
-        const float c = fg * cpv + ig * gg;
-        const float h = og * chain_tanh(c);
+        for (int g = 0; g < 4; ++g) pre[g] = read_sum<MT, NT, NWAVE, RLD>(t.red, ebl, g * UN + eu) + gxv[g];
+        const LstmCell k = lstm_cell(pre, cpv);
         const int64_t o = (int64_t)eb * H + eunit;
-        p.h_out[o] = h;
-        p.c_out[o] = c;
-        if (p.hm_out) p.hm_out[o] = mv * h;
+        p.h_out[o] = k.h;
+        p.c_out[o] = k.c;
+        if (p.hm_out) p.hm_out[o] = mv * k.h;
         if (p.stash) {
             float* st = p.stash + (int64_t)eb * 4 * H + eunit;
-            st[0] = ig;
-            st[(int64_t)H] = fg;
-            st[(int64_t)2 * H] = gg;
-            st[(int64_t)3 * H] = og;
+            st[0] = k.i;
+            st[(int64_t)H] = k.f;
+            st[(int64_t)2 * H] = k.g;
+            st[(int64_t)3 * H] = k.o;
         }
     }
 }
@@ -161,7 +91,7 @@ int lstm_chain_fwd_launch(hipStream_t stream, const ChainFwdLaunch& a) {
     for (int i = 0; i < a.n; ++i) {
         const ChainFwdStep& s = a.s[i];
         S2VT_REQUIRE(s.h_out && s.c_out && (s.gx || s.bias) && s.w_hh && (!s.x || s.w_in) && (!s.mask || s.hm_out) &&
-                     (!s.emb || (s.w_e && s.E > 0 && s.tok_limit > 0)), "lstm_chain_fwd: bad layer-step");
+                     (!s.emb || (s.w_e && s.E > 0 && s.tok.tok_limit > 0)), "lstm_chain_fwd: bad layer-step");
         vec = vec && vec_rows(s.h_prev, a.H) && vec_rows(s.w_hh, a.H) && vec_rows(s.x, a.H) && vec_rows(s.w_in, s.ldw_in) &&
               (!s.emb || (s.E % 4 == 0 && vec_ok(s.emb, s.E) && vec_ok(s.w_e, s.ldw_e)));
     }
@@ -185,26 +115,17 @@ int lstm_chain_fwd_launch(hipStream_t stream, const ChainFwdLaunch& a) {
 template <bool VEC>
 __device__ __forceinline__ void chain_bwd_body(const ChainBwdStep& p, int B, int H, int bid) {
     constexpr int MT = 1, NT = 1;
-    constexpr int TM = 16 * MT, TN = 16 * NT;
-    constexpr int NWAVE = NW_CHAIN, NTHR = NWAVE * 64;
+    constexpr int TN = 16 * NT;
+    constexpr int NWAVE = NW_CHAIN;
     constexpr int NA = 2;
-    __shared__ __attribute__((aligned(16))) float smem[NWAVE * (TM + TN) * SLD];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float* sA = smem + wave * (TM + TN) * SLD;
-    float* sB = sA + TM * SLD;
-    int tx, ty;
-    if (!xcd_tile((H + TN - 1) / TN, (B + TM - 1) / TM, tx, ty, bid)) return;
-    const int b0 = ty * TM, n0 = tx * TN;
-    const int lrow = lane / LPR;
-
+    __shared__ __attribute__((aligned(16))) float smem[step_lds_floats(MT, NT, NWAVE)];
+    StepTile t;
+    if (!step_tile<MT, NT, NWAVE, TN>(t, smem, H, B, bid)) return;
+    const int eb = t.eb, eunit = t.ecol;
+    const bool evalid = t.evalid;
     f32x4 acc[MT][NT][NA];
-    acc[0][0][0] = f32x4{0.f, 0.f, 0.f, 0.f};
-    acc[0][0][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    zero_acc(acc);
 
-    static_assert(TM * TN <= NTHR, "one epilogue element per thread");
-    const int ebl = tid / TN, eul = tid % TN;
-    const int eb = b0 + ebl, eunit = n0 + eul;
-    const bool evalid = (tid < TM * TN) && (eb < B) && (eunit < H);
     float stv[4], cv, cpv, dcv, dhv;
     {
         const int64_t o = (int64_t)eb * H + eunit;
@@ -216,54 +137,30 @@ __device__ __forceinline__ void chain_bwd_body(const ChainBwdStep& p, int B, int
         dhv = *((evalid && p.dh_ext) ? p.dh_ext + o : g_zero4);
     }
 
-    const float* arow[LPT];
-    const float* brow[LPT];
+    const int64_t H4 = 4 * (int64_t)H;
     if (p.dg_up) {      // m ⊙ (dG^{up}_t · W_in^{up}): first, so that the mask scales this segment alone
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int b = b0 + lrow + RPL * i, n = n0 + lrow + RPL * i;
-            arow[i] = (b < B) ? p.dg_up + (int64_t)b * 4 * H : nullptr;
-            brow[i] = (n < H) ? p.w_in_t + (int64_t)n * 4 * H : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.dg_up, p.w_in_t, arow, brow, 4 * H, sA, sB, wave, lane);
+        segment_plain<VEC, NWAVE>(acc, t, p.dg_up, DenseRows{p.dg_up, H4}, B, p.w_in_t, H4, H, 4 * H);
         if (p.mask) {   // 16x16 C layout: col = lane & 15, row = 4 (lane >> 4) + r
-            const int col = n0 + (lane & 15);
+            const int col = t.n0 + (t.lane & 15);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int row = b0 + 4 * (lane >> 4) + r;
+                const int row = t.b0 + 4 * (t.lane >> 4) + r;
                 const float m = *((row < B && col < H) ? p.mask + (int64_t)row * H + col : g_zero4);
                 acc[0][0][0][r] *= m;
                 acc[0][0][1][r] *= m;
             }
         }
     }
-    if (p.dg_next) {    // dG_{t+1} · W_hh
-#pragma unroll
-        for (int i = 0; i < LPT; ++i) {
-            const int b = b0 + lrow + RPL * i, n = n0 + lrow + RPL * i;
-            arow[i] = (b < B) ? p.dg_next + (int64_t)b * 4 * H : nullptr;
-            brow[i] = (n < H) ? p.w_hh_t + (int64_t)n * 4 * H : nullptr;
-        }
-        wave_gemm_nt<MT, NT, NA, VEC, NWAVE>(acc, p.dg_next, p.w_hh_t, arow, brow, 4 * H, sA, sB, wave, lane);
-    }
-    __syncthreads();
-    float* red = smem;
-    write_partials<MT, NT, NA>(acc, red, wave, lane);
-    __syncthreads();
+    if (p.dg_next) segment_plain<VEC, NWAVE>(acc, t, p.dg_next, DenseRows{p.dg_next, H4}, B, p.w_hh_t, H4, H, 4 * H);   // dG_{t+1} · W_hh
+    reduce_partials(acc, t);
 
     if (evalid) {
-        const int64_t o = (int64_t)eb * H + eunit;
-        const float dh = read_sum<MT, NT, NWAVE>(red, ebl, eul) + dhv;
-        const float ig = stv[0], fg = stv[1], gg = stv[2], og = stv[3];
-        const float tc = chain_tanh(cv);
-        const float dc = dh * og * (1.0f - tc * tc) + dcv;
-        const float d_o = dh * tc;
+        const float dh = read_sum<MT, NT, NWAVE>(t.red, t.ebl, t.ecl) + dhv;
+        const LstmCellGrad d = lstm_cell_grad(dh, stv, cv, cpv, dcv);
         float* dg = p.dg + (int64_t)eb * 4 * H + eunit;
-        dg[0] = dc * gg * ig * (1.0f - ig);
-        dg[(int64_t)H] = dc * cpv * fg * (1.0f - fg);
-        dg[(int64_t)2 * H] = dc * ig * (1.0f - gg * gg);
-        dg[(int64_t)3 * H] = d_o * og * (1.0f - og);
-        p.dc[o] = dc * fg;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) dg[(int64_t)g * H] = d.dg[g];
+        p.dc[(int64_t)eb * H + eunit] = d.dc_prev;
     }
 }
 

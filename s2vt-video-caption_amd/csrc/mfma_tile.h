@@ -1,4 +1,5 @@
-// The fp32 MFMA tile machinery of the launch-per-timestep recurrence kernels (lstm.hip, gru.hip): guarded 16-byte staging
+// The fp32 MFMA tile machinery of the launch-per-timestep recurrence kernels (lstm.hip, gru.hip, lstm_stack.hip, through the
+// frame of step_frame.h): guarded 16-byte staging
 // loads, the K-split wave contraction on v_mfma_f32_16x16x4_f32 with a register prefetch, the fixed-order reduction of the
 // waves' partial tiles through LDS, and the XCD-aware workgroup placement.
 #pragma once

@@ -88,12 +88,47 @@ __host__ __device__ __forceinline__ int64_t packed_token(unsigned long long w) {
 
 // The token a scheduled step feeds row b of its launch: `packed` = the previous step's packed words of the launch's rows (null
 // at step 0).  *has = false for a padding row (the caller keeps its own rule there).
-__device__ __forceinline__ int64_t ss_token(const SsArgs& s, const unsigned long long* packed, int b, bool* has) {
+__host__ __device__ __forceinline__ int64_t ss_token(const SsArgs& s, const unsigned long long* packed, int b, bool* has) {
     const uint32_t row = s.row0 + (uint32_t)b;
     *has = row < s.rows;
     if (!*has) return 0;
     if (packed && s.step > 0 && ss_coin(s.seed_lo, s.seed_hi, row, s.step) < s.p) return packed_token(packed[b]);
     return s.forced[(int64_t)b * s.ld + s.step];
+}
+
+// ---- where a token step (an embedding K segment or a per-token gate-input table: lstm.hip, lstm_gemv.hip, gru.hip,
+// lstm_stack.hip) takes the word of batch row b from
+struct TokenSrc {
+    const int32_t* tok_idx;                  // int32 token per batch row, or
+    const unsigned long long* tok_packed;    // packed argmax word of the previous decode step, or
+    int tok_const;                           // one token for every row (<sos>); used when both null
+    // guard of the token path (tok_idx / tok_packed / tok_const): an id outside [0, tok_limit) is read as token 0 and raises
+    // *tok_err (the S2VT_ERR_INDEX flag word of the caller's workspace) instead of addressing memory outside the table - a
+    // producer bug (e.g. a packed argmax word that no workgroup wrote) then surfaces as an error code, not as a GPU fault.
+    // tok_limit == 0: no token segment in use
+    int tok_limit; int* tok_err;
+    // optional (scheduled sampling): with ss.forced the token of row b is the packed word only where the row's coin falls below
+    // ss.p, the forced ground-truth id otherwise; tok_idx is then not read.  Same guard for a forced id.
+    SsArgs ss;
+};
+
+// the token of row b of the launch (b inside the launch's batch: the caller guards)
+__host__ __device__ __forceinline__ int64_t token_of(const TokenSrc& s, int b) {
+    int64_t tok = s.tok_const;
+    bool forced = false;
+    if (s.ss.forced) {       // (wave-uniform: a kernel argument)
+        const int64_t t = ss_token(s.ss, s.tok_packed, b, &forced);
+        if (forced) tok = t;
+    }
+    if (!forced) {
+        if (s.tok_idx) tok = s.tok_idx[b];
+        else if (s.tok_packed) tok = packed_token(s.tok_packed[b]);
+    }
+    if ((uint64_t)tok >= (uint64_t)(int64_t)s.tok_limit) {
+        if (s.tok_err) *s.tok_err = 1;
+        tok = 0;
+    }
+    return tok;
 }
 
 }  // namespace s2vt

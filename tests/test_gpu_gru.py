@@ -45,8 +45,8 @@ def _close(got, ref, what):
     assert err <= 1e-5 * max(ref.abs().max().item(), 1e-30), (what, err, ref.abs().max().item())
 
 
-@pytest.mark.parametrize("B", [4, 10, 16, 64])
-@pytest.mark.parametrize("H", [30, 32, 512, 1000])
+@pytest.mark.parametrize("B", [4, 10, 16, 17, 33, 64])
+@pytest.mark.parametrize("H", [30, 32, 36, 512, 1000])      # H = 36: 2 K chunks for 8 waves
 def test_gru_step_kernels_against_fp64_cell(lib, B, H):
     """Forward (zero state / given state, with and without the token segment) and the BPTT step against the fp64 cell and
     its autograd.  H = 30 with E = 26 (rows not a multiple of 4 floats) runs the scalar-load kernels, the other sizes the

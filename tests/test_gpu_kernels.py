@@ -294,9 +294,11 @@ def test_split_precision_gemm_is_exact_on_integers(lib):
 
 
 @pytest.mark.parametrize("B,H", [(1, 32), (4, 500), (33, 40), (64, 1000), (16, 8), (17, 36), (8, 1000), (5, 1000), (2, 1500),
-                                 (3, 30)])
+                                 (3, 30), (33, 36)])
 def test_lstm_step_fwd_matches_cell(lib, B, H):
-    """Batches from 1 to 64, including the small batches (B <= 8) of the reference's plumbing configuration and of decode."""
+    """Batches from 1 to 64, including the small batches (B <= 8) of the reference's plumbing configuration and of decode.
+    H = 36 is 2 K chunks of 32 for the 8 waves of a workgroup (six waves contract nothing): with B = 17 on the 16-row tile, with
+    B = 33 on the 32-row tile whose second row block is ragged."""
     from s2vt_video_caption_amd import ops
     k = 1.0 / H ** 0.5
     w_hh = (torch.rand(4 * H, H, generator=torch.Generator().manual_seed(1)) * 2 - 1) * k
@@ -415,8 +417,99 @@ def test_decode_step_token_segment_and_poisoned_token_word(lib):
     assert torch.equal(h4, h)
 
 
-@pytest.mark.parametrize("B,H", [(3, 32), (20, 100), (64, 500)])
+def _token_step(kernel, src, lib, d, V, E, H, B):
+    """h of one token step of `kernel` fed by `src` = dict(tok_const=..) | dict(tok_packed=..) | dict(ss=(targets, p, seed, step),
+    tok_packed=..); the LSTM cells start from (hp, cp) with the 4H gate input, the GRU from hp with the first 3H columns."""
+    from s2vt_video_caption_amd import ops
+    if kernel in ("lstm_tile", "lstm_gemv"):
+        prev = lib.s2vt_set_option(b"gemv", -1)
+        try:
+            lib.s2vt_set_option(b"gemv", 1 if kernel == "lstm_gemv" else 0)      # (1: B <= 4 takes the gate GEMVs)
+            return ops.lstm_step_fwd_token(d["gx"], d["w_hh"], d["hp"], d["cp"], d["emb"], d["w_ih"], **src)[0]
+        finally:
+            lib.s2vt_set_option(b"gemv", prev)
+    if kernel == "gru":
+        return ops.gru_step_fwd_token(d["gx"][:, :3 * H].contiguous(), d["w_hh"][:3 * H], d["bias"][:3 * H], d["hp"], d["emb"],
+                                      d["w_ih"][:3 * H], **src)
+    lay = dict(w_hh=d["w_hh"], bias=d["bias"], h0=d["hp"], c0=d["cp"], h=torch.empty(B, H, device=DEV), c=torch.empty(B, H, device=DEV),
+               emb=d["emb"], w_e=d["w_ih"], E=E, V=V, tok_const=src.get("tok_const", 0), tok_packed=src.get("tok_packed"), ss=src.get("ss"))
+    ops.lstm_chain_fwd(1, B, H, [lay])
+    return lay["h"]
+
+
+@pytest.mark.parametrize("kernel,source", [(k, s) for k in ("lstm_tile", "lstm_gemv", "gru", "chain")
+                                           for s in ("tok_const", "tok_packed", "ss_p0", "ss_p1") if not (k.startswith("lstm") and s.startswith("ss"))])
+def test_every_token_kernel_feeds_the_same_word(lib, kernel, source):
+    """The one token rule (token_of) in each kernel that gathers an embedding row: the tile and the GEMV LSTM step, the GRU token
+    step and a one-layer-step chain launch must feed the word sampling.py's numpy restatement names - the constant, the packed
+    arg-max word, and under scheduled sampling targets[:, step] at p = 0, the packed word at p = 1 - and read row 0 for a poisoned
+    packed word or an out-of-range forced target.  The index flag: the LSTM step posts it for every source; the GRU step and the
+    chain post it for the ids of a caller (the forced targets), a packed word is the arg-max kernel's own there.  The LSTM step
+    entry point has no scheduled form (its scheduled pass is the decode driver's, tests/test_gpu_scheduled.py): those cells do
+    not exist.  Against the fp64 cells at the siblings' tolerances (absolute 2e-6 for the tile LSTM step, 4e-6 for the GEMV one, 1e-5 relative
+    otherwise)."""
+    from s2vt_video_caption_amd import capi, sampling
+    V, E, H, B, step, seed = 50, 40, 64, 3, 2, 11
+    t = {n: _r(*shape, seed=i + 1, scale=sc) for i, (n, shape, sc) in enumerate(
+        [("gx", (B, 4 * H), 1.0), ("w_hh", (4 * H, H), H ** -0.5), ("w_ih", (4 * H, E + H), (E + H) ** -0.5), ("emb", (V, E), 1.0),
+         ("hp", (B, H), 0.5), ("cp", (B, H), 0.5), ("bias", (4 * H,), 0.3)])}
+    d = {n: x.to(DEV) for n, x in t.items()}
+    g = torch.Generator().manual_seed(5)
+    draws = torch.randint(1, V, (B,), generator=g)
+    targets = torch.randint(1, V, (B, 4), generator=g)
+    packed = ((torch.arange(B, dtype=torch.int64) + 77) << 32) | (0xFFFFFFFF - draws)
+
+    def ref(tok):
+        D = {n: x.double() for n, x in t.items()}
+        e = D["emb"][tok] @ D["w_ih"][:, :E].t()
+        if kernel == "gru":
+            W, bh = D["w_hh"][:3 * H], D["bias"][:3 * H]
+            xg, gh = D["gx"][:, :3 * H] + e[:, :3 * H], D["hp"] @ W.t() + bh
+            r, z = torch.sigmoid(xg[:, :H] + gh[:, :H]), torch.sigmoid(xg[:, H:2 * H] + gh[:, H:2 * H])
+            n = torch.tanh(xg[:, 2 * H:] + r * gh[:, 2 * H:])
+            return n + z * (D["hp"] - n)
+        pre = (D["gx"] if kernel != "chain" else D["bias"]) + D["hp"] @ D["w_hh"].t() + e
+        i, f, gg, o = pre.chunk(4, dim=1)
+        return torch.sigmoid(o) * torch.tanh(torch.sigmoid(f) * D["cp"] + torch.sigmoid(i) * torch.tanh(gg))
+
+    def check(src, tok, raises):
+        capi.check_async_error()
+        h = _token_step(kernel, src, lib, d, V, E, H, B)
+        torch.cuda.synchronize()
+        if raises:
+            with pytest.raises(IndexError):
+                capi.check_async_error()
+        else:
+            capi.check_async_error()
+        want = ref(tok)
+        err = (h.cpu().double() - want).abs().max().item()
+        print(kernel, source, "max |h - fp64| = %.3g" % err)
+        assert err < {"lstm_tile": 2e-6, "lstm_gemv": 4e-6}.get(kernel, 1e-5 * want.abs().max().item())
+
+    posts_all = kernel.startswith("lstm")
+    row0 = lambda tok: torch.cat([tok[:1], torch.zeros(1, dtype=torch.int64), tok[2:]])
+    if source == "tok_const":
+        check(dict(tok_const=9), torch.full((B,), 9), False)
+    elif source == "tok_packed":
+        check(dict(tok_packed=packed.to(DEV)), draws, False)
+        poisoned = packed.clone()
+        poisoned[1] = 0                                  # a word no producer wrote: token 0xFFFFFFFF
+        check(dict(tok_packed=poisoned.to(DEV)), row0(draws), posts_all)
+    else:
+        p = 0.0 if source == "ss_p0" else 1.0
+        used = torch.from_numpy(sampling.ss_used(targets.numpy(), draws.numpy()[:, None].repeat(4, 1), p, seed))[:, step]
+        assert torch.equal(used, targets[:, step] if p == 0.0 else draws)
+        check(dict(ss=(targets.to(DEV), p, seed, step), tok_packed=packed.to(DEV)), used, False)
+        if p == 0.0:
+            bad = targets.clone()
+            bad[1, step] = V                             # an out-of-range forced target
+            check(dict(ss=(bad.to(DEV), p, seed, step), tok_packed=packed.to(DEV)), row0(targets[:, step]), True)
+
+
+@pytest.mark.parametrize("B,H", [(3, 32), (20, 100), (64, 500), (256, 480), (224, 480)])
 def test_lstm_step_bwd_matches_autograd(lib, B, H):
+    """(256, 480) and (224, 480): the two sides of the launcher's tile choice - 30 x 8 = 240 tiles of 32 rows take the 32-row
+    tile, 30 x 7 = 210 stay on the 16-row one."""
     from s2vt_video_caption_amd import ops
     k = 1.0 / H ** 0.5
     w_hh = ((torch.rand(4 * H, H, generator=torch.Generator().manual_seed(1)) * 2 - 1) * k)

@@ -2,14 +2,14 @@
 argument as a tag and the sha1 of every output tensor of every timed run; the inputs are seeded, so two library builds on one box
 (S2VT_LIB, interleaved processes) can be compared for speed AND for bit-equal results.
 usage: [S2VT_LIB=<library>] python tools/bench_persist.py [TAG]"""
-import hashlib
 import os
 import sys
-import time
 
 import torch
 
 sys.path.insert(0, ".")
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from bench_sha import sha, show as _show  # noqa
 import s2vt_video_caption_amd  # noqa
 from s2vt_video_caption_amd import build, capi, ops
 
@@ -20,17 +20,8 @@ capi.load()
 DEV = "cuda:0"
 
 
-def sha(out):
-    """sha1 (16 hex digits) of every tensor of a run's result, in order"""
-    if torch.is_tensor(out):
-        return [hashlib.sha1(out.detach().cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()[:16]]
-    if isinstance(out, (tuple, list)):
-        return [h for o in out for h in sha(o)]
-    return []
-
-
 def show(line, shas):
-    print("%s %s | sha1 %s" % (TAG, line, " ".join("/".join(r) for r in shas)), flush=True)
+    _show(TAG, line, shas)
 
 
 T, H = 159, 1000

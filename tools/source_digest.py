@@ -13,9 +13,9 @@ KERNEL_SOURCES = {
     "gemm_x3_kernel": ["gemm_x3.hip", "gemm_persist.h"], "gemm_b1_kernel": ["gemm_b1.hip", "gemm_persist.h"], "gemm_f32_kernel": ["gemm.hip"],
     "lstm_seq_fwd_x3_persist_kernel": ["lstm_persist_x3.hip", "lstm_persist_frame.h"], "lstm_seq_bwd_x3_persist_kernel": ["lstm_persist_x3.hip", "lstm_persist_frame.h"],
     "lstm_seq_fwd_bf16_persist_kernel": ["lstm_persist.hip", "lstm_persist_frame.h"], "lstm_seq_bwd_bf16_persist_kernel": ["lstm_persist.hip", "lstm_persist_frame.h"],
-    "lstm_step_fwd_kernel": ["lstm.hip"], "lstm_step_bwd_kernel": ["lstm.hip"],
+    "lstm_step_fwd_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"], "lstm_step_bwd_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"],
     "lstm_step_fwd_bf16_kernel": ["lstm_bf16.hip"], "lstm_step_bwd_bf16_kernel": ["lstm_bf16.hip"],
-    "logits_argmax_x3_kernel": ["argmax_x3.hip"], "logits_argmax_kernel": ["lstm.hip"],
+    "logits_argmax_x3_kernel": ["argmax_x3.hip"], "logits_argmax_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"],
     "split_dual_kernel": ["split.hip"], "split3_rows_kernel": ["split.hip"],
 }
 
