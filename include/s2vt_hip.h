@@ -500,6 +500,11 @@ int s2vt_set_recurrence_mode(int32_t mode);
 /* Which recurrence kernels s2vt_train_forward / s2vt_train_backward would run for (B, H) in the current modes:
  * *fwd, *bwd = 0 one launch per timestep, 1 persistent bf16, 3 persistent split precision. */
 int s2vt_recurrence_plan(int32_t B, int32_t H, int32_t* fwd, int32_t* bwd);
+/* Which path a decode of *d would take in the current modes (encode_only != 0: s2vt_decode_encode_cached): *padded_B = the batch the
+ * library runs (d->B, or the next multiple of 64 where it pads), *persist_encode = 1 where the encode phase runs as persistent
+ * split-precision launches, *schedule of the token-dependent steps = 0 launches per timestep on two lanes, 1 a step and an argmax
+ * launch per step (two chains over the batch halves at B % 128 == 0), 2 fused (option "decode_fused"). */
+int s2vt_decode_plan(const s2vt_dims* d, int32_t encode_only, int32_t* padded_B, int32_t* persist_encode, int32_t* schedule);
 
 /* Persistent forward recurrence in split precision (lstm_persist_x3.hip): the same computation as s2vt_lstm_seq_fwd with ONE launch
  * per `block` timesteps (0 = all T) and each compute unit's slice of W_hh resident in registers: both operands of

@@ -143,6 +143,7 @@ SIGNATURES = {
                                      [c_void_p] * 4 + [c_int32, c_void_p, c_size_t, c_void_p]),
     "s2vt_set_recurrence_mode": (c_int32, [c_int32]),
     "s2vt_recurrence_plan": (c_int32, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
+    "s2vt_decode_plan": (c_int32, [POINTER(Dims), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),
     "s2vt_decode_step_argmax": (c_int32, [c_int32, c_int32, c_int32] + [c_void_p] * 5),
     "s2vt_decode_step_argmax_x3_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_decode_step_argmax_x3": (c_int32, [c_int32, c_int32, c_int32] + [c_void_p] * 5 + [c_size_t, c_void_p]),
@@ -269,3 +270,12 @@ def recurrence_plan(B, H):
     lib = load()
     check(lib.s2vt_recurrence_plan(int(lib.s2vt_padded_batch(int(B))), int(H), ctypes.byref(f), ctypes.byref(b)), "s2vt_recurrence_plan")
     return f.value, b.value
+
+
+def decode_plan(dims, encode_only=False):
+    """(padded B, persist_encode, schedule) of a decode of `dims` (a Dims, or a (B, L, F, H, E, V) tuple) under the current options -
+    schedule: 0 launches per timestep on two lanes, 1 a step and an argmax launch per step (two chains), 2 fused."""
+    d = dims if isinstance(dims, Dims) else Dims(*[int(x) for x in dims])
+    b, pe, sc = c_int32(0), c_int32(0), c_int32(0)
+    check(load().s2vt_decode_plan(d, 1 if encode_only else 0, ctypes.byref(b), ctypes.byref(pe), ctypes.byref(sc)), "s2vt_decode_plan")
+    return b.value, pe.value, sc.value

@@ -2,7 +2,8 @@
 //   api_runtime.hip  errors, asynchronous device-side errors, live timing, launch-sequence capture, the side stream, setters
 //   api_shared.hip   plane-operand helpers (split / GEMM wrappers), recurrence loops and argument builders
 //   api_train.hip    s2vt_train_forward / s2vt_train_backward (+ dropout, fused criterion backward, gradient-group events)
-//   api_decode.hip   greedy decode, the encode phase for the beam search, the decode step's argmax entry points
+//   api_decode.hip   greedy / sampled / scheduled decode and the encode phase for the beam search (DecodeDriver: one function per
+//                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
 // Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue.hip.
@@ -85,6 +86,8 @@ static inline bool batch_pads(int B, bool decode = false) {
     const int from = decode ? option(O_PAD_MIN_BATCH) * 3 / 4 : option(O_PAD_MIN_BATCH);
     return option(O_GEMM_MODE) != 0 && B % 64 != 0 && B >= (from > 0 ? from : 1);
 }
+static inline bool batch_padded(const s2vt_dims& d) { return batch_pads(d.B); }       // (the train drivers' rule)
+static inline s2vt_dims padded_dims(const s2vt_dims& d) { s2vt_dims q = d; q.B = (d.B + 63) / 64 * 64; return q; }
 static inline bool dims_ok(const s2vt_dims* d) { return d && d->B > 0 && d->L > 1 && d->F > 0 && d->H > 0 && d->E > 0 && d->V > 0; }
 static inline int pad64(int x) { return (x + 63) / 64 * 64; }
 
@@ -135,6 +138,30 @@ static inline RecurrencePlan train_recurrence_plan(int B, int H) {
     }
     return pl;
 }
+// Which path a decode of d (as the caller hands it over) takes under the current modes and options - the ONE statement of it, as
+// train_recurrence_plan is for the train drivers: the driver (api_decode.hip) switches on it, the size / cache queries and the beam
+// step (api_beam.hip) read it, s2vt_decode_plan reports it (the enum's values are that entry point's).
+//   padded / B      ragged batches run padded to the next multiple of 64: a plain decode from three quarters of option pad_min_batch
+//                   on (batch_pads), the encode phase for the beam search (encode_only) always
+//   planes          split-precision plane path (gemm modes 1 and 3, B % 64 == 0 after padding): plane GEMMs, gate table, argmax_x3
+//   persist_encode  both layers' encode steps and vid_rnn's decode steps as persistent split-precision launches; behind them the token
+//   schedule / nh   steps fused, or a step + an argmax launch per step as nh chains over the batch halves; else DEC_PER_STEP: the
+//                   two-lane launch-per-timestep loop over all T steps
+// device = false leaves out the one device query (does the persistent kernel fit?): carve_decode and the size queries work without a
+// GPU that way, and their answer is never narrower than the plan's.
+enum DecSchedule { DEC_PER_STEP = 0, DEC_TWO_CHAINS = 1, DEC_FUSED = 2 };
+struct DecodePlan { bool padded; int B; bool planes, persist_encode; DecSchedule schedule; int nh; };
+static inline DecodePlan decode_plan(const s2vt_dims& d, bool encode_only, bool device = true) {
+    DecodePlan pl;
+    pl.padded = encode_only ? (gemm_mode() != 0 && d.B % 64 != 0) : batch_pads(d.B, true);
+    pl.B = pl.padded ? padded_dims(d).B : d.B;
+    pl.planes = gemm_mode() != 0 && pl.B % 64 == 0;
+    pl.persist_encode = pl.planes && d.H <= 1024 && pipe_block() > 0 && persist_x3_fwd_on() &&
+                        (!device || lstm_seq_fwd_x3_persist_supported(pl.B, d.H));
+    pl.schedule = !pl.persist_encode ? DEC_PER_STEP : option(O_DECODE_FUSED) == 1 ? DEC_FUSED : DEC_TWO_CHAINS;
+    pl.nh = (pl.persist_encode && pl.B % 128 == 0) ? 2 : 1;      // (chains of the two-chain schedule, whichever is selected)
+    return pl;
+}
 // the recurrence options that decide how a train workspace is carved and which images a forward leaves in it
 static inline int persist_bits() { return persist_mode() | (persist_x3_fwd_on() ? 2 : 0) | (option(O_PERSIST_X3_BWD) << 2); }
 
@@ -167,6 +194,11 @@ struct PB { unsigned short* p; int64_t ld; int kpad; };       // packed planes o
 // (gemm_x3.hip) k0/16 records of 3072 elements
 static inline int64_t koff(int k0) { return XP == 3 ? (int64_t)k0 * 192 : (int64_t)k0 * XP; }
 static inline size_t rows64(size_t r) { return (r + 63) / 64 * 64; }
+// a packed operand of `planes` planes carved from c: rows rounded up to 64, k to a multiple of 64
+static inline PB take_planes(Carver& c, size_t rows, size_t k, int planes) {
+    const int kpad = pad64((int)k);
+    return PB{c.take<unsigned short>(rows64(rows) * (size_t)planes * kpad), (int64_t)planes * kpad, kpad};
+}
 int psplit(const Lane& ln, const PB& dst, int r0, const float* in, int64_t ld, RowMap imap, int rows, int cols);
 int pdual(const Lane& ln, const float* in, int64_t ld, RowMap imap, int rows, int cols, const PB* r, int r0, const PB* t, int k0,
           float* colpart);

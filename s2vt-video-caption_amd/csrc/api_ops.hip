@@ -242,15 +242,8 @@ static SeqBf16WS carve_seq_bf16(int T, int B, int H, void* base) {
     SeqBf16WS w;
     w.err = c.take<int>(64);
     w.sync = c.take<unsigned int>(lstm_persist_sync_bytes() / sizeof(unsigned int));
-    auto mk = [&](size_t rows, size_t k) {
-        PB b;
-        b.kpad = pad64((int)k);
-        b.ld = b.kpad;
-        b.p = c.take<unsigned short>(rows64(rows) * (size_t)b.ld);
-        return b;
-    };
-    w.wb = mk((size_t)4 * H, H);
-    w.hb = mk((size_t)T * B, H);
+    w.wb = take_planes(c, (size_t)4 * H, H, 1);
+    w.hb = take_planes(c, (size_t)T * B, H, 1);
     w.bytes = align_up(c.off, 256);
     return w;
 }
@@ -341,15 +334,8 @@ static SeqBwdBf16WS carve_seq_bwd_bf16(int T, int B, int H, void* base) {
     SeqBwdBf16WS w;
     w.err = c.take<int>(64);
     w.sync = c.take<unsigned int>(lstm_persist_sync_bytes() / sizeof(unsigned int));
-    auto mk = [&](size_t rows, size_t k) {
-        PB b;
-        b.kpad = pad64((int)k);
-        b.ld = b.kpad;
-        b.p = c.take<unsigned short>(rows64(rows) * (size_t)b.ld);
-        return b;
-    };
-    w.wt = mk((size_t)H, (size_t)4 * H);
-    w.dgb = mk((size_t)T * B, (size_t)4 * H);
+    w.wt = take_planes(c, (size_t)H, (size_t)4 * H, 1);
+    w.dgb = take_planes(c, (size_t)T * B, (size_t)4 * H, 1);
     w.dc = c.take<float>((size_t)B * H);
     w.bytes = align_up(c.off, 256);
     return w;

@@ -121,13 +121,7 @@ struct PlaneWS {
 static PlaneWS carve_planes(const s2vt_dims& d, void* base) {
     const size_t B = d.B, L = d.L, F = d.F, H = d.H, E = d.E, V = d.V, T = 2 * L - 1, R = (L - 1) * B;
     Carver c{reinterpret_cast<char*>(base), 0, 0};
-    auto mk = [&](size_t rows, size_t k) {
-        PB b;
-        b.kpad = pad64((int)k);
-        b.ld = (int64_t)XP * b.kpad;
-        b.p = c.take<unsigned short>(rows64(rows) * (size_t)b.ld);
-        return b;
-    };
+    auto mk = [&](size_t rows, size_t k) { return take_planes(c, rows, k, XP); };
     PlaneWS w;
     w.feats = mk(B * L, F);   w.wf = mk(H, F);       w.x1 = mk(L * B, H);    w.wih1 = mk(4 * H, H);
     w.h1 = mk(T * B, H);      w.we = mk(4 * H, E);   w.wv = mk(4 * H, H);    w.emb = mk(R, E);
@@ -876,8 +870,6 @@ extern "C" {
 // never handed out, and their dlogits rows are zero, so every gradient they contribute is an exact zero (dG = 0 for a row
 // whose dh and dc are 0) - the sums the real rows form are unchanged up to the order of fp32 additions.  Staging copies:
 // features, targets, logits / dlogits, the dropout mask (a few tens of MB at these batch sizes).
-static inline bool batch_padded(const s2vt_dims& d) { return batch_pads(d.B); }
-static inline s2vt_dims padded_dims(const s2vt_dims& d) { s2vt_dims q = d; q.B = (d.B + 63) / 64 * 64; return q; }
 struct PadWS { float* feats; int64_t* targets; float* logits; float* mask; float* dfeats; size_t bytes; };
 static PadWS carve_pad(const s2vt_dims& d, const s2vt_dims& dp, void* base) {
     const size_t Bp = dp.B, L = d.L, F = d.F, H = d.H, V = d.V;

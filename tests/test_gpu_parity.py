@@ -666,6 +666,121 @@ def test_decode_schedules_on_ragged_shapes_against_the_oracle(lib, dims):
     assert torch.equal(out[1][rows], oids[rows])
 
 
+# every path of the decode driver: options on top of the defaults -> the (persist_encode, schedule) s2vt_decode_plan must report
+# (schedule: 2 fused, 1 a step and an argmax launch per step, 0 launches per timestep on two lanes)
+_DECODE_DEFAULTS = dict(_PLAN_DEFAULTS, gemm_mode=3, decode_fused=1, pad_min_batch=33)
+_DECODE_PATHS = {"fused": ({}, (1, 2)), "two_chains": (dict(decode_fused=0), (1, 1)), "persist0": (dict(persist=0), (0, 0)),
+                 "pipe_block0": (dict(pipe_block=0), (0, 0)), "gemm_mode0": (dict(gemm_mode=0), (0, 0))}
+
+
+def _small_model(dims, seed):
+    B, L, Fd, H, E, V = dims
+    sd = synth.make_state_dict(V, Fd, H, E, seed=seed)
+    return sd, _model(dict(V=V, F=Fd, L=L, H=H, E=E), sd).eval()
+
+
+@pytest.mark.parametrize("dims", [(64, 5, 70, 44, 28, 61), (128, 4, 36, 100, 52, 333)])
+def test_every_decode_path_by_plan_against_the_oracle(lib, dims):
+    """The five paths of the decode driver (api_decode.hip: fused, two chains, and the two-lane launch-per-timestep loop reached through
+    persist = 0, pipe_block = 0 and the fp32-MFMA mode), each ASSERTED through s2vt_decode_plan instead of inferred: on every row whose
+    weakest top-2 margin in the oracle is >= 1e-4 the ids are the oracle's (oracle/s2vt_oracle.py::greedy_decode), so all five agree there."""
+    from s2vt_video_caption_amd import capi
+    B, L, Fd, H, E, V = dims
+    sd, m = _small_model(dims, 11)
+    feats = synth.make_batch(B, L, Fd, V, seed=12)[0]
+    oids, marg = orc.greedy_decode(sd, feats, return_margins=True)
+    rows = (marg.reshape(B, -1).min(dim=1).values >= 1e-4).nonzero().flatten()
+    assert len(rows) >= B // 2, len(rows)
+    out = {}
+    for name, (kv, want) in _DECODE_PATHS.items():
+        with _options(lib, **dict(_DECODE_DEFAULTS, **kv)), torch.no_grad():
+            assert capi.decode_plan(dims) == (B,) + want, (name, capi.decode_plan(dims))
+            out[name] = m(feats.to(DEV), mode="test").cpu()
+    for name, ids in out.items():
+        assert torch.equal(ids[rows], oids[rows]), name
+        assert torch.equal(ids[rows], out["fused"][rows]), name
+
+
+_HANDOUT_DIMS = (64, 7, 24, 44, 28, 61)
+_HANDOUT_REF = {}
+
+
+def _handout_reference():
+    """(model, its parameter list, features, fp64 roll-out of the encode phase and of vid_rnn's first 6 decode steps) at _HANDOUT_DIMS, computed once"""
+    if not _HANDOUT_REF:
+        B, L, Fd, H, E, V = _HANDOUT_DIMS
+        sd, m = _small_model(_HANDOUT_DIMS, 31)
+        feats = synth.make_batch(B, L, Fd, V, seed=32)[0].to(DEV)
+        p = {k: v.double().to(DEV) for k, v in sd.items()}
+
+        def run(x, layer, h, c):
+            wi, wh, b = p[layer + ".weight_ih_l0"], p[layer + ".weight_hh_l0"], p[layer + ".bias_ih_l0"] + p[layer + ".bias_hh_l0"]
+            hs = []
+            for t in range(x.shape[1]):
+                i, f, g, o = (x[:, t] @ wi.T + h @ wh.T + b).chunk(4, dim=1)
+                c = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
+                h = torch.sigmoid(o) * torch.tanh(c)
+                hs.append(h)
+            return torch.stack(hs, 1), h, c
+        z = torch.zeros(B, H, dtype=torch.float64, device=DEV)
+        h1s, h1, c1 = run(feats.double() @ p["feat_linear.weight"].T + p["feat_linear.bias"], "vid_rnn", z, z)
+        _, h2, c2 = run(torch.cat([torch.zeros(B, L, E, dtype=torch.float64, device=DEV), h1s], dim=2), "word_rnn", z, z)
+        hd, _, _ = run(torch.zeros(B, 6, H, dtype=torch.float64, device=DEV), "vid_rnn", h1, c1)
+        gx = hd @ p["word_rnn.weight_ih_l0"][:, E:].T + p["word_rnn.bias_ih_l0"] + p["word_rnn.bias_hh_l0"]      # [B, 6, 4H]
+        from s2vt_video_caption_amd import capi
+        _HANDOUT_REF["ref"] = (m, tuple(m.state_dict()[k] for k in capi.PARAM_KEYS), feats, (h1, c1, h2, c2), gx.transpose(0, 1))
+    return _HANDOUT_REF["ref"]
+
+
+@pytest.mark.parametrize("depth", [None, 1, 6])
+@pytest.mark.parametrize("pipe_block", [2, 32])
+def test_encode_hand_out_across_the_block_boundary(lib, pipe_block, depth):
+    """s2vt_decode_encode_cached where vid_rnn's decode-phase steps do not end with the block that partners word_rnn's last encode block
+    (pipe_block = 2, depth = 6: steps 7..8 ride with that block, 9..12 are the launch of their own behind it), where they do
+    (depth = 1; pipe_block = 32) and without any (depth none): the four states and gx_dec against the fp64 roll-out, to the bounds of
+    test_library_encode_phase_is_the_beam_searchs_python_encoder."""
+    from s2vt_video_caption_amd import capi, functional
+    m, plist, feats, states, gx_ref = _handout_reference()
+    with _options(lib, **dict(_DECODE_DEFAULTS, pipe_block=pipe_block)):
+        assert capi.decode_plan(_HANDOUT_DIMS, encode_only=True)[:2] == (64, 1)
+        functional.clear_decode_cache(m)
+        out = functional.decode_encode(feats, plist, m, depth=depth or 0)
+    assert out is not None
+    for got, ref in zip(out[:4], states):
+        assert (got.double() - ref).abs().max().item() < 2e-6
+    if depth is None:
+        assert out[4] is None
+    else:
+        assert out[4].shape == (depth, 64, 4 * 44)
+        assert (out[4].double() - gx_ref[:depth]).abs().max().item() < 1e-5
+
+
+def test_batch_padding_leaks_nothing_bitwise(lib):
+    """B = 40 is padded to 64 rows of which 24 see zero features (pad_min_batch = 1; s2vt_decode_plan says so): greedy ids under both
+    token schedules, sampled ids (temperature 0.5, a fixed seed) and the encode hand-out with depth 6 are BIT-equal to rows 0..39 of
+    the B = 64 call whose rows 40..63 are zero features - the same computation row for row, so no tolerance."""
+    from s2vt_video_caption_amd import capi, functional
+    L, Fd, H, E, V = _HANDOUT_DIMS[1:]
+    sd, m = _small_model(_HANDOUT_DIMS, 31)
+    plist = tuple(m.state_dict()[k] for k in capi.PARAM_KEYS)
+    f40 = synth.make_batch(40, L, Fd, V, seed=33)[0].to(DEV)
+    f64 = torch.cat([f40, torch.zeros(24, L, Fd, device=DEV)], dim=0)
+
+    def both(fn):
+        a, b = fn(f40), fn(f64)
+        a, b = (a, b) if isinstance(a, tuple) else ((a,), (b,))
+        for x, y in zip(a, b):
+            assert x.shape[-2] == 40 and torch.equal(x, y[..., :40, :])
+    for fused in (1, 0):
+        with _options(lib, **dict(_DECODE_DEFAULTS, pad_min_batch=1, decode_fused=fused)), torch.no_grad():
+            assert capi.decode_plan((40,) + _HANDOUT_DIMS[1:]) == (64, 1, 2 if fused else 1)
+            both(lambda f: m(f, mode="test"))
+    with _options(lib, **dict(_DECODE_DEFAULTS, pad_min_batch=1)), torch.no_grad():
+        both(lambda f: m(f, mode="sample", temperature=0.5, seed=20261))
+        assert capi.decode_plan((40,) + _HANDOUT_DIMS[1:], encode_only=True)[:2] == (64, 1)
+        both(lambda f: functional.decode_encode(f, plist, m, depth=6))
+
+
 def test_c3_full_size_bf16_against_reference_golden(lib, golden):
     """BASELINE configs[2] at its own size: B=256, L=80, F=4096, H=E=1000, V=12000 with s2vt_set_gemm_mode(1) (bf16
     operands for the batched GEMMs and the recurrence - k padded 1000 -> 1024, 4000 -> 4032 - fp32 accumulation, cell
