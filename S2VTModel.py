@@ -62,14 +62,22 @@ class S2VT(nn.Module):
                     "dim_embed + dim_hid inputs and gets dim_embed + 2*dim_hid)")
 
     def forward(self, feats, targets=None, mode='train', beam_width=3, max_beam_depth=30, ss_prob=0.0, ss_temperature=None,
-                temperature=1.0, seed=None):
+                length_alpha=0.7, n_best=1, temperature=1.0, seed=None):
         """
         :param feats: [B, L, feat_dim]
         :param targets: [B, L-1] word ids (train mode)
         :param mode: 'train' -> logits [B, L-1, V]; 'test' -> greedy ids [B, L-1] (int64);
-                     'beam_search' -> list of id sequences (each starting with <sos>);
+                     'beam_search' -> list of id sequences (each starting with <sos>): the reference's search, score = the LAST
+                     token's log-prob / len**0.7;
+                     'beam' -> (ids int64 [B, n_best, max_beam_depth], lengths int64 [B, n_best], scores fp32 [B, n_best]) on the
+                     device, best first: hypotheses ranked by the SUM of their tokens' log-probs, divided by
+                     length**length_alpha when they end (<eos>, or max_beam_depth words); ids are the words after <sos>, padded
+                     with eos_ix; lengths count the <eos> where there is one (not in the reference; beam.beam_cumulative);
                      'sample' -> ids [B, L-1] (int64) drawn step by step from softmax(logit / temperature), never stopping at
                      <eos> (not in the reference; for sequence-level training, utils.RewardCriterion)
+        :param beam_width: 'beam_search': any; 'beam': 1..8
+        :param length_alpha: mode='beam' only: finite and >= 0 (0: the plain sum)
+        :param n_best: mode='beam' only: hypotheses returned per clip, 1..beam_width
         :param temperature: mode='sample' only: finite and > 0
         :param seed: mode='sample' and scheduled sampling: None draws a 63-bit seed from torch's default generator
                      (torch.manual_seed makes the run reproducible); an int is used as is.  Same seed, same weights, same clips ->
@@ -83,6 +91,8 @@ class S2VT(nn.Module):
                      softmax(logit / ss_temperature)
         """
         ss_prob = _F.check_ss_prob(ss_prob) if mode == 'train' else 0.0      # (ignored elsewhere, as temperature is outside 'sample')
+        if mode == 'beam':
+            _beam.check_beam_args(beam_width, max_beam_depth, length_alpha, n_best, self.vocab_size)
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
@@ -96,6 +106,9 @@ class S2VT(nn.Module):
         feats = self.feat_drop(feats)                      # identity at the reference's p=0 (S2VTModel.py:52)
         if mode == 'beam_search':
             return _beam.beam_search(self, feats, params, beam_width=beam_width, max_depth=max_beam_depth)
+        if mode == 'beam':
+            return _beam.beam_cumulative(self, feats, params, beam_width=beam_width, max_depth=max_beam_depth,
+                                         length_alpha=length_alpha, n_best=n_best)
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")
@@ -120,6 +133,8 @@ class S2VT(nn.Module):
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
                                       "(S2VTModel.py:153, 'DO NOT SUPPORT GRU'); use mode='test'")
+        if mode == 'beam':
+            raise NotImplementedError("mode='beam' of a GRU model: the batched depth step is the LSTM's; use mode='test'")
         clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':
@@ -146,6 +161,9 @@ class S2VT(nn.Module):
             raise NotImplementedError("beam search of a stacked model (num_layers > 1): the reference's BeamSearchNode views the "
                                       "per-sample [num_layers, H] state as [1, 1, -1] (S2VTModel.py:253-254) and raises for "
                                       "num_layers > 1; use mode='test'")
+        if mode == 'beam':
+            raise NotImplementedError("mode='beam' of a stacked model (num_layers > 1): the batched depth step is the one-layer "
+                                      "LSTM's; use mode='test'")
         clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':

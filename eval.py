@@ -1,6 +1,7 @@
 """Caption generation for the MI355X S2VT path: the decode loops of the reference's eval.py
 (`eval()` eval.py:30-60, `beam_eval()` :63-99) on top of the drop-in model — load a full-module checkpoint, decode the
-test split greedily or by beam search, map ids to words and cut at `<eos>` (eval.py:54-58, :90-96).
+test split greedily or by beam search, map ids to words and cut at `<eos>` (eval.py:54-58, :90-96).  --beam-mode cumulative
+decodes with the cumulative-score beam search instead (mode='beam', not in the reference), through the same post-processing.
 
 `main()` writes the predictions as JSON ({video_id: caption}) and, with --gts, scores them as the reference's
 `__main__` does (eval.py:222-236: gts.json -> pred_to_coco_samples_IDs -> COCOScorer.score) with caption_metrics.py:
@@ -24,14 +25,16 @@ def ids_to_caption(ids, ix2word, drop_sos=False):
 
 
 def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', beam_width=5, max_beam_depth=30,
-             split='test', device=None):
+             split='test', device=None, length_alpha=0.7, n_best=1, nbest=None):
+    """{video_id: caption} of a split.  mode: 'test' (greedy), 'beam_search' (the reference's search) or 'beam' (cumulative scores,
+    length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]})."""
     import dataloader
     dev = device or torch.device('cuda', 0)
     dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
     loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
     model = torch.load(model_path, weights_only=False).to(dev)          # full-module pickle (eval.py:41)
     model.eval()
-    if mode == 'beam_search':                                           # old pickles lack these attrs (eval.py:84-86)
+    if mode in ('beam_search', 'beam'):                                 # old pickles lack these attrs (eval.py:84-86)
         model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
     preds = {}
     with torch.no_grad():
@@ -40,6 +43,15 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                 out = model(feats, mode='beam_search', beam_width=beam_width, max_beam_depth=max_beam_depth)
                 for vid, seq in zip(ids, out):
                     preds[vid] = ids_to_caption([int(t.item()) for t in seq], dataset.ix2word, drop_sos=True)
+            elif mode == 'beam':
+                out, lens, _ = model(feats, mode='beam', beam_width=beam_width, max_beam_depth=max_beam_depth,
+                                     length_alpha=length_alpha, n_best=n_best)
+                out, lens = out.cpu().tolist(), lens.cpu().tolist()
+                for vid, rows, ln in zip(ids, out, lens):
+                    caps = [ids_to_caption(r[:n], dataset.ix2word) for r, n in zip(rows, ln)]
+                    preds[vid] = caps[0]
+                    if nbest is not None:
+                        nbest[vid] = caps
             else:
                 out = model(feats, mode='test').cpu()
                 for vid, seq in zip(ids, out):
@@ -65,21 +77,32 @@ def score(prediction_dict, gts_file):
     return scorer
 
 
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-path", required=True)
     ap.add_argument("--caption-file", default="./data/captions_server.json")
     ap.add_argument("--feats-path", default="./data/feats/vgg16_bn")
     ap.add_argument("--batch-size", type=int, default=10)
     ap.add_argument("--beam", type=int, default=0, help="beam width (0: greedy)")
+    ap.add_argument("--beam-mode", choices=("reference", "cumulative"), default="reference",
+                    help="with --beam: the reference's search (last-token scores) or cumulative log-prob scores (width <= 8)")
+    ap.add_argument("--length-alpha", type=float, default=0.7, help="cumulative: a finished caption scores sum / length**alpha")
+    ap.add_argument("--n-best", type=int, default=1,
+                    help="cumulative: captions kept per clip; more than one also writes {video_id: [captions]} to <out>.nbest.json")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
-    a = ap.parse_args()
+    a = ap.parse_args(argv)
+    cumulative = bool(a.beam) and a.beam_mode == "cumulative"
+    nbest = {} if cumulative and a.n_best > 1 else None
     preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
-                     'beam_search' if a.beam else 'test', beam_width=a.beam or 5)
+                     ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
+                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest)
     with open(a.out, 'w', encoding='utf-8') as f:
         json.dump(preds, f, ensure_ascii=False, indent=1)
     print("wrote {} captions to {}".format(len(preds), a.out))
+    if nbest is not None:
+        with open(a.out + ".nbest.json", 'w', encoding='utf-8') as f:
+            json.dump(nbest, f, ensure_ascii=False, indent=1)
     if a.gts:
         scorer = score(preds, a.gts)
         print("***********************")

@@ -145,6 +145,29 @@ int s2vt_beam_queue_step(int32_t B, int32_t beam_width, int32_t max_depth, int32
 int s2vt_beam_queue_result(int32_t B, int32_t beam_width, int32_t max_depth, void* state, size_t state_bytes, int32_t* out_tokens,
                            int32_t out_cap, int32_t* out_len, void* stream);
 
+/* Cumulative-score beam search (S2VT.forward(mode='beam'); not in the reference): the search policy ON THE DEVICE on the same fixed
+ * rows r = b * beam_width + slot, one wave per sample and depth.  A hypothesis scores S = the fp32 sum of its tokens' log-probs (each
+ * clamped to <= 0); per depth t the min(beam_width, count) best of the candidates S_j + top_lp[j][f] by (S descending, slot ascending,
+ * token ascending) are kept: one ending in <eos> enters the sample's pool with score S / t**length_alpha, the others are the next
+ * live slots in that order; at t = max_depth the live ones enter the pool with S / max_depth**length_alpha and no <eos>.  The pool
+ * keeps its best beam_width entries by (score descending, insertion ascending).  t**alpha is fp32(double pow), as len**0.7 above.
+ * 1 <= beam_width <= 8 (the fan-out of 20 is then exact), length_alpha finite and >= 0.  `state`: s2vt_beam_cum_bytes() of
+ * caller-owned device memory that lives for one search.
+ *   depth = 1          : initialise; writes row_b / row_state / row_tok for the first s2vt_beam_step
+ *   depth = 2..max     : consume top_ix / top_lp [B*beam_width][20] of step depth-1 and write the rows of the next step
+ *   depth = 0          : consume the last step, max_depth (a search that stops early may call it as well: frozen samples ignore it)
+ * A sample is frozen when no live slot is left, at max_depth, or as soon as its pool is full and pool[beam_width-1].score >=
+ * live[0].S / max_depth**alpha (no later hypothesis can enter: scores only fall and ties lose by insertion order).  A frozen sample's
+ * slots carry token 0 / state row 0.  The int32 at byte 0 of `state` counts the frozen samples.
+ * s2vt_beam_cum_result: the pool's first n_best entries (1 <= n_best <= beam_width) -> out_tokens [B][n_best][max_depth] int32 (words
+ * after <sos>, padded with eos_ix), out_len [B][n_best] (tokens, <eos> included where present), out_score [B][n_best], best first. */
+size_t s2vt_beam_cum_bytes(int32_t B, int32_t beam_width, int32_t max_depth);
+int s2vt_beam_cum_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, double length_alpha, int32_t depth,
+                       void* state, size_t state_bytes, const int32_t* top_ix, const float* top_lp, int32_t* row_b, int32_t* row_state,
+                       int32_t* row_tok, void* stream);
+int s2vt_beam_cum_result(int32_t B, int32_t beam_width, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state, size_t state_bytes,
+                         int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream);
+
 /* Data-parallel overlap (no reference counterpart: the reference is single-device).  After s2vt_train_backward has
  * RETURNED (all of its work is enqueued), make `stream` wait until a group of that call's parameter gradients is
  * final, so that their all-reduce can run under the rest of the backward:

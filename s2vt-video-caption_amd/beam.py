@@ -12,6 +12,10 @@ Semantics kept exactly: score = log-prob of the LAST token / l
 cumulative), queue cleared after popping `beam_width` entries, finished (<eos>) entries re-inserted
 unchanged, fan-out = top-20 tokens pushed in ascending token order, stop when the queue holds
 <= beam_width entries, answer = best queue entry back-traced, first element the [[<sos>]] tensor.
+
+`S2VT.forward(mode='beam')` (beam_cumulative below) is the search the reference does not have: hypotheses ranked by their
+cumulative log-probability, length-normalised when they end, n-best out.  It shares the encoder, the depth step and the depth
+loop (_device_depth_loop) with the search above; only the policy kernel differs (csrc/beam_cum.hip).
 """
 import heapq
 
@@ -53,29 +57,23 @@ PLANE_ENCODER = True             # A/B switch: the whole encode phase by the lib
 VID_PRECOMPUTE = True            # A/B switch: vid_rnn's token-independent decode steps and their gate-input GEMM once, in front of the depth loop
 
 
-@torch.no_grad()
-def beam_search(model, feats, params, beam_width=3, max_depth=30):
+def _encoder_states(model, feats, params, max_depth, library_encode):
+    """(vid_h, vid_c, word_h, word_c, gx_dec): the states [B, H] a search starts from - vid_rnn over the L real frames only, word_rnn
+    with a zero embedding (S2VTModel.py:57-60) - and, from the library's encode phase only, vid_rnn's token-independent decode steps
+    (functional.decode_encode; None otherwise)."""
     (w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2, w_f, b_f, w_o, b_o, emb) = [p.detach() for p in params]
-    dev = feats.device
     B, L, _ = feats.shape
-    H, E, V = model.dim_hid, model.dim_embed, model.vocab_size
-    if V < FANOUT:
-        raise RuntimeError("beam search needs vocab_size >= %d (topk(20), S2VTModel.py:216)" % FANOUT)
-    sos, eos = int(model.sos_ix), int(model.eos_ix)
-    bsum1 = (b_ih1 + b_hh1).contiguous()
-    bsum2 = (b_ih2 + b_hh2).contiguous()
-    w_v = w_ih2[:, E:]          # [4H, H] view, row stride E+H
-    w_e = w_ih2[:, :E]
-
-    # ---- encoder: vid_rnn over the L real frames only, word_rnn with a zero embedding (S2VTModel.py:57-60)
-    lib0 = capi.load()
-    if (DEVICE_QUEUES and PLANE_STEP and PLANE_ENCODER and lib0.s2vt_beam_queue_bytes(B, beam_width, max_depth) > 0):
+    H, E = model.dim_hid, model.dim_embed
+    if library_encode:
         # the library's own encode phase (what mode='test' runs: plane-path GEMMs, paired persistent recurrence launches); it
         # fills the weight-image cache the plane-path depth step reads
         from . import functional
         enc = functional.decode_encode(feats, params, model, depth=max_depth if VID_PRECOMPUTE else 0)
         if enc is not None:
-            return _beam_search_device_queues(lib0, model, feats, params, B, H, beam_width, max_depth, sos, eos, *enc)
+            return enc
+    bsum1 = (b_ih1 + b_hh1).contiguous()
+    bsum2 = (b_ih2 + b_hh2).contiguous()
+    w_v = w_ih2[:, E:]          # [4H, H] view, row stride E+H
     x1 = ops.feat_proj_fwd(feats.contiguous(), w_f, b_f)                       # [L*B, H] time-major
     gx1 = _gemm_strided(x1, w_ih1, bsum1)
     # (the persistent split-precision recurrence, lstm_persist_x3.hip, where the shape is supported; else launches per timestep)
@@ -88,17 +86,30 @@ def beam_search(model, feats, params, beam_width=3, max_depth=30):
     h1_all, c1_all, _ = layer(gx1, w_hh1)
     gx2 = _gemm_strided(h1_all, w_v, bsum2)
     h2_all, c2_all, _ = layer(gx2, w_hh2)
-    vid_h, vid_c = h1_all[(L - 1) * B:], c1_all[(L - 1) * B:]
-    word_h, word_c = h2_all[(L - 1) * B:].clone(), c2_all[(L - 1) * B:].clone()
+    return (h1_all[(L - 1) * B:], c1_all[(L - 1) * B:], h2_all[(L - 1) * B:].clone(), c2_all[(L - 1) * B:].clone(), None)
+
+
+@torch.no_grad()
+def beam_search(model, feats, params, beam_width=3, max_depth=30):
+    (w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2, w_f, b_f, w_o, b_o, emb) = [p.detach() for p in params]
+    dev = feats.device
+    B, L, _ = feats.shape
+    H, E, V = model.dim_hid, model.dim_embed, model.vocab_size
+    if V < FANOUT:
+        raise RuntimeError("beam search needs vocab_size >= %d (topk(20), S2VTModel.py:216)" % FANOUT)
+    sos, eos = int(model.sos_ix), int(model.eos_ix)
+    lib = capi.load()
+    device_queues = DEVICE_QUEUES and lib.s2vt_beam_queue_bytes(B, beam_width, max_depth) > 0
+    states = _encoder_states(model, feats, params, max_depth, device_queues and PLANE_STEP and PLANE_ENCODER)
+    if device_queues:
+        return _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_depth, sos, eos, *states)
+    vid_h, vid_c, word_h, word_c, _ = states
 
     # ---- per-sample queues (host, BeamQueues) + one library call per depth (s2vt_beam_step): vid step for the batch,
     # word step / out_linear / log_softmax / top-20 for all expandable (sample, beam slot) rows
     import ctypes
     from .functional import _ptr, _stream, _dims, _params_struct
-    lib = capi.load()
     max_rows = max(B * beam_width, B)
-    if DEVICE_QUEUES and lib.s2vt_beam_queue_bytes(B, beam_width, max_depth) > 0:
-        return _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_depth, sos, eos, vid_h, vid_c, word_h, word_c)
     global LAST_PATH
     LAST_PATH = "host queues"
     queues = (BeamQueues if FAST_QUEUES else HeapQueues)(B, beam_width, sos, eos)
@@ -154,13 +165,14 @@ PLANE_STEP = True            # s2vt_beam_step_cached: the depth's GEMMs on the p
 LAST_PATH = None             # which path the last beam_search call took (bench.py reports it beside the rate)
 
 
-def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_depth, sos, eos, vid_h, vid_c, word_h, word_c,
-                               gx_dec=None):
-    """The depth loop with the queue bookkeeping on the device: per depth ONE s2vt_beam_queue_step (push the children of the
-    depth before, freeze finished samples, pop the next beam with heapq's own sift order, write the rows of the step) and ONE
-    s2vt_beam_step over the fixed rows r = b * beam_width + slot; nothing crosses PCIe until the back-traced sequences at the
-    end.  The reference's early exit (all samples stopped, S2VTModel.py:189) is polled without blocking: the frozen-sample
-    counter is copied to pinned memory after every depth and read one depth late - extra depths change nothing."""
+def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, vid_h, vid_c, word_h, word_c, gx_dec, qbytes, policy_step,
+                       policy_name):
+    """The depth loop of a search whose policy lives on the device: per depth ONE policy_step(depth, qs, top_ix, top_lp, rows, st)
+    (consume the top-20 of the depth before, freeze finished samples, write the rows of the step) and ONE s2vt_beam_step over the
+    fixed rows r = b * beam_width + slot; nothing crosses PCIe.  The early exit (all samples frozen) is polled without blocking:
+    the frozen-sample counter (the int32 at byte 0 of the policy's state) is copied to pinned memory after every depth and read
+    one depth late - extra depths change nothing.  Ends with policy_step(0, ...), the last depth's results.  Returns the policy's
+    state tensor (qbytes) and the stream."""
     import ctypes
     from .functional import _ptr, _stream, _dims, _params_struct
     dev = feats.device
@@ -176,19 +188,18 @@ def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_
     if PLANE_STEP:
         cache, valid = functional.decode_cache_entry(model, params, d, dev, lib)
         if cache is not None and not valid:
-            functional.greedy_decode(feats, params, sos, owner=model)
+            functional.greedy_decode(feats, params, int(model.sos_ix), owner=model)
             cache, valid = functional.decode_cache_entry(model, params, d, dev, lib)
             if not valid:
                 cache = None
     global LAST_PATH
     if cache is None:
         gx_dec = None
-    LAST_PATH = ("device queues + plane-path depth step (decode cache)" + (", vid_rnn steps precomputed" if gx_dec is not None else "")) \
-        if cache is not None else "device queues + fp32-MFMA depth step"
+    LAST_PATH = (policy_name + " + plane-path depth step (decode cache)" + (", vid_rnn steps precomputed" if gx_dec is not None else "")) \
+        if cache is not None else policy_name + " + fp32-MFMA depth step"
     with torch.cuda.device(dev):
         nbytes = lib.s2vt_beam_workspace_bytes(ctypes.byref(d), R)
         ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        qbytes = lib.s2vt_beam_queue_bytes(B, beam_width, max_depth)
         qs = torch.empty(qbytes, dtype=torch.uint8, device=dev)
         vid = [(vid_h.contiguous(), vid_c.contiguous()), (torch.empty(B, H, device=dev), torch.empty(B, H, device=dev))]
         tab = [(torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)) for _ in range(2)]
@@ -201,16 +212,12 @@ def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_
         frozen_dev = qs[:4].view(torch.int32)
         events = []
         st = _stream(dev)
-
-        def qstep(depth):
-            capi.check(lib.s2vt_beam_queue_step(B, beam_width, max_depth, sos, eos, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
-                                                _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_queue_step")
         depth = 0
         while depth < max_depth:
             if depth >= 2 and events[depth - 2].query() and int(frozen[depth - 1]) == B:
                 break                                   # every sample had stopped two depths ago: the reference's loop ended there
             depth += 1
-            qstep(depth)
+            policy_step(depth, qs, top_ix, top_lp, rows, st)
             if depth > 1:
                 frozen[depth].copy_(frozen_dev[0], non_blocking=True)
             ev = torch.cuda.Event()
@@ -232,7 +239,30 @@ def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_
                 capi.check(lib.s2vt_beam_step(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
                                               _ptr(vh_in), _ptr(vc_in), _ptr(vh_out), _ptr(vc_out), _ptr(wh_in), _ptr(wc_in),
                                               _ptr(wh_out), _ptr(wc_out), _ptr(top_ix), _ptr(top_lp), _ptr(ws), nbytes, st), "s2vt_beam_step")
-        qstep(0)                                        # the last depth's push
+        policy_step(0, qs, top_ix, top_lp, rows, st)    # the last depth's results
+        global LAST_DEPTHS
+        LAST_DEPTHS = depth
+    return qs, st
+
+
+LAST_DEPTHS = 0              # depth steps the last device-policy search ran (tools/bench_beam_cum.py: time per depth)
+
+
+def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_depth, sos, eos, vid_h, vid_c, word_h, word_c,
+                               gx_dec=None):
+    """mode='beam_search' with the reference's queue bookkeeping on the device (s2vt_beam_queue_step: push the children of the depth
+    before, freeze finished samples, pop the next beam with heapq's own sift order); only the back-traced sequences cross PCIe, at
+    the end."""
+    from .functional import _ptr
+    dev = feats.device
+    qbytes = lib.s2vt_beam_queue_bytes(B, beam_width, max_depth)
+
+    def qstep(depth, qs, top_ix, top_lp, rows, st):
+        capi.check(lib.s2vt_beam_queue_step(B, beam_width, max_depth, sos, eos, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
+                                            _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_queue_step")
+    qs, st = _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, vid_h, vid_c, word_h, word_c, gx_dec, qbytes,
+                                qstep, "device queues")
+    with torch.cuda.device(dev):
         cap = max_depth + 2
         out = torch.empty(B, cap, dtype=torch.int32, device=dev)
         out_len = torch.empty(B, dtype=torch.int32, device=dev)
@@ -247,6 +277,60 @@ def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_
         o += lens[b]
         sentences.append([t[:1].view(1, 1)] + list(t[1:].unbind(0)))
     return sentences
+
+
+MAX_BEAM_WIDTH = 8           # widths for which the step kernels' fan-out of 20 is exact (and the policy kernel's limit)
+
+
+def check_beam_args(beam_width, max_depth, length_alpha, n_best, vocab_size):
+    """(beam_width, max_depth, length_alpha, n_best) of mode='beam' as ints / a float, or ValueError - before anything reaches the
+    library"""
+    import math
+    W, D, nb, alpha = int(beam_width), int(max_depth), int(n_best), float(length_alpha)
+    if W != beam_width or not 1 <= W <= MAX_BEAM_WIDTH:
+        raise ValueError("mode='beam': beam_width must be an integer in [1, %d], got %r" % (MAX_BEAM_WIDTH, beam_width))
+    if nb != n_best or not 1 <= nb <= W:
+        raise ValueError("mode='beam': n_best must be an integer in [1, beam_width = %d], got %r" % (W, n_best))
+    if D != max_depth or D < 1:
+        raise ValueError("mode='beam': max_beam_depth must be an integer >= 1, got %r" % (max_depth,))
+    if not math.isfinite(alpha) or alpha < 0:
+        raise ValueError("mode='beam': length_alpha must be finite and >= 0, got %r" % (length_alpha,))
+    if int(vocab_size) < FANOUT:
+        raise ValueError("mode='beam': vocab_size must be >= %d (the depth step returns each row's %d best tokens), got %r"
+                         % (FANOUT, FANOUT, vocab_size))
+    return W, D, alpha, nb
+
+
+@torch.no_grad()
+def beam_cumulative(model, feats, params, beam_width=3, max_depth=30, length_alpha=0.7, n_best=1):
+    """mode='beam' (not in the reference): hypotheses ranked by the fp32 sum of their tokens' log-probs, the
+    beam_width best of all live slots' candidates kept per depth by (sum descending, slot ascending, token ascending), a hypothesis
+    that ends in <eos> at depth t pooled with score sum / t**length_alpha, the ones still live at max_depth with sum /
+    max_depth**length_alpha.  Same encoder, decode cache, depth step and polled early exit as mode='beam_search'; the policy is
+    csrc/beam_cum.hip.  Returns (ids int64 [B, n_best, max_depth] padded with <eos>, lengths int64 [B, n_best], scores fp32
+    [B, n_best]) on the device, best first; no host synchronisation."""
+    from .functional import _ptr
+    W, D, alpha, n_best = check_beam_args(beam_width, max_depth, length_alpha, n_best, model.vocab_size)
+    dev = feats.device
+    B, H = feats.shape[0], model.dim_hid
+    sos, eos = int(model.sos_ix), int(model.eos_ix)
+    lib = capi.load()
+    qbytes = lib.s2vt_beam_cum_bytes(B, W, D)
+    if qbytes == 0:
+        raise ValueError("mode='beam': batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (B, W, D))
+    states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
+
+    def cstep(depth, qs, top_ix, top_lp, rows, st):
+        capi.check(lib.s2vt_beam_cum_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp), _ptr(rows[0]),
+                                          _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_cum_step")
+    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, cstep, "cumulative beam")
+    with torch.cuda.device(dev):
+        ids = torch.empty(B, n_best, D, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, n_best, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_beam_cum_result(B, W, D, eos, n_best, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(scores), st),
+                   "s2vt_beam_cum_result")
+        return ids.long(), lens.long(), scores
 
 
 class HeapQueues(object):

@@ -6,7 +6,7 @@
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
-// Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue.hip.
+// Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue / beam_cum.hip.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>

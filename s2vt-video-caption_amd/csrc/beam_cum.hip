@@ -1,0 +1,296 @@
+// Cumulative-score beam search (S2VT.forward(mode='beam'); not in the reference): the search policy ON THE DEVICE, for all samples of a
+// batch at once, on the row protocol of beam_queue.hip (fixed rows r = b * beam_width + slot of s2vt_beam_step, nothing compacted,
+// nothing crosses PCIe per depth).  Definition, per sample, W = beam_width, D = max_depth:
+//   live = [(tokens [], S = 0, <sos>)], pool = []; for t = 1..D:
+//     candidates (j, v) of every live slot j and token v score S_j + lp_j[v] (one fp32 add);
+//     the min(W, count) best by (S descending, j ascending, v ascending) are walked in that order: v == <eos> enters the pool with
+//     score S / t**alpha, anything else becomes the next live slot; live empty -> done; t == D -> every live hypothesis enters the
+//     pool with S / D**alpha (no <eos> appended), done.
+//   pool is kept ordered by (score descending, insertion ascending), its best W entries only; the answer is its first n_best.
+// Fan-out 20 is exact for W <= 8: a candidate outside its parent's top W has W better candidates of the SAME parent in front of it.
+// top_ix rows are in ascending token order, so the candidate index c = j * 20 + f already IS (j ascending, v ascending): one 64-bit
+// key (order-preserving score bits high, ~c low) and W rounds of a wave-wide max select with the tie rule, no replay path.
+//
+// Early stop.  A sample is frozen after a depth when its pool holds W entries and pool[W-1].score >= live[0].S / D**alpha.  This
+// cannot change an output: the kernel clamps every log-prob to <= 0 (fminf(lp, 0)), so S never rises along a hypothesis and live[0]
+// (the first selected, unfinished candidate) holds the largest live S.  Any hypothesis finished later has S' <= live[0].S <= 0 and a
+// length t' <= D; the divisor table is non-decreasing in the length for alpha >= 0 (pow and the rounding to fp32 are monotone), so
+// S' / t'**alpha <= S' / D**alpha <= live[0].S / D**alpha, and the rounded fp32 quotients keep that order (division is monotone in
+// both operands here).  Its score is therefore <= pool[W-1].score, and an equal score loses to the earlier insertion: it never
+// enters the best W.
+#include <math.h>
+
+#include <map>
+#include <mutex>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace s2vt {
+
+constexpr int BC_FAN = 20;          // tokens per row that s2vt_beam_step returns (top20_logprob, ce.hip)
+constexpr int BC_MAXBW = 8;
+constexpr int BC_CPL = (BC_MAXBW * BC_FAN + 63) / 64;       // candidates per lane
+
+struct BeamC {
+    int B, bw, D, NN, sos, eos, depth;         // depth: 1 = initialise; 2..D = consume step depth-1; 0 = consume step D
+    int* done_count; int* done; int* n_live; int* n_nodes;
+    int* node_tok; int* node_prev;                           // [B][NN]: every selected candidate, for the back-trace
+    float* live_S; int* live_nid;                            // [B][bw]
+    int* pool_n; float* pool_score; int* pool_nid; int* pool_len;      // [B], [B][bw] x 3
+    float* powa;                                             // fp32(len ** alpha): double pow, then fp32
+    const int* top_ix; const float* top_lp;                  // [B*bw][20] of the depth just stepped
+    int* row_b; int* row_state; int* row_tok;                // [B*bw] for the next s2vt_beam_step
+};
+
+// fp32 -> uint32 whose unsigned order is the float order (no NaN reaches it: fminf(lp, 0) maps a NaN log-prob to 0)
+__device__ __forceinline__ unsigned int bc_ordered(float x) {
+    const unsigned int u = __float_as_uint(x);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float bc_unordered(unsigned int o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+__device__ __forceinline__ unsigned long long bc_wave_max(unsigned long long v) {
+    for (int o = 32; o; o >>= 1) {
+        const unsigned int hi = (unsigned int)__shfl_xor((int)(v >> 32), o), lo = (unsigned int)__shfl_xor((int)(unsigned int)v, o);
+        const unsigned long long ov = ((unsigned long long)hi << 32) | lo;
+        v = ov > v ? ov : v;
+    }
+    return v;
+}
+
+// One WAVE per sample.  Keys are distinct (the low word is the candidate index), so every round has exactly one winner.
+__global__ __launch_bounds__(64) void beam_cum_kernel(BeamC q) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int bw = q.bw;
+    float* lS = q.live_S + b * bw;
+    int* lnid = q.live_nid + b * bw;
+    int* ntok = q.node_tok + (int64_t)b * q.NN;
+    int* nprev = q.node_prev + (int64_t)b * q.NN;
+    if (q.depth == 1) {            // live = one empty hypothesis on the encoder state (row b of the first state table)
+        if (lane == 0) {
+            q.done[b] = 0; q.n_live[b] = 1; q.n_nodes[b] = 1; q.pool_n[b] = 0;
+            ntok[0] = q.sos; nprev[0] = -1;
+            lS[0] = 0.0f; lnid[0] = 0;
+            for (int j = 0; j < bw; ++j) {
+                q.row_b[b * bw + j] = b;
+                q.row_state[b * bw + j] = j == 0 ? b : 0;
+                q.row_tok[b * bw + j] = j == 0 ? q.sos : 0;
+            }
+        }
+        return;
+    }
+    if (q.done[b]) return;         // frozen: its rows were cleared when it stopped
+    const int t = q.depth == 0 ? q.D : q.depth - 1;
+    const int nl = q.n_live[b];
+    const int n = nl * BC_FAN;
+    // ---- candidates: c = j * 20 + f, score S_j + min(lp, 0)
+    unsigned long long key[BC_CPL];
+#pragma unroll
+    for (int k = 0; k < BC_CPL; ++k) {
+        const int c = lane + 64 * k;
+        key[k] = 0;
+        if (c < n) {
+            const int j = c / BC_FAN;
+            float s = lS[j] + fminf(q.top_lp[(int64_t)(b * bw + j) * BC_FAN + (c - j * BC_FAN)], 0.0f);
+            s = s == 0.0f ? 0.0f : s;                       // (-0 and +0 are one score)
+            key[k] = ((unsigned long long)bc_ordered(s) << 32) | (unsigned int)~(unsigned int)c;
+        }
+    }
+    // ---- selection: W rounds of a wave-wide max; every lane ends with the same list
+    const int m = n < bw ? n : bw;
+    float selS[BC_MAXBW];
+    int selc[BC_MAXBW];
+#pragma unroll
+    for (int r = 0; r < BC_MAXBW; ++r) {
+        if (r < m) {
+            unsigned long long mx = 0;
+#pragma unroll
+            for (int k = 0; k < BC_CPL; ++k) mx = key[k] > mx ? key[k] : mx;
+            mx = bc_wave_max(mx);
+#pragma unroll
+            for (int k = 0; k < BC_CPL; ++k) key[k] = key[k] == mx ? 0 : key[k];
+            selS[r] = bc_unordered((unsigned int)(mx >> 32));
+            selc[r] = (int)~(unsigned int)mx;
+        }
+    }
+    if (lane != 0) return;
+    // ---- walk the selected candidates: <eos> -> pool, anything else -> next live slot
+    float pS[BC_MAXBW];
+    int pnid[BC_MAXBW], plen[BC_MAXBW], oldnid[BC_MAXBW];
+    int pn = q.pool_n[b];
+#pragma unroll
+    for (int i = 0; i < BC_MAXBW; ++i) {
+        const bool in = i < pn;
+        pS[i] = in ? q.pool_score[b * bw + i] : 0.0f;
+        pnid[i] = in ? q.pool_nid[b * bw + i] : 0;
+        plen[i] = in ? q.pool_len[b * bw + i] : 0;
+        oldnid[i] = i < nl ? lnid[i] : 0;
+    }
+    auto pool_insert = [&](float score, int nid, int len) {
+        int p = 0;
+        while (p < pn && !(score > pS[p])) ++p;             // behind every entry that is not worse: insertion order breaks ties
+        if (p >= bw) return;
+        const int last = pn < bw ? pn : bw - 1;
+        for (int i = last; i > p; --i) { pS[i] = pS[i - 1]; pnid[i] = pnid[i - 1]; plen[i] = plen[i - 1]; }
+        pS[p] = score; pnid[p] = nid; plen[p] = len;
+        pn = pn < bw ? pn + 1 : bw;
+    };
+    const float div_t = q.powa[t], div_D = q.powa[q.D];
+    float nS[BC_MAXBW];
+    int nnid[BC_MAXBW], nrow[BC_MAXBW], ntk[BC_MAXBW];
+    int nn = q.n_nodes[b], nnl = 0;
+    for (int r = 0; r < m; ++r) {
+        const int c = selc[r], j = c / BC_FAN;
+        const int v = q.top_ix[(int64_t)(b * bw + j) * BC_FAN + (c - j * BC_FAN)];
+        const int id = nn < q.NN ? nn : q.NN - 1;          // (NN = 1 + D * W: never exceeded)
+        ntok[id] = v; nprev[id] = oldnid[j];
+        ++nn;
+        if (v == q.eos) {
+            pool_insert(selS[r] / div_t, id, t);
+        } else {
+            nS[nnl] = selS[r]; nnid[nnl] = id; nrow[nnl] = b * bw + j; ntk[nnl] = v;
+            ++nnl;
+        }
+    }
+    q.n_nodes[b] = nn < q.NN ? nn : q.NN;
+    if (t == q.D) {                // unfinished at the depth limit: into the pool as they are, no <eos> appended
+        for (int i = 0; i < nnl; ++i) pool_insert(nS[i] / div_D, nnid[i], t);
+        nnl = 0;
+    }
+    const bool stop = nnl == 0 || (pn == bw && pS[bw - 1] >= nS[0] / div_D);     // (the early stop: see the proof at the top)
+    q.pool_n[b] = pn;
+    for (int i = 0; i < pn; ++i) { q.pool_score[b * bw + i] = pS[i]; q.pool_nid[b * bw + i] = pnid[i]; q.pool_len[b * bw + i] = plen[i]; }
+    if (stop) {
+        nnl = 0;
+        q.done[b] = 1;
+        atomicAdd(q.done_count, 1);
+    }
+    q.n_live[b] = nnl;
+    for (int j = 0; j < bw; ++j) {
+        const bool in = j < nnl;
+        if (in) { lS[j] = nS[j]; lnid[j] = nnid[j]; }
+        q.row_state[b * bw + j] = in ? nrow[j] : 0;
+        q.row_tok[b * bw + j] = in ? ntk[j] : 0;
+    }
+}
+
+// back-trace of the pool's first n_best entries: one thread per (sample, rank)
+__global__ void beam_cum_result_kernel(BeamC q, int n_best, int32_t* out, int32_t* out_len, float* out_score) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= q.B * n_best) return;
+    const int b = i / n_best, k = i - b * n_best;
+    const int* ntok = q.node_tok + (int64_t)b * q.NN;
+    const int* nprev = q.node_prev + (int64_t)b * q.NN;
+    int32_t* o = out + (int64_t)i * q.D;
+    const bool have = k < q.pool_n[b];                     // (always, once the sample is done)
+    int len = have ? q.pool_len[b * q.bw + k] : 0;
+    len = len < q.D ? len : q.D;
+    for (int p = len; p < q.D; ++p) o[p] = q.eos;
+    int node = have ? q.pool_nid[b * q.bw + k] : -1;
+    for (int p = len - 1; p >= 0 && node > 0; --p, node = nprev[node]) o[p] = ntok[node];
+    out_len[i] = len;
+    out_score[i] = have ? q.pool_score[b * q.bw + k] : -INFINITY;
+}
+
+static BeamC carve_beamc(int B, int bw, int D, void* base, size_t* bytes) {
+    char* p = reinterpret_cast<char*>(base);
+    size_t off = 0;
+    auto take = [&](size_t n) { off = align_up(off, 256); char* r = base ? p + off : nullptr; off += n; return r; };
+    const size_t slots = (size_t)B * bw;
+    BeamC q;
+    q.B = B; q.bw = bw; q.D = D; q.NN = 1 + D * bw;
+    q.done_count = reinterpret_cast<int*>(take(sizeof(int)));          // (first: the frozen-sample counter is at byte 0)
+    q.done = reinterpret_cast<int*>(take(sizeof(int) * B));
+    q.n_live = reinterpret_cast<int*>(take(sizeof(int) * B));
+    q.n_nodes = reinterpret_cast<int*>(take(sizeof(int) * B));
+    q.node_tok = reinterpret_cast<int*>(take(sizeof(int) * (size_t)B * q.NN));
+    q.node_prev = reinterpret_cast<int*>(take(sizeof(int) * (size_t)B * q.NN));
+    q.live_S = reinterpret_cast<float*>(take(sizeof(float) * slots));
+    q.live_nid = reinterpret_cast<int*>(take(sizeof(int) * slots));
+    q.pool_n = reinterpret_cast<int*>(take(sizeof(int) * B));
+    q.pool_score = reinterpret_cast<float*>(take(sizeof(float) * slots));
+    q.pool_nid = reinterpret_cast<int*>(take(sizeof(int) * slots));
+    q.pool_len = reinterpret_cast<int*>(take(sizeof(int) * slots));
+    q.powa = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(D + 1)));
+    if (bytes) *bytes = align_up(off, 256);
+    return q;
+}
+
+static bool beamc_dims_ok(int B, int bw, int D) {
+    return B > 0 && bw >= 1 && bw <= BC_MAXBW && D >= 1 && (int64_t)B * (1 + (int64_t)D * bw) < (1ll << 28);
+}
+
+// fp32(len ** alpha) for len = 0..D, evaluated as beam_queue.hip evaluates len ** 0.7 (libm double pow, then fp32), in pinned host
+// memory that lives for the life of the process: the copy to the device is asynchronous (no host synchronisation at the start of a
+// search), so a table is never freed or rewritten - one per distinct alpha, regrown (the shorter one stays) for a larger D.
+static const float* beamc_pow_table(double alpha, int D) {
+    static std::mutex mu;
+    static std::map<double, std::pair<float*, int>> tabs;
+    std::lock_guard<std::mutex> lock(mu);
+    auto& e = tabs[alpha];
+    if (e.second < D + 1) {
+        float* grown = nullptr;
+        const int len = (D + 1 + 1023) / 1024 * 1024;
+        if (hipHostMalloc(reinterpret_cast<void**>(&grown), (size_t)len * sizeof(float), hipHostMallocDefault) != hipSuccess) return nullptr;
+        for (int l = 0; l < len; ++l) grown[l] = l > 0 ? (float)pow((double)l, alpha) : 1.0f;
+        e = {grown, len};
+    }
+    return e.first;
+}
+
+}  // namespace s2vt
+
+using namespace s2vt;
+
+extern "C" {
+
+size_t s2vt_beam_cum_bytes(int32_t B, int32_t beam_width, int32_t max_depth) {
+    if (!beamc_dims_ok(B, beam_width, max_depth)) return 0;
+    size_t bytes = 0;
+    carve_beamc(B, beam_width, max_depth, nullptr, &bytes);
+    return bytes;
+}
+
+int s2vt_beam_cum_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, double length_alpha, int32_t depth,
+                       void* state, size_t state_bytes, const int32_t* top_ix, const float* top_lp, int32_t* row_b, int32_t* row_state,
+                       int32_t* row_tok, void* stream) {
+    S2VT_REQUIRE(beamc_dims_ok(B, beam_width, max_depth) && depth >= 0 && depth <= max_depth && state && row_b && row_state && row_tok,
+                 "s2vt_beam_cum_step: null/invalid argument (1 <= beam_width <= %d, 0 <= depth <= max_depth)", BC_MAXBW);
+    S2VT_REQUIRE(isfinite(length_alpha) && length_alpha >= 0.0, "s2vt_beam_cum_step: length_alpha must be finite and >= 0");
+    S2VT_REQUIRE(depth == 1 || (top_ix && top_lp), "s2vt_beam_cum_step: the step's top-20 arrays are needed from depth 2 on");
+    size_t need = 0;
+    BeamC q = carve_beamc(B, beam_width, max_depth, state, &need);
+    S2VT_REQUIRE(state_bytes >= need, "s2vt_beam_cum_step: state %zu < %zu bytes", state_bytes, need);
+    q.sos = sos_ix; q.eos = eos_ix; q.depth = depth;
+    q.top_ix = top_ix; q.top_lp = top_lp;
+    q.row_b = row_b; q.row_state = row_state; q.row_tok = row_tok;
+    hipStream_t st = (hipStream_t)stream;
+    if (depth == 1) {
+        const float* tab = beamc_pow_table(length_alpha, max_depth);
+        S2VT_REQUIRE(tab, "s2vt_beam_cum_step: no pinned memory for the length table");
+        S2VT_HIP(hipMemcpyAsync(q.powa, tab, (size_t)(max_depth + 1) * sizeof(float), hipMemcpyHostToDevice, st));
+        S2VT_HIP(hipMemsetAsync(q.done_count, 0, sizeof(int), st));
+    }
+    hipLaunchKernelGGL(beam_cum_kernel, dim3(B), dim3(64), 0, st, q);
+    S2VT_LAUNCH_CHECK("beam_cum_kernel");
+    return 0;
+}
+
+int s2vt_beam_cum_result(int32_t B, int32_t beam_width, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state, size_t state_bytes,
+                         int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream) {
+    S2VT_REQUIRE(beamc_dims_ok(B, beam_width, max_depth) && n_best >= 1 && n_best <= beam_width && state && out_tokens && out_len && out_score,
+                 "s2vt_beam_cum_result: null/invalid argument (1 <= n_best <= beam_width <= %d)", BC_MAXBW);
+    size_t need = 0;
+    BeamC q = carve_beamc(B, beam_width, max_depth, state, &need);
+    S2VT_REQUIRE(state_bytes >= need, "s2vt_beam_cum_result: state %zu < %zu bytes", state_bytes, need);
+    q.sos = 0; q.eos = eos_ix; q.depth = 0;
+    q.top_ix = nullptr; q.top_lp = nullptr; q.row_b = q.row_state = q.row_tok = nullptr;
+    hipLaunchKernelGGL(beam_cum_result_kernel, dim3(cdiv(B * n_best, 64)), dim3(64), 0, (hipStream_t)stream, q, n_best, out_tokens, out_len,
+                       out_score);
+    S2VT_LAUNCH_CHECK("beam_cum_result_kernel");
+    return 0;
+}
+
+}  // extern "C"
