@@ -367,6 +367,52 @@ int s2vt_feat_proj_bwd(const s2vt_dims* d, const float* feats, const float* w, c
                        float* dbias, float* dfeats, float* colsum_ws, void* stream);
 size_t s2vt_colsum_ws_floats(int64_t rows, int32_t cols);
 
+/* ---- per-op entry points, TEST SUPPORT (tests/test_gpu_backward_aux.py): the gather / scatter / reorder pieces of the train
+ * backward one at a time, as the whole-path drivers call them.  No kernel of their own.  Each checks its arguments on the host
+ * (null pointers, scratch below the *_ws_* size, geometry) and returns S2VT_ERR_ARG with a message before any launch.
+ *
+ * A row map (idx, inner, outer) names the STORED row of logical row r: idx[r] if idx != NULL (a gather), else
+ * (r % inner) * outer + r / inner if inner != 0 (batch-major <-> time-major; inner * outer = the number of mapped rows), else r. */
+
+/* s2vt_gemm_f32_splitk with a row map on the stored rows of A, B and C (the embedding lookup and every batch-major <->
+ * time-major reorder of gemm mode 0).  The stored rows of A are m if a_kmajor, else k; those of B are n if b_kmajor, else k; a
+ * gather is taken on m / n rows only.  splitk_cap > 0: K is split into at most that many slices (the launcher plans with
+ * min(ws_floats, splitk_cap * M * N) floats of scratch); 0: no cap.  Slice s of a split writes ws[s*M*N .. (s+1)*M*N). */
+int s2vt_gemm_f32_mapped(int32_t a_kmajor, int32_t b_kmajor, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda,
+                         const int32_t* a_idx, int32_t a_inner, int32_t a_outer, const float* B, int64_t ldb, const int32_t* b_idx,
+                         int32_t b_inner, int32_t b_outer, float* C, int64_t ldc, const int32_t* c_idx, int32_t c_inner,
+                         int32_t c_outer, const float* bias, int32_t accumulate, float* ws, size_t ws_floats, int32_t splitk_cap,
+                         void* stream);
+/* Embedding gradient (autograd of S2VTModel.py:71): d_emb[v, :] = sum of d_rows[r, :] over the rows with tok[r] == v, in a fixed
+ * order; EVERY row of d_emb [V, E] is written (zeros for unused ids).  d_rows [rows, E], tok int32 [rows] with ids in [0, V);
+ * ws: >= s2vt_embedding_grad_ws_ints(rows, V) ints, contents irrelevant on entry; on return it holds, for H = rows / 64 + 2,
+ * ws[0 .. n) = the ids with more than 64 matches (summed by the many-row kernel; any order), ws[H] = their number n, and
+ * ws[H + 1 + v] = the number of rows with tok[r] == v. */
+size_t s2vt_embedding_grad_ws_ints(int64_t rows, int32_t V);
+int s2vt_embedding_grad(const float* d_rows, int64_t rows, int32_t E, const int32_t* tok, int32_t V, float* d_emb, int32_t* ws,
+                        size_t ws_ints, void* stream);
+/* out[r, 0:cols] = src[idx[r], 0:cols] (src rows of stride ld, out contiguous); rows <= 65535. */
+int s2vt_gather_rows(const float* src, int64_t ld, const int32_t* idx, int64_t rows, int32_t cols, float* out, void* stream);
+/* out[cols][rows] = in[rows][cols]^T, both contiguous. */
+int s2vt_transpose_f32(const float* in, int32_t rows, int32_t cols, float* out, void* stream);
+/* out[c] (+)= sum_r x[r*ld + c] in a fixed order: partial sums over 64-row chunks into ws[chunk*cols + c]
+ * (>= s2vt_colsum_ws_floats(rows, cols) floats), then s2vt_colsum_finish over the ceil(rows / 64) chunks. */
+int s2vt_colsum(const float* x, int64_t rows, int32_t cols, int64_t ld, float* ws, size_t ws_floats, float* out, int32_t accumulate,
+                void* stream);
+int s2vt_colsum_finish(const float* partial, int32_t nchunks, int32_t cols, float* out, int32_t accumulate, void* stream);
+/* One pass over in [rows][cols] (row stride ld, rows through the row map) that writes any of: out_r, the planes of
+ * s2vt_split_planes(transpose = 0) (rows [0, rows) of the image; kpad_r = cols rounded up to 64); out_t, those of transpose = 1
+ * (kpad_t = rows rounded up to 64); colpart [ceil(rows / 64)][cols], the column sums of each 64-row chunk (s2vt_colsum's partial
+ * sums).  Images as for s2vt_split_planes: 16-byte aligned, whole 64-row blocks, ldo % 8 == 0, ldo >= nplanes * kpad.
+ * With lse (then target, gout too; no row map): `in` holds the logits [B*Lm1][cols] and what is split and summed is the mean-CE
+ * gradient (exp(in[r][c] - lse[r]) - [c == target[b*target_ld + j + 1]]) * gout[0] / rows of row r = b*Lm1 + j, bit for bit
+ * s2vt_mean_ce_backward's.  alpha_out (optional, with lse): only the power of two s2 of the scale gout[0] / rows = alpha * s2,
+ * alpha in [1, 2), goes into the planes; alpha is written to alpha_out[0] and colpart holds alpha * (the sums of the planes' values). */
+int s2vt_split_planes_dual(int32_t nplanes, const float* in, int64_t ld, const int32_t* idx, int32_t inner, int32_t outer, int32_t rows,
+                           int32_t cols, uint16_t* out_r, int64_t ldo_r, int32_t kpad_r, uint16_t* out_t, int64_t ldo_t, int32_t kpad_t,
+                           float* colpart, const float* lse, const int64_t* target, int64_t target_ld, int32_t Lm1, const float* gout,
+                           float* alpha_out, void* stream);
+
 /* One LSTM timestep, gates i,f,g,o (what nn.LSTM runs per step: S2VTModel.py:67,77,86,93,103):
  *   G = gx (or bias if gx == NULL) + h_prev·W_hh^T ; cell update; writes h_out, c_out and, if stash != NULL,
  *   the activated gates [B,4H] for the backward.  h_prev/c_prev NULL = zero state.  Row stride of every

@@ -112,6 +112,18 @@ SIGNATURES = {
     "s2vt_feat_proj_bwd": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),
     "s2vt_colsum_ws_floats": (c_size_t, [c_int64, c_int32]),
+    # per-op test support: the backward's gather / scatter / reorder pieces (tests/test_gpu_backward_aux.py)
+    "s2vt_gemm_f32_mapped": (c_int32, [c_int32] * 5 + [c_void_p, c_int64, c_void_p, c_int32, c_int32] * 3 +
+                             [c_void_p, c_int32, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_embedding_grad_ws_ints": (c_size_t, [c_int64, c_int32]),
+    "s2vt_embedding_grad": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "s2vt_gather_rows": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "s2vt_transpose_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "s2vt_colsum": (c_int32, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_size_t, c_void_p, c_int32, c_void_p]),
+    "s2vt_colsum_finish": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "s2vt_split_planes_dual": (c_int32, [c_int32, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                         c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p,
+                                         c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
     "s2vt_lstm_step_fwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 9),
     "s2vt_lstm_step_fwd_token": (c_int32, [c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
                                                                                             c_int32, c_void_p, c_void_p, c_void_p]),

@@ -139,6 +139,97 @@ int s2vt_feat_proj_fwd(const s2vt_dims* d, const float* feats, const float* w, c
 
 size_t s2vt_colsum_ws_floats(int64_t rows, int32_t cols) { return colsum_partial_floats(rows, cols); }
 
+// ------------------------------------------------------------------ per-op entry points, test support
+// The backward's gather / scatter / reorder pieces one at a time (tests/test_gpu_backward_aux.py): each forwards to the launch
+// function the whole-path drivers call (kernels.h) after checking on the host what a launch would otherwise take on trust.
+static bool rowmap_ok(const int32_t* idx, int32_t inner, int32_t outer, int64_t mapped_rows) {
+    if (inner < 0 || outer < 0) return false;
+    if (inner == 0) return outer == 0;
+    return idx == nullptr && (int64_t)inner * outer == mapped_rows;       // a permutation of exactly the rows it maps
+}
+static RowMap rowmap(const int32_t* idx, int32_t inner, int32_t outer) { return RowMap{idx, inner, outer}; }
+
+int s2vt_gemm_f32_mapped(int32_t a_kmajor, int32_t b_kmajor, int32_t M, int32_t N, int32_t K, const float* A, int64_t lda,
+                         const int32_t* a_idx, int32_t a_inner, int32_t a_outer, const float* B, int64_t ldb, const int32_t* b_idx,
+                         int32_t b_inner, int32_t b_outer, float* C, int64_t ldc, const int32_t* c_idx, int32_t c_inner,
+                         int32_t c_outer, const float* bias, int32_t accumulate, float* ws, size_t ws_floats, int32_t splitk_cap,
+                         void* stream) {
+    S2VT_REQUIRE(M > 0 && N > 0 && K > 0 && A && B && C, "s2vt_gemm_f32_mapped: null operand or non-positive size (M=%d N=%d K=%d)", M, N, K);
+    S2VT_REQUIRE(lda >= (a_kmajor ? K : M) && ldb >= (b_kmajor ? K : N) && ldc >= N,
+                 "s2vt_gemm_f32_mapped: a row stride is shorter than the row it strides over");
+    S2VT_REQUIRE(rowmap_ok(a_idx, a_inner, a_outer, a_kmajor ? M : K) && rowmap_ok(b_idx, b_inner, b_outer, b_kmajor ? N : K) &&
+                     rowmap_ok(c_idx, c_inner, c_outer, M),
+                 "s2vt_gemm_f32_mapped: bad row map (an index and a permutation together, or inner * outer != the mapped rows)");
+    S2VT_REQUIRE(splitk_cap >= 0 && (ws != nullptr || ws_floats == 0), "s2vt_gemm_f32_mapped: bad split-K scratch or cap");
+    // the cap reaches the launcher as the scratch size it may plan with: its own rule n * M * N > scratch ends the search
+    size_t planned = ws ? ws_floats : 0;
+    if (splitk_cap > 0 && (size_t)splitk_cap * M * N < planned) planned = (size_t)splitk_cap * M * N;
+    ProfScope ps((hipStream_t)stream, K_GEMM, 1);
+    return gemm_f32((hipStream_t)stream, a_kmajor != 0, b_kmajor != 0, M, N, K, A, lda, rowmap(a_idx, a_inner, a_outer), B, ldb,
+                    rowmap(b_idx, b_inner, b_outer), C, ldc, rowmap(c_idx, c_inner, c_outer), bias, accumulate != 0, ws, planned);
+}
+
+size_t s2vt_embedding_grad_ws_ints(int64_t rows, int32_t V) {
+    if (rows < 0 || V <= 0) return 0;
+    return embedding_grad_ws_ints(rows, V);
+}
+int s2vt_embedding_grad(const float* d_rows, int64_t rows, int32_t E, const int32_t* tok, int32_t V, float* d_emb, int32_t* ws,
+                        size_t ws_ints, void* stream) {
+    S2VT_REQUIRE(rows >= 0 && rows <= 0x7fffffff && E > 0 && V > 0 && d_emb && ws && (rows == 0 || (d_rows && tok)),
+                 "s2vt_embedding_grad: null argument or bad size (rows=%lld E=%d V=%d)", (long long)rows, E, V);
+    S2VT_REQUIRE(ws_ints >= embedding_grad_ws_ints(rows, V), "s2vt_embedding_grad: scratch %zu < %zu ints", ws_ints,
+                 embedding_grad_ws_ints(rows, V));
+    return embedding_grad((hipStream_t)stream, d_rows, rows, E, tok, V, d_emb, ws);
+}
+
+int s2vt_gather_rows(const float* src, int64_t ld, const int32_t* idx, int64_t rows, int32_t cols, float* out, void* stream) {
+    S2VT_REQUIRE(src && idx && out && rows > 0 && rows <= 65535 && cols > 0 && ld >= cols,
+                 "s2vt_gather_rows: null argument or bad geometry (rows=%lld cols=%d ld=%lld)", (long long)rows, cols, (long long)ld);
+    return gather_rows_f32((hipStream_t)stream, src, ld, idx, rows, cols, out);
+}
+
+int s2vt_transpose_f32(const float* in, int32_t rows, int32_t cols, float* out, void* stream) {
+    S2VT_REQUIRE(in && out && in != out && rows > 0 && cols > 0 && (rows + 63) / 64 <= 65535,
+                 "s2vt_transpose_f32: null argument or bad geometry (rows=%d cols=%d)", rows, cols);
+    return transpose_f32((hipStream_t)stream, in, rows, cols, out);
+}
+
+int s2vt_colsum(const float* x, int64_t rows, int32_t cols, int64_t ld, float* ws, size_t ws_floats, float* out, int32_t accumulate,
+                void* stream) {
+    S2VT_REQUIRE(x && ws && out && rows > 0 && rows <= 64 * (int64_t)65535 && cols > 0 && ld >= cols,
+                 "s2vt_colsum: null argument or bad geometry (rows=%lld cols=%d ld=%lld)", (long long)rows, cols, (long long)ld);
+    S2VT_REQUIRE(ws_floats >= colsum_partial_floats(rows, cols), "s2vt_colsum: scratch %zu < %zu floats", ws_floats,
+                 colsum_partial_floats(rows, cols));
+    return colsum_f32((hipStream_t)stream, x, rows, cols, ld, ws, out, accumulate != 0);
+}
+int s2vt_colsum_finish(const float* partial, int32_t nchunks, int32_t cols, float* out, int32_t accumulate, void* stream) {
+    S2VT_REQUIRE(partial && out && nchunks > 0 && cols > 0, "s2vt_colsum_finish: null argument or bad geometry (nchunks=%d cols=%d)",
+                 nchunks, cols);
+    return colsum_finish((hipStream_t)stream, partial, nchunks, cols, out, accumulate != 0);
+}
+
+int s2vt_split_planes_dual(int32_t nplanes, const float* in, int64_t ld, const int32_t* idx, int32_t inner, int32_t outer, int32_t rows,
+                           int32_t cols, uint16_t* out_r, int64_t ldo_r, int32_t kpad_r, uint16_t* out_t, int64_t ldo_t, int32_t kpad_t,
+                           float* colpart, const float* lse, const int64_t* target, int64_t target_ld, int32_t Lm1, const float* gout,
+                           float* alpha_out, void* stream) {
+    S2VT_REQUIRE((nplanes == 1 || nplanes == 3) && in && rows > 0 && cols > 0 && ld >= cols && (out_r || out_t || colpart),
+                 "s2vt_split_planes_dual: null input, no output, or bad size (planes=%d rows=%d cols=%d)", nplanes, rows, cols);
+    S2VT_REQUIRE(rowmap_ok(idx, inner, outer, rows), "s2vt_split_planes_dual: bad row map");
+    auto image_ok = [&](const uint16_t* p, int64_t ldo, int kpad, int k) {
+        return !p || (kpad % 64 == 0 && kpad >= k && kpad <= 64 * cdiv(k, 64) && ldo % 8 == 0 && ldo >= (int64_t)nplanes * kpad &&
+                      (reinterpret_cast<uintptr_t>(p) & 15) == 0);
+    };
+    S2VT_REQUIRE(image_ok(out_r, ldo_r, kpad_r, cols) && image_ok(out_t, ldo_t, kpad_t, rows),
+                 "s2vt_split_planes_dual: bad plane geometry (kpad = the k extent rounded up to 64, ldo >= planes * kpad, 16-byte aligned)");
+    const bool with_ce = lse || target || gout || alpha_out;
+    if (!with_ce) return split_planes_dual((hipStream_t)stream, nplanes, in, ld, rowmap(idx, inner, outer), rows, cols, out_r, ldo_r,
+                                            kpad_r, out_t, ldo_t, kpad_t, colpart, nullptr);
+    S2VT_REQUIRE(lse && target && gout && Lm1 > 0 && rows % Lm1 == 0 && target_ld >= Lm1 + 1 && !idx && inner == 0,
+                 "s2vt_split_planes_dual: bad CE-gradient arguments (lse, target and gout together, rows = B * Lm1, no row map)");
+    const CeGradArgs ce = {lse, target, gout, Lm1, target_ld, alpha_out};
+    return split_planes_dual((hipStream_t)stream, nplanes, in, ld, ID, rows, cols, out_r, ldo_r, kpad_r, out_t, ldo_t, kpad_t, colpart, &ce);
+}
+
 int s2vt_feat_proj_bwd(const s2vt_dims* d, const float* feats, const float* w, const float* dx1, float* dw,
                        float* dbias, float* dfeats, float* colsum_ws, void* stream) {
     S2VT_REQUIRE(dims_ok(d) && feats && w && dx1 && dw && dbias && colsum_ws, "s2vt_feat_proj_bwd: null/invalid argument");

@@ -658,3 +658,160 @@ def sc_weights(sampled, r_sample, r_greedy, sos_ix, eos_ix):
         capi.check(lib.s2vt_sc_weights(_ptr(sampled), _ptr(r_sample), _ptr(r_greedy), B, T, int(sos_ix), int(eos_ix), _ptr(caps),
                                        _ptr(weight), _stream(dev)), "s2vt_sc_weights")
     return caps, weight
+
+
+# ---------------------------------------------------------------- per-op test support (include/s2vt_hip.h: the backward's
+# gather / scatter / reorder pieces).  Matrices here are float32 ROWS: unit column stride, the row stride is the tensor's own
+# (a column block of a wider tensor is passed as the view it is).
+def _f32rows(t, name):
+    require_hip(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1:
+        raise capi.S2VTHipError("%s must be float32 rows with unit column stride, got %s %s" % (name, t.dtype, tuple(t.stride())))
+    return t
+
+
+def _rowmap(m, name):
+    """(idx pointer, inner, outer) of a row map: None (identity), an int32 tensor (gather) or a pair (inner, outer)"""
+    if m is None:
+        return ctypes.c_void_p(0), 0, 0
+    if isinstance(m, torch.Tensor):
+        require_hip(m, name)
+        if m.dtype != torch.int32 or m.dim() != 1 or not m.is_contiguous():
+            raise capi.S2VTHipError("%s: a gather index must be a contiguous int32 vector" % name)
+        return _ptr(m), 0, 0
+    inner, outer = m
+    return ctypes.c_void_p(0), int(inner), int(outer)
+
+
+def gemm_mapped(a, b, out, a_kmajor=True, b_kmajor=True, amap=None, bmap=None, cmap=None, bias=None, accumulate=False,
+                splitk_ws=None, splitk_cap=0):
+    """out (+)= op(a)·op(b) (+bias) through row maps on the stored rows of a, b and out (s2vt_gemm_f32_mapped).  A map is None,
+    an int32 index tensor (gather; rows m / n only) or (inner, outer).  splitk_ws: fp32 scratch that allows split-K, in at most
+    splitk_cap slices (0: the launcher's own choice)."""
+    lib = capi.load()
+    a, b, out = _f32rows(a, "a"), _f32rows(b, "b"), _f32rows(out, "out")
+    K = a.shape[1] if a_kmajor else a.shape[0]
+    # (a gather stands on m / n rows: the index then counts them; on k rows the library refuses it)
+    M = amap.numel() if isinstance(amap, torch.Tensor) and a_kmajor else (a.shape[0] if a_kmajor else a.shape[1])
+    N = bmap.numel() if isinstance(bmap, torch.Tensor) and b_kmajor else (b.shape[0] if b_kmajor else b.shape[1])
+    if (b.shape[1] if b_kmajor else b.shape[0]) != K:
+        raise ValueError("gemm_mapped: inner dims differ")
+    if out.shape[1] != N or (not isinstance(cmap, torch.Tensor) and out.shape[0] != M):
+        raise ValueError("gemm_mapped: out is %s for M=%d N=%d" % (tuple(out.shape), M, N))
+    (ai, ain, aout), (bi, bin_, bout), (ci, cin, cout) = _rowmap(amap, "amap"), _rowmap(bmap, "bmap"), _rowmap(cmap, "cmap")
+    dev = a.device
+    with torch.cuda.device(dev):
+        capi.check(lib.s2vt_gemm_f32_mapped(int(a_kmajor), int(b_kmajor), M, N, K, _ptr(a), a.stride(0), ai, ain, aout, _ptr(b),
+                                            b.stride(0), bi, bin_, bout, _ptr(out), out.stride(0), ci, cin, cout, _ptr(bias),
+                                            int(accumulate), _ptr(splitk_ws), splitk_ws.numel() if splitk_ws is not None else 0,
+                                            int(splitk_cap), _stream(dev)), "s2vt_gemm_f32_mapped")
+    return out
+
+
+def embedding_grad(d_rows, tok, V, out=None, ws=None):
+    """d_emb [V, E] = index_add of d_rows [rows, E] by tok (int32 [rows]) in a fixed order (s2vt_embedding_grad).  `out` / `ws`
+    (int32 scratch of at least s2vt_embedding_grad_ws_ints) may be handed in pre-filled: every row of out is written."""
+    lib = capi.load()
+    d_rows = _f32c(d_rows, "d_rows")
+    rows, E = d_rows.shape
+    require_hip(tok, "tok")
+    if tok.dtype != torch.int32 or tuple(tok.shape) != (rows,) or not tok.is_contiguous():
+        raise capi.S2VTHipError("embedding_grad: tok must be a contiguous int32 [rows]")
+    dev = d_rows.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(V, E, dtype=torch.float32, device=dev)
+        if ws is None:
+            ws = torch.empty(lib.s2vt_embedding_grad_ws_ints(rows, V), dtype=torch.int32, device=dev)
+        capi.check(lib.s2vt_embedding_grad(_ptr(d_rows) if rows else None, rows, E, _ptr(tok) if rows else None, V, _ptr(out),
+                                           _ptr(ws), ws.numel(), _stream(dev)), "s2vt_embedding_grad")
+    return out
+
+
+def gather_rows(src, idx):
+    """out [rows, cols] = src[idx] (s2vt_gather_rows); src float32 rows, idx int32 [rows]."""
+    lib = capi.load()
+    src = _f32rows(src, "src")
+    iptr, _, _ = _rowmap(idx, "idx")
+    dev = src.device
+    with torch.cuda.device(dev):
+        out = torch.empty(idx.numel(), src.shape[1], dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_gather_rows(_ptr(src), src.stride(0), iptr, idx.numel(), src.shape[1], _ptr(out), _stream(dev)),
+                   "s2vt_gather_rows")
+    return out
+
+
+def transpose(x):
+    """x^T as a new contiguous tensor (s2vt_transpose_f32)."""
+    lib = capi.load()
+    x = _f32c(x, "x")
+    rows, cols = x.shape
+    dev = x.device
+    with torch.cuda.device(dev):
+        out = torch.empty(cols, rows, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_transpose_f32(_ptr(x), rows, cols, _ptr(out), _stream(dev)), "s2vt_transpose_f32")
+    return out
+
+
+def colsum(x, out=None, accumulate=False):
+    """(out [cols] (+)= x.sum(0), partial [ceil(rows / 64), cols]): the fixed-order column sum (s2vt_colsum) and its per-chunk
+    partial sums."""
+    lib = capi.load()
+    x = _f32rows(x, "x")
+    rows, cols = x.shape
+    dev = x.device
+    with torch.cuda.device(dev):
+        ws = torch.empty(lib.s2vt_colsum_ws_floats(rows, cols), dtype=torch.float32, device=dev)
+        if out is None:
+            out = torch.zeros(cols, dtype=torch.float32, device=dev) if accumulate else torch.empty(cols, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_colsum(_ptr(x), rows, cols, x.stride(0), _ptr(ws), ws.numel(), _ptr(out), int(accumulate), _stream(dev)),
+                   "s2vt_colsum")
+    return out, ws.view(-1, cols)
+
+
+def colsum_finish(partial, out=None, accumulate=False):
+    """out [cols] (+)= the fixed-order sum of the rows of partial [nchunks, cols] (s2vt_colsum_finish)."""
+    lib = capi.load()
+    partial = _f32c(partial, "partial")
+    nchunks, cols = partial.shape
+    dev = partial.device
+    with torch.cuda.device(dev):
+        if out is None:
+            out = torch.empty(cols, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_colsum_finish(_ptr(partial), nchunks, cols, _ptr(out), int(accumulate), _stream(dev)), "s2vt_colsum_finish")
+    return out
+
+
+def split_planes_dual(x, nplanes=3, rowmap=None, want_r=True, want_t=False, want_colpart=False, ce=None):
+    """s2vt_split_planes_dual on x (float32 rows): a dict with any of 'r' / 't' (images as split_planes(.) / split_planes(.,
+    transpose=True) return them: zero-filled int16 [ceil64(operand rows), nplanes * kpad]) and 'colpart' [ceil(rows / 64), cols].
+    rowmap: None, an int32 index (then rows = its length) or (inner, outer).  ce = dict(lse, target, Lm1, gout[, alpha]): x holds
+    logits and the mean-CE gradient is what is split (alpha=True: the power-of-two form; 'alpha' is returned as a 1-element tensor)."""
+    lib = capi.load()
+    x = _f32rows(x, "x")
+    cols = x.shape[1]
+    rows = rowmap.numel() if isinstance(rowmap, torch.Tensor) else x.shape[0]
+    idx, inner, outer = _rowmap(rowmap, "rowmap")
+    pad = lambda n: (n + 63) // 64 * 64
+    dev = x.device
+    res = {}
+    with torch.cuda.device(dev):
+        kr, kt = pad(cols), pad(rows)
+        if want_r:
+            res["r"] = torch.zeros(pad(rows), nplanes * kr, dtype=torch.int16, device=dev)
+        if want_t:
+            res["t"] = torch.zeros(pad(cols), nplanes * kt, dtype=torch.int16, device=dev)
+        if want_colpart:
+            res["colpart"] = torch.empty((rows + 63) // 64, cols, dtype=torch.float32, device=dev)
+        lse = target = gout = None
+        ldt = Lm1 = 0
+        if ce is not None:
+            lse, target, gout, Lm1 = ce["lse"], ce["target"], ce["gout"], int(ce["Lm1"])
+            ldt = target.stride(0)
+            if ce.get("alpha"):
+                res["alpha"] = torch.empty(1, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_split_planes_dual(nplanes, _ptr(x), x.stride(0), idx, inner, outer, rows, cols, _ptr(res.get("r")),
+                                              nplanes * kr, kr, _ptr(res.get("t")), nplanes * kt, kt, _ptr(res.get("colpart")),
+                                              _ptr(lse), _ptr(target), ldt, Lm1, _ptr(gout), _ptr(res.get("alpha")), _stream(dev)),
+                   "s2vt_split_planes_dual")
+    return res
