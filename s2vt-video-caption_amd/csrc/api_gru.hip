@@ -64,28 +64,23 @@ static int gru_step_fwd_token_impl(int32_t B, int32_t H, int32_t E, int32_t V, c
         set_error("s2vt_gru_step_fwd_token: token id %d outside [0, %d)", (int)tok_const, (int)V);
         return S2VT_ERR_INDEX;
     }
-    int* flags = nullptr;
-    int rc, rc0 = 0;
+    PostedFlags flags;
+    int rc;
     const bool posts = tok || ss;      // (ids of the caller: a caller's int32 array, or the ground-truth words of a scheduled pass)
-    if (posts) {
-        if ((rc = device_flags(&flags))) return rc;
-        rc0 = poll_async_error(false);
-        if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
-    }
+    if (posts && (rc = flags.open(st))) return rc;
     GruFwdArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.H = H;
     a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H; a.b_hh = b_hh;
     a.gx = gx; a.ldgx = 3 * (int64_t)H;
     a.x2 = emb; a.ldx2 = E; a.K2 = E; a.w2 = w_e; a.ldw2 = ldw_e;
-    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags, ss ? *ss : SsArgs{}};
+    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags.p, ss ? *ss : SsArgs{}};
     a.h_out = h_out; a.ldho = H;
     {
         ProfScope ps(st, K_STEP_FWD, 1);
         if ((rc = gru_step_fwd(st, a))) return rc;
     }
-    if (!posts) return 0;
-    return rc0 ? rc0 : post_async_error(st, flags, 3);
+    return flags.close(st, 3);
 }
 extern "C" {
 
@@ -163,13 +158,11 @@ int s2vt_gru_seq_bwd(int32_t T, int32_t B, int32_t H, const float* w_hh, const f
 int s2vt_tokens_time_major(int32_t B, int32_t Lm1, int32_t V, const int64_t* targets, int64_t targets_ld, int32_t* tok, void* stream) {
     S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0 && targets && tok && targets_ld >= Lm1, "s2vt_tokens_time_major: null/invalid argument");
     hipStream_t st = (hipStream_t)stream;
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
-    if ((rc = targets_to_time_major(st, targets, B, Lm1, targets_ld, V, tok, flags))) return rc;
-    return rc0 ? rc0 : post_async_error(st, flags, 0);
+    if ((rc = flags.open(st))) return rc;
+    if ((rc = targets_to_time_major(st, targets, B, Lm1, targets_ld, V, tok, flags.p))) return rc;
+    return flags.close(st, 0);
 }
 
 }  // extern "C"

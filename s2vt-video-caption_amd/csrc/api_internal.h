@@ -35,6 +35,16 @@ const char* last_error_text();
 int poll_async_error(bool wait);
 int post_async_error(hipStream_t st, const int* dev_flags, int kind = 0);
 int device_flags(int** out);
+// The flag words of a per-op entry point that has no workspace of its own, and the protocol around them: open() before the
+// work - fetch the device's words, poll (an earlier call's error, if its flags have arrived, is kept), zero the words on st;
+// close() after it - that earlier error if there was one, else post this call's flags as a record of `kind`.  A PostedFlags
+// that was never opened (p == nullptr: the call reads no id of the caller's) closes as 0 without posting.
+struct PostedFlags {
+    int* p = nullptr;
+    int rc0 = 0;
+    int open(hipStream_t st);
+    int close(hipStream_t st, int kind);
+};
 
 // live kernel timing: launch sites bracket kernels of one kind with hipEvents on the launch stream while s2vt_prof_enable(1)
 enum { K_GEMM = 0, K_STEP_FWD = 1, K_STEP_BWD = 2, K_CE = 3, K_ARGMAX = 4, K_GEMM_CORUN = 5, K_NKINDS = 6 };   // (5: a GEMM planned for PART of the

@@ -18,17 +18,15 @@ int s2vt_mean_ce_forward(int32_t B, int32_t Lm1, int32_t V, const float* logits,
     S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0, "s2vt_mean_ce_forward: bad dims");
     hipStream_t st = (hipStream_t)stream;
     // target ids outside [0, V): flagged on the device, reported like the embedding's (s2vt_check_async_error)
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    if ((rc = flags.open(st))) return rc;
     {
         ProfScope ps(st, K_CE, 1);
-        if ((rc = mean_ce_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, lse, rowloss, loss_out, flags)))
+        if ((rc = mean_ce_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, lse, rowloss, loss_out, flags.p)))
             return rc;
     }
-    return rc0 ? rc0 : post_async_error(st, flags, 2);
+    return flags.close(st, 2);
 }
 int s2vt_mean_ce_backward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target,
                           int64_t target_ld, const float* lse, const float* gout, float* dlogits, void* stream) {
@@ -44,17 +42,15 @@ int s2vt_mask_criterion_forward(int32_t B, int32_t Lm1, int32_t V, const float* 
                                 const float* mask, int64_t mask_ld, float* lse, float* rowloss, float* out3, void* stream) {
     S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0 && mask_ld >= Lm1 + 1, "s2vt_mask_criterion_forward: bad dims");
     hipStream_t st = (hipStream_t)stream;
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    if ((rc = flags.open(st))) return rc;
     {
         ProfScope ps(st, K_CE, 1);
-        if ((rc = mask_criterion_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, mask, mask_ld, lse, rowloss, out3, flags)))
+        if ((rc = mask_criterion_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, mask, mask_ld, lse, rowloss, out3, flags.p)))
             return rc;
     }
-    return rc0 ? rc0 : post_async_error(st, flags, 2);
+    return flags.close(st, 2);
 }
 // Its autograd down to the mean CE: g_ce[0] = sum_i (gout[0] / sum(w)) * w_i - the `gout` of s2vt_mean_ce_backward[_fused].
 int s2vt_mask_criterion_backward(int32_t B, int32_t Lm1, const float* mask, int64_t mask_ld, const float* out3, const float* gout,
@@ -70,17 +66,15 @@ int s2vt_weighted_ce_forward(int32_t B, int32_t Lm1, int32_t V, const float* log
     S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0 && target_ld >= Lm1 + 1 && weight_ld >= Lm1 + 1, "s2vt_weighted_ce_forward: bad dims");
     S2VT_REQUIRE(logits && target && weight && lse && rowloss && out2, "s2vt_weighted_ce_forward: null argument");
     hipStream_t st = (hipStream_t)stream;
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    if ((rc = flags.open(st))) return rc;
     {
         ProfScope ps(st, K_CE, 1);
-        if ((rc = weighted_ce_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, weight, weight_ld, lse, rowloss, out2, flags)))
+        if ((rc = weighted_ce_fwd(st, logits, (int64_t)B * Lm1, V, target, Lm1, target_ld, weight, weight_ld, lse, rowloss, out2, flags.p)))
             return rc;
     }
-    return rc0 ? rc0 : post_async_error(st, flags, 2);
+    return flags.close(st, 2);
 }
 int s2vt_weighted_ce_backward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target, int64_t target_ld,
                               const float* weight, int64_t weight_ld, const float* lse, const float* out2, const float* gout,
@@ -266,17 +260,15 @@ int s2vt_lstm_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const f
     S2VT_REQUIRE(B > 0 && H > 0 && E > 0 && V > 0 && gx && w_hh && emb && w_e && h_out && c_out && ldw_e >= E,
                  "s2vt_lstm_step_fwd_token: null/invalid argument");
     hipStream_t st = (hipStream_t)stream;
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    if ((rc = flags.open(st))) return rc;
     StepFwdArgs a;
     memset(&a, 0, sizeof(a));
     a.B = B; a.H = H;
     a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H;
     a.x2 = emb; a.ldx2 = E; a.K2 = E; a.w2 = w_e; a.ldw2 = ldw_e;
-    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags, {}};
+    a.tok = TokenSrc{tok, tok_packed, tok_const, V, flags.p, {}};
     a.gx = gx; a.ldgx = 4 * (int64_t)H;
     a.c_prev = c_prev; a.ldc = H;
     a.h_out = h_out; a.ldho = H; a.c_out = c_out; a.ldco = H;
@@ -284,7 +276,7 @@ int s2vt_lstm_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const f
         ProfScope ps(st, K_STEP_FWD, 1);
         if ((rc = lstm_step_fwd(st, a))) return rc;
     }
-    return rc0 ? rc0 : post_async_error(st, flags, 2);
+    return flags.close(st, 2);
 }
 
 int s2vt_lstm_step_bwd(int32_t B, int32_t H, const float* dg_next, const float* w_hh_t, const float* dh_out,

@@ -104,6 +104,16 @@ int device_flags(int** out) {
     *out = flags_of[dev];
     return 0;
 }
+int PostedFlags::open(hipStream_t st) {
+    int rc;
+    if ((rc = device_flags(&p))) return rc;
+    rc0 = poll_async_error(false);
+    return fill_zero(st, p, 4 * sizeof(int));
+}
+int PostedFlags::close(hipStream_t st, int kind) {
+    if (!p) return 0;
+    return rc0 ? rc0 : post_async_error(st, p, kind);
+}
 
 // ------------------------------------------------------------------ live kernel timing
 static bool g_prof = false;

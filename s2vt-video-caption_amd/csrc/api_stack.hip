@@ -44,15 +44,10 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
     const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
     // a scheduled-sampling token segment reads the caller's ground-truth ids: a bad one is posted on the ring of the
     // asynchronous-error table (as s2vt_gru_step_fwd_token does for a caller's int32 ids), so a loop of steps never waits
-    int* flags = nullptr;
-    int rc0 = 0;
+    PostedFlags flags;
     bool posts = false;
     for (int j = 0; j < n; ++j) posts = posts || (layers[j].emb && layers[j].ss_targets);
-    if (posts) {
-        if ((rc = device_flags(&flags))) return rc;
-        rc0 = poll_async_error(false);
-        if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
-    }
+    if (posts && (rc = flags.open(st))) return rc;
     for (int d = 0; d < T + n - 1; ++d) {
         ChainFwdLaunch a;
         memset(&a, 0, sizeof(a));
@@ -79,7 +74,7 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
                 if (l.ss_targets) {
                     s.tok.ss = SsArgs{l.ss_targets, l.ss_ld, l.ss_prob, (uint32_t)(l.ss_seed & 0xFFFFFFFFull), (uint32_t)(l.ss_seed >> 32),
                                       (uint32_t)l.ss_step, (uint32_t)l.ss_row0, (uint32_t)l.ss_row0 + (uint32_t)B};
-                    s.tok.tok_err = flags;
+                    s.tok.tok_err = flags.p;
                 }
             }
             s.mask = l.mask ? l.mask + t * BH : nullptr;
@@ -93,8 +88,7 @@ int s2vt_lstm_chain_fwd(int32_t T, int32_t B, int32_t H, int32_t n, const s2vt_l
         }
         if (a.n && (rc = lstm_chain_fwd_launch(st, a))) return rc;
     }
-    if (!posts) return 0;
-    return rc0 ? rc0 : post_async_error(st, flags, 3);
+    return flags.close(st, 3);
 }
 
 size_t s2vt_lstm_chain_bwd_workspace_bytes(int32_t B, int32_t H, int32_t n) {

@@ -230,16 +230,14 @@ int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, 
                      tb.n_idf >= 0 && (tb.n_idf == 0 || (tb.idf_keys && tb.idf_vals)),
                  "s2vt_cider_rewards: incomplete table");
     hipStream_t st = (hipStream_t)stream;
-    int* flags = nullptr;
+    PostedFlags flags;
     int rc;
-    if ((rc = device_flags(&flags))) return rc;
-    const int rc0 = poll_async_error(false);
-    if ((rc = fill_zero(st, flags, 4 * sizeof(int)))) return rc;
+    if ((rc = flags.open(st))) return rc;
     hipLaunchKernelGGL(cider_rewards_kernel, dim3((unsigned)B), dim3(kCiderThreads), 0, st, tb, clip_rows, ids, (int)T, ld, (int)sos,
-                       (int)eos, out, flags);
+                       (int)eos, out, flags.p);
     S2VT_LAUNCH_CHECK("cider_rewards_kernel");
     // two calls per self-critical step: the ring of records, so that a call never waits for the copy of the one before it
-    return rc0 ? rc0 : post_async_error(st, flags, 3);
+    return flags.close(st, 3);
 }
 
 int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t T, int32_t sos,

@@ -36,7 +36,7 @@ int split_planes(hipStream_t s, int nplanes, bool transpose, const float* in, in
                  unsigned short* out, int64_t ldo, int kpad, int out_rows_pad);
 
 // optional input transform of split_planes_dual: the input is the logits [B*(L-1)][V] (batch-major rows) and what is split is
-// the mean-CE gradient (exp(logit - lse[r]) - onehot(target)) * gout / rows (ce.hip: ce_bwd_kernel's expression)
+// the mean-CE gradient (exp(logit - lse[r]) - onehot(target)) * gout / rows (row_frame.h: ce_grad, as ce.hip's ce_bwd_kernel)
 struct CeGradArgs {
     const float* lse;            // [rows] from mean_ce_fwd
     const int64_t* target;       // [B][ldt]: row r = b*Lm1 + j reads target[b*ldt + j + 1]

@@ -4,6 +4,7 @@
 // ever sees the k-contiguous "NT" form.  Rows and columns are padded with zeros to multiples of 8 elements.
 #include "common.h"
 #include "kernels.h"
+#include "row_frame.h"
 
 namespace s2vt {
 
@@ -135,8 +136,8 @@ __global__ __launch_bounds__(256) void split_transpose_kernel(const float* in, i
 // Tensors that feed both a data-gradient GEMM (row planes) and a weight-gradient GEMM (transposed planes) — dG,
 // dlogits, h, x1, the weights themselves — are read from HBM once.
 // CE = true: the input is the LOGITS and the value that is split is the mean-CE gradient (utils.py:22 under loss.backward())
-//   d[r][c] = (exp(logit[r][c] - lse[r]) - [c == target(r)]) * gout / rows
-// - the expression of ce_bwd_kernel (ce.hip), evaluated here so that the fp32 dlogits tensor is never written and re-read
+//   d[r][c] = ce_grad(logit[r][c], lse[r], c == target(r), gout / rows)
+// - ce_bwd_kernel's element (ce.hip; the function is row_frame.h's), evaluated here so that the fp32 dlogits tensor is never written and re-read
 // (971 MB each way at B = 256): the planes and the bias-gradient partial sums come out bit for bit as from the two-kernel route.
 template <int NP, bool CE>
 __global__ __launch_bounds__(256) void split_dual_kernel(const float* in, int64_t ld, RowMap imap, int rows, int cols,
@@ -158,8 +159,7 @@ __global__ __launch_bounds__(256) void split_dual_kernel(const float* in, int64_
             int64_t t = 0;
             float l = 0.f;
             if (r < rows) {
-                t = ce.target[(int64_t)(r / ce.Lm1) * ce.ldt + (r % ce.Lm1) + 1];
-                t = t < 0 ? 0 : (t >= cols ? cols - 1 : t);
+                t = clamp_target(shifted_col(ce.target, r, ce.Lm1, ce.ldt), cols);
                 l = ce.lse[r];
             }
             row_tgt[threadIdx.x] = (int)t;
@@ -193,7 +193,7 @@ __global__ __launch_bounds__(256) void split_dual_kernel(const float* in, int64_
             if (CE) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
-                    x[j] = (c + j < cols) ? (expf(x[j] - row_lse[rl]) - (c + j == row_tgt[rl] ? 1.f : 0.f)) * ce_scale : 0.f;
+                    x[j] = (c + j < cols) ? ce_grad(x[j], row_lse[rl], c + j == row_tgt[rl], ce_scale) : 0.f;
             }
         }
         *reinterpret_cast<f32x4*>(&tile[rl][cl ^ TSW(rl)]) = x;

@@ -357,6 +357,25 @@ def _ce_inputs(logits, target):
     return logits, target
 
 
+def _row_matrix(t, name, B, L):
+    """A criterion's mask / weight as the kernels read it: fp32, 2-D with unit column stride, [B, L]"""
+    require_hip(t, name)
+    if t.dtype != torch.float32:
+        t = t.float()
+    if t.dim() != 2 or t.stride(1) != 1:
+        t = t.reshape(t.shape[0], -1).contiguous()
+    if t.shape[0] != B or t.shape[1] != L:
+        raise ValueError("%s must be [B, L] = [%d, %d], got %s" % (name, B, L, tuple(t.shape)))
+    return t
+
+
+def _ce_scratch(B, Lm1, extra, dev):
+    """One allocation behind a criterion's forward: lse [B * Lm1], rowloss [B * Lm1] and the finisher's `extra` output words"""
+    rows = B * Lm1
+    scratch = torch.empty(2 * rows + extra, dtype=torch.float32, device=dev)
+    return scratch[:rows], scratch[rows:2 * rows], scratch[2 * rows:]
+
+
 def _fusable_train_node(logits):
     """The _TrainForward node behind `logits` when the criterion's backward may write the dlogits operand planes into that
     forward's workspace instead of a [B, L-1, V] fp32 tensor (fused route), else None."""
@@ -391,8 +410,7 @@ class _MeanCE(torch.autograd.Function):
         B, Lm1, V = logits.shape
         dev = logits.device
         with torch.cuda.device(dev):
-            scratch = torch.empty(2 * B * Lm1 + 1, dtype=torch.float32, device=dev)
-            lse, rowloss, loss = scratch[:B * Lm1], scratch[B * Lm1:2 * B * Lm1], scratch[2 * B * Lm1:]
+            lse, rowloss, loss = _ce_scratch(B, Lm1, 1, dev)
             capi.check(lib.s2vt_mean_ce_forward(B, Lm1, V, _ptr(logits), _ptr(target), target.stride(0), _ptr(lse),
                                                 _ptr(rowloss), _ptr(loss), _stream(dev)), "s2vt_mean_ce_forward")
         ctx.save_for_backward(logits, target, lse)
@@ -413,18 +431,11 @@ class _MaskCriterion(torch.autograd.Function):
     def forward(ctx, logits, target, mask):
         lib = capi.load()
         logits, target = _ce_inputs(logits, target)
-        require_hip(mask, "mask")
-        if mask.dtype != torch.float32:
-            mask = mask.float()
-        if mask.dim() != 2 or mask.stride(1) != 1:
-            mask = mask.reshape(mask.shape[0], -1).contiguous()
         B, Lm1, V = logits.shape
-        if mask.shape[0] != B or mask.shape[1] != Lm1 + 1:
-            raise ValueError("mask must be [B, L] = [%d, %d], got %s" % (B, Lm1 + 1, tuple(mask.shape)))
+        mask = _row_matrix(mask, "mask", B, Lm1 + 1)
         dev = logits.device
         with torch.cuda.device(dev):
-            scratch = torch.empty(2 * B * Lm1 + 4, dtype=torch.float32, device=dev)
-            lse, rowloss, out3 = scratch[:B * Lm1], scratch[B * Lm1:2 * B * Lm1], scratch[2 * B * Lm1:]
+            lse, rowloss, out3 = _ce_scratch(B, Lm1, 4, dev)
             capi.check(lib.s2vt_mask_criterion_forward(B, Lm1, V, _ptr(logits), _ptr(target), target.stride(0), _ptr(mask),
                                                        mask.stride(0), _ptr(lse), _ptr(rowloss), _ptr(out3), _stream(dev)),
                        "s2vt_mask_criterion_forward")
@@ -453,18 +464,11 @@ class _WeightedCE(torch.autograd.Function):
     def forward(ctx, logits, target, weight):
         lib = capi.load()
         logits, target = _ce_inputs(logits, target)
-        require_hip(weight, "weight")
-        if weight.dtype != torch.float32:
-            weight = weight.float()
-        if weight.dim() != 2 or weight.stride(1) != 1:
-            weight = weight.reshape(weight.shape[0], -1).contiguous()
         B, Lm1, V = logits.shape
-        if weight.shape[0] != B or weight.shape[1] != Lm1 + 1:
-            raise ValueError("weight must be [B, L] = [%d, %d], got %s" % (B, Lm1 + 1, tuple(weight.shape)))
+        weight = _row_matrix(weight, "weight", B, Lm1 + 1)
         dev = logits.device
         with torch.cuda.device(dev):
-            scratch = torch.empty(2 * B * Lm1 + 2, dtype=torch.float32, device=dev)
-            lse, rowloss, out2 = scratch[:B * Lm1], scratch[B * Lm1:2 * B * Lm1], scratch[2 * B * Lm1:]
+            lse, rowloss, out2 = _ce_scratch(B, Lm1, 2, dev)
             capi.check(lib.s2vt_weighted_ce_forward(B, Lm1, V, _ptr(logits), _ptr(target), target.stride(0), _ptr(weight),
                                                     weight.stride(0), _ptr(lse), _ptr(rowloss), _ptr(out2), _stream(dev)),
                        "s2vt_weighted_ce_forward")

@@ -564,7 +564,10 @@ def test_lstm_seq_fwd_bwd_vs_autograd(lib):
     assert (dw - w_hh.grad).abs().max().item() < 2e-5
 
 
-@pytest.mark.parametrize("B,Lm1,V", [(3, 7, 50), (4, 79, 100), (2, 5, 12000), (1, 1, 3)])
+# V selects the path of ce_row_kernel / ce_grad_row: scalar (V % 4 != 0: 50, 3, 1027), the row in registers (V % 4 == 0 up to 16384:
+# 100, 12000, 1028, 16384), the 16-byte loop (V % 4 == 0 beyond: 16388)
+@pytest.mark.parametrize("B,Lm1,V", [(3, 7, 50), (4, 79, 100), (2, 5, 12000), (1, 1, 3), (1, 2, 16388), (2, 3, 16384), (2, 3, 1028),
+                                     (2, 3, 1027)])
 def test_mean_ce_fwd_bwd(lib, B, Lm1, V):
     from s2vt_video_caption_amd import functional as F
     logits = _r(B, Lm1, V, seed=1, scale=3.0)
@@ -886,6 +889,118 @@ def test_beam_step_at_config5_size(lib):
     assert int((~same).sum()) <= 2
     assert (tix[:, 1:] > tix[:, :-1]).all()                                                        # ascending token order
     assert (tlp - logp.gather(1, tix.long())).abs().max() < tol
+
+
+# ---- the top-20 fan-out (ce.hip: top20_logprob_kernel<Row>) in every instantiation, through s2vt_beam_step
+_TOP20_DIMS = (2, 4, 16, 16, 16)          # B, L, F, H, E: as small as the step kernels take; only V selects the top-20 kernel
+# V on the bracket edges of top20_logprob: RegRow<16> up to 4096 (20: the smallest legal vocabulary), <32> to 8192, <48> to 12288,
+# <64> to 16384, then the LDS form (16385: 65.5 KB of dynamic LDS, past the 48 KB attribute switch; 38400: the stated maximum)
+_TOP20_V = [20, 257, 4096, 4097, 8192, 8193, 12288, 12289, 16384, 16385, 38400]
+
+
+def _tie_bias(V, seed):
+    """out_linear.bias with planted exact ties, all of it inside (-1, 1): the scale of the logits of
+    test_beam_step_matches_cell_and_topk (about +-0.5 there), whose 5e-6 on the log-probs is asserted here.  Thread tid of the
+    kernel owns the ids tid + 256 j.  Background U(-0.5, 0.5); above it
+      0.9 at ids 0 and 256 k (the last multiple of 256 below V): a tie inside ONE thread
+      0.8 at ids 10 and 11: a tie between two threads
+      15 distinct values 0.7 - j / 256 at seeded ids: with the four above, 19 values above 0.6
+      0.6 at ids 5, 6 and 261: the 20th place and the two behind it are equal - id 5 takes it
+    V = 20 has no 21st place: the ties at (10, 11) and (5, 6) only, every id is selected."""
+    g = torch.Generator().manual_seed(seed)
+    bias = torch.rand(V, generator=g) - 0.5
+    bias[10] = bias[11] = 0.8
+    bias[5] = bias[6] = 0.6
+    if V > 20:
+        taken = {0, (V - 1) // 256 * 256, 10, 11, 5, 6, 261}
+        bias[0] = bias[(V - 1) // 256 * 256] = 0.9
+        if V > 261:
+            bias[261] = 0.6
+        free = [i for i in torch.randperm(V, generator=g).tolist() if i not in taken][:15]
+        for j, i in enumerate(free):
+            bias[i] = 0.7 - j / 256.0
+    return bias
+
+
+@pytest.mark.parametrize("V", _TOP20_V)
+def test_top20_every_instantiation_exact_logits_and_ties(lib, V):
+    """out_linear.weight = 0: the logits ARE the bias, so the expected ids are known exactly - the 20 best under (value
+    descending, id ascending), returned ascending - and the log-probs come from an fp64 log_softmax of the bias."""
+    from s2vt_video_caption_amd import ops, synth, capi
+    B, L, F, H, E = _TOP20_DIMS
+    R = 5
+    sd = synth.make_state_dict(V, F, H, E, seed=9)
+    sd["out_linear.weight"].zero_()
+    bias = sd["out_linear.bias"] = _tie_bias(V, seed=V)
+    g = torch.Generator().manual_seed(3)
+    row_b = torch.randint(0, B, (R,), generator=g, dtype=torch.int32)
+    row_state = torch.randint(0, 7, (R,), generator=g, dtype=torch.int32)
+    tok = torch.randint(0, V, (R,), generator=g, dtype=torch.int32)
+    out = ops.beam_step([sd[k].to(DEV) for k in capi.PARAM_KEYS], (B, L, F, H, E, V), row_b.to(DEV), row_state.to(DEV), tok.to(DEV),
+                        _r(B, H, seed=1, scale=0.5).to(DEV), _r(B, H, seed=2, scale=0.5).to(DEV),
+                        _r(7, H, seed=3, scale=0.5).to(DEV), _r(7, H, seed=4, scale=0.5).to(DEV))
+    tix, tlp = out[4].cpu(), out[5].cpu()
+    order = np.lexsort((np.arange(V), -bias.numpy()))             # value descending, then id ascending
+    if V > 20:
+        assert bias[order[19]] == bias[order[20]] and order[19] == 5 and order[20] == 6     # the planted tie straddles the cut
+    rix = torch.from_numpy(np.sort(order[:20])).long()
+    assert torch.equal(tix.long(), rix[None, :].expand(R, 20))
+    logp = torch.log_softmax(bias.double(), 0)[rix]
+    err = (tlp.double() - logp[None, :]).abs().max().item()
+    print("V %d: max |log-prob - fp64| = %.3g" % (V, err))
+    assert err < 5e-6
+
+
+@pytest.mark.parametrize("V", [257, 8192, 12288, 16384, 16385])
+def test_top20_every_bracket_random_weights(lib, V):
+    """test_beam_step_matches_cell_and_topk's assertions at one vocabulary per top-20 instantiation"""
+    from s2vt_video_caption_amd import ops, synth, capi
+    B, L, F, H, E = _TOP20_DIMS
+    R = 5
+    sd = synth.make_state_dict(V, F, H, E, seed=9)
+    params = [sd[k] for k in capi.PARAM_KEYS]
+    g = torch.Generator().manual_seed(3)
+    row_b = torch.randint(0, B, (R,), generator=g, dtype=torch.int32)
+    row_state = torch.randint(0, 7, (R,), generator=g, dtype=torch.int32)
+    tok = torch.randint(0, V, (R,), generator=g, dtype=torch.int32)
+    vid_h, vid_c = _r(B, H, seed=1, scale=0.5), _r(B, H, seed=2, scale=0.5)
+    word_h, word_c = _r(7, H, seed=3, scale=0.5), _r(7, H, seed=4, scale=0.5)
+    out = ops.beam_step([p.to(DEV) for p in params], (B, L, F, H, E, V), row_b.to(DEV), row_state.to(DEV), tok.to(DEV),
+                        vid_h.to(DEV), vid_c.to(DEV), word_h.to(DEV), word_c.to(DEV))
+    vh, vc, wh, wc, tix, tlp = [t.cpu() for t in out]
+    w_ih1, w_hh1, b_ih1, b_hh1, w_ih2, w_hh2, b_ih2, b_hh2, w_f, b_f, w_o, b_o, emb = params
+    rvh, rvc = orc.lstm_cell(torch.zeros(B, H), vid_h, vid_c, w_ih1, w_hh1, b_ih1, b_hh1)
+    x = torch.cat([emb[tok.long()], rvh[row_b.long()]], dim=1)
+    rwh, rwc = orc.lstm_cell(x, word_h[row_state.long()], word_c[row_state.long()], w_ih2, w_hh2, b_ih2, b_hh2)
+    logp = torch.log_softmax(rwh @ w_o.t() + b_o, dim=1)
+    rix = logp.topk(20, dim=1).indices.sort(dim=1).values
+    assert (vh - rvh).abs().max() < 2e-6 and (vc - rvc).abs().max() < 2e-6
+    assert (wh - rwh).abs().max() < 2e-6 and (wc - rwc).abs().max() < 2e-6
+    assert torch.equal(tix.long(), rix)
+    assert (tlp - logp.gather(1, rix)).abs().max() < 5e-6
+
+
+@pytest.mark.parametrize("B,Lm1,V", [(2, 3, 300), (1, 2, 16388)])
+def test_fused_and_materialised_criterion_backward_agree_in_bits(lib, B, Lm1, V):
+    """The default training path splits the criterion's gradient straight from the logits (split_dual_kernel<*, true>); the tests
+    compare against the tensor s2vt_mean_ce_backward materialises (ce_bwd_kernel).  Both evaluate row_frame.h's ce_grad: the
+    row-plane images of the two routes are equal bit for bit (they were at the commit before the shared function, too)."""
+    from s2vt_video_caption_amd import ops, capi
+    R = B * Lm1
+    logits = _r(R, V, seed=5, scale=3.0).to(DEV)
+    target = torch.randint(0, V, (B, Lm1 + 1), generator=torch.Generator().manual_seed(6)).to(DEV)
+    gout = torch.tensor([0.37], dtype=torch.float32, device=DEV)
+    scratch = torch.empty(2 * R + 1, device=DEV)
+    lse = scratch[:R]
+    capi.check(lib.s2vt_mean_ce_forward(B, Lm1, V, logits.data_ptr(), target.data_ptr(), target.stride(0), lse.data_ptr(),
+                                        scratch[R:2 * R].data_ptr(), scratch[2 * R:].data_ptr(), None), "s2vt_mean_ce_forward")
+    dlogits = torch.empty_like(logits)
+    capi.check(lib.s2vt_mean_ce_backward(B, Lm1, V, logits.data_ptr(), target.data_ptr(), target.stride(0), lse.data_ptr(),
+                                         gout.data_ptr(), dlogits.data_ptr(), None), "s2vt_mean_ce_backward")
+    assert bool(torch.isfinite(dlogits).all()) and float(dlogits.abs().max()) > 0
+    fused = ops.split_planes_dual(logits, nplanes=3, ce=dict(lse=lse, target=target, Lm1=Lm1, gout=gout))["r"]
+    assert torch.equal(fused, ops.split_planes_dual(dlogits, nplanes=3)["r"])
+    capi.check_async_error()
 
 
 # ---------------------------------------------------------------------------------------------- config-3 (bf16) kernels

@@ -354,7 +354,7 @@ def _reward_case(B, L, V, seed):
     return logits, target, weight
 
 
-@pytest.mark.parametrize("B,L,V", [(1, 5, 50), (7, 9, 301), (64, 12, 1000)])
+@pytest.mark.parametrize("B,L,V", [(1, 5, 50), (7, 9, 301), (64, 12, 1000), (2, 4, 16388), (3, 5, 1027)])
 def test_reward_criterion_matches_float64_autograd(lib, B, L, V):
     import utils
     logits, target, weight = _reward_case(B, L, V, 50 + B)
@@ -399,6 +399,23 @@ def test_reward_criterion_all_zero_weight_and_bad_target(lib):
     torch.cuda.synchronize()
     with pytest.raises(IndexError):
         capi.check_async_error()
+
+
+def test_bad_id_of_the_second_of_two_flagged_entry_points_is_reported_once(lib):
+    """Two per-op entry points that share the device's flag words (PostedFlags), back to back: the mean CE with good targets,
+    then s2vt_tokens_time_major with one bad id.  The first call's record is clean, the second's is not: one IndexError."""
+    from s2vt_video_caption_amd import functional as F
+    capi.check_async_error()
+    logits, target, _ = _reward_case(3, 6, 40, 2)
+    loss = F.mean_cross_entropy(logits.to(DEV), target.to(DEV))
+    bad = target.clone()
+    bad[1, 2] = 40
+    tok = ops.tokens_time_major(bad.to(DEV), 5, 40)
+    torch.cuda.synchronize()
+    assert bool(torch.isfinite(loss)) and int(tok.max()) < 40           # (the bad id is clamped)
+    with pytest.raises(IndexError):
+        capi.check_async_error()
+    capi.check_async_error()
 
 
 def test_reward_criterion_trains_the_model_on_sampled_ids(lib):

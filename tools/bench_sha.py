@@ -1,4 +1,4 @@
-"""What the A/B bench tools (bench_persist.py, bench_step_kernels.py) print per line: a tag and the sha1 of every output tensor of
+"""What the A/B bench tools (bench_persist.py, bench_step_kernels.py, bench_criterion.py) print per line: a tag and the sha1 of every output tensor of
 every timed run, so that two library builds on one box can be compared for speed AND for bit-equal results."""
 import hashlib
 

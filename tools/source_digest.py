@@ -16,7 +16,8 @@ KERNEL_SOURCES = {
     "lstm_step_fwd_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"], "lstm_step_bwd_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"],
     "lstm_step_fwd_bf16_kernel": ["lstm_bf16.hip"], "lstm_step_bwd_bf16_kernel": ["lstm_bf16.hip"],
     "logits_argmax_x3_kernel": ["argmax_x3.hip"], "logits_argmax_kernel": ["lstm.hip", "step_frame.h", "mfma_tile.h"],
-    "split_dual_kernel": ["split.hip"], "split3_rows_kernel": ["split.hip"],
+    "split_dual_kernel": ["split.hip", "row_frame.h"], "split3_rows_kernel": ["split.hip"],
+    "ce_row_kernel": ["ce.hip", "row_frame.h"], "ce_bwd_kernel": ["ce.hip", "row_frame.h"],
 }
 
 
