@@ -429,6 +429,43 @@ int s2vt_lstm_step_fwd(int32_t B, int32_t H, const float* gx, const float* bias,
 int s2vt_lstm_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const float* gx, const float* w_hh, const float* h_prev,
                              const float* c_prev, const float* emb, const float* w_e, int64_t ldw_e, const int32_t* tok,
                              const unsigned long long* tok_packed, int32_t tok_const, float* h_out, float* c_out, void* stream);
+
+/* ---- the decode step's kernel forms, TEST SUPPORT (tests/test_gpu_decode_forms.py): the forms of the step and arg-max kernels
+ * that the greedy / sampled decode drivers and the beam plane-path step run, one launch at a time.  No kernel of their own; each
+ * checks its arguments on the host and returns S2VT_ERR_ARG with a message before any launch.  Row strides are the natural widths
+ * (gx, stash: 4H; w_hh, h_prev, c_prev, h_out, c_out: H) unless an ld argument says otherwise.
+ *
+ * s2vt_lstm_step_fwd_table: one word_rnn step in the plane-path form,
+ *   G[b] = gx[gx_idx ? gx_idx[b] : b] (or bias if gx == NULL) + gtab[token(b)] + h_prev[b]·W_hh^T ; cell update.
+ * gx_idx (optional, only with gx): beam slots that share their sample's gate-input row.  gtab [V][ldtab] (optional, ldtab >= 4H):
+ * the per-token gate table Emb·W_e^T; token sources and the out-of-range rule (token 0, S2VT_ERR_INDEX posted) as
+ * s2vt_lstm_step_fwd_token.  h_prev / c_prev NULL = zero state.  stash (optional): the activated gates.  h_planes (optional): h_t
+ * also as three bf16 planes in the blocked image of s2vt_split_planes(3 planes): hp_rows >= B rounded up to 64 rows of ldhp
+ * elements, ldhp >= 3 * (H rounded up to 64), ldhp % 8 == 0, 16-byte aligned; only the elements of (b < B, unit < H) are written.
+ * contract_only = 1: the contraction alone, z_out[b][g*H + u] = sum_k h_prev[b][k] W_hh[g*H + u][k] (rows of ldz >= 4H floats);
+ * h_prev, w_hh and z_out are required, every other pointer is ignored and nothing else is written.  contract_only = 0: z_out
+ * must be NULL. */
+int s2vt_lstm_step_fwd_table(int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias, const float* gtab,
+                             int64_t ldtab, const int32_t* tok, const unsigned long long* tok_packed, int32_t tok_const, const float* w_hh,
+                             const float* h_prev, const float* c_prev, float* h_out, float* c_out, float* stash, uint16_t* h_planes,
+                             int64_t ldhp, int32_t hp_rows, float* z_out, int64_t ldz, int32_t contract_only, void* stream);
+/* The cell update of a step whose contraction ran as its own launch: the step above with z [B][ldz] (ldz >= 4H) in place of
+ * h_prev·W_hh^T - the same additions in the same order, so every output has the fused step's bits. */
+int s2vt_lstm_cell_pointwise(int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias, const float* gtab,
+                             int64_t ldtab, const int32_t* tok, const unsigned long long* tok_packed, int32_t tok_const, const float* z,
+                             int64_t ldz, const float* c_prev, float* h_out, float* c_out, float* stash, uint16_t* h_planes, int64_t ldhp,
+                             int32_t hp_rows, void* stream);
+/* The plane-path arg-max launch (csrc/argmax_x3.hip) on caller-made blocked 3-plane images (s2vt_split_planes) of one padded k = K:
+ * W [w_rows >= V rounded up to 64][ldw], Hp = h_t [hp_rows >= B rounded up to 64][ldh], packed as for s2vt_decode_step_argmax.
+ * M2 > 0: the same launch also writes z[b][m] = h_t[b]·W2[m] for m < M2 (W2 [w2_rows >= M2 rounded up to 64][ldw2], z rows of
+ * ldz >= M2 floats, ldz % 4 == 0, 16-byte aligned): nothing of z past column M2 or row B is written.  with_logits = 0: the z role
+ * alone (M2 > 0; packed is left as it is).  sample != 0 (with the logits only): the draw of s2vt_decode_step_sample_x3 with the
+ * same temperature / seed / step / row0. */
+int s2vt_argmax_x3_planes(int32_t B, int32_t V, int32_t K, const uint16_t* W, int64_t ldw, int32_t w_rows, const uint16_t* Hp, int64_t ldh,
+                          int32_t kpad_h, int32_t hp_rows, const float* bias, unsigned long long* packed, const uint16_t* W2, int64_t ldw2,
+                          int32_t kpad_w2, int32_t w2_rows, int32_t M2, float* z, int64_t ldz, int32_t with_logits, int32_t sample,
+                          float temperature, uint64_t seed, int32_t step, int32_t row0, void* stream);
+
 /* BPTT of one step: dh = dh_out + dg_next·W_hh (w_hh_t = W_hh^T [H,4H]); dc (in/out, [B,H]) carries dL/dc;
  * dg [B,4H] out (may alias stash). dg_next NULL at the last step; dc_is_zero = 1 there. */
 int s2vt_lstm_step_bwd(int32_t B, int32_t H, const float* dg_next, const float* w_hh_t, const float* dh_out,

@@ -127,6 +127,14 @@ SIGNATURES = {
     "s2vt_lstm_step_fwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 9),
     "s2vt_lstm_step_fwd_token": (c_int32, [c_int32, c_int32, c_int32, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
                                                                                             c_int32, c_void_p, c_void_p, c_void_p]),
+    # per-op test support: the decode step's kernel forms (tests/test_gpu_decode_forms.py)
+    "s2vt_lstm_step_fwd_table": (c_int32, [c_int32] * 3 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int32] + [c_void_p] * 7 +
+                                 [c_int64, c_int32, c_void_p, c_int64, c_int32, c_void_p]),
+    "s2vt_lstm_cell_pointwise": (c_int32, [c_int32] * 3 + [c_void_p] * 4 + [c_int64, c_void_p, c_void_p, c_int32, c_void_p, c_int64] +
+                                 [c_void_p] * 5 + [c_int64, c_int32, c_void_p]),
+    "s2vt_argmax_x3_planes": (c_int32, [c_int32] * 3 + [c_void_p, c_int64, c_int32, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p,
+                                                        c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int32,
+                                                        c_float, c_uint64, c_int32, c_int32, c_void_p]),
     "s2vt_lstm_step_bwd": (c_int32, [c_int32, c_int32] + [c_void_p] * 7 + [c_int32, c_void_p, c_void_p]),
     "s2vt_lstm_seq_fwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 6),
     "s2vt_lstm_seq_bwd": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 5),

@@ -534,11 +534,7 @@ int s2vt_decode_encode_cached(const s2vt_dims* d, const s2vt_params* p, const fl
 }
 // ------------------------------------------------------------------ sampled decode (mode='sample')
 // The greedy drivers with the sampling variants of their arg-max launches: same workspace, same weight-image cache.
-// finite and > 0 with a finite reciprocal - what the kernels multiply by: NaN fails the compares, inf gives 0, a subnormal gives inf
-static bool temperature_ok(float t) { const float r = 1.0f / t; return t > 0.f && r > 0.f && r <= 3.4028234e38f; }
-static GumbelArgs gumbel_args(float temperature, uint64_t seed, uint32_t step, uint32_t row0, uint32_t rows) {
-    return GumbelArgs{1.0f / temperature, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), step, row0, rows};
-}
+// (temperature_ok / gumbel_args: api_internal.h)
 static DecodeModes draw_mode_of(float temperature, uint64_t seed, int B, bool on = true) {      // every step of a B-row decode draws
     DecodeModes m{};
     m.smp = Draw{gumbel_args(temperature, seed, 0, 0, (uint32_t)B), on};

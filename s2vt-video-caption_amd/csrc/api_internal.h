@@ -243,6 +243,13 @@ SeqFwdBf16Args persist_fwd_args(int t0, int t1, int B, int H, float* gx_stash, i
 SeqBwdBf16Args seq_bwd_bf16_args(int T, int t0, int t1, int B, int H, const PB& wt, const PB& dgb, const float* dh_out, int dh_first,
                                  const float* c_all, float* stash_dg, float* dc, unsigned int* sync, int* err);
 
+// ------------------------------------------------------------------ sampling arguments (api_decode.hip, api_ops.hip)
+// finite and > 0 with a finite reciprocal - what the kernels multiply by: NaN fails the compares, inf gives 0, a subnormal gives inf
+static inline bool temperature_ok(float t) { const float r = 1.0f / t; return t > 0.f && r > 0.f && r <= 3.4028234e38f; }
+static inline GumbelArgs gumbel_args(float temperature, uint64_t seed, uint32_t step, uint32_t row0, uint32_t rows) {
+    return GumbelArgs{1.0f / temperature, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), step, row0, rows};
+}
+
 // ------------------------------------------------------------------ api_decode.hip (shared with the beam step)
 // What a decode derives from the WEIGHTS alone (plane images of W_f, W_ih1, W_v, W_o and the per-token gate-input table):
 // carved from the tail of the call's workspace, or from a caller-kept cache that outlives the call (s2vt_greedy_decode_cached)

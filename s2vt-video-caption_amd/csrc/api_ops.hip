@@ -279,6 +279,125 @@ int s2vt_lstm_step_fwd_token(int32_t B, int32_t H, int32_t E, int32_t V, const f
     return flags.close(st, 2);
 }
 
+// ------------------------------------------------------------------ the decode step's kernel forms, test support
+// The forms of lstm_step_fwd / lstm_cell_pointwise / logits_argmax_x3 that only the decode drivers and the beam plane path fill in
+// (api_decode.hip: decode_fused, decode_two_chains; api_beam.hip), one launch at a time (tests/test_gpu_decode_forms.py).  No kernel
+// of their own: host checks, one args struct, one existing launch function.
+static bool h_planes_ok(const uint16_t* p, int64_t ldhp, int32_t rows, int B, int H) {
+    return !p || (ldhp >= 3 * (int64_t)pad64(H) && ldhp % 8 == 0 && (reinterpret_cast<uintptr_t>(p) & 15) == 0 &&
+                  rows >= (int64_t)rows64((size_t)B));
+}
+// the arguments the fused table step and the stand-alone cell update share (everything but the recurrent segment and z)
+static StepFwdArgs table_step_args(int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias,
+                                   const float* gtab, int64_t ldtab, const int32_t* tok, const unsigned long long* tok_packed,
+                                   int32_t tok_const, int* tok_err, const float* c_prev, float* h_out, float* c_out, float* stash,
+                                   uint16_t* h_planes, int64_t ldhp) {
+    StepFwdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.H = H;
+    if (gtab) a.tok = TokenSrc{tok, tok_packed, tok_const, V, tok_err, {}};
+    a.gx = gx; a.ldgx = 4 * (int64_t)H; a.gx_idx = gx_idx; a.bias = bias;
+    a.gx_tab = gtab; a.ldtab = ldtab;
+    a.c_prev = c_prev; a.ldc = H;
+    a.h_out = h_out; a.ldho = H; a.c_out = c_out; a.ldco = H;
+    a.stash = stash; a.ldst = 4 * (int64_t)H;
+    a.h_planes = h_planes; a.ldhp = ldhp;
+    return a;
+}
+// ... and the host checks on them (who: the entry's name)
+static int table_step_check(const char* who, int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias,
+                            const float* gtab, int64_t ldtab, const float* h_out, const float* c_out, const uint16_t* h_planes, int64_t ldhp,
+                            int32_t hp_rows) {
+    S2VT_REQUIRE(B > 0 && H > 0 && h_out && c_out && (gx || bias), "%s: null output, neither gx nor bias, or bad size (B=%d H=%d)", who, B, H);
+    S2VT_REQUIRE(!gx_idx || gx, "%s: gx_idx names rows of gx, which is null", who);
+    S2VT_REQUIRE(!gtab || (V > 0 && ldtab >= 4 * (int64_t)H), "%s: a gate table needs V > 0 rows of at least 4H floats (V=%d ldtab=%lld)", who, V,
+                 (long long)ldtab);
+    S2VT_REQUIRE(h_planes_ok(h_planes, ldhp, hp_rows, B, H),
+                 "%s: bad h-plane image (ldhp >= 3 * pad64(H), ldhp %% 8 == 0, 16-byte aligned, whole 64-row blocks for B rows)", who);
+    return 0;
+}
+
+int s2vt_lstm_step_fwd_table(int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias, const float* gtab,
+                             int64_t ldtab, const int32_t* tok, const unsigned long long* tok_packed, int32_t tok_const, const float* w_hh,
+                             const float* h_prev, const float* c_prev, float* h_out, float* c_out, float* stash, uint16_t* h_planes,
+                             int64_t ldhp, int32_t hp_rows, float* z_out, int64_t ldz, int32_t contract_only, void* stream) {
+    if (contract_only) {
+        S2VT_REQUIRE(B > 0 && H > 0 && w_hh && h_prev && z_out && ldz >= 4 * (int64_t)H,
+                     "s2vt_lstm_step_fwd_table: a contraction-only step needs w_hh, h_prev and z_out rows of at least 4H floats (ldz=%lld)",
+                     (long long)ldz);
+        StepFwdArgs a;
+        memset(&a, 0, sizeof(a));
+        a.B = B; a.H = H;
+        a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H;
+        a.z_out = z_out; a.ldz = ldz;
+        ProfScope ps((hipStream_t)stream, K_STEP_FWD, 1);
+        return lstm_step_fwd((hipStream_t)stream, a);
+    }
+    int rc;
+    if ((rc = table_step_check("s2vt_lstm_step_fwd_table", B, H, V, gx, gx_idx, bias, gtab, ldtab, h_out, c_out, h_planes, ldhp, hp_rows))) return rc;
+    S2VT_REQUIRE(!z_out, "s2vt_lstm_step_fwd_table: z_out is the output of contract_only = 1");
+    S2VT_REQUIRE(!h_prev || w_hh, "s2vt_lstm_step_fwd_table: h_prev without w_hh");
+    hipStream_t st = (hipStream_t)stream;
+    PostedFlags flags;
+    if ((rc = flags.open(st))) return rc;
+    StepFwdArgs a = table_step_args(B, H, V, gx, gx_idx, bias, gtab, ldtab, tok, tok_packed, tok_const, flags.p, c_prev, h_out, c_out,
+                                    stash, h_planes, ldhp);
+    a.h_prev = h_prev; a.ldh = H; a.w_hh = w_hh; a.ldw = H;
+    {
+        ProfScope ps(st, K_STEP_FWD, 1);
+        if ((rc = lstm_step_fwd(st, a))) return rc;
+    }
+    return flags.close(st, 2);
+}
+
+int s2vt_lstm_cell_pointwise(int32_t B, int32_t H, int32_t V, const float* gx, const int32_t* gx_idx, const float* bias, const float* gtab,
+                             int64_t ldtab, const int32_t* tok, const unsigned long long* tok_packed, int32_t tok_const, const float* z,
+                             int64_t ldz, const float* c_prev, float* h_out, float* c_out, float* stash, uint16_t* h_planes, int64_t ldhp,
+                             int32_t hp_rows, void* stream) {
+    int rc;
+    if ((rc = table_step_check("s2vt_lstm_cell_pointwise", B, H, V, gx, gx_idx, bias, gtab, ldtab, h_out, c_out, h_planes, ldhp, hp_rows))) return rc;
+    S2VT_REQUIRE(z && ldz >= 4 * (int64_t)H, "s2vt_lstm_cell_pointwise: z is null or its rows are shorter than 4H floats (ldz=%lld)", (long long)ldz);
+    hipStream_t st = (hipStream_t)stream;
+    PostedFlags flags;
+    if ((rc = flags.open(st))) return rc;
+    StepFwdArgs a = table_step_args(B, H, V, gx, gx_idx, bias, gtab, ldtab, tok, tok_packed, tok_const, flags.p, c_prev, h_out, c_out,
+                                    stash, h_planes, ldhp);
+    a.z_out = const_cast<float*>(z); a.ldz = ldz;            // (the cell update reads it)
+    {
+        ProfScope ps(st, K_STEP_FWD, 1);
+        if ((rc = lstm_cell_pointwise(st, a))) return rc;
+    }
+    return flags.close(st, 2);
+}
+
+int s2vt_argmax_x3_planes(int32_t B, int32_t V, int32_t K, const uint16_t* W, int64_t ldw, int32_t w_rows, const uint16_t* Hp, int64_t ldh,
+                          int32_t kpad_h, int32_t hp_rows, const float* bias, unsigned long long* packed, const uint16_t* W2, int64_t ldw2,
+                          int32_t kpad_w2, int32_t w2_rows, int32_t M2, float* z, int64_t ldz, int32_t with_logits, int32_t sample,
+                          float temperature, uint64_t seed, int32_t step, int32_t row0, void* stream) {
+    S2VT_REQUIRE(B > 0 && V > 0 && K > 0 && K % 64 == 0 && W && Hp && packed && M2 >= 0,
+                 "s2vt_argmax_x3_planes: null argument or bad size (B=%d V=%d K=%d M2=%d)", B, V, K, M2);
+    S2VT_REQUIRE(kpad_h == K && (M2 == 0 || kpad_w2 == K), "s2vt_argmax_x3_planes: the images must share one padded k (K=%d, h %d, W2 %d)", K,
+                 kpad_h, kpad_w2);
+    S2VT_REQUIRE(w_rows >= (int64_t)rows64((size_t)V) && hp_rows >= (int64_t)rows64((size_t)B) && (M2 == 0 || w2_rows >= (int64_t)rows64((size_t)M2)),
+                 "s2vt_argmax_x3_planes: an image has fewer rows than the 64-row blocks the launch reads (W %d, h %d, W2 %d)", w_rows, hp_rows,
+                 w2_rows);
+    S2VT_REQUIRE(with_logits || M2 > 0, "s2vt_argmax_x3_planes: with_logits = 0 needs a second image (M2 > 0)");
+    S2VT_REQUIRE(!sample || (with_logits && step >= 0 && row0 >= 0), "s2vt_argmax_x3_planes: a draw needs the logits, step >= 0 and row0 >= 0");
+    S2VT_REQUIRE(!sample || temperature_ok(temperature), "s2vt_argmax_x3_planes: temperature and 1 / temperature must be finite and > 0 (got %g)",
+                 (double)temperature);
+    ArgmaxX3Args ax;
+    memset(&ax, 0, sizeof(ax));
+    ax.B = B; ax.V = V; ax.K = K;
+    ax.W = W; ax.ldw = ldw; ax.Hp = Hp; ax.ldh = ldh;
+    ax.bias = bias; ax.packed = packed;
+    if (M2 > 0) { ax.W2 = W2; ax.ldw2 = ldw2; ax.M2 = M2; ax.z = z; ax.ldz = ldz; }
+    ax.v_off = with_logits ? 0 : cdiv(V, 64);
+    GumbelArgs g{};
+    if (sample) g = gumbel_args(temperature, seed, (uint32_t)step, (uint32_t)row0, (uint32_t)row0 + (uint32_t)B);
+    ProfScope ps((hipStream_t)stream, K_ARGMAX, 1);
+    return logits_argmax_x3((hipStream_t)stream, ax, sample ? &g : nullptr);       // (geometry of ld / alignment / ldz: the launcher's own checks)
+}
+
 int s2vt_lstm_step_bwd(int32_t B, int32_t H, const float* dg_next, const float* w_hh_t, const float* dh_out,
                        const float* stash, const float* c, const float* c_prev, float* dc, int32_t dc_is_zero,
                        float* dg, void* stream) {

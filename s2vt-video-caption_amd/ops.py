@@ -815,3 +815,131 @@ def split_planes_dual(x, nplanes=3, rowmap=None, want_r=True, want_t=False, want
                                               _ptr(lse), _ptr(target), ldt, Lm1, _ptr(gout), _ptr(res.get("alpha")), _stream(dev)),
                    "s2vt_split_planes_dual")
     return res
+
+
+# ---------------------------------------------------------------- per-op test support (include/s2vt_hip.h: the decode step's
+# kernel forms).  Outputs may be handed in (pre-filled: the tests look at what a launch leaves alone); every tensor is passed as
+# the view it is - c_prev may start anywhere in its storage.
+def _i32vec(t, n, name):
+    if t is None:
+        return None
+    require_hip(t, name)
+    if t.dtype != torch.int32 or tuple(t.shape) != (n,) or not t.is_contiguous():
+        raise capi.S2VTHipError("%s must be a contiguous int32 [%d]" % (name, n))
+    return t
+
+
+def _rows_of(t, cols, name):
+    """float32 [rows, >= cols] with unit column stride and contiguous rows (row stride = cols): the natural width"""
+    if t is None:
+        return None
+    require_hip(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != cols or t.stride(1) != 1 or t.stride(0) != cols:
+        raise capi.S2VTHipError("%s must be float32 [rows, %d] with row stride %d, got %s %s" % (name, cols, cols, tuple(t.shape),
+                                                                                                  tuple(t.stride())))
+    return t
+
+
+def h_plane_image(B, H, dev, fill=0, extra_ld=0):
+    """(image, ld, kpad): an int16 blocked 3-plane image for B rows of H units as split_planes lays it out, every element = fill"""
+    kpad = (H + 63) // 64 * 64
+    ld = 3 * kpad + extra_ld
+    return torch.full(((B + 63) // 64 * 64, ld), fill, dtype=torch.int16, device=dev), ld, kpad
+
+
+def _table_step_common(B, H, gx, gx_idx, gtab, tok, c_prev, h_out, c_out, stash, want_stash, h_planes, dev):
+    gx, c_prev = _rows_of(gx, 4 * H, "gx"), _rows_of(c_prev, H, "c_prev")
+    gx_idx, tok = _i32vec(gx_idx, B, "gx_idx"), _i32vec(tok, B, "tok")
+    V, ldtab = 0, 0
+    if gtab is not None:
+        require_hip(gtab, "gtab")
+        if gtab.dtype != torch.float32 or gtab.dim() != 2 or gtab.stride(1) != 1:
+            raise capi.S2VTHipError("gtab must be float32 rows with unit column stride")
+        V, ldtab = gtab.shape[0], gtab.stride(0)
+    h_out = h_out if h_out is not None else torch.empty(B, H, dtype=torch.float32, device=dev)
+    c_out = c_out if c_out is not None else torch.empty(B, H, dtype=torch.float32, device=dev)
+    if stash is None and want_stash:
+        stash = torch.empty(B, 4 * H, dtype=torch.float32, device=dev)
+    img, ldhp, hp_rows = (h_planes[0], h_planes[1], h_planes[0].shape[0]) if h_planes is not None else (None, 0, 0)
+    return gx, gx_idx, gtab, V, ldtab, tok, c_prev, _rows_of(h_out, H, "h_out"), _rows_of(c_out, H, "c_out"), \
+        _rows_of(stash, 4 * H, "stash"), img, ldhp, hp_rows
+
+
+def lstm_step_fwd_table(w_hh, h_prev, c_prev, gx=None, gx_idx=None, bias=None, gtab=None, tok=None, tok_packed=None, tok_const=0,
+                        h_out=None, c_out=None, stash=None, want_stash=False, h_planes=None):
+    """One word_rnn step in the plane-path form (s2vt_lstm_step_fwd_table): gates = gx[gx_idx] (or bias) + gtab[token] +
+    h_prev·w_hh^T.  h_planes = (image, ld, kpad) as split_planes / h_plane_image return it: h_t is also written there as three
+    bf16 planes.  Returns (h, c, stash or None)."""
+    lib = capi.load()
+    w_hh = _f32c(w_hh, "w_hh")
+    H = w_hh.shape[1]
+    B = gx_idx.numel() if gx_idx is not None else (gx.shape[0] if gx is not None else h_prev.shape[0])
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        gx, gx_idx, gtab, V, ldtab, tok, c_prev, h_out, c_out, stash, img, ldhp, hp_rows = _table_step_common(
+            B, H, gx, gx_idx, gtab, tok, c_prev, h_out, c_out, stash, want_stash, h_planes, dev)
+        capi.check(lib.s2vt_lstm_step_fwd_table(B, H, V, _ptr(gx), _ptr(gx_idx), _ptr(bias), _ptr(gtab), ldtab, _ptr(tok), _ptr(tok_packed),
+                                                int(tok_const), _ptr(w_hh), _ptr(_rows_of(h_prev, H, "h_prev")), _ptr(c_prev), _ptr(h_out),
+                                                _ptr(c_out), _ptr(stash), _ptr(img), ldhp, hp_rows, None, 0, 0, _stream(dev)),
+                   "s2vt_lstm_step_fwd_table")
+    return h_out, c_out, stash
+
+
+def lstm_step_contract(w_hh, h_prev, z=None):
+    """z [B, >= 4H] = h_prev·w_hh^T, the contraction-only form of the step kernel (s2vt_lstm_step_fwd_table, contract_only = 1);
+    `z` may be handed in (any row stride >= 4H): only its first 4H columns of the B rows are written."""
+    lib = capi.load()
+    w_hh = _f32c(w_hh, "w_hh")
+    H = w_hh.shape[1]
+    h_prev = _rows_of(h_prev, H, "h_prev")
+    B = h_prev.shape[0]
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        if z is None:
+            z = torch.empty(B, 4 * H, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_lstm_step_fwd_table(B, H, 0, None, None, None, None, 0, None, None, 0, _ptr(w_hh), _ptr(h_prev), None, None,
+                                                None, None, None, 0, 0, _ptr(z), z.stride(0), 1, _stream(dev)),
+                   "s2vt_lstm_step_fwd_table")
+    return z
+
+
+def lstm_cell_pointwise(z, H, c_prev, gx=None, gx_idx=None, bias=None, gtab=None, tok=None, tok_packed=None, tok_const=0, h_out=None,
+                        c_out=None, stash=None, want_stash=False, h_planes=None, B=None):
+    """The cell update of a step whose contraction z [>= B, >= 4H] ran as its own launch (s2vt_lstm_cell_pointwise); the other
+    arguments as lstm_step_fwd_table.  Returns (h, c, stash or None)."""
+    lib = capi.load()
+    require_hip(z, "z")
+    if z.dtype != torch.float32 or z.dim() != 2 or z.stride(1) != 1:
+        raise capi.S2VTHipError("z must be float32 rows with unit column stride")
+    if B is None:
+        B = gx_idx.numel() if gx_idx is not None else (gx.shape[0] if gx is not None else z.shape[0])
+    dev = z.device
+    with torch.cuda.device(dev):
+        gx, gx_idx, gtab, V, ldtab, tok, c_prev, h_out, c_out, stash, img, ldhp, hp_rows = _table_step_common(
+            B, H, gx, gx_idx, gtab, tok, c_prev, h_out, c_out, stash, want_stash, h_planes, dev)
+        capi.check(lib.s2vt_lstm_cell_pointwise(B, H, V, _ptr(gx), _ptr(gx_idx), _ptr(bias), _ptr(gtab), ldtab, _ptr(tok), _ptr(tok_packed),
+                                                int(tok_const), _ptr(z), z.stride(0), _ptr(c_prev), _ptr(h_out), _ptr(c_out), _ptr(stash),
+                                                _ptr(img), ldhp, hp_rows, _stream(dev)), "s2vt_lstm_cell_pointwise")
+    return h_out, c_out, stash
+
+
+def argmax_x3_planes(pw, ph, B, V, bias=None, packed=None, pw2=None, M2=0, z=None, with_logits=True, sample=None):
+    """The plane-path arg-max launch on caller-made images (s2vt_argmax_x3_planes).  pw / ph / pw2 = (image, ld, kpad) of
+    out_linear.weight [V, H], h_t [B, H] and the second weight [M2, H] as split_planes returns them.  packed: int64 [B] (zeroed
+    if not given).  z: float32 [rows, ldz] to receive h_t·W2^T in its first M2 columns of the first B rows.  with_logits = False:
+    the z role alone.  sample = (temperature, seed, step, row0): a draw instead of the arg-max.  Returns (packed, z)."""
+    lib = capi.load()
+    (w, ldw, kw), (hp, ldh, kh) = pw, ph
+    w2, ldw2, kw2 = pw2 if pw2 is not None else (None, 0, 0)
+    dev = w.device
+    temperature, seed, step, row0 = sample if sample is not None else (1.0, 0, 0, 0)
+    with torch.cuda.device(dev):
+        if packed is None:
+            packed = torch.zeros(B, dtype=torch.int64, device=dev)
+        if z is None and M2 > 0:
+            z = torch.empty(B, (M2 + 3) // 4 * 4, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_argmax_x3_planes(B, V, kw, _ptr(w), ldw, w.shape[0], _ptr(hp), ldh, kh, hp.shape[0], _ptr(bias), _ptr(packed),
+                                             _ptr(w2), ldw2, kw2, w2.shape[0] if w2 is not None else 0, int(M2), _ptr(z),
+                                             z.stride(0) if z is not None else 0, int(bool(with_logits)), int(sample is not None),
+                                             float(temperature), int(seed), int(step), int(row0), _stream(dev)), "s2vt_argmax_x3_planes")
+    return packed, z
