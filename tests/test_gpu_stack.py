@@ -199,14 +199,21 @@ def _check_train(m, feats, caps, rnn_masks=None, out_mask=None, logits=None):
         _close(p.grad, P[name].grad, name, rel=1e-4)
 
 
-@pytest.mark.parametrize("N", [2, 3])
+# (the mode-3 cases keep the ids they had before the GEMM mode became a parameter)
+@pytest.mark.parametrize("N,gemm_mode", [pytest.param(2, 3, id="2"), pytest.param(3, 3, id="3"),
+                                         pytest.param(2, 0, id="2-gemm0"), pytest.param(3, 0, id="3-gemm0")])
 @pytest.mark.parametrize("B,H", [(5, 30), (16, 64), (64, 128)])
-def test_stacked_train_against_fp64_composite(lib, N, B, H):
+def test_stacked_train_against_fp64_composite(lib, N, B, H, gemm_mode):
     """S2VT.forward(mode='train') of a stacked model: logits and every parameter gradient (all _l1 / _l2 tensors included)
-    against an fp64 composite of single-layer nn.LSTMs."""
+    against an fp64 composite of single-layer nn.LSTMs, with the projections on the plane GEMMs (mode 3) and on s2vt_gemm_f32
+    (mode 0)."""
     m, feats, caps = _model(N, B, 6, 48, H, H - 8, 37)
-    logits = m(feats, targets=caps[:, :-1], mode="train")
-    _check_train(m, feats, caps, logits=logits)
+    prev = lib.s2vt_set_gemm_mode(gemm_mode)
+    try:
+        logits = m(feats, targets=caps[:, :-1], mode="train")
+        _check_train(m, feats, caps, logits=logits)
+    finally:
+        lib.s2vt_set_gemm_mode(prev)
 
 
 def test_stacked_train_with_injected_masks(lib):
