@@ -17,6 +17,7 @@ from s2vt_video_caption_amd import beam as _beam
 from s2vt_video_caption_amd import gru_functional as _G
 from s2vt_video_caption_amd import stack_functional as _S
 from s2vt_video_caption_amd import sampling as _sampling
+from s2vt_video_caption_amd import score as _score
 
 
 class S2VT(nn.Module):
@@ -74,9 +75,17 @@ class S2VT(nn.Module):
                      length**length_alpha when they end (<eos>, or max_beam_depth words); ids are the words after <sos>, padded
                      with eos_ix; lengths count the <eos> where there is one (not in the reference; beam.beam_cumulative);
                      'sample' -> ids [B, L-1] (int64) drawn step by step from softmax(logit / temperature), never stopping at
-                     <eos> (not in the reference; for sequence-level training, utils.RewardCriterion)
+                     <eos> (not in the reference; for sequence-level training, utils.RewardCriterion);
+                     'score' -> (scores fp32 [B(, K)], lengths int64 [B(, K)], token_logprobs fp32 [B(, K), T-1]) on the device:
+                     the log-likelihood of the GIVEN captions `targets`, int64 [B, T] or [B, K, T] (K candidates per clip, which
+                     share one encode; an expanded view is fine), each <sos>, words, <eos>, padding with 2 <= T <= length.
+                     token_logprobs[j] = log_softmax(logits of mode='train' without dropout)[targets[j + 1]] up to and including
+                     the first <eos> (0 behind), lengths counts those tokens, scores = their sum / length**length_alpha - the
+                     rule of mode='beam', whose scores are directly comparable at the same length_alpha (the signature's default
+                     is 0.7; pass length_alpha=0.0 for the plain log-likelihood).  No gradient (not in the reference;
+                     score.score_captions)
         :param beam_width: 'beam_search': any; 'beam': 1..8
-        :param length_alpha: mode='beam' only: finite and >= 0 (0: the plain sum)
+        :param length_alpha: mode='beam' and mode='score' only: finite and >= 0 (0: the plain sum)
         :param n_best: mode='beam' only: hypotheses returned per clip, 1..beam_width
         :param temperature: mode='sample' only: finite and > 0
         :param seed: mode='sample' and scheduled sampling: None draws a 63-bit seed from torch's default generator
@@ -93,6 +102,9 @@ class S2VT(nn.Module):
         ss_prob = _F.check_ss_prob(ss_prob) if mode == 'train' else 0.0      # (ignored elsewhere, as temperature is outside 'sample')
         if mode == 'beam':
             _beam.check_beam_args(beam_width, max_beam_depth, length_alpha, n_best, self.vocab_size)
+        if mode == 'score':                                # (shape checks again, with the dims, in score.score_captions)
+            _score.check_score_args(targets, feats.shape[0] if isinstance(feats, torch.Tensor) and feats.dim() else -1, self.length,
+                                    None, length_alpha)
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
@@ -102,6 +114,8 @@ class S2VT(nn.Module):
         if _S.is_stacked_lstm_model(self):
             return self._forward_stacked(feats, targets, mode, sample, (ss_prob, ss_temperature, seed))
         params = self._hip_params()
+        if mode == 'score':                                # (inference arithmetic whatever self.training says: no feat_drop draw)
+            return _score.score_captions(self, feats, targets, params, length_alpha=length_alpha)
         clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # identity at the reference's p=0 (S2VTModel.py:52)
         if mode == 'beam_search':
@@ -135,6 +149,9 @@ class S2VT(nn.Module):
                                       "(S2VTModel.py:153, 'DO NOT SUPPORT GRU'); use mode='test'")
         if mode == 'beam':
             raise NotImplementedError("mode='beam' of a GRU model: the batched depth step is the LSTM's; use mode='test'")
+        if mode == 'score':
+            raise NotImplementedError("mode='score' of a GRU model: the scoring driver's word step is the LSTM's; take the logits "
+                                      "of mode='train' and log_softmax(...).gather(...) them")
         clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':
@@ -164,6 +181,9 @@ class S2VT(nn.Module):
         if mode == 'beam':
             raise NotImplementedError("mode='beam' of a stacked model (num_layers > 1): the batched depth step is the one-layer "
                                       "LSTM's; use mode='test'")
+        if mode == 'score':
+            raise NotImplementedError("mode='score' of a stacked model (num_layers > 1): the scoring driver's word step is the "
+                                      "one-layer LSTM's; take the logits of mode='train' and log_softmax(...).gather(...) them")
         clean = feats                                      # (the scheduled pass runs without dropout)
         feats = self.feat_drop(feats)                      # S2VTModel.py:52
         if mode == 'train':

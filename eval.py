@@ -6,7 +6,8 @@ decodes with the cumulative-score beam search instead (mode='beam', not in the r
 `main()` writes the predictions as JSON ({video_id: caption}) and, with --gts, scores them as the reference's
 `__main__` does (eval.py:222-236: gts.json -> pred_to_coco_samples_IDs -> COCOScorer.score) with caption_metrics.py:
 BLEU-1..4, ROUGE-L, CIDEr.  METEOR and the Stanford tokenizer are Java jars the reference does not ship
-(`.MISSING_LARGE_BLOBS`); see caption_metrics.py for what stands in for them.
+(`.MISSING_LARGE_BLOBS`); see caption_metrics.py for what stands in for them.  --perplexity scores the split's reference captions
+under the model instead (mode='score', not in the reference): per-word perplexity and per-reference log-likelihoods.
 """
 import argparse
 import json
@@ -59,6 +60,58 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
     return preds
 
 
+def pack_references(ref_lists, eos_ix, max_len):
+    """The reference captions of a batch of clips as ONE mode='score' input: ref_lists = per clip its token lists (<sos>, words,
+    <eos>, as dataloader.VideoDataset.captions holds them), cut at max_len.  -> (int64 [B, K, T], counts): K = the most references
+    any clip has (a clip with fewer repeats its first one; counts[b] says how many rows are real), T = the batch's longest caption
+    (at least 2), shorter ones right-padded with <eos>."""
+    refs = [[list(r)[:max_len] for r in rs] for rs in ref_lists]
+    if not refs or any(not rs or any(len(r) < 2 for r in rs) for rs in refs):
+        raise ValueError("every clip needs at least one reference caption of at least two tokens")
+    K = max(len(rs) for rs in refs)
+    T = max(len(r) for rs in refs for r in rs)
+    caps = torch.full((len(refs), K, T), int(eos_ix), dtype=torch.long)
+    for b, rs in enumerate(refs):
+        for k in range(K):
+            r = rs[k] if k < len(rs) else rs[0]
+            caps[b, k, :len(r)] = torch.tensor(r, dtype=torch.long)
+    return caps, [len(rs) for rs in refs]
+
+
+def perplexity_summary(logliks, lengths):
+    """{total_loglik, tokens, perplexity, mean_caption_loglik} of per-caption log-likelihoods and scored-token counts (the <eos>
+    counts): per-word perplexity = exp(-sum of log-likelihoods / sum of tokens)."""
+    import math
+    total, tokens = float(sum(logliks)), int(sum(lengths))
+    if not logliks or tokens <= 0:
+        raise ValueError("no caption was scored")
+    return {"total_loglik": total, "tokens": tokens, "perplexity": math.exp(-total / tokens),
+            "mean_caption_loglik": total / len(logliks)}
+
+
+def reference_logliks(model_path, caption_file, feats_path, batch_size=10, split='test', device=None):
+    """({video_id: [log-likelihood of each reference caption]}, summary) of a split under the model: every reference of every clip
+    scored by mode='score' (length_alpha = 0: plain sums), the references of a clip in one call."""
+    import dataloader
+    dev = device or torch.device('cuda', 0)
+    dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
+    model = torch.load(model_path, weights_only=False).to(dev)
+    model.eval()
+    model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
+    out, lls, ns = {}, [], []
+    with torch.no_grad():
+        for feats, targets, ids, masks in dataloader.feed_batches(loader, dev):
+            caps, counts = pack_references([dataset.captions[v] for v in ids], model.eos_ix, model.length)
+            scores, lengths, _ = model(feats, targets=caps.to(dev), mode='score', length_alpha=0.0)
+            scores, lengths = scores.cpu().tolist(), lengths.cpu().tolist()
+            for vid, sc, ln, c in zip(ids, scores, lengths, counts):
+                out[vid] = sc[:c]
+                lls.extend(sc[:c])
+                ns.extend(ln[:c])
+    return out, perplexity_summary(lls, ns)
+
+
 def to_samples(prediction_dict, gts):
     """{video_id: caption} -> ({video_id: [{'image_id', 'caption'}]}, ids) for the ids that have ground truth
     (pred_to_coco_samples_IDs, eval.py:138-151)."""
@@ -77,7 +130,7 @@ def score(prediction_dict, gts_file):
     return scorer
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model-path", required=True)
     ap.add_argument("--caption-file", default="./data/captions_server.json")
@@ -89,9 +142,24 @@ def main(argv=None):
     ap.add_argument("--length-alpha", type=float, default=0.7, help="cumulative: a finished caption scores sum / length**alpha")
     ap.add_argument("--n-best", type=int, default=1,
                     help="cumulative: captions kept per clip; more than one also writes {video_id: [captions]} to <out>.nbest.json")
+    ap.add_argument("--perplexity", action="store_true",
+                    help="instead of decoding: score every reference caption of the split (mode='score'), print total "
+                         "log-likelihood, tokens, per-word perplexity and mean per-caption log-likelihood, write "
+                         "{video_id: [per-reference log-likelihoods]} to <out>.ll.json")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
+    if a.perplexity:
+        per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
+        print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "
+              "mean per-caption log-likelihood {mean_caption_loglik:.4f}".format(**summary))
+        with open(a.out + ".ll.json", 'w', encoding='utf-8') as f:
+            json.dump(per_clip, f, ensure_ascii=False, indent=1)
+        return summary
     cumulative = bool(a.beam) and a.beam_mode == "cumulative"
     nbest = {} if cumulative and a.n_best > 1 else None
     preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,

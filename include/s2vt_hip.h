@@ -168,6 +168,41 @@ int s2vt_beam_cum_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t
 int s2vt_beam_cum_result(int32_t B, int32_t beam_width, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state, size_t state_bytes,
                          int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream);
 
+/* Caption scoring (S2VT.forward(mode='score'); not in the reference): the log-likelihood of GIVEN captions, K candidates per clip, in
+ * the arithmetic of mode='train' without dropout.  A caption c[0..T-1] (2 <= T <= L) is <sos>, words, <eos>, padding, as the data
+ * loader lays it out (dataloader.py); candidate k of clip b starts at captions + b * stride_b + k * stride_k (unit token stride;
+ * either stride may be 0 - a broadcast view - nothing is copied).  Row r = b * K + k:
+ *   n        = 1 + the position of the first eos_ix in c[1:], T-1 where there is none (the <eos> counts, as in s2vt_beam_cum_result)
+ *   lp[j]    = min(log_softmax(z_j)[c[j+1]], 0) for j < n, 0 behind; z_j = row j of the logits s2vt_train_forward gives for c[:-1]
+ *              (S2VTModel.py:63-81; the log_softmax of :214, clamped as s2vt_beam_cum_step clamps it)     -> token_lp [B*K][T-1]
+ *   score    = (fp32 sum of lp[0..n-1], j ascending) / fp32(pow((double)n, length_alpha)), s2vt_beam_cum_step's power rule
+ *   length   = n (int64)
+ * The K candidates of a clip share ONE encode of it (feature projection, both layers over the L frames, vid_rnn's input-free decode
+ * steps: S2VTModel.py:54, 64-67); then T-1 word steps over the B*K rows (the step of s2vt_beam_step), out_linear (:80) over all
+ * steps' hidden states in chunks of S2VT_SCORE_HEAD_ROWS rows - the workspace never holds more logits than that - and one finisher
+ * launch.  Every id of `captions`, also behind the first <eos>, must lie in [0, V): another one is reported as S2VT_ERR_INDEX through
+ * s2vt_check_async_error, as nn.Embedding's IndexError (:71), and is clamped before it indexes anything.
+ * cache == NULL: the fp32-input MFMA path, launches per timestep.  Otherwise the plane path on the weight images of
+ * s2vt_greedy_decode_cached (same cache, same cache_valid protocol: 0 = the images are built by this call) with the encode phase of
+ * s2vt_decode_encode_cached, which refuses (S2VT_ERR_ARG, nothing enqueued) shapes and modes without the persistent recurrence -
+ * s2vt_decode_plan(d, 1, ...) tells.  Stream-ordered on `stream`, no host round trip.
+ * The workspace holds what the word steps, the head and the finisher work on.  The encode phase's own scratch (a decode workspace,
+ * s2vt_decode_workspace_bytes, dead once the states are handed out and several times larger than all the rest) is not in it: the
+ * library keeps one such buffer per (device, stream) and grows it on demand - the only calls that allocate, and that wait for the
+ * device, are the ones that grow it.
+ * s2vt_score_workspace_bytes: 0 where the shape cannot be served (K < 1, T outside [2, L], 2^31 or more token rows). */
+#define S2VT_SCORE_HEAD_ROWS 1024
+size_t s2vt_score_workspace_bytes(const s2vt_dims* d, int32_t K, int32_t T);
+int s2vt_score_captions(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* captions, int64_t stride_b,
+                        int64_t stride_k, int32_t K, int32_t T, int32_t eos_ix, double length_alpha, float* token_lp, float* score,
+                        int64_t* length, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
+                        void* stream);
+/* The head kernel of the above alone: lp_out[r] = min(x[target[r]] - max(x) - logf(sum_i expf(x[i] - max(x))), 0) for the rows
+ * x = logits + r * ld (ld >= V), i.e. log_softmax (S2VTModel.py:214) read at one token.  One workgroup per row, any V.  A target
+ * outside [0, V) sets *err_flag (device int32, may be NULL) to non-zero and reads the nearest valid column. */
+int s2vt_pick_logprob(const float* logits, int64_t ld, int64_t rows, int32_t V, const int32_t* target, float* lp_out, int32_t* err_flag,
+                      void* stream);
+
 /* Data-parallel overlap (no reference counterpart: the reference is single-device).  After s2vt_train_backward has
  * RETURNED (all of its work is enqueued), make `stream` wait until a group of that call's parameter gradients is
  * final, so that their all-reduce can run under the rest of the backward:

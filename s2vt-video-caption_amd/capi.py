@@ -108,6 +108,11 @@ SIGNATURES = {
     "s2vt_beam_cum_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_beam_cum_step": (c_int32, [c_int32] * 5 + [c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 6),
     "s2vt_beam_cum_result": (c_int32, [c_int32] * 5 + [c_void_p, c_size_t] + [c_void_p] * 4),
+    "s2vt_score_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
+    "s2vt_score_captions": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
+                                      c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32,
+                                      c_void_p]),
+    "s2vt_pick_logprob": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "s2vt_feat_proj_fwd": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "s2vt_feat_proj_bwd": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p]),

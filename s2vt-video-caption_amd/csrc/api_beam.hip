@@ -3,6 +3,26 @@
 
 using namespace s2vt;
 
+namespace s2vt {
+// One word_rnn step over R fixed rows whose tokens are known (S2VTModel.py:211-212; the beam searches' depth step and the scoring
+// driver's word steps, api_score.hip): h_prev · W_hh^T + the rows' gate input + the embedded token's segment - the per-token gate
+// table of the decode cache (kc) on the plane path, the embedding rows against W_e inside the kernel's second K segment otherwise.
+int rows_word_step(hipStream_t st, const s2vt_dims& d, const s2vt_params* p, const DecodeConst* kc, const RowsStep& r) {
+    const int H = d.H, E = d.E;
+    StepFwdArgs a = {};
+    a.B = r.R; a.H = H;
+    a.h_prev = r.h_prev; a.ldh = H; a.w_hh = p->word_w_hh; a.ldw = H;
+    a.tok.tok_idx = r.tok; a.tok.tok_limit = d.V; a.tok.tok_err = r.err;
+    a.gx = r.gx; a.ldgx = 4 * (int64_t)H; a.gx_idx = r.gx_idx;
+    a.c_prev = r.c_prev; a.ldc = H;
+    a.h_out = r.h_out; a.ldho = H; a.c_out = r.c_out; a.ldco = H;
+    a.h_planes = r.h_planes; a.ldhp = r.ldhp;
+    if (kc) { a.gx_tab = kc->gtab; a.ldtab = 4 * (int64_t)H; }
+    else { a.x2 = p->emb_w; a.ldx2 = E; a.K2 = E; a.w2 = p->word_w_ih; a.ldw2 = E + H; }
+    return lstm_step_fwd(st, a);
+}
+}  // namespace s2vt
+
 extern "C" {
 
 // ---------------------------------------------------------------------------------- batched beam-search depth
@@ -66,15 +86,12 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     // with the embedding rows gathered inside the kernel's second K segment (:211-212)
     if ((rc = gather_rows_f32(st, word_h_in, H, row_state, R, H, w.ph))) return rc;
     if ((rc = gather_rows_f32(st, word_c_in, H, row_state, R, H, w.pc))) return rc;
-    // the word step of the R rows: parents' states, the token checked against V (nn.Embedding raises IndexError for such an id,
-    // S2VTModel.py:211); each path below adds the embedded word's segment (gate table, or embedding + W_ih) and the gate input
-    StepFwdArgs a = {};
-    a.B = R; a.H = H;
-    a.h_prev = w.ph; a.ldh = H; a.w_hh = p->word_w_hh; a.ldw = H;
-    a.tok.tok_idx = tok; a.tok.tok_limit = V; a.tok.tok_err = w.err;
-    a.gx = w.gx; a.ldgx = 4 * H;
-    a.c_prev = w.pc; a.ldc = H;
-    a.h_out = word_h_out; a.ldho = H; a.c_out = word_c_out; a.ldco = H;
+    // the word step of the R rows (rows_word_step above): parents' states, the token checked against V; each path below names its
+    // gate input - per sample + the gate table on the plane path, per row + the embedding K segment otherwise
+    RowsStep a = {};
+    a.R = R; a.tok = tok; a.err = w.err;
+    a.gx = w.gx;
+    a.h_prev = w.ph; a.c_prev = w.pc; a.h_out = word_h_out; a.c_out = word_c_out;
     if (cache && decode_plan(*d, true, false).planes && H <= 1024) {     // (any batch: the row counts of its GEMMs are free, the images are the cache's)
         // PLANE PATH (the weight-derived images of a greedy decode of the same weights, s2vt_greedy_decode_cached: W_v and W_o
         // as blocked 3-plane operands, the per-token gate table): the vid_out half of the gate input once per SAMPLE (every beam
@@ -88,12 +105,11 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
             if ((rc = pgemm(ln, B, 4 * H, H, w.pvid, 0, 0, kc.wv, 0, 0, w.gx, 4 * H, ID, w.bsum2, false))) return rc;
         }
         if ((rc = fill_zero(st, w.pword.p, rows64((size_t)R) * (size_t)w.pword.ld * sizeof(unsigned short)))) return rc;
-        a.gx_tab = kc.gtab; a.ldtab = 4 * (int64_t)H;
         if (gx_vid) a.gx = gx_vid;
         a.gx_idx = row_b;
         a.h_planes = w.pword.p; a.ldhp = w.pword.ld;
         if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
-        if ((rc = lstm_step_fwd(st, a))) return rc;
+        if ((rc = rows_word_step(st, *d, p, &kc, a))) return rc;
         if ((rc = pgemm(ln, R, V, H, w.pword, 0, 0, kc.wo, 0, 0, w.logits, V, ID, p->out_b, false))) return rc;
         if ((rc = top20_logprob(st, w.logits, V, R, V, top_ix, top_lp))) return rc;
         return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
@@ -102,9 +118,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     if ((rc = lgemm(ln, true, true, R, 4 * H, H, vid_h_out, H, gather(row_b), p->word_w_ih + E, E + H, ID, w.gx, 4 * H, ID,
                     w.bsum2, false)))
         return rc;
-    a.x2 = p->emb_w; a.ldx2 = E; a.K2 = E; a.w2 = p->word_w_ih; a.ldw2 = E + H;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
-    if ((rc = lstm_step_fwd(st, a))) return rc;
+    if ((rc = rows_word_step(st, *d, p, nullptr, a))) return rc;
     if ((rc = lgemm(ln, true, true, R, V, H, word_h_out, H, ID, p->out_w, H, ID, w.logits, V, ID, p->out_b, false))) return rc;   // (:213)
     if ((rc = top20_logprob(st, w.logits, V, R, V, top_ix, top_lp))) return rc;                                                    // (:214-219)
     return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)

@@ -5,6 +5,7 @@
 //   api_decode.hip   greedy / sampled / scheduled decode and the encode phase for the beam search (DecodeDriver: one function per
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
+//   api_score.hip    teacher-forced caption scoring (S2VT.forward(mode='score'))
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
 // Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue / beam_cum.hip.
 #pragma once
@@ -255,5 +256,18 @@ static inline GumbelArgs gumbel_args(float temperature, uint64_t seed, uint32_t 
 // carved from the tail of the call's workspace, or from a caller-kept cache that outlives the call (s2vt_greedy_decode_cached)
 struct DecodeConst { PB wf, wih1, wv, wo; float* gtab; unsigned short *xw1, *xw2; PB whh; size_t bytes; };   // xw: W_hh planes [3][4H][Kp]; whh: word_rnn's W_hh, blocked
 DecodeConst carve_decode_const(const s2vt_dims& d, void* base);
+
+// ------------------------------------------------------------------ api_beam.hip (shared with the scoring driver, api_score.hip)
+// One word_rnn step over R fixed rows with known tokens: row r reads gate-input row gx_idx[r] of gx (null: row r), its own h_prev /
+// c_prev row, token tok[r] (outside [0, V): token 0, *err raised).  kc != null: plane path - the gate table of the decode cache
+// stands for the embedded word and h_t also leaves as blocked planes (h_planes, k padding zeroed by the caller); kc == null: the
+// embedding rows against W_e in the kernel's second K segment.
+struct RowsStep {
+    int R; const int32_t* tok; int* err;
+    const float* gx; const int32_t* gx_idx;
+    const float *h_prev, *c_prev; float *h_out, *c_out;
+    unsigned short* h_planes; int64_t ldhp;
+};
+int rows_word_step(hipStream_t st, const s2vt_dims& d, const s2vt_params* p, const DecodeConst* kc, const RowsStep& r);
 
 }  // namespace s2vt

@@ -225,7 +225,7 @@ static bool beamc_dims_ok(int B, int bw, int D) {
 // fp32(len ** alpha) for len = 0..D, evaluated as beam_queue.hip evaluates len ** 0.7 (libm double pow, then fp32), in pinned host
 // memory that lives for the life of the process: the copy to the device is asynchronous (no host synchronisation at the start of a
 // search), so a table is never freed or rewritten - one per distinct alpha, regrown (the shorter one stays) for a larger D.
-static const float* beamc_pow_table(double alpha, int D) {
+const float* length_pow_table(double alpha, int D) {       // (kernels.h: the scoring finisher divides by the same table)
     static std::mutex mu;
     static std::map<double, std::pair<float*, int>> tabs;
     std::lock_guard<std::mutex> lock(mu);
@@ -268,7 +268,7 @@ int s2vt_beam_cum_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t
     q.row_b = row_b; q.row_state = row_state; q.row_tok = row_tok;
     hipStream_t st = (hipStream_t)stream;
     if (depth == 1) {
-        const float* tab = beamc_pow_table(length_alpha, max_depth);
+        const float* tab = length_pow_table(length_alpha, max_depth);
         S2VT_REQUIRE(tab, "s2vt_beam_cum_step: no pinned memory for the length table");
         S2VT_HIP(hipMemcpyAsync(q.powa, tab, (size_t)(max_depth + 1) * sizeof(float), hipMemcpyHostToDevice, st));
         S2VT_HIP(hipMemsetAsync(q.done_count, 0, sizeof(int), st));

@@ -362,4 +362,103 @@ int top20_logprob(hipStream_t s, const float* logits, int64_t ld, int64_t rows, 
     return 0;
 }
 
+// ---------------------------------------------------------------------------------- caption scoring (S2VT.forward(mode='score'))
+// Per logits row: the log-probability of ONE given token, lp = min(x[t] - max - logf(sum_i expf(x[i] - max)), 0) - log_softmax
+// (S2VTModel.py:214) read at the target instead of fanned out.  One workgroup per row, the row read from memory twice (max pass,
+// exp-sum pass): nothing of it is kept in LDS or registers, so V is unbounded.  Order of the sums as in ce_row_kernel: thread strips
+// in ascending i (16-byte loads over the multiple-of-4 part of a 16-byte-aligned row, the last V % 4 elements scalar; a row that
+// is not aligned scalar throughout), wave butterfly, (w0 + w1) + (w2 + w3).  A target outside [0, V) raises *err and reads the
+// clamped column (clamp_target).
+__global__ __launch_bounds__(256) void pick_logprob_kernel(const float* logits, int64_t ld, int V, const int32_t* target, float* lp_out,
+                                                           int* err) {
+    __shared__ float sred[4];
+    const int64_t r = blockIdx.x;
+    const float* row = logits + r * ld;
+    const int tid = threadIdx.x;
+    const int V4 = ((reinterpret_cast<uintptr_t>(row) & 15) == 0) ? (V & ~3) : 0;       // the part read by 16-byte loads
+    float m = -INFINITY;
+    for (int c = tid * 4; c < V4; c += 1024) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + c);
+        m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
+    }
+    for (int c = V4 + tid; c < V; c += 256) m = fmaxf(m, row[c]);
+    m = block_max_256<false>(m, sred);
+    float s = 0.f;
+    for (int c = tid * 4; c < V4; c += 1024) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + c);
+        s += expf(v[0] - m) + expf(v[1] - m) + expf(v[2] - m) + expf(v[3] - m);
+    }
+    for (int c = V4 + tid; c < V; c += 256) s += expf(row[c] - m);
+    const float tot = block_sum_256(s, sred);
+    if (tid == 0) {
+        const int64_t t = target[r];
+        if ((t < 0 || t >= V) && err) atomicExch(err, 2);
+        lp_out[r] = fminf(row[clamp_target(t, V)] - m - logf(tot), 0.f);
+    }
+}
+int pick_logprob(hipStream_t s, const float* logits, int64_t ld, int64_t rows, int V, const int32_t* target, float* lp_out, int* err_flag) {
+    if (rows <= 0) return 0;
+    S2VT_REQUIRE(V > 0 && ld >= V && logits && target && lp_out, "pick_logprob: bad arguments");
+    hipLaunchKernelGGL(pick_logprob_kernel, dim3((unsigned)rows), dim3(256), 0, s, logits, ld, V, target, lp_out, err_flag);
+    S2VT_LAUNCH_CHECK("pick_logprob_kernel");
+    return 0;
+}
+
+// The captions of a scoring call, caps[b][k][j] at b * stride_b + k * stride_k + j (either stride may be 0: a broadcast view), as
+// what the word steps and the head read: tok [T][Rp] int32, time-major over the fixed rows r = b * K + k (rows R..Rp: token 0),
+// and row_b [Rp] = r / K (pad rows: 0).  EVERY id of the tensor is checked, also behind the first <eos> (nn.Embedding would have
+// seen it, S2VTModel.py:71): one outside [0, V) raises *err and is stored clamped, so nothing downstream indexes with it.
+__global__ __launch_bounds__(256) void score_prep_kernel(const int64_t* caps, int64_t stride_b, int64_t stride_k, int R, int K, int T,
+                                                         int Rp, int V, int32_t* tok, int32_t* row_b, int* err) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)T * Rp) return;
+    const int j = (int)(i / Rp), r = (int)(i % Rp);
+    int32_t t = 0;
+    if (r < R) {
+        const int64_t c = caps[(int64_t)(r / K) * stride_b + (int64_t)(r % K) * stride_k + j];
+        if (c < 0 || c >= V) atomicExch(err, 1);
+        t = (int32_t)clamp_target(c, V);
+    }
+    tok[i] = t;
+    if (j == 0) row_b[r] = r < R ? r / K : 0;
+}
+int score_prep(hipStream_t s, const int64_t* caps, int64_t stride_b, int64_t stride_k, int R, int K, int T, int Rp, int V, int32_t* tok,
+               int32_t* row_b, int* err_flag) {
+    S2VT_REQUIRE(caps && tok && row_b && err_flag && R > 0 && K > 0 && T > 1 && Rp >= R && V > 0, "score_prep: bad arguments");
+    const int64_t n = (int64_t)T * Rp;
+    hipLaunchKernelGGL(score_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, caps, stride_b, stride_k, R, K, T, Rp, V,
+                       tok, row_b, err_flag);
+    S2VT_LAUNCH_CHECK("score_prep_kernel");
+    return 0;
+}
+
+// The finisher of a scoring call, one lane per caption: n = the position of the first <eos> among tok[1..T-1] counted from 1 (none:
+// T - 1), token_lp[r][j] = lp[j][r] for j < n and 0 behind, score = (their fp32 sum, j ascending) / powa[n], powa[n] = fp32(n **
+// alpha) from the host's table (beam_cum.hip's power rule).  Sequential per caption: deterministic.
+__global__ __launch_bounds__(256) void score_finish_kernel(const float* lp, const int32_t* tok, int R, int Rp, int T, int eos,
+                                                           const float* powa, float* token_lp, float* score, int64_t* length) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const int S = T - 1;
+    int n = S;
+    for (int j = 0; j < S; ++j)
+        if (tok[(int64_t)(j + 1) * Rp + r] == eos) { n = j + 1; break; }
+    float sum = 0.f;
+    for (int j = 0; j < S; ++j) {
+        const float l = j < n ? lp[(int64_t)j * Rp + r] : 0.f;
+        token_lp[(int64_t)r * S + j] = l;
+        if (j < n) sum += l;
+    }
+    score[r] = sum / powa[n];
+    length[r] = n;
+}
+int score_finish(hipStream_t s, const float* lp, const int32_t* tok, int R, int Rp, int T, int eos, const float* powa, float* token_lp,
+                 float* score, int64_t* length) {
+    S2VT_REQUIRE(lp && tok && powa && token_lp && score && length && R > 0 && Rp >= R && T > 1, "score_finish: bad arguments");
+    hipLaunchKernelGGL(score_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, s, lp, tok, R, Rp, T, eos, powa, token_lp,
+                       score, length);
+    S2VT_LAUNCH_CHECK("score_finish_kernel");
+    return 0;
+}
+
 }  // namespace s2vt

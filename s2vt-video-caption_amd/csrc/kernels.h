@@ -367,4 +367,15 @@ int weighted_ce_fwd(hipStream_t s, const float* logits, int64_t rows, int V, con
 int weighted_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
                     const float* weight, int64_t ldw, const float* lse, const float* fwd_out, const float* gout, float* dlogits);
 
+// caption scoring (mode='score'): the log-prob of one given token per logits row (target outside [0, V): *err_flag raised, the
+// clamped column read); the captions as time-major int32 tokens + the rows' clips; per-caption length, masked sum and score
+int pick_logprob(hipStream_t s, const float* logits, int64_t ld, int64_t rows, int V, const int32_t* target, float* lp_out, int* err_flag);
+int score_prep(hipStream_t s, const int64_t* caps, int64_t stride_b, int64_t stride_k, int R, int K, int T, int Rp, int V, int32_t* tok,
+               int32_t* row_b, int* err_flag);
+int score_finish(hipStream_t s, const float* lp, const int32_t* tok, int R, int Rp, int T, int eos, const float* powa, float* token_lp,
+                 float* score, int64_t* length);
+// fp32(len ** alpha) for len = 0..D (len 0: 1), libm double pow then fp32, in pinned host memory that lives for the life of the
+// process (beam_cum.hip: the power rule of mode='beam'); null when no pinned memory is left
+const float* length_pow_table(double alpha, int D);
+
 }  // namespace s2vt

@@ -741,6 +741,25 @@ def gather_rows(src, idx):
     return out
 
 
+def pick_logprob(logits, target):
+    """(lp [rows], flag int32 [1]): lp[r] = min(log_softmax(logits[r])[target[r]], 0) (s2vt_pick_logprob, the head kernel of
+    mode='score').  logits float32 [rows, V] with a unit column stride (any row stride >= V), target int32 [rows]; a target outside
+    [0, V) sets flag and reads the nearest valid column."""
+    lib = capi.load()
+    logits = _f32rows(logits, "logits")
+    require_hip(target, "target")
+    rows, V = logits.shape
+    if target.dtype != torch.int32 or target.numel() != rows or not target.is_contiguous():
+        raise ValueError("target must be a contiguous int32 tensor of %d ids" % rows)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        lp = torch.empty(rows, dtype=torch.float32, device=dev)
+        flag = torch.zeros(1, dtype=torch.int32, device=dev)
+        capi.check(lib.s2vt_pick_logprob(_ptr(logits), logits.stride(0), rows, V, _ptr(target), _ptr(lp), _ptr(flag), _stream(dev)),
+                   "s2vt_pick_logprob")
+    return lp, flag
+
+
 def transpose(x):
     """x^T as a new contiguous tensor (s2vt_transpose_f32)."""
     lib = capi.load()
