@@ -671,6 +671,31 @@ size_t s2vt_lstm_seq_bwd_x3_workspace_bytes(int32_t T, int32_t B, int32_t H, int
 int s2vt_lstm_seq_bwd_x3_persist(int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
                                  const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
                                  float* stash_dg1, int32_t block, void* workspace, size_t workspace_bytes, void* stream);
+/* ---- the persistent split-precision kernels' fused outputs, TEST SUPPORT (tests/test_gpu_persist_emit.py): the two entry points
+ * above with the fields that otherwise only the train / decode drivers fill in.  No kernel of their own; the extra arguments are
+ * checked on the host and refused with S2VT_ERR_ARG and a message before any device call.
+ *
+ * s2vt_lstm_seq_fwd_x3_persist_emit: hblk (per layer, nullable) - h_t also as the blocked 3-plane row image of
+ * s2vt_split_planes(3 planes) that the batched GEMMs read: rows t * B + b of ldhblk elements, k = unit; needs B % 64 == 0,
+ * ldhblk >= 3 * (H rounded up to 64), ldhblk % 8 == 0, 16-byte aligned, (T * B) rows.  The kernel writes whole 16-unit k records:
+ * units [H, 16 * ceil(H / 16)) of a written row receive zeros, nothing past them is touched (the caller keeps those at zero).
+ * no_stash = 1: the activated gates are not written back to gx_stash.
+ *
+ * s2vt_lstm_seq_bwd_x3_persist_emit: dgp (per layer, nullable) - dG_t also as such a row image with k = g * H + u: needs
+ * H % 8 == 0, B % 64 == 0, lddgp >= 3 * (4H rounded up to 64), lddgp % 8 == 0, 16-byte aligned; exactly the elements of rows
+ * < T * B, k < 4H are written (the k padding is the caller's to zero).  colpart (per layer, nullable) [T * B / 32][4H]: the column
+ * sums of dG over each 32-row chain, row t * (B / 32) + chain (s2vt_colsum_finish over them is the bias gradient).  skip_dg = 1
+ * (needs dgp for every layer): the fp32 dG is not stored and stash_dg keeps the activated gates. */
+int s2vt_lstm_seq_fwd_x3_persist_emit(int32_t T, int32_t B, int32_t H, float* gx_stash0, float* gx_stash1, int32_t n_gx,
+                                      const float* bias0, const float* bias1, const float* w_hh0, const float* w_hh1, float* h_all0,
+                                      float* h_all1, float* c_all0, float* c_all1, uint16_t* hblk0, int64_t ldhblk0, uint16_t* hblk1,
+                                      int64_t ldhblk1, int32_t no_stash, int32_t block, void* workspace, size_t workspace_bytes,
+                                      void* stream);
+int s2vt_lstm_seq_bwd_x3_persist_emit(int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
+                                      const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
+                                      float* stash_dg1, uint16_t* dgp0, int64_t lddgp0, uint16_t* dgp1, int64_t lddgp1, float* colpart0,
+                                      float* colpart1, int32_t skip_dg, int32_t block, void* workspace, size_t workspace_bytes,
+                                      void* stream);
 /* One greedy decode step's out_linear + argmax (S2VTModel.py:95-96,105-106): packed[b] (zeroed by the caller)
  * receives max over v of (ordered(logit) << 32 | (0xFFFFFFFF - v)); token = 0xFFFFFFFF - low 32 bits. */
 int s2vt_decode_step_argmax(int32_t B, int32_t H, int32_t V, const float* h, const float* w_out, const float* b_out,

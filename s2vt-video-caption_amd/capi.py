@@ -169,6 +169,12 @@ SIGNATURES = {
     "s2vt_lstm_seq_bwd_x3_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "s2vt_lstm_seq_bwd_x3_persist": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32] +
                                      [c_void_p] * 4 + [c_int32, c_void_p, c_size_t, c_void_p]),
+    # per-op test support: the persistent split-precision kernels' fused outputs (tests/test_gpu_persist_emit.py)
+    "s2vt_lstm_seq_fwd_x3_persist_emit": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 8 +
+                                          [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_size_t, c_void_p]),
+    "s2vt_lstm_seq_bwd_x3_persist_emit": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32] +
+                                          [c_void_p] * 4 + [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32,
+                                                            c_void_p, c_size_t, c_void_p]),
     "s2vt_set_recurrence_mode": (c_int32, [c_int32]),
     "s2vt_recurrence_plan": (c_int32, [c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
     "s2vt_decode_plan": (c_int32, [POINTER(Dims), c_int32, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32)]),

@@ -628,16 +628,26 @@ size_t s2vt_lstm_seq_x3_workspace_bytes(int32_t T, int32_t B, int32_t H) {
     const size_t Kp = (size_t)(H + 63) / 64 * 64;
     return 256 + 2 * lstm_persist_sync_bytes() + 2 * align_up(3 * 4 * (size_t)H * Kp * 2, 256) + 2 * align_up(3 * (size_t)T * B * Kp * 2, 256);
 }
-int s2vt_lstm_seq_fwd_x3_persist(int32_t T, int32_t B, int32_t H, float* gx_stash0, float* gx_stash1, int32_t n_gx,
-                                 const float* bias0, const float* bias1, const float* w_hh0, const float* w_hh1, float* h_all0,
-                                 float* h_all1, float* c_all0, float* c_all1, int32_t block, void* workspace,
-                                 size_t workspace_bytes, void* stream) {
+// One body for the entry point and its test-support form (s2vt_lstm_seq_fwd_x3_persist_emit): the latter also fills in the fields
+// that otherwise only the train / decode drivers set - SeqFwdX3Args::hblk / ldhblk (h_t as the batched GEMMs' row image) and
+// no_stash.  The image's requirements repeat prep_x so that they are refused here, before any device call.
+struct X3Image { unsigned short* p; int64_t ld; };
+static bool x3_image_ok(const X3Image& im, int B, int64_t k) {
+    return !im.p || (B % 64 == 0 && im.ld >= 3 * ((k + 63) / 64 * 64) && im.ld % 8 == 0 && (reinterpret_cast<uintptr_t>(im.p) & 15) == 0);
+}
+static int seq_fwd_x3_entry(const char* who, int32_t T, int32_t B, int32_t H, float* gx_stash0, float* gx_stash1, int32_t n_gx,
+                            const float* bias0, const float* bias1, const float* w_hh0, const float* w_hh1, float* h_all0,
+                            float* h_all1, float* c_all0, float* c_all1, X3Image hblk0, X3Image hblk1, int32_t no_stash,
+                            int32_t block, void* workspace, size_t workspace_bytes, void* stream) {
     S2VT_REQUIRE(T > 0 && B > 0 && H > 0 && gx_stash0 && w_hh0 && h_all0 && c_all0 && workspace && n_gx >= 0 && n_gx <= T &&
-                     (n_gx == T || bias0), "s2vt_lstm_seq_fwd_x3_persist: bad arguments");
-    S2VT_REQUIRE(H <= 1024 && lstm_seq_fwd_x3_persist_supported(B, H), "s2vt_lstm_seq_fwd_x3_persist: shape not supported");
-    S2VT_REQUIRE(workspace_bytes >= s2vt_lstm_seq_x3_workspace_bytes(T, B, H), "s2vt_lstm_seq_fwd_x3_persist: workspace too small");
+                     (n_gx == T || bias0) && (no_stash == 0 || no_stash == 1), "%s: bad arguments", who);
     const bool two = gx_stash1 != nullptr;
-    S2VT_REQUIRE(!two || (w_hh1 && h_all1 && c_all1 && (n_gx == T || bias1)), "s2vt_lstm_seq_fwd_x3_persist: second layer incomplete");
+    S2VT_REQUIRE(two || !hblk1.p, "%s: an h row image for a second layer that is not there", who);
+    S2VT_REQUIRE(x3_image_ok(hblk0, B, H) && x3_image_ok(hblk1, B, H),
+                 "%s: the h row image needs B %% 64 == 0 and 16-byte aligned rows of ldhblk >= 3 * pad64(H) elements, ldhblk %% 8 == 0", who);
+    S2VT_REQUIRE(H <= 1024 && lstm_seq_fwd_x3_persist_supported(B, H), "%s: shape not supported", who);
+    S2VT_REQUIRE(workspace_bytes >= s2vt_lstm_seq_x3_workspace_bytes(T, B, H), "%s: workspace too small", who);
+    S2VT_REQUIRE(!two || (w_hh1 && h_all1 && c_all1 && (n_gx == T || bias1)), "%s: second layer incomplete", who);
     const int64_t Kp = (H + 63) / 64 * 64;
     const size_t wbytes = align_up(3 * 4 * (size_t)H * Kp * 2, 256), hbytes = align_up(3 * (size_t)T * B * Kp * 2, 256);
     char* base = reinterpret_cast<char*>(workspace);
@@ -656,12 +666,32 @@ int s2vt_lstm_seq_fwd_x3_persist(int32_t T, int32_t B, int32_t H, float* gx_stas
     for (int t0 = 0; t0 < T; t0 += blk) {
         const int t1 = (t0 + blk < T) ? t0 + blk : T;
         ProfScope ps(st, K_STEP_FWD, (two ? 2 : 1) * (t1 - t0));
-        const SeqFwdX3Args a0 = persist_fwd_x3_args(t0, t1, B, H, T, Kp, gx_stash0, n_gx, bias0, wp[0], hp[0], h_all0, c_all0, sa, err);
+        SeqFwdX3Args a0 = persist_fwd_x3_args(t0, t1, B, H, T, Kp, gx_stash0, n_gx, bias0, wp[0], hp[0], h_all0, c_all0, sa, err);
+        a0.hblk = hblk0.p; a0.ldhblk = hblk0.ld; a0.no_stash = no_stash;
         SeqFwdX3Args a1;
-        if (two) a1 = persist_fwd_x3_args(t0, t1, B, H, T, Kp, gx_stash1, n_gx, bias1, wp[1], hp[1], h_all1, c_all1, sb, err);
+        if (two) {
+            a1 = persist_fwd_x3_args(t0, t1, B, H, T, Kp, gx_stash1, n_gx, bias1, wp[1], hp[1], h_all1, c_all1, sb, err);
+            a1.hblk = hblk1.p; a1.ldhblk = hblk1.ld; a1.no_stash = no_stash;
+        }
         if ((rc = lstm_seq_fwd_x3_persist2(st, a0, two ? &a1 : nullptr))) return rc;
     }
     return 0;
+}
+int s2vt_lstm_seq_fwd_x3_persist(int32_t T, int32_t B, int32_t H, float* gx_stash0, float* gx_stash1, int32_t n_gx,
+                                 const float* bias0, const float* bias1, const float* w_hh0, const float* w_hh1, float* h_all0,
+                                 float* h_all1, float* c_all0, float* c_all1, int32_t block, void* workspace,
+                                 size_t workspace_bytes, void* stream) {
+    return seq_fwd_x3_entry("s2vt_lstm_seq_fwd_x3_persist", T, B, H, gx_stash0, gx_stash1, n_gx, bias0, bias1, w_hh0, w_hh1, h_all0, h_all1,
+                            c_all0, c_all1, X3Image{nullptr, 0}, X3Image{nullptr, 0}, 0, block, workspace, workspace_bytes, stream);
+}
+int s2vt_lstm_seq_fwd_x3_persist_emit(int32_t T, int32_t B, int32_t H, float* gx_stash0, float* gx_stash1, int32_t n_gx,
+                                      const float* bias0, const float* bias1, const float* w_hh0, const float* w_hh1, float* h_all0,
+                                      float* h_all1, float* c_all0, float* c_all1, uint16_t* hblk0, int64_t ldhblk0, uint16_t* hblk1,
+                                      int64_t ldhblk1, int32_t no_stash, int32_t block, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return seq_fwd_x3_entry("s2vt_lstm_seq_fwd_x3_persist_emit", T, B, H, gx_stash0, gx_stash1, n_gx, bias0, bias1, w_hh0, w_hh1, h_all0,
+                            h_all1, c_all0, c_all1, X3Image{hblk0, ldhblk0}, X3Image{hblk1, ldhblk1}, no_stash, block, workspace,
+                            workspace_bytes, stream);
 }
 // split-precision persistent BPTT as its own entry point.
 // workspace: [err int x64][sync A][sync B] then per layer [W_hh^T fp32][W_hh^T planes][dc][partial-sum ring]
@@ -675,15 +705,22 @@ size_t s2vt_lstm_seq_bwd_x3_workspace_bytes(int32_t T, int32_t B, int32_t H, int
     const int blk = (block > 0 && block < T) ? block : T;
     return 256 + 2 * lstm_persist_sync_bytes() + 2 * bwd_x3_ws_layer_bytes(T, B, H, blk + 1);
 }
-int s2vt_lstm_seq_bwd_x3_persist(int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
-                                 const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
-                                 float* stash_dg1, int32_t block, void* workspace, size_t workspace_bytes, void* stream) {
-    S2VT_REQUIRE(T > 0 && B > 0 && H > 0 && w_hh0 && c_all0 && stash_dg0 && workspace && dh_first >= 0,
-                 "s2vt_lstm_seq_bwd_x3_persist: bad arguments");
-    S2VT_REQUIRE(H <= 1024 && lstm_seq_bwd_x3_persist_supported(B, H), "s2vt_lstm_seq_bwd_x3_persist: shape not supported");
-    S2VT_REQUIRE(workspace_bytes >= s2vt_lstm_seq_bwd_x3_workspace_bytes(T, B, H, block), "s2vt_lstm_seq_bwd_x3_persist: workspace too small");
+// ... and for the BPTT (s2vt_lstm_seq_bwd_x3_persist_emit): SeqBwdX3Args::dgp / lddgp, colpart and skip_dg, refused as prep_y does.
+static int seq_bwd_x3_entry(const char* who, int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
+                            const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
+                            float* stash_dg1, X3Image dgp0, X3Image dgp1, float* colpart0, float* colpart1, int32_t skip_dg, int32_t block,
+                            void* workspace, size_t workspace_bytes, void* stream) {
+    S2VT_REQUIRE(T > 0 && B > 0 && H > 0 && w_hh0 && c_all0 && stash_dg0 && workspace && dh_first >= 0 && (skip_dg == 0 || skip_dg == 1),
+                 "%s: bad arguments", who);
     const bool two = stash_dg1 != nullptr;
-    S2VT_REQUIRE(!two || (w_hh1 && c_all1), "s2vt_lstm_seq_bwd_x3_persist: second layer incomplete");
+    S2VT_REQUIRE(two || (!dgp1.p && !colpart1), "%s: a dG row image or column sums for a second layer that is not there", who);
+    S2VT_REQUIRE((!dgp0.p && !dgp1.p) || H % 8 == 0, "%s: the dG row image needs H %% 8 == 0", who);
+    S2VT_REQUIRE(x3_image_ok(dgp0, B, 4 * (int64_t)H) && x3_image_ok(dgp1, B, 4 * (int64_t)H),
+                 "%s: the dG row image needs B %% 64 == 0 and 16-byte aligned rows of lddgp >= 3 * pad64(4H) elements, lddgp %% 8 == 0", who);
+    S2VT_REQUIRE(!skip_dg || (dgp0.p && (!two || dgp1.p)), "%s: skip_dg without a dG row image", who);
+    S2VT_REQUIRE(H <= 1024 && lstm_seq_bwd_x3_persist_supported(B, H), "%s: shape not supported", who);
+    S2VT_REQUIRE(workspace_bytes >= s2vt_lstm_seq_bwd_x3_workspace_bytes(T, B, H, block), "%s: workspace too small", who);
+    S2VT_REQUIRE(!two || (w_hh1 && c_all1), "%s: second layer incomplete", who);
     const int blk = (block > 0 && block < T) ? block : T;
     const int64_t Kp = (H + 63) / 64 * 64, Hp = (H + 15) / 16 * 16;
     const int64_t pslot = (int64_t)lstm_seq_bwd_x3_part_slot_floats(B, H);
@@ -709,14 +746,33 @@ int s2vt_lstm_seq_bwd_x3_persist(int32_t T, int32_t B, int32_t H, const float* w
     for (int t1 = T; t1 > 0; t1 -= blk) {
         const int t0 = (t1 - blk > 0) ? t1 - blk : 0;
         ProfScope ps(st, K_STEP_BWD, (two ? 2 : 1) * (t1 - t0));
-        const SeqBwdX3Args a0 = persist_bwd_x3_args(T, t0, t1, B, H, Kp, Hp, wtp[0], dh_out0, dh_first, c_all0, stash_dg0, dc[0],
-                                                    part[0], pslot, blk + 1, sy[0], err);
+        SeqBwdX3Args a0 = persist_bwd_x3_args(T, t0, t1, B, H, Kp, Hp, wtp[0], dh_out0, dh_first, c_all0, stash_dg0, dc[0],
+                                              part[0], pslot, blk + 1, sy[0], err);
+        a0.dgp = dgp0.p; a0.lddgp = dgp0.ld; a0.colpart = colpart0; a0.skip_dg = skip_dg;
         SeqBwdX3Args a1;
-        if (two) a1 = persist_bwd_x3_args(T, t0, t1, B, H, Kp, Hp, wtp[1], dh_out1, dh_first, c_all1, stash_dg1, dc[1],
-                                          part[1], pslot, blk + 1, sy[1], err);
+        if (two) {
+            a1 = persist_bwd_x3_args(T, t0, t1, B, H, Kp, Hp, wtp[1], dh_out1, dh_first, c_all1, stash_dg1, dc[1],
+                                     part[1], pslot, blk + 1, sy[1], err);
+            a1.dgp = dgp1.p; a1.lddgp = dgp1.ld; a1.colpart = colpart1; a1.skip_dg = skip_dg;
+        }
         if ((rc = lstm_seq_bwd_x3_persist2(st, a0, two ? &a1 : nullptr))) return rc;
     }
     return 0;
+}
+int s2vt_lstm_seq_bwd_x3_persist(int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
+                                 const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
+                                 float* stash_dg1, int32_t block, void* workspace, size_t workspace_bytes, void* stream) {
+    return seq_bwd_x3_entry("s2vt_lstm_seq_bwd_x3_persist", T, B, H, w_hh0, w_hh1, dh_out0, dh_out1, dh_first, c_all0, c_all1, stash_dg0,
+                            stash_dg1, X3Image{nullptr, 0}, X3Image{nullptr, 0}, nullptr, nullptr, 0, block, workspace, workspace_bytes, stream);
+}
+int s2vt_lstm_seq_bwd_x3_persist_emit(int32_t T, int32_t B, int32_t H, const float* w_hh0, const float* w_hh1, const float* dh_out0,
+                                      const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1, float* stash_dg0,
+                                      float* stash_dg1, uint16_t* dgp0, int64_t lddgp0, uint16_t* dgp1, int64_t lddgp1, float* colpart0,
+                                      float* colpart1, int32_t skip_dg, int32_t block, void* workspace, size_t workspace_bytes,
+                                      void* stream) {
+    return seq_bwd_x3_entry("s2vt_lstm_seq_bwd_x3_persist_emit", T, B, H, w_hh0, w_hh1, dh_out0, dh_out1, dh_first, c_all0, c_all1,
+                            stash_dg0, stash_dg1, X3Image{dgp0, lddgp0}, X3Image{dgp1, lddgp1}, colpart0, colpart1, skip_dg, block,
+                            workspace, workspace_bytes, stream);
 }
 
 }

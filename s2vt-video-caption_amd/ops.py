@@ -416,6 +416,92 @@ def lstm_seq_bwd_persist(T, B, w_hh, dh_out, dh_first, c_all, gates, block=0, se
     return sets[0][3] if second is None else (sets[0][3], sets[1][3])
 
 
+def row_plane_image(rows, k, dev, fill=0, extra_ld=0, extra_rows=0):
+    """(image, ld): an int16 blocked 3-plane ROW image for `rows` rows of k elements as split_planes lays it out (row stride
+    3 * pad64(k) + extra_ld, extra_rows further rows), every element = fill"""
+    ld = 3 * ((k + 63) // 64 * 64) + extra_ld
+    return torch.full(((rows + 63) // 64 * 64 + extra_rows, ld), fill, dtype=torch.int16, device=dev), ld
+
+
+def _f32_inout(t, name):
+    """a buffer the call writes into: float32 and contiguous as it stands (a copy would take the results with it)"""
+    if _f32c(t, name) is not t:
+        raise capi.S2VTHipError("%s is written in place and must be contiguous" % name)
+    return t
+
+
+def _x3_image(img, name):
+    if img is None:
+        return None, 0
+    t, ld = img
+    require_hip(t, name)
+    if t.dtype != torch.int16 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) != ld:
+        raise capi.S2VTHipError("%s must be (int16 rows with unit column stride, their row stride)" % name)
+    return t, int(ld)
+
+
+def lstm_seq_fwd_persist_emit(T, B, stash, n_gx, bias, w_hh, hblk=None, no_stash=False, block=0, second=None):
+    """lstm_seq_fwd_persist with the fields the train / decode drivers fill in (s2vt_lstm_seq_fwd_x3_persist_emit).  stash
+    [T*B, 4H]: the caller's buffer, its first n_gx * B rows the gate input; the activated gates are written into it unless
+    no_stash.  hblk = (int16 image, row stride) or None: h_t as the batched GEMMs' row image, written into the caller's tensor
+    (row_plane_image).  Returns (h_all, c_all); `second` = (stash, bias, w_hh, hblk) of a layer that shares every launch: then
+    a pair of them."""
+    lib = capi.load()
+    w_hh = _f32c(w_hh, "w_hh")
+    H = w_hh.shape[1]
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        n = lib.s2vt_lstm_seq_x3_workspace_bytes(T, B, H)
+        if n == 0:
+            raise capi.S2VTHipError("lstm_seq_fwd_persist_emit: shape B=%d H=%d is not supported on this device" % (B, H))
+        ws = torch.full((n,), 0xFF, dtype=torch.uint8, device=dev)      # (bf16 NaN patterns, as lstm_seq_fwd_persist)
+        sets = []
+        for s, b, w, im in [(stash, bias, w_hh, hblk)] + ([second] if second is not None else []):
+            s = _f32_inout(s, "stash")
+            if tuple(s.shape) != (T * B, 4 * H):
+                raise capi.S2VTHipError("lstm_seq_fwd_persist_emit: stash must be [T*B, 4H]")
+            sets.append((s, b, _f32c(w, "w_hh"), torch.empty(T * B, H, dtype=torch.float32, device=dev),
+                         torch.empty(T * B, H, dtype=torch.float32, device=dev)) + _x3_image(im, "hblk"))
+        a, b2 = sets[0], (sets[1] if len(sets) > 1 else (None,) * 6 + (0,))
+        capi.check(lib.s2vt_lstm_seq_fwd_x3_persist_emit(T, B, H, _ptr(a[0]), _ptr(b2[0]), int(n_gx), _ptr(a[1]), _ptr(b2[1]), _ptr(a[2]),
+                                                         _ptr(b2[2]), _ptr(a[3]), _ptr(b2[3]), _ptr(a[4]), _ptr(b2[4]), _ptr(a[5]), a[6],
+                                                         _ptr(b2[5]), b2[6], int(bool(no_stash)), int(block), _ptr(ws), n, _stream(dev)),
+                   "s2vt_lstm_seq_fwd_x3_persist_emit")
+        _check_persist_err(ws)
+    outs = [(x[3], x[4]) for x in sets]
+    return outs[0] if second is None else tuple(outs)
+
+
+def lstm_seq_bwd_persist_emit(T, B, w_hh, dh_out, dh_first, c_all, stash_dg, dgp=None, colpart=None, skip_dg=False, block=0, second=None):
+    """lstm_seq_bwd_persist with the fields the train driver fills in (s2vt_lstm_seq_bwd_x3_persist_emit), everything written
+    into the caller's tensors: stash_dg [T*B, 4H] (activated gates in; fp32 dG out unless skip_dg), dgp = (int16 image, row
+    stride) or None: dG_t as the batched GEMMs' row image, colpart [>= T*B/32, 4H] or None: its 32-row column sums.
+    `second` = (w_hh, dh_out, c_all, stash_dg, dgp, colpart)."""
+    lib = capi.load()
+    w_hh = _f32c(w_hh, "w_hh")
+    H = w_hh.shape[1]
+    dev = w_hh.device
+    with torch.cuda.device(dev):
+        n = lib.s2vt_lstm_seq_bwd_x3_workspace_bytes(T, B, H, int(block))
+        ws = torch.full((n,), 0xFF, dtype=torch.uint8, device=dev)     # (NaN patterns, as lstm_seq_bwd_persist)
+        sets = []
+        for w, dh, c, s, im, cp in [(w_hh, dh_out, c_all, stash_dg, dgp, colpart)] + ([second] if second is not None else []):
+            s = _f32_inout(s, "stash_dg")
+            if tuple(s.shape) != (T * B, 4 * H):
+                raise capi.S2VTHipError("lstm_seq_bwd_persist_emit: stash_dg must be [T*B, 4H]")
+            if cp is not None:
+                cp = _f32_inout(cp, "colpart")
+                if cp.dim() != 2 or cp.shape[0] < T * (B // 32) or cp.shape[1] != 4 * H:
+                    raise capi.S2VTHipError("lstm_seq_bwd_persist_emit: colpart must be [>= T*B/32, 4H]")
+            sets.append((_f32c(w, "w_hh"), dh, _f32c(c, "c_all"), s) + _x3_image(im, "dgp") + (cp,))
+        a, b2 = sets[0], (sets[1] if len(sets) > 1 else (None,) * 5 + (0, None))
+        capi.check(lib.s2vt_lstm_seq_bwd_x3_persist_emit(T, B, H, _ptr(a[0]), _ptr(b2[0]), _ptr(a[1]), _ptr(b2[1]), int(dh_first),
+                                                         _ptr(a[2]), _ptr(b2[2]), _ptr(a[3]), _ptr(b2[3]), _ptr(a[4]), a[5], _ptr(b2[4]),
+                                                         b2[5], _ptr(a[6]), _ptr(b2[6]), int(bool(skip_dg)), int(block), _ptr(ws), n,
+                                                         _stream(dev)), "s2vt_lstm_seq_bwd_x3_persist_emit")
+        _check_persist_err(ws)
+
+
 # ---------------------------------------------------------------- GRU cell (include/s2vt_hip.h: s2vt_gru_*)
 def gru_step_fwd(gx, b_ih, w_hh, b_hh, h_prev, want_stash=False, B=None):
     """One nn.GRU step: gx [B,3H] (x W_ih^T + b_ih) or None (then b_ih alone: a zero input); h_prev [B,H] or None (zero state;
