@@ -45,7 +45,7 @@ static BeamWS carve_beam(const s2vt_dims& d, int max_rows, void* base) {
     w.gws_floats = 4 * R * (V > 4 * H ? V : 4 * H);
     w.gws = c.take<float>(w.gws_floats);
     w.err = c.take<int>(4);
-    w.pvid = take_planes(c, d.B, H, 3); w.pword = take_planes(c, R, H, 3);
+    w.pvid = take_planes(c, d.B, H, DECODE_PLANES); w.pword = take_planes(c, R, H, DECODE_PLANES);
     w.bytes = align_up(c.off, 256);
     return w;
 }
@@ -69,8 +69,7 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     const BeamWS w = carve_beam(*d, R > 0 ? R : 1, workspace);
     hipStream_t st = (hipStream_t)stream;
     int rc;
-    if (!gx_vid && (rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
-    if (!gx_vid && (rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
+    if (!gx_vid && (rc = bias_sums(st, p, H, w.bsum1, w.bsum2))) return rc;
     if (!gx_vid) {   // one zero-input vid_rnn step for the whole batch (S2VTModel.py:208-210)
         StepFwdArgs a = {};
         a.B = B; a.H = H;
@@ -97,7 +96,6 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         // as blocked 3-plane operands, the per-token gate table): the vid_out half of the gate input once per SAMPLE (every beam
         // slot reads its sample's row), the embedded word from the table, out_linear on the bf16 matrix cores in split
         // precision (fp32-equivalent) from the h_t planes the step kernel writes itself
-        XP = 3;
         S2VT_REQUIRE(cache_bytes >= carve_decode_const(*d, nullptr).bytes, "s2vt_beam_step_cached: cache too small");
         const DecodeConst kc = carve_decode_const(*d, cache);
         if (!gx_vid) {

@@ -41,10 +41,9 @@ static DecodeWS carve_decode(const s2vt_dims& d, void* base) {
     w.gws_floats = gemm_ws_floats(d);
     w.gws_a = c.take<float>(w.gws_floats); w.gws_b = c.take<float>(w.gws_floats);
     if (planes_ok(d)) {
-        XP = 3;     // greedy decode must stay fp32-equivalent (bit-exact ids): split precision in every plane mode
-        w.feats = take_planes(c, B * L, F, XP); w.px1 = take_planes(c, L * B, H, XP);
-        w.ph1 = take_planes(c, T * B, H, XP);   w.ph2 = take_planes(c, B, H, XP);
-        w.embp = take_planes(c, d.V, d.E, XP);  w.wep = take_planes(c, 4 * H, d.E, XP);
+        w.feats = take_planes(c, B * L, F, DECODE_PLANES); w.px1 = take_planes(c, L * B, H, DECODE_PLANES);
+        w.ph1 = take_planes(c, T * B, H, DECODE_PLANES);   w.ph2 = take_planes(c, B, H, DECODE_PLANES);
+        w.embp = take_planes(c, d.V, d.E, DECODE_PLANES);  w.wep = take_planes(c, 4 * H, d.E, DECODE_PLANES);
     }
     // (0: the persistent encode phase is not selectable.  The plan WITHOUT its device query - a size function works without a GPU -
     // so the carve is broader than the plan: wherever decode_plan selects the persistent encode, the workspace provides for it)
@@ -64,16 +63,14 @@ DecodeConst carve_decode_const(const s2vt_dims& d, void* base) {
     const size_t F = d.F, H = d.H;
     Carver c{reinterpret_cast<char*>(base), 0, 0};
     DecodeConst k;
-    k.gtab = nullptr; k.xw1 = k.xw2 = nullptr;
-    k.wf = k.wih1 = k.wv = k.wo = k.whh = PB{nullptr, 0, 0};
+    k.gtab = nullptr; k.xw1 = k.xw2 = nullptr;      // (the images: PB{})
     if (gemm_mode() != 0) {     // (the images depend on the weights' dims only: one cache serves every batch size)
-        XP = 3;
-        k.wf = take_planes(c, H, F, XP);     k.wih1 = take_planes(c, 4 * H, H, XP);
-        k.wv = take_planes(c, 4 * H, H, XP); k.wo = take_planes(c, d.V, H, XP);
+        k.wf = take_planes(c, H, F, DECODE_PLANES);     k.wih1 = take_planes(c, 4 * H, H, DECODE_PLANES);
+        k.wv = take_planes(c, 4 * H, H, DECODE_PLANES); k.wo = take_planes(c, d.V, H, DECODE_PLANES);
         k.gtab = c.take<float>((size_t)d.V * 4 * H);
         const size_t xkp = (H <= 1024) ? (size_t)pad64((int)H) : 0;
         k.xw1 = c.take<unsigned short>(3 * 4 * H * xkp); k.xw2 = c.take<unsigned short>(3 * 4 * H * xkp);
-        k.whh = take_planes(c, 4 * H, H, XP);       // (last: the images in front keep their offsets)
+        k.whh = take_planes(c, 4 * H, H, DECODE_PLANES);       // (last: the images in front keep their offsets)
     }
     k.bytes = align_up(c.off, 256);
     return k;
@@ -144,32 +141,22 @@ static ArgmaxX3Args argmax_x3_args(int nb, int V, const PB& wo, const unsigned s
     ax.packed = packed;
     return ax;
 }
-// What every schedule of a decode works with - dims, parameters, the workspace and weight-image views, the modes, the plan, the two
-// lanes (la: vid_rnn's, the caller's stream st; lb: word_rnn's, the side stream sx - the same stream when pipe_block is 0), the
-// running event index - and the call shapes the schedules share.  Lives on the stack of one greedy_decode_core call.
-struct DecodeDriver {
+// What every schedule of a decode works with - dims, parameters, the workspace and weight-image views, the modes, the plan, the lane
+// frame (Lanes; la: vid_rnn's lane on the caller's stream, lb: word_rnn's - encode, then the 79 decode steps) - and the call shapes
+// the schedules share.  Lives on the stack of one greedy_decode_core call.
+struct DecodeDriver : Lanes {
     const s2vt_params* p; const float* feats; int64_t* ids;
     const DecodeWS& w; const DecodeConst& kc; const DecodeModes& m; const DecodePlan pl;
     const int B, L, F, H, E, V, T, sos_ix;
     const int64_t BH, B4H;
     const bool fill, fill_all;        // see fill_weight_images
     const bool px;                    // the plan's persistent encode, and the workspace provides for it
-    hipStream_t st, sx;
-    Lane la, lb;
-    size_t ev = 0;
     DecodeDriver(const s2vt_dims* d, const s2vt_params* p_, const float* feats_, int32_t sos_ix_, int64_t* ids_, const DecodeWS& w_,
-                 const DecodeConst& kc_, const DecodeModes& m_, const DecodePlan& pl_, bool cached, bool cache_valid, hipStream_t st_)
+                 const DecodeConst& kc_, const DecodeModes& m_, const DecodePlan& pl_, bool cached, bool cache_valid)
         : p(p_), feats(feats_), ids(ids_), w(w_), kc(kc_), m(m_), pl(pl_), B(d->B), L(d->L), F(d->F), H(d->H), E(d->E), V(d->V),
           T(2 * d->L - 1), sos_ix(sos_ix_), BH((int64_t)d->B * d->H), B4H(4 * (int64_t)d->B * d->H), fill(!(cached && cache_valid)),
-          fill_all(fill && cached), px(pl_.persist_encode && w_.xkp > 0), st(st_), sx(st_) {}
-    int open_lanes() {
-        int rc;
-        if (pipe_block() > 0 && (rc = side_stream(st, &sx))) return rc;
-        la = Lane{st, w.gws_a, w.gws_floats, nullptr};     // vid_rnn lane (caller's stream)
-        lb = Lane{sx, w.gws_b, w.gws_floats, nullptr};     // word_rnn lane: encode, then the 79 decode steps
-        return 0;
-    }
-    int hand(hipStream_t from, hipStream_t to) { return handoff(from, to, ev++); }      // `to` waits for everything enqueued on `from`
+          fill_all(fill && cached), px(pl_.persist_encode && w_.xkp > 0) {}
+    int open_lanes(hipStream_t caller) { return open(caller, w.gws_a, w.gws_b, w.gws_floats, nullptr, nullptr); }
     // the plan's token schedule, ANDed with what only the driver knows (the fused launch needs W_hh's image with W_o's k padding)
     DecSchedule schedule() const {
         if (!px) return DEC_PER_STEP;
@@ -204,10 +191,7 @@ struct DecodeDriver {
     // feature projection + vid_rnn input GEMM on lane A                                  S2VTModel.py:54, 64-67
     int project_features() {
         int rc;
-        if (!pl.planes) {
-            if ((rc = lgemm(la, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, w.x1, H, perm(L, B), p->feat_b, false))) return rc;
-            return lgemm(la, true, true, L * B, 4 * H, H, w.x1, H, ID, p->vid_w_ih, H, ID, w.gx1, 4 * H, ID, w.bsum1, false);
-        }
+        if (!pl.planes) return project_features_f32(la, s2vt_dims{B, L, F, H, E, V}, p, feats, w.x1, w.gx1, w.bsum1);
         if ((rc = psplit(la, w.feats, 0, feats, F, ID, B * L, F))) return rc;
         if (fill && (rc = psplit(la, kc.wf, 0, p->feat_w, F, ID, H, F))) return rc;
         if (fill && (rc = psplit(la, kc.wih1, 0, p->vid_w_ih, H, ID, 4 * H, H))) return rc;
@@ -306,10 +290,7 @@ struct DecodeDriver {
     int encode_x3_persistent(int Tend, int* tv) {
         int rc;
         if ((rc = hand(sx, st))) return rc;                     // lane B's weight images before their first use on this stream
-        {   // (the k16 records of w.ph1 past the last column slice are zeroed here)
-            const size_t kc0 = (size_t)cdiv(H, 16), kc1 = (size_t)(w.ph1.kpad / 16);
-            if (kc1 > kc0) S2VT_HIP(hipMemset2DAsync(w.ph1.p + kc0 * 3072, (size_t)64 * w.ph1.ld * 2, 0, (kc1 - kc0) * 6144, (size_t)(T * B / 64), st));
-        }
+        if ((rc = zero_k16_tail(st, w.ph1, H, (size_t)T * B))) return rc;     // (the k16 records of w.ph1 past the last column slice)
         const std::vector<int> be = pipe_bounds(L, L, balanced_block(L, pipe_block()));     // blocks over the L encode steps
         const int nb = (int)be.size() - 1;
         // vid_rnn's blocks: the encode blocks and ONE block of its decode-phase steps (no input, no token) - the partner of word_rnn's
@@ -450,15 +431,13 @@ static int greedy_decode_core(const s2vt_dims* d, const s2vt_params* p, const fl
     // behind the per-call part of the workspace (rebuilt by every call)
     const DecodeConst kc = carve_decode_const(*d, cache ? cache : reinterpret_cast<char*>(workspace) + w.bytes);
     const DecodePlan pl = decode_plan(*d, m.enc.on);
-    if (pl.planes) XP = 3;
-    DecodeDriver dr(d, p, feats, sos_ix, ids, w, kc, m, pl, cache != nullptr, cache_valid, (hipStream_t)stream);
+    DecodeDriver dr(d, p, feats, sos_ix, ids, w, kc, m, pl, cache != nullptr, cache_valid);
     // (refused BEFORE anything is enqueued: the caller frees the workspace on this error)
     S2VT_REQUIRE(!m.enc.on || dr.px, "s2vt_decode_encode_cached: this shape / mode does not take the persistent split-precision encode phase");
     int rc;
-    if ((rc = dr.open_lanes())) return rc;
+    if ((rc = dr.open_lanes((hipStream_t)stream))) return rc;
     hipStream_t st = dr.st;
-    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * dr.H))) return rc;
-    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * dr.H))) return rc;
+    if ((rc = bias_sums(st, p, dr.H, w.bsum1, w.bsum2))) return rc;
     if ((rc = fill_zero(st, w.packed, sizeof(unsigned long long) * (size_t)(dr.L - 1) * dr.B))) return rc;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = dr.hand(st, dr.sx))) return rc;

@@ -1,6 +1,6 @@
 // Host-side internals shared by the C-ABI units of libs2vt_hip.so:
 //   api_runtime.hip  errors, asynchronous device-side errors, live timing, launch-sequence capture, the side stream, setters
-//   api_shared.hip   plane-operand helpers (split / GEMM wrappers), recurrence loops and argument builders
+//   api_shared.hip   plane-operand helpers (split / GEMM wrappers), the drivers' lane frame and shared prologues, recurrence loops, argument builders
 //   api_train.hip    s2vt_train_forward / s2vt_train_backward (+ dropout, fused criterion backward, gradient-group events)
 //   api_decode.hip   greedy / sampled / scheduled decode and the encode phase for the beam search (DecodeDriver: one function per
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
@@ -107,6 +107,10 @@ static inline int pipe_block() { return option(O_PIPE_BLOCK); }      // timestep
 // 0: fp32-input MFMA GEMMs; 3: split precision, 3 bf16 planes (fp32-equivalent); 1: plain bf16 operands (config 3: bf16
 // storage, fp32 accumulate) for the batched GEMMs AND the timestep kernels (lstm_bf16.hip)
 static inline int gemm_mode() { return option(O_GEMM_MODE); }
+// planes per operand of the TRAIN plane drivers: bf16 rows in gemm mode 1, the blocked 3-plane images otherwise
+static inline int train_planes() { return gemm_mode() == 1 ? 1 : 3; }
+// ... of the decode, beam and score drivers: a greedy decode must stay fp32-equivalent (bit-exact ids) - split precision in every plane mode
+static constexpr int DECODE_PLANES = 3;
 // plane modes need every k-offset inside a packed operand to be a multiple of 64 (k = time*B + b): B % 64 == 0
 static inline bool planes_ok(const s2vt_dims& d) { return gemm_mode() != 0 && d.B % 64 == 0; }
 // Recurrence schedule of the train drivers (option "persist"): 1 (default) = one persistent launch per block of timesteps with
@@ -189,6 +193,17 @@ int get_event(size_t i, hipEvent_t* out);
 int handoff(hipStream_t from, hipStream_t to, size_t ev_index);       // `to` waits for everything enqueued so far on `from`
 int lgemm(const Lane& ln, bool ak, bool bk, int M, int N, int K, const float* A, int64_t lda, RowMap am, const float* B, int64_t ldb,
           RowMap bm, float* C, int64_t ldc, RowMap cm, const float* bias, bool acc);
+// The frame of one call of a two-lane driver (api_shared.hip): the caller's stream st and the side stream sx (the same stream when
+// pipe_block is 0), a Lane on each (la: st, lb: sx) and the running index into the event pool.
+struct Lanes {
+    hipStream_t st = nullptr, sx = nullptr;
+    Lane la{}, lb{};
+    size_t ev = 0;
+    int open(hipStream_t caller, float* gws_a, float* gws_b, size_t gws_floats, float* colsum_a, float* colsum_b);
+    int hand(hipStream_t from, hipStream_t to) { return handoff(from, to, ev++); }      // `to` waits for everything enqueued on `from`
+    int record(hipStream_t s, long* idx);     // an event behind everything enqueued on s so far; *idx names it for wait()
+    int wait(hipStream_t s, long idx);
+};
 
 // ------------------------------------------------------------------ api_shared.hip
 // LSTM layer forward over steps [t0, t1) / BPTT over steps t1-1 .. t0 as launches per timestep (time-major buffers)
@@ -199,25 +214,38 @@ int seq_bwd(hipStream_t st, int T, int t0, int t1, int B, int H, const float* w_
 int balanced_block(int L, int blk);
 std::vector<int> pipe_bounds(int T, int L, int blk);
 
-extern int XP;            // planes per operand of the running plane driver (3 or 1); set by the entry points
-struct PB { unsigned short* p; int64_t ld; int kpad; };       // packed planes of a k-major operand [rows][k]
-// element offset of k index k0 (a multiple of 64) inside an operand: row layout (1 plane) k0; blocked 3-plane layout
-// (gemm_x3.hip) k0/16 records of 3072 elements
-static inline int64_t koff(int k0) { return XP == 3 ? (int64_t)k0 * 192 : (int64_t)k0 * XP; }
+// packed planes of a k-major operand [rows][k]: 1 plane = bf16 rows, 3 = the blocked 3-plane image (gemm_x3.hip); ld = planes * kpad.
+// PB{} (planes 0) is the operand a mode does not provide.
+struct PB { unsigned short* p = nullptr; int64_t ld = 0; int kpad = 0; int planes = 0; };
+// One k16 record of the blocked 3-plane layout - 16 k columns of a 64-row block: [3 planes][2 halves of 8 columns][64 rows] 16-byte slots
+static constexpr size_t K16_HALF_ELEMS = 64 * 8;                        // 512 elements = 1024 bytes
+static constexpr size_t K16_REC_ELEMS = 3 * 2 * K16_HALF_ELEMS;         // 3072 elements = 6144 bytes
+// element offset of k index k0 (a multiple of 64) inside an operand: row layout (1 plane) k0; blocked 3-plane layout k0/16 records
+static inline int64_t koff(const PB& b, int k0) { return b.planes == 3 ? (int64_t)k0 * 192 : (int64_t)k0 * b.planes; }
 static inline size_t rows64(size_t r) { return (r + 63) / 64 * 64; }
 // a packed operand of `planes` planes carved from c: rows rounded up to 64, k to a multiple of 64
 static inline PB take_planes(Carver& c, size_t rows, size_t k, int planes) {
     const int kpad = pad64((int)k);
-    return PB{c.take<unsigned short>(rows64(rows) * (size_t)planes * kpad), (int64_t)planes * kpad, kpad};
+    return PB{c.take<unsigned short>(rows64(rows) * (size_t)planes * kpad), (int64_t)planes * kpad, kpad, planes};
 }
+// zero the k16 records from cdiv(H, 16) to the end of the k padding in every 64-row block of the first `rows` rows of a blocked
+// 3-plane image (the kernel that writes the image's H valid columns itself leaves them alone); nothing where there are none
+int zero_k16_tail(hipStream_t st, const PB& img, int H, size_t rows);
+// The plane count of a call is its operands': psplit / pdual write dst's / r's and t's (which must agree), the GEMMs require A's == B's.
 int psplit(const Lane& ln, const PB& dst, int r0, const float* in, int64_t ld, RowMap imap, int rows, int cols);
 int pdual(const Lane& ln, const float* in, int64_t ld, RowMap imap, int rows, int cols, const PB* r, int r0, const PB* t, int k0,
           float* colpart);
+// pdual with no image to write, the 64-row partial column sums alone: the split kernel of `planes` planes (no operand names them)
+int pcolpart(const Lane& ln, int planes, const float* in, int64_t ld, RowMap imap, int rows, int cols, float* colpart);
 int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, const PB& B, int b0, int kb, float* C, int64_t ldc,
           RowMap cm, const float* bias, bool acc);
 int pgemm_tt(const Lane& ln, int M, int N, int K, const PB& A, int a_row0, const PB& B, int b_row0, float* C, int64_t ldc, RowMap cm,
              const float* bias, bool acc);
 int lcolsum_finish(const Lane& ln, const float* partial, int nchunks, int cols, float* out, bool accumulate);   // colsum_finish on ln.s
+// every driver's prologue: bsum1 = vid_rnn's b_ih + b_hh, bsum2 = word_rnn's (4H each)
+int bias_sums(hipStream_t st, const s2vt_params* p, int H, float* bsum1, float* bsum2);
+// fp32-MFMA feature projection on ln: x1 (time-major) = feats·W_f^T + b_f, gx1 = x1·W_ih1^T + bsum1          S2VTModel.py:54, 64-67
+int project_features_f32(const Lane& ln, const s2vt_dims& d, const s2vt_params* p, const float* feats, float* x1, float* gx1, const float* bsum1);
 // Test support (s2vt_test_lane_delay): inside a LaneDelayScope - the train backward drivers, `caller` = their own stream - every
 // launch of the Lane helpers above (and lgemm) on a selected lane (bit 0: the caller's stream, bit 1: the side lane) is preceded
 // on its stream by one occupy_kernel workgroup (no LDS) that spins for g_lane_delay_us.  Off (the default): no launch at all.

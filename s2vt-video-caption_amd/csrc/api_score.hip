@@ -26,8 +26,8 @@ struct ScoreEnc { float *bsum1, *bsum2, *x1, *gxb, *h1, *c1, *h2, *c2; size_t by
 static ScoreHead carve_score_head(const s2vt_dims& d, size_t rows, bool planes, void* base) {
     Carver c{reinterpret_cast<char*>(base), 0, 0};
     ScoreHead h;
-    h.himg = PB{nullptr, 0, 0}; h.hrows = nullptr;
-    if (planes) h.himg = take_planes(c, rows, d.H, 3);
+    h.hrows = nullptr;
+    if (planes) h.himg = take_planes(c, rows, d.H, DECODE_PLANES);
     else h.hrows = c.take<float>(rows * (size_t)d.H);
     h.logits = c.take<float>((size_t)S2VT_SCORE_HEAD_ROWS * d.V);
     h.bytes = align_up(c.off, 256);
@@ -97,17 +97,15 @@ static int encode_scratch(hipStream_t st, size_t bytes, void** out) {
 // feature projection, vid_rnn over the L frames and its S input-free decode steps, their half of word_rnn's gate input, word_rnn
 // over the L frames with a zero embedding.  Leaves what the word steps start from in w.states / w.gx_dec.
 static int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const float* feats, int S, const ScoreWS& w, hipStream_t st) {
-    const int B = d.B, L = d.L, F = d.F, H = d.H, E = d.E, Tv = L + S;
+    const int B = d.B, L = d.L, H = d.H, E = d.E, Tv = L + S;
     const int64_t BH = (int64_t)B * H;
     void* scratch = nullptr;
     if (int r = encode_scratch(st, carve_score_enc(d, S, nullptr).bytes, &scratch)) return r;
     const ScoreEnc e = carve_score_enc(d, S, scratch);
     const Lane ln{st, w.gws, w.gws_floats, nullptr};
     int rc;
-    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, e.bsum1, 4 * H))) return rc;
-    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, e.bsum2, 4 * H))) return rc;
-    if ((rc = lgemm(ln, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, e.x1, H, perm(L, B), p->feat_b, false))) return rc;
-    if ((rc = lgemm(ln, true, true, L * B, 4 * H, H, e.x1, H, ID, p->vid_w_ih, H, ID, e.gxb, 4 * H, ID, e.bsum1, false))) return rc;
+    if ((rc = bias_sums(st, p, H, e.bsum1, e.bsum2))) return rc;
+    if ((rc = project_features_f32(ln, d, p, feats, e.x1, e.gxb, e.bsum1))) return rc;
     if ((rc = seq_fwd(st, 0, Tv, B, H, e.gxb, L, e.bsum1, p->vid_w_hh, e.h1, e.c1, false))) return rc;
     if ((rc = lgemm(ln, true, true, Tv * B, 4 * H, H, e.h1, H, ID, p->word_w_ih + E, E + H, ID, e.gxb, 4 * H, ID, e.bsum2, false))) return rc;
     if ((rc = seq_fwd(st, 0, L, B, H, e.gxb, L, e.bsum2, p->word_w_hh, e.h2, e.c2, false))) return rc;
@@ -145,7 +143,6 @@ int s2vt_score_captions(const s2vt_dims* d, const s2vt_params* p, const float* f
         if ((rc = s2vt_decode_encode_cached(d, p, feats, scratch, sbytes, cache, cache_bytes, cache_valid, w.states, w.states + BH,
                                             w.states + 2 * BH, w.states + 3 * BH, w.gx_dec, S, stream)))
             return rc;
-        XP = 3;
     } else if ((rc = score_encode_per_step(*d, p, feats, S, w, st))) {
         return rc;
     }

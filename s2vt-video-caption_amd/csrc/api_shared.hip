@@ -1,5 +1,5 @@
 // Helpers the whole-path drivers and the per-op entry points share: the launch-per-timestep recurrence loops, pipeline block
-// boundaries, plane-operand wrappers (split kernels, plane GEMMs) and the argument builders of the persistent recurrence kernels.
+// boundaries, the lane frame, shared prologues, plane-operand wrappers (split kernels, plane GEMMs), the persistent kernels' argument builders.
 #include "api_internal.h"
 
 namespace s2vt {
@@ -73,7 +73,44 @@ std::vector<int> pipe_bounds(int T, int L, int blk) {
     return b;
 }
 
-int XP = 3;        // planes per operand of the running plane driver (3 or 1); set by the entry points
+// a side stream only when the two layers are pipelined (pipe_block > 0)
+int Lanes::open(hipStream_t caller, float* gws_a, float* gws_b, size_t gws_floats, float* colsum_a, float* colsum_b) {
+    st = sx = caller;
+    if (pipe_block() > 0)
+        if (const int rc = side_stream(caller, &sx)) return rc;
+    la = Lane{st, gws_a, gws_floats, colsum_a};
+    lb = Lane{sx, gws_b, gws_floats, colsum_b};
+    return 0;
+}
+int Lanes::record(hipStream_t s, long* idx) {
+    hipEvent_t e;
+    *idx = (long)ev++;
+    if (const int r = get_event((size_t)*idx, &e)) return r;
+    S2VT_HIP(hipEventRecord(e, s));
+    return 0;
+}
+int Lanes::wait(hipStream_t s, long idx) {
+    hipEvent_t e;
+    if (const int r = get_event((size_t)idx, &e)) return r;
+    S2VT_HIP(hipStreamWaitEvent(s, e, 0));
+    return 0;
+}
+
+int bias_sums(hipStream_t st, const s2vt_params* p, int H, float* bsum1, float* bsum2) {
+    if (const int rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, bsum1, 4 * H)) return rc;
+    return add_vectors(st, p->word_b_ih, p->word_b_hh, bsum2, 4 * H);
+}
+int project_features_f32(const Lane& ln, const s2vt_dims& d, const s2vt_params* p, const float* feats, float* x1, float* gx1, const float* bsum1) {
+    const int B = d.B, L = d.L, F = d.F, H = d.H;
+    if (const int rc = lgemm(ln, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, x1, H, perm(L, B), p->feat_b, false)) return rc;
+    return lgemm(ln, true, true, L * B, 4 * H, H, x1, H, ID, p->vid_w_ih, H, ID, gx1, 4 * H, ID, bsum1, false);
+}
+int zero_k16_tail(hipStream_t st, const PB& img, int H, size_t rows) {
+    const size_t kc0 = (size_t)cdiv(H, 16), kc1 = (size_t)(img.kpad / 16);
+    if (kc1 <= kc0) return 0;
+    S2VT_HIP(hipMemset2DAsync(img.p + kc0 * K16_REC_ELEMS, (size_t)64 * img.ld * 2, 0, (kc1 - kc0) * K16_REC_ELEMS * 2, rows / 64, st));
+    return 0;
+}
 
 int g_lane_delay_lanes = 0;
 long long g_lane_delay_us = 0;
@@ -90,25 +127,31 @@ int lane_delay(hipStream_t s) {
 // rows [r0, r0+rows) of the operand <- planes of in[rows][cols]
 int psplit(const Lane& ln, const PB& dst, int r0, const float* in, int64_t ld, RowMap imap, int rows, int cols) {
     if (int rc = lane_delay(ln.s)) return rc;
-    return split_planes(ln.s, XP, false, in, ld, imap, rows, cols, dst.p + (int64_t)r0 * dst.ld, dst.ld, dst.kpad, rows);
+    return split_planes(ln.s, dst.planes, false, in, ld, imap, rows, cols, dst.p + (int64_t)r0 * dst.ld, dst.ld, dst.kpad, rows);
 }
 // one pass over in[rows][cols]: row planes into r (operand rows r0..), transposed planes into t (k range k0..),
 // 64-row partial column sums into colpart (each may be null)
 int pdual(const Lane& ln, const float* in, int64_t ld, RowMap imap, int rows, int cols, const PB* r, int r0,
                  const PB* t, int k0, float* colpart) {
     if (!r && !t && !colpart) return 0;          // (bf16 mode with transposed-read GEMMs: the recurrence kernels wrote the rows already)
+    S2VT_REQUIRE(r || t, "pdual: column sums alone name no plane count (pcolpart)");
+    S2VT_REQUIRE(!r || !t || r->planes == t->planes, "pdual: row image of %d planes, transposed image of %d", r->planes, t->planes);
     if (int rc = lane_delay(ln.s)) return rc;
-    return split_planes_dual(ln.s, XP, in, ld, imap, rows, cols, r ? r->p + (int64_t)r0 * r->ld : nullptr, r ? r->ld : 0,
-                             r ? r->kpad : 0, t ? t->p + koff(k0) : nullptr, t ? t->ld : 0, t ? pad64(rows) : 0,
-                             colpart);
+    return split_planes_dual(ln.s, (r ? r : t)->planes, in, ld, imap, rows, cols, r ? r->p + (int64_t)r0 * r->ld : nullptr, r ? r->ld : 0,
+                             r ? r->kpad : 0, t ? t->p + koff(*t, k0) : nullptr, t ? t->ld : 0, t ? pad64(rows) : 0, colpart);
+}
+int pcolpart(const Lane& ln, int planes, const float* in, int64_t ld, RowMap imap, int rows, int cols, float* colpart) {
+    if (int rc = lane_delay(ln.s)) return rc;
+    return split_planes_dual(ln.s, planes, in, ld, imap, rows, cols, nullptr, 0, 0, nullptr, 0, 0, colpart);
 }
 // C[M,N] (+)= A[rows a0.., k ka..ka+K) · B[rows b0.., k kb..kb+K)^T
 int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, const PB& B, int b0, int kb, float* C,
                  int64_t ldc, RowMap cm, const float* bias, bool acc) {
+    S2VT_REQUIRE(A.planes == B.planes, "pgemm: A of %d planes, B of %d", A.planes, B.planes);
     if (int rc = lane_delay(ln.s)) return rc;
     ProfScope ps(ln.s, cu_plan_cap_current() ? K_GEMM_CORUN : K_GEMM, 1);
-    return gemm_bf16_nt(ln.s, XP, M, N, pad64(K), A.p + (int64_t)a0 * A.ld + koff(ka), A.ld,
-                        B.p + (int64_t)b0 * B.ld + koff(kb), B.ld, C, ldc, cm, bias, acc, ln.gws, ln.gws_floats);
+    return gemm_bf16_nt(ln.s, A.planes, M, N, pad64(K), A.p + (int64_t)a0 * A.ld + koff(A, ka), A.ld,
+                        B.p + (int64_t)b0 * B.ld + koff(B, kb), B.ld, C, ldc, cm, bias, acc, ln.gws, ln.gws_floats);
 }
 
 // The weight-gradient GEMMs (dW = dG^T h, dW_o = dlogits^T h2) read BOTH operands transposed from the row planes the forward / the
@@ -117,9 +160,10 @@ int pgemm(const Lane& ln, int M, int N, int K, const PB& A, int a0, int ka, cons
 // C[M,N] = A_img[a_row0 .., :M]^T . B_img[b_row0 .., :N] over K image rows (row offsets: multiples of 64)
 int pgemm_tt(const Lane& ln, int M, int N, int K, const PB& A, int a_row0, const PB& B, int b_row0, float* C, int64_t ldc,
                     RowMap cm, const float* bias, bool acc) {
+    S2VT_REQUIRE(A.planes == B.planes, "pgemm_tt: A of %d planes, B of %d", A.planes, B.planes);
     if (int rc = lane_delay(ln.s)) return rc;
     ProfScope ps(ln.s, cu_plan_cap_current() ? K_GEMM_CORUN : K_GEMM, 1);
-    if (XP == 1)
+    if (A.planes == 1)
         return gemm_b1_tt(ln.s, M, N, K, A.p + (int64_t)a_row0 * A.ld, A.ld, B.p + (int64_t)b_row0 * B.ld, B.ld, C, ldc, cm, bias, acc,
                           ln.gws, ln.gws_floats);
     return gemm_x3_tt(ln.s, M, N, K, A.p + (int64_t)a_row0 * A.ld, A.ld, B.p + (int64_t)b_row0 * B.ld, B.ld, C, ldc, cm, bias, acc,

@@ -118,18 +118,16 @@ struct PlaneWS {
     size_t bytes;
 };
 
-static PlaneWS carve_planes(const s2vt_dims& d, void* base) {
+static PlaneWS carve_planes(const s2vt_dims& d, int planes, void* base) {
     const size_t B = d.B, L = d.L, F = d.F, H = d.H, E = d.E, V = d.V, T = 2 * L - 1, R = (L - 1) * B;
     Carver c{reinterpret_cast<char*>(base), 0, 0};
-    auto mk = [&](size_t rows, size_t k) { return take_planes(c, rows, k, XP); };
+    auto mk = [&](size_t rows, size_t k) { return take_planes(c, rows, k, planes); };
     PlaneWS w;
     w.feats = mk(B * L, F);   w.wf = mk(H, F);       w.x1 = mk(L * B, H);    w.wih1 = mk(4 * H, H);
     w.h1 = mk(T * B, H);      w.we = mk(4 * H, E);   w.wv = mk(4 * H, H);    w.emb = mk(R, E);
     w.h2r = mk(T * B, H);     w.wo = mk(V, H);
-    if (XP == 1) {            // bf16 mode: recurrent weights as bf16 rows (forward) and transposed rows (BPTT)
+    if (planes == 1) {        // bf16 mode: recurrent weights as bf16 rows (forward) and transposed rows (BPTT); otherwise PB{}
         w.whh1 = mk(4 * H, H); w.whh2 = mk(4 * H, H); w.whh1T = mk(H, 4 * H); w.whh2T = mk(H, 4 * H);
-    } else {
-        w.whh1 = w.whh2 = w.whh1T = w.whh2T = PB{nullptr, 0, 0};
     }
     w.dlog = mk(R, V);        w.woT = mk(H, V);
     w.wvT = mk(H, 4 * H);     w.weT = mk(E, 4 * H);  w.wih1T = mk(H, 4 * H);
@@ -154,7 +152,7 @@ static void record_forward(const void* ws, const s2vt_dims& d, bool planes) {
             if (it->second.seq < oldest->second.seq) oldest = it;
         g_fwd_records.erase(oldest);
     }
-    g_fwd_records[ws] = FwdRecord{d, gemm_mode(), planes ? ((gemm_mode() == 1) ? 1 : 3) : 0, persist_bits(), pipe_block(), ++g_fwd_seq, false};
+    g_fwd_records[ws] = FwdRecord{d, gemm_mode(), planes ? train_planes() : 0, persist_bits(), pipe_block(), ++g_fwd_seq, false};
 }
 static int check_forward_record(const void* ws, const s2vt_dims& d, bool planes, bool* dlog_ready = nullptr) {
     FwdRecord r;
@@ -167,8 +165,7 @@ static int check_forward_record(const void* ws, const s2vt_dims& d, bool planes,
     }
     if (dlog_ready) *dlog_ready = r.dlog_ready;
     S2VT_REQUIRE(memcmp(&r.d, &d, sizeof(d)) == 0, "s2vt_train_backward: dims differ from the forward that filled this workspace");
-    const int planes_now = planes ? ((gemm_mode() == 1) ? 1 : 3) : 0;
-    S2VT_REQUIRE(r.gemm_mode == gemm_mode() && r.planes == planes_now && r.persist == persist_bits() && r.blk == pipe_block(),
+    S2VT_REQUIRE(r.gemm_mode == gemm_mode() && r.planes == (planes ? train_planes() : 0) && r.persist == persist_bits() && r.blk == pipe_block(),
                  "s2vt_train_backward: the forward ran with gemm mode %d / recurrence options %d / pipeline block %d, now %d / %d / %d: the "
                  "workspace layout differs (do not change gemm_mode / persist / persist_x3_fwd / persist_x3_bwd / pipe_block "
                  "between a forward and its backward)", r.gemm_mode, r.persist, r.blk, gemm_mode(), persist_bits(), pipe_block());
@@ -184,11 +181,6 @@ static void key_options(std::vector<uint64_t>& key) {
     key.push_back((uint64_t)g_lane_delay_us);
 }
 
-// One k16 record of the blocked 3-plane layout (gemm_x3.hip) - 16 k columns of a 64-row block: [3 planes][2 halves of 8 columns][64 rows]
-// 16-byte slots of 8 bf16 elements
-static constexpr size_t K16_HALF_ELEMS = 64 * 8;                        // 512 elements = 1024 bytes
-static constexpr size_t K16_REC_ELEMS = 3 * 2 * K16_HALF_ELEMS;         // 3072 elements = 6144 bytes
-
 // What a BPTT schedule reports to the shared tail of train_backward_x3
 struct BpttDone {
     int bias_chunk = 64;      // rows per partial column sum of dG (32: written by the persistent split-precision BPTT itself)
@@ -197,48 +189,24 @@ struct BpttDone {
     long demb_ev = -1;        // ... and behind the embedded-word gradient GEMM
 };
 
-// What every schedule of the plane drivers works with - dims, the parameter / gradient / workspace views, the two lanes (la: the caller's
-// stream st, lb: the side stream sx; the same stream when pipe_block is 0), the running event index, the pipeline's block bounds -
-// and the call shapes the schedules share.  Lives on the stack of one train_forward_x3 / train_backward_x3 call.
-struct TrainDriver {
+// What every schedule of the plane drivers works with - dims, the parameter / gradient / workspace views, the lane frame (Lanes), the
+// pipeline's block bounds - and the call shapes the schedules share.  Lives on the stack of one train_forward_x3 / train_backward_x3 call.
+struct TrainDriver : Lanes {
     const s2vt_params* p; const s2vt_grads* g; const TrainWS& w; const PlaneWS& q;
     const float* out_mask; float* logits;       // (logits: forward only)
     const int B, L, F, H, E, V, T, R, blk;
     const int64_t BH, B4H;
     const bool bf;                    // bf16 mode: the bf16 timestep kernels write the h / dG planes themselves
     const bool emit;                  // the persistent x3 BPTT hands dG over as the GEMMs' row-plane image itself (see x3_bptt_begin)
-    hipStream_t st, sx;
-    Lane la, lb;
-    size_t ev = 0;
     std::vector<int> bd;
-    TrainDriver(const s2vt_dims* d, const s2vt_params* p_, const s2vt_grads* g_, const TrainWS& w_, const PlaneWS& q_, hipStream_t st_,
+    TrainDriver(const s2vt_dims* d, const s2vt_params* p_, const s2vt_grads* g_, const TrainWS& w_, const PlaneWS& q_,
                 const float* out_mask_, float* logits_)
         : p(p_), g(g_), w(w_), q(q_), out_mask(out_mask_), logits(logits_), B(d->B), L(d->L), F(d->F), H(d->H), E(d->E), V(d->V),
-          T(2 * d->L - 1), R((d->L - 1) * d->B), blk(pipe_block()), BH((int64_t)d->B * d->H), B4H(4 * (int64_t)d->B * d->H), bf(XP == 1),
-          emit(d->H % 8 == 0), st(st_), sx(st_) {}
-    int open_lanes() {
-        int rc;
-        if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-        la = Lane{st, w.gws_a, w.gws_floats, w.colsum_a};
-        lb = Lane{sx, w.gws_b, w.gws_floats, w.colsum_b};
-        return 0;
-    }
+          T(2 * d->L - 1), R((d->L - 1) * d->B), blk(pipe_block()), BH((int64_t)d->B * d->H), B4H(4 * (int64_t)d->B * d->H),
+          bf(q_.h1.planes == 1), emit(d->H % 8 == 0) {}
+    int open_lanes(hipStream_t caller) { return open(caller, w.gws_a, w.gws_b, w.gws_floats, w.colsum_a, w.colsum_b); }
     void set_bounds(bool persistent) { bd = pipe_bounds(T, L, persistent ? balanced_block(L, blk) : blk); }
 
-    int hand(hipStream_t from, hipStream_t to) { return handoff(from, to, ev++); }      // `to` waits for everything enqueued on `from`
-    int record(hipStream_t s, long* idx) {      // an event behind everything enqueued on s so far; *idx names it for wait()
-        hipEvent_t e;
-        *idx = (long)ev++;
-        if (const int r = get_event((size_t)*idx, &e)) return r;
-        S2VT_HIP(hipEventRecord(e, s));
-        return 0;
-    }
-    int wait(hipStream_t s, long idx) {
-        hipEvent_t e;
-        if (const int r = get_event((size_t)idx, &e)) return r;
-        S2VT_HIP(hipStreamWaitEvent(s, e, 0));
-        return 0;
-    }
     // zero `elems` elements from element `first` on of every 64-row block of a blocked 3-plane image, on the caller's stream
     int zero_k16(const PB& img, size_t first, size_t elems) {
         S2VT_HIP(hipMemset2DAsync(img.p + first, (size_t)64 * img.ld * 2, 0, elems * 2, (size_t)(T * B / 64), st));
@@ -275,8 +243,11 @@ struct TrainDriver {
     // dG of the steps [t0, t1) of a layer: row planes (dh1, d-embedding and - read transposed - weight-gradient GEMMs; want_planes = false:
     // the BPTT kernel wrote them) and the bias-gradient partial sums over 64 rows, all from one read
     int split_dg_block(const Lane& ln, int layer, int t0, int t1, bool want_planes) {
-        return pdual(ln, (layer == 2 ? w.s2 : w.s1) + t0 * B4H, 4 * H, ID, (t1 - t0) * B, 4 * H, want_planes ? (layer == 2 ? &q.dg2 : &q.dg1) : nullptr,
-                     t0 * B, nullptr, t0 * B, (layer == 2 ? w.colsum_a : w.colsum_b) + (int64_t)(t0 * B / 64) * 4 * H);
+        const PB& dg = layer == 2 ? q.dg2 : q.dg1;
+        const float* in = (layer == 2 ? w.s2 : w.s1) + t0 * B4H;
+        float* colpart = (layer == 2 ? w.colsum_a : w.colsum_b) + (int64_t)(t0 * B / 64) * 4 * H;
+        return want_planes ? pdual(ln, in, 4 * H, ID, (t1 - t0) * B, 4 * H, &dg, t0 * B, nullptr, t0 * B, colpart)
+                           : pcolpart(ln, dg.planes, in, 4 * H, ID, (t1 - t0) * B, 4 * H, colpart);
     }
     // gradient into vid_out for the steps [t0, t1): dh1 = dG2 . W_v
     int dh1_gemm(const Lane& ln, int t0, int t1) {
@@ -320,10 +291,8 @@ int TrainDriver::fwd_x3_persistent(int f_cus, int tenths, int gxe_c) {
     const int nb = (int)bd.size() - 1;
     // the kernel writes h_t into the GEMMs' row images itself (the hand-off payload's own 16-byte pieces); the k16 records past
     // the last column slice are zeroed here (H = 1000: units 1008..1023)
-    for (const PB* img : {&q.h1, &q.h2r}) {
-        const size_t kc0 = (size_t)cdiv(H, 16), kc1 = (size_t)(img->kpad / 16);
-        if (kc1 > kc0 && (rc = zero_k16(*img, kc0 * K16_REC_ELEMS, (kc1 - kc0) * K16_REC_ELEMS))) return rc;
-    }
+    for (const PB* img : {&q.h1, &q.h2r})
+        if ((rc = zero_k16_tail(st, *img, H, (size_t)T * B))) return rc;
     // decode steps whose logits run beside the last (word_rnn-only) stage: their h2 rows are final before it starts
     int lg_c = (nb >= 2 && !out_mask) ? (L - 1) * ((2 * tenths + 1) / 3) / 10 : 0;
     if (lg_c > bd[nb - 1] - L) lg_c = bd[nb - 1] - L > 0 ? bd[nb - 1] - L : 0;
@@ -405,16 +374,15 @@ int TrainDriver::fwd_two_lanes() {
 static int train_forward_x3(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
                             int64_t targets_ld, float* logits, const TrainWS& w, const PlaneWS& q, hipStream_t st,
                             const float* out_mask) {
-    TrainDriver x(d, p, nullptr, w, q, st, out_mask, logits);
+    TrainDriver x(d, p, nullptr, w, q, out_mask, logits);
     const int B = x.B, L = x.L, F = x.F, H = x.H, E = x.E, V = x.V, T = x.T, R = x.R;
     const int64_t B4H = x.B4H;
     int rc;
-    if ((rc = x.open_lanes())) return rc;
+    if ((rc = x.open_lanes(st))) return rc;
     const hipStream_t sx = x.sx;
     const Lane &la = x.la, &lb = x.lb;
     const bool bf = x.bf;
-    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
-    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
+    if ((rc = bias_sums(st, p, H, w.bsum1, w.bsum2))) return rc;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
     if (bf) {   // zero the k padding of the bf16 h row images (valid columns are written by the step kernels)
@@ -472,10 +440,9 @@ int TrainDriver::x3_bptt_begin() {
     // is in LDS as planes anyway - no split pass reads dG back, the fp32 dG is never stored.  (H % 8: a 16-byte slot of the image
     // holds 8 consecutive units of one gate.)  The k padding [4H, pad64(4H)) of both images is zeroed here once per backward.
     if (emit && q.dg2.kpad > 4 * H) {
-        const size_t kc0 = (size_t)(4 * H / 16), kc1 = (size_t)(q.dg2.kpad / 16);       // k16 records [kc0, kc1) of every 64-row block
-        const size_t first = (4 * H % 16) ? kc0 + 1 : kc0;                              // (4H % 16 == 8: the straddling record's upper half
-        for (const PB* img : {&q.dg2, &q.dg1}) {                                        //  is zeroed piece by piece below)
-            if (kc1 > first && (rc = zero_k16(*img, first * K16_REC_ELEMS, (kc1 - first) * K16_REC_ELEMS))) return rc;
+        const size_t kc0 = (size_t)(4 * H / 16);                                        // (4H % 16 == 8: the upper half of the record that
+        for (const PB* img : {&q.dg2, &q.dg1}) {                                        //  straddles 4H is zeroed piece by piece below)
+            if ((rc = zero_k16_tail(st, *img, 4 * H, (size_t)T * B))) return rc;
             if (4 * H % 16)
                 for (int pl = 0; pl < 3; ++pl)
                     if ((rc = zero_k16(*img, kc0 * K16_REC_ELEMS + (pl * 2 + 1) * K16_HALF_ELEMS, K16_HALF_ELEMS))) return rc;
@@ -656,11 +623,11 @@ int TrainDriver::bptt_two_lanes() {
 static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                              const s2vt_grads* g, float* dfeats, const TrainWS& w, const PlaneWS& q, hipStream_t st,
                              const float* out_mask, bool dlog_ready) {
-    TrainDriver x(d, p, g, w, q, st, out_mask, nullptr);
+    TrainDriver x(d, p, g, w, q, out_mask, nullptr);
     const int B = x.B, L = x.L, F = x.F, H = x.H, E = x.E, V = x.V, T = x.T, R = x.R;
     const int64_t BH = x.BH;
     int rc;
-    if ((rc = x.open_lanes())) return rc;
+    if ((rc = x.open_lanes(st))) return rc;
     const hipStream_t sx = x.sx;
     const Lane &la = x.la, &lb = x.lb;        // la: word_rnn lane, lb: vid_rnn lane
     const bool bf = x.bf;
@@ -754,30 +721,25 @@ static int train_forward_f32(const s2vt_dims* d, const s2vt_params* p, const flo
                              int64_t targets_ld, float* logits, const TrainWS& w, hipStream_t st, const float* out_mask) {
     const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1;
     const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
+    Lanes x;
     int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // vid_rnn lane (caller's stream)
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // word_rnn lane
-    size_t ev = 0;
-    if ((rc = add_vectors(st, p->vid_b_ih, p->vid_b_hh, w.bsum1, 4 * H))) return rc;
-    if ((rc = add_vectors(st, p->word_b_ih, p->word_b_hh, w.bsum2, 4 * H))) return rc;
+    if ((rc = x.open(st, w.gws_a, w.gws_b, w.gws_floats, w.colsum_a, w.colsum_b))) return rc;
+    const hipStream_t sx = x.sx;
+    const Lane &la = x.la, &lb = x.lb;        // la: vid_rnn lane (caller's stream), lb: word_rnn lane
+    if ((rc = bias_sums(st, p, H, w.bsum1, w.bsum2))) return rc;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
-    if ((rc = handoff(st, sx, ev++))) return rc;
+    if ((rc = x.hand(st, sx))) return rc;
     // lane B, independent of vid_rnn: embedded-word half of the word_rnn gate input (+ both biases) for the
     // L-1 caption steps                                                             S2VTModel.py:71-75
     if ((rc = lgemm(lb, true, true, (L - 1) * B, 4 * H, E, p->emb_w, E, gather(w.tok), p->word_w_ih, E + H, ID,
                     w.s2 + (int64_t)L * B4H, 4 * H, ID, w.bsum2, false))) return rc;
-    // lane A: x1 (time-major) = feats·W_f^T + b_f ; gx1 = x1·W_ih1^T + biases       S2VTModel.py:54, 64-67
-    if ((rc = lgemm(la, true, true, B * L, H, F, feats, F, ID, p->feat_w, F, ID, w.x1, H, perm(L, B), p->feat_b, false))) return rc;
-    if ((rc = lgemm(la, true, true, L * B, 4 * H, H, w.x1, H, ID, p->vid_w_ih, H, ID, w.s1, 4 * H, ID, w.bsum1, false))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, blk);
+    if ((rc = project_features_f32(la, *d, p, feats, w.x1, w.s1, w.bsum1))) return rc;
+    const std::vector<int> bd = pipe_bounds(T, L, pipe_block());
     for (size_t k = 0; k + 1 < bd.size(); ++k) {
         const int t0 = bd[k], t1 = bd[k + 1];
         if ((rc = seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true))) return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;
+        if ((rc = x.hand(st, sx))) return rc;
         // vid_out half of the word_rnn gate input for this block: rows < L get the biases here, rows >= L
         // accumulate onto the embedded-word half                                    S2VTModel.py:75-77
         const bool cap = t0 >= L;
@@ -792,22 +754,20 @@ static int train_forward_f32(const s2vt_dims* d, const s2vt_params* p, const flo
         hdec = w.dh2dec;
     }
     if ((rc = lgemm(lb, true, true, (L - 1) * B, V, H, hdec, H, ID, p->out_w, H, ID, logits, V, perm(B, L - 1), p->out_b, false))) return rc;
-    return handoff(sx, st, ev++);
+    return x.hand(sx, st);
 }
 
 static int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                               const s2vt_grads* g, float* dfeats, const TrainWS& w, hipStream_t st, const float* out_mask) {
     const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1, R = (L - 1) * B;
     const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    const int blk = pipe_block();
-    hipStream_t sx = st;
+    Lanes x;
     int rc;
-    if (blk > 0 && (rc = side_stream(st, &sx))) return rc;
-    const Lane la{st, w.gws_a, w.gws_floats, w.colsum_a};     // word_rnn lane (caller's stream)
-    const Lane lb{sx, w.gws_b, w.gws_floats, w.colsum_b};     // vid_rnn lane
+    if ((rc = x.open(st, w.gws_a, w.gws_b, w.gws_floats, w.colsum_a, w.colsum_b))) return rc;
+    const hipStream_t sx = x.sx;
+    const Lane &la = x.la, &lb = x.lb;        // la: word_rnn lane (caller's stream), lb: vid_rnn lane
     LaneDelayScope delay(st);
-    size_t ev = 0;
-    if ((rc = handoff(st, sx, ev++))) return rc;
+    if ((rc = x.hand(st, sx))) return rc;
     // lane A: gradient into the decode-step hidden states, then word_rnn BPTT       (autograd of S2VTModel.py:80, :77)
     if ((rc = lgemm(la, true, false, R, H, V, dlogits, V, ID, p->out_w, H, ID, w.dh2dec, H, perm(L - 1, B), nullptr, false))) return rc;
     if (out_mask && (rc = mul_vectors(st, w.dh2dec, out_mask, w.dh2dec, (int64_t)R * H))) return rc;      // autograd of out_drop
@@ -822,14 +782,14 @@ static int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const fl
     if ((rc = colsum_f32(sx, dlogits, R, V, V, lb.colsum, g->out_b, false))) return rc;
     if ((rc = grads_ready(0, sx))) return rc;
     if ((rc = transpose_f32(sx, p->vid_w_hh, 4 * H, H, w.wt1))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, blk);
+    const std::vector<int> bd = pipe_bounds(T, L, pipe_block());
     for (size_t k = bd.size() - 1; k >= 1; --k) {
         const int t0 = bd[k - 1], t1 = bd[k];
         if ((rc = seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2))) return rc;
         // gradient into vid_out for this block: dh1 = dG2·W_v                        (autograd of :75)
         if ((rc = lgemm(la, true, false, (t1 - t0) * B, H, 4 * H, w.s2 + t0 * B4H, 4 * H, ID, p->word_w_ih + E, E + H, ID,
                         w.dh1 + t0 * BH, H, ID, nullptr, false))) return rc;
-        if ((rc = handoff(st, sx, ev++))) return rc;
+        if ((rc = x.hand(st, sx))) return rc;
         if ((rc = seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1))) return rc;   // (autograd of :67)
     }
     // lane A: word_rnn parameter gradients + embedding gradient (run while lane B finishes the vid_rnn BPTT)
@@ -853,7 +813,7 @@ static int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const fl
     if ((rc = lgemm(lb, false, false, H, F, L * B, w.dx1, H, ID, feats, F, perm(B, L), g->feat_w, F, ID, nullptr, false))) return rc;
     if ((rc = colsum_f32(sx, w.dx1, (int64_t)L * B, H, H, lb.colsum, g->feat_b, false))) return rc;
     if (dfeats && (rc = lgemm(lb, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, perm(B, L), nullptr, false))) return rc;
-    return handoff(sx, st, ev++);
+    return x.hand(sx, st);
 }
 
 }  // namespace s2vt
@@ -885,12 +845,7 @@ static PadWS carve_pad(const s2vt_dims& d, const s2vt_dims& dp, void* base) {
 }
 static size_t train_core_bytes(const s2vt_dims& d) {
     size_t n = carve_train(d, nullptr).bytes;
-    if (planes_ok(d)) {
-        const int keep = XP;                       // a size query must not change the state of a running path
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        n += carve_planes(d, nullptr).bytes;
-        XP = keep;
-    }
+    if (planes_ok(d)) n += carve_planes(d, train_planes(), nullptr).bytes;
     return n;
 }
 
@@ -937,8 +892,7 @@ static int train_forward_core(const s2vt_dims* d, const s2vt_params* p, const fl
     if (rc0) return rc0;
     record_forward(workspace, *d, planes_ok(*d));
     if (planes_ok(*d)) {
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
+        const PlaneWS q = carve_planes(*d, train_planes(), reinterpret_cast<char*>(workspace) + w.bytes);
         S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_forward: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
         const std::vector<uint64_t> key = graph_key(0xF0, d, p, nullptr, {kw(feats), kw(targets), (uint64_t)targets_ld, kw(logits), kw(workspace),
                                                                            kw(out_mask), kw(st)});
@@ -1003,8 +957,7 @@ static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const f
     if (rc0 || (rc0 = check_forward_record(workspace, *d, planes_ok(*d), &dlog_ready))) return rc0;
     S2VT_REQUIRE(dlogits || dlog_ready, "s2vt_train_backward: dlogits is null and s2vt_mean_ce_backward_fused has not run on this workspace");
     if (planes_ok(*d)) {
-        XP = (gemm_mode() == 1) ? 1 : 3;
-        const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
+        const PlaneWS q = carve_planes(*d, train_planes(), reinterpret_cast<char*>(workspace) + w.bytes);
         S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_train_backward: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
         const std::vector<uint64_t> key = graph_key(0xB0 + (dlog_ready ? 1 : 0), d, p, g, {kw(feats), kw(dlogits), kw(dfeats), kw(workspace),
                                                                                             kw(out_mask), kw(st)});
@@ -1082,18 +1035,17 @@ int s2vt_mean_ce_backward_fused(const s2vt_dims* d, const float* logits, const i
                          !it->second.dlog_ready,
                      "s2vt_mean_ce_backward_fused: no matching s2vt_train_forward has run on this workspace");
     }
-    XP = (gemm_mode() == 1) ? 1 : 3;
-    const PlaneWS q = carve_planes(*d, reinterpret_cast<char*>(workspace) + w.bytes);
+    const PlaneWS q = carve_planes(*d, train_planes(), reinterpret_cast<char*>(workspace) + w.bytes);
     S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_mean_ce_backward_fused: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
     const int R = (d->L - 1) * d->B, V = d->V;
     CeGradArgs ce;
     ce.lse = lse; ce.target = target; ce.gout = gout; ce.Lm1 = d->L - 1; ce.ldt = target_ld;
-    ce.alpha_out = (XP == 1) ? w.ce_alpha : nullptr;       // bf16 operands: power-of-two scale in the planes, mantissa downstream
+    ce.alpha_out = (q.dlog.planes == 1) ? w.ce_alpha : nullptr;      // bf16 operands: power-of-two scale in the planes, mantissa downstream
     hipStream_t st = (hipStream_t)stream;
     int rc;
     {
         ProfScope ps(st, K_CE, 1);
-        if ((rc = split_planes_dual(st, XP, logits, V, ID, R, V, q.dlog.p, q.dlog.ld, q.dlog.kpad, nullptr, 0, 0, w.colsum_c, &ce))) return rc;
+        if ((rc = split_planes_dual(st, q.dlog.planes, logits, V, ID, R, V, q.dlog.p, q.dlog.ld, q.dlog.kpad, nullptr, 0, 0, w.colsum_c, &ce))) return rc;
     }
     std::lock_guard<std::mutex> lock(g_fwd_mutex);
     g_fwd_records[workspace].dlog_ready = true;

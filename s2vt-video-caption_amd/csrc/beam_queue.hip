@@ -291,18 +291,10 @@ int s2vt_beam_queue_step(int32_t B, int32_t beam_width, int32_t max_depth, int32
     hipStream_t st = (hipStream_t)stream;
     if (depth == 1) {
         // score divisor len ** 0.7 exactly as the reference evaluates it: Python float pow (libm double), then fp32 (:262-266)
-        // The table lives in pinned host memory for the life of the process (it depends on nothing but the length), so the copy
-        // is asynchronous: no host synchronisation at the start of a search, and the call can be stream-captured.
-        static float* tab = nullptr;
-        static int tab_len = 0;
-        if (tab_len < max_depth + 4) {
-            float* grown = nullptr;
-            const int len = (max_depth + 4 + 1023) / 1024 * 1024;
-            S2VT_HIP(hipHostMalloc(reinterpret_cast<void**>(&grown), (size_t)len * sizeof(float), hipHostMallocDefault));
-            for (int l = 0; l < len; ++l) grown[l] = l > 0 ? (float)pow((double)l, 0.7) : 1.0f;
-            tab = grown;            // (an older, shorter table stays allocated: copies from it may still be in flight)
-            tab_len = len;
-        }
+        // The table (length_pow_table, beam_cum.hip: entries 0 .. max_depth + 3) lives in pinned host memory for the life of the
+        // process, so the copy is asynchronous: no host synchronisation at the start of a search, and the call can be stream-captured.
+        const float* tab = length_pow_table(0.7, max_depth + 3);
+        S2VT_REQUIRE(tab, "s2vt_beam_queue_step: no pinned memory for the length table");
         S2VT_HIP(hipMemcpyAsync(const_cast<float*>(q.pow07), tab, (size_t)(max_depth + 4) * sizeof(float), hipMemcpyHostToDevice, st));
         S2VT_HIP(hipMemsetAsync(q.done_count, 0, sizeof(int), st));
     }

@@ -1208,6 +1208,66 @@ def test_graph_replay_is_bitwise_the_eager_sequence(lib, cfg, gemm_mode):
         lib.s2vt_set_gemm_mode(prev)
 
 
+@pytest.mark.parametrize("gemm_mode", [1, 3])
+def test_plane_mode_is_per_call_not_process_state(lib, gemm_mode):
+    """How many planes an operand has (bf16 rows in gemm mode 1, three planes in mode 3; three for every decode / score call) belongs
+    to the call that carved it, not to the process: two Adam steps at mid64 - the smallest named shape on the plane drivers - give
+    the same losses and the same 13 gradients bit for bit when size queries run between each forward and its backward, and a
+    decode and a scoring call of another model instance (3-plane operands in either mode) between the two steps; and those
+    interleaved ids and scores are the ones the same calls give alone."""
+    import utils
+    from s2vt_video_caption_amd import capi
+    d = synth.CONFIGS["mid64"]
+    sd = synth.make_state_dict(d["V"], d["F"], d["H"], d["E"], seed=41)
+    feats, caps, mask = (t.to(DEV) for t in synth.make_batch(d["B"], d["L"], d["F"], d["V"], seed=42))
+    dims = capi.Dims(d["B"], d["L"], d["F"], d["H"], d["E"], d["V"])
+    crit = utils.MaskCriterion()
+    prev = lib.s2vt_set_gemm_mode(gemm_mode)
+    try:
+        def infer(m):
+            with torch.no_grad():
+                ids = m.eval()(feats, mode="test")
+                scores, lengths, token_lp = m(feats, targets=caps, mode="score")
+            return ids, scores, lengths, token_lp
+
+        def size_queries():
+            sizes = (lib.s2vt_decode_workspace_bytes(dims), lib.s2vt_decode_cache_bytes(dims), lib.s2vt_train_workspace_bytes(dims))
+            assert all(s > 0 for s in sizes), sizes
+
+        def run(between_forward_and_backward, between_steps):
+            m = _model(d, sd)
+            opt = torch.optim.Adam(m.parameters(), lr=1e-3)
+            out = []
+            for step in range(2):
+                opt.zero_grad()
+                logits = m(feats, targets=caps[:, :-1], mode="train")
+                loss = crit(logits, caps, mask)
+                between_forward_and_backward()
+                loss.backward()
+                out.append((float(loss), {n: p.grad.clone() for n, p in m.named_parameters()}))
+                opt.step()
+                if step == 0:
+                    between_steps()
+            capi.check_async_error()
+            return out
+
+        alone = infer(_model(d, sd))
+        ref = run(lambda: None, lambda: None)
+        interleaved = []
+        other = _model(d, sd)
+        got = run(size_queries, lambda: interleaved.append(infer(other)))
+        assert len(ref) == len(got) == 2 and len(interleaved) == 1
+        for (l0, g0), (l1, g1) in zip(ref, got):
+            assert l0 == l1
+            assert len(g0) == len(g1) == 13
+            for n in g0:
+                assert torch.equal(g0[n], g1[n]), n
+        for a, b in zip(alone, interleaved[0]):
+            assert torch.equal(a, b)
+    finally:
+        lib.s2vt_set_gemm_mode(prev)
+
+
 def test_decode_cache_follows_the_weights(lib, golden):
     """The weight-image cache of mode='test' (s2vt_greedy_decode_cached; functional._DECODE_CACHES): a second call on unchanged
     weights reuses the images and must give the ids of the first (= the reference's, c2 fixture); after the weights change - an
