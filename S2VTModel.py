@@ -142,6 +142,32 @@ class S2VT(nn.Module):
             return _F.greedy_decode(feats, params, self.sos_ix, owner=self, sample=sample)
         return None                                        # the reference falls through for unknown modes
 
+    @torch.no_grad()
+    def sample(self, feats, n_samples=1, temperature=1.0, seed=None):
+        """ids int64 [B, n_samples, L-1] on the device: K = n_samples captions per clip drawn as mode='sample' draws them (never
+        stopping at <eos>), for sequence-level training with K samples per clip (not in the reference).  Row b*K + k draws with
+        the noise of (seed, decode step, batch row b*K + k, v), so `sample(feats, K, t, s).view(B*K, -1)` is the draw of
+        `forward(feats.repeat_interleave(K, 0), mode='sample', temperature=t, seed=s)` - the two can differ only where two scores
+        are closer than the paths' logit rounding - and K = 1 is mode='sample' with a middle axis of 1.  The one-layer LSTM
+        encodes every clip ONCE and runs only the word steps over the B*K rows (sampling.sample_rows); a GRU or stacked model
+        gives the same ids by decoding the repeated clips, without the shared encode.  feat_drop is applied once per clip, as
+        forward applies it; temperature / seed as for mode='sample'.  No gradient.
+        :param feats: [B, L, feat_dim]
+        :param n_samples: an integer >= 1
+        """
+        K = _sampling.check_n_samples(n_samples)
+        t, s = _sampling.check_sample_args(temperature, seed)
+        _F.require_hip(feats, "feats")
+        if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
+            raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        B = feats.shape[0]
+        if _G.is_gru_model(self) or _S.is_stacked_lstm_model(self):
+            decode = _G.greedy_decode if _G.is_gru_model(self) else _S.greedy_decode
+            rows = self.feat_drop(feats).repeat_interleave(K, 0)
+            return decode(self, rows, self.sos_ix, sample=(t, s)).view(B, K, -1)
+        params = self._hip_params()
+        return _sampling.sample_rows(self, self.feat_drop(feats), params, K, t, s)
+
     def _forward_gru(self, feats, targets, mode, sample=None, ss=(0.0, None, None)):
         """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""
         if mode == 'beam_search':

@@ -337,6 +337,18 @@ int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, 
  * fp64 difference rounded once - on positions 1 .. the first eos of the row inclusive (all T without one), zero elsewhere. */
 int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t T, int32_t sos,
                     int32_t eos, int64_t* caps, float* weight, void* stream);
+/* The same for K sampled captions per clip, rows r = b*K + k (sampled int64 [B*K, T], r_sample fp64 [B*K]); one wavefront per clip.
+ *   r_greedy == NULL: baseline[b*K + k] = ((sum over j = 0 .. K-1, ascending, from 0.0, of r_sample[b*K + j]) - r_sample[b*K + k])
+ *                     / (K - 1) in fp64 - the mean reward of the clip's OTHER samples (Luo 2020).  Needs K >= 2 (S2VT_ERR_ARG).
+ *   r_greedy != NULL: baseline[b*K + k] = r_greedy[b] (fp64 [B]); K = 1 is then s2vt_sc_weights.
+ * caps int64 [B*K, T+1] = sos || sampled; weight fp32 [B*K, T+1] = fp32(r_sample[r] - baseline[r]), the fp64 difference rounded
+ * once, on positions 1 .. the first eos inclusive (all T without one), zero elsewhere; baseline fp64 [B*K] or NULL.  Adds, one
+ * subtract, one divide in the stated order: self_critical.group_advantages restates it in numpy bit for bit.  A clip whose K
+ * rewards are all equal (r_greedy == NULL) gets weight 0 on every row: its baseline is that reward itself, by comparison - the
+ * rounded K-term sum alone would leave a difference of rounding size (at K = 3 for about half of all values), a weight that is
+ * not zero.  s2vt_weighted_ce_forward's normaliser counts the tokens that carry a weight, so that clip's tokens are not counted. */
+int s2vt_sc_weights_group(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t K, int32_t T,
+                          int32_t sos, int32_t eos, int64_t* caps, float* weight, double* baseline, void* stream);
 
 /* The same gradient handed to s2vt_train_backward WITHOUT an fp32 dlogits tensor (utils.py:22 under loss.backward(), train.py:124):
  * evaluates (softmax(logits) - onehot(target)) * gout[0] / (B*(L-1)) inside the plane-split pass of the TRAIN workspace the
@@ -734,6 +746,22 @@ int s2vt_sample_decode(const s2vt_dims* d, const s2vt_params* p, const float* fe
 int s2vt_sample_decode_cached(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t sos_ix, float temperature,
                               uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                               int32_t cache_valid, void* stream);
+/* K draws per clip on ONE encode (S2VT.sample; csrc/api_sample_rows.hip): ids int64 [B*K, L-1], row r = b*K + k.
+ * THE NOISE CONTRACT: row b*K + k draws with the noise of (seed, decode step, batch row = b*K + k, v) above - same stream tag, same
+ * mapping as s2vt_sample_decode.  The call therefore makes the draw that s2vt_sample_decode makes on the clips repeated K times
+ * (clip b at rows b*K .. b*K + K-1), up to the paths' logit rounding where two scores are that close; K = 1 is s2vt_sample_decode.
+ * Feature projection and both layers over the L frames run once per clip; the L-1 word steps run over the B*K rows, each reading
+ * its clip's gate input and the word it drew at the step before on the device.  cache == NULL: fp32-input MFMA path throughout.
+ * cache != NULL (s2vt_decode_cache_bytes; the protocol of s2vt_greedy_decode_cached): the persistent split-precision encode of
+ * s2vt_decode_encode_cached and the plane-path step and head; shapes that encode does not take are refused (S2VT_ERR_ARG) before
+ * anything is enqueued.  The encode's scratch is kept by the library per (device, stream), as for s2vt_score_captions.  One chain on
+ * the caller's stream, no host round trip.  temperature as above, K >= 1, sos_ix in [0, V), workspace_bytes >=
+ * s2vt_sample_rows_workspace_bytes: checked on the host before anything is enqueued (S2VT_ERR_ARG).
+ * s2vt_sample_rows_workspace_bytes: 0 where the shape cannot be served (K < 1, or (L-1) * rows64(B*K) >= 2^31 packed words). */
+size_t s2vt_sample_rows_workspace_bytes(const s2vt_dims* d, int32_t K);
+int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, float temperature,
+                            uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                            int32_t cache_valid, void* stream);
 
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the

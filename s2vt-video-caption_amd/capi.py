@@ -190,6 +190,9 @@ SIGNATURES = {
                                      c_size_t, c_void_p]),
     "s2vt_sample_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_float, c_uint64, c_void_p, c_void_p,
                                             c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_sample_rows_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
+    "s2vt_sample_decode_rows": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_int32, c_float, c_uint64, c_void_p,
+                                          c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
     "s2vt_scheduled_decode": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float, c_uint64,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_scheduled_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float,
@@ -206,6 +209,8 @@ SIGNATURES = {
     "s2vt_cider_rewards": (c_int32, [POINTER(CiderTable), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
                                      c_void_p]),
     "s2vt_sc_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "s2vt_sc_weights_group": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
     "s2vt_mean_ce_backward_fused": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
     "s2vt_set_option": (c_int32, [c_char_p, c_int32]),

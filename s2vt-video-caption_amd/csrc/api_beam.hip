@@ -12,7 +12,8 @@ int rows_word_step(hipStream_t st, const s2vt_dims& d, const s2vt_params* p, con
     StepFwdArgs a = {};
     a.B = r.R; a.H = H;
     a.h_prev = r.h_prev; a.ldh = H; a.w_hh = p->word_w_hh; a.ldw = H;
-    a.tok.tok_idx = r.tok; a.tok.tok_limit = d.V; a.tok.tok_err = r.err;
+    a.tok.tok_idx = r.tok; a.tok.tok_packed = r.tok_packed; a.tok.tok_const = r.tok_const;
+    a.tok.tok_limit = d.V; a.tok.tok_err = r.err;
     a.gx = r.gx; a.ldgx = 4 * (int64_t)H; a.gx_idx = r.gx_idx;
     a.c_prev = r.c_prev; a.ldc = H;
     a.h_out = r.h_out; a.ldho = H; a.c_out = r.c_out; a.ldco = H;

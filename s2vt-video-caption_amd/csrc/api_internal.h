@@ -6,6 +6,7 @@
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
 //   api_score.hip    teacher-forced caption scoring (S2VT.forward(mode='score'))
+//   api_sample_rows.hip  K sampled captions per clip on one encode (S2VT.sample)
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
 // Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue / beam_cum.hip.
 #pragma once
@@ -286,16 +287,26 @@ struct DecodeConst { PB wf, wih1, wv, wo; float* gtab; unsigned short *xw1, *xw2
 DecodeConst carve_decode_const(const s2vt_dims& d, void* base);
 
 // ------------------------------------------------------------------ api_beam.hip (shared with the scoring driver, api_score.hip)
-// One word_rnn step over R fixed rows with known tokens: row r reads gate-input row gx_idx[r] of gx (null: row r), its own h_prev /
-// c_prev row, token tok[r] (outside [0, V): token 0, *err raised).  kc != null: plane path - the gate table of the decode cache
+// One word_rnn step over R fixed rows: row r reads gate-input row gx_idx[r] of gx (null: row r), its own h_prev / c_prev row and
+// its token - tok[r], or with tok == null the packed arg-max word tok_packed[r] of the step before (the rows' sampled decode), or
+// with both null tok_const for every row (outside [0, V): token 0, *err raised).  kc != null: plane path - the gate table of the decode cache
 // stands for the embedded word and h_t also leaves as blocked planes (h_planes, k padding zeroed by the caller); kc == null: the
 // embedding rows against W_e in the kernel's second K segment.
 struct RowsStep {
     int R; const int32_t* tok; int* err;
+    const unsigned long long* tok_packed; int tok_const;
     const float* gx; const int32_t* gx_idx;
     const float *h_prev, *c_prev; float *h_out, *c_out;
     unsigned short* h_planes; int64_t ldhp;
 };
 int rows_word_step(hipStream_t st, const s2vt_dims& d, const s2vt_params* p, const DecodeConst* kc, const RowsStep& r);
+
+// ------------------------------------------------------------------ api_score.hip (shared with the rows' sampled decode, api_sample_rows.hip)
+// The library-kept scratch of an encode phase, one buffer per (device, stream), grown on demand (a call that grows it synchronises
+// the device once); calls on one stream are stream-ordered and share it.
+int encode_scratch(hipStream_t st, size_t bytes, void** out);
+// The encode phase as launches per timestep on the fp32-input MFMA, once per clip: leaves vid_h, vid_c, word_h, word_c [B][H] after
+// the L frames in `states` and vid_rnn's half of word_rnn's gate input (+ biases) of the S decode steps in gx_dec [S][B][4H].
+int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const float* feats, int S, float* states, float* gx_dec, const Lane& ln);
 
 }  // namespace s2vt

@@ -1,0 +1,126 @@
+// K sampled captions per clip on one encode (S2VT.sample; not in the reference): the draws of mode='sample' for the R = B * K rows
+// r = b * K + k, for sequence-level training with K samples per clip.  One encode per clip (the scoring driver's two encode phases),
+// word_rnn's start state gathered to the rows, then L-1 word steps over the fixed rows (the beam searches' step, rows_word_step):
+// row r reads its clip's gate input through gx_idx and the packed word it drew at the step before, and the sampling head - the
+// decode drivers' arg-max launches with their Gumbel arguments - draws for all R rows with row0 = 0, rows = R.  One chain on the
+// caller's stream: no schedule splits the rows, so batch row = r at every launch.  A final launch turns the packed words into ids.
+#include "api_internal.h"
+
+using namespace s2vt;
+
+extern "C" {
+
+struct SampleRowsWS {
+    int32_t* row_b;                  // [Rp] clip of each row
+    int* err;
+    float *states, *gx_dec;          // vid_h, vid_c, word_h, word_c [B][H] after the L frames; [L-1][B][4H] vid_rnn's half of the gate input
+    float *ph, *pc;                  // [2][R][H] h_t ping-pong, [R][H] c_t
+    unsigned long long* packed;      // [L-1][Rp] the steps' packed draws
+    float* gws; size_t gws_floats;
+    PB himg;                         // plane path: the step's h_t as blocked planes [Rp rows]
+    size_t bytes;
+};
+static bool sample_rows_shape_ok(const s2vt_dims* d, int K) {
+    return dims_ok(d) && K >= 1 && (int64_t)(d->L - 1) * (int64_t)rows64((size_t)d->B * K) < (1ll << 31);
+}
+static SampleRowsWS carve_sample_rows(const s2vt_dims& d, int K, void* base) {
+    const size_t B = d.B, H = d.H, R = B * K, Rp = rows64(R), S = d.L - 1;
+    Carver c{reinterpret_cast<char*>(base), 0, 0};
+    SampleRowsWS w;
+    w.row_b = c.take<int32_t>(Rp);
+    w.err = c.take<int>(4);
+    w.states = c.take<float>(4 * B * H); w.gx_dec = c.take<float>(S * B * 4 * H);
+    w.ph = c.take<float>(2 * R * H); w.pc = c.take<float>(R * H);
+    w.packed = c.take<unsigned long long>(S * Rp);
+    w.gws_floats = (size_t)4 << 20;
+    w.gws = c.take<float>(w.gws_floats);
+    // (sized for either path: which one a call takes depends on its cache argument)
+    if (gemm_mode() != 0) w.himg = take_planes(c, R, H, DECODE_PLANES);
+    w.bytes = align_up(c.off, 256);
+    return w;
+}
+size_t s2vt_sample_rows_workspace_bytes(const s2vt_dims* d, int32_t K) {
+    return sample_rows_shape_ok(d, K) ? carve_sample_rows(*d, K, nullptr).bytes : 0;
+}
+
+int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, float temperature,
+                            uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                            int32_t cache_valid, void* stream) {
+    S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace, "s2vt_sample_decode_rows: null/invalid argument");
+    S2VT_REQUIRE(sample_rows_shape_ok(d, K), "s2vt_sample_decode_rows: K = %d samples per clip: need K >= 1 and fewer than 2^31 packed words",
+                 (int)K);
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_sample_decode_rows: temperature and 1 / temperature must be finite and > 0 (got %g)",
+                 (double)temperature);
+    S2VT_REQUIRE(sos_ix >= 0 && sos_ix < d->V, "s2vt_sample_decode_rows: sos_ix %d outside [0, V = %d)", (int)sos_ix, d->V);
+    const SampleRowsWS w = carve_sample_rows(*d, K, workspace);
+    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_sample_decode_rows: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    const int B = d->B, H = d->H, V = d->V, S = d->L - 1, R = B * K, Rp = (int)rows64((size_t)R);
+    const int64_t BH = (int64_t)B * H, RH = (int64_t)R * H;
+    const bool planes = cache != nullptr;
+    S2VT_REQUIRE(!planes || w.himg.p, "s2vt_sample_decode_rows: a cache needs a plane mode (gemm mode 1 / 3)");
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    // ---- 1. encode, once per clip.  With a cache: the decode drivers' encode phase on the plane path (persistent split-precision
+    // recurrence; it fills the cache when cache_valid == 0 and refuses, before anything is enqueued, a shape or mode it does not take)
+    if (planes) {
+        void* scratch = nullptr;
+        const size_t sbytes = s2vt_decode_workspace_bytes(d);
+        if ((rc = encode_scratch(st, sbytes, &scratch))) return rc;
+        if ((rc = s2vt_decode_encode_cached(d, p, feats, scratch, sbytes, cache, cache_bytes, cache_valid, w.states, w.states + BH,
+                                            w.states + 2 * BH, w.states + 3 * BH, w.gx_dec, S, stream)))
+            return rc;
+    } else if ((rc = score_encode_per_step(*d, p, feats, S, w.states, w.gx_dec, Lane{st, w.gws, w.gws_floats, nullptr}))) {
+        return rc;
+    }
+    if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
+    if ((rc = rows_clip(st, R, K, Rp, w.row_b))) return rc;
+    // every step's packed words start from zero (the heads take an atomic max); rows R .. Rp - 1 stay zero and are never read
+    if ((rc = fill_zero(st, w.packed, (size_t)S * Rp * sizeof(unsigned long long)))) return rc;
+    // ---- 2. start states of the rows: their clip's word_rnn (h, c)
+    const DecodeConst kc = planes ? carve_decode_const(*d, cache) : DecodeConst{};
+    // (the whole image once: the steps write the H valid columns of the R rows, the k padding and the pad rows stay zero)
+    if (planes && (rc = fill_zero(st, w.himg.p, (size_t)Rp * (size_t)w.himg.ld * sizeof(unsigned short)))) return rc;
+    if ((rc = gather_rows_f32(st, w.states + 2 * BH, H, w.row_b, R, H, w.ph))) return rc;
+    if ((rc = gather_rows_f32(st, w.states + 3 * BH, H, w.row_b, R, H, w.pc))) return rc;
+    // ---- 3. L-1 steps: the word step over the rows, fed <sos> (step 0) or the previous step's packed draw, then the sampling head
+    // over the same rows - noise of (seed, step j, batch row r, v)
+    const float* hprev = w.ph;
+    for (int j = 0; j < S; ++j) {
+        unsigned long long* packed = w.packed + (int64_t)j * Rp;
+        RowsStep a = {};
+        a.R = R; a.err = w.err;
+        a.tok_packed = j > 0 ? packed - Rp : nullptr; a.tok_const = sos_ix;
+        a.gx = w.gx_dec + (int64_t)j * 4 * BH; a.gx_idx = w.row_b;
+        a.h_prev = hprev; a.c_prev = w.pc; a.c_out = w.pc;
+        a.h_out = w.ph + ((j + 1) & 1) * RH;
+        if (planes) { a.h_planes = w.himg.p; a.ldhp = w.himg.ld; }
+        {
+            ProfScope ps(st, K_STEP_FWD, 1);
+            if ((rc = rows_word_step(st, *d, p, planes ? &kc : nullptr, a))) return rc;
+        }
+        hprev = a.h_out;
+        const GumbelArgs g = gumbel_args(temperature, seed, (uint32_t)j, 0u, (uint32_t)R);
+        ProfScope ps(st, K_ARGMAX, 1);
+        if (planes) {
+            ArgmaxX3Args ax;
+            memset(&ax, 0, sizeof(ax));
+            ax.B = R; ax.V = V; ax.K = kc.wo.kpad;
+            ax.W = kc.wo.p; ax.ldw = kc.wo.ld;
+            ax.Hp = w.himg.p; ax.ldh = w.himg.ld;
+            ax.bias = p->out_b;
+            ax.packed = packed;
+            rc = logits_argmax_x3(st, ax, &g);
+        } else {
+            LogitsArgmaxArgs la;
+            la.B = R; la.H = H; la.V = V; la.h = a.h_out; la.ldh = H; la.w_out = p->out_w; la.ldw = H; la.b_out = p->out_b;
+            la.packed = packed;
+            la.stamps = nullptr;
+            rc = logits_argmax(st, la, &g);
+        }
+        if (rc) return rc;
+    }
+    // ---- 4. ids[r][j] of the R rows
+    if ((rc = unpack_rows(st, w.packed, S, Rp, R, ids))) return rc;
+    return post_async_error(st, w.err, 3);       // (a ring slot: no wait for an earlier call's record)
+}
+}

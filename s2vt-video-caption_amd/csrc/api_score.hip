@@ -75,7 +75,9 @@ size_t s2vt_score_workspace_bytes(const s2vt_dims* d, int32_t K, int32_t T) {
 // once the states and vid_rnn's gate-input rows are handed out.  The library keeps one such buffer per (device, stream) and grows
 // it on demand - hipMalloc / hipFree, so a call that grows it synchronises the device once; every other call allocates nothing.
 // Calls on one stream are stream-ordered, so they can share it; calls on different streams get different buffers.
-static int encode_scratch(hipStream_t st, size_t bytes, void** out) {
+}  // (C linkage ends: the encode phase is shared with api_sample_rows.hip, see api_internal.h)
+namespace s2vt {
+int encode_scratch(hipStream_t st, size_t bytes, void** out) {
     static std::mutex mu;
     static std::map<std::pair<int, hipStream_t>, std::pair<void*, size_t>> bufs;
     int dev = 0;
@@ -95,14 +97,14 @@ static int encode_scratch(hipStream_t st, size_t bytes, void** out) {
 
 // The encode phase as launches per timestep on the fp32-input MFMA (S2VTModel.py:54, 64-67 of mode='train' without its dropout):
 // feature projection, vid_rnn over the L frames and its S input-free decode steps, their half of word_rnn's gate input, word_rnn
-// over the L frames with a zero embedding.  Leaves what the word steps start from in w.states / w.gx_dec.
-static int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const float* feats, int S, const ScoreWS& w, hipStream_t st) {
+// over the L frames with a zero embedding.  Leaves what the word steps start from in states / gx_dec.
+int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const float* feats, int S, float* states, float* gx_dec, const Lane& ln) {
     const int B = d.B, L = d.L, H = d.H, E = d.E, Tv = L + S;
     const int64_t BH = (int64_t)B * H;
+    hipStream_t st = ln.s;
     void* scratch = nullptr;
     if (int r = encode_scratch(st, carve_score_enc(d, S, nullptr).bytes, &scratch)) return r;
     const ScoreEnc e = carve_score_enc(d, S, scratch);
-    const Lane ln{st, w.gws, w.gws_floats, nullptr};
     int rc;
     if ((rc = bias_sums(st, p, H, e.bsum1, e.bsum2))) return rc;
     if ((rc = project_features_f32(ln, d, p, feats, e.x1, e.gxb, e.bsum1))) return rc;
@@ -111,10 +113,12 @@ static int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const
     if ((rc = seq_fwd(st, 0, L, B, H, e.gxb, L, e.bsum2, p->word_w_hh, e.h2, e.c2, false))) return rc;
     const float* last[4] = {e.h1 + (L - 1) * BH, e.c1 + (L - 1) * BH, e.h2 + (L - 1) * BH, e.c2 + (L - 1) * BH};
     for (int k = 0; k < 4; ++k)
-        S2VT_HIP(hipMemcpyAsync(w.states + k * BH, last[k], (size_t)BH * sizeof(float), hipMemcpyDeviceToDevice, st));
-    S2VT_HIP(hipMemcpyAsync(w.gx_dec, e.gxb + (int64_t)L * 4 * BH, (size_t)S * 4 * BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+        S2VT_HIP(hipMemcpyAsync(states + k * BH, last[k], (size_t)BH * sizeof(float), hipMemcpyDeviceToDevice, st));
+    S2VT_HIP(hipMemcpyAsync(gx_dec, e.gxb + (int64_t)L * 4 * BH, (size_t)S * 4 * BH * sizeof(float), hipMemcpyDeviceToDevice, st));
     return 0;
 }
+}  // namespace s2vt
+extern "C" {
 
 int s2vt_score_captions(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* captions, int64_t stride_b,
                         int64_t stride_k, int32_t K, int32_t T, int32_t eos_ix, double length_alpha, float* token_lp, float* score,
@@ -143,7 +147,7 @@ int s2vt_score_captions(const s2vt_dims* d, const s2vt_params* p, const float* f
         if ((rc = s2vt_decode_encode_cached(d, p, feats, scratch, sbytes, cache, cache_bytes, cache_valid, w.states, w.states + BH,
                                             w.states + 2 * BH, w.states + 3 * BH, w.gx_dec, S, stream)))
             return rc;
-    } else if ((rc = score_encode_per_step(*d, p, feats, S, w, st))) {
+    } else if ((rc = score_encode_per_step(*d, p, feats, S, w.states, w.gx_dec, Lane{st, w.gws, w.gws_floats, nullptr}))) {
         return rc;
     }
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;

@@ -213,6 +213,49 @@ __global__ __launch_bounds__(kCiderThreads) void sc_weights_kernel(const int64_t
     }
 }
 
+// One wavefront = one clip and its K rows r = b * K + k.  Baseline of row k: r_greedy[b], or without it the mean of the OTHER K - 1
+// rewards - the K rewards summed in ascending k from 0.0, minus the row's own, divided by K - 1: adds, one subtract, one divide in
+// fp64, no product (nothing to contract); a clip whose K rewards compare equal takes that reward itself.  Every lane walks the same K
+// numbers, so the sum needs no exchange.
+constexpr int kGroupThreads = 64;
+__global__ __launch_bounds__(kGroupThreads) void sc_weights_group_kernel(const int64_t* sampled, const double* r_sample,
+                                                                         const double* r_greedy, int K, int T, int sos, int eos,
+                                                                         int64_t* caps, float* weight, double* baseline) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double* rs = r_sample + (int64_t)b * K;
+    double sum = 0.0;
+    bool same = !r_greedy;                        // all K rewards equal: the baseline IS that reward (see the header)
+    if (!r_greedy)
+        for (int j = 0; j < K; ++j) {
+            sum += rs[j];
+            same = same && rs[j] == rs[0];
+        }
+    for (int k = 0; k < K; ++k) {
+        const int64_t r = (int64_t)b * K + k;
+        const int64_t* row = sampled + r * T;
+        int first = T;                            // index of the first <eos>, T without one
+        for (int i = lane; i < T; i += kGroupThreads)
+            if (row[i] == (int64_t)eos) { first = i; break; }
+        for (int o = kGroupThreads / 2; o > 0; o >>= 1) {
+            const int other = __shfl_xor(first, o, kGroupThreads);
+            first = other < first ? other : first;
+        }
+        const double base = r_greedy ? r_greedy[b] : same ? rs[k] : (sum - rs[k]) / (double)(K - 1);
+        const float adv = (float)(rs[k] - base);
+        int64_t* crow = caps + r * (T + 1);
+        float* wrow = weight + r * (T + 1);
+        if (lane == 0) {
+            crow[0] = sos;
+            wrow[0] = 0.0f;
+            if (baseline) baseline[r] = base;
+        }
+        for (int i = lane; i < T; i += kGroupThreads) {
+            crow[1 + i] = row[i];
+            wrow[1 + i] = i <= first ? adv : 0.0f;
+        }
+    }
+}
+
 }  // namespace s2vt
 
 using namespace s2vt;
@@ -247,6 +290,17 @@ int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double
     hipLaunchKernelGGL(sc_weights_kernel, dim3((unsigned)B), dim3(kCiderThreads), 0, (hipStream_t)stream, sampled, r_sample, r_greedy,
                        (int)T, (int)sos, (int)eos, caps, weight);
     S2VT_LAUNCH_CHECK("sc_weights_kernel");
+    return 0;
+}
+
+int s2vt_sc_weights_group(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t K, int32_t T,
+                          int32_t sos, int32_t eos, int64_t* caps, float* weight, double* baseline, void* stream) {
+    S2VT_REQUIRE(sampled && r_sample && caps && weight, "s2vt_sc_weights_group: null argument");
+    S2VT_REQUIRE(B > 0 && K > 0 && T > 0, "s2vt_sc_weights_group: bad dims (B %d, K %d, T %d)", (int)B, (int)K, (int)T);
+    S2VT_REQUIRE(r_greedy || K >= 2, "s2vt_sc_weights_group: the mean of the other K - 1 rewards needs K >= 2 (got K = %d)", (int)K);
+    hipLaunchKernelGGL(sc_weights_group_kernel, dim3((unsigned)B), dim3(kGroupThreads), 0, (hipStream_t)stream, sampled, r_sample,
+                       r_greedy, (int)K, (int)T, (int)sos, (int)eos, caps, weight, baseline);
+    S2VT_LAUNCH_CHECK("sc_weights_group_kernel");
     return 0;
 }
 

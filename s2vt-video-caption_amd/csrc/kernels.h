@@ -341,6 +341,9 @@ int gather_rows_f32(hipStream_t s, const float* src, int64_t ld, const int32_t* 
 size_t embedding_grad_ws_ints(int64_t rows, int V);
 int embedding_grad(hipStream_t s, const float* d_rows, int64_t rows, int E, const int32_t* tok, int V, float* d_emb, int* ws);
 int unpack_tokens(hipStream_t s, const unsigned long long* packed, int steps, int B, int64_t* out_ids);
+int rows_clip(hipStream_t s, int R, int K, int Rp, int32_t* row_b);      // row_b[r] = r / K for r < R, 0 up to Rp
+// packed[steps][ldp] -> ids[R][steps] for the rows r < R <= ldp
+int unpack_rows(hipStream_t s, const unsigned long long* packed, int steps, int ldp, int R, int64_t* out_ids);
 // scheduled sampling: packed[step][ldp rows] -> used [B][steps] (the words each step was fed: ss.forced, or the previous step's
 // draw where the coin fell below ss.p) and, optionally, draws [B][steps] (every step's own choice); ss.step is not read
 int unpack_scheduled(hipStream_t s, const unsigned long long* packed, int steps, int ldp, int B, const SsArgs& ss, int64_t* used,

@@ -391,6 +391,33 @@ int unpack_tokens(hipStream_t s, const unsigned long long* packed, int steps, in
     return 0;
 }
 
+// the same from a padded image: packed[step][ldp] -> ids[r][step] for the rows r < R <= ldp (the rows' sampled decode)
+__global__ void unpack_rows_kernel(const unsigned long long* packed, int steps, int ldp, int R, int64_t* out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)steps * R) return;
+    const int st = (int)(i / R), r = (int)(i % R);
+    out[(int64_t)r * steps + st] = packed_token(packed[(int64_t)st * ldp + r]);
+}
+int unpack_rows(hipStream_t s, const unsigned long long* packed, int steps, int ldp, int R, int64_t* out_ids) {
+    const int64_t n = (int64_t)steps * R;
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(unpack_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, packed, steps, ldp, R, out_ids);
+    S2VT_LAUNCH_CHECK("unpack_rows_kernel");
+    return 0;
+}
+
+// row_b[r] = r / K: the clip of row r = b * K + k (rows R .. Rp - 1 of the padding: clip 0, never read as a row)
+__global__ void rows_clip_kernel(int R, int K, int Rp, int32_t* row_b) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r < Rp) row_b[r] = r < R ? r / K : 0;
+}
+int rows_clip(hipStream_t s, int R, int K, int Rp, int32_t* row_b) {
+    if (Rp <= 0) return 0;
+    hipLaunchKernelGGL(rows_clip_kernel, dim3(cdiv(Rp, 256)), dim3(256), 0, s, R, K, Rp, row_b);
+    S2VT_LAUNCH_CHECK("rows_clip_kernel");
+    return 0;
+}
+
 // scheduled sampling: packed[step][ldp] -> used[b][step] (forced word, or the previous step's draw where the coin fell below p)
 // and draws[b][step] (optional)
 __global__ void unpack_scheduled_kernel(const unsigned long long* packed, int steps, int ldp, int B, SsArgs ss, int64_t* used,

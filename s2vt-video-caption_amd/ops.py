@@ -746,6 +746,36 @@ def sc_weights(sampled, r_sample, r_greedy, sos_ix, eos_ix):
     return caps, weight
 
 
+def sc_weights_group(sampled, r_sample, r_greedy, K, sos_ix, eos_ix, return_baseline=False):
+    """(caps int64 [B*K, T+1], weight fp32 [B*K, T+1][, baseline fp64 [B*K]]) for K sampled captions per clip, rows r = b*K + k -
+    s2vt_sc_weights_group.  sampled int64 [B*K, T], r_sample fp64 [B*K].  r_greedy None: each row is baselined with the mean reward
+    of its clip's other K - 1 rows (self_critical.group_advantages; K >= 2); r_greedy fp64 [B]: with its clip's greedy reward."""
+    lib = capi.load()
+    K = int(K)
+    if K < 1 or (r_greedy is None and K < 2):
+        raise ValueError("sc_weights_group: the mean of the other K - 1 rewards needs K >= 2 (K >= 1 with r_greedy), got K = %d" % K)
+    require_hip(sampled, "sampled")
+    if sampled.dim() != 2 or sampled.dtype != torch.int64 or sampled.shape[0] % K != 0 or sampled.shape[0] == 0:
+        raise capi.S2VTHipError("sc_weights_group: sampled must be int64 [B*K, T]")
+    sampled = sampled.contiguous()
+    R, T = sampled.shape
+    B = R // K
+    for name, r, n in (("r_sample", r_sample, R), ("r_greedy", r_greedy, B)):
+        if r is None:
+            continue
+        require_hip(r, name)
+        if r.dtype != torch.float64 or tuple(r.shape) != (n,) or not r.is_contiguous():
+            raise capi.S2VTHipError("sc_weights_group: %s must be a contiguous float64 [%d]" % (name, n))
+    dev = sampled.device
+    with torch.cuda.device(dev):
+        caps = torch.empty(R, T + 1, dtype=torch.int64, device=dev)
+        weight = torch.empty(R, T + 1, dtype=torch.float32, device=dev)
+        baseline = torch.empty(R, dtype=torch.float64, device=dev) if return_baseline else None
+        capi.check(lib.s2vt_sc_weights_group(_ptr(sampled), _ptr(r_sample), _ptr(r_greedy), B, K, T, int(sos_ix), int(eos_ix), _ptr(caps),
+                                             _ptr(weight), _ptr(baseline), _stream(dev)), "s2vt_sc_weights_group")
+    return (caps, weight, baseline) if return_baseline else (caps, weight)
+
+
 # ---------------------------------------------------------------- per-op test support (include/s2vt_hip.h: the backward's
 # gather / scatter / reorder pieces).  Matrices here are float32 ROWS: unit column stride, the row stride is the tensor's own
 # (a column block of a wider tensor is passed as the view it is).

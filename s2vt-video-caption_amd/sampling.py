@@ -108,3 +108,52 @@ def check_sample_args(temperature, seed):
     if not 0 <= seed < 2 ** 64:
         raise ValueError("seed must be in [0, 2^64), got %r" % (seed,))
     return t, seed
+
+
+def check_n_samples(n_samples):
+    """n_samples as an int >= 1 or ValueError (2.5, '3', True and 0 are refused) - before anything reaches the library"""
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or int(n_samples) < 1:
+        raise ValueError("n_samples must be an integer >= 1, got %r" % (n_samples,))
+    return int(n_samples)
+
+
+def sample_rows(model, feats, params, K, temperature, seed):
+    """ids int64 [B, K, L-1]: K draws per clip on ONE encode - s2vt_sample_decode_rows.  Row b*K + k draws with the noise of
+    (seed, decode step, batch row b*K + k, v): the draw of mode='sample' on feats.repeat_interleave(K, 0).  With the model's decode
+    cache where a decode of the batch takes the plane path's persistent encode (filled here on fresh weights), on the fp32-input
+    MFMA path otherwise.  On the device, no host synchronisation, no gradient."""
+    import ctypes
+
+    import torch
+
+    from . import capi
+    from . import functional as F
+    with torch.no_grad():
+        lib = capi.load()
+        F.require_hip(feats, "feats")
+        feats = F._f32c(feats, "feats")
+        raw = params
+        params = tuple(F._f32c(p.detach(), "parameter") for p in params)
+        d = F._dims(feats, params)
+        nbytes = lib.s2vt_sample_rows_workspace_bytes(ctypes.byref(d), K)
+        if nbytes <= 0:
+            raise ValueError("sample: %d clips x %d samples is not a shape the library serves" % (d.B, K))
+        dev = feats.device
+        with torch.cuda.device(dev):
+            cache, valid = None, False
+            # (the plane path where a greedy decode of this batch takes it: fewer than 24 clips run as they are on the
+            # launch-per-timestep path - api_internal.h, batch_pads)
+            if capi.decode_plan(d, encode_only=False)[1]:
+                cache, valid = F.decode_cache_entry(model, raw, d, dev, lib)
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            ids = torch.empty(d.B, K, d.L - 1, dtype=torch.int64, device=dev)
+            ps = F._params_struct(capi.Params, params)
+            capi.check(lib.s2vt_sample_decode_rows(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix), temperature,
+                                                   seed, F._ptr(ids), F._ptr(ws), nbytes, F._ptr(cache),
+                                                   cache.numel() if cache is not None else 0, 1 if valid else 0, F._stream(dev)),
+                       "s2vt_sample_decode_rows")
+            if cache is not None:
+                entry = F._DECODE_CACHES.get(model)
+                if entry is not None and entry[1] is cache:
+                    entry[2] = True                 # (stream-ordered, as in functional.greedy_decode: the call wrote every image)
+    return ids

@@ -54,6 +54,34 @@ def advantage_weights(sampled, advantage, eos_ix):
     return w
 
 
+def group_advantages(rewards, greedy=None):
+    """(advantage, baseline) float64 [B, K] for K sampled captions per clip with rewards [B, K].  greedy None: row k is baselined
+    with the mean reward of the clip's OTHER K - 1 rows (Luo 2020), K >= 2 -
+        baseline[b, k] = ((r[b, 0] + r[b, 1] + ... + r[b, K-1], added in that order from 0.0) - r[b, k]) / (K - 1);
+    greedy float64 [B]: baseline[b, k] = greedy[b].  advantage = r - baseline.  s2vt_sc_weights_group's arithmetic operation for
+    operation (np.sum would add pairwise), so the device reproduces it bit for bit.  A clip whose K rewards compare equal takes
+    that reward as every row's baseline: its advantages are exactly zero."""
+    r = np.asarray(rewards, dtype=np.float64)
+    if r.ndim != 2 or r.shape[1] < 1:
+        raise ValueError("group_advantages: rewards must be [B, K], got %s" % (r.shape,))
+    B, K = r.shape
+    if greedy is None:
+        if K < 2:
+            raise ValueError("group_advantages: the mean of the other K - 1 rewards needs K >= 2, got K = %d" % K)
+        total = np.zeros(B, dtype=np.float64)
+        for j in range(K):
+            total = total + r[:, j]
+        baseline = (total[:, None] - r) / np.float64(K - 1)
+        same = (r == r[:, :1]).all(1)          # K equal rewards: the baseline is that reward, exactly (the rounded sum would
+        baseline[same] = r[same]               # leave a difference of rounding size, and with it a weight that is not zero)
+    else:
+        g = np.asarray(greedy, dtype=np.float64)
+        if g.shape != (B,):
+            raise ValueError("group_advantages: greedy must be [B] = [%d], got %s" % (B, g.shape))
+        baseline = np.broadcast_to(g[:, None], r.shape).copy()
+    return r - baseline, baseline
+
+
 # ------------------------------------------------------------------ the same score on the device (train.py --sc-reward device)
 KEY_TOKENS, KEY_BITS = 4, 16         # an n-gram key: up to four tokens of 16 bits in a uint64, first token on top, absent positions 0
 

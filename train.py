@@ -66,6 +66,13 @@ def parse(argv=None):
                          "of the ids.  device: self_critical.DeviceCiderRewarder - the reference table is built once and lives on the "
                          "card, the rewards, the <sos>-prefixed captions and the advantage weights come from HIP kernels "
                          "(s2vt_cider_rewards, s2vt_sc_weights) and the ids never leave the device")
+    ap.add_argument("--sc-samples", type=int, default=1, metavar="K",
+                    help="captions sampled per clip in a --self-critical step (S2VT.sample: one encode per clip, K rows of word "
+                         "steps); the train step then runs on the B*K captions.  1 (default): today's step")
+    ap.add_argument("--sc-baseline", choices=("greedy", "mean"), default="greedy",
+                    help="what a sampled caption's reward is compared with.  greedy: the reward of the clip's greedy caption (SCST, "
+                         "Rennie et al. 2017).  mean: the mean reward of the clip's other K - 1 samples (Luo 2020) - no greedy "
+                         "decode runs; needs --sc-samples >= 2")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
     ap.add_argument("--scheduled-sampling-start", type=int, default=-1, metavar="E",
                     help="scheduled sampling (Bengio et al., 2015) from epoch E on: each decode-step input of a training step is, with "
@@ -79,6 +86,12 @@ def parse(argv=None):
     ap.add_argument("--ss-temperature", type=float, default=None,
                     help="the model's own word is a draw from softmax(logit / temperature); absent: the arg-max")
     opt = ap.parse_args(argv)
+    if (opt.sc_samples != 1 or opt.sc_baseline != "greedy") and not opt.self_critical:
+        ap.error("--sc-samples / --sc-baseline need --self-critical")
+    if opt.sc_samples < 1:
+        ap.error("--sc-samples must be at least 1")
+    if opt.sc_baseline == "mean" and opt.sc_samples < 2:
+        ap.error("--sc-baseline mean needs --sc-samples >= 2 (the mean of the other K - 1 samples)")
     if opt.scheduled_sampling_start >= 0:
         if opt.self_critical:
             ap.error("--scheduled-sampling-start cannot be combined with --self-critical (it is the stage before it)")
@@ -102,14 +115,66 @@ def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
-                            reducer=None):
+                            reducer=None, samples=1, baseline="greedy"):
     """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
     train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
     (every phase ends with a device synchronisation), hist["reward_sample"] / ["reward_greedy"] the batch means.  sc_reward
     "host": rewarder is a CiderRewarder and the ids make a round trip through the host; "device": a DeviceCiderRewarder, and
-    nothing but the two batch means leaves the card."""
+    nothing but the two batch means leaves the card.
+    samples = K > 1 (or baseline "mean"): K captions per clip from model.sample (one encode per clip), rewards over the B*K rows,
+    each row's reward compared with its clip's greedy reward (baseline "greedy") or with the mean reward of the clip's other K - 1
+    rows (baseline "mean": no greedy decode runs, sc_split_ms["greedy"] stays 0 and hist["reward_greedy"] empty), then the train step
+    on the clips repeated K times with the B*K captions.  hist["reward_baseline"] gets the batch mean of the baselines."""
     from s2vt_video_caption_amd import dp, ops
-    from s2vt_video_caption_amd.self_critical import advantage_weights
+    from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages
+    K = int(samples)
+    if baseline not in ("greedy", "mean") or K < 1 or (baseline == "mean" and K < 2):
+        raise ValueError("samples must be >= 1 and baseline 'greedy' or 'mean' (which needs samples >= 2), got %r, %r" % (samples, baseline))
+
+    def group_step(feats, ids):
+        sp = hist["sc_split_ms"]
+        on_device = sc_reward == "device"
+        t0 = time.perf_counter()
+        sampled = model.sample(feats, K, temperature=temperature).view(feats.shape[0] * K, -1)
+        if on_device:
+            torch.cuda.synchronize(dev)
+        else:
+            sampled = sampled.cpu()
+        t1 = time.perf_counter()
+        greedy = None
+        if baseline == "greedy":
+            with torch.no_grad():
+                greedy = model(feats, mode='test')
+            if on_device:
+                torch.cuda.synchronize(dev)
+            else:
+                greedy = greedy.cpu()
+        t2 = time.perf_counter()
+        row_ids = [v for v in ids for _ in range(K)]
+        r_s = rewarder.rewards(row_ids, sampled)
+        r_g = rewarder.rewards(ids, greedy) if greedy is not None else None
+        if on_device:
+            caps, weight, base = ops.sc_weights_group(sampled, r_s, r_g, K, sos, eos, return_baseline=True)
+            means = torch.stack([r_s.mean(), base.mean()] + ([r_g.mean()] if r_g is not None else [])).tolist()   # the phase's synchronisation
+        else:
+            adv, base = group_advantages(r_s.reshape(-1, K), r_g)
+            weight = advantage_weights(sampled, adv.reshape(-1), eos).to(dev)
+            caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
+            means = [float(r_s.mean()), float(base.mean())] + ([float(r_g.mean())] if r_g is not None else [])
+        t3 = time.perf_counter()
+        loss = dp.train_step(model, reward_criterion, optimizer, feats.repeat_interleave(K, 0), caps, weight, reducer, check_errors=True)
+        t4 = time.perf_counter()
+        for k, v in (("sample", t1 - t0), ("greedy", t2 - t1 if greedy is not None else 0.0), ("scoring", t3 - t2), ("train", t4 - t3)):
+            sp[k] += 1e3 * v
+        sp["steps"] += 1
+        hist["reward_sample"].append(means[0])
+        hist.setdefault("reward_baseline", []).append(means[1])
+        if r_g is not None:
+            hist["reward_greedy"].append(means[2])
+        return loss
+
+    if K > 1 or baseline == "mean":
+        return group_step
 
     def host_step(feats, ids):
         sp = hist["sc_split_ms"]
@@ -131,6 +196,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         sp["steps"] += 1
         hist["reward_sample"].append(float(r_s.mean()))
         hist["reward_greedy"].append(float(r_g.mean()))
+        hist.setdefault("reward_baseline", []).append(float(r_g.mean()))
         return loss
 
     def device_step(feats, ids):
@@ -155,6 +221,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         sp["steps"] += 1
         hist["reward_sample"].append(means[0])
         hist["reward_greedy"].append(means[1])
+        hist.setdefault("reward_baseline", []).append(means[1])
         return loss
 
     return device_step if sc_reward == "device" else host_step
@@ -250,11 +317,11 @@ def run(opt):
         reward_criterion = RewardCriterion()
         # wall-clock split of the self-critical steps (ms, summed over the run; each phase ends with a device synchronisation)
         hist["sc_split_ms"] = {"sample": 0.0, "greedy": 0.0, "scoring": 0.0, "train": 0.0, "steps": 0}
-        hist["reward_sample"], hist["reward_greedy"] = [], []
+        hist["reward_sample"], hist["reward_greedy"], hist["reward_baseline"] = [], [], []
 
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
-                                                     opt.sc_reward, reducer)
+                                                     opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline)
 
     def save(name):
         if rank == 0:
@@ -271,6 +338,7 @@ def run(opt):
         # (ss_prob == 0 passes no keyword at all: the plain teacher-forced step; every process draws its own seeds)
         ss_kwargs = dict(ss_prob=ss_prob, ss_temperature=opt.ss_temperature) if ss_prob > 0 else None
         running, count = 0.0, 0
+        sc_from = len(hist["reward_baseline"]) if rewarder is not None else 0
         for feats, targets, ids, masks in dataloader.feed_batches(train_loader, dev):
             # train.py:116-127; check_errors: a device-side error of this step (IndexError for a caption id outside the vocabulary)
             # is raised BEFORE optimizer.step(), as in the reference, whose nn.Embedding raises in the forward
@@ -297,9 +365,13 @@ def run(opt):
         hist["train_loss"].append(train_loss)
         hist["valid_loss"].append(valid_loss)
         if rank == 0:
-            print("epoch {} train loss:{} valid loss: {} lr: {}{}".format(
+            sc_text = ""
+            if rewarder is not None and len(hist["reward_baseline"]) > sc_from:      # the epoch's mean sampled reward and baseline
+                n = len(hist["reward_baseline"]) - sc_from
+                sc_text = " reward: {} baseline: {}".format(sum(hist["reward_sample"][sc_from:]) / n, sum(hist["reward_baseline"][sc_from:]) / n)
+            print("epoch {} train loss:{} valid loss: {} lr: {}{}{}".format(
                 epoch, train_loss, valid_loss, optimizer.param_groups[0]['lr'],
-                " ss_prob: {}".format(ss_prob) if opt.scheduled_sampling_start >= 0 else ""))
+                " ss_prob: {}".format(ss_prob) if opt.scheduled_sampling_start >= 0 else "", sc_text))
         lr_scheduler.step(valid_loss)                                                          # train.py:155
         n_before = early_stopping.val_loss_min
         if rank == 0:
