@@ -281,7 +281,7 @@ def _check_step(tag, got, want, tols):
 def test_table_step_against_the_fp64_cell_and_its_plane_image(lib, B, H, gemv):
     """(c) lstm_step_fwd with gx_tab + gx_idx + h_planes - the 16- and 32-row MFMA tiles, and for B <= 8 the GEMV kernel (option gemv
     = 2: lstm_step_fwd_gemv_ok holds at B = 5, H = 44) - against the fp64 cell for every token source; an id == V raises IndexError and its row runs with table row 0.  The plane
-    image: bit-equal to ops.split_planes of the kernel's own h_out, and into a sentinel-filled image of a wider row stride exactly
+    image: bit-equal to ops.split_planes of the kernel's own h_out (the split itself against a host split: test_gpu_plane_split.py), and into a sentinel-filled image of a wider row stride exactly
     the elements of (b < B, unit < H) are written, with the same bits."""
     from s2vt_video_caption_amd import capi, ops
     case = _step_case(B, H)

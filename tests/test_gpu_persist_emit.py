@@ -5,7 +5,7 @@ drivers, through the test-support entry points s2vt_lstm_seq_{fwd,bwd}_x3_persis
   BPTT      SeqBwdX3Args::dgp (dG_t as such an image, through the XOR-swizzled LDS tile), colpart (the bias gradient's 32-row
             column sums per chain) and skip_dg.
 
-Whole images are pinned by BIT equality with ops.split_planes (tested on its own in test_gpu_kernels.py) of the fp32 output of the
+Whole images are pinned by BIT equality with ops.split_planes (tested on its own, against a host split, in test_gpu_plane_split.py) of the fp32 output of the
 run without emission - which test_persistent_split_precision_recurrence / _bptt pin against fp64 - and by a sentinel pre-fill of an
 image with a wider row stride and 64 more rows: nothing outside the documented elements may change.  Column sums are pinned against
 the fp64 sum of the same fp32 dG: (n - 1) * 2^-24 * sum|x| bounds an n-term fp32 sum in ANY fixed order (every one of the n - 1
