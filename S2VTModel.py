@@ -66,7 +66,11 @@ class S2VT(nn.Module):
                 length_alpha=0.7, n_best=1, temperature=1.0, seed=None):
         """
         :param feats: [B, L, feat_dim]
-        :param targets: [B, L-1] word ids (train mode)
+        :param targets: [B, L-1] word ids (train mode); or [B, K, L-1] (any strides, an expanded view is read as it is): K captions
+                     per clip (not in the reference) -> logits [B, K, L-1, V], those of the call on feats.repeat_interleave(K, 0)
+                     with targets.reshape(B*K, L-1), and its gradients (feats.grad summed over a clip's K rows).  The one-layer
+                     LSTM encodes every clip once (functional.train_forward_group); a GRU or stacked model runs the repeated
+                     clips.  feat_drop is drawn once per clip, out_drop on [B*K, L-1, H]; ss_prob > 0 is refused
         :param mode: 'train' -> logits [B, L-1, V]; 'test' -> greedy ids [B, L-1] (int64);
                      'beam_search' -> list of id sequences (each starting with <sos>): the reference's search, score = the LAST
                      token's log-prob / len**0.7;
@@ -105,10 +109,26 @@ class S2VT(nn.Module):
         if mode == 'score':                                # (shape checks again, with the dims, in score.score_captions)
             _score.check_score_args(targets, feats.shape[0] if isinstance(feats, torch.Tensor) and feats.dim() else -1, self.length,
                                     None, length_alpha)
+        # K captions per clip (not in the reference): 3-D targets [B, K, L-1] -> logits [B, K, L-1, V] on one encode per clip
+        grouped = mode == 'train' and isinstance(targets, torch.Tensor) and targets.dim() == 3
+        if grouped:
+            if ss_prob > 0:
+                raise ValueError("scheduled sampling (ss_prob > 0) is not implemented for K captions per clip (3-D targets)")
+            nb = feats.shape[0] if isinstance(feats, torch.Tensor) and feats.dim() == 3 else -1
+            if targets.shape[0] != nb or targets.shape[1] < 1 or targets.shape[2] != self.length - 1:
+                raise ValueError("targets must be [B, K, L-1] = [%d, K >= 1, %d], got %s" % (nb, self.length - 1, tuple(targets.shape)))
         _F.require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
         sample = _sampling.check_sample_args(temperature, seed) if mode == 'sample' else None
+        if grouped and (_G.is_gru_model(self) or _S.is_stacked_lstm_model(self)):
+            # no shared encode on these paths: the repeated clips (as S2VT.sample runs them), feat_drop drawn once per clip
+            _F.require_hip(targets, "targets")
+            B, K = targets.shape[0], targets.shape[1]
+            run = self._forward_gru if _G.is_gru_model(self) else self._forward_stacked
+            out = run(self.feat_drop(feats).repeat_interleave(K, 0), targets.reshape(B * K, -1), mode, None, (0.0, None, None),
+                      drop_feats=False)
+            return out.view(B, K, self.length - 1, -1)
         if _G.is_gru_model(self):
             return self._forward_gru(feats, targets, mode, sample, (ss_prob, ss_temperature, seed))
         if _S.is_stacked_lstm_model(self):
@@ -128,6 +148,15 @@ class S2VT(nn.Module):
                 raise ValueError("mode='train' needs targets")
             if ss_prob > 0:
                 targets = _F.scheduled_inputs(clean, targets, params, ss_prob, temperature=ss_temperature, seed=seed, owner=self)
+            if grouped:
+                # every clip encoded once (feat_drop drawn once per clip, above); the out_drop mask is the draw the call on the
+                # repeated clips would make: nn.Dropout on a [B*K, L-1, H] ones tensor, time-major for the kernels
+                out_mask = None
+                if self.training and self.out_drop.p > 0:
+                    R, H = feats.shape[0] * targets.shape[1], self.dim_hid
+                    keep = self.out_drop(torch.ones(R, self.length - 1, H, dtype=torch.float32, device=feats.device))
+                    out_mask = keep.transpose(0, 1).reshape((self.length - 1) * R, H).contiguous()
+                return _F.train_forward_group(feats, targets, params, grad_sink=_F.grad_sink_for(self), out_mask=out_mask)
             out_mask = None
             if self.training and self.out_drop.p > 0:
                 # S2VTModel.py:79 applies nn.Dropout to the [B, L-1, H] decode-step hidden states: the same call on a ones
@@ -168,7 +197,7 @@ class S2VT(nn.Module):
         params = self._hip_params()
         return _sampling.sample_rows(self, self.feat_drop(feats), params, K, t, s)
 
-    def _forward_gru(self, feats, targets, mode, sample=None, ss=(0.0, None, None)):
+    def _forward_gru(self, feats, targets, mode, sample=None, ss=(0.0, None, None), drop_feats=True):
         """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
@@ -179,7 +208,7 @@ class S2VT(nn.Module):
             raise NotImplementedError("mode='score' of a GRU model: the scoring driver's word step is the LSTM's; take the logits "
                                       "of mode='train' and log_softmax(...).gather(...) them")
         clean = feats                                      # (the scheduled pass runs without dropout)
-        feats = self.feat_drop(feats)                      # S2VTModel.py:52
+        feats = self.feat_drop(feats) if drop_feats else feats      # S2VTModel.py:52 (drop_feats False: the caller drew it)
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")
@@ -198,7 +227,7 @@ class S2VT(nn.Module):
             return _G.greedy_decode(self, feats, self.sos_ix, sample=sample)
         return None
 
-    def _forward_stacked(self, feats, targets, mode, sample=None, ss=(0.0, None, None)):
+    def _forward_stacked(self, feats, targets, mode, sample=None, ss=(0.0, None, None), drop_feats=True):
         """nn.LSTM with num_layers > 1: the layer-wavefront chain kernels under autograd glue (stack_functional.py)"""
         if mode == 'beam_search':
             raise NotImplementedError("beam search of a stacked model (num_layers > 1): the reference's BeamSearchNode views the "
@@ -211,7 +240,7 @@ class S2VT(nn.Module):
             raise NotImplementedError("mode='score' of a stacked model (num_layers > 1): the scoring driver's word step is the "
                                       "one-layer LSTM's; take the logits of mode='train' and log_softmax(...).gather(...) them")
         clean = feats                                      # (the scheduled pass runs without dropout)
-        feats = self.feat_drop(feats)                      # S2VTModel.py:52
+        feats = self.feat_drop(feats) if drop_feats else feats      # S2VTModel.py:52 (drop_feats False: the caller drew it)
         if mode == 'train':
             if targets is None:
                 raise ValueError("mode='train' needs targets")

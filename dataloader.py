@@ -24,7 +24,7 @@ device = torch.device('cuda' if torch.cuda.is_available() else 'cpu')
 
 
 class VideoDataset(Dataset):
-    def __init__(self, captions_file, feat_path, max_len=80, mode='train', device_items=False):
+    def __init__(self, captions_file, feat_path, max_len=80, mode='train', device_items=False, captions_per_clip=1):
         with open(captions_file, encoding='utf-8') as f:
             data = json.load(f)
             self.word2ix = data['word2ix']
@@ -35,12 +35,19 @@ class VideoDataset(Dataset):
         self.feat_paths = [p for p in plb.Path(feat_path).glob('*.npy') if p.stem in keep]
         self.max_len = max_len
         self.device_items = device_items
+        # K > 1 (not in the reference): an item carries K captions of its clip, drawn by K successive draws of the rule below (with
+        # replacement, as K items of the same clip would draw them); pad_label and mask are then [K, max_len].  1: the reference's item
+        self.captions_per_clip = int(captions_per_clip)
+        if self.captions_per_clip < 1:
+            raise ValueError("captions_per_clip must be at least 1, got %r" % (captions_per_clip,))
         print("prepare {} dataset. vocab_size: {}, dataset_size: {}".format(mode, len(self.word2ix), len(self.feat_paths)))
 
     def __getitem__(self, index):
         ID = self.feat_paths[index].stem
         feat = torch.from_numpy(np.load(str(self.feat_paths[index]), mmap_mode='r').astype(np.float32, copy=True))
         labels = self.captions[ID]
+        if self.captions_per_clip > 1:
+            return self._item_of_k_captions(feat, labels, ID)
         label = labels[int(np.random.randint(0, len(labels), size=1)[0])]      # == np.random.choice(labels, 1)[0]
         if len(label) > self.max_len:
             label = label[:self.max_len]
@@ -49,6 +56,21 @@ class VideoDataset(Dataset):
         mask = torch.zeros([self.max_len], dtype=torch.float)
         mask[:len(label)] = 1
         if self.device_items:       # the reference's per-item device tensors (feat is a leaf requiring grad there)
+            feat = feat.to(device).requires_grad_(True)
+            pad_label, mask = pad_label.to(device), mask.to(device)
+        return feat, pad_label, ID, mask
+
+    def _item_of_k_captions(self, feat, labels, ID):
+        K = self.captions_per_clip
+        pad_label = torch.zeros([K, self.max_len], dtype=torch.long)
+        mask = torch.zeros([K, self.max_len], dtype=torch.float)
+        for k in range(K):
+            label = labels[int(np.random.randint(0, len(labels), size=1)[0])]
+            if len(label) > self.max_len:
+                label = label[:self.max_len]
+            pad_label[k, :len(label)] = torch.tensor(label, dtype=torch.long)
+            mask[k, :len(label)] = 1
+        if self.device_items:
             feat = feat.to(device).requires_grad_(True)
             pad_label, mask = pad_label.to(device), mask.to(device)
         return feat, pad_label, ID, mask

@@ -97,6 +97,25 @@ int s2vt_train_forward_dropout(const s2vt_dims* d, const s2vt_params* p, const f
                                int64_t targets_ld, const float* out_mask, float* logits, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* mode='train' on K captions per clip with ONE encode per clip (not in the reference; additive, ABI 9).
+ *   feats [B, L, F]; targets int64 [B, K, L-1] at b * stride_b + k * stride_k + j (either stride may be 0: an expanded view);
+ *   logits [B, K, L-1, V] out = those of s2vt_train_forward on the clips repeated K times, row r = b * K + k.
+ *   out_mask: NULL, or the out_drop mask [(L-1)*B*K, H] TIME-MAJOR (row j*B*K + r), entries 0 or 1/(1-p); the backward gets the same.
+ * The backward writes the 13 parameter gradients of that repeated call and, if dfeats != NULL, dfeats [B, L, F] = the repeated
+ * call's dfeats summed over each clip's K rows; K is the forward's.  The feature projection, vid_rnn and word_rnn's L encode steps
+ * run once per clip in both directions; the gradients arriving at them are summed over a clip's K rows in a fixed order
+ * (s2vt_group_sum_rows), so a step is bitwise reproducible.  Launches per timestep on the fp32-input MFMA in every gemm mode.
+ * Workspace, errors and gradient-group events (s2vt_backward_wait_grads) as for s2vt_train_forward / s2vt_train_backward: a target id
+ * outside [0, V) is clamped and reported as S2VT_ERR_INDEX by s2vt_check_async_error / the next call; a backward on a workspace no
+ * grouped forward filled, or a second backward on one forward, is refused.  Shapes whose row or element counts overflow what the
+ * GEMMs index are refused on the host (S2VT_ERR_ARG; the size query returns 0 for them, for invalid dims and for K < 1). */
+size_t s2vt_train_group_workspace_bytes(const s2vt_dims* d, int32_t K);
+int s2vt_train_group_forward(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t stride_b,
+                             int64_t stride_k, int32_t K, const float* out_mask, float* logits, void* workspace, size_t workspace_bytes,
+                             void* stream);
+int s2vt_train_group_backward(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits, const float* out_mask,
+                              const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Device-side errors are asynchronous: a target id outside [0, V) (the reference's nn.Embedding raises IndexError,
  * S2VTModel.py:71) or a timed-out hand-off of the persistent recurrence raise a flag that every s2vt_train_forward
  * copies to the host at its end.  The NEXT s2vt_train_forward / s2vt_train_backward that finds the copy complete returns
@@ -440,6 +459,11 @@ int s2vt_embedding_grad(const float* d_rows, int64_t rows, int32_t E, const int3
                         size_t ws_ints, void* stream);
 /* out[r, 0:cols] = src[idx[r], 0:cols] (src rows of stride ld, out contiguous); rows <= 65535. */
 int s2vt_gather_rows(const float* src, int64_t ld, const int32_t* idx, int64_t rows, int32_t cols, float* out, void* stream);
+/* out[g*ld_out + c] = in[(g*K + 0)*ld_in + c] + in[(g*K + 1)*ld_in + c] + ... + in[(g*K + K-1)*ld_in + c] for g < groups, c < cols:
+ * fp32 adds in exactly that order, no atomics (bit-reproducible); 16-byte accesses where both row images are 16-byte aligned, any
+ * cols >= 1; nothing outside [groups, cols] of out is written; out must not overlap in.  The grouped train backward's sum of a
+ * clip's K caption rows (s2vt_train_group_backward: the decode steps' gate gradients, the carried cell gradient). */
+int s2vt_group_sum_rows(const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t groups, int32_t K, int32_t cols, void* stream);
 /* out[cols][rows] = in[rows][cols]^T, both contiguous. */
 int s2vt_transpose_f32(const float* in, int32_t rows, int32_t cols, float* out, void* stream);
 /* out[c] (+)= sum_r x[r*ld + c] in a fixed order: partial sums over 64-row chunks into ws[chunk*cols + c]

@@ -67,6 +67,11 @@ SIGNATURES = {
                                              c_void_p, c_size_t, c_void_p]),
     "s2vt_train_backward_dropout": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_void_p, POINTER(Grads),
                                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "s2vt_train_group_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
+    "s2vt_train_group_forward": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p,
+                                           c_void_p, c_size_t, c_void_p]),
+    "s2vt_train_group_backward": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_void_p, POINTER(Grads), c_void_p,
+                                            c_void_p, c_size_t, c_void_p]),
     "s2vt_check_async_error": (c_int32, [c_int32]),
     "s2vt_train_backward": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, POINTER(Grads), c_void_p,
                                       c_void_p, c_size_t, c_void_p]),
@@ -123,6 +128,7 @@ SIGNATURES = {
     "s2vt_embedding_grad_ws_ints": (c_size_t, [c_int64, c_int32]),
     "s2vt_embedding_grad": (c_int32, [c_void_p, c_int64, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_gather_rows": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p]),
+    "s2vt_group_sum_rows": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p]),
     "s2vt_transpose_f32": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "s2vt_colsum": (c_int32, [c_void_p, c_int64, c_int32, c_int64, c_void_p, c_size_t, c_void_p, c_int32, c_void_p]),
     "s2vt_colsum_finish": (c_int32, [c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p]),

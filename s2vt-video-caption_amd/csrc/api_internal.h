@@ -2,13 +2,14 @@
 //   api_runtime.hip  errors, asynchronous device-side errors, live timing, launch-sequence capture, the side stream, setters
 //   api_shared.hip   plane-operand helpers (split / GEMM wrappers), the drivers' lane frame and shared prologues, recurrence loops, argument builders
 //   api_train.hip    s2vt_train_forward / s2vt_train_backward (+ dropout, fused criterion backward, gradient-group events)
+//   api_train_group.hip  s2vt_train_group_forward / _backward: mode='train' on K captions per clip, one encode per clip
 //   api_decode.hip   greedy / sampled / scheduled decode and the encode phase for the beam search (DecodeDriver: one function per
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
 //   api_score.hip    teacher-forced caption scoring (S2VT.forward(mode='score'))
 //   api_sample_rows.hip  K sampled captions per clip on one encode (S2VT.sample)
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
-// Host code only; every kernel lives in gemm* / lstm* / ce / misc / split / argmax_x3 / beam_queue / beam_cum.hip.
+// Host code only; every kernel lives in gemm* / lstm* / ce / misc / group / split / argmax_x3 / beam_queue / beam_cum.hip.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>
@@ -272,6 +273,12 @@ SeqFwdBf16Args persist_fwd_args(int t0, int t1, int B, int H, float* gx_stash, i
                                 float* h_all, float* c_all, unsigned int* sync, int* err);
 SeqBwdBf16Args seq_bwd_bf16_args(int T, int t0, int t1, int B, int H, const PB& wt, const PB& dgb, const float* dh_out, int dh_first,
                                  const float* c_all, float* stash_dg, float* dc, unsigned int* sync, int* err);
+
+// ------------------------------------------------------------------ api_train.hip (shared with the grouped train driver, api_train_group.hip)
+// "gradient group `group` is final behind everything enqueued on s" of the backward that is being enqueued (s2vt_backward_wait_grads:
+// 0 = out_linear, 1 = word_rnn + embedding); backward_order_reset() at the start of every backward (s2vt_backward_order)
+int grads_ready(int group, hipStream_t s);
+void backward_order_reset();
 
 // ------------------------------------------------------------------ sampling arguments (api_decode.hip, api_ops.hip)
 // finite and > 0 with a finite reciprocal - what the kernels multiply by: NaN fails the compares, inf gives 0, a subnormal gives inf

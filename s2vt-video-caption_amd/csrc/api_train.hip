@@ -95,7 +95,8 @@ static bool g_grad_ev_set[2] = {false, false};
 // resident, so the event that releases the out_linear all-reduce (group 0) must have been recorded LAST behind the last such
 // launch of the backward - g_bwd_group0_after = persistent BPTT launches enqueued when group 0's event was last recorded
 static int g_bwd_persist_launches = 0, g_bwd_group0_after = 0;
-static int grads_ready(int group, hipStream_t s) {
+void backward_order_reset() { g_bwd_persist_launches = g_bwd_group0_after = 0; }
+int grads_ready(int group, hipStream_t s) {
     if (group == 0) {
         g_bwd_group0_after = g_bwd_persist_launches;
         cu_reserve_window(true);         // from here on a collective's kernels may hold compute units beside this backward's GEMMs
@@ -943,8 +944,7 @@ int s2vt_train_forward_dropout(const s2vt_dims* d, const s2vt_params* p, const f
 static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                                const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream,
                                const float* out_mask) {
-    g_bwd_persist_launches = 0;          // (s2vt_backward_order describes THIS backward, whichever driver it takes)
-    g_bwd_group0_after = 0;
+    backward_order_reset();              // (s2vt_backward_order describes THIS backward, whichever driver it takes)
     struct ReserveWindow {               // option cu_reserve: off until gradient group 0 is released, off again when the backward is enqueued
         ReserveWindow() { cu_reserve_window(false); }
         ~ReserveWindow() { cu_reserve_window(false); }

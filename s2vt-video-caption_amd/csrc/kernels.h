@@ -354,6 +354,16 @@ int fill_zero(hipStream_t s, void* p, size_t bytes);
 int occupy_cus(hipStream_t s, int workgroups, int lds_bytes, long long microseconds);   // test support (co-residency tests)
 int zero_pad_cols_u16(hipStream_t s, unsigned short* p, int64_t rows, int64_t ld, int col0, int col1);
 
+// ---- group.hip: a clip's K caption rows r = g * K + k against the clip's one row g (api_train_group.hip)
+// out[g][c] = in[g*K][c] + in[g*K+1][c] + ... + in[g*K+K-1][c], fp32 adds in exactly that order (no atomics: bit-reproducible)
+int group_sum_rows(hipStream_t s, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t groups, int K, int cols);
+// out[g*K+k][c] (+)= in[g][c]
+int group_expand_rows(hipStream_t s, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t groups, int K, int cols,
+                      bool accumulate);
+// caps[b][k][j] (strides stride_b, stride_k, 1; either may be 0) -> tok[j * B*K + b*K + k]; ids outside [0, V) clamped, *err_flag raised
+int group_tokens(hipStream_t s, const int64_t* caps, int64_t stride_b, int64_t stride_k, int B, int K, int S, int V, int32_t* tok,
+                 int* err_flag);
+
 // ---- ce.hip
 int mean_ce_fwd(hipStream_t s, const float* logits, int64_t rows, int V, const int64_t* target, int Lm1, int64_t ldt,
                 float* lse, float* rowloss, float* loss_out, int* err_flag);

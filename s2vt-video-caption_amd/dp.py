@@ -212,20 +212,29 @@ def global_mean(total, count, device="cpu"):
     return float(t[0] / torch.clamp(t[1], min=1.0))
 
 
-def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False, forward_kwargs=None):
+def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False, forward_kwargs=None, group=None):
     """One optimisation step of train.py:116-127 on this rank's shard; returns the (local) loss tensor.
     With `reducer`, gradients are averaged over ranks before the optimiser step.
     `check_errors`: synchronise and raise device-side errors of this step (a caption id outside the vocabulary -> IndexError, as
     nn.Embedding raises in the reference's forward; a timed-out hand-off) BEFORE optimizer.step(), so that a bad batch never
     reaches the weights - what the reference's ordering gives for free.  Costs one synchronisation per step; a loop that reads
     loss.item() every step (train.py:127) pays that anyway.
-    `forward_kwargs`: further keywords of the model's forward (scheduled sampling: ss_prob, ss_temperature)."""
+    `forward_kwargs`: further keywords of the model's forward (scheduled sampling: ss_prob, ss_temperature).
+    `group` = K: K captions per clip on one encode per clip - feats is [B, ...] and caps / mask (or the criterion's weights) are
+    [B*K, ...] with row b*K + k the k-th caption of clip b, exactly the rows of the step on feats.repeat_interleave(K, 0), whose
+    loss and gradients this step computes (S2VT.forward with 3-D targets).  None (default): one caption per row of feats."""
     if reducer is not None:
         reducer.zero_grad()
     else:
         optimizer.zero_grad()
     model.train()
-    probs = model(feats, targets=caps[:, :-1], mode='train', **(forward_kwargs or {}))
+    if group is None:
+        probs = model(feats, targets=caps[:, :-1], mode='train', **(forward_kwargs or {}))
+    else:
+        K = int(group)
+        if K < 1 or caps.shape[0] != feats.shape[0] * K:
+            raise ValueError("group=%r: caps must have B*K = %d*%d rows, got %d" % (group, feats.shape[0], K, caps.shape[0]))
+        probs = model(feats, targets=caps[:, :-1].unflatten(0, (feats.shape[0], K)), mode='train', **(forward_kwargs or {})).flatten(0, 1)
     loss = criterion(probs, caps, mask)
     loss.backward()
     if reducer is not None:

@@ -169,6 +169,96 @@ def train_forward(feats, targets, params, grad_sink=None, out_mask=None):
     return _TrainForward.apply(feats, targets, grad_sink, out_mask, *params)
 
 
+def group_targets(targets, B, Lm1):
+    """targets of a grouped train forward as the library reads them: int64 [B, K, L-1] with unit stride along the words (the clip and
+    caption strides are passed as they are, so an expanded view is not copied), or ValueError"""
+    require_hip(targets, "targets")
+    if targets.dim() != 3:
+        raise ValueError("grouped targets must be 3-D [B, K, L-1], got %s" % (tuple(targets.shape),))
+    if targets.shape[0] != B or targets.shape[2] != Lm1 or targets.shape[1] < 1:
+        raise ValueError("targets must be [B, K, L-1] = [%d, K >= 1, %d], got %s" % (B, Lm1, tuple(targets.shape)))
+    if targets.dtype != torch.int64:
+        targets = targets.long()
+    if targets.stride(2) != 1 or targets.stride(0) < 0 or targets.stride(1) < 0:
+        targets = targets.contiguous()
+    return targets
+
+
+class _TrainForwardGroup(torch.autograd.Function):
+    """_TrainForward on K captions per clip with one encode per clip (s2vt_train_group_forward / _backward)"""
+
+    @staticmethod
+    def forward(ctx, feats, targets, grad_sink, out_mask, *params):
+        lib = capi.load()
+        feats = _f32c(feats, "feats")
+        params = tuple(_f32c(p, "parameter") for p in params)
+        d = _dims(feats, params)
+        targets = group_targets(targets, d.B, d.L - 1)
+        K = targets.shape[1]
+        dev = feats.device
+        with torch.cuda.device(dev):
+            nbytes = lib.s2vt_train_group_workspace_bytes(ctypes.byref(d), K)
+            if nbytes == 0:
+                raise capi.S2VTHipError("grouped train forward: B = %d, K = %d, L = %d is not a shape the driver takes (row or "
+                                        "element counts overflow what its GEMMs index)" % (d.B, K, d.L))
+            if out_mask is not None:      # out_dropout > 0: mask [(L-1)*B*K, H] time-major, entries 0 or 1/(1-p)
+                out_mask = _f32c(out_mask, "out_mask")
+                if tuple(out_mask.shape) != ((d.L - 1) * d.B * K, d.H):
+                    raise ValueError("out_mask must be [(L-1)*B*K, H] = [%d, %d], got %s"
+                                     % ((d.L - 1) * d.B * K, d.H, tuple(out_mask.shape)))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            logits = torch.empty(d.B, K, d.L - 1, d.V, dtype=torch.float32, device=dev)
+            ps = _params_struct(capi.Params, params)
+            capi.check(lib.s2vt_train_group_forward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(targets), targets.stride(0),
+                                                    targets.stride(1), K, _ptr(out_mask), _ptr(logits), _ptr(ws), nbytes, _stream(dev)),
+                       "s2vt_train_group_forward")
+        ctx.out_mask = out_mask
+        ctx.save_for_backward(feats, *params)
+        ctx.ws, ctx.d, ctx.used, ctx.grad_sink = ws, d, False, grad_sink
+        ctx.dlog_fused = False
+        ctx.fusable = False           # (the fused criterion backward writes a plane-driver workspace: not this one)
+        return logits
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        if ctx.used:
+            raise capi.S2VTHipError("S2VT backward ran twice on one forward: the saved activations are consumed "
+                                    "in place (retain_graph is not supported)")
+        ctx.used = True
+        lib = capi.load()
+        feats, *params = ctx.saved_tensors
+        d, ws = ctx.d, ctx.ws
+        dev = feats.device
+        dlogits = _f32c(dlogits, "dlogits")
+        with torch.cuda.device(dev):
+            sink = ctx.grad_sink
+            if sink is not None:          # data-parallel mode: see _TrainForward.backward
+                if len(sink) != len(params) or any(g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous()
+                                                   or g.device != p.device for g, p in zip(sink, params)):
+                    raise capi.S2VTHipError("gradient sink does not match the 13 S2VT parameters")
+                grads = list(sink)
+            else:
+                grads = [torch.empty_like(p) for p in params]
+            dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
+            ps = _params_struct(capi.Params, params)
+            gs = _params_struct(capi.Grads, grads)
+            capi.check(lib.s2vt_train_group_backward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(dlogits), _ptr(ctx.out_mask),
+                                                     ctypes.byref(gs), _ptr(dfeats), _ptr(ws), ws.numel(), _stream(dev)),
+                       "s2vt_train_group_backward")
+        ctx.ws = None
+        if sink is not None:
+            return (dfeats, None, None, None) + (None,) * len(params)
+        return (dfeats, None, None, None) + tuple(grads)
+
+
+def train_forward_group(feats, targets, params, grad_sink=None, out_mask=None):
+    """logits [B, K, L-1, V] of S2VT.forward(mode='train') on K captions per clip, targets int64 [B, K, L-1] (any strides): those of
+    train_forward(feats.repeat_interleave(K, 0), targets.reshape(B*K, L-1)), with every clip encoded once.  The backward gives that
+    repeated call's parameter gradients and dfeats [B, L, F] = its dfeats summed over each clip's K rows.  `grad_sink` as for
+    train_forward; `out_mask`: the out_drop mask as [(L-1)*B*K, H] time-major (row j*B*K + b*K + k), None = no dropout."""
+    return _TrainForwardGroup.apply(feats, targets, grad_sink, out_mask, *params)
+
+
 # Weight-derived images of the decode (plane images of four weight matrices, the per-token gate-input table) kept between
 # mode='test' calls of one model while its parameters stand: key = every parameter's (data_ptr, _version) + dims + library
 # modes + stream.  In-place updates through autograd-visible ops (optimizers, load_state_dict, .to()) change the key; writes

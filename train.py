@@ -73,6 +73,14 @@ def parse(argv=None):
                     help="what a sampled caption's reward is compared with.  greedy: the reward of the clip's greedy caption (SCST, "
                          "Rennie et al. 2017).  mean: the mean reward of the clip's other K - 1 samples (Luo 2020) - no greedy "
                          "decode runs; needs --sc-samples >= 2")
+    ap.add_argument("--sc-shared-encode", action="store_true",
+                    help="the train step of a --self-critical step with --sc-samples K encodes every clip once (S2VT.forward with "
+                         "3-D targets: dp.train_step(group=K)) instead of running on the clips repeated K times.  Same loss and "
+                         "gradients; which is faster depends on the shapes (profiles/train_group.txt), so it is opt-in")
+    ap.add_argument("--captions-per-clip", type=int, default=1, metavar="K",
+                    help="cross-entropy training on K reference captions of every clip per step (dataloader.VideoDataset("
+                         "captions_per_clip=K)), the clip encoded once; the loss is MaskCriterion over the B*K captions.  1 "
+                         "(default): the reference's one caption per clip.  Validation stays one caption")
     ap.add_argument("--init-state", default=None, help="state_dict file to start from instead of the seeded default init")
     ap.add_argument("--scheduled-sampling-start", type=int, default=-1, metavar="E",
                     help="scheduled sampling (Bengio et al., 2015) from epoch E on: each decode-step input of a training step is, with "
@@ -92,6 +100,17 @@ def parse(argv=None):
         ap.error("--sc-samples must be at least 1")
     if opt.sc_baseline == "mean" and opt.sc_samples < 2:
         ap.error("--sc-baseline mean needs --sc-samples >= 2 (the mean of the other K - 1 samples)")
+    if opt.sc_shared_encode and not opt.self_critical:
+        ap.error("--sc-shared-encode needs --self-critical")
+    if opt.captions_per_clip < 1:
+        ap.error("--captions-per-clip must be at least 1")
+    if opt.captions_per_clip > 1:
+        if opt.self_critical:
+            ap.error("--captions-per-clip applies to cross-entropy training (--self-critical samples its captions: --sc-samples)")
+        if opt.model == "att_baseline":
+            ap.error("--captions-per-clip needs --model s2vt (Att_Baseline takes one caption per clip)")
+        if opt.scheduled_sampling_start >= 0:
+            ap.error("--captions-per-clip cannot be combined with scheduled sampling (--scheduled-sampling-start)")
     if opt.scheduled_sampling_start >= 0:
         if opt.self_critical:
             ap.error("--scheduled-sampling-start cannot be combined with --self-critical (it is the stage before it)")
@@ -115,7 +134,7 @@ def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
-                            reducer=None, samples=1, baseline="greedy"):
+                            reducer=None, shared_encode=False, samples=1, baseline="greedy"):
     """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
     train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
     (every phase ends with a device synchronisation), hist["reward_sample"] / ["reward_greedy"] the batch means.  sc_reward
@@ -124,7 +143,9 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
     samples = K > 1 (or baseline "mean"): K captions per clip from model.sample (one encode per clip), rewards over the B*K rows,
     each row's reward compared with its clip's greedy reward (baseline "greedy") or with the mean reward of the clip's other K - 1
     rows (baseline "mean": no greedy decode runs, sc_split_ms["greedy"] stays 0 and hist["reward_greedy"] empty), then the train step
-    on the clips repeated K times with the B*K captions.  hist["reward_baseline"] gets the batch mean of the baselines."""
+    on the clips repeated K times with the B*K captions - or, with shared_encode, on the clips as they are with K captions each
+    (dp.train_step(group=K): one encode per clip, same loss and gradients).  hist["reward_baseline"] gets the batch mean of the
+    baselines."""
     from s2vt_video_caption_amd import dp, ops
     from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages
     K = int(samples)
@@ -162,7 +183,10 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
             caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
             means = [float(r_s.mean()), float(base.mean())] + ([float(r_g.mean())] if r_g is not None else [])
         t3 = time.perf_counter()
-        loss = dp.train_step(model, reward_criterion, optimizer, feats.repeat_interleave(K, 0), caps, weight, reducer, check_errors=True)
+        if shared_encode:
+            loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, group=K)
+        else:
+            loss = dp.train_step(model, reward_criterion, optimizer, feats.repeat_interleave(K, 0), caps, weight, reducer, check_errors=True)
         t4 = time.perf_counter()
         for k, v in (("sample", t1 - t0), ("greedy", t2 - t1 if greedy is not None else 0.0), ("scoring", t3 - t2), ("train", t4 - t3)):
             sp[k] += 1e3 * v
@@ -173,7 +197,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
             hist["reward_greedy"].append(means[2])
         return loss
 
-    if K > 1 or baseline == "mean":
+    if K > 1 or baseline == "mean":           # (K = 1: the steps below run on the clips as they are - nothing to share)
         return group_step
 
     def host_step(feats, ids):
@@ -256,7 +280,11 @@ def run(opt):
     if rank == 0:                                           # the run's configuration beside its checkpoints (save_opt, train.py:51-53)
         with open(os.path.join(opt.save_path, start_time + 'opt.txt'), 'w+', encoding='utf-8') as f:
             f.write(str(vars(opt)))
-    trainset = dataloader.VideoDataset(opt.caption_file, opt.feats_path, max_len=opt.train_length)
+    cpc = opt.captions_per_clip
+    if cpc > 1:
+        trainset = dataloader.VideoDataset(opt.caption_file, opt.feats_path, max_len=opt.train_length, captions_per_clip=cpc)
+    else:
+        trainset = dataloader.VideoDataset(opt.caption_file, opt.feats_path, max_len=opt.train_length)
     validset = dataloader.VideoDataset(opt.caption_file, opt.feats_path, max_len=opt.train_length, mode='valid')
     shuffle = not opt.no_shuffle
     sampler = torch.utils.data.distributed.DistributedSampler(trainset, shuffle=shuffle, drop_last=True) if world > 1 else None
@@ -321,7 +349,8 @@ def run(opt):
 
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
-                                                     opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline)
+                                                     opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline,
+                                                     shared_encode=opt.sc_shared_encode)
 
     def save(name):
         if rank == 0:
@@ -344,6 +373,9 @@ def run(opt):
             # is raised BEFORE optimizer.step(), as in the reference, whose nn.Embedding raises in the forward
             if rewarder is not None:
                 loss = self_critical_step(feats, ids)
+            elif cpc > 1:       # targets / masks [B, K, L]: row b*K + k of the step = caption k of clip b, the clip encoded once
+                loss = dp.train_step(model, criterion, optimizer, feats, targets.flatten(0, 1), masks.flatten(0, 1), reducer,
+                                     check_errors=True, group=cpc)
             else:
                 loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True,
                                      forward_kwargs=ss_kwargs)
