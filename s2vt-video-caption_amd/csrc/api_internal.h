@@ -1,8 +1,9 @@
 // Host-side internals shared by the C-ABI units of libs2vt_hip.so:
 //   api_runtime.hip  errors, asynchronous device-side errors, live timing, launch-sequence capture, the side stream, setters
 //   api_shared.hip   plane-operand helpers (split / GEMM wrappers), the drivers' lane frame and shared prologues, recurrence loops, argument builders
-//   api_train.hip    s2vt_train_forward / s2vt_train_backward (+ dropout, fused criterion backward, gradient-group events)
-//   api_train_group.hip  s2vt_train_group_forward / _backward: mode='train' on K captions per clip, one encode per clip
+//   api_train.hip    s2vt_train_forward / s2vt_train_backward (+ dropout, fused criterion backward, gradient-group events): the plane drivers
+//   api_train_f32.hip  the fp32-MFMA launch-per-timestep train driver, plain (behind s2vt_train_forward / _backward) and grouped
+//                    (s2vt_train_group_forward / _backward: mode='train' on K captions per clip, one encode per clip)
 //   api_decode.hip   greedy / sampled / scheduled decode and the encode phase for the beam search (DecodeDriver: one function per
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
@@ -274,11 +275,71 @@ SeqFwdBf16Args persist_fwd_args(int t0, int t1, int B, int H, float* gx_stash, i
 SeqBwdBf16Args seq_bwd_bf16_args(int T, int t0, int t1, int B, int H, const PB& wt, const PB& dgb, const float* dh_out, int dh_first,
                                  const float* c_all, float* stash_dg, float* dc, unsigned int* sync, int* err);
 
-// ------------------------------------------------------------------ api_train.hip (shared with the grouped train driver, api_train_group.hip)
+// ------------------------------------------------------------------ api_train.hip (shared with the fp32 train driver, api_train_f32.hip)
 // "gradient group `group` is final behind everything enqueued on s" of the backward that is being enqueued (s2vt_backward_wait_grads:
 // 0 = out_linear, 1 = word_rnn + embedding); backward_order_reset() at the start of every backward (s2vt_backward_order)
 int grads_ready(int group, hipStream_t s);
 void backward_order_reset();
+// Every backward entry point opens with one: s2vt_backward_order describes THIS backward, whichever driver it takes, and option
+// cu_reserve is off until gradient group 0 is released and off again when the backward is enqueued
+struct BackwardScope {
+    BackwardScope() { backward_order_reset(); cu_reserve_window(false); }
+    ~BackwardScope() { cu_reserve_window(false); }
+};
+
+// What a forward left in its workspace, keyed by the workspace: its backward takes the record and refuses a workspace no forward
+// filled.  Forwards that never ran a backward (validation, forward-only tools) leave theirs behind: above 64 the OLDEST goes, never
+// one of a forward still awaiting its backward.  Host-side only; the mutex because autograd runs the backward on its own thread.
+template <typename Rec> class RecordTable {
+    struct Slot { Rec rec; unsigned long long seq; };
+    std::map<const void*, Slot> slots;
+    std::mutex mutex;
+    unsigned long long seq = 0;
+public:
+    void put(const void* ws, const Rec& rec) {
+        std::lock_guard<std::mutex> lock(mutex);
+        if (slots.size() >= 64 && !slots.count(ws)) {
+            auto oldest = slots.begin();
+            for (auto it = slots.begin(); it != slots.end(); ++it)
+                if (it->second.seq < oldest->second.seq) oldest = it;
+            slots.erase(oldest);
+        }
+        slots[ws] = Slot{rec, ++seq};
+    }
+    // find + erase
+    bool take(const void* ws, Rec* out) {
+        std::lock_guard<std::mutex> lock(mutex);
+        auto it = slots.find(ws);
+        if (it == slots.end()) return false;
+        *out = it->second.rec;
+        slots.erase(it);
+        return true;
+    }
+    // f(record) under the lock, its answer handed on; false where the workspace has no record
+    template <typename F> bool with(const void* ws, F f) {
+        std::lock_guard<std::mutex> lock(mutex);
+        auto it = slots.find(ws);
+        return it != slots.end() && f(it->second.rec);
+    }
+};
+
+// The buffers of a train workspace that the fp32-MFMA driver works with (time-major images; layer 1 = vid_rnn, 2 = word_rnn): the
+// head of TrainWS (api_train.hip, shared with the plane drivers) and of the grouped workspace (api_train_f32.hip)
+struct TrainBufs {
+    float *bsum1, *bsum2, *x1, *s1, *h1, *c1, *s2, *h2, *c2;
+    float *wt1, *wt2, *dh1, *dh2dec, *dx1, *de, *dc1, *dc2, *colsum_a, *colsum_b, *gws_a, *gws_b;
+    size_t gws_floats;
+    int32_t* tok;
+    int* embws;              // embedding_grad scratch (heavy-token list)
+    int* err;                // [0] target id out of range, [1] persistent-recurrence hand-off timed out
+};
+
+// ------------------------------------------------------------------ api_train_f32.hip
+// The launch-per-timestep fp32-MFMA driver (gemm mode 0, and batches the plane drivers do not take): fp32 operands read in place
+int train_forward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets, int64_t targets_ld,
+                      float* logits, const TrainBufs& w, hipStream_t st, const float* out_mask);
+int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits, const s2vt_grads* g,
+                       float* dfeats, const TrainBufs& w, hipStream_t st, const float* out_mask);
 
 // ------------------------------------------------------------------ sampling arguments (api_decode.hip, api_ops.hip)
 // finite and > 0 with a finite reciprocal - what the kernels multiply by: NaN fails the compares, inf gives 0, a subnormal gives inf

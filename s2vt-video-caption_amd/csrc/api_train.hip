@@ -1,18 +1,13 @@
 // s2vt_train_forward / s2vt_train_backward (S2VTModel.py:48-81 and its autograd; train.py:116-127): workspace carving, the
-// two-lane / persistent launch sequences of the plane drivers and of the fp32-MFMA driver, gradient-group events for the
-// data-parallel overlap, MaskCriterion's backward fused into the hand-over.
+// two-lane / persistent launch sequences of the plane drivers (the fp32-MFMA driver: api_train_f32.hip), gradient-group events
+// for the data-parallel overlap, MaskCriterion's backward fused into the hand-over.
 #include "api_internal.h"
 
 namespace s2vt {
 
-struct TrainWS {
-    float *bsum1, *bsum2, *x1, *s1, *h1, *c1, *s2, *h2, *c2;
-    float *wt1, *wt2, *dh1, *dh2dec, *dx1, *de, *dc1, *dc2, *colsum_a, *colsum_b, *colsum_c, *gws_a, *gws_b;
+struct TrainWS : TrainBufs {
+    float* colsum_c;
     float* ce_alpha;         // [1] mantissa of the mean-CE scale (bf16 mode, fused criterion backward: CeGradArgs::alpha_out)
-    size_t gws_floats;
-    int32_t* tok;
-    int* embws;              // embedding_grad scratch (heavy-token list)
-    int* err;                // [0] target id out of range, [1] persistent-recurrence hand-off timed out
     unsigned int *psync_a, *psync_b;     // hand-off counters of the persistent recurrence kernels (one block per lane)
     unsigned short *xw1, *xw2, *xh1, *xh2;   // split-precision persistent forward (lstm_persist_x3.hip): W_hh planes [3][4H][Kp],
     int64_t xkp;                             // h_t planes [3][T*B][Kp] per layer; Kp = H rounded up to 64 (0: H > 1024, no images)
@@ -141,29 +136,14 @@ static PlaneWS carve_planes(const s2vt_dims& d, int planes, void* base) {
 // What a forward was run with, keyed by its workspace: s2vt_train_backward must find the same arithmetic mode and
 // recurrence schedule (they decide how the workspace is carved and which images the forward left in it), otherwise it
 // refuses instead of reading a differently carved workspace.  Host-side only.
-struct FwdRecord { s2vt_dims d; int gemm_mode, planes, persist, blk; unsigned long long seq; bool dlog_ready; };
-static std::map<const void*, FwdRecord> g_fwd_records;
-static std::mutex g_fwd_mutex;          // autograd runs the backward on its own thread
-static unsigned long long g_fwd_seq = 0;
+struct FwdRecord { s2vt_dims d; int gemm_mode, planes, persist, blk; bool dlog_ready; };
+static RecordTable<FwdRecord> g_fwd_records;
 static void record_forward(const void* ws, const s2vt_dims& d, bool planes) {
-    std::lock_guard<std::mutex> lock(g_fwd_mutex);
-    if (g_fwd_records.size() >= 64 && !g_fwd_records.count(ws)) {     // forwards that never ran a backward (validation,
-        auto oldest = g_fwd_records.begin();                          // forward-only tools): the OLDEST record goes, never
-        for (auto it = g_fwd_records.begin(); it != g_fwd_records.end(); ++it)      // one of a forward still awaiting its backward
-            if (it->second.seq < oldest->second.seq) oldest = it;
-        g_fwd_records.erase(oldest);
-    }
-    g_fwd_records[ws] = FwdRecord{d, gemm_mode(), planes ? train_planes() : 0, persist_bits(), pipe_block(), ++g_fwd_seq, false};
+    g_fwd_records.put(ws, FwdRecord{d, gemm_mode(), planes ? train_planes() : 0, persist_bits(), pipe_block(), false});
 }
 static int check_forward_record(const void* ws, const s2vt_dims& d, bool planes, bool* dlog_ready = nullptr) {
     FwdRecord r;
-    {
-        std::lock_guard<std::mutex> lock(g_fwd_mutex);
-        auto it = g_fwd_records.find(ws);
-        S2VT_REQUIRE(it != g_fwd_records.end(), "s2vt_train_backward: no s2vt_train_forward has run on this workspace");
-        r = it->second;
-        g_fwd_records.erase(it);
-    }
+    S2VT_REQUIRE(g_fwd_records.take(ws, &r), "s2vt_train_backward: no s2vt_train_forward has run on this workspace");
     if (dlog_ready) *dlog_ready = r.dlog_ready;
     S2VT_REQUIRE(memcmp(&r.d, &d, sizeof(d)) == 0, "s2vt_train_backward: dims differ from the forward that filled this workspace");
     S2VT_REQUIRE(r.gemm_mode == gemm_mode() && r.planes == (planes ? train_planes() : 0) && r.persist == persist_bits() && r.blk == pipe_block(),
@@ -717,106 +697,6 @@ static int train_backward_x3(const s2vt_dims* d, const s2vt_params* p, const flo
     return x.hand(sx, st);
 }
 
-// The launch-per-timestep fp32-MFMA driver (gemm mode 0, and batches the plane drivers do not take): fp32 operands read in place
-static int train_forward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const int64_t* targets,
-                             int64_t targets_ld, float* logits, const TrainWS& w, hipStream_t st, const float* out_mask) {
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    Lanes x;
-    int rc;
-    if ((rc = x.open(st, w.gws_a, w.gws_b, w.gws_floats, w.colsum_a, w.colsum_b))) return rc;
-    const hipStream_t sx = x.sx;
-    const Lane &la = x.la, &lb = x.lb;        // la: vid_rnn lane (caller's stream), lb: word_rnn lane
-    if ((rc = bias_sums(st, p, H, w.bsum1, w.bsum2))) return rc;
-    if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
-    if ((rc = targets_to_time_major(st, targets, B, L - 1, targets_ld, V, w.tok, w.err))) return rc;
-    if ((rc = x.hand(st, sx))) return rc;
-    // lane B, independent of vid_rnn: embedded-word half of the word_rnn gate input (+ both biases) for the
-    // L-1 caption steps                                                             S2VTModel.py:71-75
-    if ((rc = lgemm(lb, true, true, (L - 1) * B, 4 * H, E, p->emb_w, E, gather(w.tok), p->word_w_ih, E + H, ID,
-                    w.s2 + (int64_t)L * B4H, 4 * H, ID, w.bsum2, false))) return rc;
-    if ((rc = project_features_f32(la, *d, p, feats, w.x1, w.s1, w.bsum1))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, pipe_block());
-    for (size_t k = 0; k + 1 < bd.size(); ++k) {
-        const int t0 = bd[k], t1 = bd[k + 1];
-        if ((rc = seq_fwd(st, t0, t1, B, H, w.s1, L, w.bsum1, p->vid_w_hh, w.h1, w.c1, true))) return rc;
-        if ((rc = x.hand(st, sx))) return rc;
-        // vid_out half of the word_rnn gate input for this block: rows < L get the biases here, rows >= L
-        // accumulate onto the embedded-word half                                    S2VTModel.py:75-77
-        const bool cap = t0 >= L;
-        if ((rc = lgemm(lb, true, true, (t1 - t0) * B, 4 * H, H, w.h1 + t0 * BH, H, ID, p->word_w_ih + E, E + H, ID,
-                        w.s2 + t0 * B4H, 4 * H, ID, cap ? nullptr : w.bsum2, cap))) return rc;
-        if ((rc = seq_fwd(sx, t0, t1, B, H, w.s2, T, w.bsum2, p->word_w_hh, w.h2, w.c2, true))) return rc;
-    }
-    // logits[b, j, :] = (out_drop mask (.)) h2[L + j]·W_o^T + b_o                    S2VTModel.py:78-80
-    const float* hdec = w.h2 + L * BH;
-    if (out_mask) {
-        if ((rc = mul_vectors(sx, hdec, out_mask, w.dh2dec, (int64_t)(L - 1) * B * H))) return rc;     // dh2dec: free in the forward
-        hdec = w.dh2dec;
-    }
-    if ((rc = lgemm(lb, true, true, (L - 1) * B, V, H, hdec, H, ID, p->out_w, H, ID, logits, V, perm(B, L - 1), p->out_b, false))) return rc;
-    return x.hand(sx, st);
-}
-
-static int train_backward_f32(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
-                              const s2vt_grads* g, float* dfeats, const TrainWS& w, hipStream_t st, const float* out_mask) {
-    const int B = d->B, L = d->L, F = d->F, H = d->H, E = d->E, V = d->V, T = 2 * L - 1, R = (L - 1) * B;
-    const int64_t BH = (int64_t)B * H, B4H = 4 * BH;
-    Lanes x;
-    int rc;
-    if ((rc = x.open(st, w.gws_a, w.gws_b, w.gws_floats, w.colsum_a, w.colsum_b))) return rc;
-    const hipStream_t sx = x.sx;
-    const Lane &la = x.la, &lb = x.lb;        // la: word_rnn lane (caller's stream), lb: vid_rnn lane
-    LaneDelayScope delay(st);
-    if ((rc = x.hand(st, sx))) return rc;
-    // lane A: gradient into the decode-step hidden states, then word_rnn BPTT       (autograd of S2VTModel.py:80, :77)
-    if ((rc = lgemm(la, true, false, R, H, V, dlogits, V, ID, p->out_w, H, ID, w.dh2dec, H, perm(L - 1, B), nullptr, false))) return rc;
-    if (out_mask && (rc = mul_vectors(st, w.dh2dec, out_mask, w.dh2dec, (int64_t)R * H))) return rc;      // autograd of out_drop
-    if ((rc = transpose_f32(st, p->word_w_hh, 4 * H, H, w.wt2))) return rc;
-    // lane B meanwhile: out_linear weight/bias gradients (need only dlogits and the (masked) h2) and W_hh1^T
-    const float* hdec = w.h2 + L * BH;
-    if (out_mask) {
-        if ((rc = mul_vectors(sx, hdec, out_mask, w.dx1, (int64_t)R * H))) return rc;      // dx1: free until the vid_rnn input gradient
-        hdec = w.dx1;
-    }
-    if ((rc = lgemm(lb, false, false, V, H, R, dlogits, V, ID, hdec, H, perm(L - 1, B), g->out_w, H, ID, nullptr, false))) return rc;
-    if ((rc = colsum_f32(sx, dlogits, R, V, V, lb.colsum, g->out_b, false))) return rc;
-    if ((rc = grads_ready(0, sx))) return rc;
-    if ((rc = transpose_f32(sx, p->vid_w_hh, 4 * H, H, w.wt1))) return rc;
-    const std::vector<int> bd = pipe_bounds(T, L, pipe_block());
-    for (size_t k = bd.size() - 1; k >= 1; --k) {
-        const int t0 = bd[k - 1], t1 = bd[k];
-        if ((rc = seq_bwd(st, T, t0, t1, B, H, w.wt2, w.dh2dec, L, w.c2, w.s2, w.dc2))) return rc;
-        // gradient into vid_out for this block: dh1 = dG2·W_v                        (autograd of :75)
-        if ((rc = lgemm(la, true, false, (t1 - t0) * B, H, 4 * H, w.s2 + t0 * B4H, 4 * H, ID, p->word_w_ih + E, E + H, ID,
-                        w.dh1 + t0 * BH, H, ID, nullptr, false))) return rc;
-        if ((rc = x.hand(st, sx))) return rc;
-        if ((rc = seq_bwd(sx, T, t0, t1, B, H, w.wt1, w.dh1, 0, w.c1, w.s1, w.dc1))) return rc;   // (autograd of :67)
-    }
-    // lane A: word_rnn parameter gradients + embedding gradient (run while lane B finishes the vid_rnn BPTT)
-    if ((rc = lgemm(la, false, false, 4 * H, H, (T - 1) * B, w.s2 + B4H, 4 * H, ID, w.h2, H, ID, g->word_w_hh, H, ID, nullptr, false))) return rc;
-    if ((rc = lgemm(la, false, false, 4 * H, H, T * B, w.s2, 4 * H, ID, w.h1, H, ID, g->word_w_ih + E, E + H, ID, nullptr, false))) return rc;
-    // dW_ih2[:, :E] = dG2[L..]^T · Emb[tok]: the embedded rows are gathered once (time-major) into w.de, which
-    // is free until the d(embedded words) GEMM below overwrites it
-    if ((rc = gather_rows_f32(st, p->emb_w, E, w.tok, R, E, w.de))) return rc;
-    if ((rc = lgemm(la, false, false, 4 * H, E, R, w.s2 + (int64_t)L * B4H, 4 * H, ID, w.de, E, ID, g->word_w_ih, E + H, ID, nullptr, false))) return rc;
-    if ((rc = colsum_f32(st, w.s2, (int64_t)T * B, 4 * H, 4 * H, la.colsum, g->word_b_ih, false))) return rc;
-    S2VT_HIP(hipMemcpyAsync(g->word_b_hh, g->word_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, st));
-    if ((rc = lgemm(la, true, false, R, E, 4 * H, w.s2 + (int64_t)L * B4H, 4 * H, ID, p->word_w_ih, E + H, ID, w.de, E, ID, nullptr, false))) return rc;
-    if ((rc = embedding_grad(st, w.de, R, E, w.tok, V, g->emb_w, w.embws))) return rc;
-    if ((rc = grads_ready(1, st))) return rc;
-    // lane B: vid_rnn and feat_linear parameter gradients                           (autograd of :67, :54)
-    if ((rc = lgemm(lb, false, false, 4 * H, H, (T - 1) * B, w.s1 + B4H, 4 * H, ID, w.h1, H, ID, g->vid_w_hh, H, ID, nullptr, false))) return rc;
-    if ((rc = lgemm(lb, false, false, 4 * H, H, L * B, w.s1, 4 * H, ID, w.x1, H, ID, g->vid_w_ih, H, ID, nullptr, false))) return rc;
-    if ((rc = colsum_f32(sx, w.s1, (int64_t)T * B, 4 * H, 4 * H, lb.colsum, g->vid_b_ih, false))) return rc;
-    S2VT_HIP(hipMemcpyAsync(g->vid_b_hh, g->vid_b_ih, sizeof(float) * 4 * H, hipMemcpyDeviceToDevice, sx));
-    if ((rc = lgemm(lb, true, false, L * B, H, 4 * H, w.s1, 4 * H, ID, p->vid_w_ih, H, ID, w.dx1, H, ID, nullptr, false))) return rc;
-    if ((rc = lgemm(lb, false, false, H, F, L * B, w.dx1, H, ID, feats, F, perm(B, L), g->feat_w, F, ID, nullptr, false))) return rc;
-    if ((rc = colsum_f32(sx, w.dx1, (int64_t)L * B, H, H, lb.colsum, g->feat_b, false))) return rc;
-    if (dfeats && (rc = lgemm(lb, true, false, L * B, F, H, w.dx1, H, ID, p->feat_w, F, ID, dfeats, F, perm(B, L), nullptr, false))) return rc;
-    return x.hand(sx, st);
-}
-
 }  // namespace s2vt
 
 using namespace s2vt;
@@ -944,11 +824,7 @@ int s2vt_train_forward_dropout(const s2vt_dims* d, const s2vt_params* p, const f
 static int train_backward_core(const s2vt_dims* d, const s2vt_params* p, const float* feats, const float* dlogits,
                                const s2vt_grads* g, float* dfeats, void* workspace, size_t workspace_bytes, void* stream,
                                const float* out_mask) {
-    backward_order_reset();              // (s2vt_backward_order describes THIS backward, whichever driver it takes)
-    struct ReserveWindow {               // option cu_reserve: off until gradient group 0 is released, off again when the backward is enqueued
-        ReserveWindow() { cu_reserve_window(false); }
-        ~ReserveWindow() { cu_reserve_window(false); }
-    } reserve_window;
+    BackwardScope scope;
     const TrainWS w = carve_train(*d, workspace);
     S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_train_backward: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t st = (hipStream_t)stream;
@@ -1028,13 +904,9 @@ int s2vt_mean_ce_backward_fused(const s2vt_dims* d, const float* logits, const i
     S2VT_REQUIRE(dims_ok(d) && logits && target && lse && gout && workspace, "s2vt_mean_ce_backward_fused: null/invalid argument");
     S2VT_REQUIRE(planes_ok(*d), "s2vt_mean_ce_backward_fused: the workspace is not a plane-driver workspace (B %% 64, gemm mode 1 or 3)");
     const TrainWS w = carve_train(*d, workspace);
-    {
-        std::lock_guard<std::mutex> lock(g_fwd_mutex);
-        auto it = g_fwd_records.find(workspace);
-        S2VT_REQUIRE(it != g_fwd_records.end() && memcmp(&it->second.d, d, sizeof(*d)) == 0 && it->second.gemm_mode == gemm_mode() &&
-                         !it->second.dlog_ready,
-                     "s2vt_mean_ce_backward_fused: no matching s2vt_train_forward has run on this workspace");
-    }
+    S2VT_REQUIRE(g_fwd_records.with(workspace, [&](const FwdRecord& r) {
+                     return memcmp(&r.d, d, sizeof(*d)) == 0 && r.gemm_mode == gemm_mode() && !r.dlog_ready;
+                 }), "s2vt_mean_ce_backward_fused: no matching s2vt_train_forward has run on this workspace");
     const PlaneWS q = carve_planes(*d, train_planes(), reinterpret_cast<char*>(workspace) + w.bytes);
     S2VT_REQUIRE(workspace_bytes >= w.bytes + q.bytes, "s2vt_mean_ce_backward_fused: workspace %zu < %zu bytes", workspace_bytes, w.bytes + q.bytes);
     const int R = (d->L - 1) * d->B, V = d->V;
@@ -1047,8 +919,7 @@ int s2vt_mean_ce_backward_fused(const s2vt_dims* d, const float* logits, const i
         ProfScope ps(st, K_CE, 1);
         if ((rc = split_planes_dual(st, q.dlog.planes, logits, V, ID, R, V, q.dlog.p, q.dlog.ld, q.dlog.kpad, nullptr, 0, 0, w.colsum_c, &ce))) return rc;
     }
-    std::lock_guard<std::mutex> lock(g_fwd_mutex);
-    g_fwd_records[workspace].dlog_ready = true;
+    g_fwd_records.with(workspace, [](FwdRecord& r) { return r.dlog_ready = true; });
     return 0;
 }
 

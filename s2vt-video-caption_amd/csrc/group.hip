@@ -1,4 +1,4 @@
-// Row-group helpers of the K-captions-per-clip train driver (api_train_group.hip): the caption rows r = g * K + k of a clip (or of
+// Row-group helpers of the K-captions-per-clip train driver (api_train_f32.hip): the caption rows r = g * K + k of a clip (or of
 // a (timestep, clip) pair of a time-major image: (t * B + b) * K + k) against the clip's one row g.
 //   group_sum_rows     out[g] = in[g*K] + in[g*K+1] + ... + in[g*K+K-1]: the gradients arriving at the shared encode
 //   group_expand_rows  out[g*K+k] (+)= in[g]: the clip's state / gate-input half handed to its K caption rows

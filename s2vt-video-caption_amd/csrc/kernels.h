@@ -354,7 +354,7 @@ int fill_zero(hipStream_t s, void* p, size_t bytes);
 int occupy_cus(hipStream_t s, int workgroups, int lds_bytes, long long microseconds);   // test support (co-residency tests)
 int zero_pad_cols_u16(hipStream_t s, unsigned short* p, int64_t rows, int64_t ld, int col0, int col1);
 
-// ---- group.hip: a clip's K caption rows r = g * K + k against the clip's one row g (api_train_group.hip)
+// ---- group.hip: a clip's K caption rows r = g * K + k against the clip's one row g (the grouped path of api_train_f32.hip)
 // out[g][c] = in[g*K][c] + in[g*K+1][c] + ... + in[g*K+K-1][c], fp32 adds in exactly that order (no atomics: bit-reproducible)
 int group_sum_rows(hipStream_t s, const float* in, int64_t ld_in, float* out, int64_t ld_out, int64_t groups, int K, int cols);
 // out[g*K+k][c] (+)= in[g][c]

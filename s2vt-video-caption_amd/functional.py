@@ -57,6 +57,48 @@ def _dims(feats, params):
     return capi.Dims(B, L, F, H, E, V)
 
 
+def _save_train_ctx(ctx, feats, params, ws, d, grad_sink, out_mask, fusable):
+    """what _train_backward, _fusable_train_node and _ce_backward read from the node of a train forward"""
+    ctx.out_mask = out_mask
+    ctx.save_for_backward(feats, *params)
+    ctx.ws, ctx.d, ctx.used, ctx.grad_sink = ws, d, False, grad_sink
+    ctx.dlog_fused = False      # set by _MeanCE.backward when it wrote the dlogits planes into ctx.ws itself (fused CE)
+    ctx.fusable = fusable
+
+
+def _train_backward(ctx, dlogits, call):
+    """The backward of a train forward node: `call(lib, d, ps, feats, dlogits, gs, dfeats, ws, stream)` runs the library's backward
+    (dlogits None: the fused criterion backward left it in the workspace)."""
+    if ctx.used:
+        raise capi.S2VTHipError("S2VT backward ran twice on one forward: the saved activations are consumed "
+                                "in place (retain_graph is not supported)")
+    ctx.used = True
+    lib = capi.load()
+    feats, *params = ctx.saved_tensors
+    dev = feats.device
+    if dlogits is not None:
+        dlogits = _f32c(dlogits, "dlogits")
+    with torch.cuda.device(dev):
+        sink = ctx.grad_sink
+        if sink is not None:
+            # data-parallel mode (dp.FlatGradAllReducer.attach): the 13 gradients are WRITTEN (not accumulated)
+            # straight into the views of the flat all-reduce buffer; autograd gets None and leaves .grad alone
+            if len(sink) != len(params) or any(g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous()
+                                               or g.device != p.device for g, p in zip(sink, params)):
+                raise capi.S2VTHipError("gradient sink does not match the 13 S2VT parameters")
+            grads = list(sink)
+        else:
+            grads = [torch.empty_like(p) for p in params]
+        dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
+        ps = _params_struct(capi.Params, params)
+        gs = _params_struct(capi.Grads, grads)
+        call(lib, ctx.d, ps, feats, dlogits, gs, dfeats, ctx.ws, _stream(dev))
+    ctx.ws = None
+    if sink is not None:
+        return (dfeats, None, None, None) + (None,) * len(params)
+    return (dfeats, None, None, None) + tuple(grads)
+
+
 class _TrainForward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feats, targets, grad_sink, out_mask, *params):
@@ -88,24 +130,13 @@ class _TrainForward(torch.autograd.Function):
                 capi.check(lib.s2vt_train_forward_dropout(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(targets),
                                                           targets.stride(0), _ptr(out_mask), _ptr(logits), _ptr(ws), nbytes,
                                                           _stream(dev)), "s2vt_train_forward_dropout")
-        ctx.out_mask = out_mask
-        ctx.save_for_backward(feats, *params)
-        ctx.ws, ctx.d, ctx.used, ctx.grad_sink = ws, d, False, grad_sink
-        ctx.dlog_fused = False      # set by _MeanCE.backward when it wrote the dlogits planes into ctx.ws itself (fused CE)
-        ctx.fusable = bool(FUSE_CE and d.B % 64 == 0 and lib.s2vt_set_gemm_mode(-1) in (1, 3))
+        _save_train_ctx(ctx, feats, params, ws, d, grad_sink, out_mask,
+                        fusable=bool(FUSE_CE and d.B % 64 == 0 and lib.s2vt_set_gemm_mode(-1) in (1, 3)))
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        if ctx.used:
-            raise capi.S2VTHipError("S2VT backward ran twice on one forward: the saved activations are consumed "
-                                    "in place (retain_graph is not supported)")
-        ctx.used = True
-        lib = capi.load()
-        feats, *params = ctx.saved_tensors
-        d, ws = ctx.d, ctx.ws
-        dev = feats.device
-        if ctx.dlog_fused:
+        if ctx.dlog_fused and not ctx.used:
             # the criterion's backward already turned the logits into dlogits operand planes inside ctx.ws; what arrives here is
             # its stride-0 placeholder.  Anything else means a second consumer of the logits added its own gradient
             # (stride 0 everywhere).  A tensor hook on the logits, anomaly mode or a future autograd that makes incoming
@@ -116,34 +147,18 @@ class _TrainForward(torch.autograd.Function):
                 raise capi.S2VTHipError("the logits of this forward fed the fused MaskCriterion backward AND another consumer: set "
                                         "s2vt_video_caption_amd.functional.FUSE_CE = False to materialise dlogits")
             dlogits = None
-        else:
-            dlogits = _f32c(dlogits, "dlogits")
-        with torch.cuda.device(dev):
-            sink = ctx.grad_sink
-            if sink is not None:
-                # data-parallel mode (dp.FlatGradAllReducer.attach): the 13 gradients are WRITTEN (not accumulated)
-                # straight into the views of the flat all-reduce buffer; autograd gets None and leaves .grad alone
-                if len(sink) != len(params) or any(g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous()
-                                                   or g.device != p.device for g, p in zip(sink, params)):
-                    raise capi.S2VTHipError("gradient sink does not match the 13 S2VT parameters")
-                grads = list(sink)
-            else:
-                grads = [torch.empty_like(p) for p in params]
-            dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
-            ps = _params_struct(capi.Params, params)
-            gs = _params_struct(capi.Grads, grads)
-            if ctx.out_mask is None:
+        out_mask = ctx.out_mask
+
+        def call(lib, d, ps, feats, dlogits, gs, dfeats, ws, stream):
+            if out_mask is None:
                 capi.check(lib.s2vt_train_backward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(dlogits),
-                                                   ctypes.byref(gs), _ptr(dfeats), _ptr(ws), ws.numel(), _stream(dev)),
+                                                   ctypes.byref(gs), _ptr(dfeats), _ptr(ws), ws.numel(), stream),
                            "s2vt_train_backward")
             else:
                 capi.check(lib.s2vt_train_backward_dropout(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(dlogits),
-                                                           _ptr(ctx.out_mask), ctypes.byref(gs), _ptr(dfeats), _ptr(ws),
-                                                           ws.numel(), _stream(dev)), "s2vt_train_backward_dropout")
-        ctx.ws = None
-        if sink is not None:
-            return (dfeats, None, None, None) + (None,) * len(params)
-        return (dfeats, None, None, None) + tuple(grads)
+                                                           _ptr(out_mask), ctypes.byref(gs), _ptr(dfeats), _ptr(ws),
+                                                           ws.numel(), stream), "s2vt_train_backward_dropout")
+        return _train_backward(ctx, dlogits, call)
 
 
 # model -> 13 gradient tensors (capi.PARAM_KEYS order) the backward writes into; kept OUT of the module's __dict__ so
@@ -212,43 +227,19 @@ class _TrainForwardGroup(torch.autograd.Function):
             capi.check(lib.s2vt_train_group_forward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(targets), targets.stride(0),
                                                     targets.stride(1), K, _ptr(out_mask), _ptr(logits), _ptr(ws), nbytes, _stream(dev)),
                        "s2vt_train_group_forward")
-        ctx.out_mask = out_mask
-        ctx.save_for_backward(feats, *params)
-        ctx.ws, ctx.d, ctx.used, ctx.grad_sink = ws, d, False, grad_sink
-        ctx.dlog_fused = False
-        ctx.fusable = False           # (the fused criterion backward writes a plane-driver workspace: not this one)
+        _save_train_ctx(ctx, feats, params, ws, d, grad_sink, out_mask,
+                        fusable=False)      # (the fused criterion backward writes a plane-driver workspace: not this one)
         return logits
 
     @staticmethod
     def backward(ctx, dlogits):
-        if ctx.used:
-            raise capi.S2VTHipError("S2VT backward ran twice on one forward: the saved activations are consumed "
-                                    "in place (retain_graph is not supported)")
-        ctx.used = True
-        lib = capi.load()
-        feats, *params = ctx.saved_tensors
-        d, ws = ctx.d, ctx.ws
-        dev = feats.device
-        dlogits = _f32c(dlogits, "dlogits")
-        with torch.cuda.device(dev):
-            sink = ctx.grad_sink
-            if sink is not None:          # data-parallel mode: see _TrainForward.backward
-                if len(sink) != len(params) or any(g.shape != p.shape or g.dtype != torch.float32 or not g.is_contiguous()
-                                                   or g.device != p.device for g, p in zip(sink, params)):
-                    raise capi.S2VTHipError("gradient sink does not match the 13 S2VT parameters")
-                grads = list(sink)
-            else:
-                grads = [torch.empty_like(p) for p in params]
-            dfeats = torch.empty_like(feats) if ctx.needs_input_grad[0] else None
-            ps = _params_struct(capi.Params, params)
-            gs = _params_struct(capi.Grads, grads)
-            capi.check(lib.s2vt_train_group_backward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(dlogits), _ptr(ctx.out_mask),
-                                                     ctypes.byref(gs), _ptr(dfeats), _ptr(ws), ws.numel(), _stream(dev)),
+        out_mask = ctx.out_mask
+
+        def call(lib, d, ps, feats, dlogits, gs, dfeats, ws, stream):
+            capi.check(lib.s2vt_train_group_backward(ctypes.byref(d), ctypes.byref(ps), _ptr(feats), _ptr(dlogits), _ptr(out_mask),
+                                                     ctypes.byref(gs), _ptr(dfeats), _ptr(ws), ws.numel(), stream),
                        "s2vt_train_group_backward")
-        ctx.ws = None
-        if sink is not None:
-            return (dfeats, None, None, None) + (None,) * len(params)
-        return (dfeats, None, None, None) + tuple(grads)
+        return _train_backward(ctx, dlogits, call)
 
 
 def train_forward_group(feats, targets, params, grad_sink=None, out_mask=None):

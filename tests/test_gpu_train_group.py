@@ -1,5 +1,5 @@
 """mode='train' on K captions per clip with one encode per clip (3-D targets [B, K, L-1] -> logits [B, K, L-1, V];
-functional.train_forward_group, s2vt_train_group_forward / _backward, csrc/api_train_group.hip) and its group-sum kernel
+functional.train_forward_group, s2vt_train_group_forward / _backward: the grouped path of csrc/api_train_f32.hip) and its group-sum kernel
 (s2vt_group_sum_rows, csrc/group.hip).
 
 The contract: the logits are those of mode='train' on feats.repeat_interleave(K, 0) with targets.reshape(B*K, L-1); the backward

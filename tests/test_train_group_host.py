@@ -1,8 +1,13 @@
-"""CPU: K captions per clip on one encode (S2VT.forward with 3-D targets, csrc/api_train_group.hip) - the C ABI's surface, the
-size query without a device, the argument checks that come before any device call, the dataset's K-caption items and train.py's
-flags."""
+"""CPU: K captions per clip on one encode (S2VT.forward with 3-D targets; the grouped path of the fp32 train driver,
+csrc/api_train_f32.hip) - the C ABI's surface, the size query without a device and its sizes against a table recorded from the build
+before the grouped driver was merged into the fp32 train driver (tests/golden/group_workspace_layout.json), the argument checks that
+come before any device call, the dataset's K-caption items and train.py's flags.
+
+Recording the table (with the library whose layout is the reference):
+    S2VT_LIB=<library> PYTHONPATH=. python tests/test_train_group_host.py tests/golden/group_workspace_layout.json"""
 import ctypes
 import inspect
+import itertools
 import json
 import os
 import re
@@ -15,7 +20,12 @@ import torch
 import s2vt_video_caption_amd  # noqa: F401
 from s2vt_video_caption_amd import capi
 
+import test_decode_plan_host as plan  # noqa: E402  (the shapes of the recorded layout tables)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden", "group_workspace_layout.json")
+GROUP_K = (1, 2, 5)
+PIPE_BLOCKS = (0, 32)
 NEW = ("s2vt_train_group_workspace_bytes", "s2vt_train_group_forward", "s2vt_train_group_backward", "s2vt_group_sum_rows")
 
 
@@ -43,6 +53,33 @@ def test_workspace_query_without_a_device(lib):
     assert lib.s2vt_train_group_workspace_bytes(ctypes.byref(d), 64 * 65535 // (80 * 16) + 1) == 0
     # the decode images are the part that grows with K: K = 5 costs less than five K = 1 workspaces
     assert sizes[3] < 5 * sizes[1]
+
+
+def group_layout_table(lib):
+    """{"pipe_block": [[s2vt_train_group_workspace_bytes at K = 1, 2, 5] for every (L, F, E, V) x H x B of test_decode_plan_host.py, in
+    that order]}; the option is put back afterwards"""
+    before = lib.s2vt_set_option(b"pipe_block", -1)
+    table = {}
+    try:
+        for blk in PIPE_BLOCKS:
+            lib.s2vt_set_option(b"pipe_block", blk)
+            table[str(blk)] = [[lib.s2vt_train_group_workspace_bytes(ctypes.byref(capi.Dims(B, L, F, H, E, V)), K) for K in GROUP_K]
+                               for (L, F, E, V), H, B in itertools.product(plan.LFEV, plan.HIDDEN, plan.BATCHES)]
+    finally:
+        lib.s2vt_set_option(b"pipe_block", before)
+    return table
+
+
+def test_group_workspace_layouts_are_the_recorded_ones(lib):
+    with open(GOLDEN) as f:
+        want = json.load(f)
+    got = group_layout_table(lib)
+    assert sorted(got) == sorted(want) == sorted(str(b) for b in PIPE_BLOCKS)
+    shapes = list(itertools.product(plan.LFEV, plan.HIDDEN, plan.BATCHES))
+    for key in want:
+        assert len(got[key]) == len(want[key]) == len(shapes)
+        for shape, g, w in zip(shapes, got[key], want[key]):
+            assert g == w and len(g) == len(GROUP_K) and 0 < g[0] < g[1] < g[2], (key, shape, g, w)
 
 
 def test_library_argument_errors_come_before_the_device(lib):
@@ -170,3 +207,10 @@ def test_train_flags():
             train.parse(bad)
     sig = inspect.signature(train.make_self_critical_step)
     assert sig.parameters["shared_encode"].default is False
+
+
+if __name__ == "__main__":
+    with open(sys.argv[1], "w") as out:
+        json.dump(group_layout_table(capi.load()), out, separators=(",", ":"))
+        out.write("\n")
+    print("recorded", sys.argv[1], "from", capi.LIB_PATH)

@@ -1,5 +1,5 @@
-"""Cost of a train pass on K captions per clip with one encode per clip (S2VT.forward with 3-D targets, csrc/api_train_group.hip)
-beside the only route there was before it - mode='train' on the clips repeated K times, which is the existing code and so the
+"""Cost of a train pass on K captions per clip with one encode per clip (S2VT.forward with 3-D targets; the grouped path of
+csrc/api_train_f32.hip) beside the only route there was before it - mode='train' on the clips repeated K times, which is the existing code and so the
 yardstick - in one process on one MI355X.  A pass = forward + MaskCriterion + backward (every parameter gradient; no optimiser step).
 Dims: train.py's defaults (B=16, L=80, F=4096, H=E=512, V=3000) at K = 1 and K = 5, and config 5 (L=80, F=4096, H=E=1000, V=12000)
 at B = 128 clips, K = 5 (B = 32 if the B = 128 pass does not fit the card).  The legs ALTERNATE pass by pass; a pass is timed with
