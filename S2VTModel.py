@@ -184,6 +184,26 @@ class S2VT(nn.Module):
         :param feats: [B, L, feat_dim]
         :param n_samples: an integer >= 1
         """
+        return self._sample(feats, n_samples, temperature, seed, 0, 1.0)
+
+    @torch.no_grad()
+    def sample_truncated(self, feats, n_samples=1, temperature=1.0, seed=None, top_k=0, top_p=1.0):
+        """`sample` with top-k / nucleus (top-p) truncation: ids int64 [B, n_samples, L-1], every word drawn from its step's
+        softmax(logit / temperature) cut to the top_k largest scores (equal values at the k-th place all stay) and then to the
+        nucleus - the shortest descending prefix whose mass, renormalised over the top-k set, reaches top_p (the rule: sampling.py,
+        include/s2vt_hip.h "truncated draw").  Same rows, same noise as `sample`: row b*K + k draws with the noise of (seed, decode
+        step, batch row b*K + k, v), so n_samples = 1 (and [:, 0]) is mode='sample' with truncation.  The fused sampling heads
+        cannot truncate; per step the one-layer LSTM runs the logits GEMM and the row kernel of csrc/truncate.hip in `sample`'s
+        driver (s2vt_sample_decode_rows_trunc), a GRU or stacked model the same pair in its step loop on the repeated clips.
+        top_k=0, top_p=1.0 (the defaults) truncate nothing and run exactly what `sample` runs.  A method of its own: the parameter
+        lists of forward and sample are fixed.  No gradient.
+        :param top_k: an int in [0, vocab_size]; 0 (or vocab_size): off
+        :param top_p: in (0, 1]; 1.0: off
+        """
+        k, p = _sampling.check_truncation(top_k, top_p, self.vocab_size)
+        return self._sample(feats, n_samples, temperature, seed, k, p)
+
+    def _sample(self, feats, n_samples, temperature, seed, k, p):
         K = _sampling.check_n_samples(n_samples)
         t, s = _sampling.check_sample_args(temperature, seed)
         _F.require_hip(feats, "feats")
@@ -193,9 +213,10 @@ class S2VT(nn.Module):
         if _G.is_gru_model(self) or _S.is_stacked_lstm_model(self):
             decode = _G.greedy_decode if _G.is_gru_model(self) else _S.greedy_decode
             rows = self.feat_drop(feats).repeat_interleave(K, 0)
-            return decode(self, rows, self.sos_ix, sample=(t, s)).view(B, K, -1)
+            smp = (t, s, k, p) if _sampling.truncates(k, p, self.vocab_size) else (t, s)
+            return decode(self, rows, self.sos_ix, sample=smp).view(B, K, -1)
         params = self._hip_params()
-        return _sampling.sample_rows(self, self.feat_drop(feats), params, K, t, s)
+        return _sampling.sample_rows(self, self.feat_drop(feats), params, K, t, s, k, p)
 
     def _forward_gru(self, feats, targets, mode, sample=None, ss=(0.0, None, None), drop_feats=True):
         """rnn_type='gru' with one unidirectional layer: the GRU timestep kernels under autograd glue (gru_functional.py)"""

@@ -35,10 +35,14 @@ class Att_Baseline(nn.Module):
         self.att_prev_hid = nn.Linear(dim_hid, dim_hid, bias=True)
         self.att_apply = nn.Linear(dim_hid, 1, bias=False)
 
-    def forward(self, feats, targets=None, mode='train', temperature=1.0, seed=None):
+    def forward(self, feats, targets=None, mode='train', temperature=1.0, seed=None, top_k=0, top_p=1.0):
         """feats [B, length, dim_feat] (HIP, fp32).  mode 'train': targets [B, length-1] int64 -> logits [B, length-1, vocab]
         (autograd-connected to every parameter); mode 'test': greedy ids [B, length] int64; mode 'sample': ids [B, length] drawn
-        from softmax(logit / temperature) step by step (seed None: drawn from torch's default generator)."""
+        from softmax(logit / temperature) step by step (seed None: drawn from torch's default generator), cut to the top_k largest
+        scores and / or the nucleus of mass top_p where those are given (S2VT.sample_truncated's; 0 / 1.0: off)."""
+        if mode == 'sample':
+            from s2vt_video_caption_amd import sampling
+            trunc = sampling.check_truncation(top_k, top_p, self.vocab_size)
         _require_hip(feats, "feats")
         if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.dim_feat:
             raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.dim_feat, tuple(feats.shape)))
@@ -49,6 +53,6 @@ class Att_Baseline(nn.Module):
         if mode == 'test':
             return _A.greedy_decode(self, feats.float())
         if mode == 'sample':
-            from s2vt_video_caption_amd import sampling
-            return _A.greedy_decode(self, feats.float(), sample=sampling.check_sample_args(temperature, seed))
+            smp = sampling.check_sample_args(temperature, seed)
+            return _A.greedy_decode(self, feats.float(), sample=smp + trunc if sampling.truncates(*trunc, self.vocab_size) else smp)
         raise ValueError("mode must be 'train', 'test' or 'sample', got %r" % (mode,))

@@ -8,6 +8,8 @@ decodes with the cumulative-score beam search instead (mode='beam', not in the r
 BLEU-1..4, ROUGE-L, CIDEr.  METEOR and the Stanford tokenizer are Java jars the reference does not ship
 (`.MISSING_LARGE_BLOBS`); see caption_metrics.py for what stands in for them.  --perplexity scores the split's reference captions
 under the model instead (mode='score', not in the reference): per-word perplexity and per-reference log-likelihoods.
+--sample K additionally writes K sampled captions per clip (S2VT.sample_truncated, not in the reference; --temperature, --top-k, --top-p,
+--sample-seed) to <out>.samples.json.
 """
 import argparse
 import json
@@ -58,6 +60,26 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                 for vid, seq in zip(ids, out):
                     preds[vid] = ids_to_caption(seq.tolist(), dataset.ix2word)
     return preds
+
+
+def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=10, temperature=1.0, top_k=0, top_p=1.0, seed=0,
+                    split='test', device=None):
+    """{video_id: [n_samples captions]} of a split, drawn by S2VT.sample_truncated (one encode per clip; top_k / top_p cut every step's
+    distribution, 0 / 1.0: off), each cut at its first <eos> like a greedy caption.  Batch i draws with seed + i."""
+    import dataloader
+    dev = device or torch.device('cuda', 0)
+    dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
+    model = torch.load(model_path, weights_only=False).to(dev)
+    model.eval()
+    out = {}
+    with torch.no_grad():
+        for i, (feats, targets, ids, masks) in enumerate(dataloader.feed_batches(loader, dev)):
+            drawn = model.sample_truncated(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k,
+                                           top_p=top_p).cpu().tolist()
+            for vid, rows in zip(ids, drawn):
+                out[vid] = [ids_to_caption(r, dataset.ix2word) for r in rows]
+    return out
 
 
 def pack_references(ref_lists, eos_ix, max_len):
@@ -146,6 +168,13 @@ def build_parser():
                     help="instead of decoding: score every reference caption of the split (mode='score'), print total "
                          "log-likelihood, tokens, per-word perplexity and mean per-caption log-likelihood, write "
                          "{video_id: [per-reference log-likelihoods]} to <out>.ll.json")
+    ap.add_argument("--sample", type=int, default=0, metavar="K",
+                    help="also draw K captions per clip (S2VT.sample_truncated) and write {video_id: [captions]} to <out>.samples.json")
+    ap.add_argument("--temperature", type=float, default=1.0, help="--sample: draw from softmax(logit / temperature)")
+    ap.add_argument("--top-k", type=int, default=0, help="--sample: draw among the k most probable words of a step (0: off)")
+    ap.add_argument("--top-p", type=float, default=1.0,
+                    help="--sample: draw from the smallest set of most probable words whose mass reaches p (1: off)")
+    ap.add_argument("--sample-seed", type=int, default=0, help="--sample: batch i draws with this seed + i")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
     return ap
@@ -171,6 +200,12 @@ def main(argv=None):
     if nbest is not None:
         with open(a.out + ".nbest.json", 'w', encoding='utf-8') as f:
             json.dump(nbest, f, ensure_ascii=False, indent=1)
+    if a.sample > 0:
+        samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
+                                  a.sample_seed)
+        with open(a.out + ".samples.json", 'w', encoding='utf-8') as f:
+            json.dump(samples, f, ensure_ascii=False, indent=1)
+        print("wrote {} sampled captions per clip to {}".format(a.sample, a.out + ".samples.json"))
     if a.gts:
         scorer = score(preds, a.gts)
         print("***********************")

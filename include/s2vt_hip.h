@@ -787,6 +787,41 @@ int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const floa
                             uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                             int32_t cache_valid, void* stream);
 
+/* ---------------------------------------------------------------- truncated draw: top-k / nucleus (top-p) ahead of the sampled draw
+ * (S2VT.sample_truncated(..., top_k=, top_p=); csrc/truncate.hip; restated in numpy by
+ * sampling.truncation_mask).  The fused heads above never hold a logits row; this draw works on one: for a row x[0..V),
+ * inv_t = 1 / temperature, top_k = k, top_p = p
+ *   1. scores   s_v = x_v * inv_t in fp32 (the heads' expression).
+ *   2. top-k    (k = 0 or k >= V: off)  tau = the k-th largest s, counted with multiplicity; survivors {v : s_v >= tau}.  Equal
+ *               values at the k-th place all stay: at least k elements survive.
+ *   3. nucleus  (p >= 1: off, not evaluated) over the survivors of 2:  m = max s, e_v = expf(s_v - m), Z = sum e_v;  v stays iff
+ *               A(s_v) < p * Z with A(y) = sum of e_u over {u : s_u > y} - the shortest descending prefix whose mass reaches p,
+ *               renormalised over the top-k set ("top-k, then top-p").  Equal values stay or go together; the maximum always stays
+ *               (A = 0).
+ *   4. draw     token = argmax over the kept v of (s_v + g_v), the lowest index wins a tie; g is EXACTLY the noise above: Philox
+ *               counter (v / 4, batch row = row0 + r, decode step, 0x47554D42), key = seed halves.  With nothing truncated the draw
+ *               is the heads' draw up to the logit rounding between GEMM paths.
+ *   5. output   packed[r] = ordered(score) << 32 | (0xFFFFFFFF - v), the heads' word (a plain store: the row's workgroup owns it,
+ *               packed need not be zeroed), read unchanged by the next token step; kept[r] (nullable) = the number of survivors.
+ * Every sum is a fixed-order fp32 reduction (per thread in ascending element order, wave butterfly, (w0 + w1) + (w2 + w3)): no
+ * floating-point atomics, the same inputs give the same bits.  The index written is always in [0, V).
+ * s2vt_truncated_draw: logits fp32 [rows, V] with row stride ld >= V; V * 4 <= 150 KiB.  Checked on the host before anything is
+ * enqueued (S2VT_ERR_ARG): top_k in [0, V], top_p in (0, 1] (NaN refused), the temperature rule of the sampled decode.
+ * s2vt_sample_decode_rows_trunc: s2vt_sample_decode_rows with, per step, the head replaced by the logits GEMM ([rows64(B*K), V]
+ * fp32 in the workspace: the plane GEMM on the cache's W_o image, or the fp32-input GEMM on out_w) and the draw above, batch row =
+ * r.  top_k == 0 and top_p >= 1 run the fused head - the launches of s2vt_sample_decode_rows.  Workspace from
+ * s2vt_sample_rows_trunc_workspace_bytes (0 where s2vt_sample_rows_workspace_bytes is 0 or V * 4 > 150 KiB). */
+int s2vt_truncated_draw(const float* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p,
+                        uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream);
+/* The beam searches' fan-out kernel on its own (csrc/ce.hip, what s2vt_beam_step runs behind out_linear): per logits row the 20 most
+ * probable tokens in ascending token order, top_ix int32 [rows, 20], and their log-probs, top_lp fp32 [rows, 20].  20 <= V, V * 4 <=
+ * 150 KiB.  The existing row kernel of the truncated draw's frame: tools/bench_sample_trunc.py times the two on one logits buffer. */
+int s2vt_top20_logprob(const float* logits, int64_t ld, int64_t rows, int32_t V, int32_t* top_ix, float* top_lp, void* stream);
+size_t s2vt_sample_rows_trunc_workspace_bytes(const s2vt_dims* d, int32_t K);
+int s2vt_sample_decode_rows_trunc(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix,
+                                  float temperature, uint64_t seed, int32_t top_k, float top_p, int64_t* ids, void* workspace,
+                                  size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

@@ -157,7 +157,8 @@ def train_forward(model, feats, targets):
 @torch.no_grad()
 def greedy_decode(model, feats, sample=None):
     """mode='test' (attention_baseline.py:85-104): ids [B, L] - L steps, the first input is <sos>.  sample = (temperature, seed):
-    mode='sample', a draw from softmax(logit / temperature) per step (ops.decode_step_sample) instead of the arg-max."""
+    mode='sample', a draw from softmax(logit / temperature) per step (ops.decode_step_sample) instead of the arg-max; with
+    (temperature, seed, top_k, top_p) a draw cut to the top-k / nucleus set (ops.truncated_draw on the step's logits)."""
     B, L, _ = feats.shape
     H, E = model.dim_hid, model.dim_embed
     ctxv = context_of(model, encode(model, feats))
@@ -172,8 +173,11 @@ def greedy_decode(model, feats, sample=None):
     for i in range(L):
         gx = ops.gemm(model.embedding(tok).contiguous(), w_e) + gctx
         h, c = ops.lstm_step_fwd(gx, None, w_hh, h, c)
-        tok = ops.decode_step_argmax(h, wo, bo) if sample is None else \
-            ops.decode_step_sample(h, wo, bo, temperature=sample[0], seed=sample[1], step=i)
+        if ops._trunc_of(sample, wo.shape[0]) is not None:      # (temperature, seed, top_k, top_p): logits GEMM + truncated draw
+            tok = ops.truncated_draw(ops.gemm(h, wo, bo), sample[0], sample[2], sample[3], sample[1], step=i)
+        else:
+            tok = ops.decode_step_argmax(h, wo, bo) if sample is None else \
+                ops.decode_step_sample(h, wo, bo, temperature=sample[0], seed=sample[1], step=i)
         preds.append(tok)
     capi.check_async_error(wait=False)
     return torch.stack(preds, dim=1)

@@ -199,6 +199,12 @@ SIGNATURES = {
     "s2vt_sample_rows_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
     "s2vt_sample_decode_rows": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_int32, c_float, c_uint64, c_void_p,
                                           c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_truncated_draw": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_float, c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p,
+                                      c_void_p, c_void_p]),
+    "s2vt_top20_logprob": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_void_p, c_void_p]),
+    "s2vt_sample_rows_trunc_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
+    "s2vt_sample_decode_rows_trunc": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int32,
+                                                c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
     "s2vt_scheduled_decode": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float, c_uint64,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_scheduled_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float,

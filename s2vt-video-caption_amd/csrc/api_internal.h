@@ -8,9 +8,10 @@
 //                    schedule, chosen by decode_plan below), the decode step's argmax entry points
 //   api_beam.hip     the batched beam-search depth step
 //   api_score.hip    teacher-forced caption scoring (S2VT.forward(mode='score'))
-//   api_sample_rows.hip  K sampled captions per clip on one encode (S2VT.sample)
+//   api_sample_rows.hip  K sampled captions per clip on one encode (S2VT.sample), plain and with top-k / nucleus truncation; the
+//                    truncated draw and the top-20 fan-out as per-op entry points
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
-// Host code only; every kernel lives in gemm* / lstm* / ce / misc / group / split / argmax_x3 / beam_queue / beam_cum.hip.
+// Host code only; every kernel lives in gemm* / lstm* / ce / truncate / misc / group / split / argmax_x3 / beam_queue / beam_cum.hip.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>

@@ -4,6 +4,9 @@
 // row r reads its clip's gate input through gx_idx and the packed word it drew at the step before, and the sampling head - the
 // decode drivers' arg-max launches with their Gumbel arguments - draws for all R rows with row0 = 0, rows = R.  One chain on the
 // caller's stream: no schedule splits the rows, so batch row = r at every launch.  A final launch turns the packed words into ids.
+// s2vt_sample_decode_rows_trunc: the same driver with top-k / nucleus truncation - per step the head is replaced by out_linear as
+// the beam step runs it (the plane GEMM on the cache's W_o image, or the fp32-input GEMM) into a [Rp, V] buffer of the workspace and
+// the truncated draw of truncate.hip over its rows; with nothing to truncate it runs the fused head, launch for launch.
 #include "api_internal.h"
 
 using namespace s2vt;
@@ -18,12 +21,13 @@ struct SampleRowsWS {
     unsigned long long* packed;      // [L-1][Rp] the steps' packed draws
     float* gws; size_t gws_floats;
     PB himg;                         // plane path: the step's h_t as blocked planes [Rp rows]
+    float* logits;                   // truncated draws only: [Rp][V] the step's logits
     size_t bytes;
 };
 static bool sample_rows_shape_ok(const s2vt_dims* d, int K) {
     return dims_ok(d) && K >= 1 && (int64_t)(d->L - 1) * (int64_t)rows64((size_t)d->B * K) < (1ll << 31);
 }
-static SampleRowsWS carve_sample_rows(const s2vt_dims& d, int K, void* base) {
+static SampleRowsWS carve_sample_rows(const s2vt_dims& d, int K, void* base, bool trunc = false) {
     const size_t B = d.B, H = d.H, R = B * K, Rp = rows64(R), S = d.L - 1;
     Carver c{reinterpret_cast<char*>(base), 0, 0};
     SampleRowsWS w;
@@ -36,6 +40,7 @@ static SampleRowsWS carve_sample_rows(const s2vt_dims& d, int K, void* base) {
     w.gws = c.take<float>(w.gws_floats);
     // (sized for either path: which one a call takes depends on its cache argument)
     if (gemm_mode() != 0) w.himg = take_planes(c, R, H, DECODE_PLANES);
+    w.logits = trunc ? c.take<float>(Rp * (size_t)d.V) : nullptr;
     w.bytes = align_up(c.off, 256);
     return w;
 }
@@ -43,21 +48,35 @@ size_t s2vt_sample_rows_workspace_bytes(const s2vt_dims* d, int32_t K) {
     return sample_rows_shape_ok(d, K) ? carve_sample_rows(*d, K, nullptr).bytes : 0;
 }
 
-int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, float temperature,
-                            uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
-                            int32_t cache_valid, void* stream) {
-    S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace, "s2vt_sample_decode_rows: null/invalid argument");
-    S2VT_REQUIRE(sample_rows_shape_ok(d, K), "s2vt_sample_decode_rows: K = %d samples per clip: need K >= 1 and fewer than 2^31 packed words",
-                 (int)K);
-    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_sample_decode_rows: temperature and 1 / temperature must be finite and > 0 (got %g)",
+// the vocabulary bound of the truncated draw's row kernel (truncate.hip: the row in registers or LDS)
+static bool trunc_vocab_ok(const s2vt_dims* d) { return (size_t)d->V * sizeof(float) <= 150 * 1024; }
+size_t s2vt_sample_rows_trunc_workspace_bytes(const s2vt_dims* d, int32_t K) {
+    return sample_rows_shape_ok(d, K) && trunc_vocab_ok(d) ? carve_sample_rows(*d, K, nullptr, true).bytes : 0;
+}
+}  // extern "C"
+
+// Both entry points (fn names the one that was called).  trunc: the workspace has the logits buffer and a step's head is the logits
+// GEMM + the truncated draw - unless top_k / top_p truncate nothing, which runs the fused head like the plain entry point.
+static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_p, const s2vt_dims* d, const s2vt_params* p,
+                           const float* feats, int32_t K, int32_t sos_ix, float temperature, uint64_t seed, int64_t* ids, void* workspace,
+                           size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream) {
+    S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace, "%s: null/invalid argument", fn);
+    S2VT_REQUIRE(sample_rows_shape_ok(d, K), "%s: K = %d samples per clip: need K >= 1 and fewer than 2^31 packed words", fn, (int)K);
+    S2VT_REQUIRE(temperature_ok(temperature), "%s: temperature and 1 / temperature must be finite and > 0 (got %g)", fn,
                  (double)temperature);
-    S2VT_REQUIRE(sos_ix >= 0 && sos_ix < d->V, "s2vt_sample_decode_rows: sos_ix %d outside [0, V = %d)", (int)sos_ix, d->V);
-    const SampleRowsWS w = carve_sample_rows(*d, K, workspace);
-    S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_sample_decode_rows: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
+    S2VT_REQUIRE(sos_ix >= 0 && sos_ix < d->V, "%s: sos_ix %d outside [0, V = %d)", fn, (int)sos_ix, d->V);
+    if (trunc) {
+        S2VT_REQUIRE(top_k >= 0 && top_k <= d->V, "%s: top_k %d outside [0, V = %d]", fn, (int)top_k, d->V);
+        S2VT_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0, 1] (got %g)", fn, (double)top_p);
+        S2VT_REQUIRE(trunc_vocab_ok(d), "%s: vocab_size %d > 38400", fn, d->V);
+    }
+    const bool cut = trunc && ((top_k > 0 && top_k < d->V) || top_p < 1.f);
+    const SampleRowsWS w = carve_sample_rows(*d, K, workspace, trunc);
+    S2VT_REQUIRE(workspace_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, w.bytes);
     const int B = d->B, H = d->H, V = d->V, S = d->L - 1, R = B * K, Rp = (int)rows64((size_t)R);
     const int64_t BH = (int64_t)B * H, RH = (int64_t)R * H;
     const bool planes = cache != nullptr;
-    S2VT_REQUIRE(!planes || w.himg.p, "s2vt_sample_decode_rows: a cache needs a plane mode (gemm mode 1 / 3)");
+    S2VT_REQUIRE(!planes || w.himg.p, "%s: a cache needs a plane mode (gemm mode 1 / 3)", fn);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     // ---- 1. encode, once per clip.  With a cache: the decode drivers' encode phase on the plane path (persistent split-precision
@@ -100,6 +119,19 @@ int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const floa
         }
         hprev = a.h_out;
         const GumbelArgs g = gumbel_args(temperature, seed, (uint32_t)j, 0u, (uint32_t)R);
+        if (cut) {
+            // out_linear as the beam step runs it (api_beam.hip), then the row kernel: it STORES the rows' packed words
+            const Lane ln{st, w.gws, w.gws_floats, nullptr};
+            {
+                ProfScope pg(st, K_GEMM, 1);
+                rc = planes ? pgemm(ln, R, V, H, w.himg, 0, 0, kc.wo, 0, 0, w.logits, V, ID, p->out_b, false)
+                            : lgemm(ln, true, true, R, V, H, a.h_out, H, ID, p->out_w, H, ID, w.logits, V, ID, p->out_b, false);
+            }
+            if (rc) return rc;
+            ProfScope ps(st, K_ARGMAX, 1);
+            if ((rc = truncated_draw(st, w.logits, V, R, V, top_k, top_p, g, packed, nullptr))) return rc;
+            continue;
+        }
         ProfScope ps(st, K_ARGMAX, 1);
         if (planes) {
             ArgmaxX3Args ax;
@@ -122,5 +154,36 @@ int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const floa
     // ---- 4. ids[r][j] of the R rows
     if ((rc = unpack_rows(st, w.packed, S, Rp, R, ids))) return rc;
     return post_async_error(st, w.err, 3);       // (a ring slot: no wait for an earlier call's record)
+}
+
+extern "C" {
+int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, float temperature,
+                            uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                            int32_t cache_valid, void* stream) {
+    return sample_rows_run("s2vt_sample_decode_rows", false, 0, 1.f, d, p, feats, K, sos_ix, temperature, seed, ids, workspace,
+                           workspace_bytes, cache, cache_bytes, cache_valid, stream);
+}
+int s2vt_sample_decode_rows_trunc(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix,
+                                  float temperature, uint64_t seed, int32_t top_k, float top_p, int64_t* ids, void* workspace,
+                                  size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream) {
+    return sample_rows_run("s2vt_sample_decode_rows_trunc", true, top_k, top_p, d, p, feats, K, sos_ix, temperature, seed, ids,
+                           workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream);
+}
+int s2vt_top20_logprob(const float* logits, int64_t ld, int64_t rows, int32_t V, int32_t* top_ix, float* top_lp, void* stream) {
+    S2VT_REQUIRE(logits && top_ix && top_lp && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V, "s2vt_top20_logprob: null/invalid argument");
+    return top20_logprob((hipStream_t)stream, logits, ld, rows, V, top_ix, top_lp);
+}
+int s2vt_truncated_draw(const float* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p,
+                        uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream) {
+    S2VT_REQUIRE(logits && packed && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V && step >= 0 && row0 >= 0,
+                 "s2vt_truncated_draw: null/invalid argument");
+    S2VT_REQUIRE((size_t)V * sizeof(float) <= 150 * 1024, "s2vt_truncated_draw: vocab_size %d > 38400", (int)V);
+    S2VT_REQUIRE(temperature_ok(temperature), "s2vt_truncated_draw: temperature and 1 / temperature must be finite and > 0 (got %g)",
+                 (double)temperature);
+    S2VT_REQUIRE(top_k >= 0 && top_k <= V, "s2vt_truncated_draw: top_k %d outside [0, V = %d]", (int)top_k, (int)V);
+    S2VT_REQUIRE(top_p > 0.f && top_p <= 1.f, "s2vt_truncated_draw: top_p must be in (0, 1] (got %g)", (double)top_p);
+    ProfScope ps((hipStream_t)stream, K_ARGMAX, 1);
+    return truncated_draw((hipStream_t)stream, logits, ld, rows, V, top_k, top_p,
+                          gumbel_args(temperature, seed, (uint32_t)step, (uint32_t)row0, (uint32_t)row0 + (uint32_t)rows), packed, kept);
 }
 }

@@ -239,72 +239,7 @@ int weighted_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, con
 //                      values is kept); (-inf, 0x7fffffff) when none is left
 //   remove(ix)         take element ix (one of the thread's) out
 constexpr int TOPK_N = 20;
-// The row in REGISTERS (VPT elements per thread): the owner's rescan after an extraction is VPT register compares instead of VPT
-// dependent LDS reads (the LDS form spent 1.4 of its 4.7 us per extraction there: 95 us per launch at V = 12000, 640 rows; this
-// one ~25).  Every access is unrolled with a compile-time index: vals never leaves the register file.
-template <int VPT>
-struct RegRow {
-    float vals[VPT];
-    __device__ __forceinline__ float load_max(const float* src, int V) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < VPT; ++j) {
-            const int i = threadIdx.x + 256 * j;
-            vals[j] = (i < V) ? src[i] : -INFINITY;
-            mx = fmaxf(mx, vals[j]);
-        }
-        return mx;
-    }
-    __device__ __forceinline__ float sum_exp(float mx, int V) const {
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < VPT; ++j)
-            if ((int)threadIdx.x + 256 * j < V) sum += expf(vals[j] - mx);
-        return sum;
-    }
-    __device__ __forceinline__ void best(float& bv, int& bi, int V) const {
-        int bj = -1;
-        bv = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < VPT; ++j)
-            if (vals[j] > bv) { bv = vals[j]; bj = j; }
-        bi = bj >= 0 ? (int)threadIdx.x + 256 * bj : 0x7fffffff;
-    }
-    __device__ __forceinline__ void remove(int ix) {
-        const int jj = ix >> 8;
-#pragma unroll
-        for (int j = 0; j < VPT; ++j) vals[j] = (j == jj) ? -INFINITY : vals[j];
-    }
-};
-// The row staged in dynamic LDS (V floats): vocabularies beyond 64 elements per thread
-struct LdsRow {
-    float* row;
-    __device__ __forceinline__ float load_max(const float* src, int V) {
-        extern __shared__ float top20_row[];
-        row = top20_row;
-        float mx = -INFINITY;
-        for (int i = threadIdx.x; i < V; i += 256) {
-            const float v = src[i];
-            row[i] = v;
-            mx = fmaxf(mx, v);
-        }
-        return mx;
-    }
-    __device__ __forceinline__ float sum_exp(float mx, int V) const {
-        float sum = 0.f;
-        for (int i = threadIdx.x; i < V; i += 256) sum += expf(row[i] - mx);
-        return sum;
-    }
-    __device__ __forceinline__ void best(float& bv, int& bi, int V) const {
-        bv = -INFINITY; bi = 0x7fffffff;
-        for (int i = threadIdx.x; i < V; i += 256) {
-            const float v = row[i];
-            if (v > bv) { bv = v; bi = i; }
-        }
-    }
-    __device__ __forceinline__ void remove(int ix) { row[ix] = -INFINITY; }
-};
-
+// (RegRow<VPT> / LdsRow: row_frame.h, shared with the truncated draw of truncate.hip)
 // Same arithmetic in the same order for every Row: max, then the sum of expf(x - max) per thread in ascending i, wave
 // butterflies, (w0 + w1) + (w2 + w3); ties -> the lower token id.
 template <class Row>

@@ -387,6 +387,11 @@ int score_prep(hipStream_t s, const int64_t* caps, int64_t stride_b, int64_t str
                int32_t* row_b, int* err_flag);
 int score_finish(hipStream_t s, const float* lp, const int32_t* tok, int R, int Rp, int T, int eos, const float* powa, float* token_lp,
                  float* score, int64_t* length);
+// ---- truncate.hip: top-k / nucleus truncation + the Gumbel-max draw over the survivors, one workgroup per logits row
+// (include/s2vt_hip.h "truncated draw"); packed[r] is stored, not max-ed; kept [rows] nullable; batch row of row r = ga.row0 + r
+bool truncation_ok(int top_k, float top_p, int V);       // top_k in [0, V], top_p in (0, 1] (NaN: no)
+int truncated_draw(hipStream_t s, const float* logits, int64_t ld, int64_t rows, int V, int top_k, float top_p, const GumbelArgs& ga,
+                   unsigned long long* packed, int32_t* kept);
 // fp32(len ** alpha) for len = 0..D (len 0: 1), libm double pow then fp32, in pinned host memory that lives for the life of the
 // process (beam_cum.hip: the power rule of mode='beam'); null when no pinned memory is left
 const float* length_pow_table(double alpha, int D);

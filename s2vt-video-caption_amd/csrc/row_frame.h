@@ -1,6 +1,7 @@
 // The frame of the row kernels (ce.hip: the three criteria, their gradients, the beam searches' top-20 fan-out; split.hip: the
-// fused criterion backward): 256-thread block reductions in ONE fixed order, the [:, 1:] read of a [B, L] matrix by flat row, the
-// clamp of a bad target and the CE gradient of one element.  Device code only.
+// fused criterion backward; truncate.hip: the truncated draw): 256-thread block reductions in ONE fixed order, the two places a
+// one-workgroup-per-row kernel keeps its row (RegRow<VPT> / LdsRow), the [:, 1:] read of a [B, L] matrix by flat row, the clamp of
+// a bad target and the CE gradient of one element.  Device code only.
 #pragma once
 #include "common.h"
 
@@ -52,6 +53,101 @@ __device__ __forceinline__ void block_argmax_256(float& v, int& ix, float* red_v
     for (int w = 1; w < 4; ++w)
         if (red_v[w] > v || (red_v[w] == v && red_i[w] < ix)) { v = red_v[w]; ix = red_i[w]; }     // (red_i read on a tie only)
 }
+
+// ---- where a one-workgroup-per-row kernel keeps its row (the top-20 fan-out of ce.hip, the truncated draw of truncate.hip).
+// Thread tid owns the elements i = tid + 256 j; the interface is described at top20_logprob_kernel (ce.hip), plus
+//   each(V, f)         f(slot, i, v) for every element i < V of the thread in ascending i, v a reference to its value; slot is the
+//                      element's register index (a compile-time constant after unrolling) or 0 where the row is not in registers
+//   slots(V, f)        the same over every slot the thread holds: the register forms' pad slots (i >= V, value -inf after
+//                      load_max) included, WITHOUT a guard - in a kernel that walks the row many times 64 loop-invariant lane
+//                      masks would otherwise be kept in (and spilled from) SGPRs; the caller gives the pads a neutral value
+//   SLOTS              registers per thread that hold the row (0: none) - what a kernel sizes a second per-element array by
+// The row in REGISTERS (VPT elements per thread): the owner's rescan after an extraction is VPT register compares instead of VPT
+// dependent LDS reads (the LDS form spent 1.4 of its 4.7 us per extraction there: 95 us per launch at V = 12000, 640 rows; this
+// one ~25).  Every access is unrolled with a compile-time index: vals never leaves the register file.
+template <int VPT>
+struct RegRow {
+    static constexpr int SLOTS = VPT;
+    float vals[VPT];
+    __device__ __forceinline__ float load_max(const float* src, int V) {
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) {
+            const int i = threadIdx.x + 256 * j;
+            vals[j] = (i < V) ? src[i] : -INFINITY;
+            mx = fmaxf(mx, vals[j]);
+        }
+        return mx;
+    }
+    __device__ __forceinline__ float sum_exp(float mx, int V) const {
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < VPT; ++j)
+            if ((int)threadIdx.x + 256 * j < V) sum += expf(vals[j] - mx);
+        return sum;
+    }
+    __device__ __forceinline__ void best(float& bv, int& bi, int V) const {
+        int bj = -1;
+        bv = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < VPT; ++j)
+            if (vals[j] > bv) { bv = vals[j]; bj = j; }
+        bi = bj >= 0 ? (int)threadIdx.x + 256 * bj : 0x7fffffff;
+    }
+    __device__ __forceinline__ void remove(int ix) {
+        const int jj = ix >> 8;
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) vals[j] = (j == jj) ? -INFINITY : vals[j];
+    }
+    template <class F>
+    __device__ __forceinline__ void each(int V, F f) {
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) {
+            const int i = threadIdx.x + 256 * j;
+            if (i < V) f(j, i, vals[j]);
+        }
+    }
+    template <class F>
+    __device__ __forceinline__ void slots(int V, F f) {
+#pragma unroll
+        for (int j = 0; j < VPT; ++j) f(j, (int)threadIdx.x + 256 * j, vals[j]);
+    }
+};
+// The row staged in dynamic LDS (V floats): vocabularies beyond 64 elements per thread
+struct LdsRow {
+    static constexpr int SLOTS = 0;
+    float* row;
+    __device__ __forceinline__ float load_max(const float* src, int V) {
+        extern __shared__ float top20_row[];
+        row = top20_row;
+        float mx = -INFINITY;
+        for (int i = threadIdx.x; i < V; i += 256) {
+            const float v = src[i];
+            row[i] = v;
+            mx = fmaxf(mx, v);
+        }
+        return mx;
+    }
+    __device__ __forceinline__ float sum_exp(float mx, int V) const {
+        float sum = 0.f;
+        for (int i = threadIdx.x; i < V; i += 256) sum += expf(row[i] - mx);
+        return sum;
+    }
+    __device__ __forceinline__ void best(float& bv, int& bi, int V) const {
+        bv = -INFINITY; bi = 0x7fffffff;
+        for (int i = threadIdx.x; i < V; i += 256) {
+            const float v = row[i];
+            if (v > bv) { bv = v; bi = i; }
+        }
+    }
+    __device__ __forceinline__ void remove(int ix) { row[ix] = -INFINITY; }
+    template <class F>
+    __device__ __forceinline__ void each(int V, F f) {
+        for (int i = threadIdx.x; i < V; i += 256) f(0, i, row[i]);
+    }
+    template <class F>
+    __device__ __forceinline__ void slots(int V, F f) { each(V, f); }       // (no pad slots)
+};
 
 // x[:, 1:] of a [B, L] matrix (row stride ld) by flat row r = b * Lm1 + j  ->  x[b * ld + j + 1]: targets, masks, weights
 // (R: the caller's row type - the division is 32-bit where its row index is)

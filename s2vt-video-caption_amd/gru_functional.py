@@ -98,7 +98,8 @@ def train_forward(model, feats, targets, out_mask=None):
 @torch.no_grad()
 def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
     """mode='test' (S2VTModel.py:82-110): ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the same loop with
-    s2vt_decode_step_sample in place of the arg-max.  ss = (targets, ss_prob, seed): the scheduled-sampling pass - every token
+    s2vt_decode_step_sample in place of the arg-max ((temperature, seed, top_k, top_p): the logits GEMM and the truncated draw,
+    ops.decode_step_token_into).  ss = (targets, ss_prob, seed): the scheduled-sampling pass - every token
     step is s2vt_gru_step_fwd_token_ss, and (used, draws) are returned instead of the ids.  vid_rnn without a stash, word_rnn's encode over the first L steps,
     then L-1 decode steps of s2vt_gru_step_fwd_token (the previous step's packed argmax word is read on the device) and
     s2vt_decode_step_argmax.  No host synchronisation inside the loop: <sos> is checked on the host by the first step, and the

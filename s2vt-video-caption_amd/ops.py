@@ -245,15 +245,69 @@ def decode_step_sample(h, w_out, b_out, temperature=1.0, seed=0, step=0, row0=0,
     return (ids, packed) if return_packed else ids
 
 
+def _trunc_of(sample, V):
+    """(top_k, top_p) of a sample tuple (temperature, seed[, top_k, top_p]) where they cut anything off a row of V scores, else None"""
+    from .sampling import truncates
+    return tuple(sample[2:4]) if sample is not None and len(sample) == 4 and truncates(sample[2], sample[3], V) else None
+
+
+def truncated_draw(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, row0=0, return_kept=False, return_packed=False, packed=None):
+    """token ids int64 [rows]: one draw per logits row from softmax(logits / temperature) cut to the top_k largest scores and then to
+    the nucleus of mass top_p (s2vt_truncated_draw; the definition: sampling.py, include/s2vt_hip.h), with the noise of
+    sampling.gumbel_noise(seed, step, row0 + r, V).  logits: fp32 [rows, V], unit column stride (a row stride > V is fine).
+    return_kept / return_packed add the survivors per row (int32) / the raw packed words (high half = ordered bits of the winning
+    score), in that order.  packed: the caller's int64 [rows] to write the words to (no allocation)."""
+    from .sampling import check_truncation
+    lib = capi.load()
+    require_hip(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    top_k, top_p = check_truncation(top_k, top_p, V)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        if packed is None:
+            packed = torch.empty(rows, dtype=torch.int64, device=dev)
+        kept = torch.empty(rows, dtype=torch.int32, device=dev) if return_kept else None
+        capi.check(lib.s2vt_truncated_draw(_ptr(logits), logits.stride(0), rows, V, temperature, top_k, top_p, int(seed), int(step),
+                                           int(row0), _ptr(packed), _ptr(kept), _stream(dev)), "s2vt_truncated_draw")
+        ids = 0xFFFFFFFF - (packed & 0xFFFFFFFF)
+    out = (ids,) + ((kept,) if return_kept else ()) + ((packed,) if return_packed else ())
+    return out if len(out) > 1 else ids
+
+
+def top20_logprob(logits):
+    """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20]): the 20 most probable tokens of every logits row in ascending token order
+    and their log-probs - the beam searches' fan-out kernel on its own (s2vt_top20_logprob).  logits: fp32 [rows, V >= 20]."""
+    lib = capi.load()
+    require_hip(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ix = torch.empty(rows, 20, dtype=torch.int32, device=dev)
+        lp = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_top20_logprob(_ptr(logits), logits.stride(0), rows, V, _ptr(ix), _ptr(lp), _stream(dev)), "s2vt_top20_logprob")
+    return ix, lp
+
+
 def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0):
     """out_linear + arg-max of one decode step into the caller's packed word row `packed_i` (int64 [B], zeroed) - what the greedy
     loops of the GRU and stacked models run per step; sample = (temperature, seed): the draw of mode='sample' for decode step
-    `step` instead (s2vt_decode_step_sample).  No allocation, no synchronisation."""
+    `step` instead (s2vt_decode_step_sample); sample = (temperature, seed, top_k, top_p) that truncate: the logits GEMM and
+    s2vt_truncated_draw.  No synchronisation; no allocation but the truncated form's logits."""
     lib = capi.load()
     B, H = h.shape
     V = w_out.shape[0]
     dev = h.device
-    if sample is None:
+    trunc = _trunc_of(sample, V)
+    if trunc is not None:
+        truncated_draw(gemm(h, w_out, b_out), sample[0], trunc[0], trunc[1], sample[1], step, packed=packed_i)
+    elif sample is None:
         capi.check(lib.s2vt_decode_step_argmax(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), _ptr(packed_i), _stream(dev)),
                    "s2vt_decode_step_argmax")
     else:

@@ -12,6 +12,18 @@ the same definition written a second time - what the tests compare the device ag
     g       = -log(-log(u))                       (in [-2.82, 16.64])
 
 Nothing of a kernel's tiling, of the batch padding or of the launch enters.
+
+Top-k / nucleus truncation ahead of the draw (`top_k`, `top_p` of S2VT.sample_truncated; csrc/truncate.hip,
+include/s2vt_hip.h "truncated draw") is restated here as well - `truncation_mask`.  For a logits row x, inv_t = 1 / temperature:
+
+    1. scores   s_v = x_v * inv_t in fp32 (the heads' expression)
+    2. top-k    (k = 0 or k >= V: off)  tau = the k-th largest s, counted with multiplicity; survivors {v : s_v >= tau} - equal
+                values at the k-th place all stay, so at least k elements survive
+    3. nucleus  (p >= 1: off, not evaluated) over the survivors of 2:  m = max s, e_v = exp(s_v - m), Z = sum e_v;  v stays iff
+                A(s_v) < p * Z with A(y) = sum of e_u over {u : s_u > y}: the shortest descending prefix whose mass reaches p,
+                renormalised over the top-k set ("top-k, then top-p"); equal values stay or go together, the maximum always stays
+    4. draw     token = argmax over the kept v of (s_v + g_v), lowest index on a tie, g the noise above - with nothing truncated,
+                today's draw
 """
 import numpy as np
 
@@ -117,8 +129,49 @@ def check_n_samples(n_samples):
     return int(n_samples)
 
 
-def sample_rows(model, feats, params, K, temperature, seed):
-    """ids int64 [B, K, L-1]: K draws per clip on ONE encode - s2vt_sample_decode_rows.  Row b*K + k draws with the noise of
+def check_truncation(top_k, top_p, V):
+    """(top_k as int in [0, V], top_p as float in (0, 1]) or ValueError (top_k: ints only - True, 2.5 and '3' are refused; top_p:
+    NaN is refused) - before anything reaches the library.  0 / 1.0 are 'off'."""
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or not 0 <= int(top_k) <= int(V):
+        raise ValueError("top_k must be an integer in [0, vocab_size = %d] (0: off), got %r" % (int(V), top_k))
+    if isinstance(top_p, (bool, str)) or not isinstance(top_p, (int, float, np.integer, np.floating)) or not 0.0 < float(top_p) <= 1.0:
+        raise ValueError("top_p must be a number in (0, 1] (1: off), got %r" % (top_p,))
+    return int(top_k), float(top_p)
+
+
+def truncates(top_k, top_p, V):
+    """whether (top_k, top_p) of check_truncation cut anything off a row of V scores"""
+    return 0 < top_k < V or top_p < 1.0
+
+
+def truncation_mask(scores, top_k, top_p):
+    """bool [rows, V]: the elements that steps 2-3 of the definition above keep, in float64 on a [rows, V] score array (scores =
+    logits * inv_t; what the device's `kept` counts and its draws stay inside)."""
+    s = np.asarray(scores, dtype=np.float64)
+    rows, V = s.shape
+    keep = np.ones((rows, V), dtype=bool)
+    if 0 < top_k < V:
+        tau = np.sort(s, axis=1)[:, V - top_k]                        # the k-th largest, with multiplicity
+        keep = s >= tau[:, None]
+    if top_p < 1.0:
+        e = np.where(keep, np.exp(s - s.max(axis=1, keepdims=True)), 0.0)
+        Z = e.sum(axis=1)
+        order = np.argsort(-s, axis=1, kind="stable")
+        ss, es = np.take_along_axis(s, order, 1), np.take_along_axis(e, order, 1)
+        before = np.cumsum(es, axis=1) - es                           # the mass in front of each element of the descending order ...
+        first = np.ones((rows, V), dtype=bool)
+        first[:, 1:] = ss[:, 1:] != ss[:, :-1]
+        # ... and in front of its run of equal values: A(s_v), the mass of the strictly larger scores
+        A_sorted = np.maximum.accumulate(np.where(first, before, 0.0), axis=1)
+        A = np.empty_like(A_sorted)
+        np.put_along_axis(A, order, A_sorted, 1)
+        keep = keep & (A < top_p * Z[:, None])
+    return keep
+
+
+def sample_rows(model, feats, params, K, temperature, seed, top_k=0, top_p=1.0):
+    """ids int64 [B, K, L-1]: K draws per clip on ONE encode - s2vt_sample_decode_rows; with a truncating (top_k, top_p) (already
+    through check_truncation) s2vt_sample_decode_rows_trunc: the same driver with the logits GEMM and the truncated draw as head.  Row b*K + k draws with the noise of
     (seed, decode step, batch row b*K + k, v): the draw of mode='sample' on feats.repeat_interleave(K, 0).  With the model's decode
     cache where a decode of the batch takes the plane path's persistent encode (filled here on fresh weights), on the fp32-input
     MFMA path otherwise.  On the device, no host synchronisation, no gradient."""
@@ -135,7 +188,8 @@ def sample_rows(model, feats, params, K, temperature, seed):
         raw = params
         params = tuple(F._f32c(p.detach(), "parameter") for p in params)
         d = F._dims(feats, params)
-        nbytes = lib.s2vt_sample_rows_workspace_bytes(ctypes.byref(d), K)
+        trunc = truncates(top_k, top_p, d.V)
+        nbytes = (lib.s2vt_sample_rows_trunc_workspace_bytes if trunc else lib.s2vt_sample_rows_workspace_bytes)(ctypes.byref(d), K)
         if nbytes <= 0:
             raise ValueError("sample: %d clips x %d samples is not a shape the library serves" % (d.B, K))
         dev = feats.device
@@ -148,10 +202,14 @@ def sample_rows(model, feats, params, K, temperature, seed):
             ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             ids = torch.empty(d.B, K, d.L - 1, dtype=torch.int64, device=dev)
             ps = F._params_struct(capi.Params, params)
-            capi.check(lib.s2vt_sample_decode_rows(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix), temperature,
-                                                   seed, F._ptr(ids), F._ptr(ws), nbytes, F._ptr(cache),
-                                                   cache.numel() if cache is not None else 0, 1 if valid else 0, F._stream(dev)),
-                       "s2vt_sample_decode_rows")
+            tail = (F._ptr(ids), F._ptr(ws), nbytes, F._ptr(cache), cache.numel() if cache is not None else 0, 1 if valid else 0,
+                    F._stream(dev))
+            if trunc:
+                capi.check(lib.s2vt_sample_decode_rows_trunc(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix),
+                                                             temperature, seed, top_k, top_p, *tail), "s2vt_sample_decode_rows_trunc")
+            else:
+                capi.check(lib.s2vt_sample_decode_rows(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix),
+                                                       temperature, seed, *tail), "s2vt_sample_decode_rows")
             if cache is not None:
                 entry = F._DECODE_CACHES.get(model)
                 if entry is not None and entry[1] is cache:

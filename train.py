@@ -61,6 +61,12 @@ def parse(argv=None):
                          "and the sampled tokens' log-likelihood is weighted with reward(sampled) - reward(greedy) "
                          "(utils.RewardCriterion).  Start from a cross-entropy-trained --init-state.  Single process.")
     ap.add_argument("--sc-temperature", type=float, default=1.0, help="temperature of the sampled caption (--self-critical)")
+    ap.add_argument("--sc-top-k", type=int, default=0, metavar="k",
+                    help="--self-critical: the sampled captions draw every word among the k most probable of its step (S2VT.sample_truncated's top_k; "
+                         "0, the default: off).  utils.RewardCriterion still weights the FULL-softmax log-prob of the drawn words")
+    ap.add_argument("--sc-top-p", type=float, default=1.0, metavar="p",
+                    help="--self-critical: ... from the nucleus, the smallest set of most probable words whose mass reaches p, taken "
+                         "after --sc-top-k (its top_p; 1, the default: off).  The loss is on the full-softmax log-prob as well")
     ap.add_argument("--sc-reward", choices=("host", "device"), default="host",
                     help="where --self-critical scores the captions.  host: self_critical.CiderRewarder on the CPU, between two copies "
                          "of the ids.  device: self_critical.DeviceCiderRewarder - the reference table is built once and lives on the "
@@ -98,6 +104,10 @@ def parse(argv=None):
         ap.error("--sc-samples / --sc-baseline need --self-critical")
     if opt.sc_samples < 1:
         ap.error("--sc-samples must be at least 1")
+    if (opt.sc_top_k != 0 or opt.sc_top_p != 1.0) and not opt.self_critical:
+        ap.error("--sc-top-k / --sc-top-p need --self-critical")
+    if opt.sc_top_k < 0 or not 0.0 < opt.sc_top_p <= 1.0:
+        ap.error("--sc-top-k must be >= 0 and --sc-top-p in (0, 1]")
     if opt.sc_baseline == "mean" and opt.sc_samples < 2:
         ap.error("--sc-baseline mean needs --sc-samples >= 2 (the mean of the other K - 1 samples)")
     if opt.sc_shared_encode and not opt.self_critical:
@@ -134,7 +144,7 @@ def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
-                            reducer=None, shared_encode=False, samples=1, baseline="greedy"):
+                            reducer=None, shared_encode=False, top_k=0, top_p=1.0, samples=1, baseline="greedy"):
     """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
     train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
     (every phase ends with a device synchronisation), hist["reward_sample"] / ["reward_greedy"] the batch means.  sc_reward
@@ -145,18 +155,33 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
     rows (baseline "mean": no greedy decode runs, sc_split_ms["greedy"] stays 0 and hist["reward_greedy"] empty), then the train step
     on the clips repeated K times with the B*K captions - or, with shared_encode, on the clips as they are with K captions each
     (dp.train_step(group=K): one encode per clip, same loss and gradients).  hist["reward_baseline"] gets the batch mean of the
-    baselines."""
+    baselines.  top_k / top_p: the truncation of the sampled captions (S2VT.sample_truncated; 0 / 1.0: off) - the loss still
+    weights the full-softmax log-prob of the drawn words."""
     from s2vt_video_caption_amd import dp, ops
     from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages
     K = int(samples)
     if baseline not in ("greedy", "mean") or K < 1 or (baseline == "mean" and K < 2):
         raise ValueError("samples must be >= 1 and baseline 'greedy' or 'mean' (which needs samples >= 2), got %r, %r" % (samples, baseline))
 
+    truncated = top_k != 0 or top_p != 1.0
+
+    def draw_one(feats):
+        """one sampled caption per clip: mode='sample'; where top_k / top_p are set, S2VT.sample_truncated's single sample
+        (Att_Baseline takes the two as keywords of its forward)"""
+        if not truncated:
+            return model(feats, mode='sample', temperature=temperature)
+        if hasattr(model, "sample_truncated"):
+            return model.sample_truncated(feats, 1, temperature=temperature, top_k=top_k, top_p=top_p)[:, 0]
+        return model(feats, mode='sample', temperature=temperature, top_k=top_k, top_p=top_p)
+
     def group_step(feats, ids):
         sp = hist["sc_split_ms"]
         on_device = sc_reward == "device"
         t0 = time.perf_counter()
-        sampled = model.sample(feats, K, temperature=temperature).view(feats.shape[0] * K, -1)
+        if truncated:
+            sampled = model.sample_truncated(feats, K, temperature=temperature, top_k=top_k, top_p=top_p).view(feats.shape[0] * K, -1)
+        else:
+            sampled = model.sample(feats, K, temperature=temperature).view(feats.shape[0] * K, -1)
         if on_device:
             torch.cuda.synchronize(dev)
         else:
@@ -204,7 +229,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         sp = hist["sc_split_ms"]
         t0 = time.perf_counter()
         with torch.no_grad():
-            sampled = model(feats, mode='sample', temperature=temperature).cpu()
+            sampled = draw_one(feats).cpu()
         t1 = time.perf_counter()
         with torch.no_grad():
             greedy = model(feats, mode='test').cpu()
@@ -227,7 +252,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         sp = hist["sc_split_ms"]
         t0 = time.perf_counter()
         with torch.no_grad():
-            sampled = model(feats, mode='sample', temperature=temperature)
+            sampled = draw_one(feats)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
         with torch.no_grad():
@@ -350,7 +375,7 @@ def run(opt):
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
                                                      opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline,
-                                                     shared_encode=opt.sc_shared_encode)
+                                                     shared_encode=opt.sc_shared_encode, top_k=opt.sc_top_k, top_p=opt.sc_top_p)
 
     def save(name):
         if rank == 0:
