@@ -164,18 +164,27 @@ __global__ __launch_bounds__(64 * GV_UNITS) void lstm_step_fwd_gemv_kernel(StepF
     if (p.h_planes) store_h_planes(p.h_planes, p.ldhp, eb, unit, k.h);
 }
 
-// the shapes this kernel takes (everything else: the MFMA tile kernel of lstm.hip)
+constexpr size_t GV_MAX_LDS = 160 * 1024;   // LDS of a compute unit: what one workgroup can be given
+
+// rows per workgroup (the kernel's NB) and the dynamic LDS their staged h and embedded-word rows take
+static int gemv_rows(const StepFwdArgs& a) { return a.B <= 1 ? 1 : a.B <= 2 ? 2 : a.B <= 4 ? 4 : 8; }
+static size_t gemv_lds_bytes(const StepFwdArgs& a) {
+    return (size_t)gemv_rows(a) * (((a.H + 3) & ~3) + (a.x2 ? ((a.K2 + 3) & ~3) : 0)) * sizeof(float);
+}
+
+// the shapes this kernel takes (everything else: the MFMA tile kernel of lstm.hip).  H and K2 up to GV_MAXK each do not bound
+// their sum: 8 rows of H + K2 > 5120 floats no longer fit the LDS, and such a step is the tile kernel's.
 bool lstm_step_fwd_gemv_ok(const StepFwdArgs& a) {
     auto al = [](const void* p, int64_t ld) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0; };
     return a.B >= 1 && a.B <= 8 && !a.z_out && a.H % 4 == 0 && a.H <= GV_MAXK && (!a.h_prev || (al(a.h_prev, a.ldh) && al(a.w_hh, a.ldw))) &&
-           (!a.x2 || (a.K2 % 4 == 0 && a.K2 <= GV_MAXK && al(a.x2, a.ldx2) && al(a.w2, a.ldw2)));
+           (!a.x2 || (a.K2 % 4 == 0 && a.K2 <= GV_MAXK && al(a.x2, a.ldx2) && al(a.w2, a.ldw2))) && gemv_lds_bytes(a) <= GV_MAX_LDS;
 }
 
 int lstm_step_fwd_gemv(hipStream_t stream, const StepFwdArgs& a) {
     S2VT_REQUIRE(lstm_step_fwd_gemv_ok(a) && a.h_out && a.c_out && (a.gx || a.bias), "lstm_step_fwd_gemv: unsupported shape / arguments");
     S2VT_REQUIRE(!(a.x2 || a.gx_tab) || a.tok.tok_limit > 0, "lstm_step_fwd_gemv: a token segment needs tok_limit (rows of the table)");
-    const int nb = a.B <= 1 ? 1 : a.B <= 2 ? 2 : a.B <= 4 ? 4 : 8;
-    const size_t lds = (size_t)nb * (((a.H + 3) & ~3) + (a.x2 ? ((a.K2 + 3) & ~3) : 0)) * sizeof(float);
+    const int nb = gemv_rows(a);
+    const size_t lds = gemv_lds_bytes(a);
     const dim3 grid((unsigned)cdiv(a.H, GV_UNITS)), block(64 * GV_UNITS);
     static size_t lds_allowed[9] = {};              // per instantiation (NB): the largest dynamic-LDS size requested so far
     auto launch = [&](auto kern) -> int {
