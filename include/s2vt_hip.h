@@ -668,6 +668,11 @@ int s2vt_lstm_seq_bwd_bf16_pair(int32_t T, int32_t B, int32_t H, const float* w_
                                 const float* dh_out1, int32_t dh_first, const float* c_all0, const float* c_all1,
                                 float* stash_dg0, float* stash_dg1, void* workspace, size_t workspace_bytes, int32_t block,
                                 void* stream);
+/* Test support: where the bf16 images lie inside the workspace of s2vt_lstm_seq_fwd_bf16 (backward = 0: the W_hh rows, then
+ * the h rows [T*B]) or of s2vt_lstm_seq_bwd_bf16 (backward = 1: the W_hh^T rows, then the dG rows [T*B]).  out[0..2] = byte
+ * offset, row stride in bf16 elements and padded k extent of the weight image, out[3..5] the same of the row image.  A _pair
+ * workspace holds two such workspaces back to back, the second at + the single-layer workspace size.  No GPU call. */
+int s2vt_lstm_seq_bf16_layout(int32_t T, int32_t B, int32_t H, int32_t backward, int64_t* out);
 /* Recurrence schedule inside the whole-path train drivers (option "persist"): 0 = one launch per timestep everywhere (a card
  * shared with another process); 1 (default) = persistent kernels where the shape allows: forward and BPTT of the bf16
  * configuration (gemm mode 1, lstm_persist.hip), forward of the fp32-equivalent configuration (gemm mode 3, the split-precision

@@ -169,6 +169,7 @@ SIGNATURES = {
                                          c_size_t, c_int32, c_int32, c_void_p]),
     "s2vt_lstm_seq_bwd_bf16_pair": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_lstm_seq_bf16_layout": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "s2vt_lstm_seq_x3_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_lstm_seq_fwd_x3_persist": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32] + [c_void_p] * 8 +
                                   [c_int32, c_void_p, c_size_t, c_void_p]),

@@ -486,9 +486,11 @@ int s2vt_lstm_seq_fwd_bf16(int32_t T, int32_t B, int32_t H, float* gx_stash, int
     S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_lstm_seq_fwd_bf16: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t st = (hipStream_t)stream;
     int rc;
+    // (refused before prepare: a shape the persistent kernel does not run launches nothing at all)
+    S2VT_REQUIRE(!persistent || lstm_seq_fwd_bf16_persist_supported(B, H, w.hb.kpad),
+                 "s2vt_lstm_seq_fwd_bf16: shape B=%d H=%d (Kp=%d) not supported by the persistent kernel (B %% 32, Kp <= 1024)", B, H, w.hb.kpad);
     if ((rc = seq_bf16_prepare(st, w, T, B, H, w_hh))) return rc;
     if (!persistent) return seq_fwd_bf16(st, 0, T, B, H, gx_stash, n_gx, bias, w.wb, w.hb, h_all, c_all);
-    S2VT_REQUIRE(lstm_seq_fwd_bf16_persist_supported(B, H, w.hb.kpad), "s2vt_lstm_seq_fwd_bf16: shape not supported by the persistent kernel");
     const int blk = block > 0 ? block : T;
     for (int t0 = 0; t0 < T; t0 += blk) {
         const int t1 = (t0 + blk < T) ? t0 + blk : T;
@@ -511,7 +513,8 @@ int s2vt_lstm_seq_fwd_bf16_pair(int32_t T, int32_t B, int32_t H, float* gx_stash
     S2VT_REQUIRE(workspace_bytes >= 2 * one, "s2vt_lstm_seq_fwd_bf16_pair: workspace %zu < %zu bytes", workspace_bytes, 2 * one);
     const SeqBf16WS w0 = carve_seq_bf16(T, B, H, workspace);
     const SeqBf16WS w1 = carve_seq_bf16(T, B, H, reinterpret_cast<char*>(workspace) + one);
-    S2VT_REQUIRE(lstm_seq_fwd_bf16_persist_supported(B, H, w0.hb.kpad), "s2vt_lstm_seq_fwd_bf16_pair: shape not supported by the persistent kernel");
+    S2VT_REQUIRE(lstm_seq_fwd_bf16_persist_supported(B, H, w0.hb.kpad),
+                 "s2vt_lstm_seq_fwd_bf16_pair: shape B=%d H=%d (Kp=%d) not supported by the persistent kernel (B %% 32, Kp <= 1024)", B, H, w0.hb.kpad);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = seq_bf16_prepare(st, w0, T, B, H, w_hh0))) return rc;
@@ -562,9 +565,11 @@ int s2vt_lstm_seq_bwd_bf16(int32_t T, int32_t B, int32_t H, const float* w_hh, c
     S2VT_REQUIRE(workspace_bytes >= w.bytes, "s2vt_lstm_seq_bwd_bf16: workspace %zu < %zu bytes", workspace_bytes, w.bytes);
     hipStream_t st = (hipStream_t)stream;
     int rc;
+    S2VT_REQUIRE(!persistent || lstm_seq_bwd_bf16_persist_supported(B, H, w.dgb.kpad),
+                 "s2vt_lstm_seq_bwd_bf16: shape B=%d H=%d (Kp=%d) not supported by the persistent kernel (B %% 32, H %% 8, 4H <= 4096)", B, H,
+                 w.dgb.kpad);
     if ((rc = seq_bwd_bf16_prepare(st, w, T, B, H, w_hh))) return rc;
     if (!persistent) return seq_bwd_bf16(st, T, 0, T, B, H, w.wt, dh_out, dh_first, c_all, stash_dg, w.dgb, w.dc);
-    S2VT_REQUIRE(lstm_seq_bwd_bf16_persist_supported(B, H, w.dgb.kpad), "s2vt_lstm_seq_bwd_bf16: shape not supported by the persistent kernel");
     const int blk = block > 0 ? block : T;
     for (int t1 = T; t1 > 0; t1 -= blk) {
         const int t0 = (t1 - blk > 0) ? t1 - blk : 0;
@@ -586,7 +591,9 @@ int s2vt_lstm_seq_bwd_bf16_pair(int32_t T, int32_t B, int32_t H, const float* w_
     S2VT_REQUIRE(workspace_bytes >= 2 * one, "s2vt_lstm_seq_bwd_bf16_pair: workspace %zu < %zu bytes", workspace_bytes, 2 * one);
     const SeqBwdBf16WS w0 = carve_seq_bwd_bf16(T, B, H, workspace);
     const SeqBwdBf16WS w1 = carve_seq_bwd_bf16(T, B, H, reinterpret_cast<char*>(workspace) + one);
-    S2VT_REQUIRE(lstm_seq_bwd_bf16_persist_supported(B, H, w0.dgb.kpad), "s2vt_lstm_seq_bwd_bf16_pair: shape not supported by the persistent kernel");
+    S2VT_REQUIRE(lstm_seq_bwd_bf16_persist_supported(B, H, w0.dgb.kpad),
+                 "s2vt_lstm_seq_bwd_bf16_pair: shape B=%d H=%d (Kp=%d) not supported by the persistent kernel (B %% 32, H %% 8, 4H <= 4096)", B, H,
+                 w0.dgb.kpad);
     hipStream_t st = (hipStream_t)stream;
     int rc;
     if ((rc = seq_bwd_bf16_prepare(st, w0, T, B, H, w_hh0))) return rc;
@@ -600,6 +607,23 @@ int s2vt_lstm_seq_bwd_bf16_pair(int32_t T, int32_t B, int32_t H, const float* w_
                                                                   w0.dc, w0.sync, w0.err), &a1)))
             return rc;
     }
+    return 0;
+}
+
+// Test support: where the bf16 images lie inside the two workspaces above, straight from their carvers.
+int s2vt_lstm_seq_bf16_layout(int32_t T, int32_t B, int32_t H, int32_t backward, int64_t* out) {
+    S2VT_REQUIRE(T > 0 && B > 0 && H > 0 && out, "s2vt_lstm_seq_bf16_layout: bad arguments");
+    char* const base = reinterpret_cast<char*>((uintptr_t)1 << 20);      // (never dereferenced: the carvers only add offsets)
+    PB w, r;
+    if (backward) {
+        const SeqBwdBf16WS ws = carve_seq_bwd_bf16(T, B, H, base);
+        w = ws.wt; r = ws.dgb;
+    } else {
+        const SeqBf16WS ws = carve_seq_bf16(T, B, H, base);
+        w = ws.wb; r = ws.hb;
+    }
+    out[0] = reinterpret_cast<char*>(w.p) - base; out[1] = w.ld; out[2] = w.kpad;
+    out[3] = reinterpret_cast<char*>(r.p) - base; out[4] = r.ld; out[5] = r.kpad;
     return 0;
 }
 

@@ -347,43 +347,63 @@ def beam_step(params, dims, row_b, row_state, tok, vid_h, vid_c, word_h, word_c)
     return vh, vc, wh[:R], wc[:R], tix[:R], tlp[:R]
 
 
-def lstm_seq_fwd_bf16(gx, n_gx, bias, w_hh, T, B, H, persistent=False, block=0):
+def _bf16_workspace(nbytes, dev, poison):
+    """the workspace of the bf16 recurrence entry points: zeros, or (poison) 0xFF bytes - bf16 NaN patterns, counters and error
+    flag at their maximum: the entry points themselves must establish whatever part of it the kernels rely on"""
+    return torch.full((nbytes,), 0xFF, dtype=torch.uint8, device=dev) if poison else torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+
+
+def seq_bf16_layout(T, B, H, backward=False):
+    """{"w": (byte offset, row stride, kpad), "rows": (...)} of the bf16 weight image and the bf16 row image (h rows of the forward,
+    dG rows of the backward) inside the workspace `return_workspace=True` hands back; a _pair workspace holds two, the second at
+    + the single-layer workspace size.  From the library's own carver (s2vt_lstm_seq_bf16_layout)."""
+    lib = capi.load()
+    out = (ctypes.c_int64 * 6)()
+    capi.check(lib.s2vt_lstm_seq_bf16_layout(T, B, H, int(bool(backward)), out), "s2vt_lstm_seq_bf16_layout")
+    return {"w": tuple(out[0:3]), "rows": tuple(out[3:6])}
+
+
+def lstm_seq_fwd_bf16(gx, n_gx, bias, w_hh, T, B, H, persistent=False, block=0, poison=False, return_workspace=False):
     """Config-3 arithmetic of one LSTM layer (bf16 operands, fp32 accumulate / cell state): returns (h_all, c_all, gates)
     [T*B,H], [T*B,H], [T*B,4H].  `gx` [T*B,4H] is left untouched (the kernels work on a copy: the gate stash is written
-    in place of the gate input).  persistent: one launch per `block` steps (0 = all)."""
+    in place of the gate input).  persistent: one launch per `block` steps (0 = all).  poison: the workspace is handed over full
+    of 0xFF bytes instead of zeros; return_workspace: the workspace is appended to the result (seq_bf16_layout)."""
     lib = capi.load()
     dev = w_hh.device
     stash = _f32c(gx, "gx").clone()
     w_hh = _f32c(w_hh, "w_hh")
     with torch.cuda.device(dev):
         nbytes = lib.s2vt_lstm_seq_bf16_workspace_bytes(T, B, H)
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        h_all = torch.empty(T * B, H, dtype=torch.float32, device=dev)
-        c_all = torch.empty(T * B, H, dtype=torch.float32, device=dev)
+        ws = _bf16_workspace(nbytes, dev, poison)
+        # (NaN: an element the kernels leave unwritten shows)
+        h_all = torch.full((T * B, H), float("nan"), dtype=torch.float32, device=dev)
+        c_all = torch.full((T * B, H), float("nan"), dtype=torch.float32, device=dev)
         capi.check(lib.s2vt_lstm_seq_fwd_bf16(T, B, H, _ptr(stash), int(n_gx), _ptr(bias), _ptr(w_hh), _ptr(h_all),
                                               _ptr(c_all), _ptr(ws), nbytes, int(persistent), int(block), _stream(dev)),
                    "s2vt_lstm_seq_fwd_bf16")
         if int(ws[:4].view(torch.int32)[0].item()) != 0:
             raise capi.S2VTHipError("persistent recurrence: a hand-off wait timed out (workgroups not co-resident?)")
-    return h_all, c_all, stash
+    return (h_all, c_all, stash, ws) if return_workspace else (h_all, c_all, stash)
 
 
-def lstm_seq_fwd_bf16_pair(gx0, gx1, n_gx, bias0, bias1, w0, w1, T, B, H, block=0):
-    """Two independent layers, every block of timesteps of both in ONE persistent launch.  Returns two (h_all, c_all, gates)."""
+def lstm_seq_fwd_bf16_pair(gx0, gx1, n_gx, bias0, bias1, w0, w1, T, B, H, block=0, poison=False, return_workspace=False):
+    """Two independent layers, every block of timesteps of both in ONE persistent launch.  Returns two (h_all, c_all, gates)
+    (and, return_workspace, the workspace of both as a third element); poison as in lstm_seq_fwd_bf16."""
     lib = capi.load()
     dev = w0.device
     st0, st1 = _f32c(gx0, "gx0").clone(), _f32c(gx1, "gx1").clone()
     w0, w1 = _f32c(w0, "w0"), _f32c(w1, "w1")
     with torch.cuda.device(dev):
         nbytes = 2 * lib.s2vt_lstm_seq_bf16_workspace_bytes(T, B, H)
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        outs = [torch.empty(T * B, H, dtype=torch.float32, device=dev) for _ in range(4)]
+        ws = _bf16_workspace(nbytes, dev, poison)
+        outs = [torch.full((T * B, H), float("nan"), dtype=torch.float32, device=dev) for _ in range(4)]
         capi.check(lib.s2vt_lstm_seq_fwd_bf16_pair(T, B, H, _ptr(st0), _ptr(st1), int(n_gx), _ptr(bias0), _ptr(bias1), _ptr(w0),
                                                    _ptr(w1), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]), _ptr(outs[3]), _ptr(ws),
                                                    nbytes, int(block), _stream(dev)), "s2vt_lstm_seq_fwd_bf16_pair")
         if int(ws[:4].view(torch.int32)[0].item()) != 0:
             raise capi.S2VTHipError("persistent recurrence: a hand-off wait timed out (workgroups not co-resident?)")
-    return (outs[0], outs[2], st0), (outs[1], outs[3], st1)
+    res = (outs[0], outs[2], st0), (outs[1], outs[3], st1)
+    return res + (ws,) if return_workspace else res
 
 
 def _check_persist_err(ws):
@@ -391,33 +411,35 @@ def _check_persist_err(ws):
         raise capi.S2VTHipError("persistent recurrence: a hand-off wait timed out (workgroups not co-resident?)")
 
 
-def lstm_seq_bwd_bf16(w_hh, dh_out, dh_first, c_all, gates, T, B, H, persistent=False, block=0):
-    """Config-3 arithmetic of one layer's BPTT: returns fp32 dG [T*B,4H] (`gates` is left untouched)."""
+def lstm_seq_bwd_bf16(w_hh, dh_out, dh_first, c_all, gates, T, B, H, persistent=False, block=0, poison=False, return_workspace=False):
+    """Config-3 arithmetic of one layer's BPTT: returns fp32 dG [T*B,4H] (`gates` is left untouched).  poison / return_workspace
+    as in lstm_seq_fwd_bf16 (then (dG, workspace) is returned)."""
     lib = capi.load()
     dev = w_hh.device
     dg = _f32c(gates, "gates").clone()
     with torch.cuda.device(dev):
         nbytes = lib.s2vt_lstm_seq_bwd_bf16_workspace_bytes(T, B, H)
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        ws = _bf16_workspace(nbytes, dev, poison)
         capi.check(lib.s2vt_lstm_seq_bwd_bf16(T, B, H, _ptr(_f32c(w_hh, "w_hh")), _ptr(dh_out), int(dh_first), _ptr(_f32c(c_all, "c_all")),
                                               _ptr(dg), _ptr(ws), nbytes, int(persistent), int(block), _stream(dev)),
                    "s2vt_lstm_seq_bwd_bf16")
         _check_persist_err(ws)
-    return dg
+    return (dg, ws) if return_workspace else dg
 
 
-def lstm_seq_bwd_bf16_pair(w0, w1, dh0, dh1, dh_first, c0, c1, gates0, gates1, T, B, H, block=0):
+def lstm_seq_bwd_bf16_pair(w0, w1, dh0, dh1, dh_first, c0, c1, gates0, gates1, T, B, H, block=0, poison=False, return_workspace=False):
+    """Two layers' BPTT, every block of both in ONE persistent launch: returns (dG0, dG1) (and, return_workspace, the workspace)."""
     lib = capi.load()
     dev = w0.device
     dg0, dg1 = _f32c(gates0, "gates0").clone(), _f32c(gates1, "gates1").clone()
     with torch.cuda.device(dev):
         nbytes = 2 * lib.s2vt_lstm_seq_bwd_bf16_workspace_bytes(T, B, H)
-        ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        ws = _bf16_workspace(nbytes, dev, poison)
         capi.check(lib.s2vt_lstm_seq_bwd_bf16_pair(T, B, H, _ptr(_f32c(w0, "w0")), _ptr(_f32c(w1, "w1")), _ptr(dh0), _ptr(dh1),
                                                    int(dh_first), _ptr(_f32c(c0, "c0")), _ptr(_f32c(c1, "c1")), _ptr(dg0), _ptr(dg1),
                                                    _ptr(ws), nbytes, int(block), _stream(dev)), "s2vt_lstm_seq_bwd_bf16_pair")
         _check_persist_err(ws)
-    return dg0, dg1
+    return (dg0, dg1, ws) if return_workspace else (dg0, dg1)
 
 
 def lstm_seq_fwd_persist(T, B, gx, n_gx, bias, w_hh, block=0, second=None, poison=True):

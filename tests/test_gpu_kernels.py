@@ -1012,20 +1012,8 @@ def _check_seq_bf16_teacher_forced(h_all, c_all, gates, gx, n_gx, bias, w_hh, T,
     """Every step checked on its own against fp64 math on the bf16-rounded operands the kernel itself saw: the h the
     kernel wrote for step t-1 (rounded to bf16 as the kernel rounds it) and its fp32 c_{t-1}.  A wrong k mapping, a
     stale or torn hand-off of h_{t-1}, a lost row or column shows as an O(0.1) error; fp32 accumulation order as ~1e-6."""
-    wb = _bf16r(w_hh.cpu())
-    h_all, c_all, gates = h_all.cpu().double(), c_all.cpu().double(), gates.cpu().double()
-    gx, bias = gx.cpu().double(), bias.cpu().double()
-    worst = 0.0
-    for t in range(T):
-        hp = _bf16r(h_all[(t - 1) * B:t * B].float()) if t else torch.zeros(B, H, dtype=torch.float64)
-        cp = c_all[(t - 1) * B:t * B] if t else torch.zeros(B, H, dtype=torch.float64)
-        pre = (gx[t * B:(t + 1) * B] if t < n_gx else bias[None, :]) + hp @ wb.t()
-        i, f, g, o = pre.chunk(4, dim=1)
-        i, f, g, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(g), torch.sigmoid(o)
-        c = f * cp + i * g
-        h = o * torch.tanh(c)
-        worst = max(worst, (h_all[t * B:(t + 1) * B] - h).abs().max().item(), (c_all[t * B:(t + 1) * B] - c).abs().max().item(),
-                    (gates[t * B:(t + 1) * B] - torch.cat([i, f, g, o], dim=1)).abs().max().item())
+    import bf16_recur_ref            # (the restatement lives there: tests/test_bf16_recur_ref_host.py holds it to the fp64 layer)
+    worst = bf16_recur_ref.fwd_teacher_forced(h_all, c_all, gates, gx, n_gx, bias, w_hh, T, B, H)["worst"]
     assert worst < tol, worst
     return worst
 
