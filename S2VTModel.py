@@ -203,6 +203,46 @@ class S2VT(nn.Module):
         k, p = _sampling.check_truncation(top_k, top_p, self.vocab_size)
         return self._sample(feats, n_samples, temperature, seed, k, p)
 
+    @torch.no_grad()
+    def decode_constrained(self, feats, n_samples=1, temperature=None, seed=None, top_k=0, top_p=1.0, no_repeat_ngram_size=0,
+                           repetition_penalty=1.0, min_length=0, banned_ids=None):
+        """Greedy or sampled decoding under constraints (not in the reference): ids int64 [B, n_samples, L-1] on the device, never
+        stopping at <eos> (callers cut behind it).  Per step, on the raw logits of a row and in this order (the rule: sampling.py,
+        include/s2vt_hip.h "constrained draw"): the repetition penalty (every distinct word generated so far: a positive logit is
+        divided by repetition_penalty, any other multiplied), no-repeat n-gram blocking (a word that would complete an n-gram the
+        row already holds gets -inf), the banned ids (-inf), and <eos> at -inf during the first min_length words.  Then the arg-max
+        (temperature=None: greedy, which needs n_samples == 1, top_k == 0, top_p == 1.0) or `sample_truncated`'s draw with the same
+        rows and noise.  The constraints run inside the row kernel of csrc/truncate.hip behind the logits GEMM: the one-layer LSTM
+        in `sample`'s driver (s2vt_decode_rows_constrained), a GRU or stacked model in its step loop on the repeated clips.  With
+        the constraints at their defaults nothing is constrained: greedy returns mode='test' (with a middle axis of 1), sampled
+        what `sample_truncated` returns.  Not covered: mode='beam' (a hypothesis's history runs through back-pointers),
+        Att_Baseline, scheduled sampling, dp.py.  No gradient.
+        :param no_repeat_ngram_size: an int >= 0; 0: off, 1: no word twice
+        :param repetition_penalty: finite and >= 1; 1.0: off
+        :param min_length: an int >= 0: no <eos> among the first min_length words
+        :param banned_ids: up to 32 word ids that are never generated
+        """
+        greedy = temperature is None
+        K = _sampling.check_n_samples(n_samples)
+        k, p = _sampling.check_truncation(top_k, top_p, self.vocab_size)
+        if greedy and (K != 1 or k != 0 or p != 1.0):
+            raise ValueError("greedy decoding (temperature=None) needs n_samples == 1, top_k == 0 and top_p == 1.0")
+        spec = _sampling.check_constraints(no_repeat_ngram_size, repetition_penalty, min_length, banned_ids, self.vocab_size, self.eos_ix,
+                                           length=self.length)
+        t, s = (1.0, 0) if greedy else _sampling.check_sample_args(temperature, seed)
+        _F.require_hip(feats, "feats")
+        if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
+            raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        if not _sampling.constrains(spec):                 # nothing to constrain: today's calls
+            return self(feats, mode='test').unsqueeze(1) if greedy else self._sample(feats, K, t, s, k, p)
+        B = feats.shape[0]
+        if _G.is_gru_model(self) or _S.is_stacked_lstm_model(self):
+            decode = _G.greedy_decode if _G.is_gru_model(self) else _S.greedy_decode
+            rows = self.feat_drop(feats).repeat_interleave(K, 0)
+            smp = None if greedy else ((t, s, k, p) if _sampling.truncates(k, p, self.vocab_size) else (t, s))
+            return decode(self, rows, self.sos_ix, sample=smp, constraints=spec).view(B, K, -1)
+        return _sampling.sample_rows(self, self.feat_drop(feats), self._hip_params(), K, t, s, k, p, constraints=(spec, greedy))
+
     def _sample(self, feats, n_samples, temperature, seed, k, p):
         K = _sampling.check_n_samples(n_samples)
         t, s = _sampling.check_sample_args(temperature, seed)

@@ -9,7 +9,8 @@ BLEU-1..4, ROUGE-L, CIDEr.  METEOR and the Stanford tokenizer are Java jars the 
 (`.MISSING_LARGE_BLOBS`); see caption_metrics.py for what stands in for them.  --perplexity scores the split's reference captions
 under the model instead (mode='score', not in the reference): per-word perplexity and per-reference log-likelihoods.
 --sample K additionally writes K sampled captions per clip (S2VT.sample_truncated, not in the reference; --temperature, --top-k, --top-p,
---sample-seed) to <out>.samples.json.
+--sample-seed) to <out>.samples.json.  --no-repeat-ngram / --repetition-penalty / --min-length / --ban-words constrain the greedy captions
+and those of --sample (S2VT.decode_constrained, not in the reference); they are refused together with --beam.
 """
 import argparse
 import json
@@ -28,9 +29,10 @@ def ids_to_caption(ids, ix2word, drop_sos=False):
 
 
 def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', beam_width=5, max_beam_depth=30,
-             split='test', device=None, length_alpha=0.7, n_best=1, nbest=None):
+             split='test', device=None, length_alpha=0.7, n_best=1, nbest=None, constraints=None):
     """{video_id: caption} of a split.  mode: 'test' (greedy), 'beam_search' (the reference's search) or 'beam' (cumulative scores,
-    length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]})."""
+    length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]}).  constraints (mode 'test'
+    only): keyword arguments of S2VT.decode_constrained, with `ban_words` looked up in the split's word2ix."""
     import dataloader
     dev = device or torch.device('cuda', 0)
     dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
@@ -39,6 +41,7 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
     model.eval()
     if mode in ('beam_search', 'beam'):                                 # old pickles lack these attrs (eval.py:84-86)
         model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
+    con = constraint_kwargs(constraints, dataset.word2ix, model)
     preds = {}
     with torch.no_grad():
         for feats, targets, ids, masks in dataloader.feed_batches(loader, dev):
@@ -56,14 +59,31 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                     if nbest is not None:
                         nbest[vid] = caps
             else:
-                out = model(feats, mode='test').cpu()
+                out = (model.decode_constrained(feats, **con)[:, 0] if con else model(feats, mode='test')).cpu()
                 for vid, seq in zip(ids, out):
                     preds[vid] = ids_to_caption(seq.tolist(), dataset.ix2word)
     return preds
 
 
+def constraint_kwargs(constraints, word2ix, model):
+    """The keyword arguments of S2VT.decode_constrained for the command line's constraints ({} where there are none): `ban_words`
+    become banned_ids through word2ix (an unknown word is an error), and <eos> is the vocabulary's."""
+    if not constraints:
+        return {}
+    con = dict(constraints)
+    words = con.pop("ban_words", None) or []
+    unknown = [w for w in words if w not in word2ix]
+    if unknown:
+        raise ValueError("--ban-words: not in the vocabulary: %s" % ", ".join(unknown))
+    con["banned_ids"] = [int(word2ix[w]) for w in words]
+    if not hasattr(model, "decode_constrained"):
+        raise NotImplementedError("constrained decoding needs S2VT.decode_constrained; %s has none" % type(model).__name__)
+    model.eos_ix = word2ix.get('<eos>', 4)                              # (old pickles lack the attribute, as for the beam modes)
+    return con
+
+
 def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=10, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                    split='test', device=None):
+                    split='test', device=None, constraints=None):
     """{video_id: [n_samples captions]} of a split, drawn by S2VT.sample_truncated (one encode per clip; top_k / top_p cut every step's
     distribution, 0 / 1.0: off), each cut at its first <eos> like a greedy caption.  Batch i draws with seed + i."""
     import dataloader
@@ -72,11 +92,12 @@ def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=
     loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
     model = torch.load(model_path, weights_only=False).to(dev)
     model.eval()
+    con = constraint_kwargs(constraints, dataset.word2ix, model)
+    draw = model.decode_constrained if con else model.sample_truncated
     out = {}
     with torch.no_grad():
         for i, (feats, targets, ids, masks) in enumerate(dataloader.feed_batches(loader, dev)):
-            drawn = model.sample_truncated(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k,
-                                           top_p=top_p).cpu().tolist()
+            drawn = draw(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k, top_p=top_p, **con).cpu().tolist()
             for vid, rows in zip(ids, drawn):
                 out[vid] = [ids_to_caption(r, dataset.ix2word) for r in rows]
     return out
@@ -175,13 +196,31 @@ def build_parser():
     ap.add_argument("--top-p", type=float, default=1.0,
                     help="--sample: draw from the smallest set of most probable words whose mass reaches p (1: off)")
     ap.add_argument("--sample-seed", type=int, default=0, help="--sample: batch i draws with this seed + i")
+    ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
+                    help="greedy and --sample: never complete an n-gram the caption already holds (0: off; not with --beam)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0, metavar="THETA",
+                    help="greedy and --sample: divide the positive logits of the words generated so far by THETA, multiply the others (1: off)")
+    ap.add_argument("--min-length", type=int, default=0, metavar="M", help="greedy and --sample: no <eos> among the first M words")
+    ap.add_argument("--ban-words", default="", metavar="W1,W2", help="greedy and --sample: words that are never generated, e.g. \"<unk>,<pad>\"")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
     return ap
 
 
+def constraints_of(a):
+    """the constraint flags of parsed arguments as a dict, or None where none is set"""
+    words = [w for w in a.ban_words.split(",") if w]
+    if a.no_repeat_ngram == 0 and a.repetition_penalty == 1.0 and a.min_length == 0 and not words:
+        return None
+    return dict(no_repeat_ngram_size=a.no_repeat_ngram, repetition_penalty=a.repetition_penalty, min_length=a.min_length, ban_words=words)
+
+
 def main(argv=None):
-    a = build_parser().parse_args(argv)
+    ap = build_parser()
+    a = ap.parse_args(argv)
+    constraints = constraints_of(a)
+    if constraints and a.beam:
+        ap.error("--no-repeat-ngram / --repetition-penalty / --min-length / --ban-words apply to greedy decoding and --sample, not to --beam")
     if a.perplexity:
         per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
         print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "
@@ -193,7 +232,7 @@ def main(argv=None):
     nbest = {} if cumulative and a.n_best > 1 else None
     preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
                      ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
-                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest)
+                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints)
     with open(a.out, 'w', encoding='utf-8') as f:
         json.dump(preds, f, ensure_ascii=False, indent=1)
     print("wrote {} captions to {}".format(len(preds), a.out))
@@ -202,7 +241,7 @@ def main(argv=None):
             json.dump(nbest, f, ensure_ascii=False, indent=1)
     if a.sample > 0:
         samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
-                                  a.sample_seed)
+                                  a.sample_seed, constraints=constraints)
         with open(a.out + ".samples.json", 'w', encoding='utf-8') as f:
             json.dump(samples, f, ensure_ascii=False, indent=1)
         print("wrote {} sampled captions per clip to {}".format(a.sample, a.out + ".samples.json"))

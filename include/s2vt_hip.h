@@ -827,6 +827,53 @@ int s2vt_sample_decode_rows_trunc(const s2vt_dims* d, const s2vt_params* p, cons
                                   float temperature, uint64_t seed, int32_t top_k, float top_p, int64_t* ids, void* workspace,
                                   size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream);
 
+/* ---------------------------------------------------------------- constrained draw: what a decode must not generate
+ * (S2VT.decode_constrained(..., no_repeat_ngram_size=, repetition_penalty=, min_length=, banned_ids=); csrc/truncate.hip; restated in
+ * numpy by sampling.constrain_logits).  For one row at decode step t - t = the number of words already generated after <sos>, the
+ * history h[0..t), the logits x[0..V) in fp32 - the rules apply in this order to the RAW logits, before the temperature:
+ *   1. repetition penalty  theta >= 1 (1: off; the rule of CTRL, Keskar et al. 2019): once for every DISTINCT v of h, not once per
+ *               occurrence, x_v <- x_v * r if x_v > 0, else x_v * theta, with r = fp32(1.0 / (double)theta) computed on the host - a
+ *               multiplication, so the numpy restatement is bitwise.
+ *   2. no-repeat n-gram    n >= 0 (0: off; n = 1 bans every word of h): if t >= n - 1, for every i in [0, t - n] with
+ *               h[i .. i+n-2] == h[t-n+1 .. t-1]:  x[h[i+n-1]] <- -inf.
+ *   3. banned ids          (at most 32, each in [0, V)):  x_v <- -inf.
+ *   4. minimum length      m >= 0: if t < m, x[eos_ix] <- -inf.
+ * A ban wins over a penalty on the same v.  Then the pick:
+ *   greedy = 1  the arg-max of x, the lowest index wins a tie (-0 counts as +0); packed = ordered(x_v) << 32 | (0xFFFFFFFF - v); no
+ *               noise; temperature, top_k, top_p must be 1, 0, 1.
+ *   greedy = 0  steps 1-5 of the truncated draw above on the constrained row; the noise contract is unchanged.
+ * The index written is always in [0, V); if nothing survives, the truncated draw's fallback holds (the row maximum by key).  A row
+ * that has emitted <eos> is processed like any other: the decoders never stop at <eos>, callers cut behind it.
+ * THE CALL MODIFIES `logits`: the edits are made in place in the rows (one workgroup owns a row, exactly one thread writes an edited
+ * element), inside the row kernel's launch and in front of its load; afterwards the buffer holds the constrained rows.
+ * hist: the drivers' packed words, unsigned long long [t][hist_ld]; the token of row r at step i is 0xFFFFFFFF - the low half of
+ * hist[i * hist_ld + r].  May be null iff t == 0.  `banned` of s2vt_constraints is a HOST pointer: the ids are copied into the launch
+ * arguments, no device allocation is made.
+ * Checked on the host before anything is enqueued (S2VT_ERR_ARG; s2vt_last_error names the rule): repetition_penalty finite and
+ * >= 1; no_repeat_ngram >= 0; min_length >= 0; n_banned in [0, 32]; every banned id and eos_ix in [0, V); t in [0, 1023]; hist_ld
+ * >= rows where t > 0; the truncated draw's rules; greedy in {0, 1} and the greedy rule above. */
+typedef struct s2vt_constraints {
+    int32_t no_repeat_ngram;
+    float repetition_penalty;
+    int32_t min_length;
+    int32_t eos_ix;
+    int32_t n_banned;
+    const int32_t* banned; /* host memory, n_banned ids; may be null when n_banned == 0 */
+} s2vt_constraints;
+int s2vt_constrained_draw(float* logits, int64_t ld, int64_t rows, int32_t V, const unsigned long long* hist, int64_t hist_ld, int32_t t,
+                          const s2vt_constraints* c, int32_t greedy, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                          int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream);
+/* s2vt_sample_decode_rows_trunc with a greedy flag and the constraints: at step j the head is the logits GEMM (plane path or
+ * fp32-input path, as there) and the constrained draw over the driver's own packed words (hist_ld = rows64(B*K), t = j).  K >= 1;
+ * greedy needs temperature 1, top_k 0, top_p 1.  With every constraint off (n = 0, theta = 1, m = 0, no banned id) the call runs
+ * today's launches: greedy the fused arg-max head, sampled exactly what s2vt_sample_decode_rows_trunc runs.  A shape that could ban a
+ * whole row is refused: V > (L - 1) + n_banned + 1 is required, and L - 1 <= 1024 (t <= 1023).  The workspace is the truncated one. */
+size_t s2vt_decode_rows_constrained_workspace_bytes(const s2vt_dims* d, int32_t K);
+int s2vt_decode_rows_constrained(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, int32_t greedy,
+                                 float temperature, uint64_t seed, int32_t top_k, float top_p, const s2vt_constraints* c, int64_t* ids,
+                                 void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
+                                 void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

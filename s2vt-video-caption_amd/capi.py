@@ -51,6 +51,12 @@ class CiderTable(ctypes.Structure):
                                                    ("n_pen", c_int32)]
 
 
+class Constraints(ctypes.Structure):
+    """s2vt_constraints of include/s2vt_hip.h: what a constrained draw must not generate (`banned` is a HOST pointer)"""
+    _fields_ = [("no_repeat_ngram", c_int32), ("repetition_penalty", c_float), ("min_length", c_int32), ("eos_ix", c_int32),
+                ("n_banned", c_int32), ("banned", POINTER(c_int32))]
+
+
 CIDER_MAX_T = 512        # S2VT_CIDER_MAX_T of include/s2vt_hip.h
 
 # name -> (restype, argtypes): every symbol include/s2vt_hip.h declares
@@ -206,6 +212,12 @@ SIGNATURES = {
     "s2vt_sample_rows_trunc_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
     "s2vt_sample_decode_rows_trunc": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_int32, c_float, c_uint64, c_int32,
                                                 c_float, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32, c_void_p]),
+    "s2vt_constrained_draw": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Constraints), c_int32, c_float,
+                                        c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "s2vt_decode_rows_constrained_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32]),
+    "s2vt_decode_rows_constrained": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_int32, c_int32, c_float, c_uint64, c_int32,
+                                               c_float, POINTER(Constraints), c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32,
+                                               c_void_p]),
     "s2vt_scheduled_decode": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float, c_uint64,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_scheduled_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_float, c_int32, c_float,

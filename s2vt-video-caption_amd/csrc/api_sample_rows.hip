@@ -7,6 +7,9 @@
 // s2vt_sample_decode_rows_trunc: the same driver with top-k / nucleus truncation - per step the head is replaced by out_linear as
 // the beam step runs it (the plane GEMM on the cache's W_o image, or the fp32-input GEMM) into a [Rp, V] buffer of the workspace and
 // the truncated draw of truncate.hip over its rows; with nothing to truncate it runs the fused head, launch for launch.
+// s2vt_decode_rows_constrained: the same driver again with a greedy flag and the constraints of the constrained draw (S2VT.
+// decode_constrained) - the head is the logits GEMM and truncate.hip's constrained row kernel, which reads the rows' history from
+// this driver's own packed words (w.packed, stride Rp, t = the step); with every constraint off, the fused heads.
 #include "api_internal.h"
 
 using namespace s2vt;
@@ -55,9 +58,47 @@ size_t s2vt_sample_rows_trunc_workspace_bytes(const s2vt_dims* d, int32_t K) {
 }
 }  // extern "C"
 
-// Both entry points (fn names the one that was called).  trunc: the workspace has the logits buffer and a step's head is the logits
+// The constraints of the constrained draw (include/s2vt_hip.h "constrained draw"), checked on the host: 0 and `out` filled in for
+// step t (the caller sets hist / hist_ld / t / eos per step: constrain_at), or S2VT_ERR_ARG with the refusing rule in the message.
+static int check_constraints(const char* fn, const s2vt_constraints* c, int V, int32_t greedy, float temperature, int32_t top_k, float top_p,
+                             ConstrainArgs* out) {
+    S2VT_REQUIRE(c, "%s: null constraints", fn);
+    S2VT_REQUIRE(c->repetition_penalty >= 1.f && c->repetition_penalty <= 3.4028234e38f,
+                 "%s: repetition_penalty must be finite and >= 1 (got %g)", fn, (double)c->repetition_penalty);
+    S2VT_REQUIRE(c->no_repeat_ngram >= 0, "%s: no_repeat_ngram %d < 0", fn, (int)c->no_repeat_ngram);
+    S2VT_REQUIRE(c->min_length >= 0, "%s: min_length %d < 0", fn, (int)c->min_length);
+    S2VT_REQUIRE(c->n_banned >= 0 && c->n_banned <= 32 && (c->n_banned == 0 || c->banned), "%s: n_banned %d outside [0, 32] (or null banned)",
+                 fn, (int)c->n_banned);
+    for (int i = 0; i < c->n_banned; ++i)
+        S2VT_REQUIRE(c->banned[i] >= 0 && c->banned[i] < V, "%s: banned id %d outside [0, V = %d)", fn, (int)c->banned[i], V);
+    S2VT_REQUIRE(c->eos_ix >= 0 && c->eos_ix < V, "%s: eos_ix %d outside [0, V = %d)", fn, (int)c->eos_ix, V);
+    S2VT_REQUIRE(greedy == 0 || greedy == 1, "%s: greedy must be 0 or 1 (got %d)", fn, (int)greedy);
+    S2VT_REQUIRE(!greedy || (temperature == 1.f && top_k == 0 && top_p == 1.f),
+                 "%s: greedy needs temperature 1, top_k 0 and top_p 1 (got %g, %d, %g)", fn, (double)temperature, (int)top_k, (double)top_p);
+    memset(out, 0, sizeof(*out));
+    out->ngram = c->no_repeat_ngram;
+    out->theta = c->repetition_penalty;
+    out->inv_theta = (float)(1.0 / (double)c->repetition_penalty);
+    out->eos = -1;
+    out->n_banned = c->n_banned;
+    for (int i = 0; i < c->n_banned; ++i) out->banned[i] = c->banned[i];
+    return 0;
+}
+static bool constraints_off(const s2vt_constraints* c) {
+    return c->no_repeat_ngram == 0 && c->repetition_penalty == 1.f && c->min_length == 0 && c->n_banned == 0;
+}
+static ConstrainArgs constrain_at(ConstrainArgs a, const s2vt_constraints* c, const unsigned long long* hist, int64_t hist_ld, int t) {
+    a.hist = t > 0 ? hist : nullptr; a.hist_ld = hist_ld; a.t = t;
+    a.eos = t < c->min_length ? c->eos_ix : -1;
+    return a;
+}
+
+// All three entry points (fn names the one that was called).  trunc: the workspace has the logits buffer and a step's head is the logits
 // GEMM + the truncated draw - unless top_k / top_p truncate nothing, which runs the fused head like the plain entry point.
-static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_p, const s2vt_dims* d, const s2vt_params* p,
+// con: s2vt_decode_rows_constrained - a greedy flag and the constraints on top of trunc; with every constraint off it runs the
+// fused heads (greedy: the arg-max, no noise) or what trunc runs.
+static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_p, const s2vt_constraints* con, int32_t greedy,
+                           const s2vt_dims* d, const s2vt_params* p,
                            const float* feats, int32_t K, int32_t sos_ix, float temperature, uint64_t seed, int64_t* ids, void* workspace,
                            size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream) {
     S2VT_REQUIRE(dims_ok(d) && p && feats && ids && workspace, "%s: null/invalid argument", fn);
@@ -70,6 +111,16 @@ static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_
         S2VT_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0, 1] (got %g)", fn, (double)top_p);
         S2VT_REQUIRE(trunc_vocab_ok(d), "%s: vocab_size %d > 38400", fn, d->V);
     }
+    ConstrainArgs ca = {};
+    if (con || greedy) {
+        int rc0;
+        if ((rc0 = check_constraints(fn, con, d->V, greedy, temperature, top_k, top_p, &ca))) return rc0;
+        S2VT_REQUIRE(d->L - 1 <= 1024, "%s: length %d: the history of a step holds at most 1023 words", fn, d->L);
+        S2VT_REQUIRE((int64_t)d->V > (int64_t)(d->L - 1) + con->n_banned + 1,
+                     "%s: vocab_size %d <= (L - 1) + n_banned + 1 = %d: the constraints could ban a whole row", fn, d->V,
+                     (int)(d->L - 1 + con->n_banned + 1));
+    }
+    const bool constrained = con && !constraints_off(con);
     const bool cut = trunc && ((top_k > 0 && top_k < d->V) || top_p < 1.f);
     const SampleRowsWS w = carve_sample_rows(*d, K, workspace, trunc);
     S2VT_REQUIRE(workspace_bytes >= w.bytes, "%s: workspace %zu < %zu bytes", fn, workspace_bytes, w.bytes);
@@ -119,7 +170,7 @@ static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_
         }
         hprev = a.h_out;
         const GumbelArgs g = gumbel_args(temperature, seed, (uint32_t)j, 0u, (uint32_t)R);
-        if (cut) {
+        if (cut || constrained) {
             // out_linear as the beam step runs it (api_beam.hip), then the row kernel: it STORES the rows' packed words
             const Lane ln{st, w.gws, w.gws_floats, nullptr};
             {
@@ -129,7 +180,11 @@ static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_
             }
             if (rc) return rc;
             ProfScope ps(st, K_ARGMAX, 1);
-            if ((rc = truncated_draw(st, w.logits, V, R, V, top_k, top_p, g, packed, nullptr))) return rc;
+            // (constrained: the rows' history is the driver's own packed words of the steps before, [j][Rp])
+            rc = constrained ? constrained_draw(st, w.logits, V, R, V, constrain_at(ca, con, w.packed, Rp, j), greedy != 0, top_k, top_p, g,
+                                                packed, nullptr)
+                             : truncated_draw(st, w.logits, V, R, V, top_k, top_p, g, packed, nullptr);
+            if (rc) return rc;
             continue;
         }
         ProfScope ps(st, K_ARGMAX, 1);
@@ -141,13 +196,13 @@ static int sample_rows_run(const char* fn, bool trunc, int32_t top_k, float top_
             ax.Hp = w.himg.p; ax.ldh = w.himg.ld;
             ax.bias = p->out_b;
             ax.packed = packed;
-            rc = logits_argmax_x3(st, ax, &g);
+            rc = logits_argmax_x3(st, ax, greedy ? nullptr : &g);
         } else {
             LogitsArgmaxArgs la;
             la.B = R; la.H = H; la.V = V; la.h = a.h_out; la.ldh = H; la.w_out = p->out_w; la.ldw = H; la.b_out = p->out_b;
             la.packed = packed;
             la.stamps = nullptr;
-            rc = logits_argmax(st, la, &g);
+            rc = logits_argmax(st, la, greedy ? nullptr : &g);
         }
         if (rc) return rc;
     }
@@ -160,14 +215,43 @@ extern "C" {
 int s2vt_sample_decode_rows(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, float temperature,
                             uint64_t seed, int64_t* ids, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                             int32_t cache_valid, void* stream) {
-    return sample_rows_run("s2vt_sample_decode_rows", false, 0, 1.f, d, p, feats, K, sos_ix, temperature, seed, ids, workspace,
+    return sample_rows_run("s2vt_sample_decode_rows", false, 0, 1.f, nullptr, 0, d, p, feats, K, sos_ix, temperature, seed, ids, workspace,
                            workspace_bytes, cache, cache_bytes, cache_valid, stream);
 }
 int s2vt_sample_decode_rows_trunc(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix,
                                   float temperature, uint64_t seed, int32_t top_k, float top_p, int64_t* ids, void* workspace,
                                   size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid, void* stream) {
-    return sample_rows_run("s2vt_sample_decode_rows_trunc", true, top_k, top_p, d, p, feats, K, sos_ix, temperature, seed, ids,
+    return sample_rows_run("s2vt_sample_decode_rows_trunc", true, top_k, top_p, nullptr, 0, d, p, feats, K, sos_ix, temperature, seed, ids,
                            workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream);
+}
+size_t s2vt_decode_rows_constrained_workspace_bytes(const s2vt_dims* d, int32_t K) { return s2vt_sample_rows_trunc_workspace_bytes(d, K); }
+int s2vt_decode_rows_constrained(const s2vt_dims* d, const s2vt_params* p, const float* feats, int32_t K, int32_t sos_ix, int32_t greedy,
+                                 float temperature, uint64_t seed, int32_t top_k, float top_p, const s2vt_constraints* c, int64_t* ids,
+                                 void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
+                                 void* stream) {
+    S2VT_REQUIRE(c, "s2vt_decode_rows_constrained: null constraints");
+    return sample_rows_run("s2vt_decode_rows_constrained", true, top_k, top_p, c, greedy, d, p, feats, K, sos_ix, temperature, seed, ids,
+                           workspace, workspace_bytes, cache, cache_bytes, cache_valid, stream);
+}
+int s2vt_constrained_draw(float* logits, int64_t ld, int64_t rows, int32_t V, const unsigned long long* hist, int64_t hist_ld, int32_t t,
+                          const s2vt_constraints* c, int32_t greedy, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                          int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream) {
+    const char* fn = "s2vt_constrained_draw";
+    S2VT_REQUIRE(logits && packed && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V && step >= 0 && row0 >= 0,
+                 "%s: null/invalid argument", fn);
+    S2VT_REQUIRE((size_t)V * sizeof(float) <= 150 * 1024, "%s: vocab_size %d > 38400", fn, (int)V);
+    S2VT_REQUIRE(temperature_ok(temperature), "%s: temperature and 1 / temperature must be finite and > 0 (got %g)", fn, (double)temperature);
+    S2VT_REQUIRE(top_k >= 0 && top_k <= V, "%s: top_k %d outside [0, V = %d]", fn, (int)top_k, (int)V);
+    S2VT_REQUIRE(top_p > 0.f && top_p <= 1.f, "%s: top_p must be in (0, 1] (got %g)", fn, (double)top_p);
+    ConstrainArgs ca;
+    int rc;
+    if ((rc = check_constraints(fn, c, V, greedy, temperature, top_k, top_p, &ca))) return rc;
+    S2VT_REQUIRE(t >= 0 && t <= 1023, "%s: t %d outside [0, 1023]", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist, "%s: null history at t = %d", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist_ld >= rows, "%s: hist_ld %lld < rows %lld", fn, (long long)hist_ld, (long long)rows);
+    ProfScope ps((hipStream_t)stream, K_ARGMAX, 1);
+    return constrained_draw((hipStream_t)stream, logits, ld, rows, V, constrain_at(ca, c, hist, hist_ld, t), greedy != 0, top_k, top_p,
+                            gumbel_args(temperature, seed, (uint32_t)step, (uint32_t)row0, (uint32_t)row0 + (uint32_t)rows), packed, kept);
 }
 int s2vt_top20_logprob(const float* logits, int64_t ld, int64_t rows, int32_t V, int32_t* top_ix, float* top_lp, void* stream) {
     S2VT_REQUIRE(logits && top_ix && top_lp && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V, "s2vt_top20_logprob: null/invalid argument");

@@ -392,6 +392,21 @@ int score_finish(hipStream_t s, const float* lp, const int32_t* tok, int R, int 
 bool truncation_ok(int top_k, float top_p, int V);       // top_k in [0, V], top_p in (0, 1] (NaN: no)
 int truncated_draw(hipStream_t s, const float* logits, int64_t ld, int64_t rows, int V, int top_k, float top_p, const GumbelArgs& ga,
                    unsigned long long* packed, int32_t* kept);
+// the constrained draw (include/s2vt_hip.h "constrained draw"): the row kernel above with the constraint phase in front of its
+// load - the rows of `logits` are EDITED IN PLACE - and, greedy, the plain arg-max in place of the draw.  Passed to the kernel by
+// value: the banned ids travel in the launch arguments.
+struct ConstrainArgs {
+    const unsigned long long* hist;  // [t][hist_ld] packed words, the row's at column r; null iff t == 0
+    int64_t hist_ld;
+    int t;                           // words generated so far, <= 1023
+    int ngram;                       // 0: off
+    float theta, inv_theta;          // repetition penalty (1: off) and fp32(1.0 / (double)theta)
+    int eos;                         // eos_ix while t < min_length, else -1
+    int n_banned;                    // <= 32
+    int banned[32];
+};
+int constrained_draw(hipStream_t s, float* logits, int64_t ld, int64_t rows, int V, const ConstrainArgs& c, bool greedy, int top_k,
+                     float top_p, const GumbelArgs& ga, unsigned long long* packed, int32_t* kept);
 // fp32(len ** alpha) for len = 0..D (len 0: 1), libm double pow then fp32, in pinned host memory that lives for the life of the
 // process (beam_cum.hip: the power rule of mode='beam'); null when no pinned memory is left
 const float* length_pow_table(double alpha, int D);

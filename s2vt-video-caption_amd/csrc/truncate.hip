@@ -1,3 +1,4 @@
+// (Behind the truncated draw, in this file: the constrained draw - the same row kernel with a constraint phase in front of its load.)
 // Top-k / nucleus (top-p) truncation ahead of the sampled draw (include/s2vt_hip.h "truncated draw" states the definition;
 // sampling.truncation_mask restates it in numpy).  The fused sampling heads never hold a logits row, so no element knows its rank;
 // here the row exists ([rows, V] fp32 from the logits GEMM) and ONE 256-thread workgroup per row holds it - in registers
@@ -68,8 +69,9 @@ struct TruncArgs {
     int32_t* kept;                   // [rows] or null
 };
 
+// The body of both row kernels below: steps 1-5 of the truncated draw on the row the workgroup owns.
 template <class Row>
-__global__ __launch_bounds__(256) void truncated_draw_kernel(TruncArgs p, GumbelArgs ga) {
+__device__ __forceinline__ void truncated_draw_row(const TruncArgs& p, const GumbelArgs& ga) {
     __shared__ float red_f[8];
     __shared__ int red_i[8];
     __shared__ unsigned long long red_w[4];
@@ -159,6 +161,139 @@ __global__ __launch_bounds__(256) void truncated_draw_kernel(TruncArgs p, Gumbel
         p.packed[blockIdx.x] = w;
         if (p.kept) p.kept[blockIdx.x] = nkept;
     }
+}
+
+template <class Row>
+__global__ __launch_bounds__(256) void truncated_draw_kernel(TruncArgs p, GumbelArgs ga) {
+    truncated_draw_row<Row>(p, ga);
+}
+
+// ---- the constrained draw (include/s2vt_hip.h "constrained draw"; sampling.constrain_logits restates it in numpy): repetition
+// penalty, no-repeat n-gram blocking, banned ids and a minimum length, applied to the RAW logits row IN PLACE in global memory in
+// front of the load - the same launch, the same workgroup per row; then either the truncated draw above on the edited row or the
+// plain arg-max (GREEDY: no noise, no bisection).  The row's history h[0..t) comes from the drivers' packed words.
+//   candidates   c in [0, C), C = t + n_banned (+ 1): the t history tokens, the banned ids, <eos> while t < min_length - kept in
+//                static LDS (tok) with one flag byte each (ban): the "edit list"
+//   n-gram       one thread per start position i in [0, t - n]: n - 1 compares of h[i ..] against the suffix h[t-n+1 ..]; a match
+//                flags position i + n - 1 (its own byte: no two threads write one)
+//   edit         one thread per candidate c scans the list once: an EARLIER candidate with the same token owns the element (this
+//                thread leaves), otherwise c is the element's only writer - it ORs the ban flags of every candidate with its token,
+//                and writes -inf (a ban wins) or, where the token is in the history, the penalised value
+// One barrier behind the stores orders them against the loads of row.load_max for the whole workgroup (its waves share a compute
+// unit and its vector cache; not a threadgroup-split build).  Every loop runs to t, n, C or a compile-time count.  Tokens outside
+// [0, V) (a history that no driver wrote) are matched like any other but never stored to.
+// LDS: 1057 * 5 bytes here + 96 of the draw - beside LdsRow's 150 KiB inside the 160 KiB of a workgroup.
+constexpr int CONSTRAIN_MAX_T = 1023, CONSTRAIN_MAX_BANNED = 32;
+constexpr int CONSTRAIN_MAX_C = CONSTRAIN_MAX_T + CONSTRAIN_MAX_BANNED + 1;
+
+template <class Row>
+__device__ __forceinline__ void greedy_pick_row(const TruncArgs& p) {
+    __shared__ unsigned long long red_g[4];
+    const int V = p.V;
+    Row row;
+    row.load_max(p.logits + (int64_t)blockIdx.x * p.ld, V);
+    unsigned long long best = 0ull;
+    row.each(V, [&](int, int i, float& v) {
+        float s = v;
+        if (s == 0.f) s = 0.f;                             // (-0 -> +0: equal values have equal keys, the lowest index wins)
+        const unsigned long long w = ((unsigned long long)tr_key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+        best = w > best ? w : best;
+    });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(best, off);
+        best = o > best ? o : best;
+    }
+    if ((threadIdx.x & 63) == 0) red_g[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long w = red_g[0];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) w = red_g[k] > w ? red_g[k] : w;
+        p.packed[blockIdx.x] = w;
+        if (p.kept) p.kept[blockIdx.x] = V;
+    }
+}
+
+template <class Row, bool GREEDY>
+__global__ __launch_bounds__(256) void constrained_draw_kernel(TruncArgs p, GumbelArgs ga, ConstrainArgs c, float* x_rows) {
+    __shared__ int tok[CONSTRAIN_MAX_C];
+    __shared__ unsigned char ban[CONSTRAIN_MAX_C];
+    const int t = c.t, n = c.ngram, nb = c.n_banned, V = p.V;
+    const int C = t + nb + (c.eos >= 0 ? 1 : 0);
+    float* x = x_rows + (int64_t)blockIdx.x * p.ld;
+    if (n > 0 || nb > 0 || c.eos >= 0 || c.theta != 1.f) {      // (block-uniform; nothing to edit: the draw alone)
+        for (int i = threadIdx.x; i < C; i += 256) {
+            int v;
+            if (i < t) v = (int)(0xFFFFFFFFu - (uint32_t)(c.hist[(int64_t)i * c.hist_ld + blockIdx.x] & 0xFFFFFFFFull));
+            else if (i < t + nb) v = c.banned[i - t];
+            else v = c.eos;
+            tok[i] = v;
+            ban[i] = i < t ? 0 : 1;
+        }
+        __syncthreads();
+        if (n > 0) {
+            for (int i = threadIdx.x; i <= t - n; i += 256) {
+                bool same = true;
+                for (int k = 0; k < n - 1; ++k) same = same && tok[i + k] == tok[t - n + 1 + k];
+                if (same) ban[i + n - 1] = 1;
+            }
+            __syncthreads();
+        }
+        for (int i = threadIdx.x; i < C; i += 256) {
+            const int v = tok[i];
+            const bool valid = (unsigned)v < (unsigned)V;
+            const float xv = valid ? x[v] : 0.f;               // (issued in front of the scan: its latency runs beside it)
+            bool first = true, banned = false, seen = false;
+            // (no early exit: a plain reduction over the list, whose LDS reads the compiler batches)
+#pragma unroll 8
+            for (int k = 0; k < C; ++k) {
+                const bool same = tok[k] == v;
+                first = first && !(same && k < i);
+                banned = banned || (same && ban[k] != 0);
+                seen = seen || (same && k < t);
+            }
+            if (!(valid && first)) continue;
+            if (banned) x[v] = -INFINITY;
+            else if (seen && c.theta != 1.f) x[v] = xv > 0.f ? xv * c.inv_theta : xv * c.theta;
+        }
+        __syncthreads();                                       // the stores above -> the loads of load_max, workgroup scope
+    }
+    if constexpr (GREEDY) greedy_pick_row<Row>(p);
+    else truncated_draw_row<Row>(p, ga);
+}
+
+template <bool GREEDY>
+static int constrained_launch(hipStream_t s, const TruncArgs& a, const GumbelArgs& ga, const ConstrainArgs& c, float* x, int64_t rows) {
+    const int V = a.V;
+    const dim3 grid((unsigned)rows), block(256);
+    const size_t lds = (size_t)V * sizeof(float);          // (the LDS form's dynamic LDS)
+    if (V <= 256 * 16) hipLaunchKernelGGL((constrained_draw_kernel<RegRow<16>, GREEDY>), grid, block, 0, s, a, ga, c, x);
+    else if (V <= 256 * 32) hipLaunchKernelGGL((constrained_draw_kernel<RegRow<32>, GREEDY>), grid, block, 0, s, a, ga, c, x);
+    else if (V <= 256 * 48) hipLaunchKernelGGL((constrained_draw_kernel<RegRow<48>, GREEDY>), grid, block, 0, s, a, ga, c, x);
+    else if (V <= 256 * 64) hipLaunchKernelGGL((constrained_draw_kernel<RegRow<64>, GREEDY>), grid, block, 0, s, a, ga, c, x);
+    else {
+        if (lds > 48 * 1024)
+            S2VT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(constrained_draw_kernel<LdsRow, GREEDY>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((constrained_draw_kernel<LdsRow, GREEDY>), grid, block, lds, s, a, ga, c, x);
+    }
+    S2VT_LAUNCH_CHECK("constrained_draw_kernel");
+    return 0;
+}
+
+int constrained_draw(hipStream_t s, float* logits, int64_t ld, int64_t rows, int V, const ConstrainArgs& c, bool greedy, int top_k,
+                     float top_p, const GumbelArgs& ga, unsigned long long* packed, int32_t* kept) {
+    if (rows <= 0) return 0;
+    S2VT_REQUIRE(logits && packed && V > 0 && ld >= V && rows < (1ll << 31), "constrained_draw: bad arguments");
+    S2VT_REQUIRE((size_t)V * sizeof(float) <= 150 * 1024, "constrained_draw: vocab_size <= 38400");
+    S2VT_REQUIRE(truncation_ok(top_k, top_p, V), "constrained_draw: top_k in [0, V], top_p in (0, 1]");
+    S2VT_REQUIRE(c.t >= 0 && c.t <= CONSTRAIN_MAX_T && c.n_banned >= 0 && c.n_banned <= CONSTRAIN_MAX_BANNED && c.ngram >= 0 &&
+                     c.eos < V && (c.t == 0 || (c.hist && c.hist_ld >= rows)),
+                 "constrained_draw: bad constraints");
+    for (int i = 0; i < c.n_banned; ++i) S2VT_REQUIRE(c.banned[i] >= 0 && c.banned[i] < V, "constrained_draw: banned id outside [0, V)");
+    const TruncArgs a{logits, ld, V, top_k, top_p, packed, kept};
+    return greedy ? constrained_launch<true>(s, a, ga, c, logits, rows) : constrained_launch<false>(s, a, ga, c, logits, rows);
 }
 
 bool truncation_ok(int top_k, float top_p, int V) { return top_k >= 0 && top_k <= V && top_p > 0.f && top_p <= 1.f; }

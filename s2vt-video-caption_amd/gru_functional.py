@@ -96,10 +96,12 @@ def train_forward(model, feats, targets, out_mask=None):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
+def greedy_decode(model, feats, sos_ix, sample=None, ss=None, constraints=None):
     """mode='test' (S2VTModel.py:82-110): ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the same loop with
     s2vt_decode_step_sample in place of the arg-max ((temperature, seed, top_k, top_p): the logits GEMM and the truncated draw,
-    ops.decode_step_token_into).  ss = (targets, ss_prob, seed): the scheduled-sampling pass - every token
+    ops.decode_step_token_into).  constraints = a sampling.ConstraintSpec: every step's head is the logits
+    GEMM and the constrained draw on the loop's packed words (S2VT.decode_constrained).
+    ss = (targets, ss_prob, seed): the scheduled-sampling pass - every token
     step is s2vt_gru_step_fwd_token_ss, and (used, draws) are returned instead of the ids.  vid_rnn without a stash, word_rnn's encode over the first L steps,
     then L-1 decode steps of s2vt_gru_step_fwd_token (the previous step's packed argmax word is read on the device) and
     s2vt_decode_step_argmax.  No host synchronisation inside the loop: <sos> is checked on the host by the first step, and the
@@ -124,7 +126,8 @@ def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
         for i in range(L - 1):
             h = ops.gru_step_fwd_token(gx_dec[i * B:(i + 1) * B], w_hh, b_hh, h, emb, w_ih, tok_packed=packed[i - 1] if i else None,
                                        tok_const=int(sos_ix), out=hs[i % 2], ss=None if ss is None else ss + (i,))
-            ops.decode_step_token_into(h, wo, bo, packed[i], sample=sample, step=i)
+            ops.decode_step_token_into(h, wo, bo, packed[i], sample=sample, step=i,
+                                       constraints=None if constraints is None else (constraints, packed, i))
     capi.check_async_error(wait=False)
     if ss is not None:
         return ops.ss_unpack(packed, *ss)

@@ -279,6 +279,45 @@ def truncated_draw(logits, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, 
     return out if len(out) > 1 else ids
 
 
+def constrained_draw(logits, hist, t, spec, greedy=False, temperature=1.0, top_k=0, top_p=1.0, seed=0, step=0, row0=0, return_kept=False,
+                     return_packed=False, packed=None):
+    """token ids int64 [rows]: the constrained draw of decode step t (s2vt_constrained_draw; the definition: sampling.py,
+    include/s2vt_hip.h "constrained draw") - repetition penalty, no-repeat n-gram, banned ids and minimum length of `spec` (a
+    sampling.ConstraintSpec) applied to the raw logits, then the arg-max (greedy) or truncated_draw's draw on the constrained row.
+    THE CALL MODIFIES `logits` (fp32 [rows, V], unit column stride): afterwards it holds the constrained rows.  hist: the decoders'
+    packed words, int64 [>= t, hist_ld >= rows] with unit column stride (row r's word of step i at hist[i, r]; the token is
+    0xFFFFFFFF - the low half); None where t == 0.  return_kept / return_packed / packed as for truncated_draw."""
+    from .sampling import check_truncation, constraints_struct
+    lib = capi.load()
+    require_hip(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    t = int(t)
+    temperature = float(temperature)
+    if not (0.0 < temperature < float("inf")):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    top_k, top_p = check_truncation(top_k, top_p, V)
+    hist_ld = 0
+    if t > 0:
+        require_hip(hist, "hist")
+        if hist.dim() != 2 or hist.dtype != torch.int64 or hist.stride(1) != 1 or hist.shape[0] < t or hist.shape[1] < rows:
+            raise ValueError("hist must be int64 [>= t = %d, >= rows = %d] with unit column stride" % (t, rows))
+        hist_ld = hist.stride(0)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        if packed is None:
+            packed = torch.empty(rows, dtype=torch.int64, device=dev)
+        kept = torch.empty(rows, dtype=torch.int32, device=dev) if return_kept else None
+        cs, keep = constraints_struct(spec)
+        capi.check(lib.s2vt_constrained_draw(_ptr(logits), logits.stride(0), rows, V, _ptr(hist) if t > 0 else None, hist_ld, t,
+                                             ctypes.byref(cs), 1 if greedy else 0, temperature, top_k, top_p, int(seed), int(step),
+                                             int(row0), _ptr(packed), _ptr(kept), _stream(dev)), "s2vt_constrained_draw")
+        ids = 0xFFFFFFFF - (packed & 0xFFFFFFFF)
+    out = (ids,) + ((kept,) if return_kept else ()) + ((packed,) if return_packed else ())
+    return out if len(out) > 1 else ids
+
+
 def top20_logprob(logits):
     """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20]): the 20 most probable tokens of every logits row in ascending token order
     and their log-probs - the beam searches' fan-out kernel on its own (s2vt_top20_logprob).  logits: fp32 [rows, V >= 20]."""
@@ -295,17 +334,24 @@ def top20_logprob(logits):
     return ix, lp
 
 
-def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0):
+def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0, constraints=None):
     """out_linear + arg-max of one decode step into the caller's packed word row `packed_i` (int64 [B], zeroed) - what the greedy
     loops of the GRU and stacked models run per step; sample = (temperature, seed): the draw of mode='sample' for decode step
     `step` instead (s2vt_decode_step_sample); sample = (temperature, seed, top_k, top_p) that truncate: the logits GEMM and
-    s2vt_truncated_draw.  No synchronisation; no allocation but the truncated form's logits."""
+    s2vt_truncated_draw.  constraints = (spec, packed_history, t): the logits GEMM and s2vt_constrained_draw on the loop's own
+    packed words (int64 [steps, B]; the words of the t steps before) - the arg-max of the constrained row where sample is None,
+    else the (truncated) draw on it.  No synchronisation; no allocation but the truncated and constrained forms' logits."""
     lib = capi.load()
     B, H = h.shape
     V = w_out.shape[0]
     dev = h.device
     trunc = _trunc_of(sample, V)
-    if trunc is not None:
+    if constraints is not None:
+        spec, hist, t = constraints
+        k, p = trunc if trunc is not None else (0, 1.0)
+        constrained_draw(gemm(h, w_out, b_out), hist, t, spec, greedy=sample is None, temperature=1.0 if sample is None else sample[0],
+                         top_k=k, top_p=p, seed=0 if sample is None else sample[1], step=step, packed=packed_i)
+    elif trunc is not None:
         truncated_draw(gemm(h, w_out, b_out), sample[0], trunc[0], trunc[1], sample[1], step, packed=packed_i)
     elif sample is None:
         capi.check(lib.s2vt_decode_step_argmax(B, H, V, _ptr(h), _ptr(w_out), _ptr(b_out), _ptr(packed_i), _stream(dev)),

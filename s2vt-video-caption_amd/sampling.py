@@ -24,7 +24,21 @@ include/s2vt_hip.h "truncated draw") is restated here as well - `truncation_mask
                 renormalised over the top-k set ("top-k, then top-p"); equal values stay or go together, the maximum always stays
     4. draw     token = argmax over the kept v of (s_v + g_v), lowest index on a tie, g the noise above - with nothing truncated,
                 today's draw
+
+Constrained decoding (S2VT.decode_constrained; csrc/truncate.hip, include/s2vt_hip.h "constrained draw") is restated here too -
+`constrain_logits`.  For one row at decode step t (t words generated after <sos>, history h[0..t)), on the RAW logits x, in order:
+
+    1. repetition penalty theta >= 1 (1: off): once per DISTINCT v of h, x_v <- x_v * r if x_v > 0 else x_v * theta, with
+       r = fp32(1.0 / (double)theta) - multiplications, so the fp32 restatement is bitwise
+    2. no-repeat n-gram n >= 0 (0: off): if t >= n - 1, every i in [0, t - n] with h[i .. i+n-2] == h[t-n+1 .. t-1] sets
+       x[h[i+n-1]] <- -inf (n = 1 bans every word of h)
+    3. banned ids: x_v <- -inf
+    4. minimum length m: if t < m, x[eos_ix] <- -inf
+
+A ban wins over a penalty.  Then the arg-max (greedy; lowest index on a tie) or steps 1-4 of the truncated draw above.
 """
+import collections
+
 import numpy as np
 
 M0, M1 = 0xD2511F53, 0xCD9E8D57          # Philox4x32 round multipliers
@@ -169,12 +183,106 @@ def truncation_mask(scores, top_k, top_p):
     return keep
 
 
-def sample_rows(model, feats, params, K, temperature, seed, top_k=0, top_p=1.0):
+MAX_BANNED = 32                          # banned ids of one call (they travel in the row kernel's launch arguments)
+MAX_HISTORY = 1023                       # the longest history a row kernel stages: length - 1 <= 1024
+ConstraintSpec = collections.namedtuple("ConstraintSpec", "no_repeat_ngram repetition_penalty min_length eos_ix banned")
+
+
+def _is_int(x):
+    return not isinstance(x, bool) and isinstance(x, (int, np.integer))
+
+
+def check_constraints(no_repeat_ngram_size, repetition_penalty, min_length, banned_ids, V, eos_ix, length=None):
+    """A ConstraintSpec (repetition_penalty as the fp32 value the library gets, banned as a tuple of distinct ints) or ValueError -
+    before anything reaches the library.  length: the model's L, for the drivers' rule that no step may ban a whole row,
+    V > (L - 1) + n_banned + 1, and for the history bound L - 1 <= 1024."""
+    V = int(V)
+    if not _is_int(no_repeat_ngram_size) or int(no_repeat_ngram_size) < 0:
+        raise ValueError("no_repeat_ngram_size must be an integer >= 0 (0: off), got %r" % (no_repeat_ngram_size,))
+    if isinstance(repetition_penalty, (bool, str)) or not isinstance(repetition_penalty, (int, float, np.integer, np.floating)):
+        raise ValueError("repetition_penalty must be a finite number >= 1 (1: off), got %r" % (repetition_penalty,))
+    with np.errstate(over="ignore"):
+        theta = float(np.float32(repetition_penalty))
+    if not 1.0 <= theta < float("inf"):
+        raise ValueError("repetition_penalty must be a finite number >= 1 (1: off), got %r" % (repetition_penalty,))
+    if not _is_int(min_length) or int(min_length) < 0:
+        raise ValueError("min_length must be an integer >= 0, got %r" % (min_length,))
+    banned = [] if banned_ids is None else list(banned_ids)
+    if any(not _is_int(b) or not 0 <= int(b) < V for b in banned):
+        raise ValueError("banned_ids must be integers in [0, vocab_size = %d), got %r" % (V, banned_ids))
+    banned = tuple(sorted(set(int(b) for b in banned)))
+    if len(banned) > MAX_BANNED:
+        raise ValueError("banned_ids: at most %d distinct ids, got %d" % (MAX_BANNED, len(banned)))
+    if not _is_int(eos_ix) or not 0 <= int(eos_ix) < V:
+        raise ValueError("eos_ix must be an integer in [0, vocab_size = %d), got %r" % (V, eos_ix))
+    if length is not None:
+        if int(length) - 1 > MAX_HISTORY + 1:
+            raise ValueError("length %d: constrained decoding keeps at most %d words of history" % (int(length), MAX_HISTORY))
+        if not V > (int(length) - 1) + len(banned) + 1:
+            raise ValueError("vocab_size %d <= (length - 1) + banned ids + 1 = %d: the constraints could ban a whole row"
+                             % (V, int(length) - 1 + len(banned) + 1))
+    return ConstraintSpec(int(no_repeat_ngram_size), theta, int(min_length), int(eos_ix), banned)
+
+
+def constrains(spec):
+    """whether a ConstraintSpec of check_constraints changes any logit at any step"""
+    return spec.no_repeat_ngram > 0 or spec.repetition_penalty != 1.0 or spec.min_length > 0 or len(spec.banned) > 0
+
+
+def constraints_struct(spec):
+    """(capi.Constraints, keep-alive): the spec as the library's s2vt_constraints (the banned ids in host memory)"""
+    import ctypes
+
+    from . import capi
+    arr = (ctypes.c_int32 * max(1, len(spec.banned)))(*spec.banned)
+    c = capi.Constraints(spec.no_repeat_ngram, spec.repetition_penalty, spec.min_length, spec.eos_ix, len(spec.banned),
+                         ctypes.cast(arr, ctypes.POINTER(ctypes.c_int32)))
+    return c, arr
+
+
+def constrain_logits(x, hist_ids, t, spec):
+    """The constrained logits of decode step t (rules 1-4 of the definition above): x float32 or float64 [rows, V] (or [V]), hist_ids
+    ints [rows, >= t] (or [>= t]) - row r's history is hist_ids[r, :t].  A new array of x's dtype: in float32 bit for bit what the
+    row kernel leaves in its logits buffer; in float64 the same rules with the same fp32 factors (theta and r as the device holds
+    them).  History ids outside [0, V) are matched like any other and never written."""
+    x = np.array(x, copy=True)
+    if x.dtype not in (np.float32, np.float64):
+        raise ValueError("x must be float32 or float64")
+    out = x.reshape(1, -1) if x.ndim == 1 else x
+    rows, V = out.shape
+    t = int(t)
+    h = np.asarray(hist_ids, dtype=np.int64).reshape(rows, -1)[:, :t] if t > 0 else np.zeros((rows, 0), dtype=np.int64)
+    if h.shape[1] != t:
+        raise ValueError("hist_ids holds fewer than t = %d words" % t)
+    theta = x.dtype.type(np.float32(spec.repetition_penalty))
+    r = x.dtype.type(np.float32(1.0 / float(np.float32(spec.repetition_penalty))))
+    n = spec.no_repeat_ngram
+    for row in range(rows):
+        hr = h[row].tolist()
+        if theta != 1:
+            for v in sorted(set(hr)):
+                if 0 <= v < V:
+                    out[row, v] = out[row, v] * r if out[row, v] > 0 else out[row, v] * theta
+        if n > 0 and t >= n - 1:
+            suffix = hr[t - n + 1:t]
+            for i in range(0, t - n + 1):
+                if hr[i:i + n - 1] == suffix and 0 <= hr[i + n - 1] < V:
+                    out[row, hr[i + n - 1]] = -np.inf
+        for v in spec.banned:
+            out[row, v] = -np.inf
+        if t < spec.min_length:
+            out[row, spec.eos_ix] = -np.inf
+    return x
+
+
+def sample_rows(model, feats, params, K, temperature, seed, top_k=0, top_p=1.0, constraints=None):
     """ids int64 [B, K, L-1]: K draws per clip on ONE encode - s2vt_sample_decode_rows; with a truncating (top_k, top_p) (already
     through check_truncation) s2vt_sample_decode_rows_trunc: the same driver with the logits GEMM and the truncated draw as head.  Row b*K + k draws with the noise of
     (seed, decode step, batch row b*K + k, v): the draw of mode='sample' on feats.repeat_interleave(K, 0).  With the model's decode
     cache where a decode of the batch takes the plane path's persistent encode (filled here on fresh weights), on the fp32-input
-    MFMA path otherwise.  On the device, no host synchronisation, no gradient."""
+    MFMA path otherwise.  On the device, no host synchronisation, no gradient.
+    constraints = (ConstraintSpec, greedy): s2vt_decode_rows_constrained - the same driver with the constrained draw as head (greedy:
+    the arg-max of the constrained row, temperature 1 / top_k 0 / top_p 1; else the truncated draw on it)."""
     import ctypes
 
     import torch
@@ -189,7 +297,9 @@ def sample_rows(model, feats, params, K, temperature, seed, top_k=0, top_p=1.0):
         params = tuple(F._f32c(p.detach(), "parameter") for p in params)
         d = F._dims(feats, params)
         trunc = truncates(top_k, top_p, d.V)
-        nbytes = (lib.s2vt_sample_rows_trunc_workspace_bytes if trunc else lib.s2vt_sample_rows_workspace_bytes)(ctypes.byref(d), K)
+        size = lib.s2vt_decode_rows_constrained_workspace_bytes if constraints is not None else (
+            lib.s2vt_sample_rows_trunc_workspace_bytes if trunc else lib.s2vt_sample_rows_workspace_bytes)
+        nbytes = size(ctypes.byref(d), K)
         if nbytes <= 0:
             raise ValueError("sample: %d clips x %d samples is not a shape the library serves" % (d.B, K))
         dev = feats.device
@@ -204,7 +314,12 @@ def sample_rows(model, feats, params, K, temperature, seed, top_k=0, top_p=1.0):
             ps = F._params_struct(capi.Params, params)
             tail = (F._ptr(ids), F._ptr(ws), nbytes, F._ptr(cache), cache.numel() if cache is not None else 0, 1 if valid else 0,
                     F._stream(dev))
-            if trunc:
+            if constraints is not None:
+                cs, keep = constraints_struct(constraints[0])
+                capi.check(lib.s2vt_decode_rows_constrained(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix),
+                                                            1 if constraints[1] else 0, temperature, seed, top_k, top_p, ctypes.byref(cs),
+                                                            *tail), "s2vt_decode_rows_constrained")
+            elif trunc:
                 capi.check(lib.s2vt_sample_decode_rows_trunc(ctypes.byref(d), ctypes.byref(ps), F._ptr(feats), K, int(model.sos_ix),
                                                              temperature, seed, top_k, top_p, *tail), "s2vt_sample_decode_rows_trunc")
             else:

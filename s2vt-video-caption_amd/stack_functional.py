@@ -171,10 +171,12 @@ def _layer_masks(N, rnn_masks, rows, H):
 
 
 @torch.no_grad()
-def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
+def greedy_decode(model, feats, sos_ix, sample=None, ss=None, constraints=None):
     """mode='test' (S2VTModel.py:82-110) of a stacked model: ids int64 [B, L-1]; sample = (temperature, seed): mode='sample', the
     same loop with s2vt_decode_step_sample in place of the arg-max ((temperature, seed, top_k, top_p): the logits GEMM and the
-    truncated draw, ops.decode_step_token_into).  ss = (targets, ss_prob, seed): the scheduled-sampling pass -
+    truncated draw, ops.decode_step_token_into).  constraints = a sampling.ConstraintSpec: every step's head is the logits
+    GEMM and the constrained draw on the loop's packed words (S2VT.decode_constrained).
+    ss = (targets, ss_prob, seed): the scheduled-sampling pass -
     the token layer of every step takes the coin's word, no dropout masks are drawn, and (used, draws) are returned.  The vid chain over T steps, the word chain's
     encode over the first L steps, then L-1 decode steps of one word-chain call each (T = 1, the previous step's state, the packed
     argmax word read on the device) followed by s2vt_decode_step_argmax.  No host synchronisation inside the loop.  In training
@@ -230,7 +232,8 @@ def greedy_decode(model, feats, sos_ix, sample=None, ss=None):
                     lay["hm"] = bufs[i % 2][k]["hm"]
             ops.lstm_chain_fwd(1, B, H, step)
             state = [(lay["h"], lay["c"]) for lay in step]
-            ops.decode_step_token_into(state[-1][0], wo, bo, packed[i], sample=sample, step=i)
+            ops.decode_step_token_into(state[-1][0], wo, bo, packed[i], sample=sample, step=i,
+                                       constraints=None if constraints is None else (constraints, packed, i))
     capi.check_async_error(wait=False)
     if ss is not None:
         return ops.ss_unpack(packed, *ss)
