@@ -20,6 +20,11 @@ from s2vt_video_caption_amd import sampling as _sampling
 from s2vt_video_caption_amd import score as _score
 
 
+# what mode='beam' and beam_constrained say to the models the batched depth step does not serve
+_BEAM_GRU = "mode='beam' of a GRU model: the batched depth step is the LSTM's; use mode='test'"
+_BEAM_STACKED = "mode='beam' of a stacked model (num_layers > 1): the batched depth step is the one-layer LSTM's; use mode='test'"
+
+
 class S2VT(nn.Module):
     def __init__(self, vocab_size, feat_dim, length, dim_hid=500, dim_embed=500, feat_dropout=0, rnn_dropout=0,
                  out_dropout=0, num_layers=1, bidirectional=False, rnn_type='lstm', sos_ix=3, eos_ix=4):
@@ -215,8 +220,7 @@ class S2VT(nn.Module):
         rows and noise.  The constraints run inside the row kernel of csrc/truncate.hip behind the logits GEMM: the one-layer LSTM
         in `sample`'s driver (s2vt_decode_rows_constrained), a GRU or stacked model in its step loop on the repeated clips.  With
         the constraints at their defaults nothing is constrained: greedy returns mode='test' (with a middle axis of 1), sampled
-        what `sample_truncated` returns.  Not covered: mode='beam' (a hypothesis's history runs through back-pointers),
-        Att_Baseline, scheduled sampling, dp.py.  No gradient.
+        what `sample_truncated` returns.  Not covered: mode='beam' (that is `beam_constrained`), Att_Baseline, scheduled sampling, dp.py.  No gradient.
         :param no_repeat_ngram_size: an int >= 0; 0: off, 1: no word twice
         :param repetition_penalty: finite and >= 1; 1.0: off
         :param min_length: an int >= 0: no <eos> among the first min_length words
@@ -243,6 +247,41 @@ class S2VT(nn.Module):
             return decode(self, rows, self.sos_ix, sample=smp, constraints=spec).view(B, K, -1)
         return _sampling.sample_rows(self, self.feat_drop(feats), self._hip_params(), K, t, s, k, p, constraints=(spec, greedy))
 
+    @torch.no_grad()
+    def beam_constrained(self, feats, beam_width=3, max_beam_depth=30, length_alpha=0.7, n_best=1, no_repeat_ngram_size=0,
+                         repetition_penalty=1.0, min_length=0, banned_ids=None):
+        """mode='beam' under the constraints of `decode_constrained` (not in the reference): (ids int64 [B, n_best, max_beam_depth]
+        padded with eos_ix, lengths int64 [B, n_best], scores fp32 [B, n_best]) on the device, best first, as mode='beam' returns
+        them.  The search is mode='beam''s with one change (include/s2vt_hip.h "constrained beam"): at every
+        depth each live hypothesis's raw logits row is first edited with the hypothesis's OWN words as history - the repetition
+        penalty on every distinct word, -inf on a word that would complete an n-gram it already holds, -inf on the banned ids, -inf
+        on <eos> during its first min_length words (sampling.constrain_logits, bit for bit) - and its log-probs are log_softmax of
+        the edited row, renormalised over the surviving words.  Scores, tie rules, the pool, length_alpha and n_best are
+        mode='beam''s.  The policy kernel keeps every beam slot's words on the device (csrc/beam_cum.hip), the depth step's fan-out
+        kernel applies the rules in front of its top 20 (csrc/ce.hip): no host round trip per depth.  With the constraints at
+        their defaults the call IS mode='beam' (the same launches, the same bits).  beam_width = 1, length_alpha = 0 gives greedy
+        `decode_constrained` up to the first <eos>.  One-layer LSTM models only (a GRU or stacked model: ValueError with mode='beam''s
+        message).  A method of its own: forward's parameter list is fixed.  Not covered: mode='beam_search', GRU and stacked
+        models, Att_Baseline, dp.py.  No gradient.
+        :param beam_width, max_beam_depth, length_alpha, n_best: as for mode='beam'; max_beam_depth <= 1023 and
+                     vocab_size >= 20 + max_beam_depth + len(banned_ids) + 1 (every edited row keeps 20 words for the fan-out)
+        :param no_repeat_ngram_size, repetition_penalty, min_length, banned_ids: as for decode_constrained
+        """
+        _beam.check_beam_args(beam_width, max_beam_depth, length_alpha, n_best, self.vocab_size)
+        spec = _sampling.check_constraints(no_repeat_ngram_size, repetition_penalty, min_length, banned_ids, self.vocab_size, self.eos_ix)
+        _beam.check_beam_constraints(spec, max_beam_depth, self.vocab_size)
+        if _G.is_gru_model(self):
+            raise ValueError(_BEAM_GRU)
+        if _S.is_stacked_lstm_model(self):
+            raise ValueError(_BEAM_STACKED)
+        if not _sampling.constrains(spec):                 # nothing to constrain: today's call
+            return self(feats, mode='beam', beam_width=beam_width, max_beam_depth=max_beam_depth, length_alpha=length_alpha, n_best=n_best)
+        _F.require_hip(feats, "feats")
+        if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
+            raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        return _beam.beam_cumulative(self, self.feat_drop(feats), self._hip_params(), beam_width=beam_width, max_depth=max_beam_depth,
+                                     length_alpha=length_alpha, n_best=n_best, constraints=spec)
+
     def _sample(self, feats, n_samples, temperature, seed, k, p):
         K = _sampling.check_n_samples(n_samples)
         t, s = _sampling.check_sample_args(temperature, seed)
@@ -264,7 +303,7 @@ class S2VT(nn.Module):
             raise NotImplementedError("beam search of a GRU model: the reference's beam search does not support GRU either "
                                       "(S2VTModel.py:153, 'DO NOT SUPPORT GRU'); use mode='test'")
         if mode == 'beam':
-            raise NotImplementedError("mode='beam' of a GRU model: the batched depth step is the LSTM's; use mode='test'")
+            raise NotImplementedError(_BEAM_GRU)
         if mode == 'score':
             raise NotImplementedError("mode='score' of a GRU model: the scoring driver's word step is the LSTM's; take the logits "
                                       "of mode='train' and log_softmax(...).gather(...) them")
@@ -295,8 +334,7 @@ class S2VT(nn.Module):
                                       "per-sample [num_layers, H] state as [1, 1, -1] (S2VTModel.py:253-254) and raises for "
                                       "num_layers > 1; use mode='test'")
         if mode == 'beam':
-            raise NotImplementedError("mode='beam' of a stacked model (num_layers > 1): the batched depth step is the one-layer "
-                                      "LSTM's; use mode='test'")
+            raise NotImplementedError(_BEAM_STACKED)
         if mode == 'score':
             raise NotImplementedError("mode='score' of a stacked model (num_layers > 1): the scoring driver's word step is the "
                                       "one-layer LSTM's; take the logits of mode='train' and log_softmax(...).gather(...) them")

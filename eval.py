@@ -10,7 +10,8 @@ BLEU-1..4, ROUGE-L, CIDEr.  METEOR and the Stanford tokenizer are Java jars the 
 under the model instead (mode='score', not in the reference): per-word perplexity and per-reference log-likelihoods.
 --sample K additionally writes K sampled captions per clip (S2VT.sample_truncated, not in the reference; --temperature, --top-k, --top-p,
 --sample-seed) to <out>.samples.json.  --no-repeat-ngram / --repetition-penalty / --min-length / --ban-words constrain the greedy captions
-and those of --sample (S2VT.decode_constrained, not in the reference); they are refused together with --beam.
+and those of --sample (S2VT.decode_constrained, not in the reference) and the search of --beam N --beam-mode cumulative
+(S2VT.beam_constrained); they are refused together with the reference's search (--beam N --beam-mode reference).
 """
 import argparse
 import json
@@ -31,8 +32,9 @@ def ids_to_caption(ids, ix2word, drop_sos=False):
 def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', beam_width=5, max_beam_depth=30,
              split='test', device=None, length_alpha=0.7, n_best=1, nbest=None, constraints=None):
     """{video_id: caption} of a split.  mode: 'test' (greedy), 'beam_search' (the reference's search) or 'beam' (cumulative scores,
-    length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]}).  constraints (mode 'test'
-    only): keyword arguments of S2VT.decode_constrained, with `ban_words` looked up in the split's word2ix."""
+    length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]}).  constraints (modes 'test'
+    and 'beam'): keyword arguments of S2VT.decode_constrained / S2VT.beam_constrained, with `ban_words` looked up in the split's
+    word2ix."""
     import dataloader
     dev = device or torch.device('cuda', 0)
     dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
@@ -50,8 +52,12 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                 for vid, seq in zip(ids, out):
                     preds[vid] = ids_to_caption([int(t.item()) for t in seq], dataset.ix2word, drop_sos=True)
             elif mode == 'beam':
-                out, lens, _ = model(feats, mode='beam', beam_width=beam_width, max_beam_depth=max_beam_depth,
-                                     length_alpha=length_alpha, n_best=n_best)
+                if con:
+                    out, lens, _ = model.beam_constrained(feats, beam_width=beam_width, max_beam_depth=max_beam_depth,
+                                                          length_alpha=length_alpha, n_best=n_best, **con)
+                else:
+                    out, lens, _ = model(feats, mode='beam', beam_width=beam_width, max_beam_depth=max_beam_depth,
+                                         length_alpha=length_alpha, n_best=n_best)
                 out, lens = out.cpu().tolist(), lens.cpu().tolist()
                 for vid, rows, ln in zip(ids, out, lens):
                     caps = [ids_to_caption(r[:n], dataset.ix2word) for r, n in zip(rows, ln)]
@@ -197,11 +203,11 @@ def build_parser():
                     help="--sample: draw from the smallest set of most probable words whose mass reaches p (1: off)")
     ap.add_argument("--sample-seed", type=int, default=0, help="--sample: batch i draws with this seed + i")
     ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
-                    help="greedy and --sample: never complete an n-gram the caption already holds (0: off; not with --beam)")
+                    help="greedy, --sample and --beam-mode cumulative: never complete an n-gram the caption already holds (0: off)")
     ap.add_argument("--repetition-penalty", type=float, default=1.0, metavar="THETA",
-                    help="greedy and --sample: divide the positive logits of the words generated so far by THETA, multiply the others (1: off)")
-    ap.add_argument("--min-length", type=int, default=0, metavar="M", help="greedy and --sample: no <eos> among the first M words")
-    ap.add_argument("--ban-words", default="", metavar="W1,W2", help="greedy and --sample: words that are never generated, e.g. \"<unk>,<pad>\"")
+                    help="greedy, --sample and --beam-mode cumulative: divide the positive logits of the words generated so far by THETA, multiply the others (1: off)")
+    ap.add_argument("--min-length", type=int, default=0, metavar="M", help="greedy, --sample and --beam-mode cumulative: no <eos> among the first M words")
+    ap.add_argument("--ban-words", default="", metavar="W1,W2", help="greedy, --sample and --beam-mode cumulative: words that are never generated, e.g. \"<unk>,<pad>\"")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
     return ap
@@ -219,8 +225,9 @@ def main(argv=None):
     ap = build_parser()
     a = ap.parse_args(argv)
     constraints = constraints_of(a)
-    if constraints and a.beam:
-        ap.error("--no-repeat-ngram / --repetition-penalty / --min-length / --ban-words apply to greedy decoding and --sample, not to --beam")
+    if constraints and a.beam and a.beam_mode != "cumulative":
+        ap.error("--no-repeat-ngram / --repetition-penalty / --min-length / --ban-words apply to greedy decoding, --sample and "
+                 "--beam N --beam-mode cumulative, not to the reference's search (--beam-mode reference)")
     if a.perplexity:
         per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
         print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "

@@ -874,6 +874,48 @@ int s2vt_decode_rows_constrained(const s2vt_dims* d, const s2vt_params* p, const
                                  void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, int32_t cache_valid,
                                  void* stream);
 
+/* ---------------------------------------------------------------- constrained beam: the constraints inside the cumulative-score search
+ * (S2VT.beam_constrained(..., no_repeat_ngram_size=, repetition_penalty=, min_length=, banned_ids=); csrc/beam_cum.hip, csrc/ce.hip;
+ * restated in fp64 by tests/beam_constrained_ref.py).  The search is EXACTLY the cumulative-score beam search above
+ * (s2vt_beam_cum_step) with one change.  At depth t, live slot j holds the words h = (w_1 .. w_{t-1}) (without <sos>).  Its fp32
+ * logits row is first edited by rules 1-4 of the constrained draw with history h and step t-1 - sampling.constrain_logits(x, h, t-1,
+ * spec), bit for bit in fp32: the penalty on every distinct word of h, -inf on a word that would complete an n-gram h already holds,
+ * -inf on the banned ids, -inf on <eos> while t-1 < min_length.  lp_j is then log_softmax of the EDITED row: the mass is renormalised
+ * over the surviving words (the stance of the constrained and the truncated draw: the rules act on the raw logits).  Scores, tie
+ * rules, the pool and S / t**alpha, hypotheses unfinished at max_depth entering the pool without <eos>, and n_best are unchanged.
+ *   defaults   with every constraint off the result is mode='beam''s bit for bit: the callers run the existing launches
+ *              (s2vt_beam_cum_step and the unconstrained fan-out), not a neutral form of the new ones.
+ *   width 1    beam_width = 1, length_alpha = 0, n_best = 1: the words up to and including the first <eos> are those of greedy
+ *              s2vt_decode_rows_constrained with the same constraints, wherever the step margins are clear.
+ *   fan-out    20 per row stays exact for beam_width <= 8: the top 20 are taken from the edited row.  A -inf candidate must never be
+ *              selected, so a shape that could leave a row fewer than 20 finite words is refused:  V >= 20 + max_depth + n_banned + 1
+ *              (per call of the head: V >= 20 + t + n_banned + 1), and max_depth <= 1023, the constraint phase's history bound.
+ *   early stop unchanged: its proof needs lp <= 0 only, which the log_softmax of any edited row still gives.
+ * s2vt_beam_cum_hist_bytes / s2vt_beam_cum_hist_step: s2vt_beam_cum_bytes / s2vt_beam_cum_step whose state also keeps every live
+ * slot's words, hist[2][B][beam_width][max_depth] int32 behind the plain state (s2vt_beam_cum_result serves both forms), ping-ponged
+ * by depth parity.  Same policy, same rows, same results as s2vt_beam_cum_step on the same inputs.  After the call with `depth`,
+ * *hist_out is the device pointer and *hist_ld_out (= max_depth) the row stride of the buffer that the NEXT depth step must read:
+ * row r = b * beam_width + slot holds that slot's depth - 1 words at (*hist_out)[r * ld + i], i < depth - 1.  Rows of unused slots and of
+ * frozen samples hold defined words (zeros, or words written earlier); their fan-out is never consumed.
+ * s2vt_top20_logprob_constrained: the fan-out head on its own - s2vt_top20_logprob with the constraint phase in front of the row's
+ * load, in the same launch.  THE CALL MODIFIES `logits` (afterwards the constrained rows).  hist_i32: int32 [rows][hist_ld], row r's t
+ * words at hist_i32[r * hist_ld + i]; null iff t == 0.  The host-side checks of s2vt_constrained_draw (S2VT_ERR_ARG), with hist_ld >= t,
+ * plus V >= 20 and V >= 20 + t + n_banned + 1.  With every constraint off it runs s2vt_top20_logprob's launch.
+ * s2vt_beam_step_constrained: the depth step with that head, for all three forms - gx_vid != NULL: s2vt_beam_step_gx (needs cache; the
+ * vid_* arguments are not read); else cache != NULL: s2vt_beam_step_cached; else s2vt_beam_step.  hist / hist_ld: what
+ * s2vt_beam_cum_hist_step returned for this depth; t = depth - 1. */
+size_t s2vt_beam_cum_hist_bytes(int32_t B, int32_t beam_width, int32_t max_depth);
+int s2vt_beam_cum_hist_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, double length_alpha,
+                            int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix, const float* top_lp, int32_t* row_b,
+                            int32_t* row_state, int32_t* row_tok, const int32_t** hist_out, int64_t* hist_ld_out, void* stream);
+int s2vt_top20_logprob_constrained(float* logits, int64_t ld, int64_t rows, int32_t V, const int32_t* hist_i32, int64_t hist_ld, int32_t t,
+                                   const s2vt_constraints* c, int32_t* top_ix, float* top_lp, void* stream);
+int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                               const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                               const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                               int32_t* top_ix, float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                               const s2vt_constraints* c, const int32_t* hist, int64_t hist_ld, int32_t t, void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

@@ -166,13 +166,15 @@ LAST_PATH = None             # which path the last beam_search call took (bench.
 
 
 def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, vid_h, vid_c, word_h, word_c, gx_dec, qbytes, policy_step,
-                       policy_name):
+                       policy_name, con=None):
     """The depth loop of a search whose policy lives on the device: per depth ONE policy_step(depth, qs, top_ix, top_lp, rows, st)
     (consume the top-20 of the depth before, freeze finished samples, write the rows of the step) and ONE s2vt_beam_step over the
     fixed rows r = b * beam_width + slot; nothing crosses PCIe.  The early exit (all samples frozen) is polled without blocking:
     the frozen-sample counter (the int32 at byte 0 of the policy's state) is copied to pinned memory after every depth and read
     one depth late - extra depths change nothing.  Ends with policy_step(0, ...), the last depth's results.  Returns the policy's
-    state tensor (qbytes) and the stream."""
+    state tensor (qbytes) and the stream.
+    con (a capi.Constraints: the constrained search): policy_step returns (pointer, row stride) of the live slots' words for the step
+    it has just prepared, and that step is s2vt_beam_step_constrained - the same three forms with the constrained fan-out head."""
     import ctypes
     from .functional import _ptr, _stream, _dims, _params_struct
     dev = feats.device
@@ -217,7 +219,7 @@ def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, v
             if depth >= 2 and events[depth - 2].query() and int(frozen[depth - 1]) == B:
                 break                                   # every sample had stopped two depths ago: the reference's loop ended there
             depth += 1
-            policy_step(depth, qs, top_ix, top_lp, rows, st)
+            words = policy_step(depth, qs, top_ix, top_lp, rows, st)
             if depth > 1:
                 frozen[depth].copy_(frozen_dev[0], non_blocking=True)
             ev = torch.cuda.Event()
@@ -225,7 +227,15 @@ def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, v
             events.append(ev)
             (vh_in, vc_in), (vh_out, vc_out) = vid[(depth - 1) & 1], vid[depth & 1]
             (wh_in, wc_in), (wh_out, wc_out) = tab[(depth - 1) & 1], tab[depth & 1]
-            if gx_dec is not None:
+            if con is not None:
+                gx = gx_dec[depth - 1] if gx_dec is not None else None
+                capi.check(lib.s2vt_beam_step_constrained(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
+                                                          _ptr(vh_in), _ptr(vc_in), _ptr(vh_out), _ptr(vc_out), _ptr(gx), _ptr(wh_in),
+                                                          _ptr(wc_in), _ptr(wh_out), _ptr(wc_out), _ptr(top_ix), _ptr(top_lp), _ptr(ws),
+                                                          nbytes, _ptr(cache), cache.numel() if cache is not None else 0,
+                                                          ctypes.byref(con), words[0], words[1], depth - 1, st),
+                           "s2vt_beam_step_constrained")
+            elif gx_dec is not None:
                 capi.check(lib.s2vt_beam_step_gx(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
                                                  _ptr(gx_dec[depth - 1]), _ptr(wh_in), _ptr(wc_in), _ptr(wh_out), _ptr(wc_out),
                                                  _ptr(top_ix), _ptr(top_lp), _ptr(ws), nbytes, _ptr(cache), cache.numel(), st),
@@ -302,28 +312,64 @@ def check_beam_args(beam_width, max_depth, length_alpha, n_best, vocab_size):
 
 
 @torch.no_grad()
-def beam_cumulative(model, feats, params, beam_width=3, max_depth=30, length_alpha=0.7, n_best=1):
+def check_beam_constraints(spec, max_depth, vocab_size):
+    """the two shape rules of the constrained search, or ValueError - before anything reaches the library: the fan-out must find 20
+    finite words in every edited row, and the constraint phase stages at most 1023 words of history"""
+    from . import sampling
+    D, V = int(max_depth), int(vocab_size)
+    if D > sampling.MAX_HISTORY:
+        raise ValueError("beam_constrained: max_beam_depth %d > %d, the history a constrained row kernel stages" % (D, sampling.MAX_HISTORY))
+    need = FANOUT + D + len(spec.banned) + 1
+    if V < need:
+        raise ValueError("beam_constrained: vocab_size %d < %d + max_beam_depth + banned ids + 1 = %d: a row could keep fewer than %d "
+                         "words" % (V, FANOUT, need, FANOUT))
+
+
+@torch.no_grad()
+def beam_cumulative(model, feats, params, beam_width=3, max_depth=30, length_alpha=0.7, n_best=1, constraints=None):
     """mode='beam' (not in the reference): hypotheses ranked by the fp32 sum of their tokens' log-probs, the
     beam_width best of all live slots' candidates kept per depth by (sum descending, slot ascending, token ascending), a hypothesis
     that ends in <eos> at depth t pooled with score sum / t**length_alpha, the ones still live at max_depth with sum /
     max_depth**length_alpha.  Same encoder, decode cache, depth step and polled early exit as mode='beam_search'; the policy is
     csrc/beam_cum.hip.  Returns (ids int64 [B, n_best, max_depth] padded with <eos>, lengths int64 [B, n_best], scores fp32
-    [B, n_best]) on the device, best first; no host synchronisation."""
+    [B, n_best]) on the device, best first; no host synchronisation.
+    constraints (a sampling.ConstraintSpec; S2VT.beam_constrained, include/s2vt_hip.h "constrained beam"): every live slot's logits
+    row is edited by the rules of the constrained draw with the slot's own words as history before its log_softmax and top 20 - the
+    policy keeps those words on the device (s2vt_beam_cum_hist_step), the depth step runs the constrained fan-out head
+    (s2vt_beam_step_constrained).  None, or a spec that constrains nothing: today's path, launch for launch."""
+    from . import sampling
     from .functional import _ptr
     W, D, alpha, n_best = check_beam_args(beam_width, max_depth, length_alpha, n_best, model.vocab_size)
+    if constraints is not None and not sampling.constrains(constraints):
+        constraints = None
+    if constraints is not None:
+        check_beam_constraints(constraints, D, model.vocab_size)
     dev = feats.device
     B, H = feats.shape[0], model.dim_hid
     sos, eos = int(model.sos_ix), int(model.eos_ix)
     lib = capi.load()
-    qbytes = lib.s2vt_beam_cum_bytes(B, W, D)
+    qbytes = (lib.s2vt_beam_cum_hist_bytes if constraints is not None else lib.s2vt_beam_cum_bytes)(B, W, D)
     if qbytes == 0:
         raise ValueError("mode='beam': batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (B, W, D))
     states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
 
-    def cstep(depth, qs, top_ix, top_lp, rows, st):
-        capi.check(lib.s2vt_beam_cum_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp), _ptr(rows[0]),
-                                          _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_cum_step")
-    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, cstep, "cumulative beam")
+    con = keep = None
+    if constraints is None:
+        def cstep(depth, qs, top_ix, top_lp, rows, st):
+            capi.check(lib.s2vt_beam_cum_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp), _ptr(rows[0]),
+                                              _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_cum_step")
+    else:
+        import ctypes
+        con, keep = sampling.constraints_struct(constraints)     # (keep: the banned ids' host array lives as long as con is used)
+        words, words_ld = ctypes.c_void_p(), ctypes.c_int64()
+
+        def cstep(depth, qs, top_ix, top_lp, rows, st):           # the same policy; it also keeps the live slots' words
+            capi.check(lib.s2vt_beam_cum_hist_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
+                                                   _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ctypes.byref(words),
+                                                   ctypes.byref(words_ld), st), "s2vt_beam_cum_hist_step")
+            return ctypes.c_void_p(words.value), words_ld.value
+    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, cstep,
+                                "constrained cumulative beam" if con is not None else "cumulative beam", con=con)
     with torch.cuda.device(dev):
         ids = torch.empty(B, n_best, D, dtype=torch.int32, device=dev)
         lens = torch.empty(B, n_best, dtype=torch.int32, device=dev)

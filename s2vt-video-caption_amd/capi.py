@@ -119,6 +119,15 @@ SIGNATURES = {
     "s2vt_beam_cum_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_beam_cum_step": (c_int32, [c_int32] * 5 + [c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 6),
     "s2vt_beam_cum_result": (c_int32, [c_int32] * 5 + [c_void_p, c_size_t] + [c_void_p] * 4),
+    # the constrained cumulative beam (S2VT.beam_constrained): the policy with per-slot histories, its fan-out head, its depth step
+    "s2vt_beam_cum_hist_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_beam_cum_hist_step": (c_int32, [c_int32] * 5 + [c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 5 +
+                                [POINTER(c_void_p), POINTER(c_int64), c_void_p]),
+    "s2vt_top20_logprob_constrained": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_void_p, c_int64, c_int32, POINTER(Constraints),
+                                                 c_void_p, c_void_p, c_void_p]),
+    "s2vt_beam_step_constrained": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 15 + [c_size_t, c_void_p, c_size_t,
+                                                                                                          POINTER(Constraints), c_void_p,
+                                                                                                          c_int64, c_int32, c_void_p]),
     "s2vt_score_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "s2vt_score_captions": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32,

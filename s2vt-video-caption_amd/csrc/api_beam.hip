@@ -56,11 +56,18 @@ size_t s2vt_beam_workspace_bytes(const s2vt_dims* d, int32_t max_rows) {
     return carve_beam(*d, max_rows, nullptr).bytes;
 }
 
+// con (nullable): the constrained search's depth step - the fan-out head is the constrained one (ce.hip: the rules of the constrained
+// draw on each row with beam slot r's own words hist[r * hist_ld + i], i < t, then log_softmax and the top 20 of the edited row)
+struct BeamCon { const char* fn; const s2vt_constraints* c; const int32_t* hist; int64_t hist_ld; int t; };
+static int beam_fan_out(hipStream_t st, float* logits, int R, int V, const BeamCon* con, int32_t* top_ix, float* top_lp) {
+    if (!con) return top20_logprob(st, logits, V, R, V, top_ix, top_lp);
+    return top20_constrained_checked(con->fn, st, logits, V, R, V, con->hist, con->hist_ld, con->t, con->c, top_ix, top_lp);
+}
 static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
                           const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
                           const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out, int32_t* top_ix,
                           float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, void* stream,
-                          const float* gx_vid) {
+                          const float* gx_vid, const BeamCon* con = nullptr) {
     S2VT_REQUIRE(d && p && workspace && (gx_vid || (vid_h_in && vid_c_in && vid_h_out && vid_c_out)), "s2vt_beam_step: null argument");
     S2VT_REQUIRE(R >= 0 && (R == 0 || (row_b && row_state && tok && word_h_in && word_c_in && word_h_out && word_c_out &&
                                         top_ix && top_lp)),
@@ -110,7 +117,7 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
         if ((rc = rows_word_step(st, *d, p, &kc, a))) return rc;
         if ((rc = pgemm(ln, R, V, H, w.pword, 0, 0, kc.wo, 0, 0, w.logits, V, ID, p->out_b, false))) return rc;
-        if ((rc = top20_logprob(st, w.logits, V, R, V, top_ix, top_lp))) return rc;
+        if ((rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;
         return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
     }
     S2VT_REQUIRE(!gx_vid, "s2vt_beam_step_gx: the precomputed vid_rnn half needs the plane path (gemm mode 1 / 3, H <= 1024)");
@@ -120,7 +127,7 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = rows_word_step(st, *d, p, nullptr, a))) return rc;
     if ((rc = lgemm(ln, true, true, R, V, H, word_h_out, H, ID, p->out_w, H, ID, w.logits, V, ID, p->out_b, false))) return rc;   // (:213)
-    if ((rc = top20_logprob(st, w.logits, V, R, V, top_ix, top_lp))) return rc;                                                    // (:214-219)
+    if ((rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;                                                   // (:214-219)
     return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
 }
 // the depth step with vid_rnn's part precomputed (s2vt_decode_encode_cached, gx_dec[depth - 1]): word step, out_linear, fan-out
@@ -131,6 +138,25 @@ int s2vt_beam_step_gx(const s2vt_dims* d, const s2vt_params* p, int32_t R, const
     S2VT_REQUIRE(cache && gx_vid, "s2vt_beam_step_gx: null cache / gx_vid");
     return beam_step_impl(d, p, R, row_b, row_state, tok, nullptr, nullptr, nullptr, nullptr, word_h_in, word_c_in, word_h_out,
                           word_c_out, top_ix, top_lp, workspace, workspace_bytes, cache, cache_bytes, stream, gx_vid);
+}
+// the depth step of the constrained search, all three forms: gx_vid != null - s2vt_beam_step_gx's (needs the cache); else cache !=
+// null - s2vt_beam_step_cached's; else s2vt_beam_step's
+int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                               const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                               const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                               int32_t* top_ix, float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                               const s2vt_constraints* c, const int32_t* hist, int64_t hist_ld, int32_t t, void* stream) {
+    S2VT_REQUIRE(c, "s2vt_beam_step_constrained: null constraints");
+    S2VT_REQUIRE(!gx_vid || cache, "s2vt_beam_step_constrained: gx_vid needs the cache");
+    S2VT_REQUIRE(t >= 0 && t <= 1023 && (t == 0 || (hist && hist_ld >= t)), "s2vt_beam_step_constrained: t %d outside [0, 1023], or no history",
+                 (int)t);
+    const BeamCon con{"s2vt_beam_step_constrained", c, hist, hist_ld, t};
+    if (gx_vid) {                  // (beam_step_impl takes vid_rnn's step from gx_vid; s2vt_beam_step_gx passes no states either)
+        vid_h_in = vid_c_in = nullptr;
+        vid_h_out = vid_c_out = nullptr;
+    }
+    return beam_step_impl(d, p, R, row_b, row_state, tok, vid_h_in, vid_c_in, vid_h_out, vid_c_out, word_h_in, word_c_in, word_h_out,
+                          word_c_out, top_ix, top_lp, workspace, workspace_bytes, cache, cache ? cache_bytes : 0, stream, gx_vid, &con);
 }
 int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
                    const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,

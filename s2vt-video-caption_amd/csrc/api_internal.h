@@ -378,4 +378,11 @@ int encode_scratch(hipStream_t st, size_t bytes, void** out);
 // the L frames in `states` and vid_rnn's half of word_rnn's gate input (+ biases) of the S decode steps in gx_dec [S][B][4H].
 int score_encode_per_step(const s2vt_dims& d, const s2vt_params* p, const float* feats, int S, float* states, float* gx_dec, const Lane& ln);
 
+// ------------------------------------------------------------------ api_sample_rows.hip (shared with the constrained depth step, api_beam.hip)
+// The constrained beam's fan-out head (ce.hip, top20_logprob_constrained) behind the host-side argument checks of
+// s2vt_constrained_draw, V >= 20 and V >= 20 + t + n_banned + 1; fn names the entry point in the messages.  EDITS `logits`.  With
+// every constraint off it runs top20_logprob.
+int top20_constrained_checked(const char* fn, hipStream_t st, float* logits, int64_t ld, int64_t rows, int V, const int32_t* hist,
+                              int64_t hist_ld, int t, const s2vt_constraints* c, int32_t* top_ix, float* top_lp);
+
 }  // namespace s2vt

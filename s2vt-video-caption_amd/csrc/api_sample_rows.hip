@@ -93,6 +93,26 @@ static ConstrainArgs constrain_at(ConstrainArgs a, const s2vt_constraints* c, co
     return a;
 }
 
+// The constrained beam's fan-out head behind the host-side checks of the constrained draw (api_internal.h): the per-op entry and
+// the constrained depth step (api_beam.hip) run it.  With every constraint off: top20_logprob, today's launch.
+namespace s2vt {
+int top20_constrained_checked(const char* fn, hipStream_t st, float* logits, int64_t ld, int64_t rows, int V, const int32_t* hist,
+                              int64_t hist_ld, int t, const s2vt_constraints* c, int32_t* top_ix, float* top_lp) {
+    S2VT_REQUIRE(logits && top_ix && top_lp && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V, "%s: null/invalid argument", fn);
+    S2VT_REQUIRE(V >= 20 && (size_t)V * sizeof(float) <= 150 * 1024, "%s: vocab_size %d outside [20, 38400]", fn, (int)V);
+    ConstrainArgs ca;
+    int rc;
+    if ((rc = check_constraints(fn, c, V, 0, 1.f, 0, 1.f, &ca))) return rc;
+    S2VT_REQUIRE(t >= 0 && t <= 1023, "%s: t %d outside [0, 1023]", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist, "%s: null history at t = %d", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist_ld >= t, "%s: hist_ld %lld < t %d", fn, (long long)hist_ld, (int)t);
+    if (constraints_off(c)) return top20_logprob(st, logits, ld, rows, V, top_ix, top_lp);
+    S2VT_REQUIRE(V >= 20 + t + c->n_banned + 1, "%s: vocab_size %d < 20 + t + n_banned + 1 = %d: a row could keep fewer than 20 words", fn,
+                 (int)V, 20 + t + (int)c->n_banned + 1);
+    return top20_logprob_constrained(st, logits, ld, rows, V, constrain_at(ca, c, nullptr, 0, t), hist, hist_ld, top_ix, top_lp);
+}
+}  // namespace s2vt
+
 // All three entry points (fn names the one that was called).  trunc: the workspace has the logits buffer and a step's head is the logits
 // GEMM + the truncated draw - unless top_k / top_p truncate nothing, which runs the fused head like the plain entry point.
 // con: s2vt_decode_rows_constrained - a greedy flag and the constraints on top of trunc; with every constraint off it runs the
@@ -256,6 +276,11 @@ int s2vt_constrained_draw(float* logits, int64_t ld, int64_t rows, int32_t V, co
 int s2vt_top20_logprob(const float* logits, int64_t ld, int64_t rows, int32_t V, int32_t* top_ix, float* top_lp, void* stream) {
     S2VT_REQUIRE(logits && top_ix && top_lp && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V, "s2vt_top20_logprob: null/invalid argument");
     return top20_logprob((hipStream_t)stream, logits, ld, rows, V, top_ix, top_lp);
+}
+int s2vt_top20_logprob_constrained(float* logits, int64_t ld, int64_t rows, int32_t V, const int32_t* hist, int64_t hist_ld, int32_t t,
+                                   const s2vt_constraints* c, int32_t* top_ix, float* top_lp, void* stream) {
+    return top20_constrained_checked("s2vt_top20_logprob_constrained", (hipStream_t)stream, logits, ld, rows, V, hist, hist_ld, t, c, top_ix,
+                                     top_lp);
 }
 int s2vt_truncated_draw(const float* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p,
                         uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream) {

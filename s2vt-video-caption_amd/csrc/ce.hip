@@ -243,7 +243,7 @@ constexpr int TOPK_N = 20;
 // Same arithmetic in the same order for every Row: max, then the sum of expf(x - max) per thread in ascending i, wave
 // butterflies, (w0 + w1) + (w2 + w3); ties -> the lower token id.
 template <class Row>
-__global__ __launch_bounds__(256) void top20_logprob_kernel(const float* logits, int64_t ld, int V, int32_t* top_ix, float* top_lp) {
+__device__ __forceinline__ void top20_logprob_row(const float* logits, int64_t ld, int V, int32_t* top_ix, float* top_lp) {
     __shared__ float red_v[4];
     __shared__ int red_i[4];
     __shared__ float sel_v[TOPK_N];
@@ -276,6 +276,53 @@ __global__ __launch_bounds__(256) void top20_logprob_kernel(const float* logits,
         top_ix[(int64_t)blockIdx.x * TOPK_N + rank] = my;
         top_lp[(int64_t)blockIdx.x * TOPK_N + rank] = sel_v[tid] - lse;
     }
+}
+template <class Row>
+__global__ __launch_bounds__(256) void top20_logprob_kernel(const float* logits, int64_t ld, int V, int32_t* top_ix, float* top_lp) {
+    top20_logprob_row<Row>(logits, ld, V, top_ix, top_lp);
+}
+// The fan-out of the CONSTRAINED cumulative beam search (S2VT.beam_constrained; include/s2vt_hip.h "constrained beam"): the
+// constraint phase of the constrained draw (row_frame.h, constrain_row) in front of the same row work, in the same launch - the
+// row of `logits` is EDITED IN PLACE, then loaded: max, sum-exp and the 20 extractions see the edited row, so the log-probs are
+// renormalised over the surviving words and a banned word (-inf) is never extracted while 20 finite words are left (the callers
+// refuse shapes that could leave fewer: V >= 20 + t + n_banned + 1).  The row's history is beam slot blockIdx.x's own words,
+// int32 hist[row * hist_ld + i] (beam_cum.hip keeps them).  expf(-inf - max) is +0: an edited element adds nothing to the sum.
+// LDS: the phase's 1057 * 5 bytes + 176 here, beside LdsRow's 150 KiB (row_frame.h asserts the sum against 160 KiB).
+template <class Row>
+__global__ __launch_bounds__(256) void top20_logprob_constrained_kernel(float* logits, int64_t ld, int V, ConstrainArgs c, BeamHist hist,
+                                                                        int32_t* top_ix, float* top_lp) {
+    constrain_row(c, hist, logits + (int64_t)blockIdx.x * ld, V);
+    top20_logprob_row<Row>(logits, ld, V, top_ix, top_lp);
+}
+
+int top20_logprob_constrained(hipStream_t s, float* logits, int64_t ld, int64_t rows, int V, const ConstrainArgs& c, const int32_t* hist,
+                              int64_t hist_ld, int32_t* top_ix, float* top_lp) {
+    if (rows <= 0) return 0;
+    S2VT_REQUIRE(logits && top_ix && top_lp && ld >= V && rows < (1ll << 31), "top20_logprob_constrained: bad arguments");
+    S2VT_REQUIRE(V >= TOPK_N && (size_t)V * sizeof(float) <= ROW_MAX_LDS, "top20_logprob_constrained: 20 <= vocab_size <= 38400");
+    S2VT_REQUIRE(c.t >= 0 && c.t <= CONSTRAIN_MAX_T && c.n_banned >= 0 && c.n_banned <= CONSTRAIN_MAX_BANNED && c.ngram >= 0 &&
+                     c.eos < V && (c.t == 0 || (hist && hist_ld >= c.t)),
+                 "top20_logprob_constrained: bad constraints");
+    for (int i = 0; i < c.n_banned; ++i)
+        S2VT_REQUIRE(c.banned[i] >= 0 && c.banned[i] < V, "top20_logprob_constrained: banned id outside [0, V)");
+    S2VT_REQUIRE(V >= TOPK_N + c.t + c.n_banned + 1,
+                 "top20_logprob_constrained: vocab_size %d < 20 + t + n_banned + 1 = %d: a row could keep fewer than 20 words", V,
+                 TOPK_N + c.t + c.n_banned + 1);
+    const BeamHist h{hist, hist_ld};
+    const dim3 grid((unsigned)rows), block(256);
+    const size_t lds = (size_t)V * sizeof(float);          // (the LDS form's dynamic LDS)
+    if (V <= 256 * 16) hipLaunchKernelGGL(top20_logprob_constrained_kernel<RegRow<16>>, grid, block, 0, s, logits, ld, V, c, h, top_ix, top_lp);
+    else if (V <= 256 * 32) hipLaunchKernelGGL(top20_logprob_constrained_kernel<RegRow<32>>, grid, block, 0, s, logits, ld, V, c, h, top_ix, top_lp);
+    else if (V <= 256 * 48) hipLaunchKernelGGL(top20_logprob_constrained_kernel<RegRow<48>>, grid, block, 0, s, logits, ld, V, c, h, top_ix, top_lp);
+    else if (V <= 256 * 64) hipLaunchKernelGGL(top20_logprob_constrained_kernel<RegRow<64>>, grid, block, 0, s, logits, ld, V, c, h, top_ix, top_lp);
+    else {
+        if (lds > 48 * 1024)
+            S2VT_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(top20_logprob_constrained_kernel<LdsRow>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(top20_logprob_constrained_kernel<LdsRow>, grid, block, lds, s, logits, ld, V, c, h, top_ix, top_lp);
+    }
+    S2VT_LAUNCH_CHECK("top20_logprob_constrained_kernel");
+    return 0;
 }
 
 int top20_logprob(hipStream_t s, const float* logits, int64_t ld, int64_t rows, int V, int32_t* top_ix, float* top_lp) {

@@ -1,7 +1,8 @@
 // The frame of the row kernels (ce.hip: the three criteria, their gradients, the beam searches' top-20 fan-out; split.hip: the
 // fused criterion backward; truncate.hip: the truncated draw): 256-thread block reductions in ONE fixed order, the two places a
-// one-workgroup-per-row kernel keeps its row (RegRow<VPT> / LdsRow), the [:, 1:] read of a [B, L] matrix by flat row, the clamp of
-// a bad target and the CE gradient of one element.  Device code only.
+// one-workgroup-per-row kernel keeps its row (RegRow<VPT> / LdsRow), the constraint phase that the constrained draw and the
+// constrained fan-out run in front of their row's load (constrain_row), the [:, 1:] read of a [B, L] matrix by flat row, the
+// clamp of a bad target and the CE gradient of one element.  Device code only.
 #pragma once
 #include "common.h"
 
@@ -148,6 +149,86 @@ struct LdsRow {
     template <class F>
     __device__ __forceinline__ void slots(int V, F f) { each(V, f); }       // (no pad slots)
 };
+
+// ---- the constraint phase of the constrained row kernels (include/s2vt_hip.h "constrained draw"; sampling.constrain_logits restates
+// it in numpy): repetition penalty, no-repeat n-gram blocking, banned ids and a minimum length, applied to the RAW logits row x
+// IN PLACE in global memory, in front of the row's load and in the same launch - truncate.hip's constrained draw and ce.hip's
+// constrained top-20 fan-out.  The row's history h[0..t) comes through an accessor (hist(i) = word i of THIS workgroup's row):
+//   PackedHist   the decode drivers' packed words, hist[i * ld + row]; the token is 0xFFFFFFFF - the low half
+//   BeamHist     the cumulative beam search's per-slot words (beam_cum.hip), int32 hist[row * ld + i]
+//   candidates   c in [0, C), C = t + n_banned (+ 1): the t history tokens, the banned ids, <eos> while t < min_length - kept in
+//                static LDS (tok) with one flag byte each (ban): the "edit list"
+//   n-gram       one thread per start position i in [0, t - n]: n - 1 compares of h[i ..] against the suffix h[t-n+1 ..]; a match
+//                flags position i + n - 1 (its own byte: no two threads write one)
+//   edit         one thread per candidate c scans the list once: an EARLIER candidate with the same token owns the element (this
+//                thread leaves), otherwise c is the element's only writer - it ORs the ban flags of every candidate with its token,
+//                and writes -inf (a ban wins) or, where the token is in the history, the penalised value
+// One barrier behind the stores orders them against the loads of row.load_max for the whole workgroup (its waves share a compute
+// unit and its vector cache; not a threadgroup-split build).  Every loop runs to t, n, C or a compile-time count.  Tokens outside
+// [0, V) (a history that no driver wrote) are matched like any other but never stored to.
+// LDS: 1057 * 5 bytes here + the caller's few hundred - beside LdsRow's 150 KiB inside the 160 KiB of a workgroup.
+constexpr int CONSTRAIN_MAX_T = 1023, CONSTRAIN_MAX_BANNED = 32;
+constexpr int CONSTRAIN_MAX_C = CONSTRAIN_MAX_T + CONSTRAIN_MAX_BANNED + 1;
+constexpr int ROW_MAX_LDS = 150 * 1024;                    // LdsRow's dynamic LDS at the largest vocabulary the row kernels take
+static_assert(ROW_MAX_LDS + CONSTRAIN_MAX_C * 5 + 1024 <= 160 * 1024,
+              "LdsRow's row + the constraint phase's edit list + a row kernel's own words must fit a workgroup's 160 KiB of LDS");
+
+struct PackedHist {
+    const unsigned long long* hist; int64_t ld;
+    __device__ __forceinline__ int operator()(int i) const {
+        return (int)(0xFFFFFFFFu - (uint32_t)(hist[(int64_t)i * ld + blockIdx.x] & 0xFFFFFFFFull));
+    }
+};
+struct BeamHist {
+    const int32_t* hist; int64_t ld;
+    __device__ __forceinline__ int operator()(int i) const { return hist[(int64_t)blockIdx.x * ld + i]; }
+};
+
+// CA: kernels.h's ConstrainArgs (t, ngram, theta, inv_theta, eos, n_banned, banned); x: the workgroup's row
+template <class Hist, class CA>
+__device__ __forceinline__ void constrain_row(const CA& c, const Hist& hist, float* x, int V) {
+    __shared__ int tok[CONSTRAIN_MAX_C];
+    __shared__ unsigned char ban[CONSTRAIN_MAX_C];
+    const int t = c.t, n = c.ngram, nb = c.n_banned;
+    const int C = t + nb + (c.eos >= 0 ? 1 : 0);
+    if (n > 0 || nb > 0 || c.eos >= 0 || c.theta != 1.f) {      // (block-uniform; nothing to edit: the caller's row work alone)
+        for (int i = threadIdx.x; i < C; i += 256) {
+            int v;
+            if (i < t) v = hist(i);
+            else if (i < t + nb) v = c.banned[i - t];
+            else v = c.eos;
+            tok[i] = v;
+            ban[i] = i < t ? 0 : 1;
+        }
+        __syncthreads();
+        if (n > 0) {
+            for (int i = threadIdx.x; i <= t - n; i += 256) {
+                bool same = true;
+                for (int k = 0; k < n - 1; ++k) same = same && tok[i + k] == tok[t - n + 1 + k];
+                if (same) ban[i + n - 1] = 1;
+            }
+            __syncthreads();
+        }
+        for (int i = threadIdx.x; i < C; i += 256) {
+            const int v = tok[i];
+            const bool valid = (unsigned)v < (unsigned)V;
+            const float xv = valid ? x[v] : 0.f;               // (issued in front of the scan: its latency runs beside it)
+            bool first = true, banned = false, seen = false;
+            // (no early exit: a plain reduction over the list, whose LDS reads the compiler batches)
+#pragma unroll 8
+            for (int k = 0; k < C; ++k) {
+                const bool same = tok[k] == v;
+                first = first && !(same && k < i);
+                banned = banned || (same && ban[k] != 0);
+                seen = seen || (same && k < t);
+            }
+            if (!(valid && first)) continue;
+            if (banned) x[v] = -INFINITY;
+            else if (seen && c.theta != 1.f) x[v] = xv > 0.f ? xv * c.inv_theta : xv * c.theta;
+        }
+        __syncthreads();                                       // the stores above -> the loads of load_max, workgroup scope
+    }
+}
 
 // x[:, 1:] of a [B, L] matrix (row stride ld) by flat row r = b * Lm1 + j  ->  x[b * ld + j + 1]: targets, masks, weights
 // (R: the caller's row type - the division is 32-bit where its row index is)

@@ -172,19 +172,9 @@ __global__ __launch_bounds__(256) void truncated_draw_kernel(TruncArgs p, Gumbel
 // penalty, no-repeat n-gram blocking, banned ids and a minimum length, applied to the RAW logits row IN PLACE in global memory in
 // front of the load - the same launch, the same workgroup per row; then either the truncated draw above on the edited row or the
 // plain arg-max (GREEDY: no noise, no bisection).  The row's history h[0..t) comes from the drivers' packed words.
-//   candidates   c in [0, C), C = t + n_banned (+ 1): the t history tokens, the banned ids, <eos> while t < min_length - kept in
-//                static LDS (tok) with one flag byte each (ban): the "edit list"
-//   n-gram       one thread per start position i in [0, t - n]: n - 1 compares of h[i ..] against the suffix h[t-n+1 ..]; a match
-//                flags position i + n - 1 (its own byte: no two threads write one)
-//   edit         one thread per candidate c scans the list once: an EARLIER candidate with the same token owns the element (this
-//                thread leaves), otherwise c is the element's only writer - it ORs the ban flags of every candidate with its token,
-//                and writes -inf (a ban wins) or, where the token is in the history, the penalised value
-// One barrier behind the stores orders them against the loads of row.load_max for the whole workgroup (its waves share a compute
-// unit and its vector cache; not a threadgroup-split build).  Every loop runs to t, n, C or a compile-time count.  Tokens outside
-// [0, V) (a history that no driver wrote) are matched like any other but never stored to.
-// LDS: 1057 * 5 bytes here + 96 of the draw - beside LdsRow's 150 KiB inside the 160 KiB of a workgroup.
-constexpr int CONSTRAIN_MAX_T = 1023, CONSTRAIN_MAX_BANNED = 32;
-constexpr int CONSTRAIN_MAX_C = CONSTRAIN_MAX_T + CONSTRAIN_MAX_BANNED + 1;
+// The phase itself - edit list, suffix match, one writer per distinct word, one barrier - is row_frame.h's constrain_row, shared
+// with the constrained top-20 fan-out of ce.hip; here it reads the history through PackedHist.
+// LDS: 1057 * 5 bytes of the phase + 96 of the draw - beside LdsRow's 150 KiB inside the 160 KiB of a workgroup.
 
 template <class Row>
 __device__ __forceinline__ void greedy_pick_row(const TruncArgs& p) {
@@ -217,48 +207,7 @@ __device__ __forceinline__ void greedy_pick_row(const TruncArgs& p) {
 
 template <class Row, bool GREEDY>
 __global__ __launch_bounds__(256) void constrained_draw_kernel(TruncArgs p, GumbelArgs ga, ConstrainArgs c, float* x_rows) {
-    __shared__ int tok[CONSTRAIN_MAX_C];
-    __shared__ unsigned char ban[CONSTRAIN_MAX_C];
-    const int t = c.t, n = c.ngram, nb = c.n_banned, V = p.V;
-    const int C = t + nb + (c.eos >= 0 ? 1 : 0);
-    float* x = x_rows + (int64_t)blockIdx.x * p.ld;
-    if (n > 0 || nb > 0 || c.eos >= 0 || c.theta != 1.f) {      // (block-uniform; nothing to edit: the draw alone)
-        for (int i = threadIdx.x; i < C; i += 256) {
-            int v;
-            if (i < t) v = (int)(0xFFFFFFFFu - (uint32_t)(c.hist[(int64_t)i * c.hist_ld + blockIdx.x] & 0xFFFFFFFFull));
-            else if (i < t + nb) v = c.banned[i - t];
-            else v = c.eos;
-            tok[i] = v;
-            ban[i] = i < t ? 0 : 1;
-        }
-        __syncthreads();
-        if (n > 0) {
-            for (int i = threadIdx.x; i <= t - n; i += 256) {
-                bool same = true;
-                for (int k = 0; k < n - 1; ++k) same = same && tok[i + k] == tok[t - n + 1 + k];
-                if (same) ban[i + n - 1] = 1;
-            }
-            __syncthreads();
-        }
-        for (int i = threadIdx.x; i < C; i += 256) {
-            const int v = tok[i];
-            const bool valid = (unsigned)v < (unsigned)V;
-            const float xv = valid ? x[v] : 0.f;               // (issued in front of the scan: its latency runs beside it)
-            bool first = true, banned = false, seen = false;
-            // (no early exit: a plain reduction over the list, whose LDS reads the compiler batches)
-#pragma unroll 8
-            for (int k = 0; k < C; ++k) {
-                const bool same = tok[k] == v;
-                first = first && !(same && k < i);
-                banned = banned || (same && ban[k] != 0);
-                seen = seen || (same && k < t);
-            }
-            if (!(valid && first)) continue;
-            if (banned) x[v] = -INFINITY;
-            else if (seen && c.theta != 1.f) x[v] = xv > 0.f ? xv * c.inv_theta : xv * c.theta;
-        }
-        __syncthreads();                                       // the stores above -> the loads of load_max, workgroup scope
-    }
+    constrain_row(c, PackedHist{c.hist, c.hist_ld}, x_rows + (int64_t)blockIdx.x * p.ld, p.V);
     if constexpr (GREEDY) greedy_pick_row<Row>(p);
     else truncated_draw_row<Row>(p, ga);
 }

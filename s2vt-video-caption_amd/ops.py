@@ -334,6 +334,35 @@ def top20_logprob(logits):
     return ix, lp
 
 
+def top20_logprob_constrained(logits, hist, t, spec):
+    """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20]): top20_logprob of the rows CONSTRAINED by `spec` (a sampling.ConstraintSpec)
+    at step t - the fan-out head of S2VT.beam_constrained on its own (s2vt_top20_logprob_constrained; include/s2vt_hip.h "constrained
+    beam").  THE CALL MODIFIES `logits` (fp32 [rows, V], unit column stride): afterwards it holds sampling.constrain_logits of the
+    rows, and the log-probs are log_softmax of those.  hist: int32 [rows, >= t] with unit column stride, row r's words hist[r, :t]
+    (the beam slots' layout); None where t == 0.  V >= 20 + t + banned ids + 1."""
+    from .sampling import constraints_struct
+    lib = capi.load()
+    require_hip(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    t = int(t)
+    hist_ld = 0
+    if t > 0:
+        require_hip(hist, "hist")
+        if hist.dim() != 2 or hist.dtype != torch.int32 or hist.stride(1) != 1 or hist.shape[0] < rows or hist.shape[1] < t:
+            raise ValueError("hist must be int32 [>= rows = %d, >= t = %d] with unit column stride" % (rows, t))
+        hist_ld = hist.stride(0)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ix = torch.empty(rows, 20, dtype=torch.int32, device=dev)
+        lp = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        cs, keep = constraints_struct(spec)
+        capi.check(lib.s2vt_top20_logprob_constrained(_ptr(logits), logits.stride(0), rows, V, _ptr(hist) if t > 0 else None, hist_ld, t,
+                                                      ctypes.byref(cs), _ptr(ix), _ptr(lp), _stream(dev)), "s2vt_top20_logprob_constrained")
+    return ix, lp
+
+
 def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0, constraints=None):
     """out_linear + arg-max of one decode step into the caller's packed word row `packed_i` (int64 [B], zeroed) - what the greedy
     loops of the GRU and stacked models run per step; sample = (temperature, seed): the draw of mode='sample' for decode step
