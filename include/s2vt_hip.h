@@ -280,6 +280,61 @@ int s2vt_greedy_decode_cached(const s2vt_dims* d, const s2vt_params* p, const fl
 int s2vt_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1, double beta2,
                    double eps, int64_t step, void* stream);
 
+/* ---------------------------------------------------------------- clipped step: global-norm clipping, weight decay, non-finite skip
+ * (optim.FlatAdam(max_grad_norm=, weight_decay=, decoupled=, no_decay=, skip_nonfinite=); csrc/optim.hip; restated in numpy by
+ * tests/optim_ref.step_ref).  s2vt_adam_step above is unchanged and is what FlatAdam launches at its defaults; these two entry
+ * points stand beside it.  For flat buffers of n elements (the layout of s2vt_adam_step), gradients g, max_norm = c:
+ *   1. norm     S = sum of (double)g_i * (double)g_i in fp64 (an fp32 square is exact there); grad_norm = fp32(sqrt(S)).  The order is
+ *               fixed: the chunk [w C, min((w+1) C, n)) with C = S2VT_GRAD_NORM_CHUNK gives one fp64 partial (per thread in ascending
+ *               element order, wave butterfly, (w0 + w1) + (w2 + w3)), written to the workspace by a plain store; a second launch of
+ *               ONE workgroup sums the partials in the same manner.  The number of partials depends on n alone.  No floating-point
+ *               atomics, no ticket, no cooperative launch, no wait across workgroups: the launch boundary is the synchronisation, and
+ *               the same gradients give the same record bits on every call.  A 4-byte-aligned `grads` that is not 16-byte aligned is
+ *               loaded element by element and gives the same bits.
+ *   2. record   scale = 1 if c <= 0 (no clipping), else coef = fp32(c) / (grad_norm + 1e-6f) and scale = coef >= 1 ? 1 : coef, all
+ *               in fp32 - the rule of torch.nn.utils.clip_grad_norm_ (a NaN coef stays NaN, as torch.clamp leaves it).
+ *               nonfinite = !isfinite(grad_norm): an inf or NaN gradient, or a norm above fp32's range.
+ *               skipped_total += nonfinite if skip_nonfinite (the caller zeroes the record ONCE; the library only ever adds).
+ *   3. step     if skip_nonfinite and record.nonfinite: nothing is written, params / exp_avg / exp_avg_sq keep their bits.  Otherwise
+ *               per element, every product and sum rounded to fp32 on its own:
+ *                 g' = g * scale
+ *                 coupled decay   (decoupled == 0, torch.optim.Adam(weight_decay=)):  g' = g' + fp32(wd) * p   where the element's
+ *                                 segment is decayed
+ *                 decoupled decay (decoupled != 0, torch.optim.AdamW):  p = p * f, f = fp32(1.0 - lr * wd) formed in double on the
+ *                                 host, where the element's segment is decayed
+ *                 then the update of s2vt_adam_step on (p, g', m, v) - the two kernels compile one expression, so a step at scale 1
+ *                 without decay is s2vt_adam_step bit for bit.
+ *               Segments: seg_end[0 .. n_seg) ascending with seg_end[n_seg - 1] == n, segment k = [seg_end[k-1], seg_end[k]), decayed iff
+ *               seg_decay[k] != 0; n_seg == 0: one segment, decayed.  Ends need not be multiples of 4: every element takes its own
+ *               segment's flag.  One wd and one f for all decayed segments; wd == 0 decays nothing.  seg_end / seg_decay are HOST
+ *               arrays, copied into the launch arguments (at most S2VT_ADAM_MAX_SEGMENTS).
+ * THE CLIPPED GRADIENT IS NOT WRITTEN BACK: `grads` keeps the unclipped gradient (4 bytes per parameter per step saved; the norm and
+ * the scale are on the record).  A SKIPPED STEP STILL COUNTS AS A STEP: the bias corrections are formed on the host from `step`, as in
+ * s2vt_adam_step, and the host does not learn of a skip without reading the record - so the caller advances `step` regardless.
+ * `record`: an s2vt_clip_record in device memory, 16-byte aligned.  s2vt_adam_step_clipped reads scale and nonfinite from it ON
+ * THE DEVICE (no host round trip: norm + step are three launches); record == NULL there means scale 1 and needs skip_nonfinite == 0
+ * (weight decay alone needs no norm).  `workspace`: s2vt_grad_norm_workspace_bytes(n) bytes of device memory, 8-byte aligned
+ * (0 for n <= 0).
+ * Checked on the host before anything is enqueued (S2VT_ERR_ARG; s2vt_last_error names the rule): n > 0; null buffers; params /
+ * grads / moments not 16-byte aligned (s2vt_grad_norm: grads not 4-byte aligned); record null or not 16-byte aligned; step < 1;
+ * weight_decay negative or not finite; n_seg outside [0, 16]; segment ends not ascending or not ending at n; max_norm NaN or -inf
+ * (any max_norm <= 0 otherwise means no clipping); a workspace that is null or too small. */
+#define S2VT_GRAD_NORM_CHUNK 16384
+#define S2VT_ADAM_MAX_SEGMENTS 16
+typedef struct s2vt_clip_record {
+    float grad_norm;       /* fp32(sqrt(sum of squares in fp64)) of the last s2vt_grad_norm */
+    float scale;           /* what s2vt_adam_step_clipped multiplies every gradient with */
+    int32_t nonfinite;     /* 1: grad_norm is inf or NaN */
+    int32_t pad;
+    int64_t skipped_total; /* calls with skip_nonfinite != 0 that found nonfinite == 1 */
+} s2vt_clip_record;
+size_t s2vt_grad_norm_workspace_bytes(int64_t n);
+int s2vt_grad_norm(const float* grads, int64_t n, double max_norm, int32_t skip_nonfinite, void* workspace, size_t workspace_bytes,
+                   void* record, void* stream);
+int s2vt_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
+                           double beta2, double eps, int64_t step, double weight_decay, int32_t decoupled, const int64_t* seg_end,
+                           const int32_t* seg_decay, int32_t n_seg, int32_t skip_nonfinite, const void* record, void* stream);
+
 /* MaskCriterion's inner nn.CrossEntropyLoss() (utils.py:11,22): mean CE of logits [B, L-1, V] against
  * target[:, 1:] (target int64 [B, L], row stride target_ld).  lse [B*(L-1)] and rowloss [B*(L-1)] are
  * caller-provided scratch (lse is consumed by the backward); loss_out is one device float.

@@ -58,6 +58,14 @@ class Constraints(ctypes.Structure):
 
 
 CIDER_MAX_T = 512        # S2VT_CIDER_MAX_T of include/s2vt_hip.h
+GRAD_NORM_CHUNK = 16384  # S2VT_GRAD_NORM_CHUNK: gradient elements per fp64 partial of s2vt_grad_norm
+ADAM_MAX_SEGMENTS = 16   # S2VT_ADAM_MAX_SEGMENTS
+
+
+class ClipRecord(ctypes.Structure):
+    """s2vt_clip_record of include/s2vt_hip.h: what s2vt_grad_norm leaves on the device for s2vt_adam_step_clipped"""
+    _fields_ = [("grad_norm", c_float), ("scale", c_float), ("nonfinite", c_int32), ("pad", c_int32), ("skipped_total", c_int64)]
+
 
 # name -> (restype, argtypes): every symbol include/s2vt_hip.h declares
 ABI_VERSION = 9          # S2VT_ABI_VERSION of include/s2vt_hip.h this binding was written against
@@ -95,6 +103,11 @@ SIGNATURES = {
     "s2vt_greedy_decode_cached": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_int32, c_void_p, c_void_p, c_size_t,
                                             c_void_p, c_size_t, c_int32, c_void_p]),
     "s2vt_adam_step": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_int64, c_void_p]),
+    # the clipped step (csrc/optim.hip): fp64 gradient norm + clip record, then Adam with clipping / weight decay / non-finite skip
+    "s2vt_grad_norm_workspace_bytes": (c_size_t, [c_int64]),
+    "s2vt_grad_norm": (c_int32, [c_void_p, c_int64, c_double, c_int32, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "s2vt_adam_step_clipped": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_double, c_double, c_double, c_double, c_int64,
+                                         c_double, c_int32, POINTER(c_int64), POINTER(c_int32), c_int32, c_int32, c_void_p, c_void_p]),
     "s2vt_mean_ce_forward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                        c_void_p, c_void_p]),
     "s2vt_mean_ce_backward": (c_int32, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,

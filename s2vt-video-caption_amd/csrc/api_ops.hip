@@ -13,6 +13,21 @@ int s2vt_adam_step(float* params, const float* grads, float* exp_avg, float* exp
     return adam_flat((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step);
 }
 
+// what stands around it: the fp64 gradient norm with its clip record, and the step that clips, decays and skips by that record (optim.hip)
+size_t s2vt_grad_norm_workspace_bytes(int64_t n) { return grad_norm_workspace_bytes(n); }
+int s2vt_grad_norm(const float* grads, int64_t n, double max_norm, int32_t skip_nonfinite, void* workspace, size_t workspace_bytes,
+                   void* record, void* stream) {
+    static_assert(sizeof(ClipRecord) == sizeof(s2vt_clip_record) && GN_CHUNK == S2VT_GRAD_NORM_CHUNK && ADAM_MAX_SEGS == S2VT_ADAM_MAX_SEGMENTS,
+                  "kernels.h and s2vt_hip.h state the same record and constants");
+    return grad_norm((hipStream_t)stream, grads, n, max_norm, skip_nonfinite, workspace, workspace_bytes, static_cast<ClipRecord*>(record));
+}
+int s2vt_adam_step_clipped(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, double lr, double beta1,
+                           double beta2, double eps, int64_t step, double weight_decay, int32_t decoupled, const int64_t* seg_end,
+                           const int32_t* seg_decay, int32_t n_seg, int32_t skip_nonfinite, const void* record, void* stream) {
+    return adam_flat_clipped((hipStream_t)stream, params, grads, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, step, weight_decay, decoupled,
+                             seg_end, seg_decay, n_seg, skip_nonfinite, static_cast<const ClipRecord*>(record));
+}
+
 int s2vt_mean_ce_forward(int32_t B, int32_t Lm1, int32_t V, const float* logits, const int64_t* target,
                          int64_t target_ld, float* lse, float* rowloss, float* loss_out, void* stream) {
     S2VT_REQUIRE(B > 0 && Lm1 > 0 && V > 0, "s2vt_mean_ce_forward: bad dims");

@@ -91,6 +91,16 @@ static __device__ __attribute__((aligned(16))) float g_zero4[4] = {0.f, 0.f, 0.f
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanhf_(float x) { return 1.0f - 2.0f / (1.0f + __expf(2.0f * x)); }
 
+// One element of torch.optim.Adam's update (the arithmetic is stated at adam_flat_kernel, misc.hip): the plain step and the clipped
+// step (optim.hip) both call this, so the two kernels compile one expression.
+__device__ __forceinline__ void adam_update(float& pp, float gg, float& mm, float& vv, float w1, float beta2, float w2,
+                                            float step_size, float bc2_sqrt, float eps) {
+    mm = mm + (gg - mm) * w1;
+    vv = beta2 * vv + w2 * gg * gg;
+    const float denom = sqrtf(vv) / bc2_sqrt + eps;
+    pp = pp - step_size * (mm / denom);
+}
+
 // fp32 -> bf16 (round to nearest even; NaN stays NaN) and the three-plane split x = p0 + p1 + p2 (24 mantissa bits) of the
 // split-precision operands (split.hip, gemm_x3.hip)
 __device__ __forceinline__ unsigned short bf16_rn_bits(float x) {

@@ -328,6 +328,21 @@ int logits_argmax_x3(hipStream_t stream, const ArgmaxX3Args& a, const GumbelArgs
 int add_vectors(hipStream_t s, const float* a, const float* b, float* out, int n);
 int adam_flat(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
               int64_t step);
+// ---- optim.hip: the gradient norm in fp64 (two launches), and the Adam step with clipping / weight decay / non-finite skip
+constexpr int GN_CHUNK = 16384;         // = S2VT_GRAD_NORM_CHUNK: gradient elements per fp64 partial (48.1 M parameters: 2938 partials)
+constexpr int ADAM_MAX_SEGS = 16;       // = S2VT_ADAM_MAX_SEGMENTS
+struct ClipRecord {                     // = s2vt_clip_record
+    float grad_norm, scale;
+    int32_t nonfinite, pad;
+    int64_t skipped_total;
+};
+size_t grad_norm_workspace_bytes(int64_t n);
+int grad_norm(hipStream_t s, const float* g, int64_t n, double max_norm, int skip_nonfinite, void* workspace, size_t workspace_bytes,
+              ClipRecord* rec);
+int adam_flat_clipped(hipStream_t s, float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2,
+                      double eps, int64_t step, double weight_decay, int decoupled, const int64_t* seg_end, const int32_t* seg_decay,
+                      int n_seg, int skip_nonfinite, const ClipRecord* rec);
+// ---- misc.hip (continued)
 int mul_vectors(hipStream_t s, const float* a, const float* b, float* out, int64_t n);
 int transpose_f32(hipStream_t s, const float* in, int rows, int cols, float* out);   // out[cols][rows]
 int colsum_f32(hipStream_t s, const float* x, int64_t rows, int cols, int64_t ld, float* partial, float* out,

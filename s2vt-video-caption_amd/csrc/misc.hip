@@ -86,12 +86,7 @@ __global__ __launch_bounds__(256) void adam_flat_kernel(float* __restrict__ p, c
                                                         float* __restrict__ v, int64_t n4, int64_t n, float w1, float beta2, float w2,
                                                         float step_size, float bc2_sqrt, float eps) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    auto upd = [&](float& pp, float gg, float& mm, float& vv) {
-        mm = mm + (gg - mm) * w1;
-        vv = beta2 * vv + w2 * gg * gg;
-        const float denom = sqrtf(vv) / bc2_sqrt + eps;
-        pp = pp - step_size * (mm / denom);
-    };
+    auto upd = [&](float& pp, float gg, float& mm, float& vv) { adam_update(pp, gg, mm, vv, w1, beta2, w2, step_size, bc2_sqrt, eps); };
     if (i < n4) {
         f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];

@@ -212,7 +212,8 @@ def global_mean(total, count, device="cpu"):
     return float(t[0] / torch.clamp(t[1], min=1.0))
 
 
-def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False, forward_kwargs=None, group=None):
+def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, check_errors=False, forward_kwargs=None, max_grad_norm=None,
+               group=None):
     """One optimisation step of train.py:116-127 on this rank's shard; returns the (local) loss tensor.
     With `reducer`, gradients are averaged over ranks before the optimiser step.
     `check_errors`: synchronise and raise device-side errors of this step (a caption id outside the vocabulary -> IndexError, as
@@ -222,7 +223,11 @@ def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, che
     `forward_kwargs`: further keywords of the model's forward (scheduled sampling: ss_prob, ss_temperature).
     `group` = K: K captions per clip on one encode per clip - feats is [B, ...] and caps / mask (or the criterion's weights) are
     [B*K, ...] with row b*K + k the k-th caption of clip b, exactly the rows of the step on feats.repeat_interleave(K, 0), whose
-    loss and gradients this step computes (S2VT.forward with 3-D targets).  None (default): one caption per row of feats."""
+    loss and gradients this step computes (S2VT.forward with 3-D targets).  None (default): one caption per row of feats.
+    `max_grad_norm` = c: torch.nn.utils.clip_grad_norm_(model.parameters(), c) on the (averaged) gradients before optimizer.step() -
+    for torch's optimisers only (GRU, stacked, Att_Baseline).  An optim.FlatAdam clips inside its own device step (its max_grad_norm
+    argument) and ignores this keyword.  The norm clip_grad_norm_ returns (a device tensor, no read) is left in optimizer.grad_norm,
+    the name FlatAdam gives its own."""
     if reducer is not None:
         reducer.zero_grad()
     else:
@@ -257,5 +262,7 @@ def train_step(model, criterion, optimizer, feats, caps, mask, reducer=None, che
                                         "hand-off): stopping with it")
         if err is not None:
             raise err
+    if max_grad_norm is not None and not hasattr(optimizer, "flat_g"):
+        optimizer.grad_norm = torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm)
     optimizer.step()
     return loss.detach()

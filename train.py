@@ -99,7 +99,28 @@ def parse(argv=None):
     ap.add_argument("--scheduled-sampling-max-prob", type=float, default=0.25, metavar="m", help="up to this value")
     ap.add_argument("--ss-temperature", type=float, default=None,
                     help="the model's own word is a draw from softmax(logit / temperature); absent: the arg-max")
+    ap.add_argument("--grad-clip", type=float, default=0.0, metavar="c",
+                    help="global-norm gradient clipping at c before every optimiser step (0, the default: off).  The one-layer LSTM "
+                         "path clips inside the device step (optim.FlatAdam(max_grad_norm=c): the norm in fp64, no host read; p.grad "
+                         "keeps the unclipped gradient); GRU, stacked and att_baseline use torch.nn.utils.clip_grad_norm_")
+    ap.add_argument("--weight-decay", type=float, default=0.0, metavar="w",
+                    help="weight decay (the reference's commented-out Opt.weight_decay = 5e-5): L2 added to the gradient, as "
+                         "torch.optim.Adam(weight_decay=w); with --adamw decoupled, as torch.optim.AdamW.  0 (default): off")
+    ap.add_argument("--adamw", action="store_true", help="decoupled weight decay (p *= 1 - lr * w before the update)")
+    ap.add_argument("--no-decay-bias", action="store_true", help="leave the bias vectors out of the weight decay")
+    ap.add_argument("--skip-nonfinite", action="store_true",
+                    help="a step whose gradient norm is inf or NaN leaves parameters and moments untouched (one-layer LSTM path only: "
+                         "the guard sits in optim.FlatAdam's device step)")
     opt = ap.parse_args(argv)
+    if not opt.grad_clip >= 0.0:
+        ap.error("--grad-clip must be >= 0 (0: off)")
+    if not 0.0 <= opt.weight_decay < float("inf"):
+        ap.error("--weight-decay must be finite and >= 0")
+    if (opt.adamw or opt.no_decay_bias) and opt.weight_decay == 0.0:
+        ap.error("--adamw / --no-decay-bias need --weight-decay")
+    if opt.skip_nonfinite and not (opt.model == "s2vt" and opt.rnn_type == "lstm" and opt.num_layers == 1):
+        ap.error("--skip-nonfinite needs the one-layer LSTM S2VT (optim.FlatAdam's device step); torch's Adam, which trains GRU, "
+                 "stacked and att_baseline models, has no such guard")
     if (opt.sc_samples != 1 or opt.sc_baseline != "greedy") and not opt.self_critical:
         ap.error("--sc-samples / --sc-baseline need --self-critical")
     if opt.sc_samples < 1:
@@ -144,7 +165,8 @@ def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
-                            reducer=None, shared_encode=False, top_k=0, top_p=1.0, samples=1, baseline="greedy"):
+                            reducer=None, shared_encode=False, max_grad_norm=None, top_k=0, top_p=1.0, samples=1,
+                            baseline="greedy"):
     """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
     train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
     (every phase ends with a device synchronisation), hist["reward_sample"] / ["reward_greedy"] the batch means.  sc_reward
@@ -156,7 +178,8 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
     on the clips repeated K times with the B*K captions - or, with shared_encode, on the clips as they are with K captions each
     (dp.train_step(group=K): one encode per clip, same loss and gradients).  hist["reward_baseline"] gets the batch mean of the
     baselines.  top_k / top_p: the truncation of the sampled captions (S2VT.sample_truncated; 0 / 1.0: off) - the loss still
-    weights the full-softmax log-prob of the drawn words."""
+    weights the full-softmax log-prob of the drawn words.  max_grad_norm: dp.train_step's (clipping for torch's optimisers; an
+    optim.FlatAdam carries its own)."""
     from s2vt_video_caption_amd import dp, ops
     from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages
     K = int(samples)
@@ -209,9 +232,11 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
             means = [float(r_s.mean()), float(base.mean())] + ([float(r_g.mean())] if r_g is not None else [])
         t3 = time.perf_counter()
         if shared_encode:
-            loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, group=K)
+            loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, group=K,
+                                 max_grad_norm=max_grad_norm)
         else:
-            loss = dp.train_step(model, reward_criterion, optimizer, feats.repeat_interleave(K, 0), caps, weight, reducer, check_errors=True)
+            loss = dp.train_step(model, reward_criterion, optimizer, feats.repeat_interleave(K, 0), caps, weight, reducer, check_errors=True,
+                                 max_grad_norm=max_grad_norm)
         t4 = time.perf_counter()
         for k, v in (("sample", t1 - t0), ("greedy", t2 - t1 if greedy is not None else 0.0), ("scoring", t3 - t2), ("train", t4 - t3)):
             sp[k] += 1e3 * v
@@ -238,7 +263,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         weight = advantage_weights(sampled, r_s - r_g, eos).to(dev)
         caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
         t3 = time.perf_counter()
-        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
+        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, max_grad_norm=max_grad_norm)
         t4 = time.perf_counter()
         for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
             sp[k] += 1e3 * v
@@ -263,7 +288,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         caps, weight = ops.sc_weights(sampled, r_s, r_g, sos, eos)
         means = torch.stack([r_s.mean(), r_g.mean()]).tolist()          # the phase's synchronisation
         t3 = time.perf_counter()
-        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True)
+        loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, max_grad_norm=max_grad_norm)
         t4 = time.perf_counter()
         for k, v in (("sample", t1 - t0), ("greedy", t2 - t1), ("scoring", t3 - t2), ("train", t4 - t3)):
             sp[k] += 1e3 * v
@@ -347,14 +372,28 @@ def run(opt):
             reducer.attach(model)
     if flat:                    # train.py:89-93's Adam, same arithmetic, as one launch over flat parameter / gradient / moment buffers
         from s2vt_video_caption_amd.optim import FlatAdam
-        optimizer = FlatAdam(model, lr=opt.lr, reducer=reducer)
-    else:
+        optimizer = FlatAdam(model, lr=opt.lr, reducer=reducer, max_grad_norm=opt.grad_clip or None, weight_decay=opt.weight_decay,
+                             decoupled=opt.adamw, no_decay=("bias",) if opt.no_decay_bias else (), skip_nonfinite=opt.skip_nonfinite)
+    elif opt.weight_decay == 0.0:
         optimizer = optim.Adam(model.parameters(), lr=opt.lr)                                       # train.py:89-93
+    else:                       # the reference's commented-out weight_decay=opt.weight_decay; --no-decay-bias: two param groups
+        from s2vt_video_caption_amd.optim import matches_no_decay
+        named = list(model.named_parameters())
+        bias = [p for n, p in named if opt.no_decay_bias and matches_no_decay(n, ("bias",))]
+        groups = [{"params": [p for n, p in named if not any(p is b for b in bias)], "weight_decay": opt.weight_decay}]
+        if bias:
+            groups.append({"params": bias, "weight_decay": 0.0})
+        optimizer = (optim.AdamW if opt.adamw else optim.Adam)(groups, lr=opt.lr)
+    # --grad-clip on torch's optimisers: dp.train_step clips before optimizer.step() (FlatAdam clips inside its device step)
+    clip = opt.grad_clip or None
+    log_norm = opt.grad_clip > 0 or opt.skip_nonfinite
     lr_scheduler = optim.lr_scheduler.ReduceLROnPlateau(optimizer, patience=opt.learning_rate_patience)   # :95-97
     early_stopping = EarlyStopping(patience=opt.early_stopping_patience, verbose=rank == 0,
                                    path=os.path.join(opt.save_path, start_time + 'stop.pth'))        # :98-100
     criterion = MaskCriterion()
     hist = {"train_loss": [], "valid_loss": [], "lr": [], "stopped_at": None, "checkpoints": [], "ss_prob": []}
+    if log_norm:                # (only then: the harness tests compare the keys of hist with the oracle's)
+        hist["grad_norm"], hist["skipped_steps"] = [], []
     rewarder = None
     if opt.self_critical:
         if world > 1 or opt.model != "s2vt":
@@ -375,7 +414,7 @@ def run(opt):
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
                                                      opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline,
-                                                     shared_encode=opt.sc_shared_encode, top_k=opt.sc_top_k, top_p=opt.sc_top_p)
+                                                     shared_encode=opt.sc_shared_encode, top_k=opt.sc_top_k, top_p=opt.sc_top_p, max_grad_norm=clip)
 
     def save(name):
         if rank == 0:
@@ -392,6 +431,7 @@ def run(opt):
         # (ss_prob == 0 passes no keyword at all: the plain teacher-forced step; every process draws its own seeds)
         ss_kwargs = dict(ss_prob=ss_prob, ss_temperature=opt.ss_temperature) if ss_prob > 0 else None
         running, count = 0.0, 0
+        norm_acc = torch.zeros(2, dtype=torch.float64, device=dev)      # sum and count of the epoch's finite gradient norms, on the device
         sc_from = len(hist["reward_baseline"]) if rewarder is not None else 0
         for feats, targets, ids, masks in dataloader.feed_batches(train_loader, dev):
             # train.py:116-127; check_errors: a device-side error of this step (IndexError for a caption id outside the vocabulary)
@@ -400,13 +440,23 @@ def run(opt):
                 loss = self_critical_step(feats, ids)
             elif cpc > 1:       # targets / masks [B, K, L]: row b*K + k of the step = caption k of clip b, the clip encoded once
                 loss = dp.train_step(model, criterion, optimizer, feats, targets.flatten(0, 1), masks.flatten(0, 1), reducer,
-                                     check_errors=True, group=cpc)
+                                     check_errors=True, group=cpc, max_grad_norm=clip)
             else:
                 loss = dp.train_step(model, criterion, optimizer, feats, targets, masks, reducer, check_errors=True,
-                                     forward_kwargs=ss_kwargs)
+                                     forward_kwargs=ss_kwargs, max_grad_norm=clip)
             running += float(loss)
             count += 1
+            if log_norm and getattr(optimizer, "grad_norm", None) is not None:       # no read here: once per epoch, below
+                gn = optimizer.grad_norm.detach().to(torch.float64)
+                ok = torch.isfinite(gn)
+                norm_acc += torch.stack([torch.where(ok, gn, torch.zeros_like(gn)), ok.to(torch.float64)])
         train_loss = running / max(count, 1)
+        norm_text = ""
+        if log_norm:
+            total, finite = norm_acc.tolist()
+            hist["grad_norm"].append(total / max(finite, 1.0))
+            hist["skipped_steps"].append(optimizer.skipped_steps if flat else 0)
+            norm_text = " grad norm: {} skipped steps: {}".format(hist["grad_norm"][-1], hist["skipped_steps"][-1])
         running, count = 0.0, 0
         model.eval()
         with torch.no_grad():
@@ -426,9 +476,9 @@ def run(opt):
             if rewarder is not None and len(hist["reward_baseline"]) > sc_from:      # the epoch's mean sampled reward and baseline
                 n = len(hist["reward_baseline"]) - sc_from
                 sc_text = " reward: {} baseline: {}".format(sum(hist["reward_sample"][sc_from:]) / n, sum(hist["reward_baseline"][sc_from:]) / n)
-            print("epoch {} train loss:{} valid loss: {} lr: {}{}{}".format(
+            print("epoch {} train loss:{} valid loss: {} lr: {}{}{}{}".format(
                 epoch, train_loss, valid_loss, optimizer.param_groups[0]['lr'],
-                " ss_prob: {}".format(ss_prob) if opt.scheduled_sampling_start >= 0 else "", sc_text))
+                " ss_prob: {}".format(ss_prob) if opt.scheduled_sampling_start >= 0 else "", sc_text, norm_text))
         lr_scheduler.step(valid_loss)                                                          # train.py:155
         n_before = early_stopping.val_loss_min
         if rank == 0:
