@@ -282,6 +282,48 @@ class S2VT(nn.Module):
         return _beam.beam_cumulative(self, self.feat_drop(feats), self._hip_params(), beam_width=beam_width, max_depth=max_beam_depth,
                                      length_alpha=length_alpha, n_best=n_best, constraints=spec)
 
+    @torch.no_grad()
+    def beam_diverse(self, feats, beam_width=6, num_groups=3, diversity_lambda=0.5, max_beam_depth=30, length_alpha=0.7, n_best=1,
+                     no_repeat_ngram_size=0, repetition_penalty=1.0, min_length=0, banned_ids=None):
+        """Diverse (group) beam search (Vijayakumar et al., 2016; not in the reference): captions that differ on purpose.  Returns
+        (ids int64 [B, num_groups, n_best, max_beam_depth] padded with eos_ix, lengths int64 [B, num_groups, n_best], scores fp32
+        [B, num_groups, n_best]) on the device, every group best first; no host synchronisation.  The beam_width slots are split
+        into num_groups groups of Wg = beam_width / num_groups.  At every depth the groups select one after the other, each the Wg
+        best candidates of its OWN live hypotheses by (sum of log-probs) - diversity_lambda * (how many candidates chosen by the
+        earlier groups at this depth carry the same word: Hamming diversity on the current word; <eos> counts like any word), ties
+        by (slot, token) as in mode='beam'.  The penalty steers the selection only: a hypothesis carries, and is pooled with, its
+        unpenalised sum, so scores are mode='beam''s (sum / length**length_alpha) and comparable with mode='score'.  Every group
+        has a pool of its own; group 0 is never penalised and is exactly mode='beam' at width Wg, and diversity_lambda = 0 makes
+        every group that search.  num_groups = 1 IS mode='beam' (or `beam_constrained`) with an axis of 1 inserted: the same
+        launches, the same bits.  The constraint arguments are `beam_constrained`'s: every live hypothesis's logits row is edited
+        with its own words in front of its log_softmax.  The policy runs on the device (csrc/beam_div.hip; include/s2vt_hip.h
+        "diverse beam"), one launch per depth beside mode='beam''s depth step.  One-layer LSTM models only (a GRU
+        or stacked model: ValueError with mode='beam''s message).  A method of its own: forward's parameter list is fixed.  Not
+        covered: mode='beam_search', GRU and stacked models, Att_Baseline, dp.py, the groups as samples of --self-critical,
+        dissimilarity measures other than Hamming on the current word, widths above 8.  No gradient.
+        :param beam_width: 1..8, a multiple of num_groups
+        :param num_groups: 1..beam_width
+        :param diversity_lambda: finite and >= 0
+        :param n_best: hypotheses returned per group, 1..beam_width / num_groups
+        :param max_beam_depth, length_alpha: as for mode='beam'; with constraints the shape rules of `beam_constrained`
+        :param no_repeat_ngram_size, repetition_penalty, min_length, banned_ids: as for decode_constrained
+        """
+        _beam.check_beam_args(beam_width, max_beam_depth, length_alpha, 1, self.vocab_size)
+        _beam.check_diverse_args(beam_width, num_groups, diversity_lambda, n_best)
+        spec = _sampling.check_constraints(no_repeat_ngram_size, repetition_penalty, min_length, banned_ids, self.vocab_size, self.eos_ix)
+        if _sampling.constrains(spec):
+            _beam.check_beam_constraints(spec, max_beam_depth, self.vocab_size)
+        if _G.is_gru_model(self):
+            raise ValueError(_BEAM_GRU)
+        if _S.is_stacked_lstm_model(self):
+            raise ValueError(_BEAM_STACKED)
+        _F.require_hip(feats, "feats")
+        if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
+            raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        return _beam.beam_diverse(self, self.feat_drop(feats), self._hip_params(), beam_width=beam_width, num_groups=num_groups,
+                                  diversity_lambda=diversity_lambda, max_depth=max_beam_depth, length_alpha=length_alpha, n_best=n_best,
+                                  constraints=spec)
+
     def _sample(self, feats, n_samples, temperature, seed, k, p):
         K = _sampling.check_n_samples(n_samples)
         t, s = _sampling.check_sample_args(temperature, seed)

@@ -12,6 +12,9 @@ under the model instead (mode='score', not in the reference): per-word perplexit
 --sample-seed) to <out>.samples.json.  --no-repeat-ngram / --repetition-penalty / --min-length / --ban-words constrain the greedy captions
 and those of --sample (S2VT.decode_constrained, not in the reference) and the search of --beam N --beam-mode cumulative
 (S2VT.beam_constrained); they are refused together with the reference's search (--beam N --beam-mode reference).
+--beam-groups G [--diversity-lambda x] (with --beam N --beam-mode cumulative, N a multiple of G) decodes by diverse beam search
+(S2VT.beam_diverse, not in the reference): the prediction of a clip is the best of its G group-best captions (the lowest group wins a
+tie), and all G with their scores (null for one that is not finite) go to <out>.groups.json.  The constraint flags compose with it.
 """
 import argparse
 import json
@@ -30,11 +33,15 @@ def ids_to_caption(ids, ix2word, drop_sos=False):
 
 
 def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', beam_width=5, max_beam_depth=30,
-             split='test', device=None, length_alpha=0.7, n_best=1, nbest=None, constraints=None):
+             split='test', device=None, length_alpha=0.7, n_best=1, nbest=None, constraints=None, beam_groups=0, diversity_lambda=0.5,
+             groups=None):
     """{video_id: caption} of a split.  mode: 'test' (greedy), 'beam_search' (the reference's search) or 'beam' (cumulative scores,
     length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]}).  constraints (modes 'test'
     and 'beam'): keyword arguments of S2VT.decode_constrained / S2VT.beam_constrained, with `ban_words` looked up in the split's
-    word2ix."""
+    word2ix.  beam_groups > 0 (mode 'beam'): diverse beam search, S2VT.beam_diverse with that many groups and diversity_lambda -
+    the caption of a clip is the group-best caption with the highest score (the lowest group wins a tie), and a dict `groups` is filled
+    with {video_id: [{"caption", "score"} of every group, in group order]} (a score that is not finite: None)."""
+    import math
     import dataloader
     dev = device or torch.device('cuda', 0)
     dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
@@ -51,6 +58,17 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                 out = model(feats, mode='beam_search', beam_width=beam_width, max_beam_depth=max_beam_depth)
                 for vid, seq in zip(ids, out):
                     preds[vid] = ids_to_caption([int(t.item()) for t in seq], dataset.ix2word, drop_sos=True)
+            elif mode == 'beam' and beam_groups > 0:
+                out, lens, scores = model.beam_diverse(feats, beam_width=beam_width, num_groups=beam_groups,
+                                                       diversity_lambda=diversity_lambda, max_beam_depth=max_beam_depth,
+                                                       length_alpha=length_alpha, n_best=1, **con)
+                out, lens, scores = out[:, :, 0].cpu().tolist(), lens[:, :, 0].cpu().tolist(), scores[:, :, 0].cpu().tolist()
+                for vid, rows, ln, sc in zip(ids, out, lens, scores):
+                    caps = [ids_to_caption(r[:n], dataset.ix2word) for r, n in zip(rows, ln)]
+                    preds[vid] = caps[max(range(len(sc)), key=lambda g: (sc[g], -g))]
+                    if groups is not None:
+                        # (a score can be -inf - a hypothesis through a word of log-prob -inf: null in the file, JSON has no infinity)
+                        groups[vid] = [{"caption": c, "score": x if math.isfinite(x) else None} for c, x in zip(caps, sc)]
             elif mode == 'beam':
                 if con:
                     out, lens, _ = model.beam_constrained(feats, beam_width=beam_width, max_beam_depth=max_beam_depth,
@@ -191,6 +209,11 @@ def build_parser():
     ap.add_argument("--length-alpha", type=float, default=0.7, help="cumulative: a finished caption scores sum / length**alpha")
     ap.add_argument("--n-best", type=int, default=1,
                     help="cumulative: captions kept per clip; more than one also writes {video_id: [captions]} to <out>.nbest.json")
+    ap.add_argument("--beam-groups", type=int, default=0, metavar="G",
+                    help="cumulative: diverse beam search (S2VT.beam_diverse) with G groups of --beam / G slots; the prediction is the "
+                         "best group-best caption, all G with their scores go to <out>.groups.json (0: off)")
+    ap.add_argument("--diversity-lambda", type=float, default=None, metavar="X",
+                    help="--beam-groups: what a candidate loses per earlier group that chose its word at this depth (default 0.5)")
     ap.add_argument("--perplexity", action="store_true",
                     help="instead of decoding: score every reference caption of the split (mode='score'), print total "
                          "log-likelihood, tokens, per-word perplexity and mean per-caption log-likelihood, write "
@@ -228,6 +251,12 @@ def main(argv=None):
     if constraints and a.beam and a.beam_mode != "cumulative":
         ap.error("--no-repeat-ngram / --repetition-penalty / --min-length / --ban-words apply to greedy decoding, --sample and "
                  "--beam N --beam-mode cumulative, not to the reference's search (--beam-mode reference)")
+    if (a.beam_groups or a.diversity_lambda is not None) and not (a.beam and a.beam_mode == "cumulative"):
+        ap.error("--beam-groups / --diversity-lambda apply to --beam N --beam-mode cumulative only")
+    if a.diversity_lambda is not None and not a.beam_groups:
+        ap.error("--diversity-lambda needs --beam-groups G")
+    if a.beam_groups < 0 or (a.beam_groups and a.n_best > 1):
+        ap.error("--beam-groups must be >= 1, and it keeps one caption per group (--n-best 1)")
     if a.perplexity:
         per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
         print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "
@@ -237,15 +266,21 @@ def main(argv=None):
         return summary
     cumulative = bool(a.beam) and a.beam_mode == "cumulative"
     nbest = {} if cumulative and a.n_best > 1 else None
+    groups = {} if a.beam_groups else None
+    diverse = dict(beam_groups=a.beam_groups, diversity_lambda=0.5 if a.diversity_lambda is None else a.diversity_lambda,
+                   groups=groups) if a.beam_groups else {}
     preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
                      ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
-                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints)
+                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints, **diverse)
     with open(a.out, 'w', encoding='utf-8') as f:
         json.dump(preds, f, ensure_ascii=False, indent=1)
     print("wrote {} captions to {}".format(len(preds), a.out))
     if nbest is not None:
         with open(a.out + ".nbest.json", 'w', encoding='utf-8') as f:
             json.dump(nbest, f, ensure_ascii=False, indent=1)
+    if groups is not None:
+        with open(a.out + ".groups.json", 'w', encoding='utf-8') as f:
+            json.dump(groups, f, ensure_ascii=False, indent=1)
     if a.sample > 0:
         samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
                                   a.sample_seed, constraints=constraints)

@@ -971,6 +971,51 @@ int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t
                                int32_t* top_ix, float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                                const s2vt_constraints* c, const int32_t* hist, int64_t hist_ld, int32_t t, void* stream);
 
+/* ---------------------------------------------------------------- diverse beam: diverse (group) beam search on the device
+ * (S2VT.beam_diverse(..., beam_width=, num_groups=, diversity_lambda=); Vijayakumar et al., 2016; not in the reference;
+ * csrc/beam_div.hip; restated in fp64 and fp32 by tests/beam_div_ref.py).  Per sample: W = beam_width slots, G = num_groups,
+ * Wg = W / G, lambda = diversity_lambda >= 0, D = max_depth; W % G == 0 and 1 <= G <= W <= 8.  Group g owns slots g*Wg .. (g+1)*Wg-1,
+ * a live list and a pool of at most Wg entries.  Every live list starts as one empty hypothesis: S = 0, last word <sos>, the encoder
+ * state of mode='beam'.  For t = 1..D:
+ *   cnt[v] = 0 for every word; the groups run in order g = 0..G-1; a group whose live list is empty is closed, is skipped and
+ *   contributes nothing to cnt.
+ *   Candidate (j, v) of live slot j (in slot order) has the score s = S_j + lp_j[v] and the selection key a = s - lambda * cnt[v].
+ *   The min(Wg, count) best candidates by (a descending, j ascending, v ascending) are walked in that order.  Every selected
+ *   candidate does cnt[v] += 1, <eos> included.  v == <eos> enters the group's pool with s / t**alpha - the unpenalised sum: the
+ *   penalty steers the selection only and is never accumulated; anything else becomes the group's next live slot with S = s.
+ *   At t == D every live hypothesis enters its group's pool with S / D**alpha, with no <eos> appended.
+ * A pool is ordered by (score descending, insertion ascending); the answer is each group's first n_best entries (n_best <= Wg).
+ * lp is log_softmax of the slot's logits row; with constraints, of the row edited with the slot's own words as history, exactly as in
+ * the constrained beam above.
+ *   fp32 form  s = S_j + fminf(lp, 0), -0 folded to +0; a = s when cnt == 0, otherwise a = s - (fp32(lambda) * fp32(cnt)), the product
+ *              and the difference each rounded to fp32 (never one FMA); pool scores divide by fp32(double pow), as above.
+ *   groups     group 0 is never penalised: it is the cumulative-score search at width Wg.  lambda = 0: every group is.  G = 1 is that
+ *              search itself; the callers then run s2vt_beam_cum_step, not this policy.
+ *   fan-out    20 per row stays exact for W <= 8: in group g at most g * Wg <= W - Wg distinct words are penalised; a candidate outside
+ *              its parent's unpenalised top W has W candidates of the same parent in front of it, at least Wg of them unpenalised,
+ *              whose keys are >= its key and which win every tie.  With constraints the argument runs on the edited row, under the
+ *              rule V >= 20 + max_depth + n_banned + 1.
+ *   early stop a group is settled when it is closed, or when its pool holds Wg entries and pool[Wg-1].score >= max_j(live S_j) /
+ *              D**alpha (the maximum: live slots are ordered by a, not by S); its pool can then never change (lp <= 0, the proof of
+ *              the cumulative search per group), and "settled" is monotone.  A sample is frozen only when ALL its groups are settled:
+ *              until then settled groups keep stepping and keep counting in cnt, because later groups depend on their choices.  A
+ *              frozen sample's slots carry token 0 / state row 0; the int32 at byte 0 of `state` counts the frozen samples.
+ * Row protocol and `depth` as for s2vt_beam_cum_step: row b * W + slot; depth = 1 gives the first slot of every group row_state = b,
+ * row_tok = <sos> (unused slots: state 0 / token 0); depth = 2..max consume the step before; depth = 0 consumes step max_depth.
+ * s2vt_beam_div_bytes: the state's size, 0 for dimensions that are refused; hist != 0: the form that also keeps every live slot's
+ * words, hist[2][B][W][max_depth] int32 behind the plain state, as s2vt_beam_cum_hist_step keeps them.
+ * s2vt_beam_div_step: hist_out and hist_ld_out both null: the plain form.  Both non-null: the form with the words; after the call
+ * *hist_out / *hist_ld_out are what s2vt_beam_step_constrained must read at the next depth step (see s2vt_beam_cum_hist_step).
+ * s2vt_beam_div_result: every group's first n_best pool entries (1 <= n_best <= Wg) -> out_tokens [B][G][n_best][max_depth] int32
+ * (words after <sos>, padded with eos_ix), out_len [B][G][n_best], out_score [B][G][n_best], each group best first; serves both forms. */
+size_t s2vt_beam_div_bytes(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t hist);
+int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t sos_ix, int32_t eos_ix,
+                       double length_alpha, double diversity_lambda, int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix,
+                       const float* top_lp, int32_t* row_b, int32_t* row_state, int32_t* row_tok, const int32_t** hist_out,
+                       int64_t* hist_ld_out, void* stream);
+int s2vt_beam_div_result(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state,
+                         size_t state_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

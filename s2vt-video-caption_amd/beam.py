@@ -379,6 +379,88 @@ def beam_cumulative(model, feats, params, beam_width=3, max_depth=30, length_alp
         return ids.long(), lens.long(), scores
 
 
+def check_diverse_args(beam_width, num_groups, diversity_lambda, n_best):
+    """(num_groups, diversity_lambda, n_best) of beam_diverse as ints / a float, or ValueError - before anything reaches the
+    library; beam_width is an int that check_beam_args has passed"""
+    import math
+    W, G, nb = int(beam_width), int(num_groups), int(n_best)
+    if G != num_groups or not 1 <= G <= W or W % G:
+        raise ValueError("beam_diverse: num_groups must be an integer in [1, beam_width = %d] that divides beam_width, got %r"
+                         % (W, num_groups))
+    if nb != n_best or not 1 <= nb <= W // G:
+        raise ValueError("beam_diverse: n_best must be an integer in [1, beam_width / num_groups = %d], got %r" % (W // G, n_best))
+    try:
+        lam = float(diversity_lambda)
+        with np.errstate(over="ignore"):
+            lam32 = float(np.float32(lam))
+    except (TypeError, ValueError, OverflowError):
+        lam = lam32 = float("nan")
+    if not math.isfinite(lam) or not math.isfinite(lam32) or lam < 0:
+        raise ValueError("beam_diverse: diversity_lambda must be finite (in fp32) and >= 0, got %r" % (diversity_lambda,))
+    return G, lam, nb
+
+
+@torch.no_grad()
+def beam_diverse(model, feats, params, beam_width=6, num_groups=3, diversity_lambda=0.5, max_depth=30, length_alpha=0.7, n_best=1,
+                 constraints=None):
+    """S2VT.beam_diverse (not in the reference; include/s2vt_hip.h "diverse beam"): diverse (group) beam search
+    (Vijayakumar et al., 2016).  The beam_width slots are num_groups groups of Wg = beam_width / num_groups; per depth the groups
+    select in order, each the Wg best of its own slots' candidates by a = (sum of log-probs) - diversity_lambda * (how often the
+    earlier groups chose the candidate's word at this depth), ties by (slot, token); hypotheses carry and are pooled with the
+    unpenalised sum, per group, by mode='beam''s rules.  Same encoder, decode cache, depth step and polled early exit as mode='beam';
+    the policy is csrc/beam_div.hip, one launch per depth, nothing crosses PCIe.  Returns (ids int64 [B, num_groups, n_best,
+    max_depth] padded with <eos>, lengths int64 [B, num_groups, n_best], scores fp32 [B, num_groups, n_best]) on the device, every
+    group best first; no host synchronisation.
+    constraints (a sampling.ConstraintSpec): as in beam_cumulative - every live slot's row is edited with the slot's own words in
+    front of its log_softmax and top 20; the policy keeps those words (the form of s2vt_beam_div_step with hist_out).
+    num_groups == 1 IS beam_cumulative with an axis of 1 inserted: the same launches, the same bits."""
+    import ctypes
+    from . import sampling
+    from .functional import _ptr
+    W, D, alpha, _ = check_beam_args(beam_width, max_depth, length_alpha, 1, model.vocab_size)
+    G, lam, n_best = check_diverse_args(W, num_groups, diversity_lambda, n_best)
+    if constraints is not None and not sampling.constrains(constraints):
+        constraints = None
+    if constraints is not None:
+        check_beam_constraints(constraints, D, model.vocab_size)
+    if G == 1:
+        ids, lens, scores = beam_cumulative(model, feats, params, beam_width=W, max_depth=D, length_alpha=alpha, n_best=n_best,
+                                            constraints=constraints)
+        return ids.unsqueeze(1), lens.unsqueeze(1), scores.unsqueeze(1)
+    dev = feats.device
+    B, H = feats.shape[0], model.dim_hid
+    sos, eos = int(model.sos_ix), int(model.eos_ix)
+    lib = capi.load()
+    qbytes = lib.s2vt_beam_div_bytes(B, W, G, D, int(constraints is not None))
+    if qbytes == 0:
+        raise ValueError("beam_diverse: batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (B, W, D))
+    states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
+
+    con = keep = None
+    if constraints is None:
+        def dstep(depth, qs, top_ix, top_lp, rows, st):
+            capi.check(lib.s2vt_beam_div_step(B, W, G, D, sos, eos, alpha, lam, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
+                                              _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), None, None, st), "s2vt_beam_div_step")
+    else:
+        con, keep = sampling.constraints_struct(constraints)     # (keep: the banned ids' host array lives as long as con is used)
+        words, words_ld = ctypes.c_void_p(), ctypes.c_int64()
+
+        def dstep(depth, qs, top_ix, top_lp, rows, st):           # the same policy; it also keeps the live slots' words
+            capi.check(lib.s2vt_beam_div_step(B, W, G, D, sos, eos, alpha, lam, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
+                                              _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ctypes.byref(words), ctypes.byref(words_ld),
+                                              st), "s2vt_beam_div_step")
+            return ctypes.c_void_p(words.value), words_ld.value
+    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, dstep,
+                                "constrained diverse beam" if con is not None else "diverse beam", con=con)
+    with torch.cuda.device(dev):
+        ids = torch.empty(B, G, n_best, D, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, G, n_best, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, G, n_best, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_beam_div_result(B, W, G, D, eos, n_best, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(scores), st),
+                   "s2vt_beam_div_result")
+        return ids.long(), lens.long(), scores
+
+
 class HeapQueues(object):
     """The reference's queue bookkeeping, literally: one Python heap of (key, node) tuples per sample
     (S2VTModel.py:186-236).  Kept as the definition the vectorised BeamQueues is tested against and as the

@@ -141,6 +141,11 @@ SIGNATURES = {
     "s2vt_beam_step_constrained": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 15 + [c_size_t, c_void_p, c_size_t,
                                                                                                           POINTER(Constraints), c_void_p,
                                                                                                           c_int64, c_int32, c_void_p]),
+    # diverse (group) beam search (S2VT.beam_diverse; csrc/beam_div.hip): the policy, plain or keeping every slot's words (hist_out given)
+    "s2vt_beam_div_bytes": (c_size_t, [c_int32] * 5),
+    "s2vt_beam_div_step": (c_int32, [c_int32] * 6 + [c_double, c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 5 +
+                           [POINTER(c_void_p), POINTER(c_int64), c_void_p]),
+    "s2vt_beam_div_result": (c_int32, [c_int32] * 6 + [c_void_p, c_size_t] + [c_void_p] * 4),
     "s2vt_score_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "s2vt_score_captions": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32,

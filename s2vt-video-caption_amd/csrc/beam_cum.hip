@@ -36,14 +36,11 @@
 #include <map>
 #include <mutex>
 
+#include "beam_wave.h"
 #include "common.h"
 #include "kernels.h"
 
 namespace s2vt {
-
-constexpr int BC_FAN = 20;          // tokens per row that s2vt_beam_step returns (top20_logprob, ce.hip)
-constexpr int BC_MAXBW = 8;
-constexpr int BC_CPL = (BC_MAXBW * BC_FAN + 63) / 64;       // candidates per lane
 
 struct BeamC {
     int B, bw, D, NN, sos, eos, depth;         // depth: 1 = initialise; 2..D = consume step depth-1; 0 = consume step D
@@ -57,23 +54,7 @@ struct BeamC {
     int* hist;                                               // [2][B][bw][D] words of the live slots (the constrained form only)
 };
 
-// fp32 -> uint32 whose unsigned order is the float order (no NaN reaches it: fminf(lp, 0) maps a NaN log-prob to 0)
-__device__ __forceinline__ unsigned int bc_ordered(float x) {
-    const unsigned int u = __float_as_uint(x);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float bc_unordered(unsigned int o) {
-    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-__device__ __forceinline__ unsigned long long bc_wave_max(unsigned long long v) {
-    for (int o = 32; o; o >>= 1) {
-        const unsigned int hi = (unsigned int)__shfl_xor((int)(v >> 32), o), lo = (unsigned int)__shfl_xor((int)(unsigned int)v, o);
-        const unsigned long long ov = ((unsigned long long)hi << 32) | lo;
-        v = ov > v ? ov : v;
-    }
-    return v;
-}
-
+// (bc_ordered / bc_unordered / bc_wave_max, the keyed wave-wide max: beam_wave.h)
 // One WAVE per sample.  Keys are distinct (the low word is the candidate index), so every round has exactly one winner.
 // HIST: the constrained form - the same policy, and the live slots' words kept in q.hist (the comment at the top).
 template <bool HIST>
