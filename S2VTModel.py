@@ -440,3 +440,6 @@ class S2VT(nn.Module):
 
 
 BeamSearchNode = _beam.BeamSearchNode
+# Ensemble([m0, m1, ...], weights=None).beam(feats, ...): mode='beam' / beam_constrained over the weighted mean of several models'
+# word distributions, on the device (not in the reference; s2vt_video_caption_amd/ensemble.py)
+from s2vt_video_caption_amd.ensemble import Ensemble  # noqa: E402

@@ -15,6 +15,9 @@ and those of --sample (S2VT.decode_constrained, not in the reference) and the se
 --beam-groups G [--diversity-lambda x] (with --beam N --beam-mode cumulative, N a multiple of G) decodes by diverse beam search
 (S2VT.beam_diverse, not in the reference): the prediction of a clip is the best of its G group-best captions (the lowest group wins a
 tie), and all G with their scores (null for one that is not finite) go to <out>.groups.json.  The constraint flags compose with it.
+--ensemble PATH[,PATH...] [--ensemble-weights w0,w1,...] (with --beam N --beam-mode cumulative) decodes with --model-path and the
+further checkpoints as ONE search over the weighted mean of their word distributions (S2VTModel.Ensemble, not in the reference); the
+first weight is --model-path's.  The constraint flags and --n-best compose with it.
 """
 import argparse
 import json
@@ -34,13 +37,15 @@ def ids_to_caption(ids, ix2word, drop_sos=False):
 
 def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', beam_width=5, max_beam_depth=30,
              split='test', device=None, length_alpha=0.7, n_best=1, nbest=None, constraints=None, beam_groups=0, diversity_lambda=0.5,
-             groups=None):
+             groups=None, ensemble_paths=None, ensemble_weights=None):
     """{video_id: caption} of a split.  mode: 'test' (greedy), 'beam_search' (the reference's search) or 'beam' (cumulative scores,
     length_alpha; with a dict `nbest`, that is filled with {video_id: [the n_best captions, best first]}).  constraints (modes 'test'
     and 'beam'): keyword arguments of S2VT.decode_constrained / S2VT.beam_constrained, with `ban_words` looked up in the split's
     word2ix.  beam_groups > 0 (mode 'beam'): diverse beam search, S2VT.beam_diverse with that many groups and diversity_lambda -
     the caption of a clip is the group-best caption with the highest score (the lowest group wins a tie), and a dict `groups` is filled
-    with {video_id: [{"caption", "score"} of every group, in group order]} (a score that is not finite: None)."""
+    with {video_id: [{"caption", "score"} of every group, in group order]} (a score that is not finite: None).
+    ensemble_paths (mode 'beam' without groups): further checkpoints decoded together with model_path by S2VTModel.Ensemble,
+    ensemble_weights: one weight per model, model_path's first (None: uniform)."""
     import math
     import dataloader
     dev = device or torch.device('cuda', 0)
@@ -51,6 +56,15 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
     if mode in ('beam_search', 'beam'):                                 # old pickles lack these attrs (eval.py:84-86)
         model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
     con = constraint_kwargs(constraints, dataset.word2ix, model)
+    ensemble = None
+    if ensemble_paths:
+        if mode != 'beam' or beam_groups > 0:
+            raise ValueError("ensemble_paths apply to mode='beam' without beam_groups")
+        import S2VTModel
+        members = [model] + [torch.load(p, weights_only=False).to(dev).eval() for p in ensemble_paths]
+        for m in members[1:]:
+            m.rnn_type, m.sos_ix, m.eos_ix = model.rnn_type, model.sos_ix, model.eos_ix
+        ensemble = S2VTModel.Ensemble(members, ensemble_weights)
     preds = {}
     with torch.no_grad():
         for feats, targets, ids, masks in dataloader.feed_batches(loader, dev):
@@ -70,7 +84,10 @@ def generate(model_path, caption_file, feats_path, batch_size=10, mode='test', b
                         # (a score can be -inf - a hypothesis through a word of log-prob -inf: null in the file, JSON has no infinity)
                         groups[vid] = [{"caption": c, "score": x if math.isfinite(x) else None} for c, x in zip(caps, sc)]
             elif mode == 'beam':
-                if con:
+                if ensemble is not None:
+                    out, lens, _ = ensemble.beam(feats, beam_width=beam_width, max_beam_depth=max_beam_depth, length_alpha=length_alpha,
+                                                 n_best=n_best, **con)
+                elif con:
                     out, lens, _ = model.beam_constrained(feats, beam_width=beam_width, max_beam_depth=max_beam_depth,
                                                           length_alpha=length_alpha, n_best=n_best, **con)
                 else:
@@ -214,6 +231,11 @@ def build_parser():
                          "best group-best caption, all G with their scores go to <out>.groups.json (0: off)")
     ap.add_argument("--diversity-lambda", type=float, default=None, metavar="X",
                     help="--beam-groups: what a candidate loses per earlier group that chose its word at this depth (default 0.5)")
+    ap.add_argument("--ensemble", default="", metavar="PATH[,PATH...]",
+                    help="cumulative: further checkpoints decoded together with --model-path as one search over the weighted mean of "
+                         "the models' word distributions (S2VTModel.Ensemble)")
+    ap.add_argument("--ensemble-weights", default="", metavar="W0,W1,...",
+                    help="--ensemble: one positive weight per model, --model-path's first (default: uniform)")
     ap.add_argument("--perplexity", action="store_true",
                     help="instead of decoding: score every reference caption of the split (mode='score'), print total "
                          "log-likelihood, tokens, per-word perplexity and mean per-caption log-likelihood, write "
@@ -257,6 +279,20 @@ def main(argv=None):
         ap.error("--diversity-lambda needs --beam-groups G")
     if a.beam_groups < 0 or (a.beam_groups and a.n_best > 1):
         ap.error("--beam-groups must be >= 1, and it keeps one caption per group (--n-best 1)")
+    ens_paths = [p for p in a.ensemble.split(",") if p]
+    ens_weights = None
+    if a.ensemble_weights and not ens_paths:
+        ap.error("--ensemble-weights needs --ensemble PATH[,PATH...]")
+    if ens_paths:
+        if not (a.beam and a.beam_mode == "cumulative") or a.beam_groups or a.sample or a.perplexity:
+            ap.error("--ensemble applies to --beam N --beam-mode cumulative only, without --beam-groups, --sample or --perplexity")
+        if a.ensemble_weights:
+            try:
+                ens_weights = [float(w) for w in a.ensemble_weights.split(",")]
+            except ValueError:
+                ap.error("--ensemble-weights: numbers separated by commas, got %r" % a.ensemble_weights)
+            if len(ens_weights) != len(ens_paths) + 1:
+                ap.error("--ensemble-weights: %d weights for %d models (--model-path's comes first)" % (len(ens_weights), len(ens_paths) + 1))
     if a.perplexity:
         per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
         print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "
@@ -271,7 +307,8 @@ def main(argv=None):
                    groups=groups) if a.beam_groups else {}
     preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
                      ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
-                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints, **diverse)
+                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints,
+                     **diverse, **(dict(ensemble_paths=ens_paths, ensemble_weights=ens_weights) if ens_paths else {}))
     with open(a.out, 'w', encoding='utf-8') as f:
         json.dump(preds, f, ensure_ascii=False, indent=1)
     print("wrote {} captions to {}".format(len(preds), a.out))

@@ -1016,6 +1016,44 @@ int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_
 int s2vt_beam_div_result(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state,
                          size_t state_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream);
 
+/* ---------------------------------------------------------------- ensemble beam: several models, one cumulative-score search
+ * (S2VT.Ensemble(models, weights=None).beam(...); csrc/ensemble.hip; restated in numpy fp32 and fp64 by tests/ensemble_ref.py).
+ * The search is EXACTLY the cumulative-score beam search above (s2vt_beam_cum_step; constrained: s2vt_beam_cum_hist_step) with one
+ * change: lp_j, the log-probs of live slot j, is the log of the weighted arithmetic mean of the members' word distributions.  Each
+ * member keeps its own encoder states, decode cache and depth step; the policy, the early-exit poll and the result are shared.
+ * Members m = 0..M-1, 1 <= M <= 8; weights w_m > 0 and finite, normalised by the host to sum 1 in fp64; lw_m = fp32(log(w_m)), the
+ * log taken in fp64; default: uniform.  For one row (a beam slot) with the members' raw logits rows x_m[0..V):
+ *   lse_m    the log-sum-exp of x_m by exactly s2vt_top20_logprob's arithmetic: the block maximum; expf(x - max) summed per thread
+ *            (thread tid owns the elements tid + 256 j) in ascending index; wave butterflies; (w0 + w1) + (w2 + w3); max + logf(sum)
+ *   a_m[v]   = (x_m[v] - lse_m) + lw_m
+ *   amax[v]  = max_m a_m[v]
+ *   c[v]     = amax[v] + logf(sum over m ascending of expf(a_m[v] - amax[v])); -inf (never NaN) where every a_m[v] is -inf, a
+ *            word the constraints removed in every member
+ *   result   the 20 largest c[v], ties -> the lower id, in ASCENDING token order as s2vt_top20_logprob returns them; top_lp = c:
+ *            the mean of normalised distributions is normalised, so there is no second normalisation
+ *   M = 1    with w = 1: c = a_0 exactly (logf(expf(0)) = 0) and the head is s2vt_top20_logprob bit for bit; that kernel runs.
+ *   constrained  every member's row of the slot is first edited IN PLACE by rules 1-4 of the constrained draw with the slot's own
+ *            words as history (the same spec for every member), in the same launch; lse_m is then that of the edited row.
+ * One 256-thread workgroup per row, fixed-order reductions, no atomics: the same inputs give the same bits.
+ * s2vt_ensemble_top20: member m's row r starts at logits + m * member_stride + r * ld.  log_w: M HOST floats, passed by value into
+ * the launch.  Requires 1 <= M <= 8, 20 <= V <= 38400, ld >= V, member_stride >= rows * ld, every log_w finite and <= 0;
+ * everything else is S2VT_ERR_ARG with a message naming the entry.
+ * s2vt_ensemble_top20_constrained: the same behind the checks of s2vt_top20_logprob_constrained (V >= 20 + t + n_banned + 1); THE
+ * CALL MODIFIES `logits`.  With every constraint off it runs s2vt_ensemble_top20's launch and leaves the buffers untouched.
+ * s2vt_beam_step_logits: the depth step of ONE member, stopped one launch early - the form is chosen as s2vt_beam_step_constrained
+ * chooses it (gx_vid, else cache, else neither), the launches are the same up to and including out_linear, which writes the R rows'
+ * logits to logits_out (row stride ld_out >= V); no fan-out, no top_ix / top_lp. */
+int s2vt_ensemble_top20(const float* logits, int64_t member_stride, int64_t ld, int32_t M, int64_t rows, int32_t V, const float* log_w,
+                        int32_t* top_ix, float* top_lp, void* stream);
+int s2vt_ensemble_top20_constrained(float* logits, int64_t member_stride, int64_t ld, int32_t M, int64_t rows, int32_t V, const float* log_w,
+                                    const int32_t* hist_i32, int64_t hist_ld, int32_t t, const s2vt_constraints* c, int32_t* top_ix,
+                                    float* top_lp, void* stream);
+int s2vt_beam_step_logits(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                          const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                          const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                          float* logits_out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                          void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

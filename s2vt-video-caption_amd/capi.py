@@ -141,6 +141,12 @@ SIGNATURES = {
     "s2vt_beam_step_constrained": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 15 + [c_size_t, c_void_p, c_size_t,
                                                                                                           POINTER(Constraints), c_void_p,
                                                                                                           c_int64, c_int32, c_void_p]),
+    # the ensemble beam (S2VT.Ensemble; csrc/ensemble.hip): the fan-out head over M members' logits, a member's depth step up to its logits
+    "s2vt_ensemble_top20": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "s2vt_ensemble_top20_constrained": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64,
+                                                  c_int32, POINTER(Constraints), c_void_p, c_void_p, c_void_p]),
+    "s2vt_beam_step_logits": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 13 + [c_int64, c_void_p, c_size_t,
+                                                                                                     c_void_p, c_size_t, c_void_p]),
     # diverse (group) beam search (S2VT.beam_diverse; csrc/beam_div.hip): the policy, plain or keeping every slot's words (hist_out given)
     "s2vt_beam_div_bytes": (c_size_t, [c_int32] * 5),
     "s2vt_beam_div_step": (c_int32, [c_int32] * 6 + [c_double, c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 5 +

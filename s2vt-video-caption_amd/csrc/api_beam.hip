@@ -67,15 +67,18 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
                           const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
                           const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out, int32_t* top_ix,
                           float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, void* stream,
-                          const float* gx_vid, const BeamCon* con = nullptr) {
+                          const float* gx_vid, const BeamCon* con = nullptr, float* logits_out = nullptr, int64_t ld_out = 0) {
     S2VT_REQUIRE(d && p && workspace && (gx_vid || (vid_h_in && vid_c_in && vid_h_out && vid_c_out)), "s2vt_beam_step: null argument");
     S2VT_REQUIRE(R >= 0 && (R == 0 || (row_b && row_state && tok && word_h_in && word_c_in && word_h_out && word_c_out &&
-                                        top_ix && top_lp)),
+                                        (logits_out || (top_ix && top_lp)))),
                  "s2vt_beam_step: null row argument");
     const int B = d->B, H = d->H, E = d->E, V = d->V;
     S2VT_REQUIRE(workspace_bytes >= carve_beam(*d, R > 0 ? R : 1, nullptr).bytes, "s2vt_beam_step: workspace too small");
     const BeamWS w = carve_beam(*d, R > 0 ? R : 1, workspace);
     hipStream_t st = (hipStream_t)stream;
+    // logits_out (s2vt_beam_step_logits): out_linear writes the caller's rows and the step ends there - no fan-out
+    float* const lg = logits_out ? logits_out : w.logits;
+    const int64_t ldl = logits_out ? ld_out : V;
     int rc;
     if (!gx_vid && (rc = bias_sums(st, p, H, w.bsum1, w.bsum2))) return rc;
     if (!gx_vid) {   // one zero-input vid_rnn step for the whole batch (S2VTModel.py:208-210)
@@ -116,8 +119,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         a.h_planes = w.pword.p; a.ldhp = w.pword.ld;
         if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
         if ((rc = rows_word_step(st, *d, p, &kc, a))) return rc;
-        if ((rc = pgemm(ln, R, V, H, w.pword, 0, 0, kc.wo, 0, 0, w.logits, V, ID, p->out_b, false))) return rc;
-        if ((rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;
+        if ((rc = pgemm(ln, R, V, H, w.pword, 0, 0, kc.wo, 0, 0, lg, ldl, ID, p->out_b, false))) return rc;
+        if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;
         return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
     }
     S2VT_REQUIRE(!gx_vid, "s2vt_beam_step_gx: the precomputed vid_rnn half needs the plane path (gemm mode 1 / 3, H <= 1024)");
@@ -126,8 +129,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         return rc;
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = rows_word_step(st, *d, p, nullptr, a))) return rc;
-    if ((rc = lgemm(ln, true, true, R, V, H, word_h_out, H, ID, p->out_w, H, ID, w.logits, V, ID, p->out_b, false))) return rc;   // (:213)
-    if ((rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;                                                   // (:214-219)
+    if ((rc = lgemm(ln, true, true, R, V, H, word_h_out, H, ID, p->out_w, H, ID, lg, ldl, ID, p->out_b, false))) return rc;       // (:213)
+    if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;                                   // (:214-219)
     return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
 }
 // the depth step with vid_rnn's part precomputed (s2vt_decode_encode_cached, gx_dec[depth - 1]): word step, out_linear, fan-out
@@ -157,6 +160,23 @@ int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t
     }
     return beam_step_impl(d, p, R, row_b, row_state, tok, vid_h_in, vid_c_in, vid_h_out, vid_c_out, word_h_in, word_c_in, word_h_out,
                           word_c_out, top_ix, top_lp, workspace, workspace_bytes, cache, cache ? cache_bytes : 0, stream, gx_vid, &con);
+}
+// the depth step of an ensemble member, all three forms chosen as s2vt_beam_step_constrained chooses them: the same launches up to
+// and including out_linear, which writes the rows' logits to logits_out (row stride ld_out >= V); no fan-out
+int s2vt_beam_step_logits(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                          const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                          const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                          float* logits_out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
+                          void* stream) {
+    S2VT_REQUIRE(d && logits_out && ld_out >= d->V, "s2vt_beam_step_logits: null logits_out, or ld_out < V");
+    S2VT_REQUIRE(!gx_vid || cache, "s2vt_beam_step_logits: gx_vid needs the cache");
+    if (gx_vid) {
+        vid_h_in = vid_c_in = nullptr;
+        vid_h_out = vid_c_out = nullptr;
+    }
+    return beam_step_impl(d, p, R, row_b, row_state, tok, vid_h_in, vid_c_in, vid_h_out, vid_c_out, word_h_in, word_c_in, word_h_out,
+                          word_c_out, nullptr, nullptr, workspace, workspace_bytes, cache, cache ? cache_bytes : 0, stream, gx_vid, nullptr,
+                          logits_out, ld_out);
 }
 int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
                    const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,

@@ -282,6 +282,27 @@ int s2vt_top20_logprob_constrained(float* logits, int64_t ld, int64_t rows, int3
     return top20_constrained_checked("s2vt_top20_logprob_constrained", (hipStream_t)stream, logits, ld, rows, V, hist, hist_ld, t, c, top_ix,
                                      top_lp);
 }
+// the ensemble beam's fan-out head (ensemble.hip); the constrained form behind top20_constrained_checked's checks, and with every
+// constraint off the unconstrained launch (the buffers stay untouched)
+int s2vt_ensemble_top20(const float* logits, int64_t member_stride, int64_t ld, int32_t M, int64_t rows, int32_t V, const float* log_w,
+                        int32_t* top_ix, float* top_lp, void* stream) {
+    return ensemble_top20("s2vt_ensemble_top20", (hipStream_t)stream, logits, member_stride, ld, M, rows, V, log_w, top_ix, top_lp);
+}
+int s2vt_ensemble_top20_constrained(float* logits, int64_t member_stride, int64_t ld, int32_t M, int64_t rows, int32_t V, const float* log_w,
+                                    const int32_t* hist, int64_t hist_ld, int32_t t, const s2vt_constraints* c, int32_t* top_ix,
+                                    float* top_lp, void* stream) {
+    const char* fn = "s2vt_ensemble_top20_constrained";
+    S2VT_REQUIRE(V >= 20 && (size_t)V * sizeof(float) <= 150 * 1024, "%s: vocab_size %d outside [20, 38400]", fn, (int)V);
+    ConstrainArgs ca;
+    int rc;
+    if ((rc = check_constraints(fn, c, V, 0, 1.f, 0, 1.f, &ca))) return rc;
+    S2VT_REQUIRE(t >= 0 && t <= 1023, "%s: t %d outside [0, 1023]", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist, "%s: null history at t = %d", fn, (int)t);
+    S2VT_REQUIRE(t == 0 || hist_ld >= t, "%s: hist_ld %lld < t %d", fn, (long long)hist_ld, (int)t);
+    if (constraints_off(c)) return ensemble_top20(fn, (hipStream_t)stream, logits, member_stride, ld, M, rows, V, log_w, top_ix, top_lp);
+    return ensemble_top20_constrained(fn, (hipStream_t)stream, logits, member_stride, ld, M, rows, V, log_w, constrain_at(ca, c, nullptr, 0, t),
+                                      hist, hist_ld, top_ix, top_lp);
+}
 int s2vt_truncated_draw(const float* logits, int64_t ld, int64_t rows, int32_t V, float temperature, int32_t top_k, float top_p,
                         uint64_t seed, int32_t step, int32_t row0, unsigned long long* packed, int32_t* kept, void* stream) {
     S2VT_REQUIRE(logits && packed && rows > 0 && rows < (1ll << 31) && V > 0 && ld >= V && step >= 0 && row0 >= 0,

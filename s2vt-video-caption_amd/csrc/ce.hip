@@ -238,44 +238,18 @@ int weighted_ce_bwd(hipStream_t s, const float* logits, int64_t rows, int V, con
 //   best(v, ix, V)     the largest of them still there and its token id (ascending i: the first, i.e. lowest id, of equal
 //                      values is kept); (-inf, 0x7fffffff) when none is left
 //   remove(ix)         take element ix (one of the thread's) out
-constexpr int TOPK_N = 20;
-// (RegRow<VPT> / LdsRow: row_frame.h, shared with the truncated draw of truncate.hip)
+// (RegRow<VPT> / LdsRow and the extraction loop with TOPK_N = 20: row_frame.h, shared with the truncated draw of truncate.hip and
+// the ensemble head of ensemble.hip)
 // Same arithmetic in the same order for every Row: max, then the sum of expf(x - max) per thread in ascending i, wave
 // butterflies, (w0 + w1) + (w2 + w3); ties -> the lower token id.
 template <class Row>
 __device__ __forceinline__ void top20_logprob_row(const float* logits, int64_t ld, int V, int32_t* top_ix, float* top_lp) {
     __shared__ float red_v[4];
     __shared__ int red_i[4];
-    __shared__ float sel_v[TOPK_N];
-    __shared__ int sel_i[TOPK_N];
-    const int tid = threadIdx.x;
     Row row;
     const float mx = block_max_256<false>(row.load_max(logits + (int64_t)blockIdx.x * ld, V), red_v);
     const float lse = mx + logf(block_sum_256(row.sum_exp(mx, V), red_v));
-    __syncthreads();                                 // (block_argmax_256 has no barrier in front)
-    // every thread keeps the best of its own elements; only the owner of an extracted element rescans
-    float bv;
-    int bi;
-    row.best(bv, bi, V);
-    for (int k = 0; k < TOPK_N; ++k) {
-        float v = bv;
-        int ix = bi;
-        block_argmax_256(v, ix, red_v, red_i);
-        if (tid == 0) { sel_v[k] = v; sel_i[k] = ix; }
-        if ((ix & 255) == tid && ix < V) {           // owner: remove it and find the next best of its elements
-            row.remove(ix);
-            row.best(bv, bi, V);
-        }
-        __syncthreads();                             // (red_v / red_i free again, sel_* visible)
-    }
-    if (tid < TOPK_N) {                              // rank by token id (ids are distinct)
-        const int my = sel_i[tid];
-        int rank = 0;
-#pragma unroll
-        for (int j = 0; j < TOPK_N; ++j) rank += (sel_i[j] < my);
-        top_ix[(int64_t)blockIdx.x * TOPK_N + rank] = my;
-        top_lp[(int64_t)blockIdx.x * TOPK_N + rank] = sel_v[tid] - lse;
-    }
+    top20_extract_row(row, V, lse, red_v, red_i, top_ix, top_lp);        // (row_frame.h, shared with the ensemble head)
 }
 template <class Row>
 __global__ __launch_bounds__(256) void top20_logprob_kernel(const float* logits, int64_t ld, int V, int32_t* top_ix, float* top_lp) {

@@ -427,6 +427,17 @@ int constrained_draw(hipStream_t s, float* logits, int64_t ld, int64_t rows, int
 // (beam_cum.hip's per-slot words).  Refused unless V >= 20 + c.t + c.n_banned + 1 (20 finite words are then left in every row).
 int top20_logprob_constrained(hipStream_t s, float* logits, int64_t ld, int64_t rows, int V, const ConstrainArgs& c, const int32_t* hist,
                               int64_t hist_ld, int32_t* top_ix, float* top_lp);
+// ---- ensemble.hip: the fan-out head of the ensemble beam search (include/s2vt_hip.h "ensemble beam"): member m's row r at logits +
+// m * member_stride + r * ld, log_w[M] on the host (fp32 log weights, finite and <= 0; passed by value into the launch) -> the 20
+// best words of the log weighted-mean distribution per row.  M == 1 with log_w[0] == 0 runs top20_logprob(_constrained) itself.
+// fn names the entry point in the messages of the argument checks (everything else: S2VT_ERR_ARG).  The constrained form edits
+// every member's rows IN PLACE first, by top20_logprob_constrained's rules and with its checks.
+constexpr int ENSEMBLE_MAX_M = 8;
+int ensemble_top20(const char* fn, hipStream_t s, const float* logits, int64_t member_stride, int64_t ld, int M, int64_t rows, int V,
+                   const float* log_w, int32_t* top_ix, float* top_lp);
+int ensemble_top20_constrained(const char* fn, hipStream_t s, float* logits, int64_t member_stride, int64_t ld, int M, int64_t rows,
+                               int V, const float* log_w, const ConstrainArgs& c, const int32_t* hist, int64_t hist_ld, int32_t* top_ix,
+                               float* top_lp);
 // fp32(len ** alpha) for len = 0..D (len 0: 1), libm double pow then fp32, in pinned host memory that lives for the life of the
 // process (beam_cum.hip: the power rule of mode='beam'); null when no pinned memory is left
 const float* length_pow_table(double alpha, int D);

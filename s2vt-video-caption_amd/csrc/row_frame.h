@@ -1,6 +1,7 @@
 // The frame of the row kernels (ce.hip: the three criteria, their gradients, the beam searches' top-20 fan-out; split.hip: the
-// fused criterion backward; truncate.hip: the truncated draw): 256-thread block reductions in ONE fixed order, the two places a
-// one-workgroup-per-row kernel keeps its row (RegRow<VPT> / LdsRow), the constraint phase that the constrained draw and the
+// fused criterion backward; truncate.hip: the truncated draw; ensemble.hip: the ensemble beam's fan-out): 256-thread block
+// reductions in ONE fixed order, the two places a one-workgroup-per-row kernel keeps its row (RegRow<VPT> / LdsRow), the extraction
+// loop of the fan-out heads (top20_extract_row), the constraint phase that the constrained draw and the
 // constrained fan-out run in front of their row's load (constrain_row), the [:, 1:] read of a [B, L] matrix by flat row, the
 // clamp of a bad target and the CE gradient of one element.  Device code only.
 #pragma once
@@ -149,6 +150,42 @@ struct LdsRow {
     template <class F>
     __device__ __forceinline__ void slots(int V, F f) { each(V, f); }       // (no pad slots)
 };
+
+// ---- the extraction loop of the fan-out heads (ce.hip: top20_logprob_row; ensemble.hip: the ensemble head): the largest element
+// still in the row is taken out TOPK_N times (ties -> the lower token id), then the winners are ranked by token id and stored in
+// ASCENDING token order as (id, value - sub): sub is the row's log-sum-exp where the row holds raw logits, 0 where it holds
+// log-probs already.  Every thread keeps the best of its own elements; only the owner of an extracted element rescans.  red_v /
+// red_i: the caller's four reduction words (free again once the barrier in front has passed).
+constexpr int TOPK_N = 20;
+template <class Row>
+__device__ __forceinline__ void top20_extract_row(Row& row, int V, float sub, float* red_v, int* red_i, int32_t* top_ix, float* top_lp) {
+    __shared__ float sel_v[TOPK_N];
+    __shared__ int sel_i[TOPK_N];
+    const int tid = threadIdx.x;
+    __syncthreads();                                 // (block_argmax_256 has no barrier in front)
+    float bv;
+    int bi;
+    row.best(bv, bi, V);
+    for (int k = 0; k < TOPK_N; ++k) {
+        float v = bv;
+        int ix = bi;
+        block_argmax_256(v, ix, red_v, red_i);
+        if (tid == 0) { sel_v[k] = v; sel_i[k] = ix; }
+        if ((ix & 255) == tid && ix < V) {           // owner: remove it and find the next best of its elements
+            row.remove(ix);
+            row.best(bv, bi, V);
+        }
+        __syncthreads();                             // (red_v / red_i free again, sel_* visible)
+    }
+    if (tid < TOPK_N) {                              // rank by token id (ids are distinct)
+        const int my = sel_i[tid];
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < TOPK_N; ++j) rank += (sel_i[j] < my);
+        top_ix[(int64_t)blockIdx.x * TOPK_N + rank] = my;
+        top_lp[(int64_t)blockIdx.x * TOPK_N + rank] = sel_v[tid] - sub;
+    }
+}
 
 // ---- the constraint phase of the constrained row kernels (include/s2vt_hip.h "constrained draw"; sampling.constrain_logits restates
 // it in numpy): repetition penalty, no-repeat n-gram blocking, banned ids and a minimum length, applied to the RAW logits row x

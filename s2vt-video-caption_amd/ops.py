@@ -363,6 +363,80 @@ def top20_logprob_constrained(logits, hist, t, spec):
     return ix, lp
 
 
+def ensemble_log_weights(weights, M):
+    """fp32 log weights of an ensemble's M members (include/s2vt_hip.h "ensemble beam") as a ctypes float array: the weights
+    normalised to sum 1 in fp64, the log in fp64, then fp32.  None: uniform.  ValueError ("Ensemble:") unless there are M of them,
+    each finite and > 0."""
+    import math
+    if weights is None:
+        weights = [1.0] * M
+    try:
+        w = [float(x) for x in weights]
+    except (TypeError, ValueError):
+        raise ValueError("Ensemble: weights must be %d numbers, got %r" % (M, weights))
+    if len(w) != M:
+        raise ValueError("Ensemble: %d weights for %d members" % (len(w), M))
+    if not all(math.isfinite(x) and x > 0 for x in w):
+        raise ValueError("Ensemble: weights must be finite and > 0, got %r" % (w,))
+    tot = math.fsum(w)
+    return (ctypes.c_float * M)(*[min(math.log(x / tot), 0.0) for x in w])      # (c_float rounds the fp64 log to fp32)
+
+
+def _ensemble_logits(logits):
+    require_hip(logits, "logits")
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1:
+        raise ValueError("logits must be fp32 [M, rows, V] with unit column stride")
+    return logits.shape
+
+
+def ensemble_top20(logits, weights=None):
+    """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20]): the fan-out head of S2VT.Ensemble on its own (s2vt_ensemble_top20;
+    include/s2vt_hip.h "ensemble beam") - per row the 20 best words, in ascending token order, of the log of the weighted mean of
+    the M members' softmax distributions, and those log-probs.  logits: fp32 [M, rows, V >= 20], 1 <= M <= 8; weights: M positive
+    numbers (normalised here), None: uniform.  M = 1 is top20_logprob."""
+    lib = capi.load()
+    M, rows, V = _ensemble_logits(logits)
+    if not 1 <= M <= 8:
+        raise ValueError("Ensemble: 1 to 8 members, got %d" % M)
+    lw = ensemble_log_weights(weights, M)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ix = torch.empty(rows, 20, dtype=torch.int32, device=dev)
+        lp = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_ensemble_top20(_ptr(logits), logits.stride(0), logits.stride(1), M, rows, V, lw, _ptr(ix), _ptr(lp),
+                                           _stream(dev)), "s2vt_ensemble_top20")
+    return ix, lp
+
+
+def ensemble_top20_constrained(logits, hist, t, spec, weights=None):
+    """ensemble_top20 of the rows CONSTRAINED by `spec` at step t (s2vt_ensemble_top20_constrained): every member's row r is first
+    edited with row r's words hist[r, :t] as top20_logprob_constrained edits it - THE CALL MODIFIES `logits` - and the members'
+    distributions are those of the edited rows.  hist: int32 [rows, >= t], None where t == 0.  V >= 20 + t + banned ids + 1.  A spec
+    that constrains nothing runs ensemble_top20's launch and leaves `logits` untouched."""
+    from .sampling import constraints_struct
+    lib = capi.load()
+    M, rows, V = _ensemble_logits(logits)
+    if not 1 <= M <= 8:
+        raise ValueError("Ensemble: 1 to 8 members, got %d" % M)
+    lw = ensemble_log_weights(weights, M)
+    t = int(t)
+    hist_ld = 0
+    if t > 0:
+        require_hip(hist, "hist")
+        if hist.dim() != 2 or hist.dtype != torch.int32 or hist.stride(1) != 1 or hist.shape[0] < rows or hist.shape[1] < t:
+            raise ValueError("hist must be int32 [>= rows = %d, >= t = %d] with unit column stride" % (rows, t))
+        hist_ld = hist.stride(0)
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ix = torch.empty(rows, 20, dtype=torch.int32, device=dev)
+        lp = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        cs, keep = constraints_struct(spec)
+        capi.check(lib.s2vt_ensemble_top20_constrained(_ptr(logits), logits.stride(0), logits.stride(1), M, rows, V, lw,
+                                                       _ptr(hist) if t > 0 else None, hist_ld, t, ctypes.byref(cs), _ptr(ix), _ptr(lp),
+                                                       _stream(dev)), "s2vt_ensemble_top20_constrained")
+    return ix, lp
+
+
 def decode_step_token_into(h, w_out, b_out, packed_i, sample=None, step=0, constraints=None):
     """out_linear + arg-max of one decode step into the caller's packed word row `packed_i` (int64 [B], zeroed) - what the greedy
     loops of the GRU and stacked models run per step; sample = (temperature, seed): the draw of mode='sample' for decode step
