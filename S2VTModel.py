@@ -257,7 +257,7 @@ class S2VT(nn.Module):
         penalty on every distinct word, -inf on a word that would complete an n-gram it already holds, -inf on the banned ids, -inf
         on <eos> during its first min_length words (sampling.constrain_logits, bit for bit) - and its log-probs are log_softmax of
         the edited row, renormalised over the surviving words.  Scores, tie rules, the pool, length_alpha and n_best are
-        mode='beam''s.  The policy kernel keeps every beam slot's words on the device (csrc/beam_cum.hip), the depth step's fan-out
+        mode='beam''s.  The policy kernel keeps every beam slot's words on the device (csrc/beam_policy.hip), the depth step's fan-out
         kernel applies the rules in front of its top 20 (csrc/ce.hip): no host round trip per depth.  With the constraints at
         their defaults the call IS mode='beam' (the same launches, the same bits).  beam_width = 1, length_alpha = 0 gives greedy
         `decode_constrained` up to the first <eos>.  One-layer LSTM models only (a GRU or stacked model: ValueError with mode='beam''s
@@ -296,7 +296,7 @@ class S2VT(nn.Module):
         has a pool of its own; group 0 is never penalised and is exactly mode='beam' at width Wg, and diversity_lambda = 0 makes
         every group that search.  num_groups = 1 IS mode='beam' (or `beam_constrained`) with an axis of 1 inserted: the same
         launches, the same bits.  The constraint arguments are `beam_constrained`'s: every live hypothesis's logits row is edited
-        with its own words in front of its log_softmax.  The policy runs on the device (csrc/beam_div.hip; include/s2vt_hip.h
+        with its own words in front of its log_softmax.  The policy runs on the device (csrc/beam_policy.hip; include/s2vt_hip.h
         "diverse beam"), one launch per depth beside mode='beam''s depth step.  One-layer LSTM models only (a GRU
         or stacked model: ValueError with mode='beam''s message).  A method of its own: forward's parameter list is fixed.  Not
         covered: mode='beam_search', GRU and stacked models, Att_Baseline, dp.py, the groups as samples of --self-critical,

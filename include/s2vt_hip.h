@@ -930,7 +930,7 @@ int s2vt_decode_rows_constrained(const s2vt_dims* d, const s2vt_params* p, const
                                  void* stream);
 
 /* ---------------------------------------------------------------- constrained beam: the constraints inside the cumulative-score search
- * (S2VT.beam_constrained(..., no_repeat_ngram_size=, repetition_penalty=, min_length=, banned_ids=); csrc/beam_cum.hip, csrc/ce.hip;
+ * (S2VT.beam_constrained(..., no_repeat_ngram_size=, repetition_penalty=, min_length=, banned_ids=); csrc/beam_policy.hip, csrc/ce.hip;
  * restated in fp64 by tests/beam_constrained_ref.py).  The search is EXACTLY the cumulative-score beam search above
  * (s2vt_beam_cum_step) with one change.  At depth t, live slot j holds the words h = (w_1 .. w_{t-1}) (without <sos>).  Its fp32
  * logits row is first edited by rules 1-4 of the constrained draw with history h and step t-1 - sampling.constrain_logits(x, h, t-1,
@@ -973,7 +973,7 @@ int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t
 
 /* ---------------------------------------------------------------- diverse beam: diverse (group) beam search on the device
  * (S2VT.beam_diverse(..., beam_width=, num_groups=, diversity_lambda=); Vijayakumar et al., 2016; not in the reference;
- * csrc/beam_div.hip; restated in fp64 and fp32 by tests/beam_div_ref.py).  Per sample: W = beam_width slots, G = num_groups,
+ * csrc/beam_policy.hip; restated in fp64 and fp32 by tests/beam_div_ref.py).  Per sample: W = beam_width slots, G = num_groups,
  * Wg = W / G, lambda = diversity_lambda >= 0, D = max_depth; W % G == 0 and 1 <= G <= W <= 8.  Group g owns slots g*Wg .. (g+1)*Wg-1,
  * a live list and a pool of at most Wg entries.  Every live list starts as one empty hypothesis: S = 0, last word <sos>, the encoder
  * state of mode='beam'.  For t = 1..D:
@@ -1007,7 +1007,10 @@ int s2vt_beam_step_constrained(const s2vt_dims* d, const s2vt_params* p, int32_t
  * s2vt_beam_div_step: hist_out and hist_ld_out both null: the plain form.  Both non-null: the form with the words; after the call
  * *hist_out / *hist_ld_out are what s2vt_beam_step_constrained must read at the next depth step (see s2vt_beam_cum_hist_step).
  * s2vt_beam_div_result: every group's first n_best pool entries (1 <= n_best <= Wg) -> out_tokens [B][G][n_best][max_depth] int32
- * (words after <sos>, padded with eos_ix), out_len [B][G][n_best], out_score [B][G][n_best], each group best first; serves both forms. */
+ * (words after <sos>, padded with eos_ix), out_len [B][G][n_best], out_score [B][G][n_best], each group best first; serves both forms.
+ * One policy, one state (csrc/beam_policy.hip): the s2vt_beam_cum_* entries are these at num_groups = 1, diversity_lambda = 0 (inert at one
+ * group) - s2vt_beam_cum_bytes(B, W, D) == s2vt_beam_div_bytes(B, W, 1, D, 0), s2vt_beam_cum_hist_bytes(B, W, D) ==
+ * s2vt_beam_div_bytes(B, W, 1, D, 1), and a state stepped through one family is read by the other's result entry. */
 size_t s2vt_beam_div_bytes(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t hist);
 int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t sos_ix, int32_t eos_ix,
                        double length_alpha, double diversity_lambda, int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix,

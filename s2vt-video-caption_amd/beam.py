@@ -14,8 +14,10 @@ unchanged, fan-out = top-20 tokens pushed in ascending token order, stop when th
 <= beam_width entries, answer = best queue entry back-traced, first element the [[<sos>]] tensor.
 
 `S2VT.forward(mode='beam')` (beam_cumulative below) is the search the reference does not have: hypotheses ranked by their
-cumulative log-probability, length-normalised when they end, n-best out.  It shares the encoder, the depth step and the depth
-loop (_device_depth_loop) with the search above; only the policy kernel differs (csrc/beam_cum.hip).
+cumulative log-probability, length-normalised when they end, n-best out.  It is the one-group case of the ONE device policy
+(csrc/beam_policy.hip: group / diverse beam search), which also serves beam_constrained, beam_diverse and Ensemble.beam through one
+driver (_group_search).  Every search whose policy lives on the device - the reference's included - runs the one depth loop
+(_device_depth_loop) over a depth-step callable, and a model's depth step is spelled out once (_DepthStep).
 """
 import heapq
 
@@ -165,48 +167,92 @@ PLANE_STEP = True            # s2vt_beam_step_cached: the depth's GEMMs on the p
 LAST_PATH = None             # which path the last beam_search call took (bench.py reports it beside the rate)
 
 
-def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, vid_h, vid_c, word_h, word_c, gx_dec, qbytes, policy_step,
-                       policy_name, con=None):
-    """The depth loop of a search whose policy lives on the device: per depth ONE policy_step(depth, qs, top_ix, top_lp, rows, st)
-    (consume the top-20 of the depth before, freeze finished samples, write the rows of the step) and ONE s2vt_beam_step over the
-    fixed rows r = b * beam_width + slot; nothing crosses PCIe.  The early exit (all samples frozen) is polled without blocking:
-    the frozen-sample counter (the int32 at byte 0 of the policy's state) is copied to pinned memory after every depth and read
-    one depth late - extra depths change nothing.  Ends with policy_step(0, ...), the last depth's results.  Returns the policy's
-    state tensor (qbytes) and the stream.
-    con (a capi.Constraints: the constrained search): policy_step returns (pointer, row stride) of the live slots' words for the step
-    it has just prepared, and that step is s2vt_beam_step_constrained - the same three forms with the constrained fan-out head."""
-    import ctypes
-    from .functional import _ptr, _stream, _dims, _params_struct
-    dev = feats.device
-    R = B * beam_width
-    pcs = tuple(p.detach().contiguous() for p in params)
-    d = _dims(feats, pcs)
-    ps = _params_struct(capi.Params, pcs)
-    # the weight-derived images of mode='test' (plane images of W_v / W_o, the per-token gate table) serve the beam's depth step
-    # as well; a model that has not decoded with these weights yet runs ONE greedy decode of this batch to fill them (7 ms, once
-    # per weight version - eval.py decodes the whole validation set with one set of weights)
+def _decode_cache(lib, model, feats, params, d):
+    """The decode cache of this model's weights - the weight-derived images of mode='test' (plane images of W_v / W_o, the per-token
+    gate table), which serve the beam's depth step as well - or None where there is none (PLANE_STEP off, fp32-MFMA mode).  A model
+    that has not decoded with these weights yet runs ONE greedy decode of this batch to fill it (7 ms, once per weight version -
+    eval.py decodes the whole validation set with one set of weights)."""
     from . import functional
-    cache = None
-    if PLANE_STEP:
-        cache, valid = functional.decode_cache_entry(model, params, d, dev, lib)
-        if cache is not None and not valid:
-            functional.greedy_decode(feats, params, int(model.sos_ix), owner=model)
-            cache, valid = functional.decode_cache_entry(model, params, d, dev, lib)
-            if not valid:
-                cache = None
+    if not PLANE_STEP:
+        return None
+    cache, valid = functional.decode_cache_entry(model, params, d, feats.device, lib)
+    if cache is not None and not valid:
+        functional.greedy_decode(feats, params, int(model.sos_ix), owner=model)
+        cache, valid = functional.decode_cache_entry(model, params, d, feats.device, lib)
+    return cache if valid else None
+
+
+class _DepthStep(object):
+    """One model's depth step over the fixed rows r = b * beam_width + slot: what the model owns in a search - parameters, dims, decode
+    cache, precomputed vid_rnn steps, workspace, vid_rnn states and word_rnn state tables (both ping-ponged by depth parity) - and the
+    ONE place that spells out the s2vt_beam_step* call."""
+
+    def __init__(self, lib, model, feats, params, R, vid_h, vid_c, word_h, word_c, gx_dec):
+        import ctypes
+        from .functional import _dims, _params_struct
+        dev = feats.device
+        B, H = feats.shape[0], model.dim_hid
+        self.lib = lib
+        self.pcs = tuple(p.detach().contiguous() for p in params)
+        self.d = _dims(feats, self.pcs)
+        self.ps = _params_struct(capi.Params, self.pcs)
+        self.cache = _decode_cache(lib, model, feats, params, self.d)
+        self.gx_dec = gx_dec if self.cache is not None else None
+        with torch.cuda.device(dev):
+            self.nbytes = lib.s2vt_beam_workspace_bytes(ctypes.byref(self.d), R)
+            self.ws = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+            self.vid = [(vid_h.contiguous(), vid_c.contiguous()), (torch.empty(B, H, device=dev), torch.empty(B, H, device=dev))]
+            self.tab = [(torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)) for _ in range(2)]
+            self.tab[0][0][:B].copy_(word_h)
+            self.tab[0][1][:B].copy_(word_c)
+
+    def __call__(self, depth, rows, st, top_ix=None, top_lp=None, con=None, words=None, logits=None):
+        """the step of `depth` for rows [3, R] (sample, state row, token): every row's top 20 into (top_ix, top_lp) - behind the
+        constrained fan-out head with con (a capi.Constraints) and words = (pointer, row stride) of the slots' histories - or, with
+        logits [R, V], stopped one launch early so that the logits stay on the card"""
+        import ctypes
+        from .functional import _ptr
+        vid = tuple(_ptr(x) for x in self.vid[(depth - 1) & 1] + self.vid[depth & 1])           # h, c in; h, c out
+        word = tuple(_ptr(x) for x in self.tab[(depth - 1) & 1] + self.tab[depth & 1])
+        gx = self.gx_dec[depth - 1] if self.gx_dec is not None else None
+        head = (ctypes.byref(self.d), ctypes.byref(self.ps), rows.shape[1], _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]))
+        out = (_ptr(top_ix), _ptr(top_lp), _ptr(self.ws), self.nbytes)
+        cache = (_ptr(self.cache), self.cache.numel() if self.cache is not None else 0)
+        if logits is not None:
+            name, args = "s2vt_beam_step_logits", head + vid + (_ptr(gx),) + word + (_ptr(logits), logits.stride(0)) + out[2:] + cache
+        elif con is not None:
+            hist = (ctypes.byref(con), words[0], words[1], depth - 1)
+            name, args = "s2vt_beam_step_constrained", head + vid + (_ptr(gx),) + word + out + cache + hist
+        elif gx is not None:
+            name, args = "s2vt_beam_step_gx", head + (_ptr(gx),) + word + out + cache
+        elif self.cache is not None:
+            name, args = "s2vt_beam_step_cached", head + vid + word + out + cache
+        else:
+            name, args = "s2vt_beam_step", head + vid + word + out
+        capi.check(getattr(self.lib, name)(*args, st), name)
+
+
+def _model_depth_step(lib, model, feats, params, R, states, policy_name, con=None):
+    """the depth step of a one-model search for _device_depth_loop; names the path in LAST_PATH"""
+    step = _DepthStep(lib, model, feats, params, R, *states)
     global LAST_PATH
-    if cache is None:
-        gx_dec = None
-    LAST_PATH = (policy_name + " + plane-path depth step (decode cache)" + (", vid_rnn steps precomputed" if gx_dec is not None else "")) \
-        if cache is not None else policy_name + " + fp32-MFMA depth step"
+    LAST_PATH = (policy_name + " + plane-path depth step (decode cache)" + (", vid_rnn steps precomputed" if step.gx_dec is not None else "")) \
+        if step.cache is not None else policy_name + " + fp32-MFMA depth step"
+    return lambda depth, rows, top_ix, top_lp, words, st: step(depth, rows, st, top_ix, top_lp, con, words)
+
+
+def _device_depth_loop(dev, B, R, max_depth, qbytes, policy_step, depth_step):
+    """The depth loop of a search whose policy lives on the device: per depth ONE words = policy_step(depth, qs, top_ix, top_lp, rows,
+    st) (consume the top-20 of the depth before, freeze finished samples, write the rows of the step; the constrained forms return
+    (pointer, row stride) of the live slots' words for the step they have just prepared) and ONE depth_step(depth, rows, top_ix,
+    top_lp, words, st) over the fixed rows r = b * beam_width + slot (R of them) that fills top_ix / top_lp: one model's
+    (_model_depth_step) or an ensemble's; nothing crosses PCIe.  The early exit (all samples frozen) is polled without blocking: the
+    frozen-sample counter (the int32 at byte 0 of the policy's state) is copied to pinned memory after every depth and read one
+    depth late - extra depths change nothing.  Ends with policy_step(0, ...), the last depth's results.  Returns the policy's state
+    tensor (qbytes) and the stream."""
+    from .functional import _stream
     with torch.cuda.device(dev):
-        nbytes = lib.s2vt_beam_workspace_bytes(ctypes.byref(d), R)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         qs = torch.empty(qbytes, dtype=torch.uint8, device=dev)
-        vid = [(vid_h.contiguous(), vid_c.contiguous()), (torch.empty(B, H, device=dev), torch.empty(B, H, device=dev))]
-        tab = [(torch.zeros(R, H, device=dev), torch.zeros(R, H, device=dev)) for _ in range(2)]
-        tab[0][0][:B].copy_(word_h)
-        tab[0][1][:B].copy_(word_c)
         rows = torch.zeros(3, R, dtype=torch.int32, device=dev)
         top_ix = torch.zeros(R, FANOUT, dtype=torch.int32, device=dev)
         top_lp = torch.zeros(R, FANOUT, dtype=torch.float32, device=dev)
@@ -225,30 +271,7 @@ def _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, v
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
             events.append(ev)
-            (vh_in, vc_in), (vh_out, vc_out) = vid[(depth - 1) & 1], vid[depth & 1]
-            (wh_in, wc_in), (wh_out, wc_out) = tab[(depth - 1) & 1], tab[depth & 1]
-            if con is not None:
-                gx = gx_dec[depth - 1] if gx_dec is not None else None
-                capi.check(lib.s2vt_beam_step_constrained(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
-                                                          _ptr(vh_in), _ptr(vc_in), _ptr(vh_out), _ptr(vc_out), _ptr(gx), _ptr(wh_in),
-                                                          _ptr(wc_in), _ptr(wh_out), _ptr(wc_out), _ptr(top_ix), _ptr(top_lp), _ptr(ws),
-                                                          nbytes, _ptr(cache), cache.numel() if cache is not None else 0,
-                                                          ctypes.byref(con), words[0], words[1], depth - 1, st),
-                           "s2vt_beam_step_constrained")
-            elif gx_dec is not None:
-                capi.check(lib.s2vt_beam_step_gx(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
-                                                 _ptr(gx_dec[depth - 1]), _ptr(wh_in), _ptr(wc_in), _ptr(wh_out), _ptr(wc_out),
-                                                 _ptr(top_ix), _ptr(top_lp), _ptr(ws), nbytes, _ptr(cache), cache.numel(), st),
-                           "s2vt_beam_step_gx")
-            elif cache is not None:
-                capi.check(lib.s2vt_beam_step_cached(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
-                                                     _ptr(vh_in), _ptr(vc_in), _ptr(vh_out), _ptr(vc_out), _ptr(wh_in), _ptr(wc_in),
-                                                     _ptr(wh_out), _ptr(wc_out), _ptr(top_ix), _ptr(top_lp), _ptr(ws), nbytes,
-                                                     _ptr(cache), cache.numel(), st), "s2vt_beam_step_cached")
-            else:
-                capi.check(lib.s2vt_beam_step(ctypes.byref(d), ctypes.byref(ps), R, _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]),
-                                              _ptr(vh_in), _ptr(vc_in), _ptr(vh_out), _ptr(vc_out), _ptr(wh_in), _ptr(wc_in),
-                                              _ptr(wh_out), _ptr(wc_out), _ptr(top_ix), _ptr(top_lp), _ptr(ws), nbytes, st), "s2vt_beam_step")
+            depth_step(depth, rows, top_ix, top_lp, words, st)
         policy_step(0, qs, top_ix, top_lp, rows, st)    # the last depth's results
         global LAST_DEPTHS
         LAST_DEPTHS = depth
@@ -270,8 +293,9 @@ def _beam_search_device_queues(lib, model, feats, params, B, H, beam_width, max_
     def qstep(depth, qs, top_ix, top_lp, rows, st):
         capi.check(lib.s2vt_beam_queue_step(B, beam_width, max_depth, sos, eos, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
                                             _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_queue_step")
-    qs, st = _device_depth_loop(lib, model, feats, params, B, H, beam_width, max_depth, vid_h, vid_c, word_h, word_c, gx_dec, qbytes,
-                                qstep, "device queues")
+    R = B * beam_width
+    qs, st = _device_depth_loop(dev, B, R, max_depth, qbytes, qstep,
+                                _model_depth_step(lib, model, feats, params, R, (vid_h, vid_c, word_h, word_c, gx_dec), "device queues"))
     with torch.cuda.device(dev):
         cap = max_depth + 2
         out = torch.empty(B, cap, dtype=torch.int32, device=dev)
@@ -325,58 +349,76 @@ def check_beam_constraints(spec, max_depth, vocab_size):
                          "words" % (V, FANOUT, need, FANOUT))
 
 
+def _checked_constraints(constraints, max_depth, vocab_size):
+    """the ConstraintSpec of a constrained search after check_beam_constraints; None for None or a spec that constrains nothing"""
+    from . import sampling
+    if constraints is None or not sampling.constrains(constraints):
+        return None
+    check_beam_constraints(constraints, max_depth, vocab_size)
+    return constraints
+
+
 @torch.no_grad()
+def _group_search(what, dev, B, W, G, D, sos, eos, alpha, lam, n_best, constraints, make_depth_step):
+    """The one driver of the device policy (csrc/beam_policy.hip) behind mode='beam', beam_constrained, beam_diverse and Ensemble.beam:
+    G groups of W / G slots, the cumulative search being G = 1 (where lam is inert).  constraints: a checked ConstraintSpec or None -
+    with one the policy keeps every live slot's words and hands them to the depth step.  make_depth_step(lib, R, con, policy_name)
+    returns the depth step of _device_depth_loop (con: the capi.Constraints or None) and names the path in LAST_PATH.  Returns
+    (ids int64 [B, G, n_best, D] padded with <eos>, lengths int64 [B, G, n_best], scores fp32 [B, G, n_best]) on the device, every
+    group best first, without the G axis at G = 1; no host synchronisation.  `what` names the caller in the error of a state too
+    large.  One group runs through the s2vt_beam_div_* entries as well: s2vt_beam_cum_* are the same launches."""
+    import ctypes
+    from . import sampling
+    from .functional import _ptr
+    lib = capi.load()
+    hist = constraints is not None
+    qbytes = lib.s2vt_beam_div_bytes(B, W, G, D, int(hist))
+    if qbytes == 0:
+        raise ValueError("%s: batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (what, B, W, D))
+    con = keep = None
+    words, words_ld = ctypes.c_void_p(), ctypes.c_int64()
+    if hist:
+        con, keep = sampling.constraints_struct(constraints)     # (keep: the banned ids' host array lives as long as con is used)
+
+    def policy_step(depth, qs, top_ix, top_lp, rows, st):
+        capi.check(lib.s2vt_beam_div_step(B, W, G, D, sos, eos, alpha, lam, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
+                                          _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ctypes.byref(words) if hist else None,
+                                          ctypes.byref(words_ld) if hist else None, st), "s2vt_beam_div_step")
+        return (ctypes.c_void_p(words.value), words_ld.value) if hist else None
+    name = ("constrained " if hist else "") + ("cumulative beam" if G == 1 else "diverse beam")
+    qs, st = _device_depth_loop(dev, B, B * W, D, qbytes, policy_step, make_depth_step(lib, B * W, con, name))
+    with torch.cuda.device(dev):
+        lead = (B, n_best) if G == 1 else (B, G, n_best)
+        ids = torch.empty(lead + (D,), dtype=torch.int32, device=dev)
+        lens = torch.empty(lead, dtype=torch.int32, device=dev)
+        scores = torch.empty(lead, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_beam_div_result(B, W, G, D, eos, n_best, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(scores), st),
+                   "s2vt_beam_div_result")
+        return ids.long(), lens.long(), scores
+
+
+def _model_group_search(what, model, feats, params, W, G, D, alpha, lam, n_best, constraints):
+    """_group_search of one model: its encoder states, decode cache and depth step"""
+    def make_depth_step(lib, R, con, policy_name):
+        states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
+        return _model_depth_step(lib, model, feats, params, R, states, policy_name, con)
+    return _group_search(what, feats.device, feats.shape[0], W, G, D, int(model.sos_ix), int(model.eos_ix), alpha, lam, n_best,
+                         _checked_constraints(constraints, D, model.vocab_size), make_depth_step)
+
+
 def beam_cumulative(model, feats, params, beam_width=3, max_depth=30, length_alpha=0.7, n_best=1, constraints=None):
     """mode='beam' (not in the reference): hypotheses ranked by the fp32 sum of their tokens' log-probs, the
     beam_width best of all live slots' candidates kept per depth by (sum descending, slot ascending, token ascending), a hypothesis
     that ends in <eos> at depth t pooled with score sum / t**length_alpha, the ones still live at max_depth with sum /
     max_depth**length_alpha.  Same encoder, decode cache, depth step and polled early exit as mode='beam_search'; the policy is
-    csrc/beam_cum.hip.  Returns (ids int64 [B, n_best, max_depth] padded with <eos>, lengths int64 [B, n_best], scores fp32
-    [B, n_best]) on the device, best first; no host synchronisation.
+    csrc/beam_policy.hip at one group.  Returns (ids int64 [B, n_best, max_depth] padded with <eos>, lengths int64 [B, n_best],
+    scores fp32 [B, n_best]) on the device, best first; no host synchronisation.
     constraints (a sampling.ConstraintSpec; S2VT.beam_constrained, include/s2vt_hip.h "constrained beam"): every live slot's logits
     row is edited by the rules of the constrained draw with the slot's own words as history before its log_softmax and top 20 - the
-    policy keeps those words on the device (s2vt_beam_cum_hist_step), the depth step runs the constrained fan-out head
-    (s2vt_beam_step_constrained).  None, or a spec that constrains nothing: today's path, launch for launch."""
-    from . import sampling
-    from .functional import _ptr
+    policy keeps those words on the device, the depth step runs the constrained fan-out head (s2vt_beam_step_constrained).  None, or
+    a spec that constrains nothing: the plain path, launch for launch."""
     W, D, alpha, n_best = check_beam_args(beam_width, max_depth, length_alpha, n_best, model.vocab_size)
-    if constraints is not None and not sampling.constrains(constraints):
-        constraints = None
-    if constraints is not None:
-        check_beam_constraints(constraints, D, model.vocab_size)
-    dev = feats.device
-    B, H = feats.shape[0], model.dim_hid
-    sos, eos = int(model.sos_ix), int(model.eos_ix)
-    lib = capi.load()
-    qbytes = (lib.s2vt_beam_cum_hist_bytes if constraints is not None else lib.s2vt_beam_cum_bytes)(B, W, D)
-    if qbytes == 0:
-        raise ValueError("mode='beam': batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (B, W, D))
-    states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
-
-    con = keep = None
-    if constraints is None:
-        def cstep(depth, qs, top_ix, top_lp, rows, st):
-            capi.check(lib.s2vt_beam_cum_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp), _ptr(rows[0]),
-                                              _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_beam_cum_step")
-    else:
-        import ctypes
-        con, keep = sampling.constraints_struct(constraints)     # (keep: the banned ids' host array lives as long as con is used)
-        words, words_ld = ctypes.c_void_p(), ctypes.c_int64()
-
-        def cstep(depth, qs, top_ix, top_lp, rows, st):           # the same policy; it also keeps the live slots' words
-            capi.check(lib.s2vt_beam_cum_hist_step(B, W, D, sos, eos, alpha, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
-                                                   _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ctypes.byref(words),
-                                                   ctypes.byref(words_ld), st), "s2vt_beam_cum_hist_step")
-            return ctypes.c_void_p(words.value), words_ld.value
-    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, cstep,
-                                "constrained cumulative beam" if con is not None else "cumulative beam", con=con)
-    with torch.cuda.device(dev):
-        ids = torch.empty(B, n_best, D, dtype=torch.int32, device=dev)
-        lens = torch.empty(B, n_best, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, n_best, dtype=torch.float32, device=dev)
-        capi.check(lib.s2vt_beam_cum_result(B, W, D, eos, n_best, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(scores), st),
-                   "s2vt_beam_cum_result")
-        return ids.long(), lens.long(), scores
+    return _model_group_search("mode='beam'", model, feats, params, W, 1, D, alpha, 0.0, n_best, constraints)
 
 
 def check_diverse_args(beam_width, num_groups, diversity_lambda, n_best):
@@ -400,7 +442,6 @@ def check_diverse_args(beam_width, num_groups, diversity_lambda, n_best):
     return G, lam, nb
 
 
-@torch.no_grad()
 def beam_diverse(model, feats, params, beam_width=6, num_groups=3, diversity_lambda=0.5, max_depth=30, length_alpha=0.7, n_best=1,
                  constraints=None):
     """S2VT.beam_diverse (not in the reference; include/s2vt_hip.h "diverse beam"): diverse (group) beam search
@@ -408,57 +449,17 @@ def beam_diverse(model, feats, params, beam_width=6, num_groups=3, diversity_lam
     select in order, each the Wg best of its own slots' candidates by a = (sum of log-probs) - diversity_lambda * (how often the
     earlier groups chose the candidate's word at this depth), ties by (slot, token); hypotheses carry and are pooled with the
     unpenalised sum, per group, by mode='beam''s rules.  Same encoder, decode cache, depth step and polled early exit as mode='beam';
-    the policy is csrc/beam_div.hip, one launch per depth, nothing crosses PCIe.  Returns (ids int64 [B, num_groups, n_best,
+    the policy is csrc/beam_policy.hip, one launch per depth, nothing crosses PCIe.  Returns (ids int64 [B, num_groups, n_best,
     max_depth] padded with <eos>, lengths int64 [B, num_groups, n_best], scores fp32 [B, num_groups, n_best]) on the device, every
     group best first; no host synchronisation.
     constraints (a sampling.ConstraintSpec): as in beam_cumulative - every live slot's row is edited with the slot's own words in
-    front of its log_softmax and top 20; the policy keeps those words (the form of s2vt_beam_div_step with hist_out).
-    num_groups == 1 IS beam_cumulative with an axis of 1 inserted: the same launches, the same bits."""
-    import ctypes
-    from . import sampling
-    from .functional import _ptr
+    front of its log_softmax and top 20; the policy keeps those words.
+    num_groups == 1 IS beam_cumulative with an axis of 1 inserted: the same launch of the same kernel, in which diversity_lambda is
+    inert; the same bits."""
     W, D, alpha, _ = check_beam_args(beam_width, max_depth, length_alpha, 1, model.vocab_size)
     G, lam, n_best = check_diverse_args(W, num_groups, diversity_lambda, n_best)
-    if constraints is not None and not sampling.constrains(constraints):
-        constraints = None
-    if constraints is not None:
-        check_beam_constraints(constraints, D, model.vocab_size)
-    if G == 1:
-        ids, lens, scores = beam_cumulative(model, feats, params, beam_width=W, max_depth=D, length_alpha=alpha, n_best=n_best,
-                                            constraints=constraints)
-        return ids.unsqueeze(1), lens.unsqueeze(1), scores.unsqueeze(1)
-    dev = feats.device
-    B, H = feats.shape[0], model.dim_hid
-    sos, eos = int(model.sos_ix), int(model.eos_ix)
-    lib = capi.load()
-    qbytes = lib.s2vt_beam_div_bytes(B, W, G, D, int(constraints is not None))
-    if qbytes == 0:
-        raise ValueError("beam_diverse: batch %d x beam_width %d x max_beam_depth %d is more than the search state holds" % (B, W, D))
-    states = _encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER)
-
-    con = keep = None
-    if constraints is None:
-        def dstep(depth, qs, top_ix, top_lp, rows, st):
-            capi.check(lib.s2vt_beam_div_step(B, W, G, D, sos, eos, alpha, lam, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
-                                              _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), None, None, st), "s2vt_beam_div_step")
-    else:
-        con, keep = sampling.constraints_struct(constraints)     # (keep: the banned ids' host array lives as long as con is used)
-        words, words_ld = ctypes.c_void_p(), ctypes.c_int64()
-
-        def dstep(depth, qs, top_ix, top_lp, rows, st):           # the same policy; it also keeps the live slots' words
-            capi.check(lib.s2vt_beam_div_step(B, W, G, D, sos, eos, alpha, lam, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp),
-                                              _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), ctypes.byref(words), ctypes.byref(words_ld),
-                                              st), "s2vt_beam_div_step")
-            return ctypes.c_void_p(words.value), words_ld.value
-    qs, st = _device_depth_loop(lib, model, feats, params, B, H, W, D, *states, qbytes, dstep,
-                                "constrained diverse beam" if con is not None else "diverse beam", con=con)
-    with torch.cuda.device(dev):
-        ids = torch.empty(B, G, n_best, D, dtype=torch.int32, device=dev)
-        lens = torch.empty(B, G, n_best, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, G, n_best, dtype=torch.float32, device=dev)
-        capi.check(lib.s2vt_beam_div_result(B, W, G, D, eos, n_best, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(scores), st),
-                   "s2vt_beam_div_result")
-        return ids.long(), lens.long(), scores
+    out = _model_group_search("beam_diverse" if G > 1 else "mode='beam'", model, feats, params, W, G, D, alpha, lam, n_best, constraints)
+    return out if G > 1 else tuple(x.unsqueeze(1) for x in out)
 
 
 class HeapQueues(object):

@@ -147,7 +147,7 @@ SIGNATURES = {
                                                   c_int32, POINTER(Constraints), c_void_p, c_void_p, c_void_p]),
     "s2vt_beam_step_logits": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 13 + [c_int64, c_void_p, c_size_t,
                                                                                                      c_void_p, c_size_t, c_void_p]),
-    # diverse (group) beam search (S2VT.beam_diverse; csrc/beam_div.hip): the policy, plain or keeping every slot's words (hist_out given)
+    # diverse (group) beam search (S2VT.beam_diverse; csrc/beam_policy.hip): the policy, plain or keeping every slot's words (hist_out given)
     "s2vt_beam_div_bytes": (c_size_t, [c_int32] * 5),
     "s2vt_beam_div_step": (c_int32, [c_int32] * 6 + [c_double, c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 5 +
                            [POINTER(c_void_p), POINTER(c_int64), c_void_p]),

@@ -11,7 +11,7 @@
 //   api_sample_rows.hip  K sampled captions per clip on one encode (S2VT.sample), plain and with top-k / nucleus truncation; the
 //                    truncated draw and the top-20 fan-out as per-op entry points
 //   api_ops.hip      per-op entry points (GEMM, split, timestep / sequence kernels, criterion)
-// Host code only; every kernel lives in gemm* / lstm* / ce / truncate / misc / group / split / argmax_x3 / beam_queue / beam_cum / beam_div.hip.
+// Host code only; every kernel lives in gemm* / lstm* / ce / truncate / misc / group / split / argmax_x3 / beam_queue / beam_policy.hip.
 #pragma once
 #include <stdarg.h>
 #include <stdlib.h>

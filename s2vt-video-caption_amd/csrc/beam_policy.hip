@@ -1,5 +1,8 @@
-// Diverse (group) beam search (S2VT.beam_diverse; Vijayakumar et al., 2016; not in the reference): the search policy ON THE DEVICE on
-// the row protocol of beam_cum.hip (fixed rows r = b * beam_width + slot of s2vt_beam_step, nothing crosses PCIe per depth).
+// The beam policy ON THE DEVICE (not in the reference): group (diverse) beam search, Vijayakumar et al., 2016 (S2VT.beam_diverse), whose
+// one-group case is the cumulative-score search (S2VT.forward(mode='beam'), S2VT.beam_constrained, S2VTModel.Ensemble.beam).  One
+// kernel, one state, one back-trace for all of them, for every sample of a batch at once, on the row protocol of beam_queue.hip (fixed
+// rows r = b * beam_width + slot of s2vt_beam_step, nothing compacted, nothing crosses PCIe per depth).
+//
 // Definition (include/s2vt_hip.h "diverse beam"), per sample: W = beam_width slots, G groups of Wg = W / G slots,
 // lambda >= 0, D = max_depth.  Group g owns slots g*Wg .. (g+1)*Wg-1, a live list that starts as one empty hypothesis (S = 0, <sos>,
 // the encoder state) and a pool of at most Wg entries.  For t = 1..D: cnt[v] = 0 for every word; the groups run in order; a group
@@ -8,37 +11,59 @@
 // min(Wg, count) best by (a descending, j ascending, v ascending) are walked in that order: every one does cnt[v] += 1 (<eos>
 // included); v == <eos> enters the group's pool with s / t**alpha - the unpenalised sum: the penalty steers the selection and is
 // never accumulated - anything else is the group's next live slot with S = s.  At t == D every live hypothesis enters its group's
-// pool with S / D**alpha, no <eos> appended.  A pool is ordered by (score descending, insertion ascending).
+// pool with S / D**alpha, no <eos> appended.  A pool is ordered by (score descending, insertion ascending); the answer is every
+// group's first n_best.
 // fp32 form: s = S_j + fminf(lp, 0) with -0 folded to +0; a = s where cnt == 0, else s - (fp32(lambda) * fp32(cnt)), product and
 // difference each rounded to fp32 (div_key below, compiled with contraction off: never one FMA); pool scores divide by length_pow_table.
 //
 // One WAVE per sample; the G groups are walked sequentially inside the launch.  All W * 20 candidates are loaded once (c = slot * 20
 // + f over the lanes, score and word in registers).  A group computes its keys - order-preserving bits of a high, ~c low with
 // c = j_local * 20 + f, which IS (j ascending, v ascending) since top_ix rows are in ascending token order - and takes Wg rounds of the
-// keyed wave-wide max (beam_wave.h); the winner's s and word come from its owner lane by one shuffle each.  The words selected so far
-// at this depth (at most 7 matter) are wave-uniform registers, so every lane counts cnt for its own candidates: no sort, no
-// floating-point atomic, the same inputs give the same bits.  The walk (pool inserts, next live slots) is lane 0's, on LDS copies of
-// the pools that lanes 0..W-1 load and write back.
+// keyed wave-wide max (beam_wave.h); keys are distinct, so every round has exactly one winner, no replay path.  The winner's s and
+// word come from its owner lane by one shuffle each.  The words selected so far at this depth (at most 7 matter) are wave-uniform
+// registers, so every lane counts cnt for its own candidates: no sort, no floating-point atomic, the same inputs give the same bits.
+// The walk (pool inserts, next live slots) is lane 0's, on LDS copies of the pools that lanes 0..W-1 load and write back.  A slot
+// that is not live has live_nid < 0; a group's live slots are compact from its first slot, in selection order.
 //
-// Fan-out 20 stays exact for W <= 8: in group g at most g * Wg <= W - Wg distinct words are penalised; a candidate outside its
+// Fan-out 20 is exact for W <= 8: in group g at most g * Wg <= W - Wg distinct words are penalised; a candidate outside its
 // parent's unpenalised top W has W candidates of the same parent in front of it, at least Wg of them unpenalised - their keys are >=
 // its key and they win every tie - so it is never selected, and W <= 8 < 20.  With constraints the argument runs on the edited row.
 //
 // Early stop.  A group is SETTLED when it is closed, or when its pool holds Wg entries and pool[Wg-1].score >= max_j(live S_j) /
 // D**alpha.  The maximum over the live S_j is needed because the live slots are ordered by a, not by s: live[0] need not hold the
-// largest S.  A settled group's pool can never change again - the proof of beam_cum.hip per group: every log-prob is clamped to
-// <= 0, so S never rises along a hypothesis; any hypothesis the group finishes later has S' <= max_j(live S_j) <= 0 and a length
-// t' <= D, the divisor table is non-decreasing in the length for alpha >= 0, so S' / t'**alpha <= S' / D**alpha <= max_j(live S_j) /
-// D**alpha <= pool[Wg-1].score in the rounded fp32 quotients too, and an equal score loses to the earlier insertion.  (The penalty
-// never enters S or a pool score, so it plays no part.)  "Settled" is monotone: the pool's Wg-th score only rises and the live maximum
-// only falls.  A SAMPLE is frozen only when every one of its groups is settled: until then a settled group keeps stepping and keeps
-// adding to cnt, because the later groups' selections depend on its choices.  Once all are settled no pool of the sample changes
-// any more, so freezing it changes no output.
+// largest S.  A settled group's pool can never change again: the kernel clamps every log-prob to <= 0 (fminf(lp, 0)), so S never
+// rises along a hypothesis; any hypothesis the group finishes later has S' <= max_j(live S_j) <= 0 and a length t' <= D; the divisor
+// table is non-decreasing in the length for alpha >= 0 (pow and the rounding to fp32 are monotone), so S' / t'**alpha <= S' / D**alpha
+// <= max_j(live S_j) / D**alpha <= pool[Wg-1].score, and the rounded fp32 quotients keep that order (division is monotone in both
+// operands here); an equal score loses to the earlier insertion, so it never enters the best Wg.  (The penalty never enters S or a
+// pool score, so it plays no part.)  "Settled" is monotone: the pool's Wg-th score only rises and the live maximum only falls.  A
+// SAMPLE is frozen only when every one of its groups is settled: until then a settled group keeps stepping and keeps adding to cnt,
+// because the later groups' selections depend on its choices.  Once all are settled no pool of the sample changes any more, so
+// freezing it changes no output.
 //
-// HIST (the constrained form): hist[2][B][W][D] int32 behind the plain state exactly as beam_cum_kernel<true> keeps it - the slots
-// live after depth t are in buffer t & 1; the parent's t-1 words are copied by the lanes and the new word appended - so
-// s2vt_beam_step_constrained is the depth step.
+// HIST (the constrained forms; include/s2vt_hip.h "constrained beam").  The depth step's fan-out head edits a slot's logits row by the
+// rules of the constrained draw with the slot's own words as history, then takes log_softmax and the top 20 of the EDITED row (ce.hip).
+// The policy is unchanged; it only has to keep every live slot's words where that head can read them: hist[2][B][W][D] int32 behind
+// the plain state, ping-ponged by depth parity - the slots that are live after depth t (t words each) are in buffer t & 1.  When
+// candidate (j, v) becomes live slot s, the wave copies parent j's t-1 words from buffer (t-1) & 1 into slot s of buffer t & 1 (lanes
+// over the words: W * (t-1) independent loads for a wave whose lanes 1..63 are otherwise idle behind the selection) and appends v.
+// Both buffers are zeroed at depth 1, and nothing else is ever written to them - nothing at t == D, nothing for a sample that has
+// just stopped: the row of an unused slot or of a frozen sample stays readable - defined words in [0, V) - and its fan-out is never
+// consumed.  Chosen over walking node_prev inside the head: that is t DEPENDENT global loads in front of every row's load, on the
+// critical path of every depth.  The early stop holds as it stands: its proof needs lp <= 0 only, which the log_softmax of any edited
+// row gives (and the clamp enforces).  A banned word is -inf in the edited row and is never among the 20 while V >= 20 + D + n_banned
+// + 1 (checked by the callers).
+//
+// One group (the s2vt_beam_cum_* entries: G = 1, lambda = 0).  Keys are computed once per group, before its first round, from the
+// words the EARLIER groups selected: at G = 1 there are none, cnt is 0 for every candidate, the key is the plain score s and div_key is
+// never evaluated - lambda is inert.  c = j * 20 + f over the whole beam.  The selection order is then s descending, the live slots
+// keep it, so live[0].S is max_j(live S_j) bit for bit (-0 is folded away before the keys) and the early stop reads
+// pool[W-1].score >= live[0].S / D**alpha; "every group settled" is "the group settled".  The definition reduces to: the W best
+// candidates of all live slots by (S descending, j ascending, v ascending), <eos> into the one pool, n_best out.
 #include <math.h>
+
+#include <map>
+#include <mutex>
 
 #include "beam_wave.h"
 #include "common.h"
@@ -46,7 +71,7 @@
 
 namespace s2vt {
 
-struct BeamD {
+struct BeamP {
     int B, bw, G, Wg, D, NN, sos, eos, depth;  // depth: 1 = initialise; 2..D = consume step depth-1; 0 = consume step D
     float lam;                                               // fp32(diversity_lambda)
     int* done_count; int* done; int* n_nodes;
@@ -56,7 +81,7 @@ struct BeamD {
     float* powa;                                             // fp32(len ** alpha): double pow, then fp32
     const int* top_ix; const float* top_lp;                  // [B*bw][20] of the depth just stepped
     int* row_b; int* row_state; int* row_tok;                // [B*bw] for the next s2vt_beam_step
-    int* hist;                                               // [2][B][bw][D] words of the live slots (the constrained form only)
+    int* hist;                                               // [2][B][bw][D] words of the live slots (the constrained forms only)
 };
 
 // The selection key a = s - (lam * cnt), the product and the difference each rounded to fp32.  __fmul_rn / __fsub_rn are plain * and -
@@ -68,8 +93,9 @@ __device__ __forceinline__ float div_key(float s, float lam, int cnt) {
     return s - pen;
 }
 
+// HIST: the constrained forms - the same policy, and the live slots' words kept in q.hist (the comment at the top).
 template <bool HIST>
-__global__ __launch_bounds__(64) void beam_div_kernel(BeamD q) {
+__global__ __launch_bounds__(64) void beam_policy_kernel(BeamP q) {
     const int b = blockIdx.x, lane = threadIdx.x;
     const int bw = q.bw, G = q.G, Wg = q.Wg;
     float* lS = q.live_S + b * bw;
@@ -255,7 +281,7 @@ __global__ __launch_bounds__(64) void beam_div_kernel(BeamD q) {
 }
 
 // back-trace of every group's first n_best pool entries: one thread per (sample, group, rank)
-__global__ void beam_div_result_kernel(BeamD q, int n_best, int32_t* out, int32_t* out_len, float* out_score) {
+__global__ void beam_policy_result_kernel(BeamP q, int n_best, int32_t* out, int32_t* out_len, float* out_score) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= q.B * q.G * n_best) return;
     const int bg = i / n_best, k = i - bg * n_best;
@@ -274,12 +300,12 @@ __global__ void beam_div_result_kernel(BeamD q, int n_best, int32_t* out, int32_
     out_score[i] = have ? q.pool_score[e] : -INFINITY;
 }
 
-static BeamD carve_beamd(int B, int bw, int G, int D, void* base, size_t* bytes, bool hist) {
+static BeamP carve_beamp(int B, int bw, int G, int D, void* base, size_t* bytes, bool hist) {
     char* p = reinterpret_cast<char*>(base);
     size_t off = 0;
     auto take = [&](size_t n) { off = align_up(off, 256); char* r = base ? p + off : nullptr; off += n; return r; };
     const size_t slots = (size_t)B * bw;
-    BeamD q;
+    BeamP q;
     q.B = B; q.bw = bw; q.G = G; q.Wg = bw / G; q.D = D; q.NN = 1 + D * bw;
     q.done_count = reinterpret_cast<int*>(take(sizeof(int)));          // (first: the frozen-sample counter is at byte 0)
     q.done = reinterpret_cast<int*>(take(sizeof(int) * B));
@@ -293,13 +319,32 @@ static BeamD carve_beamd(int B, int bw, int G, int D, void* base, size_t* bytes,
     q.pool_nid = reinterpret_cast<int*>(take(sizeof(int) * slots));
     q.pool_len = reinterpret_cast<int*>(take(sizeof(int) * slots));
     q.powa = reinterpret_cast<float*>(take(sizeof(float) * (size_t)(D + 1)));
-    q.hist = hist ? reinterpret_cast<int*>(take(sizeof(int) * 2 * slots * (size_t)D)) : nullptr;       // (last, as in beam_cum.hip)
+    // (last: a state with words is the plain one with the words behind it - the result entries serve both)
+    q.hist = hist ? reinterpret_cast<int*>(take(sizeof(int) * 2 * slots * (size_t)D)) : nullptr;
     if (bytes) *bytes = align_up(off, 256);
     return q;
 }
 
-static bool beamd_dims_ok(int B, int bw, int G, int D) {
+static bool beamp_dims_ok(int B, int bw, int G, int D) {
     return B > 0 && bw >= 1 && bw <= BC_MAXBW && G >= 1 && G <= bw && bw % G == 0 && D >= 1 && (int64_t)B * (1 + (int64_t)D * bw) < (1ll << 28);
+}
+
+// fp32(len ** alpha) for len = 0..D, evaluated as beam_queue.hip evaluates len ** 0.7 (libm double pow, then fp32), in pinned host
+// memory that lives for the life of the process: the copy to the device is asynchronous (no host synchronisation at the start of a
+// search), so a table is never freed or rewritten - one per distinct alpha, regrown (the shorter one stays) for a larger D.
+const float* length_pow_table(double alpha, int D) {       // (kernels.h: the scoring finisher divides by the same table)
+    static std::mutex mu;
+    static std::map<double, std::pair<float*, int>> tabs;
+    std::lock_guard<std::mutex> lock(mu);
+    auto& e = tabs[alpha];
+    if (e.second < D + 1) {
+        float* grown = nullptr;
+        const int len = (D + 1 + 1023) / 1024 * 1024;
+        if (hipHostMalloc(reinterpret_cast<void**>(&grown), (size_t)len * sizeof(float), hipHostMallocDefault) != hipSuccess) return nullptr;
+        for (int l = 0; l < len; ++l) grown[l] = l > 0 ? (float)pow((double)l, alpha) : 1.0f;
+        e = {grown, len};
+    }
+    return e.first;
 }
 
 }  // namespace s2vt
@@ -308,44 +353,45 @@ using namespace s2vt;
 
 extern "C" {
 
-size_t s2vt_beam_div_bytes(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t hist) {
-    if (!beamd_dims_ok(B, beam_width, num_groups, max_depth)) return 0;
-    size_t bytes = 0;
-    carve_beamd(B, beam_width, num_groups, max_depth, nullptr, &bytes, hist != 0);
-    return bytes;
+// Every exported entry below is its arguments over these three (fn names the entry that was called); the s2vt_beam_cum_* entries are
+// G = 1, lambda = 0.
+static size_t bytes(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, bool hist) {
+    if (!beamp_dims_ok(B, beam_width, num_groups, max_depth)) return 0;
+    size_t n = 0;
+    carve_beamp(B, beam_width, num_groups, max_depth, nullptr, &n, hist);
+    return n;
 }
 
-// hist_out / hist_ld_out both non-null: the form that keeps the live slots' words (the constrained search); both null: the plain form
-int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t sos_ix, int32_t eos_ix,
-                       double length_alpha, double diversity_lambda, int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix,
-                       const float* top_lp, int32_t* row_b, int32_t* row_state, int32_t* row_tok, const int32_t** hist_out,
-                       int64_t* hist_ld_out, void* stream) {
-    S2VT_REQUIRE(num_groups >= 1 && beam_width >= 1 && beam_width <= BC_MAXBW && num_groups <= beam_width && beam_width % num_groups == 0,
-                 "s2vt_beam_div_step: beam_width must be a multiple of num_groups (1 <= num_groups <= beam_width <= %d)", BC_MAXBW);
-    S2VT_REQUIRE(beamd_dims_ok(B, beam_width, num_groups, max_depth) && depth >= 0 && depth <= max_depth && state && row_b && row_state &&
-                 row_tok, "s2vt_beam_div_step: null/invalid argument (B >= 1, 0 <= depth <= max_depth)");
-    S2VT_REQUIRE(isfinite(length_alpha) && length_alpha >= 0.0, "s2vt_beam_div_step: length_alpha must be finite and >= 0");
+// hist_out / hist_ld_out both non-null: the form that keeps the live slots' words (the constrained searches); both null: the plain form
+static int step(const char* fn, int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t sos_ix, int32_t eos_ix,
+                double length_alpha, double diversity_lambda, int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix,
+                const float* top_lp, int32_t* row_b, int32_t* row_state, int32_t* row_tok, const int32_t** hist_out, int64_t* hist_ld_out,
+                void* stream) {
+    S2VT_REQUIRE(beamp_dims_ok(B, beam_width, num_groups, max_depth) && depth >= 0 && depth <= max_depth && state && row_b && row_state &&
+                 row_tok, "%s: null/invalid argument (B >= 1, 1 <= num_groups <= beam_width <= %d, beam_width a multiple of num_groups, "
+                 "0 <= depth <= max_depth)", fn, BC_MAXBW);
+    S2VT_REQUIRE(isfinite(length_alpha) && length_alpha >= 0.0, "%s: length_alpha must be finite and >= 0", fn);
     S2VT_REQUIRE(isfinite(diversity_lambda) && diversity_lambda >= 0.0 && isfinite((float)diversity_lambda),
-                 "s2vt_beam_div_step: diversity_lambda must be finite (in fp32) and >= 0");
-    S2VT_REQUIRE(depth == 1 || (top_ix && top_lp), "s2vt_beam_div_step: the step's top-20 arrays are needed from depth 2 on");
-    S2VT_REQUIRE((hist_out == nullptr) == (hist_ld_out == nullptr), "s2vt_beam_div_step: hist_out and hist_ld_out go together");
+                 "%s: diversity_lambda must be finite (in fp32) and >= 0", fn);
+    S2VT_REQUIRE(depth == 1 || (top_ix && top_lp), "%s: the step's top-20 arrays are needed from depth 2 on", fn);
+    S2VT_REQUIRE((hist_out == nullptr) == (hist_ld_out == nullptr), "%s: hist_out and hist_ld_out go together", fn);
     const bool hist = hist_out != nullptr;
     size_t need = 0;
-    BeamD q = carve_beamd(B, beam_width, num_groups, max_depth, state, &need, hist);
-    S2VT_REQUIRE(state_bytes >= need, "s2vt_beam_div_step: state %zu < %zu bytes", state_bytes, need);
+    BeamP q = carve_beamp(B, beam_width, num_groups, max_depth, state, &need, hist);
+    S2VT_REQUIRE(state_bytes >= need, "%s: state %zu < %zu bytes", fn, state_bytes, need);
     q.sos = sos_ix; q.eos = eos_ix; q.depth = depth; q.lam = (float)diversity_lambda;
     q.top_ix = top_ix; q.top_lp = top_lp;
     q.row_b = row_b; q.row_state = row_state; q.row_tok = row_tok;
     hipStream_t st = (hipStream_t)stream;
     if (depth == 1) {
         const float* tab = length_pow_table(length_alpha, max_depth);
-        S2VT_REQUIRE(tab, "s2vt_beam_div_step: no pinned memory for the length table");
+        S2VT_REQUIRE(tab, "%s: no pinned memory for the length table", fn);
         S2VT_HIP(hipMemcpyAsync(q.powa, tab, (size_t)(max_depth + 1) * sizeof(float), hipMemcpyHostToDevice, st));
         S2VT_HIP(hipMemsetAsync(q.done_count, 0, sizeof(int), st));
     }
-    if (hist) hipLaunchKernelGGL(beam_div_kernel<true>, dim3(B), dim3(64), 0, st, q);
-    else hipLaunchKernelGGL(beam_div_kernel<false>, dim3(B), dim3(64), 0, st, q);
-    S2VT_LAUNCH_CHECK("beam_div_kernel");
+    if (hist) hipLaunchKernelGGL(beam_policy_kernel<true>, dim3(B), dim3(64), 0, st, q);
+    else hipLaunchKernelGGL(beam_policy_kernel<false>, dim3(B), dim3(64), 0, st, q);
+    S2VT_LAUNCH_CHECK("beam_policy_kernel");
     if (hist) {
         // the slots that are live after this call hold depth - 1 words each (depth 1: none), in buffer (depth - 1) & 1
         const int t = depth == 0 ? max_depth : depth - 1;
@@ -355,23 +401,59 @@ int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_
     return 0;
 }
 
-int s2vt_beam_div_result(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state,
-                         size_t state_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream) {
-    S2VT_REQUIRE(num_groups >= 1 && beam_width >= 1 && beam_width <= BC_MAXBW && num_groups <= beam_width && beam_width % num_groups == 0,
-                 "s2vt_beam_div_result: beam_width must be a multiple of num_groups (1 <= num_groups <= beam_width <= %d)", BC_MAXBW);
-    S2VT_REQUIRE(beamd_dims_ok(B, beam_width, num_groups, max_depth) && state && out_tokens && out_len && out_score,
-                 "s2vt_beam_div_result: null/invalid argument");
-    S2VT_REQUIRE(n_best >= 1 && n_best <= beam_width / num_groups, "s2vt_beam_div_result: 1 <= n_best <= beam_width / num_groups = %d",
+static int result(const char* fn, int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t eos_ix, int32_t n_best,
+                  void* state, size_t state_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream) {
+    S2VT_REQUIRE(beamp_dims_ok(B, beam_width, num_groups, max_depth) && state && out_tokens && out_len && out_score,
+                 "%s: null/invalid argument (B >= 1, 1 <= num_groups <= beam_width <= %d, beam_width a multiple of num_groups)", fn, BC_MAXBW);
+    S2VT_REQUIRE(n_best >= 1 && n_best <= beam_width / num_groups, "%s: 1 <= n_best <= beam_width / num_groups = %d", fn,
                  beam_width / num_groups);
     size_t need = 0;                                       // (the plain state: the words, where there are any, lie behind it)
-    BeamD q = carve_beamd(B, beam_width, num_groups, max_depth, state, &need, false);
-    S2VT_REQUIRE(state_bytes >= need, "s2vt_beam_div_result: state %zu < %zu bytes", state_bytes, need);
+    BeamP q = carve_beamp(B, beam_width, num_groups, max_depth, state, &need, false);
+    S2VT_REQUIRE(state_bytes >= need, "%s: state %zu < %zu bytes", fn, state_bytes, need);
     q.sos = 0; q.eos = eos_ix; q.depth = 0; q.lam = 0.0f;
     q.top_ix = nullptr; q.top_lp = nullptr; q.row_b = q.row_state = q.row_tok = nullptr;
-    hipLaunchKernelGGL(beam_div_result_kernel, dim3(cdiv(B * num_groups * n_best, 64)), dim3(64), 0, (hipStream_t)stream, q, n_best,
+    hipLaunchKernelGGL(beam_policy_result_kernel, dim3(cdiv(B * num_groups * n_best, 64)), dim3(64), 0, (hipStream_t)stream, q, n_best,
                        out_tokens, out_len, out_score);
-    S2VT_LAUNCH_CHECK("beam_div_result_kernel");
+    S2VT_LAUNCH_CHECK("beam_policy_result_kernel");
     return 0;
+}
+
+size_t s2vt_beam_cum_bytes(int32_t B, int32_t beam_width, int32_t max_depth) { return bytes(B, beam_width, 1, max_depth, false); }
+size_t s2vt_beam_cum_hist_bytes(int32_t B, int32_t beam_width, int32_t max_depth) { return bytes(B, beam_width, 1, max_depth, true); }
+size_t s2vt_beam_div_bytes(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t hist) {
+    return bytes(B, beam_width, num_groups, max_depth, hist != 0);
+}
+
+int s2vt_beam_cum_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, double length_alpha, int32_t depth,
+                       void* state, size_t state_bytes, const int32_t* top_ix, const float* top_lp, int32_t* row_b, int32_t* row_state,
+                       int32_t* row_tok, void* stream) {
+    return step("s2vt_beam_cum_step", B, beam_width, 1, max_depth, sos_ix, eos_ix, length_alpha, 0.0, depth, state, state_bytes, top_ix,
+                top_lp, row_b, row_state, row_tok, nullptr, nullptr, stream);
+}
+int s2vt_beam_cum_hist_step(int32_t B, int32_t beam_width, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, double length_alpha,
+                            int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix, const float* top_lp, int32_t* row_b,
+                            int32_t* row_state, int32_t* row_tok, const int32_t** hist_out, int64_t* hist_ld_out, void* stream) {
+    S2VT_REQUIRE(hist_out && hist_ld_out, "s2vt_beam_cum_hist_step: null hist_out / hist_ld_out");
+    return step("s2vt_beam_cum_hist_step", B, beam_width, 1, max_depth, sos_ix, eos_ix, length_alpha, 0.0, depth, state, state_bytes, top_ix,
+                top_lp, row_b, row_state, row_tok, hist_out, hist_ld_out, stream);
+}
+int s2vt_beam_div_step(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t sos_ix, int32_t eos_ix,
+                       double length_alpha, double diversity_lambda, int32_t depth, void* state, size_t state_bytes, const int32_t* top_ix,
+                       const float* top_lp, int32_t* row_b, int32_t* row_state, int32_t* row_tok, const int32_t** hist_out,
+                       int64_t* hist_ld_out, void* stream) {
+    return step("s2vt_beam_div_step", B, beam_width, num_groups, max_depth, sos_ix, eos_ix, length_alpha, diversity_lambda, depth, state,
+                state_bytes, top_ix, top_lp, row_b, row_state, row_tok, hist_out, hist_ld_out, stream);
+}
+
+int s2vt_beam_cum_result(int32_t B, int32_t beam_width, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state, size_t state_bytes,
+                         int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream) {
+    return result("s2vt_beam_cum_result", B, beam_width, 1, max_depth, eos_ix, n_best, state, state_bytes, out_tokens, out_len, out_score,
+                  stream);
+}
+int s2vt_beam_div_result(int32_t B, int32_t beam_width, int32_t num_groups, int32_t max_depth, int32_t eos_ix, int32_t n_best, void* state,
+                         size_t state_bytes, int32_t* out_tokens, int32_t* out_len, float* out_score, void* stream) {
+    return result("s2vt_beam_div_result", B, beam_width, num_groups, max_depth, eos_ix, n_best, state, state_bytes, out_tokens, out_len,
+                  out_score, stream);
 }
 
 }  // extern "C"

@@ -291,7 +291,7 @@ int s2vt_beam_queue_step(int32_t B, int32_t beam_width, int32_t max_depth, int32
     hipStream_t st = (hipStream_t)stream;
     if (depth == 1) {
         // score divisor len ** 0.7 exactly as the reference evaluates it: Python float pow (libm double), then fp32 (:262-266)
-        // The table (length_pow_table, beam_cum.hip: entries 0 .. max_depth + 3) lives in pinned host memory for the life of the
+        // The table (length_pow_table, beam_policy.hip: entries 0 .. max_depth + 3) lives in pinned host memory for the life of the
         // process, so the copy is asynchronous: no host synchronisation at the start of a search, and the call can be stream-captured.
         const float* tab = length_pow_table(0.7, max_depth + 3);
         S2VT_REQUIRE(tab, "s2vt_beam_queue_step: no pinned memory for the length table");

@@ -1,4 +1,4 @@
-// What the device-side beam policies share (beam_cum.hip, beam_div.hip): the fan-out of the depth step, the width limit and the
+// What the device-side beam policy (beam_policy.hip) is built from: the fan-out of the depth step, the width limit and the
 // 64-bit keyed wave-wide max that selects candidates with the tie rule in one reduction.
 #pragma once
 

@@ -260,7 +260,7 @@ __global__ __launch_bounds__(256) void top20_logprob_kernel(const float* logits,
 // row of `logits` is EDITED IN PLACE, then loaded: max, sum-exp and the 20 extractions see the edited row, so the log-probs are
 // renormalised over the surviving words and a banned word (-inf) is never extracted while 20 finite words are left (the callers
 // refuse shapes that could leave fewer: V >= 20 + t + n_banned + 1).  The row's history is beam slot blockIdx.x's own words,
-// int32 hist[row * hist_ld + i] (beam_cum.hip keeps them).  expf(-inf - max) is +0: an edited element adds nothing to the sum.
+// int32 hist[row * hist_ld + i] (beam_policy.hip keeps them).  expf(-inf - max) is +0: an edited element adds nothing to the sum.
 // LDS: the phase's 1057 * 5 bytes + 176 here, beside LdsRow's 150 KiB (row_frame.h asserts the sum against 160 KiB).
 template <class Row>
 __global__ __launch_bounds__(256) void top20_logprob_constrained_kernel(float* logits, int64_t ld, int V, ConstrainArgs c, BeamHist hist,
@@ -390,7 +390,7 @@ int score_prep(hipStream_t s, const int64_t* caps, int64_t stride_b, int64_t str
 
 // The finisher of a scoring call, one lane per caption: n = the position of the first <eos> among tok[1..T-1] counted from 1 (none:
 // T - 1), token_lp[r][j] = lp[j][r] for j < n and 0 behind, score = (their fp32 sum, j ascending) / powa[n], powa[n] = fp32(n **
-// alpha) from the host's table (beam_cum.hip's power rule).  Sequential per caption: deterministic.
+// alpha) from the host's table (beam_policy.hip's power rule).  Sequential per caption: deterministic.
 __global__ __launch_bounds__(256) void score_finish_kernel(const float* lp, const int32_t* tok, int R, int Rp, int T, int eos,
                                                            const float* powa, float* token_lp, float* score, int64_t* length) {
     const int r = blockIdx.x * 256 + threadIdx.x;

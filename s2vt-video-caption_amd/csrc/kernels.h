@@ -424,7 +424,7 @@ int constrained_draw(hipStream_t s, float* logits, int64_t ld, int64_t rows, int
                      float top_p, const GumbelArgs& ga, unsigned long long* packed, int32_t* kept);
 // the constrained beam's fan-out (ce.hip): the same constraint phase in front of top20_logprob's row work, in one launch - the rows
 // of `logits` are EDITED IN PLACE.  c.hist / c.hist_ld are not read: row r's history is int32 hist[r * hist_ld + i], i < c.t
-// (beam_cum.hip's per-slot words).  Refused unless V >= 20 + c.t + c.n_banned + 1 (20 finite words are then left in every row).
+// (beam_policy.hip's per-slot words).  Refused unless V >= 20 + c.t + c.n_banned + 1 (20 finite words are then left in every row).
 int top20_logprob_constrained(hipStream_t s, float* logits, int64_t ld, int64_t rows, int V, const ConstrainArgs& c, const int32_t* hist,
                               int64_t hist_ld, int32_t* top_ix, float* top_lp);
 // ---- ensemble.hip: the fan-out head of the ensemble beam search (include/s2vt_hip.h "ensemble beam"): member m's row r at logits +
@@ -439,7 +439,7 @@ int ensemble_top20_constrained(const char* fn, hipStream_t s, float* logits, int
                                int V, const float* log_w, const ConstrainArgs& c, const int32_t* hist, int64_t hist_ld, int32_t* top_ix,
                                float* top_lp);
 // fp32(len ** alpha) for len = 0..D (len 0: 1), libm double pow then fp32, in pinned host memory that lives for the life of the
-// process (beam_cum.hip: the power rule of mode='beam'); null when no pinned memory is left
+// process (beam_policy.hip: the power rule of mode='beam'); null when no pinned memory is left
 const float* length_pow_table(double alpha, int D);
 
 }  // namespace s2vt

@@ -192,7 +192,7 @@ __device__ __forceinline__ void top20_extract_row(Row& row, int V, float sub, fl
 // IN PLACE in global memory, in front of the row's load and in the same launch - truncate.hip's constrained draw and ce.hip's
 // constrained top-20 fan-out.  The row's history h[0..t) comes through an accessor (hist(i) = word i of THIS workgroup's row):
 //   PackedHist   the decode drivers' packed words, hist[i * ld + row]; the token is 0xFFFFFFFF - the low half
-//   BeamHist     the cumulative beam search's per-slot words (beam_cum.hip), int32 hist[row * ld + i]
+//   BeamHist     the cumulative beam search's per-slot words (beam_policy.hip), int32 hist[row * ld + i]
 //   candidates   c in [0, C), C = t + n_banned (+ 1): the t history tokens, the banned ids, <eos> while t < min_length - kept in
 //                static LDS (tok) with one flag byte each (ban): the "edit list"
 //   n-gram       one thread per start position i in [0, t - n]: n - 1 compares of h[i ..] against the suffix h[t-n+1 ..]; a match

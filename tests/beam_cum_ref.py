@@ -10,7 +10,7 @@ first n_best entries.
 
   search_fp64   the whole path in torch fp64 on the CPU (model arithmetic from oracle/s2vt_oracle.py), with the two decision gaps
   PolicyF32     the policy alone over given per-depth top-20 arrays, in numpy float32 with the device's adds, power table and
-                division - what csrc/beam_cum.hip must reproduce exactly
+                division - what csrc/beam_policy.hip must reproduce exactly
 """
 import numpy as np
 import torch

@@ -13,7 +13,7 @@ by sampling.constrain_logits with slot j's own words as history, as in tests/bea
 
   search_fp64    the whole path in torch fp64 on the CPU (model arithmetic from oracle/s2vt_oracle.py), with the two decision gaps
   PolicyDivF32   the policy alone over given per-depth top-20 arrays, in numpy float32 with the device's operations - what
-                 csrc/beam_div.hip must reproduce exactly
+                 csrc/beam_policy.hip must reproduce exactly
 """
 import numpy as np
 import torch

@@ -1,4 +1,4 @@
-"""CPU: the cumulative-score beam search (S2VT.forward(mode='beam'), csrc/beam_cum.hip) - argument checks of the Python surface and
+"""CPU: the cumulative-score beam search (S2VT.forward(mode='beam'), csrc/beam_policy.hip) - argument checks of the Python surface and
 of the C ABI before anything is launched, and the fp64 restatement the GPU tests compare against (tests/beam_cum_ref.py): it
 degenerates to greedy decoding at width 1, its float32 policy restatement takes the same decisions, and at most a quarter of each
 case's samples rest on a near-tie (the cap on what tests/test_gpu_beam_cum.py may leave out)."""

@@ -244,6 +244,18 @@ def test_header_declares_and_capi_binds_the_new_symbols(lib):
         assert lib.s2vt_beam_div_bytes(*bad, 0) == 0 and lib.s2vt_beam_div_bytes(*bad, 1) == 0, bad
 
 
+def test_the_cumulative_entries_size_the_one_group_state(lib):
+    """one policy, one state: s2vt_beam_cum_bytes IS s2vt_beam_div_bytes at one group, plain and with histories, and both refuse the
+    same dims"""
+    for B, W, D in ((1, 1, 1), (3, 5, 6), (64, 5, 12), (128, 8, 30), (7, 3, 1023)):
+        nb, nh = lib.s2vt_beam_cum_bytes(B, W, D), lib.s2vt_beam_cum_hist_bytes(B, W, D)
+        assert nb > 0 and nb == lib.s2vt_beam_div_bytes(B, W, 1, D, 0), (B, W, D)
+        assert nh >= nb + 2 * B * W * D * 4 and nh == lib.s2vt_beam_div_bytes(B, W, 1, D, 1), (B, W, D)
+    for bad in ((0, 5, 12), (64, 0, 12), (64, 9, 12), (64, 5, 0), (-1, 5, 12), (1 << 20, 8, 1 << 10)):
+        assert lib.s2vt_beam_cum_bytes(*bad) == 0 and lib.s2vt_beam_cum_hist_bytes(*bad) == 0, bad
+        assert lib.s2vt_beam_div_bytes(bad[0], bad[1], 1, bad[2], 0) == 0 and lib.s2vt_beam_div_bytes(bad[0], bad[1], 1, bad[2], 1) == 0, bad
+
+
 def test_c_abi_refuses_bad_arguments_before_a_launch(lib):
     import ctypes
     p = ctypes.c_void_p(256)                        # never dereferenced: every call below is refused before a launch

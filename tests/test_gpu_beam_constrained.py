@@ -1,7 +1,7 @@
 """GPU: the constrained cumulative-score beam search, S2VT.beam_constrained (include/s2vt_hip.h "constrained beam").
 
 The fan-out head (csrc/ce.hip: the constraint phase in front of the top 20) by value against sampling.constrain_logits; the policy
-kernel with per-slot histories (csrc/beam_cum.hip) bit for bit against the float32 restatement and against the plain policy
+kernel with per-slot histories (csrc/beam_policy.hip) bit for bit against the float32 restatement and against the plain policy
 entry; the whole path against the fp64 restatement (tests/beam_constrained_ref.py) on every sample whose decisions are clear;
 width 1 against greedy decode_constrained; default constraints against mode='beam'; both depth-step paths; eval.py."""
 import ctypes

@@ -1,4 +1,4 @@
-"""GPU: the cumulative-score beam search, S2VT.forward(mode='beam') (csrc/beam_cum.hip + beam.beam_cumulative).
+"""GPU: the cumulative-score beam search, S2VT.forward(mode='beam') (csrc/beam_policy.hip + beam.beam_cumulative).
 
 The policy kernel alone is compared bit for bit with the float32 restatement of the definition (tests/beam_cum_ref.PolicyF32: same
 adds, same power table, same division); the whole path with the fp64 restatement on every sample whose decisions are clear

@@ -1,4 +1,4 @@
-"""GPU: diverse (group) beam search, S2VT.beam_diverse (csrc/beam_div.hip + beam.beam_diverse; include/s2vt_hip.h "diverse beam").
+"""GPU: diverse (group) beam search, S2VT.beam_diverse (csrc/beam_policy.hip + beam.beam_diverse; include/s2vt_hip.h "diverse beam").
 
 The policy kernel alone, plain and with per-slot histories, is compared bit for bit with the float32 restatement of the definition
 (tests/beam_div_ref.PolicyDivF32: the same adds, the product and the difference of the penalty rounded separately, the same power
@@ -155,14 +155,14 @@ def crafted_eos_first(B, W, D):
     return tops
 
 
-def crafted_early(B, W, D):
-    """<eos> at log-prob 0 from depth 2 on, every other word a little below (alpha = 0: the score is the sum): pools fill with sums no
-    live hypothesis can reach any more"""
+def crafted_early(B, W, D, rows=None):
+    """<eos> at log-prob 0 from depth 2 on (in the given rows; None: all), every other word a little below (alpha = 0: the score is
+    the sum): pools fill with sums no live hypothesis can reach any more"""
     tops = _random_tops(B, W, D, 15, eos=False)
     tops[0][1][:] = tops[0][1] / 3.0 * 0.04 - 0.01                # depth 1 in [-0.05, -0.01]
     for t in range(1, D):
         tops[t][1][:] = tops[t][1] / 3.0 * 0.004 - 0.001          # then in [-0.005, -0.001]
-        _with_eos(tops[t][0], tops[t][1], range(B * W), 0.0)
+        _with_eos(tops[t][0], tops[t][1], range(B * W) if rows is None else rows, 0.0)
     return tops
 
 
@@ -223,6 +223,91 @@ def test_policy_kernel_on_crafted_inputs(lib):
         for hist in (False, True):
             counts, partial, early = _drive(lib, B, W, G, D, 0.0, lam, crafted_early(B, W, D), hist)
             assert early and counts[D - 2] == B and (partial or not late), (W, G, counts)
+
+
+def _drive_one_group(lib, B, W, D, alpha, tops, hist):
+    """s2vt_beam_cum_step / s2vt_beam_cum_hist_step beside s2vt_beam_div_step at one group with lambda = 0.5, each on its own zeroed
+    state and rows, fed the same top-20 arrays: after every call the rows and the WHOLE states (the counter at byte 0 and both word
+    buffers included) are equal, and the returned word buffers are the same place; at the end both result entries give the same
+    bits on either state.  -> the depth after which the restatement has each sample frozen"""
+    R = B * W
+    plain = lib.s2vt_beam_cum_bytes(B, W, D)
+    nbytes = lib.s2vt_beam_cum_hist_bytes(B, W, D) if hist else plain
+    assert 0 < plain <= nbytes == lib.s2vt_beam_div_bytes(B, W, 1, D, int(hist))
+    q_cum, q_div = (torch.zeros(nbytes, dtype=torch.uint8, device=DEV) for _ in range(2))
+    r_cum, r_div = (torch.full((3, R), -7, dtype=torch.int32, device=DEV) for _ in range(2))
+    ix_d = torch.zeros(R, 20, dtype=torch.int32, device=DEV)
+    lp_d = torch.zeros(R, 20, dtype=torch.float32, device=DEV)
+    st = torch.cuda.current_stream(DEV).cuda_stream
+    w_cum, w_div, ld_cum, ld_div = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64()
+
+    def call(depth):
+        a = (alpha, depth, _ptr(q_cum), nbytes, _ptr(ix_d), _ptr(lp_d), _ptr(r_cum[0]), _ptr(r_cum[1]), _ptr(r_cum[2]))
+        if hist:
+            capi.check(lib.s2vt_beam_cum_hist_step(B, W, D, ref.SOS, ref.EOS, *a, ctypes.byref(w_cum), ctypes.byref(ld_cum), st),
+                       "s2vt_beam_cum_hist_step")
+        else:
+            capi.check(lib.s2vt_beam_cum_step(B, W, D, ref.SOS, ref.EOS, *a, st), "s2vt_beam_cum_step")
+        capi.check(lib.s2vt_beam_div_step(B, W, 1, D, ref.SOS, ref.EOS, alpha, 0.5, depth, _ptr(q_div), nbytes, _ptr(ix_d), _ptr(lp_d),
+                                          _ptr(r_div[0]), _ptr(r_div[1]), _ptr(r_div[2]), ctypes.byref(w_div) if hist else None,
+                                          ctypes.byref(ld_div) if hist else None, st), "s2vt_beam_div_step")
+        assert torch.equal(r_cum, r_div), (depth, r_cum, r_div)
+        assert torch.equal(q_cum, q_div), depth
+        count = int(q_cum[:4].view(torch.int32).item())
+        assert count == int(q_div[:4].view(torch.int32).item())
+        if hist:
+            off = w_cum.value - q_cum.data_ptr()
+            assert off == w_div.value - q_div.data_ptr() and ld_cum.value == ld_div.value == D
+            assert plain <= off and off % 4 == 0 and off + R * D * 4 <= nbytes
+            assert torch.equal(q_cum[off:off + R * D * 4], q_div[off:off + R * D * 4])
+        return r_cum.cpu().numpy(), count
+    pol = ref.PolicyF32(B, W, D, alpha)
+    got, count = call(1)
+    assert count == 0 and np.array_equal(got[0], np.repeat(np.arange(B), W)) and np.array_equal(got[1:], pol.rows())
+    frozen = np.zeros(B, dtype=bool)
+    when = np.zeros(B, dtype=np.int64)
+    for t in range(1, D + 1):
+        ix_d.copy_(torch.from_numpy(tops[t - 1][0]))
+        lp_d.copy_(torch.from_numpy(tops[t - 1][1]))
+        got, count = call(t + 1 if t < D else 0)
+        pol.step(*tops[t - 1])
+        now = (pol.done | pol.may_stop()) & ~frozen
+        when[now] = t
+        frozen |= now
+        want = pol.rows()
+        want[:, np.repeat(frozen, W)] = 0
+        assert np.array_equal(got[1:], want) and count == int(frozen.sum()), (t, got[1:], want, count)
+    assert frozen.all()
+    wi, wl, _ = pol.result()
+    outs = []
+    for q in (q_cum, q_div):
+        for entry in ("s2vt_beam_cum_result", "s2vt_beam_div_result"):
+            ids = torch.empty(B, W, D, dtype=torch.int32, device=DEV)
+            lens = torch.empty(B, W, dtype=torch.int32, device=DEV)
+            scores = torch.empty(B, W, dtype=torch.float32, device=DEV)
+            groups = (1,) if entry == "s2vt_beam_div_result" else ()
+            capi.check(getattr(lib, entry)(B, W, *groups, D, ref.EOS, W, _ptr(q), nbytes, _ptr(ids), _ptr(lens), _ptr(scores), st), entry)
+            outs.append((ids.cpu().numpy(), lens.cpu().numpy(), scores.cpu().numpy()))
+    assert np.array_equal(outs[0][0], wi) and np.array_equal(outs[0][1], wl)
+    assert all(_same_bits(o, outs[0]) for o in outs[1:])
+    return when
+
+
+@pytest.mark.parametrize("W", [1, 5, 8])
+@pytest.mark.parametrize("hist", [False, True], ids=["plain", "hist"])
+def test_one_group_is_the_cumulative_entries_launch_for_launch(lib, W, hist):
+    """one policy kernel: the cumulative entries are the group entries at one group, where lambda is inert.  Two inputs, on each of
+    which the restatement freezes some sample early and runs some to D: sample 0 selects nothing but <eos> at depth 2 (its live list
+    empties; alpha = 0.7) - the others never see <eos>; and crafted_early without <eos> for the last sample (alpha = 0: at W > 1 the
+    early stop fires while hypotheses are live)"""
+    B, D = 3, 6
+    tops = _random_tops(B, W, D, 40 + W, eos=False)
+    tops[1][1][:W] -= 5.0
+    _with_eos(tops[1][0], tops[1][1], range(W), -0.001)
+    when = _drive_one_group(lib, B, W, D, 0.7, tops, hist)
+    assert when.tolist() == [2, D, D]
+    when = _drive_one_group(lib, B, W, D, 0.0, crafted_early(B, W, D, rows=range((B - 1) * W)), hist)
+    assert (when[:B - 1] < D).all() and when[B - 1] == D, when
 
 
 # ------------------------------------------------------------------ 2. the whole path against the fp64 restatement

@@ -1,4 +1,4 @@
-"""Cost of the constraints inside the cumulative-score beam search (S2VT.beam_constrained; csrc/beam_cum.hip with per-slot
+"""Cost of the constraints inside the cumulative-score beam search (S2VT.beam_constrained; csrc/beam_policy.hip with per-slot
 histories, csrc/ce.hip's constrained top-20 fan-out) beside the unconstrained search (mode='beam') in one process on one MI355X.
 Whole search: config 5 dims (L=80, F=4096, H=E=1000, V=12000), B = 128, width 5, depth 30, one seeded model;
 beam_constrained(no_repeat_ngram_size=3, repetition_penalty=1.2, min_length=5, 2 banned ids) against mode='beam'.  The two share

@@ -1,4 +1,4 @@
-"""Cost of a depth of the cumulative-score beam search (mode='beam', csrc/beam_cum.hip) beside the reference's search
+"""Cost of a depth of the cumulative-score beam search (mode='beam', csrc/beam_policy.hip) beside the reference's search
 (mode='beam_search', csrc/beam_queue.hip), in one process on one MI355X: config 5 dims (L=80, F=4096, H=E=1000, V=12000), B = 128,
 width 5, depth 30, one seeded model.  The two share the encoder, the depth step and the depth loop, so the ratio of their times
 per depth isolates the policy kernel and the driver.  The legs ALTERNATE call by call; a call is timed with HIP events on the

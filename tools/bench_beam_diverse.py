@@ -1,8 +1,8 @@
-"""Cost of diverse (group) beam search (S2VT.beam_diverse; csrc/beam_div.hip) beside the cumulative-score search (mode='beam') at
+"""Cost of diverse (group) beam search (S2VT.beam_diverse; csrc/beam_policy.hip) beside the cumulative-score search (mode='beam') at
 the same width in one process on one MI355X.
 Whole search: config 5 dims (L=80, F=4096, H=E=1000, V=12000), B = 128, depth 30, one seeded model; beam_diverse(beam_width=6,
 num_groups=3, diversity_lambda=0.5) against mode='beam' at beam_width=6.  The two share the encoder, the depth loop and every launch
-of a depth but the policy kernel.  The legs ALTERNATE call by call; a call is timed with HIP events on the stream, and its time per
+of a depth, the policy kernel included (one group against three).  The legs ALTERNATE call by call; a call is timed with HIP events on the stream, and its time per
 depth is the call time / the depths that call actually ran (beam.LAST_DEPTHS).  The diverse search runs until the SLOWEST group of a
 sample has settled, so it may run more depths than mode='beam': the depths run are printed beside the times.  Median and spread
 over --calls calls per leg after --warmup calls of each.
