@@ -18,6 +18,11 @@ tie), and all G with their scores (null for one that is not finite) go to <out>.
 --ensemble PATH[,PATH...] [--ensemble-weights w0,w1,...] (with --beam N --beam-mode cumulative) decodes with --model-path and the
 further checkpoints as ONE search over the weighted mean of their word distributions (S2VTModel.Ensemble, not in the reference); the
 first weight is --model-path's.  The constraint flags and --n-best compose with it.
+--consensus (with --sample K, K >= 2; --beam N --beam-mode cumulative --n-best n, n >= 2, also under --ensemble; or --beam-groups G,
+G >= 2; not in the reference) chooses among a clip's candidates the one that agrees most with the others under CIDEr-D with the
+training split's idf (consensus / minimum-Bayes-risk selection, consensus.select on the device) and writes {video_id: {"chosen",
+"utility", "captions"}} to <out>.consensus.json: with a beam search the choice is the prediction, with --sample the greedy
+predictions stay.  Without the flag every file is what it was.
 """
 import argparse
 import json
@@ -144,6 +149,75 @@ def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=
     return out
 
 
+def consensus_captions(model_path, caption_file, feats_path, source, batch_size=10, split='test', device=None, constraints=None,
+                       n_samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, beam_width=5, max_beam_depth=30, length_alpha=0.7,
+                       n_best=1, beam_groups=0, diversity_lambda=0.5, ensemble_paths=None, ensemble_weights=None):
+    """--consensus: per clip of a split the candidate caption that agrees most with the clip's other candidates under CIDEr-D
+    (consensus.select: one kernel call per batch, the ids never leave the device before the choice is made), with the document
+    frequencies of the caption file's TRAINING split - a DeviceCiderRewarder built the way train.py builds --sc-reward device's.
+    source names the candidates, produced exactly as sample_captions / generate produce them: 'sample' the n_samples draws of
+    S2VT.sample_truncated (batch i with seed + i), 'nbest' the n_best list of the cumulative beam search (plain, constrained or the
+    ensemble's), 'groups' the group-best captions of S2VT.beam_diverse.  A candidate whose score is not finite is not a candidate.
+    -> (preds {video_id: chosen caption}, detail {video_id: {"chosen": k, "utility": [...], "captions": [...]}} - the utility of a
+    candidate that is not valid: null -, scores {video_id: [the candidates' search scores]}, None for 'sample')."""
+    import math
+    import dataloader
+    from s2vt_video_caption_amd import consensus
+    from s2vt_video_caption_amd.self_critical import DeviceCiderRewarder
+    if source not in ('sample', 'nbest', 'groups'):
+        raise ValueError("consensus_captions: source must be 'sample', 'nbest' or 'groups', got %r" % (source,))
+    dev = device or torch.device('cuda', 0)
+    dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
+    loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
+    trainset = dataloader.VideoDataset(caption_file, feats_path, mode='train')
+    sos, eos = dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
+    rewarder = DeviceCiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, device=dev,
+                                   vocab_size=len(dataset.word2ix))
+    model = torch.load(model_path, weights_only=False).to(dev)
+    model.eval()
+    if source != 'sample':
+        model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', sos, eos
+    con = constraint_kwargs(constraints, dataset.word2ix, model)
+    ensemble = None
+    if ensemble_paths:
+        if source != 'nbest':
+            raise ValueError("ensemble_paths apply to source 'nbest'")
+        import S2VTModel
+        members = [model] + [torch.load(p, weights_only=False).to(dev).eval() for p in ensemble_paths]
+        for m in members[1:]:
+            m.rnn_type, m.sos_ix, m.eos_ix = model.rnn_type, model.sos_ix, model.eos_ix
+        ensemble = S2VTModel.Ensemble(members, ensemble_weights)
+    preds, detail, all_scores = {}, {}, (None if source == 'sample' else {})
+    with torch.no_grad():
+        for i, (feats, targets, ids, masks) in enumerate(dataloader.feed_batches(loader, dev)):
+            scores = None
+            if source == 'sample':
+                draw = model.decode_constrained if con else model.sample_truncated
+                cands = draw(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k, top_p=top_p, **con)
+            elif source == 'groups':
+                cands, _, scores = model.beam_diverse(feats, beam_width=beam_width, num_groups=beam_groups, diversity_lambda=diversity_lambda,
+                                                      max_beam_depth=max_beam_depth, length_alpha=length_alpha, n_best=1, **con)
+                cands, scores = cands[:, :, 0], scores[:, :, 0]
+            else:
+                kw = dict(beam_width=beam_width, max_beam_depth=max_beam_depth, length_alpha=length_alpha, n_best=n_best)
+                if ensemble is not None:
+                    cands, _, scores = ensemble.beam(feats, **kw, **con)
+                elif con:
+                    cands, _, scores = model.beam_constrained(feats, **kw, **con)
+                else:
+                    cands, _, scores = model(feats, mode='beam', **kw)
+            _, best, utility = consensus.select(rewarder, cands, scores)
+            rows, best, utility = cands.cpu().tolist(), best.cpu().tolist(), utility.cpu().tolist()
+            scores = None if scores is None else scores.cpu().tolist()
+            for b, vid in enumerate(ids):
+                caps = [ids_to_caption(r, dataset.ix2word) for r in rows[b]]
+                preds[vid] = caps[best[b]]
+                detail[vid] = {"chosen": best[b], "utility": [u if math.isfinite(u) else None for u in utility[b]], "captions": caps}
+                if scores is not None:
+                    all_scores[vid] = scores[b]
+    return preds, detail, all_scores
+
+
 def pack_references(ref_lists, eos_ix, max_len):
     """The reference captions of a batch of clips as ONE mode='score' input: ref_lists = per clip its token lists (<sos>, words,
     <eos>, as dataloader.VideoDataset.captions holds them), cut at max_len.  -> (int64 [B, K, T], counts): K = the most references
@@ -253,6 +327,12 @@ def build_parser():
                     help="greedy, --sample and --beam-mode cumulative: divide the positive logits of the words generated so far by THETA, multiply the others (1: off)")
     ap.add_argument("--min-length", type=int, default=0, metavar="M", help="greedy, --sample and --beam-mode cumulative: no <eos> among the first M words")
     ap.add_argument("--ban-words", default="", metavar="W1,W2", help="greedy, --sample and --beam-mode cumulative: words that are never generated, e.g. \"<unk>,<pad>\"")
+    ap.add_argument("--consensus", action="store_true",
+                    help="with --sample K (K >= 2), --beam N --beam-mode cumulative --n-best n (n >= 2; also under --ensemble) or "
+                         "--beam-groups G (G >= 2): choose among the clip's candidates the one that agrees most with the others under "
+                         "CIDEr-D (consensus / minimum-Bayes-risk selection on the device, consensus.select; idf of the training split) "
+                         "and write {video_id: {chosen, utility, captions}} to <out>.consensus.json.  With a beam search the choice is "
+                         "the prediction; with --sample the greedy predictions stay as they are")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
     return ap
@@ -293,6 +373,14 @@ def main(argv=None):
                 ap.error("--ensemble-weights: numbers separated by commas, got %r" % a.ensemble_weights)
             if len(ens_weights) != len(ens_paths) + 1:
                 ap.error("--ensemble-weights: %d weights for %d models (--model-path's comes first)" % (len(ens_weights), len(ens_paths) + 1))
+    cons_source = None
+    if a.consensus:
+        sources = [s for s, on in (("sample", a.sample >= 2), ("groups", a.beam_groups >= 2),
+                                   ("nbest", bool(a.beam) and a.beam_mode == "cumulative" and not a.beam_groups and a.n_best >= 2)) if on]
+        if len(sources) != 1 or a.perplexity:
+            ap.error("--consensus chooses among the candidates of exactly one of --sample K (K >= 2), --beam N --beam-mode cumulative "
+                     "--n-best n (n >= 2) and --beam-groups G (G >= 2), and not with --perplexity")
+        cons_source = sources[0]
     if a.perplexity:
         per_clip, summary = reference_logliks(a.model_path, a.caption_file, a.feats_path, a.batch_size)
         print("total log-likelihood {total_loglik:.4f} over {tokens} tokens: per-word perplexity {perplexity:.4f}, "
@@ -305,10 +393,25 @@ def main(argv=None):
     groups = {} if a.beam_groups else None
     diverse = dict(beam_groups=a.beam_groups, diversity_lambda=0.5 if a.diversity_lambda is None else a.diversity_lambda,
                    groups=groups) if a.beam_groups else {}
-    preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
-                     ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
-                     length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints,
-                     **diverse, **(dict(ensemble_paths=ens_paths, ensemble_weights=ens_weights) if ens_paths else {}))
+    cons = None
+    if cons_source in ("nbest", "groups"):
+        # the search's candidates, the consensus choice as the prediction; the n-best / groups files as without the flag
+        import math
+        preds, cons, cand_scores = consensus_captions(
+            a.model_path, a.caption_file, a.feats_path, cons_source, a.batch_size, constraints=constraints, beam_width=a.beam,
+            length_alpha=a.length_alpha, n_best=a.n_best, beam_groups=a.beam_groups,
+            diversity_lambda=0.5 if a.diversity_lambda is None else a.diversity_lambda, ensemble_paths=ens_paths or None,
+            ensemble_weights=ens_weights)
+        if nbest is not None:
+            nbest.update({v: d["captions"] for v, d in cons.items()})
+        if groups is not None:
+            groups.update({v: [{"caption": c, "score": x if math.isfinite(x) else None} for c, x in zip(d["captions"], cand_scores[v])]
+                           for v, d in cons.items()})
+    else:
+        preds = generate(a.model_path, a.caption_file, a.feats_path, a.batch_size,
+                         ('beam' if cumulative else 'beam_search') if a.beam else 'test', beam_width=a.beam or 5,
+                         length_alpha=a.length_alpha, n_best=a.n_best if cumulative else 1, nbest=nbest, constraints=constraints,
+                         **diverse, **(dict(ensemble_paths=ens_paths, ensemble_weights=ens_weights) if ens_paths else {}))
     with open(a.out, 'w', encoding='utf-8') as f:
         json.dump(preds, f, ensure_ascii=False, indent=1)
     print("wrote {} captions to {}".format(len(preds), a.out))
@@ -319,11 +422,21 @@ def main(argv=None):
         with open(a.out + ".groups.json", 'w', encoding='utf-8') as f:
             json.dump(groups, f, ensure_ascii=False, indent=1)
     if a.sample > 0:
-        samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
-                                  a.sample_seed, constraints=constraints)
+        if cons_source == "sample":            # the same draws, kept on the device for the choice; the predictions above stay greedy
+            _, cons, _ = consensus_captions(a.model_path, a.caption_file, a.feats_path, "sample", a.batch_size, constraints=constraints,
+                                            n_samples=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed)
+            samples = {v: d["captions"] for v, d in cons.items()}
+        else:
+            samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
+                                      a.sample_seed, constraints=constraints)
         with open(a.out + ".samples.json", 'w', encoding='utf-8') as f:
             json.dump(samples, f, ensure_ascii=False, indent=1)
         print("wrote {} sampled captions per clip to {}".format(a.sample, a.out + ".samples.json"))
+    if cons is not None:
+        with open(a.out + ".consensus.json", 'w', encoding='utf-8') as f:
+            json.dump(cons, f, ensure_ascii=False, indent=1)
+        print("wrote the consensus choice among {} candidates per clip to {}".format(
+            len(next(iter(cons.values()))["captions"]) if cons else 0, a.out + ".consensus.json"))
     if a.gts:
         scorer = score(preds, a.gts)
         print("***********************")

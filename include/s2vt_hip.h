@@ -406,6 +406,29 @@ typedef struct s2vt_cider_table {
  * s2vt_check_async_error / a later call. */
 int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, const int64_t* ids, int32_t B, int32_t T, int64_t ld,
                        int32_t sos, int32_t eos, double* out, void* stream);
+/* Consensus (minimum-Bayes-risk) selection among the K candidate captions of each of B clips: ids int64 [B*K, T], rows r = b*K + k
+ * with row stride ld >= T; valid uint8 [B*K] or NULL (every candidate valid).  With words_k = strip_caption(row k) and vec_k =
+ * cider_vector(ngrams(words_k, 4), df, log_n) - df / log_n of the table's training split; the clips themselves need not be in it -
+ * and Vb the valid candidates of clip b:
+ *   utility[b*K + i] = cider_of_vectors(vec_i, [vec_j for j ascending, j in Vb, j != i], 4, sigma)   for i in Vb (0.0 when i is alone)
+ *                    = -inf                                                                           for i not in Vb
+ *   best[b]          = the smallest i in Vb whose utility is the maximum, 0 when Vb is empty
+ * i.e. CIDEr-D of candidate i with the other candidates as its references: the clipped product min(w_i, w_j) * w_j per order, divided
+ * by both norms where both are non-zero, times the length penalty pen[|bigrams_i - bigrams_j|], the pairs' terms added in ascending j
+ * from 0.0 per order, mean over the orders and the others, x10.  A candidate without words has all norms zero and utility 0.0.
+ * fp64 in a fixed order, no floating-point atomics: a clip's result does not depend on the rest of the batch, and the same inputs
+ * give the same bits on every call.  Of the table only idf_keys, idf_vals, n_idf, log_n, pen and n_pen are read.
+ * 1 <= K <= S2VT_CONSENSUS_MAX_K, 1 <= T <= S2VT_CIDER_MAX_T; null pointers, bad dims, a workspace below
+ * s2vt_cider_consensus_workspace_bytes(B, K, T) (0 for bad dims) or an incomplete table: S2VT_ERR_ARG before any launch.  A row that
+ * is not valid is not read.  A token outside [0, 65535] before the first eos of a valid row is never used as an index: the row is
+ * scored without it and the call is reported as S2VT_ERR_INDEX by s2vt_check_async_error / a later call, as for s2vt_cider_rewards;
+ * other clips are untouched.  Three launches: the candidate phase of s2vt_cider_rewards per row into the workspace's slots, one
+ * workgroup per (clip, candidate) over the pairs, one wavefront per clip for the arg-max. */
+#define S2VT_CONSENSUS_MAX_K 64
+size_t s2vt_cider_consensus_workspace_bytes(int32_t B, int32_t K, int32_t T);
+int s2vt_cider_consensus(const s2vt_cider_table* table, const int64_t* ids, int32_t B, int32_t K, int32_t T, int64_t ld,
+                         int32_t sos, int32_t eos, const uint8_t* valid, double* utility, int32_t* best,
+                         void* workspace, size_t workspace_bytes, void* stream);
 /* What the self-critical step feeds the train step (self_critical.advantage_weights and the <sos> column, on the device):
  * caps int64 [B, T+1] = sos || sampled (int64 [B, T], contiguous); weight fp32 [B, T+1] = fp32(r_sample[b] - r_greedy[b]) - the
  * fp64 difference rounded once - on positions 1 .. the first eos of the row inclusive (all T without one), zero elsewhere. */

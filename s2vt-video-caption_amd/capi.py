@@ -58,6 +58,7 @@ class Constraints(ctypes.Structure):
 
 
 CIDER_MAX_T = 512        # S2VT_CIDER_MAX_T of include/s2vt_hip.h
+CONSENSUS_MAX_K = 64     # S2VT_CONSENSUS_MAX_K
 GRAD_NORM_CHUNK = 16384  # S2VT_GRAD_NORM_CHUNK: gradient elements per fp64 partial of s2vt_grad_norm
 ADAM_MAX_SEGMENTS = 16   # S2VT_ADAM_MAX_SEGMENTS
 
@@ -266,6 +267,10 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p]),
     "s2vt_cider_rewards": (c_int32, [POINTER(CiderTable), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
                                      c_void_p]),
+    # consensus (MBR) selection among K candidates per clip (consensus.select; csrc/cider.hip)
+    "s2vt_cider_consensus_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_cider_consensus": (c_int32, [POINTER(CiderTable), c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_sc_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "s2vt_sc_weights_group": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),

@@ -1,6 +1,7 @@
 // Self-critical rewards on the device (train.py --sc-reward device): CIDEr of a batch of id rows against a reference table that
 // self_critical.DeviceCiderRewarder builds once (s2vt_cider_table of include/s2vt_hip.h), and the <sos>-prefixed captions and
-// advantage weights the train step takes.  fp64 throughout; every factor that needs log / exp comes precomputed from the host, so
+// advantage weights the train step takes; and consensus (MBR) selection among the K candidates of a clip (consensus.select,
+// eval.py --consensus), the same score with the clip's other candidates as the references.  fp64 throughout; every factor that needs log / exp comes precomputed from the host, so
 // the kernels only add, multiply, divide, take sqrt and min - in a fixed order, without floating-point atomics.
 #include "api_internal.h"
 
@@ -36,27 +37,27 @@ __device__ __forceinline__ double cider_wave_sum(double v) {
     return v;
 }
 
-// One workgroup = one candidate row.
-__global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider_table tb, const int32_t* clip_rows, const int64_t* ids,
-                                                                      int T, int64_t ld, int sos, int eos, double* out, int* err) {
-    __shared__ int32_t words[kCiderMaxT];
-    __shared__ uint64_t keys[kCiderMaxN];
-    __shared__ double wts[kCiderMaxN];            // tf * idf at the first entry of a run of equal keys, 0 elsewhere
-    __shared__ int s_m;
-    __shared__ double s_hn[4];
-    __shared__ double s_tot[kCiderThreads / 64][4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int crow = clip_rows[b];
-    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
-        if (tid == 0) {
-            atomicExch(err, 2);
-            out[b] = 0.0;
-        }
-        return;
-    }
+// What the candidate phase leaves in LDS: the sorted 1..4-gram keys of a row, tf * idf at the first entry of every run of equal keys
+// (0 elsewhere), the norm per order.  34 KB of the 160 KB a workgroup may use.
+struct CiderRowLds {
+    int32_t words[kCiderMaxT];
+    uint64_t keys[kCiderMaxN];
+    double wts[kCiderMaxN];
+    double hn[4];
+    int m;
+};
+struct CiderRow { int total, n2; };               // entries of keys / wts in use; the scorer's length (the number of bigrams)
+
+// The candidate phase of one id row, by the whole workgroup (every thread calls it; it holds barriers and ends behind one): strip,
+// keys, sort, run heads carrying tf * idf, per-order norms.  cider_rewards_kernel and the consensus kernels share it.
+__device__ __forceinline__ CiderRow cider_candidate(const s2vt_cider_table& tb, const int64_t* row, int T, int sos, int eos,
+                                                    CiderRowLds& L, int* err) {
+    int32_t* words = L.words;
+    uint64_t* keys = L.keys;
+    double* wts = L.wts;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // ---- the words of the row (strip_caption): one wavefront walks it in chunks of 64 and compacts with ballots
     if (wave == 0) {
-        const int64_t* row = ids + (int64_t)b * ld;
         int m = 0;
         bool bad = false;
         for (int base = 0; base < T; base += 64) {
@@ -73,10 +74,10 @@ __global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider
             if (eosm) break;
         }
         if (__ballot(bad) && lane == 0) atomicExch(err, 2);
-        if (lane == 0) s_m = m;
+        if (lane == 0) L.m = m;
     }
     __syncthreads();
-    const int m = s_m;
+    const int m = L.m;
     const int n1 = m, n2 = m > 1 ? m - 1 : 0, n3 = m > 2 ? m - 2 : 0, n4 = m > 3 ? m - 3 : 0;
     const int total = n1 + n2 + n3 + n4;
     int N = 1;
@@ -134,9 +135,31 @@ __global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider
             if (w != 0.0 && cider_key_order(keys[i]) == wave + 1) s += w * w;
         }
         s = cider_wave_sum(s);
-        if (lane == 0) s_hn[wave] = sqrt(s);
+        if (lane == 0) L.hn[wave] = sqrt(s);
     }
     __syncthreads();
+    return CiderRow{total, n2};
+}
+
+// One workgroup = one candidate row.
+__global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider_table tb, const int32_t* clip_rows, const int64_t* ids,
+                                                                      int T, int64_t ld, int sos, int eos, double* out, int* err) {
+    __shared__ CiderRowLds L;
+    __shared__ double s_tot[kCiderThreads / 64][4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int crow = clip_rows[b];
+    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) {
+            atomicExch(err, 2);
+            out[b] = 0.0;
+        }
+        return;
+    }
+    const CiderRow cr = cider_candidate(tb, ids + (int64_t)b * ld, T, sos, eos, L, err);
+    const int total = cr.total, n2 = cr.n2;
+    const uint64_t* keys = L.keys;
+    const double* wts = L.wts;
+    const double* s_hn = L.hn;
     // ---- against the references of the clip: wavefront w takes references w, w + 4, ..; its lanes share the n-grams
     const int r0 = tb.clip_ref_off[crow], r1 = tb.clip_ref_off[crow + 1];
     double tot0 = 0.0, tot1 = 0.0, tot2 = 0.0, tot3 = 0.0;
@@ -186,6 +209,139 @@ __global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider
         const double mean = (((t[0] + t[1]) + t[2]) + t[3]) / 4.0;
         out[b] = mean / (double)(r1 - r0) * 10.0;
     }
+}
+
+// ---------------------------------------------------------------- consensus (MBR) selection among the K candidates of a clip
+// s2vt_cider_consensus in three launches over a per-call workspace of fixed-size slots, one per candidate row r = b * K + k:
+//   keys / wts [R][slot]   the row's sorted keys and run-head weights as cider_candidate leaves them (slot = 4 T >= total entries)
+//   norm [R][4], meta [R][2] = {total, n2}
+// The lookup of a key in another candidate's slot is a lower bound over ALL its entries: equal keys are adjacent, the lower bound
+// is the run's head, which carries the weight; a key names its own order, so the orders need no segments of their own.
+struct ConsensusWs { uint64_t* keys; double* wts; double* norm; int32_t* meta; int64_t slot; };
+
+// Phase 1.  One workgroup = one candidate row; a row that is not valid is not read (its meta says "no entries").
+__global__ __launch_bounds__(kCiderThreads) void consensus_candidate_kernel(s2vt_cider_table tb, const int64_t* ids, int T, int64_t ld,
+                                                                            int sos, int eos, const uint8_t* valid, ConsensusWs ws,
+                                                                            int* err) {
+    __shared__ CiderRowLds L;
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (valid && !valid[r]) {                     // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) ws.meta[2 * r] = ws.meta[2 * r + 1] = 0;
+        return;
+    }
+    const CiderRow cr = cider_candidate(tb, ids + r * ld, T, sos, eos, L, err);
+    uint64_t* keys = ws.keys + r * ws.slot;
+    double* wts = ws.wts + r * ws.slot;
+    for (int i = tid; i < cr.total; i += kCiderThreads) {        // total <= 4 T = slot
+        keys[i] = L.keys[i];
+        wts[i] = L.wts[i];
+    }
+    if (tid < 4) ws.norm[4 * r + tid] = L.hn[tid];
+    if (tid == 0) {
+        ws.meta[2 * r] = cr.total;
+        ws.meta[2 * r + 1] = cr.n2;
+    }
+}
+
+// Phase 2.  One workgroup = one (clip b, candidate i): CIDEr-D of i with the clip's other valid candidates as its references.
+// Wavefront w takes the others j = w, w + 4, ..; its lanes share i's run heads (entry e to lane e mod 64, ascending) and a butterfly
+// closes each per-order sum, as cider_rewards_kernel does against a reference.  The pair's four terms dot / norms * penalty wait in
+// LDS; one thread per order then adds them in ascending j from 0.0 - the host's order over the others - whatever wavefront made them.
+__global__ __launch_bounds__(kCiderThreads) void consensus_pair_kernel(s2vt_cider_table tb, int K, const uint8_t* valid, ConsensusWs ws,
+                                                                       double* utility) {
+    __shared__ uint64_t keys[kCiderMaxN];
+    __shared__ double wts[kCiderMaxN];
+    __shared__ double s_term[S2VT_CONSENSUS_MAX_K][4];
+    __shared__ double s_tot[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t r = blockIdx.x;
+    const int64_t r0 = r - r % K;                 // the clip's first row
+    const int i = (int)(r - r0);
+    if (valid && !valid[r]) {                     // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) utility[r] = -__builtin_inf();
+        return;
+    }
+    const int total = ws.meta[2 * r], n2 = ws.meta[2 * r + 1];
+    for (int e = tid; e < total; e += kCiderThreads) {
+        keys[e] = ws.keys[r * ws.slot + e];
+        wts[e] = ws.wts[r * ws.slot + e];
+    }
+    __syncthreads();
+    const double* hn = ws.norm + 4 * r;
+    for (int j = wave; j < K; j += kCiderThreads / 64) {
+        const int64_t rj = r0 + j;
+        if (j == i || (valid && !valid[rj])) continue;           // (uniform over the wavefront)
+        const uint64_t* jk = ws.keys + rj * ws.slot;
+        const double* jw = ws.wts + rj * ws.slot;
+        const int tj = ws.meta[2 * rj];
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        for (int e = lane; e < total; e += 64) {
+            const double w = wts[e];
+            if (w == 0.0) continue;               // not the head of a run, or idf 0: contributes exactly 0
+            const uint64_t key = keys[e];
+            const int64_t at = cider_find(jk, 0, tj, key);
+            if (at < 0) continue;
+            const double wr = jw[at];
+            const double c = (w < wr ? w : wr) * wr;
+            const int k = cider_key_order(key) - 1;
+            if (k == 0) a0 += c;
+            else if (k == 1) a1 += c;
+            else if (k == 2) a2 += c;
+            else a3 += c;
+        }
+        a0 = cider_wave_sum(a0);
+        a1 = cider_wave_sum(a1);
+        a2 = cider_wave_sum(a2);
+        a3 = cider_wave_sum(a3);
+        int d = n2 - ws.meta[2 * rj + 1];
+        d = d < 0 ? -d : d;
+        const double pen = tb.pen[d < tb.n_pen ? d : tb.n_pen - 1];
+        const double* rn = ws.norm + 4 * rj;
+        if (hn[0] != 0.0 && rn[0] != 0.0) a0 /= hn[0] * rn[0];
+        if (hn[1] != 0.0 && rn[1] != 0.0) a1 /= hn[1] * rn[1];
+        if (hn[2] != 0.0 && rn[2] != 0.0) a2 /= hn[2] * rn[2];
+        if (hn[3] != 0.0 && rn[3] != 0.0) a3 /= hn[3] * rn[3];
+        if (lane == 0) {
+            s_term[j][0] = a0 * pen;
+            s_term[j][1] = a1 * pen;
+            s_term[j][2] = a2 * pen;
+            s_term[j][3] = a3 * pen;
+        }
+    }
+    __syncthreads();
+    int others = 0;
+    if (tid < 4) {
+        double t = 0.0;
+        for (int j = 0; j < K; ++j) {
+            if (j == i || (valid && !valid[r0 + j])) continue;
+            t += s_term[j][tid];
+            ++others;
+        }
+        s_tot[tid] = t;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const double mean = (((s_tot[0] + s_tot[1]) + s_tot[2]) + s_tot[3]) / 4.0;
+        utility[r] = others ? mean / (double)others * 10.0 : 0.0;
+    }
+}
+
+// Phase 3.  One wavefront = one clip, lane k its candidate k (K <= 64): the smallest valid k whose utility is the maximum, 0 without
+// a valid one.  max is exact in any order; the ballot picks the first lane.
+__global__ __launch_bounds__(64) void consensus_best_kernel(int K, const uint8_t* valid, const double* utility, int32_t* best) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int64_t r = (int64_t)b * K + lane;
+    const bool ok = lane < K && (!valid || valid[r]);
+    const double u = ok ? utility[r] : -__builtin_inf();
+    double m = u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_xor(m, o, 64);
+        m = other > m ? other : m;
+    }
+    const unsigned long long hit = __ballot(ok && u == m);
+    if (lane == 0) best[b] = hit ? __ffsll((long long)hit) - 1 : 0;
 }
 
 // One workgroup = one row of sampled ids.
@@ -280,6 +436,57 @@ int s2vt_cider_rewards(const s2vt_cider_table* table, const int32_t* clip_rows, 
                        (int)eos, out, flags.p);
     S2VT_LAUNCH_CHECK("cider_rewards_kernel");
     // two calls per self-critical step: the ring of records, so that a call never waits for the copy of the one before it
+    return flags.close(st, 3);
+}
+
+// the consensus workspace: keys, wts [R][4 T], norm [R][4], meta [R][2], each part on a 256-byte boundary
+static bool consensus_dims_ok(int32_t B, int32_t K, int32_t T) {
+    return B > 0 && K >= 1 && K <= S2VT_CONSENSUS_MAX_K && T >= 1 && T <= S2VT_CIDER_MAX_T;
+}
+static size_t carve_consensus(int32_t B, int32_t K, int32_t T, void* base, ConsensusWs* ws) {
+    Carver c{static_cast<char*>(base), 0, 0};
+    const size_t R = (size_t)B * (size_t)K, slot = 4 * (size_t)T;
+    ConsensusWs w;
+    w.keys = c.take<uint64_t>(R * slot);
+    w.wts = c.take<double>(R * slot);
+    w.norm = c.take<double>(R * 4);
+    w.meta = c.take<int32_t>(R * 2);
+    w.slot = (int64_t)slot;
+    if (ws) *ws = w;
+    return align_up(c.off, 256);
+}
+
+size_t s2vt_cider_consensus_workspace_bytes(int32_t B, int32_t K, int32_t T) {
+    return consensus_dims_ok(B, K, T) ? carve_consensus(B, K, T, nullptr, nullptr) : 0;
+}
+
+int s2vt_cider_consensus(const s2vt_cider_table* table, const int64_t* ids, int32_t B, int32_t K, int32_t T, int64_t ld, int32_t sos,
+                         int32_t eos, const uint8_t* valid, double* utility, int32_t* best, void* workspace, size_t workspace_bytes,
+                         void* stream) {
+    S2VT_REQUIRE(table && ids && utility && best && workspace, "s2vt_cider_consensus: null argument");
+    S2VT_REQUIRE(consensus_dims_ok(B, K, T) && ld >= T,
+                 "s2vt_cider_consensus: bad dims (B %d, K %d of 1..%d, T %d of 1..%d: the n-gram list in LDS, ld %lld)", (int)B, (int)K,
+                 S2VT_CONSENSUS_MAX_K, (int)T, S2VT_CIDER_MAX_T, (long long)ld);
+    S2VT_REQUIRE((int64_t)B * K <= 0x7FFFFFFF, "s2vt_cider_consensus: B * K = %lld rows, one workgroup each", (long long)B * K);
+    S2VT_REQUIRE(workspace_bytes >= s2vt_cider_consensus_workspace_bytes(B, K, T), "s2vt_cider_consensus: workspace of %zu bytes, %zu needed",
+                 workspace_bytes, s2vt_cider_consensus_workspace_bytes(B, K, T));
+    const s2vt_cider_table& tb = *table;          // the kernels read idf_keys, idf_vals, n_idf, log_n, pen and n_pen alone
+    S2VT_REQUIRE(tb.pen && tb.n_pen > 0 && tb.n_idf >= 0 && (tb.n_idf == 0 || (tb.idf_keys && tb.idf_vals)),
+                 "s2vt_cider_consensus: incomplete table");
+    hipStream_t st = (hipStream_t)stream;
+    ConsensusWs ws;
+    carve_consensus(B, K, T, workspace, &ws);
+    PostedFlags flags;
+    int rc;
+    if ((rc = flags.open(st))) return rc;
+    const unsigned R = (unsigned)((int64_t)B * K);
+    hipLaunchKernelGGL(consensus_candidate_kernel, dim3(R), dim3(kCiderThreads), 0, st, tb, ids, (int)T, ld, (int)sos, (int)eos, valid, ws,
+                       flags.p);
+    S2VT_LAUNCH_CHECK("consensus_candidate_kernel");
+    hipLaunchKernelGGL(consensus_pair_kernel, dim3(R), dim3(kCiderThreads), 0, st, tb, (int)K, valid, ws, utility);
+    S2VT_LAUNCH_CHECK("consensus_pair_kernel");
+    hipLaunchKernelGGL(consensus_best_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)K, valid, utility, best);
+    S2VT_LAUNCH_CHECK("consensus_best_kernel");
     return flags.close(st, 3);
 }
 

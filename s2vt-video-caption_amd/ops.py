@@ -949,6 +949,39 @@ def cider_rewards(table, clip_rows, ids, sos_ix, eos_ix):
     return out
 
 
+def cider_consensus(table, ids, sos_ix, eos_ix, valid=None):
+    """(best int64 [B], utility fp64 [B, K]) on the device, no synchronisation: consensus (MBR) selection among the K candidate rows of
+    each clip under CIDEr-D with the table's idf - s2vt_cider_consensus (the definition is in include/s2vt_hip.h).  ids HIP int64
+    [B, K, T]: a last stride other than 1 means a contiguous copy, a row-strided view (one stride from row b*K + k to the next) is
+    taken as it is.  valid: bool / uint8 [B, K] on the device or None (all valid); a candidate that is not valid gets -inf and is
+    nobody's reference.  A token outside [0, 65535] raises IndexError at the next capi.check_async_error()."""
+    lib = capi.load()
+    require_hip(ids, "ids")
+    if ids.dim() != 3 or ids.shape[0] < 1:
+        raise capi.S2VTHipError("cider_consensus: ids [B, K, T] expected, got %s" % (tuple(ids.shape),))
+    B, K, T = ids.shape
+    if not 1 <= K <= capi.CONSENSUS_MAX_K:
+        raise ValueError("cider_consensus: %d candidates per clip; 1..%d are supported" % (K, capi.CONSENSUS_MAX_K))
+    if not 1 <= T <= capi.CIDER_MAX_T:
+        raise ValueError("cider_consensus: rows of %d ids; the kernel's n-gram list in LDS holds rows of 1..%d" % (T, capi.CIDER_MAX_T))
+    if ids.dtype != torch.int64 or ids.stride(2) != 1 or ids.stride(1) < T or ids.stride(0) != K * ids.stride(1):
+        ids = ids.long().contiguous()
+    dev = ids.device
+    if valid is not None:
+        require_hip(valid, "valid")
+        if tuple(valid.shape) != (B, K) or valid.dtype not in (torch.bool, torch.uint8):
+            raise capi.S2VTHipError("cider_consensus: valid must be bool / uint8 [B, K] = [%d, %d]" % (B, K))
+        valid = valid.to(torch.uint8).contiguous()
+    with torch.cuda.device(dev):
+        nbytes = lib.s2vt_cider_consensus_workspace_bytes(B, K, T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        utility = torch.empty(B, K, dtype=torch.float64, device=dev)
+        best = torch.empty(B, dtype=torch.int32, device=dev)
+        capi.check(lib.s2vt_cider_consensus(ctypes.byref(table), _ptr(ids), B, K, T, ids.stride(1), int(sos_ix), int(eos_ix), _ptr(valid),
+                                            _ptr(utility), _ptr(best), _ptr(ws), nbytes, _stream(dev)), "s2vt_cider_consensus")
+    return best.long(), utility
+
+
 def sc_weights(sampled, r_sample, r_greedy, sos_ix, eos_ix):
     """(caps int64 [B, T+1] = <sos> || sampled, weight fp32 [B, T+1] = self_critical.advantage_weights(sampled, r_sample - r_greedy,
     eos_ix)) from sampled ids int64 [B, T] and the two fp64 reward vectors [B], all on the device - s2vt_sc_weights."""

@@ -41,6 +41,43 @@ class CiderRewarder(object):
         rows = ids.tolist() if isinstance(ids, torch.Tensor) else ids
         return np.array([self.score(v, r) for v, r in zip(video_ids, rows)])
 
+    def consensus(self, ids, valid=None):
+        """Consensus (minimum-Bayes-risk) selection among the K candidate id rows of each clip, ids [B, K, T] (host tensor, array or
+        nested lists), valid bool [B, K] or None (all valid): numpy (best int64 [B], utility float64 [B, K]).  utility[b, i] is the
+        CIDEr of candidate i against the clip's OTHER valid candidates, in ascending order, as its references - cider_of_vectors
+        with the document frequencies of this rewarder's split; 0.0 when it has no other, -inf where i is not valid.  best[b] is the
+        smallest valid i whose utility is the maximum, 0 without a valid candidate.  The clips need not be of the split."""
+        rows, valid = _consensus_args(ids, valid)
+        B, K = valid.shape
+        best, utility = np.zeros(B, dtype=np.int64), np.full((B, K), -np.inf, dtype=np.float64)
+        for b in range(B):
+            vecs = [cider_vector(ngrams(strip_caption(rows[b][k], self.sos_ix, self.eos_ix), self.n), self.df, self.log_n, self.n)
+                    if valid[b, k] else None for k in range(K)]
+            for i in range(K):
+                if valid[b, i]:
+                    others = [vecs[j] for j in range(K) if valid[b, j] and j != i]
+                    utility[b, i] = float(cider_of_vectors(vecs[i], others, self.n, self.sigma)) if others else 0.0
+            best[b] = _first_best(utility[b], valid[b])
+        return best, utility
+
+
+def _consensus_args(ids, valid):
+    """(rows as nested lists [B][K][T], valid bool [B, K]) of the arguments of a consensus call"""
+    rows = ids.tolist() if isinstance(ids, (torch.Tensor, np.ndarray)) else ids
+    B, K = len(rows), len(rows[0]) if len(rows) else 0
+    if B < 1 or K < 1 or any(len(r) != K for r in rows):
+        raise ValueError("consensus: ids must be [B, K, T] with B, K >= 1")
+    valid = np.ones((B, K), dtype=bool) if valid is None else np.asarray(valid.cpu() if isinstance(valid, torch.Tensor) else valid).astype(bool)
+    if valid.shape != (B, K):
+        raise ValueError("consensus: valid must be [B, K] = [%d, %d], got %s" % (B, K, valid.shape))
+    return rows, valid
+
+
+def _first_best(utility, valid):
+    """the smallest valid index whose utility is the maximum over the valid ones; 0 where none is valid"""
+    ix = np.nonzero(valid)[0]
+    return int(ix[np.argmax(utility[ix])]) if len(ix) else 0
+
 
 def advantage_weights(sampled, advantage, eos_ix):
     """weight fp32 [B, L] for RewardCriterion from sampled ids [B, L-1] (host tensor) and one advantage per row: the advantage on
@@ -119,7 +156,8 @@ class DeviceCiderRewarder(object):
       ref_norm [4 * n_refs], ref_len [n_refs], pen [n_pen]
 
     `host` keeps the numpy copies (table_walk scores from them without a GPU); `device` uploads them at construction,
-    otherwise the first rewards() call uploads to the device of its ids."""
+    otherwise the first rewards() / consensus() call uploads to the device of its ids.  consensus() (s2vt_cider_consensus) scores the
+    K candidates of a clip against each other instead of the references and reads only idf_keys, idf_vals and pen of the table."""
 
     def __init__(self, captions, video_ids, sos_ix, eos_ix, n=4, sigma=6.0, device=None, vocab_size=None):
         if n != KEY_TOKENS:
@@ -185,8 +223,18 @@ class DeviceCiderRewarder(object):
         clip_rows = torch.tensor(rows, dtype=torch.int32).to(ids.device, non_blocking=True)
         return ops.cider_rewards(self._dev[2], clip_rows, ids, self.sos_ix, self.eos_ix)
 
-    def table_walk(self, video_id, tokens):
-        """the kernel's walk over the flat arrays in numpy (float64), on the host copy: what s2vt_cider_rewards computes for one row"""
+    def consensus(self, ids, valid=None):
+        """(best int64 [B], utility fp64 [B, K]) HIP tensors: CiderRewarder.consensus on the device (ops.cider_consensus) for ids HIP
+        int64 [B, K, T] and valid bool [B, K] on the device or None.  No host work beyond the first call's upload of the table."""
+        from . import ops
+        from .functional import require_hip
+        require_hip(ids, "ids")
+        if self._dev is None or self._dev[0] != ids.device:
+            self._upload(ids.device)
+        return ops.cider_consensus(self._dev[2], ids, self.sos_ix, self.eos_ix, valid)
+
+    def _row_walk(self, tokens):
+        """the candidate phase of the kernels in numpy: (unique keys ascending, tf * idf, order of each key, norm per order, bigrams)"""
         h = self.host
         words = strip_caption(tokens, self.sos_ix, self.eos_ix)
         keys = np.array([pack_key(words[i:i + k]) for k in range(1, self.n + 1) for i in range(len(words) - k + 1)], dtype=np.uint64)
@@ -198,7 +246,44 @@ class DeviceCiderRewarder(object):
             hit = at[i] < len(h["idf_keys"]) and h["idf_keys"][at[i]] == uniq[i]
             w[i] = float(tf[i]) * (h["idf_vals"][at[i]] if hit else self.log_n)
         hn = [np.sqrt(sum(x * x for x in w[order == k + 1])) for k in range(self.n)]
-        hl = max(len(words) - 1, 0)
+        return uniq, w, order, hn, max(len(words) - 1, 0)
+
+    def consensus_walk(self, rows, valid=None):
+        """s2vt_cider_consensus' walk for ONE clip in numpy (float64), on the host copy of the table: rows = its K id rows, valid =
+        K flags or None -> (best, utility float64 [K]).  Every candidate is a sorted key list with weights; a pair (i, j) looks i's
+        keys up in j's list; the pairs' terms are added per order in ascending j."""
+        h = self.host
+        K = len(rows)
+        valid = np.ones(K, dtype=bool) if valid is None else np.asarray(valid).astype(bool)
+        cand = [self._row_walk(r) if valid[k] else None for k, r in enumerate(rows)]
+        utility = np.full(K, -np.inf, dtype=np.float64)
+        for i in range(K):
+            if not valid[i]:
+                continue
+            uniq, w, order, hn, hl = cand[i]
+            total, others = np.zeros(self.n), 0
+            for j in range(K):
+                if j == i or not valid[j]:
+                    continue
+                jk, jw, _, jn, jl = cand[j]
+                pen = h["pen"][abs(hl - jl)]
+                dot = np.zeros(self.n)
+                for e in np.nonzero(w != 0.0)[0]:
+                    at = int(np.searchsorted(jk, uniq[e]))
+                    if at < len(jk) and jk[at] == uniq[e]:
+                        dot[order[e] - 1] += min(w[e], jw[at]) * jw[at]
+                for k in range(self.n):
+                    if hn[k] != 0 and jn[k] != 0:
+                        dot[k] /= hn[k] * jn[k]
+                    total[k] += dot[k] * pen
+                others += 1
+            utility[i] = float((((total[0] + total[1]) + total[2]) + total[3]) / 4.0 / others * 10.0) if others else 0.0
+        return _first_best(utility, valid), utility
+
+    def table_walk(self, video_id, tokens):
+        """the kernel's walk over the flat arrays in numpy (float64), on the host copy: what s2vt_cider_rewards computes for one row"""
+        h = self.host
+        uniq, w, order, hn, hl = self._row_walk(tokens)
         c = self.row_of[video_id]
         r0, r1 = int(h["clip_ref_off"][c]), int(h["clip_ref_off"][c + 1])
         total = np.zeros(self.n)
