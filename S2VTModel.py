@@ -324,6 +324,42 @@ class S2VT(nn.Module):
                                   diversity_lambda=diversity_lambda, max_depth=max_beam_depth, length_alpha=length_alpha, n_best=n_best,
                                   constraints=spec)
 
+    @torch.no_grad()
+    def sample_distinct(self, feats, n_samples=5, temperature=1.0, seed=None, max_depth=30):
+        """Stochastic beam search (Kool, van Hoof, Welling, ICML 2019; not in the reference): n_samples captions per clip that are
+        guaranteed PAIRWISE DISTINCT - sampled WITHOUT replacement from the model's distribution over whole sentences at
+        `temperature`, in the exact order a sequential without-replacement sampler would draw them.  `sample` draws its K rows
+        independently, and a peaked model returns mostly copies; this returns K different sentences on one encode.  Returns
+        (ids int64 [B, n_samples, max_depth] - the words after <sos>, padded with eos_ix, lengths int64 [B, n_samples] - counting the
+        <eos> where there is one; a sample still unfinished at max_depth has length max_depth and no <eos>, logprobs fp32
+        [B, n_samples] - the sum of the words' log-probs under softmax(logit / temperature), mode='score' with length_alpha=0.0 at
+        temperature 1, perturbed fp32 [B, n_samples] - the samples' perturbed scores G, non-increasing along a clip's row and <= 0,
+        kappa fp32 [B] - the largest perturbed score that was NOT kept, <= perturbed[:, -1]: the threshold of the inclusion
+        probabilities q = exp(-exp(kappa - logprob)) of importance-weighted estimators) on the device; no host synchronisation.
+        The search (include/s2vt_hip.h "stochastic beam") is beam-shaped: mode='beam''s encoder states, decode
+        cache and depth step over the rows b * n_samples + slot; the fan-out head ranks a row's words by log-prob + Gumbel noise
+        (csrc/gumbel_top.hip; the counter-based noise of mode='sample', keyed by seed, depth, row and word), the policy keeps the
+        n_samples best children by the perturbed score conditioned on their parent's (csrc/sbs_policy.hip, fp64), one launch each per
+        depth.  n_samples = 1 is ancestral sampling: ids[:, 0] are the words of `sample(feats, 1, temperature, seed)` up to the first
+        <eos>, wherever a draw is decided.  Same seed, same weights, same clips -> the same bits.  One-layer LSTM models only (a GRU or
+        stacked model: ValueError naming `sample`).  A method of its own: the parameter lists of forward and sample are fixed.  Not
+        covered: top-k / nucleus truncation and the constraint rules inside this search, GRU, stacked and Att_Baseline models,
+        Ensemble, widths above 8, kappa as a training baseline, dp.py.  No gradient.
+        :param n_samples: an integer in [1, 8]
+        :param temperature: finite and > 0
+        :param seed: None draws a 63-bit seed from torch's default generator, as `sample` does; an int is used as is
+        :param max_depth: an integer >= 1: the most words a sample gets
+        """
+        W, t, s, D = _beam.check_stochastic_args(n_samples, temperature, seed, max_depth, self.vocab_size)
+        if _G.is_gru_model(self):
+            raise ValueError("sample_distinct of a GRU model: the batched depth step is the LSTM's; use sample")
+        if _S.is_stacked_lstm_model(self):
+            raise ValueError("sample_distinct of a stacked model (num_layers > 1): the batched depth step is the one-layer LSTM's; use sample")
+        _F.require_hip(feats, "feats")
+        if feats.dim() != 3 or feats.shape[1] != self.length or feats.shape[2] != self.feat_dim:
+            raise ValueError("feats must be [B, %d, %d], got %s" % (self.length, self.feat_dim, tuple(feats.shape)))
+        return _beam.stochastic(self, self.feat_drop(feats), self._hip_params(), n_samples=W, temperature=t, seed=s, max_depth=D)
+
     def _sample(self, feats, n_samples, temperature, seed, k, p):
         K = _sampling.check_n_samples(n_samples)
         t, s = _sampling.check_sample_args(temperature, seed)

@@ -9,7 +9,8 @@ BLEU-1..4, ROUGE-L, CIDEr.  METEOR and the Stanford tokenizer are Java jars the 
 (`.MISSING_LARGE_BLOBS`); see caption_metrics.py for what stands in for them.  --perplexity scores the split's reference captions
 under the model instead (mode='score', not in the reference): per-word perplexity and per-reference log-likelihoods.
 --sample K additionally writes K sampled captions per clip (S2VT.sample_truncated, not in the reference; --temperature, --top-k, --top-p,
---sample-seed) to <out>.samples.json.  --no-repeat-ngram / --repetition-penalty / --min-length / --ban-words constrain the greedy captions
+--sample-seed) to <out>.samples.json; with --sample-distinct (K <= 8) they are the K pairwise distinct captions of S2VT.sample_distinct
+(stochastic beam search, not in the reference; no truncation, no constraints).  --no-repeat-ngram / --repetition-penalty / --min-length / --ban-words constrain the greedy captions
 and those of --sample (S2VT.decode_constrained, not in the reference) and the search of --beam N --beam-mode cumulative
 (S2VT.beam_constrained); they are refused together with the reference's search (--beam N --beam-mode reference).
 --beam-groups G [--diversity-lambda x] (with --beam N --beam-mode cumulative, N a multiple of G) decodes by diverse beam search
@@ -128,10 +129,21 @@ def constraint_kwargs(constraints, word2ix, model):
     return con
 
 
+def distinct_draw(model, word2ix):
+    """the draw of --sample-distinct as a callable (feats, n_samples, temperature, seed) -> ids [B, n_samples, L-1]: the n_samples
+    pairwise distinct captions of S2VT.sample_distinct (stochastic beam search), at most L-1 words each as the other draws"""
+    if not hasattr(model, "sample_distinct"):
+        raise NotImplementedError("--sample-distinct needs S2VT.sample_distinct; %s has none" % type(model).__name__)
+    model.rnn_type, model.sos_ix, model.eos_ix = 'lstm', word2ix.get('<sos>', 3), word2ix.get('<eos>', 4)      # (as for the beam modes)
+    return lambda feats, n_samples, temperature, seed: model.sample_distinct(feats, n_samples, temperature=temperature, seed=seed,
+                                                                             max_depth=model.length - 1)[0]
+
+
 def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=10, temperature=1.0, top_k=0, top_p=1.0, seed=0,
-                    split='test', device=None, constraints=None):
+                    split='test', device=None, constraints=None, distinct=False):
     """{video_id: [n_samples captions]} of a split, drawn by S2VT.sample_truncated (one encode per clip; top_k / top_p cut every step's
-    distribution, 0 / 1.0: off), each cut at its first <eos> like a greedy caption.  Batch i draws with seed + i."""
+    distribution, 0 / 1.0: off), each cut at its first <eos> like a greedy caption.  Batch i draws with seed + i.  distinct: the
+    n_samples pairwise distinct captions of S2VT.sample_distinct instead (no truncation, no constraints)."""
     import dataloader
     dev = device or torch.device('cuda', 0)
     dataset = dataloader.VideoDataset(caption_file, feats_path, mode=split)
@@ -140,10 +152,14 @@ def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=
     model.eval()
     con = constraint_kwargs(constraints, dataset.word2ix, model)
     draw = model.decode_constrained if con else model.sample_truncated
+    pick = distinct_draw(model, dataset.word2ix) if distinct else None
     out = {}
     with torch.no_grad():
         for i, (feats, targets, ids, masks) in enumerate(dataloader.feed_batches(loader, dev)):
-            drawn = draw(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k, top_p=top_p, **con).cpu().tolist()
+            if pick is not None:
+                drawn = pick(feats, n_samples, temperature, int(seed) + i).cpu().tolist()
+            else:
+                drawn = draw(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k, top_p=top_p, **con).cpu().tolist()
             for vid, rows in zip(ids, drawn):
                 out[vid] = [ids_to_caption(r, dataset.ix2word) for r in rows]
     return out
@@ -151,12 +167,12 @@ def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=
 
 def consensus_captions(model_path, caption_file, feats_path, source, batch_size=10, split='test', device=None, constraints=None,
                        n_samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, beam_width=5, max_beam_depth=30, length_alpha=0.7,
-                       n_best=1, beam_groups=0, diversity_lambda=0.5, ensemble_paths=None, ensemble_weights=None):
+                       n_best=1, beam_groups=0, diversity_lambda=0.5, ensemble_paths=None, ensemble_weights=None, distinct=False):
     """--consensus: per clip of a split the candidate caption that agrees most with the clip's other candidates under CIDEr-D
     (consensus.select: one kernel call per batch, the ids never leave the device before the choice is made), with the document
     frequencies of the caption file's TRAINING split - a DeviceCiderRewarder built the way train.py builds --sc-reward device's.
     source names the candidates, produced exactly as sample_captions / generate produce them: 'sample' the n_samples draws of
-    S2VT.sample_truncated (batch i with seed + i), 'nbest' the n_best list of the cumulative beam search (plain, constrained or the
+    S2VT.sample_truncated (batch i with seed + i; distinct: the pairwise distinct captions of S2VT.sample_distinct), 'nbest' the n_best list of the cumulative beam search (plain, constrained or the
     ensemble's), 'groups' the group-best captions of S2VT.beam_diverse.  A candidate whose score is not finite is not a candidate.
     -> (preds {video_id: chosen caption}, detail {video_id: {"chosen": k, "utility": [...], "captions": [...]}} - the utility of a
     candidate that is not valid: null -, scores {video_id: [the candidates' search scores]}, None for 'sample')."""
@@ -191,7 +207,9 @@ def consensus_captions(model_path, caption_file, feats_path, source, batch_size=
     with torch.no_grad():
         for i, (feats, targets, ids, masks) in enumerate(dataloader.feed_batches(loader, dev)):
             scores = None
-            if source == 'sample':
+            if source == 'sample' and distinct:
+                cands = distinct_draw(model, dataset.word2ix)(feats, n_samples, temperature, int(seed) + i)
+            elif source == 'sample':
                 draw = model.decode_constrained if con else model.sample_truncated
                 cands = draw(feats, n_samples, temperature=temperature, seed=int(seed) + i, top_k=top_k, top_p=top_p, **con)
             elif source == 'groups':
@@ -321,6 +339,9 @@ def build_parser():
     ap.add_argument("--top-p", type=float, default=1.0,
                     help="--sample: draw from the smallest set of most probable words whose mass reaches p (1: off)")
     ap.add_argument("--sample-seed", type=int, default=0, help="--sample: batch i draws with this seed + i")
+    ap.add_argument("--sample-distinct", action="store_true",
+                    help="--sample K (K <= 8): the K captions are pairwise distinct - sampled without replacement by stochastic beam "
+                         "search (S2VT.sample_distinct) at --temperature; not with --top-k, --top-p or the constraint flags")
     ap.add_argument("--no-repeat-ngram", type=int, default=0, metavar="N",
                     help="greedy, --sample and --beam-mode cumulative: never complete an n-gram the caption already holds (0: off)")
     ap.add_argument("--repetition-penalty", type=float, default=1.0, metavar="THETA",
@@ -373,6 +394,12 @@ def main(argv=None):
                 ap.error("--ensemble-weights: numbers separated by commas, got %r" % a.ensemble_weights)
             if len(ens_weights) != len(ens_paths) + 1:
                 ap.error("--ensemble-weights: %d weights for %d models (--model-path's comes first)" % (len(ens_weights), len(ens_paths) + 1))
+    if a.sample_distinct:
+        if not 1 <= a.sample <= 8:
+            ap.error("--sample-distinct needs --sample K with 1 <= K <= 8")
+        if a.top_k != 0 or a.top_p != 1.0 or constraints:
+            ap.error("--sample-distinct samples from the whole distribution: not with --top-k, --top-p, --no-repeat-ngram, "
+                     "--repetition-penalty, --min-length or --ban-words")
     cons_source = None
     if a.consensus:
         sources = [s for s, on in (("sample", a.sample >= 2), ("groups", a.beam_groups >= 2),
@@ -424,11 +451,12 @@ def main(argv=None):
     if a.sample > 0:
         if cons_source == "sample":            # the same draws, kept on the device for the choice; the predictions above stay greedy
             _, cons, _ = consensus_captions(a.model_path, a.caption_file, a.feats_path, "sample", a.batch_size, constraints=constraints,
-                                            n_samples=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed)
+                                            n_samples=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed,
+                                            distinct=a.sample_distinct)
             samples = {v: d["captions"] for v, d in cons.items()}
         else:
             samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
-                                      a.sample_seed, constraints=constraints)
+                                      a.sample_seed, constraints=constraints, distinct=a.sample_distinct)
         with open(a.out + ".samples.json", 'w', encoding='utf-8') as f:
             json.dump(samples, f, ensure_ascii=False, indent=1)
         print("wrote {} sampled captions per clip to {}".format(a.sample, a.out + ".samples.json"))

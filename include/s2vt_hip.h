@@ -1080,6 +1080,64 @@ int s2vt_beam_step_logits(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
                           float* logits_out, int64_t ld_out, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes,
                           void* stream);
 
+/* ---------------------------------------------------------------- stochastic beam: K distinct sampled captions per clip
+ * (S2VT.sample_distinct(feats, n_samples=, temperature=, seed=, max_depth=); Kool, van Hoof, Welling, "Stochastic Beams and Where to
+ * Find Them", ICML 2019; not in the reference; csrc/gumbel_top.hip, csrc/sbs_policy.hip; restated in numpy by tests/sbs_ref.py).
+ * Sampling WITHOUT replacement from the model's distribution over whole sentences: W pairwise distinct captions of a clip, in the exact
+ * order a sequential without-replacement sampler would draw them, with their log-probabilities, their perturbed scores and the
+ * threshold that inclusion probabilities need - in one beam-shaped pass.
+ * Per clip b: W = n_samples slots, 1 <= W <= 8; D = max_depth; inv_t = fp32(1 / temperature); a 64-bit seed.  A slot is empty, live or
+ * finished and carries phi (fp32: the sum of its words' log-probs), G (fp64: its perturbed score), a back-trace node and a length.
+ *   start      slot 0 is live with phi = 0, G = 0, last word <sos> and the encoder state of mode='beam'; the others are empty;
+ *              kappa = -inf.
+ *   depth t = 1..D: the depth step runs over the fixed rows r = b * W + slot, as in mode='beam'.  After it, for every live slot j:
+ *   head       per logits row x of row r, in fp32: s_v = x_v * inv_t; lse = max + logf(sum expf(s - max)) in s2vt_top20_logprob's
+ *              fixed order; lp_v = fminf(s_v - lse, 0); g_v = lp_v + gumbel(seed, step = t - 1, row = r, v) - the draw of the
+ *              sampled decode above (Philox4x32-10, counter (v / 4, row, step, 0x47554D42), word v % 4; same stream tag).  The
+ *              head returns the 20 largest g_v by (g descending, v ascending), IN THAT ORDER: top_ix, top_lp (unperturbed), top_g.
+ *   children   child f of slot j: phi' = phi_j + top_lp[f], one fp32 add with -0 folded to +0.
+ *   scores     Z = top_g[0], g = top_g[f], both widened exactly to fp64; in fp64: d = g - Z; l = log(-expm1(d)) if d > -ln 2, else
+ *              log1p(-exp(d)); u = (G_j - g) + l; G~ = (G_j - max(u, 0)) - log1p(exp(-|u|)) - the numerically stable form of
+ *              -log(exp(-G_j) - exp(-Z) + exp(-g)).  At f = 0: d = 0, l = u = -inf and G~ = G_j exactly.  Every G~ <= G_j.
+ *   finished   a finished slot is one candidate, itself, with its own G.
+ *   candidate  index c = j * 20 + f, f = 0 for a finished slot.
+ *   selection  the min(W, count) best by (G~ descending, c ascending) become slots 0, 1, ... in that order.  A finished candidate
+ *              stays as it is.  A child appends a back-trace node; v == <eos> makes it finished with length t, otherwise it is
+ *              live with row_state its parent's row and row_tok = v.
+ *   threshold  kappa = max(kappa, best unselected G~).
+ *   stop       a clip with no live slot after the walk is frozen: nothing of it can change any more.  The int32 at byte 0 of
+ *              `state` counts the frozen clips.
+ *   end        after depth D the live slots remain as unfinished samples of length D, no <eos> appended.  The answer is the W slots
+ *              in order, which is non-increasing G: the order in which sampling without replacement draws them.
+ *   fan-out    20 per row is exact: G~ is increasing in g for one parent, so a parent's selected children are a prefix of its
+ *              g-order; at most W <= 8 are selected and its best unselected child is at most its 9th.
+ *   W = 1      ancestral Gumbel-max sampling with the noise of the sampled decode (row b, step t - 1): the words of
+ *              s2vt_sample_decode_rows at K = 1 up to the first <eos>, wherever the draw is decided.
+ * s2vt_top20_gumbel: the head on its own.  One 256-thread workgroup per row on s2vt_top20_logprob's register / LDS forms, every
+ * element runs its own Philox block, fixed-order reductions, no atomics: the same inputs give the same bits.  Row i of the launch
+ * draws with batch row row0 + i.  top_lp is recomputed from the logits row, not by subtracting the noise from g.  Requires
+ * 20 <= V <= 38400, ld >= V, inv_temperature finite and > 0, step >= 0, row0 >= 0.
+ * s2vt_beam_step_gumbel: the depth step with that head, the form chosen as s2vt_beam_step_constrained chooses it (gx_vid, else cache,
+ * else neither); the launches in front of the head are those of the other forms; adds the output top_g [R, 20]; row0 = 0.
+ * s2vt_sbs_bytes / s2vt_sbs_step / s2vt_sbs_result: the policy, one wave per clip, on the row protocol and `depth` convention of
+ * s2vt_beam_cum_step (depth = 1 initialises; 2..max_depth consume the step before; 0 consumes step max_depth).  Rows of slots that
+ * are not live carry token 0 / state row 0.  s2vt_sbs_bytes is 0 for dimensions that are refused.  s2vt_sbs_result back-traces:
+ * out_tokens [B][W][max_depth] int32 (words after <sos>, padded with eos_ix), out_len [B][W], out_logprob [B][W] fp32 (phi),
+ * out_perturbed [B][W] fp32 (G rounded), out_kappa [B] fp32. */
+int s2vt_top20_gumbel(const float* logits, int64_t ld, int64_t rows, int32_t V, float inv_temperature, uint64_t seed, int32_t step,
+                      int32_t row0, int32_t* top_ix, float* top_lp, float* top_g, void* stream);
+int s2vt_beam_step_gumbel(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                          const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                          const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                          int32_t* top_ix, float* top_lp, float* top_g, void* workspace, size_t workspace_bytes, void* cache,
+                          size_t cache_bytes, float inv_temperature, uint64_t seed, int32_t step, void* stream);
+size_t s2vt_sbs_bytes(int32_t B, int32_t n_samples, int32_t max_depth);
+int s2vt_sbs_step(int32_t B, int32_t n_samples, int32_t max_depth, int32_t sos_ix, int32_t eos_ix, int32_t depth, void* state,
+                  size_t state_bytes, const int32_t* top_ix, const float* top_lp, const float* top_g, int32_t* row_b, int32_t* row_state,
+                  int32_t* row_tok, void* stream);
+int s2vt_sbs_result(int32_t B, int32_t n_samples, int32_t max_depth, int32_t eos_ix, void* state, size_t state_bytes, int32_t* out_tokens,
+                    int32_t* out_len, float* out_logprob, float* out_perturbed, float* out_kappa, void* stream);
+
 /* ---------------------------------------------------------------- scheduled sampling (S2VT.forward(mode='train', ss_prob > 0))
  * Bengio et al., NeurIPS 2015: during training each decode-step input is the ground-truth word with probability 1 - p and the
  * word the model itself chose at the previous step with probability p.  Two passes: the decode drivers above run once more with

@@ -206,10 +206,11 @@ class _DepthStep(object):
             self.tab[0][0][:B].copy_(word_h)
             self.tab[0][1][:B].copy_(word_c)
 
-    def __call__(self, depth, rows, st, top_ix=None, top_lp=None, con=None, words=None, logits=None):
+    def __call__(self, depth, rows, st, top_ix=None, top_lp=None, con=None, words=None, logits=None, top_g=None, gumbel=None):
         """the step of `depth` for rows [3, R] (sample, state row, token): every row's top 20 into (top_ix, top_lp) - behind the
         constrained fan-out head with con (a capi.Constraints) and words = (pointer, row stride) of the slots' histories - or, with
-        logits [R, V], stopped one launch early so that the logits stay on the card"""
+        logits [R, V], stopped one launch early so that the logits stay on the card - or, with top_g [R, 20] and gumbel = (fp32
+        inv_temperature, seed), behind the perturbed head of the stochastic beam (best g first; the noise of step depth - 1)"""
         import ctypes
         from .functional import _ptr
         vid = tuple(_ptr(x) for x in self.vid[(depth - 1) & 1] + self.vid[depth & 1])           # h, c in; h, c out
@@ -220,6 +221,9 @@ class _DepthStep(object):
         cache = (_ptr(self.cache), self.cache.numel() if self.cache is not None else 0)
         if logits is not None:
             name, args = "s2vt_beam_step_logits", head + vid + (_ptr(gx),) + word + (_ptr(logits), logits.stride(0)) + out[2:] + cache
+        elif top_g is not None:
+            name = "s2vt_beam_step_gumbel"
+            args = head + vid + (_ptr(gx),) + word + out[:2] + (_ptr(top_g),) + out[2:] + cache + (gumbel[0], gumbel[1], depth - 1)
         elif con is not None:
             hist = (ctypes.byref(con), words[0], words[1], depth - 1)
             name, args = "s2vt_beam_step_constrained", head + vid + (_ptr(gx),) + word + out + cache + hist
@@ -241,7 +245,7 @@ def _model_depth_step(lib, model, feats, params, R, states, policy_name, con=Non
     return lambda depth, rows, top_ix, top_lp, words, st: step(depth, rows, st, top_ix, top_lp, con, words)
 
 
-def _device_depth_loop(dev, B, R, max_depth, qbytes, policy_step, depth_step):
+def _device_depth_loop(dev, B, R, max_depth, qbytes, policy_step, depth_step, with_top_g=False):
     """The depth loop of a search whose policy lives on the device: per depth ONE words = policy_step(depth, qs, top_ix, top_lp, rows,
     st) (consume the top-20 of the depth before, freeze finished samples, write the rows of the step; the constrained forms return
     (pointer, row stride) of the live slots' words for the step they have just prepared) and ONE depth_step(depth, rows, top_ix,
@@ -249,13 +253,15 @@ def _device_depth_loop(dev, B, R, max_depth, qbytes, policy_step, depth_step):
     (_model_depth_step) or an ensemble's; nothing crosses PCIe.  The early exit (all samples frozen) is polled without blocking: the
     frozen-sample counter (the int32 at byte 0 of the policy's state) is copied to pinned memory after every depth and read one
     depth late - extra depths change nothing.  Ends with policy_step(0, ...), the last depth's results.  Returns the policy's state
-    tensor (qbytes) and the stream."""
+    tensor (qbytes) and the stream.  with_top_g (the stochastic beam): a third buffer top_g fp32 [R, 20], the perturbed scores, is
+    allocated beside top_ix / top_lp and handed to both callables as their last argument."""
     from .functional import _stream
     with torch.cuda.device(dev):
         qs = torch.empty(qbytes, dtype=torch.uint8, device=dev)
         rows = torch.zeros(3, R, dtype=torch.int32, device=dev)
         top_ix = torch.zeros(R, FANOUT, dtype=torch.int32, device=dev)
         top_lp = torch.zeros(R, FANOUT, dtype=torch.float32, device=dev)
+        extra = (torch.zeros(R, FANOUT, dtype=torch.float32, device=dev),) if with_top_g else ()
         frozen = torch.zeros(max_depth + 2, dtype=torch.int32).pin_memory()
         frozen_dev = qs[:4].view(torch.int32)
         events = []
@@ -265,14 +271,14 @@ def _device_depth_loop(dev, B, R, max_depth, qbytes, policy_step, depth_step):
             if depth >= 2 and events[depth - 2].query() and int(frozen[depth - 1]) == B:
                 break                                   # every sample had stopped two depths ago: the reference's loop ended there
             depth += 1
-            words = policy_step(depth, qs, top_ix, top_lp, rows, st)
+            words = policy_step(depth, qs, top_ix, top_lp, rows, st, *extra)
             if depth > 1:
                 frozen[depth].copy_(frozen_dev[0], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(dev))
             events.append(ev)
-            depth_step(depth, rows, top_ix, top_lp, words, st)
-        policy_step(0, qs, top_ix, top_lp, rows, st)    # the last depth's results
+            depth_step(depth, rows, top_ix, top_lp, words, st, *extra)
+        policy_step(0, qs, top_ix, top_lp, rows, st, *extra)    # the last depth's results
         global LAST_DEPTHS
         LAST_DEPTHS = depth
     return qs, st
@@ -460,6 +466,70 @@ def beam_diverse(model, feats, params, beam_width=6, num_groups=3, diversity_lam
     G, lam, n_best = check_diverse_args(W, num_groups, diversity_lambda, n_best)
     out = _model_group_search("beam_diverse" if G > 1 else "mode='beam'", model, feats, params, W, G, D, alpha, lam, n_best, constraints)
     return out if G > 1 else tuple(x.unsqueeze(1) for x in out)
+
+
+def check_stochastic_args(n_samples, temperature, seed, max_depth, vocab_size):
+    """(n_samples, temperature, seed, max_depth) of sample_distinct as ints / a float, or ValueError - before anything reaches the
+    library; seed None draws one as `sample` does"""
+    from . import sampling
+    if isinstance(n_samples, bool) or not isinstance(n_samples, (int, np.integer)) or not 1 <= int(n_samples) <= MAX_BEAM_WIDTH:
+        raise ValueError("sample_distinct: n_samples must be an integer in [1, %d], got %r" % (MAX_BEAM_WIDTH, n_samples))
+    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, np.integer)) or int(max_depth) < 1:
+        raise ValueError("sample_distinct: max_depth must be an integer >= 1, got %r" % (max_depth,))
+    if int(vocab_size) < FANOUT:
+        raise ValueError("sample_distinct: vocab_size must be >= %d (the depth step returns each row's %d best words), got %r"
+                         % (FANOUT, FANOUT, vocab_size))
+    if isinstance(temperature, (bool, str)) or not isinstance(temperature, (int, float, np.integer, np.floating)):
+        raise ValueError("sample_distinct: temperature must be finite and > 0, got %r" % (temperature,))
+    t, seed = sampling.check_sample_args(temperature, seed)
+    return int(n_samples), t, seed, int(max_depth)
+
+
+def inv_temperature(temperature):
+    """fp32(1 / temperature) as the library's sampled decodes form it: the fp32 quotient of fp32 operands"""
+    return float(np.float32(1.0) / np.float32(temperature))
+
+
+@torch.no_grad()
+def stochastic(model, feats, params, n_samples=5, temperature=1.0, seed=0, max_depth=30):
+    """S2VT.sample_distinct (not in the reference; include/s2vt_hip.h "stochastic beam"): stochastic beam search
+    (Kool, van Hoof, Welling, 2019) - n_samples pairwise distinct captions per clip, sampled without replacement from the model's
+    distribution over sentences at `temperature`, in the order a sequential without-replacement sampler draws them.  Same encoder
+    states, decode cache, precomputed vid_rnn steps, depth loop and polled early exit as mode='beam'; the depth step ends in the
+    perturbed fan-out head (csrc/gumbel_top.hip), the policy is csrc/sbs_policy.hip, one launch per depth; nothing crosses PCIe.
+    Arguments as check_stochastic_args returns them.  Returns (ids int64 [B, W, D] padded with <eos>, lengths int64 [B, W], logprobs
+    fp32 [B, W], perturbed fp32 [B, W], kappa fp32 [B]) on the device; no host synchronisation."""
+    from .functional import _ptr
+    lib = capi.load()
+    dev = feats.device
+    B, W, D = feats.shape[0], n_samples, max_depth
+    sos, eos = int(model.sos_ix), int(model.eos_ix)
+    qbytes = lib.s2vt_sbs_bytes(B, W, D)
+    if qbytes == 0:
+        raise ValueError("sample_distinct: batch %d x n_samples %d x max_depth %d is more than the search state holds" % (B, W, D))
+    gum = (inv_temperature(temperature), int(seed))
+    step = _DepthStep(lib, model, feats, params, B * W, *_encoder_states(model, feats, params, D, PLANE_STEP and PLANE_ENCODER))
+    global LAST_PATH
+    LAST_PATH = "stochastic beam + " + (("plane-path depth step (decode cache)" + (", vid_rnn steps precomputed" if step.gx_dec is not None
+                                                                                   else "")) if step.cache is not None
+                                        else "fp32-MFMA depth step")
+
+    def policy_step(depth, qs, top_ix, top_lp, rows, st, top_g):
+        capi.check(lib.s2vt_sbs_step(B, W, D, sos, eos, depth, _ptr(qs), qbytes, _ptr(top_ix), _ptr(top_lp), _ptr(top_g), _ptr(rows[0]),
+                                     _ptr(rows[1]), _ptr(rows[2]), st), "s2vt_sbs_step")
+
+    def depth_step(depth, rows, top_ix, top_lp, words, st, top_g):
+        step(depth, rows, st, top_ix, top_lp, top_g=top_g, gumbel=gum)
+    qs, st = _device_depth_loop(dev, B, B * W, D, qbytes, policy_step, depth_step, with_top_g=True)
+    with torch.cuda.device(dev):
+        ids = torch.empty(B, W, D, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, W, dtype=torch.int32, device=dev)
+        lp = torch.empty(B, W, dtype=torch.float32, device=dev)
+        g = torch.empty(B, W, dtype=torch.float32, device=dev)
+        kappa = torch.empty(B, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_sbs_result(B, W, D, eos, _ptr(qs), qbytes, _ptr(ids), _ptr(lens), _ptr(lp), _ptr(g), _ptr(kappa), st),
+                   "s2vt_sbs_result")
+        return ids.long(), lens.long(), lp, g, kappa
 
 
 class HeapQueues(object):

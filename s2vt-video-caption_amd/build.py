@@ -8,7 +8,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libs2vt_hip.so")
-SOURCES = ["api_runtime.hip", "api_shared.hip", "api_train.hip", "api_train_f32.hip", "api_decode.hip", "api_beam.hip", "api_score.hip", "api_sample_rows.hip", "api_ops.hip", "api_gru.hip", "api_stack.hip", "options.hip", "gemm.hip", "gemm_bf16.hip", "gemm_x3.hip", "gemm_b1.hip", "split.hip", "lstm.hip", "gru.hip", "lstm_stack.hip", "lstm_gemv.hip", "lstm_bf16.hip", "lstm_persist.hip", "lstm_persist_x3.hip", "argmax_x3.hip", "ce.hip", "ensemble.hip", "truncate.hip", "cider.hip", "misc.hip", "optim.hip", "group.hip", "beam_queue.hip", "beam_policy.hip"]
+SOURCES = ["api_runtime.hip", "api_shared.hip", "api_train.hip", "api_train_f32.hip", "api_decode.hip", "api_beam.hip", "api_score.hip", "api_sample_rows.hip", "api_ops.hip", "api_gru.hip", "api_stack.hip", "options.hip", "gemm.hip", "gemm_bf16.hip", "gemm_x3.hip", "gemm_b1.hip", "split.hip", "lstm.hip", "gru.hip", "lstm_stack.hip", "lstm_gemv.hip", "lstm_bf16.hip", "lstm_persist.hip", "lstm_persist_x3.hip", "argmax_x3.hip", "ce.hip", "ensemble.hip", "truncate.hip", "cider.hip", "misc.hip", "optim.hip", "group.hip", "beam_queue.hip", "beam_policy.hip", "gumbel_top.hip", "sbs_policy.hip"]
 HEADERS = ["common.h", "philox.h", "mfma_tile.h", "step_frame.h", "row_frame.h", "kernels.h", "gemm_persist.h", "lstm_persist_frame.h", "beam_wave.h", "experiment.h", "api_internal.h", os.path.join("..", "..", "include", "s2vt_hip.h")]
 
 

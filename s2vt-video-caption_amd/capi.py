@@ -153,6 +153,15 @@ SIGNATURES = {
     "s2vt_beam_div_step": (c_int32, [c_int32] * 6 + [c_double, c_double, c_int32, c_void_p, c_size_t] + [c_void_p] * 5 +
                            [POINTER(c_void_p), POINTER(c_int64), c_void_p]),
     "s2vt_beam_div_result": (c_int32, [c_int32] * 6 + [c_void_p, c_size_t] + [c_void_p] * 4),
+    # stochastic beam search (S2VT.sample_distinct; csrc/gumbel_top.hip, csrc/sbs_policy.hip): the perturbed fan-out head, the depth
+    # step with it, the policy
+    "s2vt_top20_gumbel": (c_int32, [c_void_p, c_int64, c_int64, c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
+    "s2vt_beam_step_gumbel": (c_int32, [POINTER(Dims), POINTER(Params), c_int32] + [c_void_p] * 16 + [c_size_t, c_void_p, c_size_t, c_float,
+                                                                                                     c_uint64, c_int32, c_void_p]),
+    "s2vt_sbs_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_sbs_step": (c_int32, [c_int32] * 6 + [c_void_p, c_size_t] + [c_void_p] * 7),
+    "s2vt_sbs_result": (c_int32, [c_int32] * 4 + [c_void_p, c_size_t] + [c_void_p] * 6),
     "s2vt_score_workspace_bytes": (c_size_t, [POINTER(Dims), c_int32, c_int32]),
     "s2vt_score_captions": (c_int32, [POINTER(Dims), POINTER(Params), c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32,
                                       c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_int32,

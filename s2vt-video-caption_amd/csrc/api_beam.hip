@@ -59,7 +59,12 @@ size_t s2vt_beam_workspace_bytes(const s2vt_dims* d, int32_t max_rows) {
 // con (nullable): the constrained search's depth step - the fan-out head is the constrained one (ce.hip: the rules of the constrained
 // draw on each row with beam slot r's own words hist[r * hist_ld + i], i < t, then log_softmax and the top 20 of the edited row)
 struct BeamCon { const char* fn; const s2vt_constraints* c; const int32_t* hist; int64_t hist_ld; int t; };
-static int beam_fan_out(hipStream_t st, float* logits, int R, int V, const BeamCon* con, int32_t* top_ix, float* top_lp) {
+// gum (nullable): the stochastic beam's depth step - the fan-out head is the perturbed one (gumbel_top.hip: every row's 20 best words by
+// log-prob + Gumbel noise of (seed, step, row r, v), best first, with the extra output top_g [R, 20])
+struct BeamGum { GumbelArgs ga; float* top_g; };
+static int beam_fan_out(hipStream_t st, float* logits, int R, int V, const BeamCon* con, int32_t* top_ix, float* top_lp,
+                        const BeamGum* gum) {
+    if (gum) return top20_gumbel(st, logits, V, R, V, gum->ga, top_ix, top_lp, gum->top_g);
     if (!con) return top20_logprob(st, logits, V, R, V, top_ix, top_lp);
     return top20_constrained_checked(con->fn, st, logits, V, R, V, con->hist, con->hist_ld, con->t, con->c, top_ix, top_lp);
 }
@@ -67,7 +72,8 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
                           const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
                           const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out, int32_t* top_ix,
                           float* top_lp, void* workspace, size_t workspace_bytes, void* cache, size_t cache_bytes, void* stream,
-                          const float* gx_vid, const BeamCon* con = nullptr, float* logits_out = nullptr, int64_t ld_out = 0) {
+                          const float* gx_vid, const BeamCon* con = nullptr, float* logits_out = nullptr, int64_t ld_out = 0,
+                          const BeamGum* gum = nullptr) {
     S2VT_REQUIRE(d && p && workspace && (gx_vid || (vid_h_in && vid_c_in && vid_h_out && vid_c_out)), "s2vt_beam_step: null argument");
     S2VT_REQUIRE(R >= 0 && (R == 0 || (row_b && row_state && tok && word_h_in && word_c_in && word_h_out && word_c_out &&
                                         (logits_out || (top_ix && top_lp)))),
@@ -120,7 +126,7 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
         if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
         if ((rc = rows_word_step(st, *d, p, &kc, a))) return rc;
         if ((rc = pgemm(ln, R, V, H, w.pword, 0, 0, kc.wo, 0, 0, lg, ldl, ID, p->out_b, false))) return rc;
-        if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;
+        if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp, gum))) return rc;
         return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
     }
     S2VT_REQUIRE(!gx_vid, "s2vt_beam_step_gx: the precomputed vid_rnn half needs the plane path (gemm mode 1 / 3, H <= 1024)");
@@ -130,7 +136,7 @@ static int beam_step_impl(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     if ((rc = fill_zero(st, w.err, 4 * sizeof(int)))) return rc;
     if ((rc = rows_word_step(st, *d, p, nullptr, a))) return rc;
     if ((rc = lgemm(ln, true, true, R, V, H, word_h_out, H, ID, p->out_w, H, ID, lg, ldl, ID, p->out_b, false))) return rc;       // (:213)
-    if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp))) return rc;                                   // (:214-219)
+    if (!logits_out && (rc = beam_fan_out(st, w.logits, R, V, con, top_ix, top_lp, gum))) return rc;                                   // (:214-219)
     return post_async_error(st, w.err, 3);       // (ring slot: no wait for the previous depth step)
 }
 // the depth step with vid_rnn's part precomputed (s2vt_decode_encode_cached, gx_dec[depth - 1]): word step, out_linear, fan-out
@@ -177,6 +183,27 @@ int s2vt_beam_step_logits(const s2vt_dims* d, const s2vt_params* p, int32_t R, c
     return beam_step_impl(d, p, R, row_b, row_state, tok, vid_h_in, vid_c_in, vid_h_out, vid_c_out, word_h_in, word_c_in, word_h_out,
                           word_c_out, nullptr, nullptr, workspace, workspace_bytes, cache, cache ? cache_bytes : 0, stream, gx_vid, nullptr,
                           logits_out, ld_out);
+}
+// the depth step of the stochastic beam (S2VT.sample_distinct), all three forms chosen as s2vt_beam_step_constrained chooses them: the
+// same launches up to and including out_linear, then the perturbed fan-out head with the noise of (seed, step, row r, v)
+int s2vt_beam_step_gumbel(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
+                          const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,
+                          const float* gx_vid, const float* word_h_in, const float* word_c_in, float* word_h_out, float* word_c_out,
+                          int32_t* top_ix, float* top_lp, float* top_g, void* workspace, size_t workspace_bytes, void* cache,
+                          size_t cache_bytes, float inv_temperature, uint64_t seed, int32_t step, void* stream) {
+    S2VT_REQUIRE(top_g || R == 0, "s2vt_beam_step_gumbel: null top_g");
+    S2VT_REQUIRE(!gx_vid || cache, "s2vt_beam_step_gumbel: gx_vid needs the cache");
+    S2VT_REQUIRE(inv_temperature > 0.f && inv_temperature <= 3.4028234e38f && step >= 0,
+                 "s2vt_beam_step_gumbel: inv_temperature must be finite and > 0 (got %g), step >= 0", (double)inv_temperature);
+    const BeamGum gum{GumbelArgs{inv_temperature, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), (uint32_t)step, 0u,
+                                 (uint32_t)(R > 0 ? R : 0)}, top_g};
+    if (gx_vid) {
+        vid_h_in = vid_c_in = nullptr;
+        vid_h_out = vid_c_out = nullptr;
+    }
+    return beam_step_impl(d, p, R, row_b, row_state, tok, vid_h_in, vid_c_in, vid_h_out, vid_c_out, word_h_in, word_c_in, word_h_out,
+                          word_c_out, top_ix, top_lp, workspace, workspace_bytes, cache, cache ? cache_bytes : 0, stream, gx_vid, nullptr,
+                          nullptr, 0, &gum);
 }
 int s2vt_beam_step(const s2vt_dims* d, const s2vt_params* p, int32_t R, const int32_t* row_b, const int32_t* row_state,
                    const int32_t* tok, const float* vid_h_in, const float* vid_c_in, float* vid_h_out, float* vid_c_out,

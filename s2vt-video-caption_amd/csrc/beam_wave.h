@@ -27,4 +27,22 @@ __device__ __forceinline__ unsigned long long bc_wave_max(unsigned long long v) 
     return v;
 }
 
+
+// ---- the stochastic beam's selection (sbs_policy.hip): candidates carry an fp64 score, which the 64-bit keyed max above has no room
+// for beside the candidate index.  fp64 -> uint64 whose unsigned order is the double order (-0 folded to +0 first: one score; no NaN
+// reaches it), 0 reserved for "no candidate" (the image of -inf is 0x000F...F + 1 > 0), and a wave-wide max over the PAIR (key, c):
+// the larger key wins, equal keys -> the lower c.  Three shuffles per butterfly step; every lane ends with the winner.
+__device__ __forceinline__ unsigned long long bc_ordered64(double x) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(x == 0.0 ? 0.0 : x);
+    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ void bc_wave_max_f64c(unsigned long long& key, int& c) {
+    for (int o = 32; o; o >>= 1) {
+        const unsigned int hi = (unsigned int)__shfl_xor((int)(key >> 32), o), lo = (unsigned int)__shfl_xor((int)(unsigned int)key, o);
+        const int oc = __shfl_xor(c, o);
+        const unsigned long long ok = ((unsigned long long)hi << 32) | lo;
+        if (ok > key || (ok == key && oc < c)) { key = ok; c = oc; }
+    }
+}
+
 }  // namespace s2vt

@@ -334,6 +334,73 @@ def top20_logprob(logits):
     return ix, lp
 
 
+def top20_gumbel(logits, inv_temperature=1.0, seed=0, step=0, row0=0):
+    """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20], top_g fp32 [rows, 20]): the fan-out head of S2VT.sample_distinct on its own
+    (s2vt_top20_gumbel; include/s2vt_hip.h "stochastic beam") - per row the 20 words with the largest g_v = lp_v + noise, lp =
+    log_softmax(logits * inv_temperature) and the noise sampling.gumbel_noise(seed, step, row0 + r, V), in the order (g descending,
+    v ascending), with their unperturbed log-probs and their g.  logits: fp32 [rows, 20 <= V <= 38400], unit column stride (a row
+    stride > V is fine); inv_temperature: the fp32 factor itself."""
+    lib = capi.load()
+    require_hip(logits, "logits")
+    if logits.dim() != 2 or logits.dtype != torch.float32 or logits.stride(1) != 1:
+        raise ValueError("logits must be fp32 [rows, V] with unit column stride")
+    rows, V = logits.shape
+    dev = logits.device
+    with torch.cuda.device(dev):
+        ix = torch.empty(rows, 20, dtype=torch.int32, device=dev)
+        lp = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        g = torch.empty(rows, 20, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_top20_gumbel(_ptr(logits), logits.stride(0), rows, V, float(inv_temperature), int(seed), int(step), int(row0),
+                                         _ptr(ix), _ptr(lp), _ptr(g), _stream(dev)), "s2vt_top20_gumbel")
+    return ix, lp, g
+
+
+def sbs_state(B, n_samples, max_depth, dev):
+    """the policy state of a stochastic beam search (uint8, s2vt_sbs_bytes) and its rows int32 [3, B * n_samples] (sample, state row,
+    token), for sbs_step / sbs_result"""
+    nbytes = capi.load().s2vt_sbs_bytes(B, n_samples, max_depth)
+    if nbytes == 0:
+        raise ValueError("sbs: %d clips x %d samples x depth %d is not a shape the policy serves" % (B, n_samples, max_depth))
+    with torch.cuda.device(dev):
+        return torch.empty(nbytes, dtype=torch.uint8, device=dev), torch.zeros(3, B * n_samples, dtype=torch.int32, device=dev)
+
+
+def sbs_step(state, rows, B, n_samples, max_depth, sos_ix, eos_ix, depth, top_ix=None, top_lp=None, top_g=None):
+    """One call of the stochastic beam's policy (s2vt_sbs_step; csrc/sbs_policy.hip) on a state of sbs_state: depth = 1 initialises,
+    depth = 2..max_depth consumes the [B * n_samples, 20] arrays (int32, fp32, fp32; a head's output, best g first) of step depth - 1,
+    depth = 0 those of step max_depth.  Writes `rows` for the next depth step; the int32 at byte 0 of `state` counts frozen clips."""
+    lib = capi.load()
+    dev = state.device
+    R = B * n_samples
+    if depth != 1:
+        for t, dt, name in ((top_ix, torch.int32, "top_ix"), (top_lp, torch.float32, "top_lp"), (top_g, torch.float32, "top_g")):
+            require_hip(t, name)
+            if t.dtype != dt or tuple(t.shape) != (R, 20) or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous %s [%d, 20]" % (name, dt, R))
+    if rows.dtype != torch.int32 or tuple(rows.shape) != (3, R) or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous int32 [3, %d]" % R)
+    with torch.cuda.device(dev):
+        capi.check(lib.s2vt_sbs_step(B, n_samples, max_depth, int(sos_ix), int(eos_ix), int(depth), _ptr(state), state.numel(),
+                                     _ptr(top_ix), _ptr(top_lp), _ptr(top_g), _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), _stream(dev)),
+                   "s2vt_sbs_step")
+
+
+def sbs_result(state, B, n_samples, max_depth, eos_ix):
+    """(ids int32 [B, W, D] padded with eos_ix, lengths int32 [B, W], logprob fp32 [B, W], perturbed fp32 [B, W], kappa fp32 [B]) of a
+    stepped state (s2vt_sbs_result)"""
+    lib = capi.load()
+    dev = state.device
+    with torch.cuda.device(dev):
+        ids = torch.empty(B, n_samples, max_depth, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, n_samples, dtype=torch.int32, device=dev)
+        lp = torch.empty(B, n_samples, dtype=torch.float32, device=dev)
+        g = torch.empty(B, n_samples, dtype=torch.float32, device=dev)
+        kappa = torch.empty(B, dtype=torch.float32, device=dev)
+        capi.check(lib.s2vt_sbs_result(B, n_samples, max_depth, int(eos_ix), _ptr(state), state.numel(), _ptr(ids), _ptr(lens), _ptr(lp),
+                                       _ptr(g), _ptr(kappa), _stream(dev)), "s2vt_sbs_result")
+    return ids, lens, lp, g, kappa
+
+
 def top20_logprob_constrained(logits, hist, t, spec):
     """(top_ix int32 [rows, 20], top_lp fp32 [rows, 20]): top20_logprob of the rows CONSTRAINED by `spec` (a sampling.ConstraintSpec)
     at step t - the fan-out head of S2VT.beam_constrained on its own (s2vt_top20_logprob_constrained; include/s2vt_hip.h "constrained
