@@ -335,7 +335,8 @@ class S2VT(nn.Module):
         [B, n_samples] - the sum of the words' log-probs under softmax(logit / temperature), mode='score' with length_alpha=0.0 at
         temperature 1, perturbed fp32 [B, n_samples] - the samples' perturbed scores G, non-increasing along a clip's row and <= 0,
         kappa fp32 [B] - the largest perturbed score that was NOT kept, <= perturbed[:, -1]: the threshold of the inclusion
-        probabilities q = exp(-exp(kappa - logprob)) of importance-weighted estimators) on the device; no host synchronisation.
+        probabilities q = 1 - exp(-exp(logprob - kappa)) of importance-weighted estimators: a caption is kept when its Gumbel(logprob)
+        score exceeds kappa; self_critical.inclusion_log_q) on the device; no host synchronisation.
         The search (include/s2vt_hip.h "stochastic beam") is beam-shaped: mode='beam''s encoder states, decode
         cache and depth step over the rows b * n_samples + slot; the fan-out head ranks a row's words by log-prob + Gumbel noise
         (csrc/gumbel_top.hip; the counter-based noise of mode='sample', keyed by seed, depth, row and word), the policy keeps the
@@ -344,7 +345,7 @@ class S2VT(nn.Module):
         <eos>, wherever a draw is decided.  Same seed, same weights, same clips -> the same bits.  One-layer LSTM models only (a GRU or
         stacked model: ValueError naming `sample`).  A method of its own: the parameter lists of forward and sample are fixed.  Not
         covered: top-k / nucleus truncation and the constraint rules inside this search, GRU, stacked and Att_Baseline models,
-        Ensemble, widths above 8, kappa as a training baseline, dp.py.  No gradient.
+        Ensemble, widths above 8, dp.py (kappa in training: train.py --sc-distinct, ops.sc_weights_swor).  No gradient.
         :param n_samples: an integer in [1, 8]
         :param temperature: finite and > 0
         :param seed: None draws a 63-bit seed from torch's default generator, as `sample` does; an int is used as is

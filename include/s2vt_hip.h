@@ -446,6 +446,34 @@ int s2vt_sc_weights(const int64_t* sampled, const double* r_sample, const double
  * not zero.  s2vt_weighted_ce_forward's normaliser counts the tokens that carry a weight, so that clip's tokens are not counted. */
 int s2vt_sc_weights_group(const int64_t* sampled, const double* r_sample, const double* r_greedy, int32_t B, int32_t K, int32_t T,
                           int32_t sos, int32_t eos, int64_t* caps, float* weight, double* baseline, void* stream);
+/* ---- without-replacement weights
+ * The same for the K pairwise distinct captions per clip of one stochastic beam search (S2VT.sample_distinct: sampled int64
+ * [B*K, T], logprob fp32 [B*K], kappa fp32 [B]), 2 <= K <= S2VT_SWOR_MAX_K: the normalised importance-weighted REINFORCE estimator
+ * with a built-in baseline of Kool, van Hoof, Welling, "Buy 4 REINFORCE Samples, Get a Baseline for Free!" (2019).  A caption with
+ * log-prob phi is among the K when its Gumbel(phi) score exceeds kappa: inclusion probability q = 1 - exp(-exp(phi - kappa)).
+ * Per clip b, rows i = 0 .. K-1 at r = b*K + i, phi_i = (double)logprob[r], kap = (double)kappa[b], r_i = r_sample[r]; everything in
+ * fp64, every sum over ascending i from 0.0, products and sums rounded apart, no atomics:
+ *   1. a_i = phi_i - kap (+inf when kap = -inf), e_i = exp(a_i)
+ *   2. lq_i = log(-expm1(-e_i)), or a_i - 0.5 * e_i when a_i < -30: log q_i, finite where e_i underflows (at the switch the two
+ *      forms differ by about e^2 / 24 < 1e-27); kap = -inf gives lq_i = 0
+ *   3. lw_i = phi_i - lq_i, m = max_i lw_i, om_i = exp(lw_i - m), pi_i = exp(phi_i - m): both exponents <= 0, and nothing changes
+ *      when phi and kap are shifted together - 79-word captions with phi ~ -700 do not underflow
+ *   4. W = sum om_j, N = sum om_j * r_j
+ *   5. base = r_greedy[b] (fp64 [B]) when given, else N / W: the importance-weighted estimate of the model's expected reward
+ *   6. W_i = (W - om_i) + pi_i, c_i = om_i / W_i, adv_i = c_i * (r_i - base)
+ *   7. caps int64 [B*K, T+1] = sos || sampled; weight fp32 [B*K, T+1] = fp32(adv_i), rounded once, on positions 1 .. the first eos
+ *      of the row inclusive (all T without one), zero elsewhere: s2vt_sc_weights_group's layout
+ * r_greedy == NULL and the K rewards compare equal: every adv_i is exactly 0 and base = r_0 (N / W alone would leave a difference
+ * of rounding size; the reason given for s2vt_sc_weights_group).  A clip is BAD when a phi is not finite or positive, kap is NaN or
+ * +inf, a reward (r_greedy[b] included) is not finite, or an fp32(adv_i) comes out not finite (rewards beyond fp32's range):
+ * weight 0 on all its rows, coef 0, base NaN - no NaN reaches a gradient, and other clips are untouched.
+ * coef fp64 [B*K] = c_i or NULL; baseline fp64 [B] = base or NULL.  self_critical.swor_advantages restates it in numpy step for step
+ * (libm's exp / expm1 / log against the device's: rtol 1e-10).  One wavefront per clip, every lane walking the same K numbers.  Null
+ * pointers, B < 1, T < 1 or K outside [2, S2VT_SWOR_MAX_K]: S2VT_ERR_ARG before any launch. */
+#define S2VT_SWOR_MAX_K 8
+int s2vt_sc_weights_swor(const int64_t* sampled, const float* logprob, const float* kappa, const double* r_sample,
+                         const double* r_greedy, int32_t B, int32_t K, int32_t T, int32_t sos, int32_t eos, int64_t* caps,
+                         float* weight, double* coef, double* baseline, void* stream);
 
 /* The same gradient handed to s2vt_train_backward WITHOUT an fp32 dlogits tensor (utils.py:22 under loss.backward(), train.py:124):
  * evaluates (softmax(logits) - onehot(target)) * gout[0] / (B*(L-1)) inside the plane-split pass of the TRAIN workspace the

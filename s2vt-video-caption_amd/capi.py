@@ -59,6 +59,7 @@ class Constraints(ctypes.Structure):
 
 CIDER_MAX_T = 512        # S2VT_CIDER_MAX_T of include/s2vt_hip.h
 CONSENSUS_MAX_K = 64     # S2VT_CONSENSUS_MAX_K
+SWOR_MAX_K = 8           # S2VT_SWOR_MAX_K
 GRAD_NORM_CHUNK = 16384  # S2VT_GRAD_NORM_CHUNK: gradient elements per fp64 partial of s2vt_grad_norm
 ADAM_MAX_SEGMENTS = 16   # S2VT_ADAM_MAX_SEGMENTS
 
@@ -283,6 +284,8 @@ SIGNATURES = {
     "s2vt_sc_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "s2vt_sc_weights_group": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),
+    # without-replacement weights of the K distinct captions of S2VT.sample_distinct (train.py --sc-distinct; csrc/cider.hip)
+    "s2vt_sc_weights_swor": (c_int32, [c_void_p] * 5 + [c_int32] * 5 + [c_void_p] * 5),
     "s2vt_mean_ce_backward_fused": (c_int32, [POINTER(Dims), c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                               c_void_p]),
     "s2vt_set_option": (c_int32, [c_char_p, c_int32]),

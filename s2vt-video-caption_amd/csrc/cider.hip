@@ -412,6 +412,91 @@ __global__ __launch_bounds__(kGroupThreads) void sc_weights_group_kernel(const i
     }
 }
 
+// Without-replacement weights (include/s2vt_hip.h, "without-replacement weights"): the K rows of a clip are the K distinct captions of
+// one stochastic beam search, logprob their log-probs phi and kappa the search's threshold.  The same shape as the kernel above - one
+// wavefront per clip, every lane walking the same K numbers, no exchange - with the header's steps 1-6 in fp64 in front of the rows'
+// copy: each sum in ascending i from 0.0, exp / expm1 / log the only calls, products and sums kept apart (contraction is off in this
+// file).  K <= S2VT_SWOR_MAX_K and the loops are unrolled to it, so the per-row values stay in registers.
+constexpr int kSworMaxK = S2VT_SWOR_MAX_K;
+__global__ __launch_bounds__(kGroupThreads) void sc_weights_swor_kernel(const int64_t* sampled, const float* logprob, const float* kappa,
+                                                                        const double* r_sample, const double* r_greedy, int K, int T,
+                                                                        int sos, int eos, int64_t* caps, float* weight, double* coef,
+                                                                        double* baseline) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const double inf = __builtin_inf();
+    const double* rs = r_sample + (int64_t)b * K;
+    const float* lp = logprob + (int64_t)b * K;
+    const double kap = (double)kappa[b];
+    bool bad = kap != kap || kap == inf || (r_greedy && !(fabs(r_greedy[b]) < inf));
+    bool same = !r_greedy;                        // all K rewards equal: every advantage is exactly 0 (see the header)
+    double lw[kSworMaxK], phi[kSworMaxK], m = -inf;
+#pragma unroll
+    for (int i = 0; i < kSworMaxK; ++i) {
+        lw[i] = phi[i] = 0.0;
+        if (i < K) {
+            phi[i] = (double)lp[i];
+            bad = bad || !(fabs(phi[i]) < inf) || phi[i] > 0.0 || !(fabs(rs[i]) < inf);
+            same = same && rs[i] == rs[0];
+            const double a = phi[i] - kap;        // +inf for kap = -inf: e = +inf, lq = log(1) = 0
+            const double e = exp(a);
+            const double lq = a < -30.0 ? a - 0.5 * e : log(-expm1(-e));
+            lw[i] = phi[i] - lq;
+            m = lw[i] > m ? lw[i] : m;
+        }
+    }
+    double om[kSworMaxK], W = 0.0, N = 0.0;
+#pragma unroll
+    for (int i = 0; i < kSworMaxK; ++i) {
+        om[i] = 0.0;
+        if (i < K && !bad) {
+            om[i] = exp(lw[i] - m);
+            W += om[i];
+            N += om[i] * rs[i];
+        }
+    }
+    const double base = bad ? __builtin_nan("") : r_greedy ? r_greedy[b] : same ? rs[0] : N / W;
+    double c[kSworMaxK], adv[kSworMaxK];
+#pragma unroll
+    for (int i = 0; i < kSworMaxK; ++i) {
+        c[i] = adv[i] = 0.0;
+        if (i < K && !bad) {
+            const double Wi = (W - om[i]) + exp(phi[i] - m);
+            c[i] = om[i] / Wi;
+            adv[i] = same ? 0.0 : c[i] * (rs[i] - base);
+        }
+    }
+    bool wild = false;                            // a weight that fp32 does not hold (finite rewards can be that large): a bad clip
+#pragma unroll
+    for (int i = 0; i < kSworMaxK; ++i)
+        if (i < K) wild = wild || !(fabsf((float)adv[i]) < __builtin_inff());
+    if (lane == 0 && baseline) baseline[b] = wild ? __builtin_nan("") : base;
+#pragma unroll
+    for (int k = 0; k < kSworMaxK; ++k) {
+        if (k >= K) break;
+        const int64_t r = (int64_t)b * K + k;
+        const int64_t* row = sampled + r * T;
+        int first = T;                            // index of the first <eos>, T without one
+        for (int i = lane; i < T; i += kGroupThreads)
+            if (row[i] == (int64_t)eos) { first = i; break; }
+        for (int o = kGroupThreads / 2; o > 0; o >>= 1) {
+            const int other = __shfl_xor(first, o, kGroupThreads);
+            first = other < first ? other : first;
+        }
+        const float w = wild ? 0.0f : (float)adv[k];
+        int64_t* crow = caps + r * (T + 1);
+        float* wrow = weight + r * (T + 1);
+        if (lane == 0) {
+            crow[0] = sos;
+            wrow[0] = 0.0f;
+            if (coef) coef[r] = wild ? 0.0 : c[k];
+        }
+        for (int i = lane; i < T; i += kGroupThreads) {
+            crow[1 + i] = row[i];
+            wrow[1 + i] = i <= first ? w : 0.0f;
+        }
+    }
+}
+
 }  // namespace s2vt
 
 using namespace s2vt;
@@ -508,6 +593,18 @@ int s2vt_sc_weights_group(const int64_t* sampled, const double* r_sample, const 
     hipLaunchKernelGGL(sc_weights_group_kernel, dim3((unsigned)B), dim3(kGroupThreads), 0, (hipStream_t)stream, sampled, r_sample,
                        r_greedy, (int)K, (int)T, (int)sos, (int)eos, caps, weight, baseline);
     S2VT_LAUNCH_CHECK("sc_weights_group_kernel");
+    return 0;
+}
+
+int s2vt_sc_weights_swor(const int64_t* sampled, const float* logprob, const float* kappa, const double* r_sample, const double* r_greedy,
+                         int32_t B, int32_t K, int32_t T, int32_t sos, int32_t eos, int64_t* caps, float* weight, double* coef,
+                         double* baseline, void* stream) {
+    S2VT_REQUIRE(sampled && logprob && kappa && r_sample && caps && weight, "s2vt_sc_weights_swor: null argument");
+    S2VT_REQUIRE(B > 0 && K >= 2 && K <= S2VT_SWOR_MAX_K && T > 0, "s2vt_sc_weights_swor: bad dims (B %d, K %d of 2..%d, T %d)", (int)B,
+                 (int)K, S2VT_SWOR_MAX_K, (int)T);
+    hipLaunchKernelGGL(sc_weights_swor_kernel, dim3((unsigned)B), dim3(kGroupThreads), 0, (hipStream_t)stream, sampled, logprob, kappa,
+                       r_sample, r_greedy, (int)K, (int)T, (int)sos, (int)eos, caps, weight, coef, baseline);
+    S2VT_LAUNCH_CHECK("sc_weights_swor_kernel");
     return 0;
 }
 

@@ -1101,6 +1101,41 @@ def sc_weights_group(sampled, r_sample, r_greedy, K, sos_ix, eos_ix, return_base
     return (caps, weight, baseline) if return_baseline else (caps, weight)
 
 
+def sc_weights_swor(sampled, logprob, kappa, r_sample, r_greedy, K, sos_ix, eos_ix, return_extras=False):
+    """(caps int64 [B*K, T+1], weight fp32 [B*K, T+1][, coef fp64 [B*K], baseline fp64 [B]]) for the K pairwise distinct captions per
+    clip of S2VT.sample_distinct, rows r = b*K + k - s2vt_sc_weights_swor (include/s2vt_hip.h "without-replacement weights";
+    self_critical.swor_advantages).  sampled int64 [B*K, T], logprob fp32 [B*K] and kappa fp32 [B] as the search returns them,
+    r_sample fp64 [B*K].  r_greedy None: the estimator's own baseline N / W; r_greedy fp64 [B]: the clip's greedy reward.
+    2 <= K <= 8."""
+    lib = capi.load()
+    K = int(K)
+    if not 2 <= K <= capi.SWOR_MAX_K:
+        raise ValueError("sc_weights_swor: K distinct captions per clip with K in [2, %d], got K = %d" % (capi.SWOR_MAX_K, K))
+    require_hip(sampled, "sampled")
+    if sampled.dim() != 2 or sampled.dtype != torch.int64 or sampled.shape[0] % K != 0 or sampled.shape[0] == 0 or sampled.shape[1] == 0:
+        raise capi.S2VTHipError("sc_weights_swor: sampled must be int64 [B*K, T]")
+    sampled = sampled.contiguous()
+    R, T = sampled.shape
+    B = R // K
+    for name, r, n, dt in (("logprob", logprob, R, torch.float32), ("kappa", kappa, B, torch.float32),
+                           ("r_sample", r_sample, R, torch.float64), ("r_greedy", r_greedy, B, torch.float64)):
+        if r is None and name == "r_greedy":
+            continue
+        require_hip(r, name)
+        if r.dtype != dt or tuple(r.shape) != (n,) or not r.is_contiguous():
+            raise capi.S2VTHipError("sc_weights_swor: %s must be a contiguous %s [%d]" % (name, str(dt).replace("torch.", ""), n))
+    dev = sampled.device
+    with torch.cuda.device(dev):
+        caps = torch.empty(R, T + 1, dtype=torch.int64, device=dev)
+        weight = torch.empty(R, T + 1, dtype=torch.float32, device=dev)
+        coef = torch.empty(R, dtype=torch.float64, device=dev) if return_extras else None
+        baseline = torch.empty(B, dtype=torch.float64, device=dev) if return_extras else None
+        capi.check(lib.s2vt_sc_weights_swor(_ptr(sampled), _ptr(logprob), _ptr(kappa), _ptr(r_sample), _ptr(r_greedy), B, K, T,
+                                            int(sos_ix), int(eos_ix), _ptr(caps), _ptr(weight), _ptr(coef), _ptr(baseline), _stream(dev)),
+                   "s2vt_sc_weights_swor")
+    return (caps, weight, coef, baseline) if return_extras else (caps, weight)
+
+
 # ---------------------------------------------------------------- per-op test support (include/s2vt_hip.h: the backward's
 # gather / scatter / reorder pieces).  Matrices here are float32 ROWS: unit column stride, the row stride is the tensor's own
 # (a column block of a wider tensor is passed as the view it is).

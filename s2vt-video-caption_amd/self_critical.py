@@ -119,6 +119,65 @@ def group_advantages(rewards, greedy=None):
     return r - baseline, baseline
 
 
+def inclusion_log_q(logprob, kappa):
+    """log of the probability that a caption with log-prob phi is among the K of a stochastic beam search whose threshold is kappa
+    (S2VT.sample_distinct): it is kept when its Gumbel(phi) score exceeds kappa, q = 1 - exp(-exp(phi - kappa)).  logprob [..., K],
+    kappa [...]; float64 [..., K].  Steps 1-2 of include/s2vt_hip.h "without-replacement weights":
+        a = phi - kappa, e = exp(a), log q = log(-expm1(-e)), or a - 0.5 * e where a < -30 (finite where e underflows);
+    kappa = -inf (nothing was left out) gives log q = 0."""
+    phi = np.asarray(logprob, dtype=np.float64)
+    kap = np.asarray(kappa, dtype=np.float64)
+    if phi.ndim != kap.ndim + 1 or phi.shape[:-1] != kap.shape:
+        raise ValueError("inclusion_log_q: logprob [..., K] with kappa [...], got %s and %s" % (phi.shape, kap.shape))
+    with np.errstate(all="ignore"):
+        a = phi - kap[..., None]
+        e = np.exp(a)
+        return np.where(a < -30.0, a - 0.5 * e, np.log(-np.expm1(-e)))
+
+
+def swor_advantages(logprob, kappa, rewards, greedy=None):
+    """(advantage float64 [B, K], coef float64 [B, K], baseline float64 [B]) for the K pairwise distinct captions per clip of
+    S2VT.sample_distinct with log-probs logprob [B, K], threshold kappa [B] and rewards [B, K], 2 <= K <= 8: the normalised
+    importance-weighted estimator with a built-in baseline (Kool, van Hoof, Welling 2019, "Buy 4 REINFORCE Samples, Get a Baseline
+    for Free!") - s2vt_sc_weights_swor's arithmetic step for step (include/s2vt_hip.h "without-replacement weights"), in float64,
+    every sum in ascending k from 0.0:
+        lw = phi - log q, m = max lw, om = exp(lw - m), pi = exp(phi - m); W = sum om, N = sum om * r;
+        baseline = greedy[b] where given, else N / W; W_i = (W - om_i) + pi_i, coef = om_i / W_i, advantage = coef * (r - baseline).
+    greedy None and K equal rewards: advantages exactly zero, baseline that reward.  A bad clip (a log-prob that is not finite or
+    positive, kappa NaN or +inf, a reward - greedy's included - that is not finite, an fp32 advantage that is not finite):
+    advantage 0, coef 0, baseline NaN."""
+    phi = np.asarray(logprob, dtype=np.float64)
+    kap = np.asarray(kappa, dtype=np.float64)
+    r = np.asarray(rewards, dtype=np.float64)
+    if r.ndim != 2 or not 2 <= r.shape[1] <= 8 or phi.shape != r.shape or kap.shape != r.shape[:1]:
+        raise ValueError("swor_advantages: logprob and rewards [B, K] with 2 <= K <= 8 and kappa [B], got %s, %s, %s" % (
+            phi.shape, r.shape, kap.shape))
+    B, K = r.shape
+    bad = ~np.isfinite(phi).all(1) | (phi > 0).any(1) | np.isnan(kap) | (kap == np.inf) | ~np.isfinite(r).all(1)
+    g = None
+    if greedy is not None:
+        g = np.asarray(greedy, dtype=np.float64)
+        if g.shape != (B,):
+            raise ValueError("swor_advantages: greedy must be [B] = [%d], got %s" % (B, g.shape))
+        bad = bad | ~np.isfinite(g)
+    with np.errstate(all="ignore"):
+        lw = phi - inclusion_log_q(phi, kap)
+        m = lw.max(1, keepdims=True)
+        om, pi = np.exp(lw - m), np.exp(phi - m)
+        W, N = np.zeros(B, dtype=np.float64), np.zeros(B, dtype=np.float64)
+        for j in range(K):
+            W = W + om[:, j]
+            N = N + om[:, j] * r[:, j]
+        same = (r == r[:, :1]).all(1) if g is None else np.zeros(B, dtype=bool)
+        base = g.copy() if g is not None else np.where(same, r[:, 0], N / W)
+        coef = om / ((W[:, None] - om) + pi)
+        adv = coef * (r - base[:, None])
+        adv[same] = 0.0
+        bad = bad | ~np.isfinite(adv.astype(np.float32)).all(1)
+    adv[bad], coef[bad], base[bad] = 0.0, 0.0, np.nan
+    return adv, coef, base
+
+
 # ------------------------------------------------------------------ the same score on the device (train.py --sc-reward device)
 KEY_TOKENS, KEY_BITS = 4, 16         # an n-gram key: up to four tokens of 16 bits in a uint64, first token on top, absent positions 0
 

@@ -79,6 +79,13 @@ def parse(argv=None):
                     help="what a sampled caption's reward is compared with.  greedy: the reward of the clip's greedy caption (SCST, "
                          "Rennie et al. 2017).  mean: the mean reward of the clip's other K - 1 samples (Luo 2020) - no greedy "
                          "decode runs; needs --sc-samples >= 2")
+    ap.add_argument("--sc-distinct", action="store_true",
+                    help="the K captions of a --self-critical step with --sc-samples K (2..8) are sampled WITHOUT replacement "
+                         "(S2VT.sample_distinct: K pairwise distinct captions per clip) and weighted with the normalised "
+                         "importance-weighted estimator of Kool et al. 2019 (s2vt_sc_weights_swor, self_critical.swor_advantages): a "
+                         "peaked model no longer spends the step on K copies of one sentence.  --sc-baseline greedy compares with the "
+                         "greedy reward, mean with the estimator's own estimate of the expected reward.  One-layer LSTM S2VT, "
+                         "temperature 1, no truncation")
     ap.add_argument("--sc-shared-encode", action="store_true",
                     help="the train step of a --self-critical step with --sc-samples K encodes every clip once (S2VT.forward with "
                          "3-D targets: dp.train_step(group=K)) instead of running on the clips repeated K times.  Same loss and "
@@ -131,6 +138,18 @@ def parse(argv=None):
         ap.error("--sc-top-k must be >= 0 and --sc-top-p in (0, 1]")
     if opt.sc_baseline == "mean" and opt.sc_samples < 2:
         ap.error("--sc-baseline mean needs --sc-samples >= 2 (the mean of the other K - 1 samples)")
+    if opt.sc_distinct:
+        if not opt.self_critical:
+            ap.error("--sc-distinct needs --self-critical")
+        if not 2 <= opt.sc_samples <= 8:
+            ap.error("--sc-distinct needs --sc-samples K with 2 <= K <= 8 (S2VT.sample_distinct's widths; one caption has nothing to "
+                     "be distinct from)")
+        if opt.sc_top_k != 0 or opt.sc_top_p != 1.0 or opt.sc_temperature != 1.0:
+            ap.error("--sc-distinct samples the distribution that is trained: not with --sc-top-k, --sc-top-p or an --sc-temperature "
+                     "other than 1 (the inclusion probabilities would be those of another distribution)")
+        if opt.model != "s2vt" or opt.rnn_type != "lstm" or opt.num_layers != 1:
+            ap.error("--sc-distinct needs the one-layer LSTM S2VT (S2VT.sample_distinct refuses GRU and stacked models; Att_Baseline "
+                     "has none)")
     if opt.sc_shared_encode and not opt.self_critical:
         ap.error("--sc-shared-encode needs --self-critical")
     if opt.captions_per_clip < 1:
@@ -165,7 +184,7 @@ def ss_prob_for_epoch(epoch, start, every, inc, max_prob):
 
 
 def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, temperature=1.0, sc_reward="host",
-                            reducer=None, shared_encode=False, max_grad_norm=None, top_k=0, top_p=1.0, samples=1,
+                            reducer=None, shared_encode=False, max_grad_norm=None, top_k=0, top_p=1.0, distinct=False, samples=1,
                             baseline="greedy"):
     """step(feats, video_ids) -> loss of one --self-critical step: sample, decode greedily, score both against the clips' references,
     train on the sampled ids weighted with reward(sampled) - reward(greedy).  hist["sc_split_ms"] accumulates the wall-clock split
@@ -179,14 +198,23 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
     (dp.train_step(group=K): one encode per clip, same loss and gradients).  hist["reward_baseline"] gets the batch mean of the
     baselines.  top_k / top_p: the truncation of the sampled captions (S2VT.sample_truncated; 0 / 1.0: off) - the loss still
     weights the full-softmax log-prob of the drawn words.  max_grad_norm: dp.train_step's (clipping for torch's optimisers; an
-    optim.FlatAdam carries its own)."""
+    optim.FlatAdam carries its own).
+    distinct (2 <= samples <= 8, temperature 1, no truncation): the K captions are sampled WITHOUT replacement, pairwise distinct
+    (model.sample_distinct), and weighted with the normalised importance-weighted estimator of Kool et al. 2019 from their
+    log-probs and the search's threshold kappa (ops.sc_weights_swor on the device, self_critical.swor_advantages on the host):
+    baseline "greedy" compares with the greedy reward, "mean" with the estimator's own estimate N / W of the expected reward.
+    Everything else - rewards, the train step, the history - is the K-sample step's."""
     from s2vt_video_caption_amd import dp, ops
-    from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages
+    from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages, swor_advantages
     K = int(samples)
     if baseline not in ("greedy", "mean") or K < 1 or (baseline == "mean" and K < 2):
         raise ValueError("samples must be >= 1 and baseline 'greedy' or 'mean' (which needs samples >= 2), got %r, %r" % (samples, baseline))
 
     truncated = top_k != 0 or top_p != 1.0
+    if distinct and (not 2 <= K <= 8 or truncated or temperature != 1.0):
+        raise ValueError("distinct needs 2 <= samples <= 8, temperature 1 and no truncation (the inclusion probabilities are those of "
+                         "the distribution that is trained), got samples %r, temperature %r, top_k %r, top_p %r" % (
+                             samples, temperature, top_k, top_p))
 
     def draw_one(feats):
         """one sampled caption per clip: mode='sample'; where top_k / top_p are set, S2VT.sample_truncated's single sample
@@ -201,7 +229,13 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         sp = hist["sc_split_ms"]
         on_device = sc_reward == "device"
         t0 = time.perf_counter()
-        if truncated:
+        logprob = kappa = None
+        if distinct:
+            sampled, _, logprob, _, kappa = model.sample_distinct(feats, K, temperature=1.0, seed=None, max_depth=model.length - 1)
+            sampled, logprob = sampled.view(feats.shape[0] * K, -1), logprob.reshape(-1)
+            if not on_device:
+                logprob, kappa = logprob.cpu().numpy(), kappa.cpu().numpy()
+        elif truncated:
             sampled = model.sample_truncated(feats, K, temperature=temperature, top_k=top_k, top_p=top_p).view(feats.shape[0] * K, -1)
         else:
             sampled = model.sample(feats, K, temperature=temperature).view(feats.shape[0] * K, -1)
@@ -223,10 +257,16 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         r_s = rewarder.rewards(row_ids, sampled)
         r_g = rewarder.rewards(ids, greedy) if greedy is not None else None
         if on_device:
-            caps, weight, base = ops.sc_weights_group(sampled, r_s, r_g, K, sos, eos, return_baseline=True)
+            if distinct:
+                caps, weight, _, base = ops.sc_weights_swor(sampled, logprob, kappa, r_s, r_g, K, sos, eos, return_extras=True)
+            else:
+                caps, weight, base = ops.sc_weights_group(sampled, r_s, r_g, K, sos, eos, return_baseline=True)
             means = torch.stack([r_s.mean(), base.mean()] + ([r_g.mean()] if r_g is not None else [])).tolist()   # the phase's synchronisation
         else:
-            adv, base = group_advantages(r_s.reshape(-1, K), r_g)
+            if distinct:
+                adv, _, base = swor_advantages(logprob.reshape(-1, K), kappa, r_s.reshape(-1, K), r_g)
+            else:
+                adv, base = group_advantages(r_s.reshape(-1, K), r_g)
             weight = advantage_weights(sampled, adv.reshape(-1), eos).to(dev)
             caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
             means = [float(r_s.mean()), float(base.mean())] + ([float(r_g.mean())] if r_g is not None else [])
@@ -414,7 +454,8 @@ def run(opt):
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
                                                      opt.sc_reward, reducer, samples=opt.sc_samples, baseline=opt.sc_baseline,
-                                                     shared_encode=opt.sc_shared_encode, top_k=opt.sc_top_k, top_p=opt.sc_top_p, max_grad_norm=clip)
+                                                     shared_encode=opt.sc_shared_encode, top_k=opt.sc_top_k, top_p=opt.sc_top_p, max_grad_norm=clip,
+                                                     distinct=opt.sc_distinct)
 
     def save(name):
         if rank == 0:
