@@ -27,6 +27,7 @@ predictions stay.  Without the flag every file is what it was.
 """
 import argparse
 import json
+import math
 
 import torch
 
@@ -167,7 +168,8 @@ def sample_captions(model_path, caption_file, feats_path, n_samples, batch_size=
 
 def consensus_captions(model_path, caption_file, feats_path, source, batch_size=10, split='test', device=None, constraints=None,
                        n_samples=0, temperature=1.0, top_k=0, top_p=1.0, seed=0, beam_width=5, max_beam_depth=30, length_alpha=0.7,
-                       n_best=1, beam_groups=0, diversity_lambda=0.5, ensemble_paths=None, ensemble_weights=None, distinct=False):
+                       n_best=1, beam_groups=0, diversity_lambda=0.5, ensemble_paths=None, ensemble_weights=None, distinct=False,
+                       weights=None):
     """--consensus: per clip of a split the candidate caption that agrees most with the clip's other candidates under CIDEr-D
     (consensus.select: one kernel call per batch, the ids never leave the device before the choice is made), with the document
     frequencies of the caption file's TRAINING split - a DeviceCiderRewarder built the way train.py builds --sc-reward device's.
@@ -175,11 +177,11 @@ def consensus_captions(model_path, caption_file, feats_path, source, batch_size=
     S2VT.sample_truncated (batch i with seed + i; distinct: the pairwise distinct captions of S2VT.sample_distinct), 'nbest' the n_best list of the cumulative beam search (plain, constrained or the
     ensemble's), 'groups' the group-best captions of S2VT.beam_diverse.  A candidate whose score is not finite is not a candidate.
     -> (preds {video_id: chosen caption}, detail {video_id: {"chosen": k, "utility": [...], "captions": [...]}} - the utility of a
-    candidate that is not valid: null -, scores {video_id: [the candidates' search scores]}, None for 'sample')."""
-    import math
+    candidate that is not valid: null -, scores {video_id: [the candidates' search scores]}, None for 'sample').
+    weights (cider, bleu), or None for (1, 0): the utility is cider * CIDEr-D + bleu * sentence BLEU-4 (a DeviceMixedRewarder)."""
     import dataloader
     from s2vt_video_caption_amd import consensus
-    from s2vt_video_caption_amd.self_critical import DeviceCiderRewarder
+    from s2vt_video_caption_amd.self_critical import DeviceCiderRewarder, DeviceMixedRewarder
     if source not in ('sample', 'nbest', 'groups'):
         raise ValueError("consensus_captions: source must be 'sample', 'nbest' or 'groups', got %r" % (source,))
     dev = device or torch.device('cuda', 0)
@@ -187,8 +189,12 @@ def consensus_captions(model_path, caption_file, feats_path, source, batch_size=
     loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=False)
     trainset = dataloader.VideoDataset(caption_file, feats_path, mode='train')
     sos, eos = dataset.word2ix.get('<sos>', 3), dataset.word2ix.get('<eos>', 4)
-    rewarder = DeviceCiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, device=dev,
-                                   vocab_size=len(dataset.word2ix))
+    if weights is None:
+        rewarder = DeviceCiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, device=dev,
+                                       vocab_size=len(dataset.word2ix))
+    else:
+        rewarder = DeviceMixedRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, weights[0], weights[1],
+                                       device=dev, vocab_size=len(dataset.word2ix))
     model = torch.load(model_path, weights_only=False).to(dev)
     model.eval()
     if source != 'sample':
@@ -354,6 +360,12 @@ def build_parser():
                          "CIDEr-D (consensus / minimum-Bayes-risk selection on the device, consensus.select; idf of the training split) "
                          "and write {video_id: {chosen, utility, captions}} to <out>.consensus.json.  With a beam search the choice is "
                          "the prediction; with --sample the greedy predictions stay as they are")
+    ap.add_argument("--consensus-cider-weight", type=float, default=1.0, metavar="w",
+                    help="--consensus: the utility is w * CIDEr-D + (--consensus-bleu-weight) * sentence BLEU-4, each against the clip's "
+                         "other candidates (1 and 0, the defaults: CIDEr-D alone, every file as without the two flags)")
+    ap.add_argument("--consensus-bleu-weight", type=float, default=0.0, metavar="w",
+                    help="--consensus: weight of the sentence BLEU-4 in the utility (s2vt_mixed_consensus on the device; "
+                         "<out>.consensus.json then records the two weights under \"_weights\")")
     ap.add_argument("--out", default="predictions.json")
     ap.add_argument("--gts", default=None, help="gts.json: also print BLEU / ROUGE-L / CIDEr of the predictions")
     return ap
@@ -401,6 +413,13 @@ def main(argv=None):
             ap.error("--sample-distinct samples from the whole distribution: not with --top-k, --top-p, --no-repeat-ngram, "
                      "--repetition-penalty, --min-length or --ban-words")
     cons_source = None
+    if not (math.isfinite(a.consensus_cider_weight) and math.isfinite(a.consensus_bleu_weight)):
+        ap.error("--consensus-cider-weight / --consensus-bleu-weight must be finite")
+    cons_weights = None
+    if a.consensus_cider_weight != 1.0 or a.consensus_bleu_weight != 0.0:
+        if not a.consensus:
+            ap.error("--consensus-cider-weight / --consensus-bleu-weight need --consensus")
+        cons_weights = (a.consensus_cider_weight, a.consensus_bleu_weight)
     if a.consensus:
         sources = [s for s, on in (("sample", a.sample >= 2), ("groups", a.beam_groups >= 2),
                                    ("nbest", bool(a.beam) and a.beam_mode == "cumulative" and not a.beam_groups and a.n_best >= 2)) if on]
@@ -423,12 +442,11 @@ def main(argv=None):
     cons = None
     if cons_source in ("nbest", "groups"):
         # the search's candidates, the consensus choice as the prediction; the n-best / groups files as without the flag
-        import math
         preds, cons, cand_scores = consensus_captions(
             a.model_path, a.caption_file, a.feats_path, cons_source, a.batch_size, constraints=constraints, beam_width=a.beam,
             length_alpha=a.length_alpha, n_best=a.n_best, beam_groups=a.beam_groups,
             diversity_lambda=0.5 if a.diversity_lambda is None else a.diversity_lambda, ensemble_paths=ens_paths or None,
-            ensemble_weights=ens_weights)
+            ensemble_weights=ens_weights, weights=cons_weights)
         if nbest is not None:
             nbest.update({v: d["captions"] for v, d in cons.items()})
         if groups is not None:
@@ -452,7 +470,7 @@ def main(argv=None):
         if cons_source == "sample":            # the same draws, kept on the device for the choice; the predictions above stay greedy
             _, cons, _ = consensus_captions(a.model_path, a.caption_file, a.feats_path, "sample", a.batch_size, constraints=constraints,
                                             n_samples=a.sample, temperature=a.temperature, top_k=a.top_k, top_p=a.top_p, seed=a.sample_seed,
-                                            distinct=a.sample_distinct)
+                                            distinct=a.sample_distinct, weights=cons_weights)
             samples = {v: d["captions"] for v, d in cons.items()}
         else:
             samples = sample_captions(a.model_path, a.caption_file, a.feats_path, a.sample, a.batch_size, a.temperature, a.top_k, a.top_p,
@@ -462,7 +480,8 @@ def main(argv=None):
         print("wrote {} sampled captions per clip to {}".format(a.sample, a.out + ".samples.json"))
     if cons is not None:
         with open(a.out + ".consensus.json", 'w', encoding='utf-8') as f:
-            json.dump(cons, f, ensure_ascii=False, indent=1)
+            json.dump(cons if cons_weights is None else dict(cons, _weights={"cider": cons_weights[0], "bleu": cons_weights[1]}), f,
+                      ensure_ascii=False, indent=1)
         print("wrote the consensus choice among {} candidates per clip to {}".format(
             len(next(iter(cons.values()))["captions"]) if cons else 0, a.out + ".consensus.json"))
     if a.gts:

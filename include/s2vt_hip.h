@@ -429,6 +429,50 @@ size_t s2vt_cider_consensus_workspace_bytes(int32_t B, int32_t K, int32_t T);
 int s2vt_cider_consensus(const s2vt_cider_table* table, const int64_t* ids, int32_t B, int32_t K, int32_t T, int64_t ld,
                          int32_t sos, int32_t eos, const uint8_t* valid, double* utility, int32_t* best,
                          void* workspace, size_t workspace_bytes, void* stream);
+/* Sentence BLEU-4 beside CIDEr (train.py --sc-bleu-weight, eval.py --consensus-bleu-weight): the per-sentence BLEU_4 of
+ * caption_metrics.bleu over token ids, with sqrt(sqrt(prod)) for prod ** 0.25 (sqrt is correctly rounded on host and device, pow is
+ * not).  In fp64, with c = the number of words of the stripped row (strip_caption) and the clip's references:
+ *   tf(g) = count of n-gram g in the row, rmax(g) = max over the references of g's count there,
+ *   match_k = sum over the distinct g of order k of min(tf(g), rmax(g)), k = 1..4 (integers, exact in any order),
+ *   guess_k = max(0, c - (k-1)),   rl = the reference length in WORDS closest to c, ties to the shorter,
+ *   f_k = (match_k + 1e-15) / (guess_k + 1e-9),   prod = (((1.0 * f_1) * f_2) * f_3) * f_4,
+ *   bleu4 = sqrt(sqrt(prod)) * bp[c][rl],   bp[c][rl] = exp(1 - 1/ratio) if ratio < 1 else 1.0, ratio = (c + 1e-15) / (rl + 1e-9).
+ * bp needs exp and comes from the host (math.exp), row-major [S2VT_CIDER_MAX_T + 1][n_rl] with n_rl > max(S2VT_CIDER_MAX_T, longest
+ * reference); an empty row scores exactly 0.0 (bp[0][*] = 0).  The mixed reward is w_cider * cider + w_bleu * bleu4: two products and
+ * one add, not contracted.  The table, built once by self_critical.DeviceMixedRewarder beside the CIDEr table of the same clips:
+ *   clip_key_off [n_clips + 1]   CSR: the (key, max count) entries of clip c - the union of its references' 1..4-grams, the keys of
+ *                                s2vt_cider_table (a key names its own order), strictly ascending inside a clip; max_count >= 1
+ *   clip_ref_off [n_clips + 1]   CSR: ref_words [n_refs], the references' lengths in words (s2vt_cider_table.ref_len counts bigrams) */
+typedef struct s2vt_bleu_table {
+    const int32_t* clip_key_off; const uint64_t* keys; const int32_t* max_count;
+    const int32_t* clip_ref_off; const int32_t* ref_words;
+    const double* bp;
+    int64_t n_keys;
+    int32_t n_clips, n_refs, n_rl;
+} s2vt_bleu_table;
+/* s2vt_cider_rewards with the BLEU-4 of the same rows: out[b] = w_cider * cider + w_bleu * bleu4, and where they are not NULL
+ * out_cider[b] / out_bleu[b] the two parts.  One workgroup per row and ONE candidate phase for both scores (the row is stripped and
+ * sorted once); the reference phase is s2vt_cider_rewards' own code, so out_cider has its bits.  BLEU works on the sorted keys in
+ * LDS: an entry that differs from its predecessor heads a run, the run's length is tf, a binary search in the clip's key range gives
+ * rmax; integer sums through wave shuffles, the closest length as a keyed minimum, the fp64 chain on one thread.  No floating-point
+ * atomics; a row's value does not depend on the rest of the batch.  Errors as s2vt_cider_rewards: T > S2VT_CIDER_MAX_T, null
+ * pointers, an incomplete table, tables of different n_clips or a weight that is not finite: S2VT_ERR_ARG before any launch; a token
+ * outside [0, 65535] or a clip row out of range (all three outputs 0.0) is never used as an index and reported as S2VT_ERR_INDEX by
+ * s2vt_check_async_error / a later call. */
+int s2vt_mixed_rewards(const s2vt_cider_table* table, const s2vt_bleu_table* bleu, const int32_t* clip_rows, const int64_t* ids,
+                       int32_t B, int32_t T, int64_t ld, int32_t sos, int32_t eos, double w_cider, double w_bleu, double* out,
+                       double* out_cider, double* out_bleu, void* stream);
+/* s2vt_cider_consensus with the mixed utility: for i in Vb with at least one other valid candidate
+ *   utility[b*K + i] = w_cider * (s2vt_cider_consensus' utility, the same bits) + w_bleu * bleu4(words_i; references = words_j for j
+ *                      ascending, j in Vb, j != i),
+ * 0.0 when i is alone, -inf for i not in Vb; best as there.  The candidate launch is s2vt_cider_consensus'; the pair launch finds,
+ * for every run head of candidate i, the largest run length at the key's lower bound in the slots of the other valid j, and rl among
+ * the others' word counts.  Of the BLEU table only bp and n_rl are read.  Same dims, workspace size, errors and launches as
+ * s2vt_cider_consensus; a weight that is not finite: S2VT_ERR_ARG. */
+size_t s2vt_mixed_consensus_workspace_bytes(int32_t B, int32_t K, int32_t T);
+int s2vt_mixed_consensus(const s2vt_cider_table* table, const s2vt_bleu_table* bleu, const int64_t* ids, int32_t B, int32_t K, int32_t T,
+                         int64_t ld, int32_t sos, int32_t eos, const uint8_t* valid, double w_cider, double w_bleu, double* utility,
+                         int32_t* best, void* workspace, size_t workspace_bytes, void* stream);
 /* What the self-critical step feeds the train step (self_critical.advantage_weights and the <sos> column, on the device):
  * caps int64 [B, T+1] = sos || sampled (int64 [B, T], contiguous); weight fp32 [B, T+1] = fp32(r_sample[b] - r_greedy[b]) - the
  * fp64 difference rounded once - on positions 1 .. the first eos of the row inclusive (all T without one), zero elsewhere. */

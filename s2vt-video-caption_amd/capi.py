@@ -51,6 +51,12 @@ class CiderTable(ctypes.Structure):
                                                    ("n_pen", c_int32)]
 
 
+class BleuTable(ctypes.Structure):
+    """s2vt_bleu_table of include/s2vt_hip.h: the reference side of sentence BLEU-4 as flat device arrays"""
+    _fields_ = [(n, c_void_p) for n in ("clip_key_off", "keys", "max_count", "clip_ref_off", "ref_words", "bp")] + [
+        ("n_keys", c_int64), ("n_clips", c_int32), ("n_refs", c_int32), ("n_rl", c_int32)]
+
+
 class Constraints(ctypes.Structure):
     """s2vt_constraints of include/s2vt_hip.h: what a constrained draw must not generate (`banned` is a HOST pointer)"""
     _fields_ = [("no_repeat_ngram", c_int32), ("repetition_penalty", c_float), ("min_length", c_int32), ("eos_ix", c_int32),
@@ -281,6 +287,12 @@ SIGNATURES = {
     "s2vt_cider_consensus_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
     "s2vt_cider_consensus": (c_int32, [POINTER(CiderTable), c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32, c_int32, c_void_p,
                                        c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # CIDEr and sentence BLEU-4 of the same rows / candidates, mixed (self_critical.DeviceMixedRewarder; csrc/cider.hip)
+    "s2vt_mixed_rewards": (c_int32, [POINTER(CiderTable), POINTER(BleuTable), c_void_p, c_void_p, c_int32, c_int32, c_int64, c_int32,
+                                     c_int32, c_double, c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "s2vt_mixed_consensus_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "s2vt_mixed_consensus": (c_int32, [POINTER(CiderTable), POINTER(BleuTable), c_void_p, c_int32, c_int32, c_int32, c_int64, c_int32,
+                                       c_int32, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "s2vt_sc_weights": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "s2vt_sc_weights_group": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
                                         c_void_p, c_void_p]),

@@ -2,7 +2,8 @@
 others under CIDEr-D (Devlin et al. 2015's consensus re-ranking).  The candidates are what the model already produces - the K rows of
 S2VT.sample / sample_truncated, the n_best list of mode='beam' / beam_constrained / Ensemble.beam, the groups of beam_diverse - as
 token ids, so every model variant is served; the utility and the choice are self_critical.CiderRewarder.consensus' (the host oracle)
-and, for a DeviceCiderRewarder, s2vt_cider_consensus' on the card."""
+and, for a DeviceCiderRewarder, s2vt_cider_consensus' on the card.  A MixedRewarder / DeviceMixedRewarder chooses under its own utility,
+cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4 (s2vt_mixed_consensus on the card)."""
 import torch
 
 from .self_critical import DeviceCiderRewarder
@@ -29,7 +30,8 @@ def select(rewarder, ids, scores=None):
     """(chosen_ids [B, T], best int64 [B], utility fp64 [B, K]) on the device of `ids`: per clip the candidate with the highest
     consensus utility (the first of equals; candidate 0 where none is valid).  rewarder: a DeviceCiderRewarder - kernel, gather on
     the device, no host read - or a host CiderRewarder, whose path copies the ids to the host and the results back (the two can
-    be compared).  scores: see flatten_candidates."""
+    be compared).  The utility is the rewarder's consensus(): CIDEr-D, or the CIDEr-D / BLEU-4 mix of a (Device)MixedRewarder - a
+    DeviceMixedRewarder is a DeviceCiderRewarder and takes the device path.  scores: see flatten_candidates."""
     flat, valid = flatten_candidates(ids, scores)
     if isinstance(rewarder, DeviceCiderRewarder):
         best, utility = rewarder.consensus(flat, valid)

@@ -1,8 +1,10 @@
 // Self-critical rewards on the device (train.py --sc-reward device): CIDEr of a batch of id rows against a reference table that
 // self_critical.DeviceCiderRewarder builds once (s2vt_cider_table of include/s2vt_hip.h), and the <sos>-prefixed captions and
 // advantage weights the train step takes; and consensus (MBR) selection among the K candidates of a clip (consensus.select,
-// eval.py --consensus), the same score with the clip's other candidates as the references.  fp64 throughout; every factor that needs log / exp comes precomputed from the host, so
-// the kernels only add, multiply, divide, take sqrt and min - in a fixed order, without floating-point atomics.
+// eval.py --consensus), the same score with the clip's other candidates as the references; and sentence BLEU-4 beside both
+// (s2vt_mixed_rewards, s2vt_mixed_consensus: w_cider * CIDEr + w_bleu * BLEU-4 from one candidate phase).  fp64 throughout; every
+// factor that needs log / exp comes precomputed from the host, so the kernels only add, multiply, divide, take sqrt and min - in a
+// fixed order, without floating-point atomics.
 #include "api_internal.h"
 
 // a * b + c stays two roundings, as in the host's arithmetic
@@ -141,21 +143,12 @@ __device__ __forceinline__ CiderRow cider_candidate(const s2vt_cider_table& tb, 
     return CiderRow{total, n2};
 }
 
-// One workgroup = one candidate row.
-__global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider_table tb, const int32_t* clip_rows, const int64_t* ids,
-                                                                      int T, int64_t ld, int sos, int eos, double* out, int* err) {
-    __shared__ CiderRowLds L;
-    __shared__ double s_tot[kCiderThreads / 64][4];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int crow = clip_rows[b];
-    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
-        if (tid == 0) {
-            atomicExch(err, 2);
-            out[b] = 0.0;
-        }
-        return;
-    }
-    const CiderRow cr = cider_candidate(tb, ids + (int64_t)b * ld, T, sos, eos, L, err);
+// The reference phase of one row, by the whole workgroup (every thread calls it; it holds one barrier): the candidate that
+// cider_candidate left in L against the references of clip crow.  Thread 0 returns the score, the others 0.  cider_rewards_kernel and
+// mixed_rewards_kernel share it, so the two give the same bits.
+__device__ __forceinline__ double cider_reference(const s2vt_cider_table& tb, int crow, CiderRow cr, const CiderRowLds& L,
+                                                  double (*s_tot)[4]) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int total = cr.total, n2 = cr.n2;
     const uint64_t* keys = L.keys;
     const double* wts = L.wts;
@@ -203,11 +196,143 @@ __global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider
         s_tot[wave][3] = tot3;
     }
     __syncthreads();
+    if (tid != 0) return 0.0;
+    double t[4];
+    for (int k = 0; k < 4; ++k) t[k] = ((s_tot[0][k] + s_tot[1][k]) + s_tot[2][k]) + s_tot[3][k];
+    const double mean = (((t[0] + t[1]) + t[2]) + t[3]) / 4.0;
+    return mean / (double)(r1 - r0) * 10.0;
+}
+
+// One workgroup = one candidate row.
+__global__ __launch_bounds__(kCiderThreads) void cider_rewards_kernel(s2vt_cider_table tb, const int32_t* clip_rows, const int64_t* ids,
+                                                                      int T, int64_t ld, int sos, int eos, double* out, int* err) {
+    __shared__ CiderRowLds L;
+    __shared__ double s_tot[kCiderThreads / 64][4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int crow = clip_rows[b];
+    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) {
+            atomicExch(err, 2);
+            out[b] = 0.0;
+        }
+        return;
+    }
+    const CiderRow cr = cider_candidate(tb, ids + (int64_t)b * ld, T, sos, eos, L, err);
+    const double score = cider_reference(tb, crow, cr, L, s_tot);
+    if (tid == 0) out[b] = score;
+}
+
+// ---------------------------------------------------------------- sentence BLEU-4 beside CIDEr (train.py --sc-bleu-weight)
+// The arithmetic of include/s2vt_hip.h "sentence BLEU-4": integer clipped matches per order, then one fp64 chain on thread 0.  The
+// brevity penalty needs exp and comes from the host (s2vt_bleu_table.bp).
+struct BleuLds {
+    int match[kCiderThreads / 64][4];
+    unsigned long long near[kCiderThreads / 64];
+};
+// (|l - c|, l) of a reference length as one key: the minimum is the closest length, ties to the shorter
+__device__ __forceinline__ unsigned long long bleu_near_key(int l, int c) {
+    const int d = l < c ? c - l : l - c;
+    return ((unsigned long long)(unsigned)d << 32) | (unsigned)l;
+}
+// number of entries equal to keys[at] from `at` on, in the ascending keys[0, n)
+__device__ __forceinline__ int bleu_run(const uint64_t* keys, int at, int n) {
+    const uint64_t key = keys[at];
+    int tf = 1;
+    while (at + tf < n && keys[at + tf] == key) ++tf;
+    return tf;
+}
+// Every thread brings its part of the four match counts and of the keyed minimum over the reference lengths (every thread calls this;
+// one barrier): sums and minimum over the workgroup - integers, exact in any order - and on thread 0 the chain
+//   prod = (((1.0 * f_1) * f_2) * f_3) * f_4, f_k = (match_k + 1e-15) / (max(0, c - (k-1)) + 1e-9);  sqrt(sqrt(prod)) * bp[c][rl].
+// The others return 0.
+__device__ __forceinline__ double bleu_close(int c, int m0, int m1, int m2, int m3, unsigned long long near, const double* bp, int n_rl,
+                                             BleuLds& S) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        m0 += __shfl_xor(m0, o, 64);
+        m1 += __shfl_xor(m1, o, 64);
+        m2 += __shfl_xor(m2, o, 64);
+        m3 += __shfl_xor(m3, o, 64);
+        const unsigned long long other = __shfl_xor(near, o, 64);
+        near = other < near ? other : near;
+    }
+    if (lane == 0) {
+        S.match[wave][0] = m0;
+        S.match[wave][1] = m1;
+        S.match[wave][2] = m2;
+        S.match[wave][3] = m3;
+        S.near[wave] = near;
+    }
+    __syncthreads();
+    if (tid != 0) return 0.0;
+    unsigned long long best = S.near[0];
+    for (int w = 1; w < kCiderThreads / 64; ++w) best = S.near[w] < best ? S.near[w] : best;
+    const unsigned url = (unsigned)(best & 0xFFFFFFFFull);
+    const int rl = url < (unsigned)n_rl ? (int)url : n_rl - 1;      // (a length the table does not cover: its last column)
+    double prod = 1.0;
+    for (int k = 0; k < 4; ++k) {
+        const int match = ((S.match[0][k] + S.match[1][k]) + S.match[2][k]) + S.match[3][k];
+        const int guess = c - k > 0 ? c - k : 0;
+        prod = prod * (((double)match + 1e-15) / ((double)guess + 1e-9));
+    }
+    return sqrt(sqrt(prod)) * bp[(int64_t)c * n_rl + rl];
+}
+
+// The BLEU phase of one row against the references of clip crow, on the sorted keys cider_candidate left in L (every thread calls it):
+// a run head is an entry that differs from its predecessor - NOT wts != 0, a head whose idf is 0 weighs 0 -, the run's length is tf,
+// a binary search in the clip's key range gives the largest count among the references.
+__device__ __forceinline__ double bleu_reference(const s2vt_bleu_table& bt, int crow, int total, const CiderRowLds& L, BleuLds& S) {
+    const int tid = threadIdx.x;
+    const int c = L.m;
+    const int64_t k0 = bt.clip_key_off[crow], k1 = bt.clip_key_off[crow + 1];
+    int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    for (int i = tid; i < total; i += kCiderThreads) {
+        const uint64_t key = L.keys[i];
+        if (i > 0 && L.keys[i - 1] == key) continue;
+        const int64_t at = cider_find(bt.keys, k0, k1, key);
+        if (at < 0) continue;
+        const int tf = bleu_run(L.keys, i, total), rmax = bt.max_count[at], hit = tf < rmax ? tf : rmax;
+        const int k = cider_key_order(key);
+        if (k == 1) m0 += hit;
+        else if (k == 2) m1 += hit;
+        else if (k == 3) m2 += hit;
+        else m3 += hit;
+    }
+    unsigned long long near = ~0ull;
+    for (int r = bt.clip_ref_off[crow] + tid; r < bt.clip_ref_off[crow + 1]; r += kCiderThreads) {
+        const unsigned long long key = bleu_near_key(bt.ref_words[r], c);
+        near = key < near ? key : near;
+    }
+    return bleu_close(c, m0, m1, m2, m3, near, bt.bp, bt.n_rl, S);
+}
+
+// One workgroup = one candidate row; ONE candidate phase serves both scores.
+__global__ __launch_bounds__(kCiderThreads) void mixed_rewards_kernel(s2vt_cider_table tb, s2vt_bleu_table bt, const int32_t* clip_rows,
+                                                                      const int64_t* ids, int T, int64_t ld, int sos, int eos,
+                                                                      double w_cider, double w_bleu, double* out, double* out_cider,
+                                                                      double* out_bleu, int* err) {
+    __shared__ CiderRowLds L;
+    __shared__ double s_tot[kCiderThreads / 64][4];
+    __shared__ BleuLds S;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int crow = clip_rows[b];
+    if (crow < 0 || crow >= tb.n_clips) {         // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) {
+            atomicExch(err, 2);
+            out[b] = 0.0;
+            if (out_cider) out_cider[b] = 0.0;
+            if (out_bleu) out_bleu[b] = 0.0;
+        }
+        return;
+    }
+    const CiderRow cr = cider_candidate(tb, ids + (int64_t)b * ld, T, sos, eos, L, err);
+    const double cider = cider_reference(tb, crow, cr, L, s_tot);
+    const double bleu = bleu_reference(bt, crow, cr.total, L, S);
     if (tid == 0) {
-        double t[4];
-        for (int k = 0; k < 4; ++k) t[k] = ((s_tot[0][k] + s_tot[1][k]) + s_tot[2][k]) + s_tot[3][k];
-        const double mean = (((t[0] + t[1]) + t[2]) + t[3]) / 4.0;
-        out[b] = mean / (double)(r1 - r0) * 10.0;
+        out[b] = w_cider * cider + w_bleu * bleu;
+        if (out_cider) out_cider[b] = cider;
+        if (out_bleu) out_bleu[b] = bleu;
     }
 }
 
@@ -244,24 +369,28 @@ __global__ __launch_bounds__(kCiderThreads) void consensus_candidate_kernel(s2vt
     }
 }
 
+struct PairLds {
+    uint64_t keys[kCiderMaxN];
+    double wts[kCiderMaxN];
+    double term[S2VT_CONSENSUS_MAX_K][4];
+    double tot[4];
+};
 // Phase 2.  One workgroup = one (clip b, candidate i): CIDEr-D of i with the clip's other valid candidates as its references.
 // Wavefront w takes the others j = w, w + 4, ..; its lanes share i's run heads (entry e to lane e mod 64, ascending) and a butterfly
 // closes each per-order sum, as cider_rewards_kernel does against a reference.  The pair's four terms dot / norms * penalty wait in
 // LDS; one thread per order then adds them in ascending j from 0.0 - the host's order over the others - whatever wavefront made them.
-__global__ __launch_bounds__(kCiderThreads) void consensus_pair_kernel(s2vt_cider_table tb, int K, const uint8_t* valid, ConsensusWs ws,
-                                                                       double* utility) {
-    __shared__ uint64_t keys[kCiderMaxN];
-    __shared__ double wts[kCiderMaxN];
-    __shared__ double s_term[S2VT_CONSENSUS_MAX_K][4];
-    __shared__ double s_tot[4];
+// consensus_pair_cider is that phase for valid candidate row r = r0 + i, by the whole workgroup (every thread calls it; it holds barriers): loads r's slot into
+// P and leaves it there; thread 0 returns the CIDEr utility (0.0 without another valid candidate) and, in *others_out, the number of
+// others; the rest return 0.  consensus_pair_kernel and mixed_pair_kernel share it, so the two give the same bits.
+__device__ __forceinline__ double consensus_pair_cider(const s2vt_cider_table& tb, int K, const uint8_t* valid, const ConsensusWs& ws,
+                                                       int64_t r, PairLds& P, int* others_out) {
+    uint64_t* keys = P.keys;
+    double* wts = P.wts;
+    double (*s_term)[4] = P.term;
+    double* s_tot = P.tot;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t r = blockIdx.x;
     const int64_t r0 = r - r % K;                 // the clip's first row
     const int i = (int)(r - r0);
-    if (valid && !valid[r]) {                     // the whole workgroup leaves together, before the first barrier
-        if (tid == 0) utility[r] = -__builtin_inf();
-        return;
-    }
     const int total = ws.meta[2 * r], n2 = ws.meta[2 * r + 1];
     for (int e = tid; e < total; e += kCiderThreads) {
         keys[e] = ws.keys[r * ws.slot + e];
@@ -321,10 +450,79 @@ __global__ __launch_bounds__(kCiderThreads) void consensus_pair_kernel(s2vt_cide
         s_tot[tid] = t;
     }
     __syncthreads();
-    if (tid == 0) {
-        const double mean = (((s_tot[0] + s_tot[1]) + s_tot[2]) + s_tot[3]) / 4.0;
-        utility[r] = others ? mean / (double)others * 10.0 : 0.0;
+    *others_out = others;
+    if (tid != 0) return 0.0;
+    const double mean = (((s_tot[0] + s_tot[1]) + s_tot[2]) + s_tot[3]) / 4.0;
+    return others ? mean / (double)others * 10.0 : 0.0;
+}
+
+__global__ __launch_bounds__(kCiderThreads) void consensus_pair_kernel(s2vt_cider_table tb, int K, const uint8_t* valid, ConsensusWs ws,
+                                                                       double* utility) {
+    __shared__ PairLds P;
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    if (valid && !valid[r]) {                     // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) utility[r] = -__builtin_inf();
+        return;
     }
+    int others;
+    const double u = consensus_pair_cider(tb, K, valid, ws, r, P, &others);
+    if (tid == 0) utility[r] = u;
+}
+
+// The same with the BLEU utility beside it: for every run head of candidate i the largest run length at the key's lower bound in the
+// slots of the other valid j (equal keys are adjacent there as well), rl from the others' word counts, then w_cider * CIDEr +
+// w_bleu * BLEU-4 in fp64.  A slot's word count follows from its meta: 0 or 1 entries are 0 or 1 words, else bigrams + 1.
+__device__ __forceinline__ int consensus_words(const int32_t* meta, int64_t r) {
+    const int total = meta[2 * r];
+    return total < 2 ? total : meta[2 * r + 1] + 1;
+}
+__global__ __launch_bounds__(kCiderThreads) void mixed_pair_kernel(s2vt_cider_table tb, const double* bp, int n_rl, int K,
+                                                                   const uint8_t* valid, ConsensusWs ws, double w_cider, double w_bleu,
+                                                                   double* utility) {
+    __shared__ PairLds P;
+    __shared__ BleuLds S;
+    const int tid = threadIdx.x;
+    const int64_t r = blockIdx.x;
+    if (valid && !valid[r]) {                     // the whole workgroup leaves together, before the first barrier
+        if (tid == 0) utility[r] = -__builtin_inf();
+        return;
+    }
+    int others;
+    const double cider = consensus_pair_cider(tb, K, valid, ws, r, P, &others);
+    const int64_t r0 = r - r % K;
+    const int i = (int)(r - r0);
+    const int total = ws.meta[2 * r], c = consensus_words(ws.meta, r);
+    int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    for (int e = tid; e < total; e += kCiderThreads) {
+        const uint64_t key = P.keys[e];
+        if (e > 0 && P.keys[e - 1] == key) continue;
+        int rmax = 0;
+        for (int j = 0; j < K; ++j) {
+            const int64_t rj = r0 + j;
+            if (j == i || (valid && !valid[rj])) continue;
+            const uint64_t* jk = ws.keys + rj * ws.slot;
+            const int tj = ws.meta[2 * rj];
+            const int64_t at = cider_find(jk, 0, tj, key);
+            if (at < 0) continue;
+            const int run = bleu_run(jk, (int)at, tj);
+            rmax = run > rmax ? run : rmax;
+        }
+        const int tf = bleu_run(P.keys, e, total), hit = tf < rmax ? tf : rmax;
+        const int k = cider_key_order(key);
+        if (k == 1) m0 += hit;
+        else if (k == 2) m1 += hit;
+        else if (k == 3) m2 += hit;
+        else m3 += hit;
+    }
+    unsigned long long near = ~0ull;
+    for (int j = tid; j < K; j += kCiderThreads) {
+        if (j == i || (valid && !valid[r0 + j])) continue;
+        const unsigned long long key = bleu_near_key(consensus_words(ws.meta, r0 + j), c);
+        near = key < near ? key : near;
+    }
+    const double bleu = bleu_close(c, m0, m1, m2, m3, near, bp, n_rl, S);      // (without others: near stays ~0, the value is not used)
+    if (tid == 0) utility[r] = others ? w_cider * cider + w_bleu * bleu : 0.0;
 }
 
 // Phase 3.  One wavefront = one clip, lane k its candidate k (K <= 64): the smallest valid k whose utility is the maximum, 0 without
@@ -570,6 +768,71 @@ int s2vt_cider_consensus(const s2vt_cider_table* table, const int64_t* ids, int3
     S2VT_LAUNCH_CHECK("consensus_candidate_kernel");
     hipLaunchKernelGGL(consensus_pair_kernel, dim3(R), dim3(kCiderThreads), 0, st, tb, (int)K, valid, ws, utility);
     S2VT_LAUNCH_CHECK("consensus_pair_kernel");
+    hipLaunchKernelGGL(consensus_best_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)K, valid, utility, best);
+    S2VT_LAUNCH_CHECK("consensus_best_kernel");
+    return flags.close(st, 3);
+}
+
+static bool finite_weight(double w) { return w - w == 0.0; }
+
+int s2vt_mixed_rewards(const s2vt_cider_table* table, const s2vt_bleu_table* bleu, const int32_t* clip_rows, const int64_t* ids, int32_t B,
+                       int32_t T, int64_t ld, int32_t sos, int32_t eos, double w_cider, double w_bleu, double* out, double* out_cider,
+                       double* out_bleu, void* stream) {
+    S2VT_REQUIRE(table && bleu && clip_rows && ids && out, "s2vt_mixed_rewards: null argument");
+    S2VT_REQUIRE(B > 0 && T > 0 && ld >= T, "s2vt_mixed_rewards: bad dims (B %d, T %d, ld %lld)", (int)B, (int)T, (long long)ld);
+    S2VT_REQUIRE(T <= S2VT_CIDER_MAX_T, "s2vt_mixed_rewards: T = %d ids per row, the n-gram list in LDS holds rows of up to %d", (int)T,
+                 S2VT_CIDER_MAX_T);
+    S2VT_REQUIRE(finite_weight(w_cider) && finite_weight(w_bleu), "s2vt_mixed_rewards: the weights must be finite");
+    const s2vt_cider_table& tb = *table;
+    S2VT_REQUIRE(tb.clip_ref_off && tb.ent_off && tb.ref_norm && tb.ref_len && tb.pen && tb.n_clips > 0 && tb.n_refs > 0 && tb.n_pen > 0 &&
+                     tb.n_idf >= 0 && (tb.n_idf == 0 || (tb.idf_keys && tb.idf_vals)),
+                 "s2vt_mixed_rewards: incomplete table");
+    const s2vt_bleu_table& bt = *bleu;
+    S2VT_REQUIRE(bt.clip_key_off && bt.clip_ref_off && bt.ref_words && bt.bp && bt.n_clips == tb.n_clips && bt.n_refs > 0 &&
+                     bt.n_rl > S2VT_CIDER_MAX_T && bt.n_keys >= 0 && (bt.n_keys == 0 || (bt.keys && bt.max_count)),
+                 "s2vt_mixed_rewards: incomplete BLEU table (or one of other clips than the CIDEr table's)");
+    hipStream_t st = (hipStream_t)stream;
+    PostedFlags flags;
+    int rc;
+    if ((rc = flags.open(st))) return rc;
+    hipLaunchKernelGGL(mixed_rewards_kernel, dim3((unsigned)B), dim3(kCiderThreads), 0, st, tb, bt, clip_rows, ids, (int)T, ld, (int)sos,
+                       (int)eos, w_cider, w_bleu, out, out_cider, out_bleu, flags.p);
+    S2VT_LAUNCH_CHECK("mixed_rewards_kernel");
+    return flags.close(st, 3);
+}
+
+size_t s2vt_mixed_consensus_workspace_bytes(int32_t B, int32_t K, int32_t T) {
+    return consensus_dims_ok(B, K, T) ? carve_consensus(B, K, T, nullptr, nullptr) : 0;
+}
+
+int s2vt_mixed_consensus(const s2vt_cider_table* table, const s2vt_bleu_table* bleu, const int64_t* ids, int32_t B, int32_t K, int32_t T,
+                         int64_t ld, int32_t sos, int32_t eos, const uint8_t* valid, double w_cider, double w_bleu, double* utility,
+                         int32_t* best, void* workspace, size_t workspace_bytes, void* stream) {
+    S2VT_REQUIRE(table && bleu && ids && utility && best && workspace, "s2vt_mixed_consensus: null argument");
+    S2VT_REQUIRE(consensus_dims_ok(B, K, T) && ld >= T,
+                 "s2vt_mixed_consensus: bad dims (B %d, K %d of 1..%d, T %d of 1..%d: the n-gram list in LDS, ld %lld)", (int)B, (int)K,
+                 S2VT_CONSENSUS_MAX_K, (int)T, S2VT_CIDER_MAX_T, (long long)ld);
+    S2VT_REQUIRE((int64_t)B * K <= 0x7FFFFFFF, "s2vt_mixed_consensus: B * K = %lld rows, one workgroup each", (long long)B * K);
+    S2VT_REQUIRE(workspace_bytes >= s2vt_mixed_consensus_workspace_bytes(B, K, T), "s2vt_mixed_consensus: workspace of %zu bytes, %zu needed",
+                 workspace_bytes, s2vt_mixed_consensus_workspace_bytes(B, K, T));
+    S2VT_REQUIRE(finite_weight(w_cider) && finite_weight(w_bleu), "s2vt_mixed_consensus: the weights must be finite");
+    const s2vt_cider_table& tb = *table;          // as s2vt_cider_consensus: idf_keys, idf_vals, n_idf, log_n, pen and n_pen alone
+    S2VT_REQUIRE(tb.pen && tb.n_pen > 0 && tb.n_idf >= 0 && (tb.n_idf == 0 || (tb.idf_keys && tb.idf_vals)),
+                 "s2vt_mixed_consensus: incomplete table");
+    S2VT_REQUIRE(bleu->bp && bleu->n_rl > S2VT_CIDER_MAX_T, "s2vt_mixed_consensus: incomplete BLEU table (bp)");
+    hipStream_t st = (hipStream_t)stream;
+    ConsensusWs ws;
+    carve_consensus(B, K, T, workspace, &ws);
+    PostedFlags flags;
+    int rc;
+    if ((rc = flags.open(st))) return rc;
+    const unsigned R = (unsigned)((int64_t)B * K);
+    hipLaunchKernelGGL(consensus_candidate_kernel, dim3(R), dim3(kCiderThreads), 0, st, tb, ids, (int)T, ld, (int)sos, (int)eos, valid, ws,
+                       flags.p);
+    S2VT_LAUNCH_CHECK("consensus_candidate_kernel");
+    hipLaunchKernelGGL(mixed_pair_kernel, dim3(R), dim3(kCiderThreads), 0, st, tb, bleu->bp, (int)bleu->n_rl, (int)K, valid, ws, w_cider,
+                       w_bleu, utility);
+    S2VT_LAUNCH_CHECK("mixed_pair_kernel");
     hipLaunchKernelGGL(consensus_best_kernel, dim3((unsigned)B), dim3(64), 0, st, (int)K, valid, utility, best);
     S2VT_LAUNCH_CHECK("consensus_best_kernel");
     return flags.close(st, 3);

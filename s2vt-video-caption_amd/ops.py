@@ -4,6 +4,7 @@ Used by the beam-search driver and by the GPU parity tests; no autograd here.  A
 contiguous float32 HIP tensors unless noted; outputs are allocated by torch.
 """
 import ctypes
+import math
 
 import torch
 
@@ -1046,6 +1047,73 @@ def cider_consensus(table, ids, sos_ix, eos_ix, valid=None):
         best = torch.empty(B, dtype=torch.int32, device=dev)
         capi.check(lib.s2vt_cider_consensus(ctypes.byref(table), _ptr(ids), B, K, T, ids.stride(1), int(sos_ix), int(eos_ix), _ptr(valid),
                                             _ptr(utility), _ptr(best), _ptr(ws), nbytes, _stream(dev)), "s2vt_cider_consensus")
+    return best.long(), utility
+
+
+def _finite_weights(what, w_cider, w_bleu):
+    w_cider, w_bleu = float(w_cider), float(w_bleu)
+    if not (math.isfinite(w_cider) and math.isfinite(w_bleu)):
+        raise ValueError("%s: the weights must be finite, got %r and %r" % (what, w_cider, w_bleu))
+    return w_cider, w_bleu
+
+
+def mixed_rewards(table, bleu_table, clip_rows, ids, sos_ix, eos_ix, w_cider, w_bleu, return_parts=False):
+    """fp64 [B]: w_cider * CIDEr + w_bleu * sentence BLEU-4 of the id rows `ids` against the references of the clips `clip_rows` -
+    s2vt_mixed_rewards, arguments as cider_rewards plus the capi.BleuTable of the same clips (self_critical.DeviceMixedRewarder
+    keeps both alive).  return_parts: (mix, cider, bleu), the CIDEr part with cider_rewards' bits.  Weights that are not finite:
+    ValueError before the library is called."""
+    lib = capi.load()
+    w_cider, w_bleu = _finite_weights("mixed_rewards", w_cider, w_bleu)
+    require_hip(ids, "ids")
+    require_hip(clip_rows, "clip_rows")
+    if ids.dim() != 2 or clip_rows.dtype != torch.int32 or clip_rows.numel() != ids.shape[0]:
+        raise capi.S2VTHipError("mixed_rewards: ids [B, T] and clip_rows int32 [B] expected")
+    if ids.dtype != torch.int64 or ids.stride(1) != 1:
+        ids = ids.long().contiguous()
+    B, T = ids.shape
+    if T > capi.CIDER_MAX_T:
+        raise ValueError("mixed_rewards: rows of %d ids; the kernel's n-gram list in LDS holds rows of up to %d" % (T, capi.CIDER_MAX_T))
+    dev = ids.device
+    with torch.cuda.device(dev):
+        out = torch.empty(B, dtype=torch.float64, device=dev)
+        cider = torch.empty(B, dtype=torch.float64, device=dev) if return_parts else None
+        bleu = torch.empty(B, dtype=torch.float64, device=dev) if return_parts else None
+        capi.check(lib.s2vt_mixed_rewards(ctypes.byref(table), ctypes.byref(bleu_table), _ptr(clip_rows.contiguous()), _ptr(ids), B, T,
+                                          ids.stride(0), int(sos_ix), int(eos_ix), w_cider, w_bleu, _ptr(out), _ptr(cider), _ptr(bleu),
+                                          _stream(dev)), "s2vt_mixed_rewards")
+    return (out, cider, bleu) if return_parts else out
+
+
+def mixed_consensus(table, bleu_table, ids, sos_ix, eos_ix, w_cider, w_bleu, valid=None):
+    """cider_consensus under the utility w_cider * CIDEr-D + w_bleu * sentence BLEU-4 (each against the clip's other valid candidates) -
+    s2vt_mixed_consensus; same arguments, shapes and results, plus the capi.BleuTable (its bp alone is read) and the two weights
+    (not finite: ValueError before the library is called)."""
+    lib = capi.load()
+    w_cider, w_bleu = _finite_weights("mixed_consensus", w_cider, w_bleu)
+    require_hip(ids, "ids")
+    if ids.dim() != 3 or ids.shape[0] < 1:
+        raise capi.S2VTHipError("mixed_consensus: ids [B, K, T] expected, got %s" % (tuple(ids.shape),))
+    B, K, T = ids.shape
+    if not 1 <= K <= capi.CONSENSUS_MAX_K:
+        raise ValueError("mixed_consensus: %d candidates per clip; 1..%d are supported" % (K, capi.CONSENSUS_MAX_K))
+    if not 1 <= T <= capi.CIDER_MAX_T:
+        raise ValueError("mixed_consensus: rows of %d ids; the kernel's n-gram list in LDS holds rows of 1..%d" % (T, capi.CIDER_MAX_T))
+    if ids.dtype != torch.int64 or ids.stride(2) != 1 or ids.stride(1) < T or ids.stride(0) != K * ids.stride(1):
+        ids = ids.long().contiguous()
+    dev = ids.device
+    if valid is not None:
+        require_hip(valid, "valid")
+        if tuple(valid.shape) != (B, K) or valid.dtype not in (torch.bool, torch.uint8):
+            raise capi.S2VTHipError("mixed_consensus: valid must be bool / uint8 [B, K] = [%d, %d]" % (B, K))
+        valid = valid.to(torch.uint8).contiguous()
+    with torch.cuda.device(dev):
+        nbytes = lib.s2vt_mixed_consensus_workspace_bytes(B, K, T)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        utility = torch.empty(B, K, dtype=torch.float64, device=dev)
+        best = torch.empty(B, dtype=torch.int32, device=dev)
+        capi.check(lib.s2vt_mixed_consensus(ctypes.byref(table), ctypes.byref(bleu_table), _ptr(ids), B, K, T, ids.stride(1), int(sos_ix),
+                                            int(eos_ix), _ptr(valid), w_cider, w_bleu, _ptr(utility), _ptr(best), _ptr(ws), nbytes,
+                                            _stream(dev)), "s2vt_mixed_consensus")
     return best.long(), utility
 
 

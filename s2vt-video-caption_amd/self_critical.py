@@ -2,7 +2,11 @@
 clip's references, and the per-token weights utils.RewardCriterion takes.
 
 The score is caption_metrics.cider's own arithmetic (its cider_vector / cider_of_vectors) over token IDS, with the document
-frequencies of the TRAINING split computed once - a batch is too small a corpus to take them from."""
+frequencies of the TRAINING split computed once - a batch is too small a corpus to take them from.  MixedRewarder /
+DeviceMixedRewarder add the sentence BLEU-4 of the same rows: the reward cider_weight * CIDEr + bleu_weight * BLEU-4."""
+import math
+from collections import Counter
+
 import numpy as np
 import torch
 
@@ -57,6 +61,102 @@ class CiderRewarder(object):
                 if valid[b, i]:
                     others = [vecs[j] for j in range(K) if valid[b, j] and j != i]
                     utility[b, i] = float(cider_of_vectors(vecs[i], others, self.n, self.sigma)) if others else 0.0
+            best[b] = _first_best(utility[b], valid[b])
+        return best, utility
+
+
+# ------------------------------------------------------------------ sentence BLEU-4 beside CIDEr (train.py --sc-bleu-weight)
+BLEU_TINY, BLEU_SMALL = 1e-15, 1e-9      # the reference scorer's epsilons on matches and on totals (caption_metrics.bleu)
+
+
+def bleu_bp(c, rl):
+    """brevity penalty of a row of c words against the reference length rl, with the scorer's epsilons"""
+    ratio = (c + BLEU_TINY) / (rl + BLEU_SMALL)
+    return math.exp(1.0 - 1.0 / ratio) if ratio < 1.0 else 1.0
+
+
+def closest_length(c, ref_lens):
+    """the reference length closest to c, ties to the shorter"""
+    return min((abs(l - c), l) for l in ref_lens)[1]
+
+
+def bleu_chain(c, match, bp):
+    """BLEU-4 from the row's length, its four clipped match counts and the brevity penalty: caption_metrics.bleu's per-sentence
+    product with sqrt(sqrt(.)) as the fourth root (correctly rounded on host and device; pow is not)"""
+    prod = 1.0
+    for k in range(4):
+        prod *= (match[k] + BLEU_TINY) / (max(0, c - k) + BLEU_SMALL)
+    return math.sqrt(math.sqrt(prod)) * bp
+
+
+def sentence_bleu4(words, refs):
+    """per-sentence BLEU_4 of a word (id) list against a list of reference word lists: caption_metrics.bleu(gts, res)[1][3] of that one
+    id, the fourth root as in bleu_chain.  An empty `words` scores exactly 0.0."""
+    c = len(words)
+    ref_max = Counter()
+    for r in refs:
+        for g, n in ngrams(r, 4).items():
+            if n > ref_max[g]:
+                ref_max[g] = n
+    match = [0] * 4
+    for g, n in ngrams(words, 4).items():
+        match[len(g) - 1] += min(n, ref_max.get(g, 0))
+    return bleu_chain(c, match, bleu_bp(c, closest_length(c, [len(r) for r in refs])))
+
+
+def _mix_weights(cider_weight, bleu_weight):
+    try:
+        w = (float(cider_weight), float(bleu_weight))
+    except (TypeError, ValueError):
+        raise ValueError("the reward weights must be finite floats, got %r and %r" % (cider_weight, bleu_weight))
+    if not all(math.isfinite(x) for x in w):
+        raise ValueError("the reward weights must be finite floats, got %r and %r" % (cider_weight, bleu_weight))
+    return w
+
+
+class MixedRewarder(CiderRewarder):
+    """CiderRewarder with the reward cider_weight * CIDEr-D + bleu_weight * sentence BLEU-4 (the mix of Luo's self-critical.pytorch:
+    cider_reward_weight / bleu_reward_weight), two products and one add in float64.  The host oracle of DeviceMixedRewarder."""
+
+    def __init__(self, captions, video_ids, sos_ix, eos_ix, cider_weight=1.0, bleu_weight=0.0, n=4, sigma=6.0):
+        self.cider_weight, self.bleu_weight = _mix_weights(cider_weight, bleu_weight)
+        if n != 4:
+            raise ValueError("the BLEU reward is BLEU-4 beside CIDEr over 1..4-grams, got n = %d" % n)
+        CiderRewarder.__init__(self, captions, video_ids, sos_ix, eos_ix, n, sigma)
+        self.ref_words = {v: [strip_caption(c, sos_ix, eos_ix) for c in captions[v]] for v in video_ids}
+        self.last_parts = None      # (cider, bleu) of the latest rewards() call
+
+    def bleu(self, video_id, tokens):
+        """sentence BLEU-4 of one candidate id sequence against the references of video_id"""
+        return sentence_bleu4(strip_caption(tokens, self.sos_ix, self.eos_ix), self.ref_words[video_id])
+
+    def score(self, video_id, tokens):
+        return self.cider_weight * CiderRewarder.score(self, video_id, tokens) + self.bleu_weight * self.bleu(video_id, tokens)
+
+    def parts(self, video_ids, ids):
+        """(cider, bleu) float64 [B] of the rows"""
+        rows = ids.tolist() if isinstance(ids, torch.Tensor) else ids
+        return (np.array([CiderRewarder.score(self, v, r) for v, r in zip(video_ids, rows)], dtype=np.float64),
+                np.array([self.bleu(v, r) for v, r in zip(video_ids, rows)], dtype=np.float64))
+
+    def rewards(self, video_ids, ids):
+        self.last_parts = cider, bleu = self.parts(video_ids, ids)
+        return self.cider_weight * cider + self.bleu_weight * bleu
+
+    def consensus(self, ids, valid=None):
+        """CiderRewarder.consensus under the mixed utility: utility[b, i] = cider_weight * (CiderRewarder.consensus' utility) +
+        bleu_weight * BLEU-4 of candidate i with the clip's other valid candidates, ascending, as its references; 0.0 when i is the
+        only valid candidate, -inf where i is not valid.  best[b] is the first maximum."""
+        _, cider = CiderRewarder.consensus(self, ids, valid)
+        rows, valid = _consensus_args(ids, valid)
+        B, K = valid.shape
+        best, utility = np.zeros(B, dtype=np.int64), np.full((B, K), -np.inf, dtype=np.float64)
+        for b in range(B):
+            words = [strip_caption(rows[b][k], self.sos_ix, self.eos_ix) if valid[b, k] else None for k in range(K)]
+            for i in range(K):
+                if valid[b, i]:
+                    others = [words[j] for j in range(K) if valid[b, j] and j != i]
+                    utility[b, i] = self.cider_weight * cider[b, i] + self.bleu_weight * sentence_bleu4(words[i], others) if others else 0.0
             best[b] = _first_best(utility[b], valid[b])
         return best, utility
 
@@ -361,3 +461,149 @@ class DeviceCiderRewarder(object):
                     dot /= hn[k] * rn
                 total[k] += dot * pen
         return float(np.mean(total) / (r1 - r0) * 10.0)
+
+
+class DeviceMixedRewarder(DeviceCiderRewarder):
+    """MixedRewarder's reward and consensus utility on the device (s2vt_mixed_rewards / s2vt_mixed_consensus): DeviceCiderRewarder with
+    the BLEU table (s2vt_bleu_table of include/s2vt_hip.h) built beside the CIDEr one, as plain arrays in `host`:
+
+      bleu_key_off [n_clips + 1]     CSR: the (bleu_keys ascending, bleu_max int32) entries of clip c - the union of its references'
+                                     1..4-grams under the keys above with the largest count among the references
+      bleu_ref_words [n_refs]        the references' lengths in WORDS, under clip_ref_off (ref_len counts bigrams)
+      bp [CIDER_MAX_T + 1, n_rl]     bleu_bp(c, rl) by math.exp for every row length and every rl up to the longest reference
+
+    A subclass of DeviceCiderRewarder, so consensus.select routes it to the device.  bleu_walk / bleu_consensus_walk restate the
+    kernels' BLEU phase in numpy over the flat arrays."""
+
+    def __init__(self, captions, video_ids, sos_ix, eos_ix, cider_weight=1.0, bleu_weight=0.0, n=4, sigma=6.0, device=None, vocab_size=None):
+        from . import capi
+        self.cider_weight, self.bleu_weight = _mix_weights(cider_weight, bleu_weight)
+        DeviceCiderRewarder.__init__(self, captions, video_ids, sos_ix, eos_ix, n, sigma, None, vocab_size)
+        key_off, keys, counts, ref_words = [0], [], [], []
+        for v in self.video_ids:
+            union = {}
+            for c in captions[v]:
+                words = strip_caption(c, sos_ix, eos_ix)
+                ref_words.append(len(words))
+                for g, tf in ngrams(words, n).items():
+                    k = pack_key(g)
+                    union[k] = max(union.get(k, 0), tf)
+            ent = sorted(union.items())
+            keys += [e[0] for e in ent]
+            counts += [e[1] for e in ent]
+            key_off.append(len(keys))
+        n_rl = max(max(ref_words), capi.CIDER_MAX_T) + 1
+        self.host.update({
+            "bleu_key_off": np.array(key_off, dtype=np.int32), "bleu_keys": np.array(keys, dtype=np.uint64),
+            "bleu_max": np.array(counts, dtype=np.int32), "bleu_ref_words": np.array(ref_words, dtype=np.int32),
+            "bp": np.array([[bleu_bp(c, rl) for rl in range(n_rl)] for c in range(capi.CIDER_MAX_T + 1)], dtype=np.float64)})
+        self.last_parts = None      # (cider, bleu) of the latest rewards() call, HIP tensors
+        if device is not None:
+            self._upload(torch.device(device))
+
+    def _upload(self, device):
+        from . import capi
+        h = self.host
+        DeviceCiderRewarder._upload(self, device)           # (host entries that are no field of the CIDEr table do not reach it)
+        tens = self._dev[1]
+        bt = capi.BleuTable()
+        for field, name in (("clip_key_off", "bleu_key_off"), ("keys", "bleu_keys"), ("max_count", "bleu_max"),
+                            ("clip_ref_off", "clip_ref_off"), ("ref_words", "bleu_ref_words"), ("bp", "bp")):
+            setattr(bt, field, tens[name].data_ptr())
+        bt.n_keys, bt.n_clips, bt.n_refs, bt.n_rl = len(h["bleu_keys"]), len(self.video_ids), len(h["bleu_ref_words"]), h["bp"].shape[1]
+        self._bleu = bt
+
+    def _tables(self, ids):
+        from .functional import require_hip
+        require_hip(ids, "ids")
+        if self._dev is None or self._dev[0] != ids.device:
+            self._upload(ids.device)
+        return self._dev[2], self._bleu
+
+    def _scores(self, video_ids, ids):
+        """(mix, cider, bleu) fp64 HIP tensors [B] of one s2vt_mixed_rewards call"""
+        from . import ops
+        tb, bt = self._tables(ids)
+        clip_rows = torch.tensor([self.row_of[v] for v in video_ids], dtype=torch.int32).to(ids.device, non_blocking=True)
+        return ops.mixed_rewards(tb, bt, clip_rows, ids, self.sos_ix, self.eos_ix, self.cider_weight, self.bleu_weight, return_parts=True)
+
+    def rewards(self, video_ids, ids):
+        """fp64 HIP tensor [B]: cider_weight * CIDEr + bleu_weight * BLEU-4 of each row (DeviceCiderRewarder.rewards' arguments)"""
+        mix, cider, bleu = self._scores(video_ids, ids)
+        self.last_parts = (cider, bleu)
+        return mix
+
+    def parts(self, video_ids, ids):
+        """(cider, bleu) fp64 HIP tensors [B] of the rows, the CIDEr part with DeviceCiderRewarder.rewards' bits"""
+        return self._scores(video_ids, ids)[1:]
+
+    def consensus(self, ids, valid=None):
+        """(best int64 [B], utility fp64 [B, K]) HIP tensors: MixedRewarder.consensus on the device (ops.mixed_consensus)"""
+        from . import ops
+        tb, bt = self._tables(ids)
+        return ops.mixed_consensus(tb, bt, ids, self.sos_ix, self.eos_ix, self.cider_weight, self.bleu_weight, valid)
+
+    def _sorted_keys(self, tokens):
+        """(number of words, the row's 1..4-gram keys ascending with repeats) - what the candidate phase leaves in LDS"""
+        words = strip_caption(tokens, self.sos_ix, self.eos_ix)
+        keys = np.array([pack_key(words[i:i + k]) for k in range(1, self.n + 1) for i in range(len(words) - k + 1)], dtype=np.uint64)
+        return len(words), np.sort(keys)
+
+    @staticmethod
+    def _run(keys, at):
+        """number of entries equal to keys[at] from `at` on"""
+        tf = 1
+        while at + tf < len(keys) and keys[at + tf] == keys[at]:
+            tf += 1
+        return tf
+
+    def bleu_walk(self, video_id, tokens):
+        """the BLEU phase of s2vt_mixed_rewards for one row in numpy, on the host copy of the table: run heads of the sorted keys, the
+        run length as tf, a binary search in the clip's key range for the largest reference count, the closest length as a keyed
+        minimum, bleu_chain with bp from the table"""
+        h = self.host
+        c, keys = self._sorted_keys(tokens)
+        row = self.row_of[video_id]
+        k0, k1 = int(h["bleu_key_off"][row]), int(h["bleu_key_off"][row + 1])
+        ck, cm = h["bleu_keys"][k0:k1], h["bleu_max"][k0:k1]
+        match = [0] * 4
+        for i in range(len(keys)):
+            if i > 0 and keys[i - 1] == keys[i]:
+                continue
+            at = int(np.searchsorted(ck, keys[i]))
+            if at < len(ck) and ck[at] == keys[i]:
+                match[len(unpack_key(keys[i])) - 1] += min(self._run(keys, i), int(cm[at]))
+        r0, r1 = int(h["clip_ref_off"][row]), int(h["clip_ref_off"][row + 1])
+        near = min((abs(int(l) - c) << 32) | int(l) for l in h["bleu_ref_words"][r0:r1])
+        return bleu_chain(c, match, float(h["bp"][c, min(near & 0xFFFFFFFF, h["bp"].shape[1] - 1)]))
+
+    def bleu_consensus_walk(self, rows, valid=None):
+        """the BLEU phase of s2vt_mixed_consensus for ONE clip in numpy: rows = its K id rows, valid = K flags or None -> float64 [K],
+        the BLEU-4 of every valid candidate against the other valid ones (for every run head the largest run length at the key's
+        lower bound in the others' sorted lists; rl among the others' word counts), 0.0 without another, -inf where not valid"""
+        h = self.host
+        K = len(rows)
+        valid = np.ones(K, dtype=bool) if valid is None else np.asarray(valid).astype(bool)
+        cand = [self._sorted_keys(r) if valid[k] else None for k, r in enumerate(rows)]
+        out = np.full(K, -np.inf, dtype=np.float64)
+        for i in range(K):
+            if not valid[i]:
+                continue
+            others = [cand[j] for j in range(K) if j != i and valid[j]]
+            if not others:
+                out[i] = 0.0
+                continue
+            c, keys = cand[i]
+            match = [0] * 4
+            for e in range(len(keys)):
+                if e > 0 and keys[e - 1] == keys[e]:
+                    continue
+                rmax = 0
+                for _, jk in others:
+                    at = int(np.searchsorted(jk, keys[e]))
+                    if at < len(jk) and jk[at] == keys[e]:
+                        rmax = max(rmax, self._run(jk, at))
+                match[len(unpack_key(keys[e])) - 1] += min(self._run(keys, e), rmax)
+            near = min((abs(jc - c) << 32) | jc for jc, _ in others)
+            out[i] = bleu_chain(c, match, float(h["bp"][c, min(near & 0xFFFFFFFF, h["bp"].shape[1] - 1)]))
+        return out

@@ -12,6 +12,7 @@ TensorBoard logging is optional (tensorboardX is not a dependency), and `ReduceL
 `verbose` argument that torch >= 2.6 removed.
 """
 import argparse
+import math
 import os
 import time
 
@@ -72,6 +73,13 @@ def parse(argv=None):
                          "of the ids.  device: self_critical.DeviceCiderRewarder - the reference table is built once and lives on the "
                          "card, the rewards, the <sos>-prefixed captions and the advantage weights come from HIP kernels "
                          "(s2vt_cider_rewards, s2vt_sc_weights) and the ids never leave the device")
+    ap.add_argument("--sc-cider-weight", type=float, default=1.0, metavar="w",
+                    help="--self-critical: the reward is w * CIDEr-D + (--sc-bleu-weight) * sentence BLEU-4 (the cider_reward_weight / "
+                         "bleu_reward_weight mix of Luo's self-critical.pytorch).  1 and 0 (the defaults): CIDEr-D alone, today's rewarder")
+    ap.add_argument("--sc-bleu-weight", type=float, default=0.0, metavar="w",
+                    help="--self-critical: weight of the sentence BLEU-4 (caption_metrics.bleu's per-sentence BLEU_4 over token ids) in the "
+                         "reward.  With --sc-reward device both scores come from one kernel call per batch (s2vt_mixed_rewards: "
+                         "self_critical.DeviceMixedRewarder); on the host (MixedRewarder) the Python scorer costs hundreds of ms per batch")
     ap.add_argument("--sc-samples", type=int, default=1, metavar="K",
                     help="captions sampled per clip in a --self-critical step (S2VT.sample: one encode per clip, K rows of word "
                          "steps); the train step then runs on the B*K captions.  1 (default): today's step")
@@ -128,6 +136,10 @@ def parse(argv=None):
     if opt.skip_nonfinite and not (opt.model == "s2vt" and opt.rnn_type == "lstm" and opt.num_layers == 1):
         ap.error("--skip-nonfinite needs the one-layer LSTM S2VT (optim.FlatAdam's device step); torch's Adam, which trains GRU, "
                  "stacked and att_baseline models, has no such guard")
+    if not (math.isfinite(opt.sc_cider_weight) and math.isfinite(opt.sc_bleu_weight)):
+        ap.error("--sc-cider-weight / --sc-bleu-weight must be finite")
+    if (opt.sc_cider_weight != 1.0 or opt.sc_bleu_weight != 0.0) and not opt.self_critical:
+        ap.error("--sc-cider-weight / --sc-bleu-weight need --self-critical")
     if (opt.sc_samples != 1 or opt.sc_baseline != "greedy") and not opt.self_critical:
         ap.error("--sc-samples / --sc-baseline need --self-critical")
     if opt.sc_samples < 1:
@@ -203,12 +215,28 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
     (model.sample_distinct), and weighted with the normalised importance-weighted estimator of Kool et al. 2019 from their
     log-probs and the search's threshold kappa (ops.sc_weights_swor on the device, self_critical.swor_advantages on the host):
     baseline "greedy" compares with the greedy reward, "mean" with the estimator's own estimate N / W of the expected reward.
-    Everything else - rewards, the train step, the history - is the K-sample step's."""
+    Everything else - rewards, the train step, the history - is the K-sample step's.
+    A rewarder that keeps `last_parts` (MixedRewarder / DeviceMixedRewarder: the CIDEr and BLEU-4 parts of its latest rewards() call)
+    also gets the batch means of the sampled rows' two parts appended to the returned step's `part_means`."""
     from s2vt_video_caption_amd import dp, ops
     from s2vt_video_caption_amd.self_critical import advantage_weights, group_advantages, swor_advantages
     K = int(samples)
     if baseline not in ("greedy", "mean") or K < 1 or (baseline == "mean" and K < 2):
         raise ValueError("samples must be >= 1 and baseline 'greedy' or 'mean' (which needs samples >= 2), got %r, %r" % (samples, baseline))
+
+    mixed = hasattr(rewarder, "last_parts")
+    part_means = []
+
+    def sampled_parts(on_device):
+        """the parts of the rewards() call just made: as two more entries of the device step's one read (a list of tensors), or
+        recorded at once from the host arrays"""
+        if not mixed:
+            return []
+        cider, bleu = rewarder.last_parts
+        if on_device:
+            return [cider.mean(), bleu.mean()]
+        part_means.append((float(cider.mean()), float(bleu.mean())))
+        return []
 
     truncated = top_k != 0 or top_p != 1.0
     if distinct and (not 2 <= K <= 8 or truncated or temperature != 1.0):
@@ -255,13 +283,16 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         t2 = time.perf_counter()
         row_ids = [v for v in ids for _ in range(K)]
         r_s = rewarder.rewards(row_ids, sampled)
+        extra = sampled_parts(on_device)
         r_g = rewarder.rewards(ids, greedy) if greedy is not None else None
         if on_device:
             if distinct:
                 caps, weight, _, base = ops.sc_weights_swor(sampled, logprob, kappa, r_s, r_g, K, sos, eos, return_extras=True)
             else:
                 caps, weight, base = ops.sc_weights_group(sampled, r_s, r_g, K, sos, eos, return_baseline=True)
-            means = torch.stack([r_s.mean(), base.mean()] + ([r_g.mean()] if r_g is not None else [])).tolist()   # the phase's synchronisation
+            means = torch.stack([r_s.mean(), base.mean()] + ([r_g.mean()] if r_g is not None else []) + extra).tolist()   # the phase's synchronisation
+            if extra:
+                part_means.append(tuple(means[-2:]))
         else:
             if distinct:
                 adv, _, base = swor_advantages(logprob.reshape(-1, K), kappa, r_s.reshape(-1, K), r_g)
@@ -288,6 +319,7 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         return loss
 
     if K > 1 or baseline == "mean":           # (K = 1: the steps below run on the clips as they are - nothing to share)
+        group_step.part_means = part_means
         return group_step
 
     def host_step(feats, ids):
@@ -299,7 +331,9 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         with torch.no_grad():
             greedy = model(feats, mode='test').cpu()
         t2 = time.perf_counter()
-        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
+        r_s = rewarder.rewards(ids, sampled)
+        sampled_parts(False)
+        r_g = rewarder.rewards(ids, greedy)
         weight = advantage_weights(sampled, r_s - r_g, eos).to(dev)
         caps = torch.cat([torch.full((sampled.shape[0], 1), sos, dtype=torch.long), sampled], 1).to(dev)
         t3 = time.perf_counter()
@@ -324,9 +358,13 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
             greedy = model(feats, mode='test')
         torch.cuda.synchronize(dev)
         t2 = time.perf_counter()
-        r_s, r_g = rewarder.rewards(ids, sampled), rewarder.rewards(ids, greedy)
+        r_s = rewarder.rewards(ids, sampled)
+        extra = sampled_parts(True)
+        r_g = rewarder.rewards(ids, greedy)
         caps, weight = ops.sc_weights(sampled, r_s, r_g, sos, eos)
-        means = torch.stack([r_s.mean(), r_g.mean()]).tolist()          # the phase's synchronisation
+        means = torch.stack([r_s.mean(), r_g.mean()] + extra).tolist()          # the phase's synchronisation
+        if extra:
+            part_means.append(tuple(means[-2:]))
         t3 = time.perf_counter()
         loss = dp.train_step(model, reward_criterion, optimizer, feats, caps, weight, reducer, check_errors=True, max_grad_norm=max_grad_norm)
         t4 = time.perf_counter()
@@ -338,7 +376,9 @@ def make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, 
         hist.setdefault("reward_baseline", []).append(means[1])
         return loss
 
-    return device_step if sc_reward == "device" else host_step
+    step = device_step if sc_reward == "device" else host_step
+    step.part_means = part_means
+    return step
 
 
 def run(opt):
@@ -439,9 +479,16 @@ def run(opt):
         if world > 1 or opt.model != "s2vt":
             raise NotImplementedError("--self-critical runs S2VT in a single process")
         from utils import RewardCriterion
-        from s2vt_video_caption_amd.self_critical import CiderRewarder, DeviceCiderRewarder
+        from s2vt_video_caption_amd.self_critical import CiderRewarder, DeviceCiderRewarder, DeviceMixedRewarder, MixedRewarder
         sos, eos = word2ix['<sos>'], word2ix['<eos>']
-        if opt.sc_reward == "device":
+        sc_mixed = opt.sc_cider_weight != 1.0 or opt.sc_bleu_weight != 0.0
+        if sc_mixed and opt.sc_reward == "device":
+            rewarder = DeviceMixedRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, opt.sc_cider_weight,
+                                           opt.sc_bleu_weight, device=dev, vocab_size=len(word2ix))
+        elif sc_mixed:
+            rewarder = MixedRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, opt.sc_cider_weight,
+                                     opt.sc_bleu_weight)
+        elif opt.sc_reward == "device":
             rewarder = DeviceCiderRewarder(trainset.captions, [p.stem for p in trainset.feat_paths], sos, eos, device=dev,
                                            vocab_size=len(word2ix))
         else:
@@ -450,6 +497,8 @@ def run(opt):
         # wall-clock split of the self-critical steps (ms, summed over the run; each phase ends with a device synchronisation)
         hist["sc_split_ms"] = {"sample": 0.0, "greedy": 0.0, "scoring": 0.0, "train": 0.0, "steps": 0}
         hist["reward_sample"], hist["reward_greedy"], hist["reward_baseline"] = [], [], []
+        if sc_mixed:            # the epoch means of the sampled rows' two parts
+            hist["reward_cider"], hist["reward_bleu"] = [], []
 
     if rewarder is not None:
         self_critical_step = make_self_critical_step(model, optimizer, reward_criterion, rewarder, hist, sos, eos, dev, opt.sc_temperature,
@@ -512,6 +561,11 @@ def run(opt):
             valid_loss = float(vl[0])
         hist["train_loss"].append(train_loss)
         hist["valid_loss"].append(valid_loss)
+        if rewarder is not None and self_critical_step.part_means:
+            pm = self_critical_step.part_means
+            hist["reward_cider"].append(sum(p[0] for p in pm) / len(pm))
+            hist["reward_bleu"].append(sum(p[1] for p in pm) / len(pm))
+            del pm[:]
         if rank == 0:
             sc_text = ""
             if rewarder is not None and len(hist["reward_baseline"]) > sc_from:      # the epoch's mean sampled reward and baseline
